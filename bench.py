@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: k-mer contexts/sec of the fused
-DM-marginal + gradient hot path at k=13, fp64, with the ELBO checked against the CPU oracle.
+DM-marginal + gradient hot path at k=13, fp64 (--full: with the ELBO checked against the CPU oracle).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--contexts C] [--workload net|ref]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--contexts C] [--workload net|ref] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over the rank's resident shard of a synthetic k=13 count
@@ -15,7 +15,13 @@ cached dataset and its build time is reported, not timed.
 workload "net" (default, the headline of BASELINE.md section 3): bear_net DM-marginal + d/dh over
 count rows + fp64 prior rows, 60 algorithmic bytes per context.  workload "ref": bear_ref with the
 stop (flat) AR prior of BASELINE.json configs[1], train + reference count rows, 40 B per context.
-The other workload is measured too and reported under "also".
+
+A plain run sets up, settles the clocks, warms up, times the K steps and prints the line.  --full
+adds everything else: the other workload and the kernels of the other entry points under "also",
+the measured stream rate, the cold figure without the settle launches, the strong-scaling pass of
+an N > 1 weak run and the CPU oracle's baseline and check of the timed launch's output.
+--dump-outputs DIR writes what the last timed step returned (the packed [sum LL, gradients] vector,
+fp64) as DIR/sum_ll_and_grads.npy; the inputs are seeded, so two builds can be compared on it.
 
 Rank 0 prints ONE JSON line.
 """
@@ -137,6 +143,11 @@ def parse_args():
     ap.add_argument("--ingest-rows", type=float, default=None,
                     help="rows of the text table of the also.ingest entry (text -> first step wall time); default: min(--contexts, 1e8); 0 = skip")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU smoke tests of the N > 1 path)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too (other workload, 'also' entries, stream rate, cold figure, "
+                         "strong pass, CPU baseline); the --no-* options above trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (rank 0) as DIR/sum_ll_and_grads.npy (fp64)")
     return ap.parse_args()
 
 
@@ -268,12 +279,14 @@ def main():
         row0, total = rank * n, int(args.contexts) * world
     h_s, tau_s, nu_s = 0.0, float(np.log(1 / 30)), float(-np.log(100))  # reference initial values
 
-    t = kernels.synth_counts(SEED, row0, n, dev, want=("train", "ref"))
-    prior = kernels.synth_prior(SEED, row0, n, dev)
+    wls = ("net", "ref") if args.full else (args.workload,)      # a plain run sets up its own workload only
+    t = kernels.synth_counts(SEED, row0, n, dev, want=("train", "ref") if "ref" in wls else ("train",))
+    prior = kernels.synth_prior(SEED, row0, n, dev) if "net" in wls else None
     torch.cuda.synchronize()
     t0 = time.time()
     # "ref": the product path of bear_ref.train -- a plan that also knows the (equally constant) reference column
-    plans = {"net": kernels.Plan(t["train"], 5), "ref": kernels.Plan(t["train"], 4, ref=t["ref"])}
+    make_plan = {"net": lambda: kernels.Plan(t["train"], 5), "ref": lambda: kernels.Plan(t["train"], 4, ref=t["ref"])}
+    plans = {wl: make_plan[wl]() for wl in wls}
     torch.cuda.synchronize()
     plan_build_s = time.time() - t0
     plan_nbytes = {k: v.nbytes for k, v in plans.items()}     # (before the linear head's paired lists are attached to the net plan below)
@@ -349,11 +362,11 @@ def main():
         barrier()
         return (time.perf_counter() - t_start) / steps * 1e3
 
-    def measure(wl, steps, warmup, do_settle=False):
+    def measure(wl, steps, warmup, do_settle=False, do_cold=False):
         gc.collect()         # now, not between the warm-up and the timed steps: the card must not idle there
-        cold_ms = cold_run(wl, min(steps, 20), warmup) if do_settle else None
+        cold_ms = cold_run(wl, min(steps, 20), warmup) if do_settle and do_cold else None
         settle_info = settle(wl) if do_settle else None
-        if settle_info is not None:
+        if settle_info is not None and do_cold:
             settle_info["cold_ms_per_step_without_settle"] = cold_ms
             settle_info["cold_note"] = ("ms_per_step of min(steps, 20) timed steps behind --warmup alone, taken BEFORE the settle launches "
                                         "on the card as the set-up left it (what --no-settle reports)")
@@ -388,8 +401,16 @@ def main():
 
     primary = args.workload
     other = "ref" if primary == "net" else "net"
-    elapsed, k_ms, result, k_stats, settle_info, per_rank = measure(primary, args.steps, args.warmup, do_settle=not args.no_settle)
-    o_elapsed, o_k_ms, o_result, _, _, _ = measure(other, max(5, args.steps // 5), 2)
+    elapsed, k_ms, result, k_stats, settle_info, per_rank = measure(primary, args.steps, args.warmup, do_settle=not args.no_settle,
+                                                                    do_cold=args.full)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: out = [sum LL, d/dh] (net) or [sum LL, d/dh, d/dtau, d/dnu] (ref)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "sum_ll_and_grads.npy"), result.astype(np.float64))
+    o_elapsed = o_k_ms = None
+    if args.full:
+        o_elapsed, o_k_ms, o_result, _, _, _ = measure(other, max(5, args.steps // 5), 2)
+
     def timed(fn, reps):
         """Median over five or more event-timed groups of back-to-back calls of `fn` (each group at least `reps` / 5 calls and
         ~1 ms), behind ~20 ms of untimed calls: every entry below follows host-side set-up during which the card clocks down
@@ -415,15 +436,15 @@ def main():
         return float(np.median([a.elapsed_time(b) / per_group for a, b in evs]))
 
     norm_ms = None
-    if rank == 0:  # the same net kernel with the caller asserting normalised prior rows
+    if args.full and rank == 0:  # the same net kernel with the caller asserting normalised prior rows
         norm_ms = timed(lambda: kernels.dm_prior_planned(plans["net"], prior, h_s, normalized=True), 10)
 
     stream_gbps = None
-    if rank == 0:   # measured read-only stream over the same prior rows (4 GB): the practical ceiling under the spec peak
+    if args.full and rank == 0:   # measured read-only stream over the same prior rows (4 GB): the practical ceiling under the spec peak
         stream_gbps = prior.numel() * 8 / (timed(lambda: kernels.stream_read(prior), 10) * 1e-3) / 1e9
 
     extra = {}
-    if rank == 0 and world == 1:  # the rows of SURVEY 8f built on the same kernels: kernel-only times, 1 GPU
+    if args.full and rank == 0 and world == 1:  # the rows of SURVEY 8f built on the same kernels: kernel-only times, 1 GPU
         plan_stream = kernels.Plan(t["train"], 4)     # mode R with the reference rows streamed every step (plan from the training counts only)
         ms = timed(lambda: kernels.dm_ref_planned(plan_stream, t["ref"], h_s, tau_s, nu_s), 10)
         extra["ref_streaming_reference_rows"] = {"kernel_ms": ms, "contexts_per_s": n / (ms * 1e-3), "achieved_GBps": n * 40 / (ms * 1e-3) / 1e9,
@@ -720,7 +741,7 @@ def main():
 
     # (7) N > 1 under weak scaling: the strong split of ONE --contexts table too (north_star: the 1e8 table at 1/2/4/8 GPUs)
     strong = None
-    if multi and args.scaling == "weak" and not args.no_strong_pass:
+    if args.full and multi and args.scaling == "weak" and not args.no_strong_pass:
         strong = strong_pass(args, rank, world, dev, dev_index, primary, (h_s, tau_s, nu_s))
 
     value = total * args.steps / elapsed
@@ -775,7 +796,7 @@ def main():
                 traffic = None
         moved = traffic if traffic is not None else n * (40 if primary == "net" else 0) + plan_nbytes[primary]
         # the other workload: PMC bytes of the committed profile when there are any, else an upper estimate (rows + whole plan)
-        other_moved, other_moved_source = n * (40 if other == "net" else 0) + plan_nbytes[other], "estimate: row bytes + plan bytes"
+        other_moved, other_moved_source = n * (40 if other == "net" else 0) + plan_nbytes.get(other, 0), "estimate: row bytes + plan bytes"
         try:
             ent = json.load(open(tpath)).get(other, {})
             if ent.get("bytes_per_launch") is not None:
@@ -845,7 +866,8 @@ def main():
             "plan_build_s": plan_build_s,
             "plan_bytes_per_context": plan_nbytes[primary] / n,
             "result": result.tolist(),
-            "also": {
+            # the other workload and the other kernels: --full only
+            "also": {} if not args.full else {
                 other: {
                     "contexts_per_s": total / (o_elapsed / max(5, args.steps // 5)),
                     "kernel_ms": o_k_ms,
@@ -869,7 +891,7 @@ def main():
                 **extra,
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], line["elbo_rel_err_vs_cpu"], line["elbo_check"] = cpu_baseline(
                 t, prior, primary, (h_s, tau_s, nu_s), result)
         else:

@@ -1,10 +1,11 @@
-"""Condenses gpurun_out/<tag>_{stats,fetch,write,sq} (rocprofv3 csv) into profiles/<tag>_*.{csv,md,json}."""
+"""Condenses profile_raw/<tag>_{stats,fetch,write,sq} (rocprofv3 csv, scripts/profile_round.sh; BEAR_PROFILE_RAW moves it) into
+profiles/<tag>_*.{csv,md,json}."""
 import collections, csv, glob, json, os, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src, dst = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+src, dst = os.environ.get("BEAR_PROFILE_RAW") or os.path.join(ROOT, "profile_raw"), os.path.join(ROOT, "profiles")
 os.makedirs(dst, exist_ok=True)
-out_md = [f"# rocprofv3 summary, round tag {tag}", "", "Command: `python3 bench.py --steps 100 --warmup 60 --no-cpu-baseline` under",
+out_md = [f"# rocprofv3 summary, round tag {tag}", "", "Command: `python3 bench.py --full --steps 100 --warmup 60 --no-cpu-baseline` under",
           "`rocprofv3 --kernel-trace --stats` (kernel stats) and, in separate passes, `--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`,",
           "`--pmc SQ_*` (scripts/profile_round.sh).", ""]
 ks = glob.glob(os.path.join(src, f"{tag}_stats", "**", "*_kernel_stats.csv"), recursive=True)

@@ -358,7 +358,7 @@ def test_bench_bare_command_starts_its_own_ranks(scaling):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(MANY), "--backend", "gloo", "--contexts", "2e6",
-                        "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--scaling", scaling],
+                        "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--scaling", scaling, "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-6000:]
     lines = p.stdout.splitlines()
@@ -390,7 +390,7 @@ def test_bench_single_rank_line_is_consistent():
     kernel time, with the 'also' entries of the other kernels in it."""
     n = 3_000_000
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3", "--contexts", str(n), "--no-cpu-baseline",
-                        "--no-baseline-configs"],      # (those run at the configs' own sizes: tests/test_config_shards_gpu.py covers the module)
+                        "--no-baseline-configs", "--full"],      # (those run at the configs' own sizes: tests/test_config_shards_gpu.py covers the module)
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-6000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -424,6 +424,35 @@ def test_bench_single_rank_line_is_consistent():
     assert d["ranks"] == {"world_size": 1, "backend": None, "launcher": "none (one process)", "devices": [0],
                           "backend_is_rccl": None, "devices_distinct": True}
     assert d["settle"]["cold_ms_per_step_without_settle"] > 0          # the figure of the same command without the settle launches
+
+
+@pytest.mark.parametrize("workload", ["net", "ref"])
+def test_bench_plain_run_dumps_its_output(workload, tmp_path):
+    """bench.py without --full: the headline line alone (nothing under 'also', no CPU baseline), exactly --steps timed steps,
+    and --dump-outputs writes the last timed step's packed output, which is the kernel's on the same seeded table."""
+    from bear_amd import kernels
+    n = 2_000_000
+    out_dir = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--contexts", str(n),
+                        "--workload", workload, "--dump-outputs", str(out_dir)],
+                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-6000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["unit"] == "contexts/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["also"] == {} and d["cpu_baseline"] is None and "cold_ms_per_step_without_settle" not in d["settle"]
+    assert sorted(os.listdir(out_dir)) == ["sum_ll_and_grads.npy"]
+    got = np.load(out_dir / "sum_ll_and_grads.npy")
+    assert got.dtype == np.float64 and got.tolist() == d["result"]
+    dev = torch.device("cuda", 0)
+    t = kernels.synth_counts(20211012, 0, n, dev, want=("train", "ref"))
+    if workload == "net":
+        want = kernels.dm_prior_planned(kernels.Plan(t["train"], 5), kernels.synth_prior(20211012, 0, n, dev), 0.0)
+    else:
+        want = kernels.dm_ref_planned(kernels.Plan(t["train"], 4, ref=t["ref"]), t["ref"], 0.0, float(np.log(1 / 30)), float(-np.log(100)))
+    assert np.allclose(got, want.cpu().numpy(), rtol=1e-12), (got, want)
 
 
 def test_bench_rccl_path_on_a_group_of_one():
