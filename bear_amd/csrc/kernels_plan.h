@@ -20,8 +20,8 @@
 //        themselves are not read at all
 //     D  wave w evaluates unit w: p = prod (x+j), p' by the product rule, one table log and one
 //        reciprocal per item; loops are wave-uniform (sorted), all lanes busy (full units)
-//     A  (mode N without the normalisation promise) wave w walks contexts 64w .. 64w+63: S = sum prior,
-//        context term from the shared-A table when S = 1 to 2 ulp, own product otherwise
+//     A  (mode N without the normalisation promise) wave w checks contexts 128w .. 128w+127: S = sum prior; the
+//        shared-A context terms come from the plan's histogram, a row with S off 1 by more than 2 ulp swaps its term for its own
 //     after the tiles: the global Stirling-path lists, densely packed over all threads, and the
 //     histogram x table terms.
 #pragma once
@@ -71,13 +71,23 @@ struct pln_tile {
 };
 static_assert(sizeof(pln_tile) == 32, "tile descriptors are fetched with one s_load_dwordx8");
 #ifndef PLN_CHUNK
-#define PLN_CHUNK 128                       // contexts per context-term ticket (multiple of 64)
+#define PLN_CHUNK 128                       // contexts per wave pass of the row-sum check (two per lane)
 #endif
 #ifndef PLN_DMA_WAVES
 #define PLN_DMA_WAVES 2                     // waves of each block that only stream tiles into LDS (see dm_prior_plan_kernel)
 #endif
 #ifndef PLN_PREFETCH_KIB
 #define PLN_PREFETCH_KIB 24                 // L2 prefetch of the tile after next by the DMA waves of the light mode-N forms (0: off)
+#endif
+// General mode-N form (rows not asserted normalised) of dm_prior_plan_kernel, switches for A/B builds:
+#ifndef PLN_GEN_PREFETCH
+#define PLN_GEN_PREFETCH 1                  // 1: the L2 prefetch of the tile after next there too
+#endif
+#ifndef PLN_GEN_NT
+#define PLN_GEN_NT 0                        // 1: the ring's LDS-DMA loads (prior rows, plan blocks) with the non-temporal policy
+#endif
+#ifndef PLN_GEN_NROW_ON_DEMAND
+#define PLN_GEN_NROW_ON_DEMAND 1            // 1: a tile's nrow bytes are staged only behind a tile with a failing row sum
 #endif
 #define PLN_DESC_CHUNK 32                   // descriptors per 1 KiB LDS-DMA piece
 #define PLN_DESC_PAD (2 * PLN_DESC_CHUNK)   // zeroed descriptors behind the last tile (plan allocation)
@@ -656,6 +666,8 @@ __device__ __forceinline__ uint32_t pln_dma(void *lds, const void *src, uint32_t
 }
 
 // One 1 KiB piece (`piece` = KiB index inside a slab of `bytes` bytes, multiple of 16) as a single DMA instruction.
+// NT: the non-temporal policy (bytes read once per launch, far more of them than the caches hold).
+template <bool NT = false>
 __device__ __forceinline__ void pln_dma_piece(void *lds, const void *src, uint32_t bytes, uint32_t piece, uint32_t lane) {
   const uint32_t m = srt_uniform((uint32_t)(uintptr_t)lds + (piece << 10));
   const unsigned char *g = static_cast<const unsigned char *>(src) + (piece << 10) + lane * 16u;
@@ -663,10 +675,16 @@ __device__ __forceinline__ void pln_dma_piece(void *lds, const void *src, uint32
     {
       // M0 is compiler-reserved: saved and restored inside the statement that uses it (no "m0" clobber: that is undefined behaviour)
       uint32_t keep_m0;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep_m0)
-                   : "v"(g), "s"(m)
-                   : "memory");
+      if (NT)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep_m0)
+                     : "v"(g), "s"(m)
+                     : "memory");
+      else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep_m0)
+                     : "v"(g), "s"(m)
+                     : "memory");
     }
 }
 
@@ -781,9 +799,12 @@ struct pln_lds_n {
   double tabD[SRT_NKEY];  // D(u + 5 eps, j + 1)
   double tabP[SRT_NKEY];
   uint32_t ticket[PLN_NBUF];  // per ring slot; zeroed one tile ahead
+  uint32_t sum_fail[PLN_NBUF];   // general form: the tile in the slot holds a row whose sum fails the test (set by compute waves)
+  uint32_t nrow_in[PLN_NBUF];    // general form: the tile in the slot was staged with its nrow range (set by the DMA waves)
   __attribute__((aligned(16))) pln_tile desc[2][PLN_DESC_CHUNK];  // descriptors of this block's tile range, 2 x 32
   __attribute__((aligned(16))) uint32_t pf_scratch[64];           // where the L2 prefetch's dwords land (never read)
 };
+static_assert(sizeof(pln_lds_n) <= 160 * 1024, "one block per CU: the planned mode-N kernels' LDS");
 
 // Tile descriptor j of the block's range from the LDS ring (wave-uniform: every lane reads the same address).
 __device__ __forceinline__ pln_tile pln_desc(const pln_tile (*ring)[PLN_DESC_CHUNK], uint64_t j, uint64_t count) {
@@ -838,6 +859,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
   if (tid < PLN_NBUF) {
     S.buf[tid].pri[PLN_SENTINEL] = 1.0;
     S.ticket[tid] = PLN_TICKET_START(PLN_WAVES - PLN_DMA_WAVES);
+    S.sum_fail[tid] = 0xffffffffu;   // no tile of this block seen yet
   }
 
   // One wave of the block (the last) is the DMA wave: it streams the tiles into the LDS ring and never computes.
@@ -846,14 +868,26 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
   // single wave per CU with <= 24 pieces in flight already sustains 5.8 TB/s.
   const bool dma_wave = wave >= PLN_WAVES - PLN_DMA_WAVES;
   const uint32_t dw = wave - (PLN_WAVES - PLN_DMA_WAVES);  // index among the DMA waves
-  auto stage = [&](const pln_tile &ti, uint32_t b) {  // DMA wave only: every piece of tile `ti` into ring slot `b`
+  constexpr bool GEN = !NORM && !AR;
+  constexpr bool NT = GEN && PLN_GEN_NT;
+  // DMA wave only: tile `ti` into ring slot `b`; without `with_nrow` the block in two ranges, E and [L.items, L.end), its nrow
+  // bytes left out (same LDS layout)
+  auto stage = [&](const pln_tile &ti, uint32_t b, bool with_nrow) {
     const uint32_t rows = ti.rows_items >> 16;
     if (rows == 0) return;
     const uint32_t pbytes = (rows * 40u) & ~15u, bbytes = ti.blk16 * 16u;
     const unsigned char *psrc = reinterpret_cast<const unsigned char *>(prior + ti.row0 * 5);
     const unsigned char *bsrc = pv.stream + (size_t)ti.off16 * 16;
-    for (uint32_t pc = dw; (pc << 10) < bbytes; pc += PLN_DMA_WAVES) pln_dma_piece(S.buf[b].blk, bsrc, bbytes, pc, lane);
-    for (uint32_t pc = dw; (pc << 10) < pbytes; pc += PLN_DMA_WAVES) pln_dma_piece(S.buf[b].pri, psrc, pbytes, pc, lane);
+    if (GEN && dw == 0 && lane == 0) S.nrow_in[b] = with_nrow ? 1u : 0u;
+    if (!GEN || with_nrow) {
+      for (uint32_t pc = dw; (pc << 10) < bbytes; pc += PLN_DMA_WAVES) pln_dma_piece<NT>(S.buf[b].blk, bsrc, bbytes, pc, lane);
+    } else {
+      const uint32_t items0 = pln_block_layout(rows, ti.rows_items & 0xffffu, ti.hc_hr >> 16, ti.hc_hr & 0xffffu).items;
+      if (dw == PLN_DMA_WAVES - 1) pln_dma_piece<NT>(S.buf[b].blk, bsrc, 64u, 0u, lane);   // E (wave 0 loads an odd tile's tail)
+      for (uint32_t pc = dw; (pc << 10) < bbytes - items0; pc += PLN_DMA_WAVES)
+        pln_dma_piece<NT>(S.buf[b].blk + items0, bsrc + items0, bbytes - items0, pc, lane);
+    }
+    for (uint32_t pc = dw; (pc << 10) < pbytes; pc += PLN_DMA_WAVES) pln_dma_piece<NT>(S.buf[b].pri, psrc, pbytes, pc, lane);
     if (dw == 0 && ((rows * 40u) & 15u)) {  // odd row count (last tile only): the trailing 8 bytes through the SCALAR path --
       // a vector load here would be followed by s_waitcnt vmcnt(0), which drains the DMA queue
       const __attribute__((address_space(4))) double *tail =
@@ -868,11 +902,12 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
   // normalised (no context pass) and the multinomial mode -- the DMA waves therefore also touch the first 24 KiB of the tile
   // AFTER next: one lane per 128-byte line, a dword each, landing in a scratch word of LDS; that tile's DMA, one iteration
   // later, finds those lines in the L2 / infinity cache: 0.778 -> 0.715 ms (NORM), 0.768 -> 0.705 ms (multinomial) per 1e8
-  // contexts, 6.2 TB/s on the bytes moved.  NOT in the general form: its tiles are bound by their compute (the context pass),
-  // and the card trades shader clock for memory power -- with the prefetch its item units ran 10 % slower (s_memtime: 2045 ->
-  // 2010 ticks per us) and the kernel 0.775 -> 0.81 ms.  Returns the number of instructions this wave issued (they are younger
-  // than the tile's DMA pieces: the wait for the tile leaves exactly that many outstanding).
-  constexpr uint32_t PF_INSTR = (NORM || AR) ? PLN_PREFETCH_KIB / 8u : 0u;
+  // contexts, 6.2 TB/s on the bytes moved.  The general form had it off while its tiles were bound by their compute (a context
+  // pass of table look-ups and own products: with the prefetch 0.775 -> 0.81 ms, the card trading shader clock for memory
+  // power); since that pass is a row-sum check (histogram terms) it is light too, and the prefetch is on (PLN_GEN_PREFETCH:
+  // 0.754 -> 0.731 ms per step, profiles/NOTES_rowsum_check.md).  Returns the number of instructions this wave issued (they are
+  // younger than the tile's DMA pieces: the wait for the tile leaves exactly that many outstanding).
+  constexpr uint32_t PF_INSTR = (NORM || AR || PLN_GEN_PREFETCH) ? PLN_PREFETCH_KIB / 8u : 0u;
   auto prefetch_behind = [&](const pln_tile &ti) -> uint32_t {
     const uint32_t rows = ti.rows_items >> 16;
     if (PF_INSTR == 0 || rows == 0) return 0u;
@@ -922,7 +957,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
   }
   __syncthreads();
   pln_tile cur = pln_desc(S.desc, 0, count), nxt = pln_desc(S.desc, 1, count);
-  if (dma_wave) stage(cur, 0);
+  if (dma_wave) stage(cur, 0, !PLN_GEN_NROW_ON_DEMAND);
   uint32_t slot = 0;
   for (uint64_t j = 0; j < count; ++j) {
 #ifdef PLN_STAMPS
@@ -936,7 +971,8 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
     const pln_tile nn = pln_desc(S.desc, j + 2, count);
     if (dma_wave) {
       if ((j & (PLN_DESC_CHUNK - 1)) == 0 && j != 0) fetch_desc(j + PLN_DESC_CHUNK);  // the ring half just left behind
-      stage(nxt, slot ^ 1u);
+      // the nrow bytes of tile j + 1 only if tile j - 1 (its compute ended at the barrier above) had a row sum that fails the test
+      stage(nxt, slot ^ 1u, !GEN || !PLN_GEN_NROW_ON_DEMAND || srt_uniform(S.sum_fail[slot ^ 1u]) == (uint32_t)j);
       pf_young = prefetch_behind(nxt);
       cur = nxt;
       nxt = nn;
@@ -953,19 +989,69 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
     const uint8_t *nrow = B.blk + L.nrow;
     const uint16_t *items = reinterpret_cast<const uint16_t *>(B.blk + L.items);
     if (tid == 0) S.ticket[(slot + 1) % PLN_NBUF] = PLN_TICKET_START(PLN_WAVES - PLN_DMA_WAVES);  // next tile's counter (its last readers passed the barrier above)
-    // Work list of the tile, dearest first: the large-count column items and contexts (Stirling path), the
-    // item units from the sorted tail down (long loops), then the 64-context chunks of the context terms.
-    // Waves draw tickets until the list is exhausted.
+    // Work list of the tile, dearest first: the large-count column items and contexts (Stirling path), then the
+    // item units from the sorted tail down (long loops).  Waves draw tickets until the list is exhausted.
     const uint32_t n_hcu = (hc + 63u) >> 6, n_hru = AR ? 0u : (hr + 63u) >> 6, n_heavy = n_hcu + n_hru;
     const uint32_t n_units = (n_light + 63u) >> 6;
-    const uint32_t n_work = n_heavy + n_units + ((NORM || AR) ? 0u : (rows + PLN_CHUNK - 1u) / PLN_CHUNK);
+    const uint32_t n_work = n_heavy + n_units;
+    // ---- A (general form): context terms  -D(A, n), (A - 5 eps) P(A, n)   with A = S u + 5 eps.  Every context with a total
+    // 1 <= n <= SRT_CL is in the plan's histogram, and block 0 adds the terms of the shared A = u + 5 eps for all of them once per
+    // launch (as in the NORM form).  Here the tile's rows are only checked: S = 1 to 2 ulp.  A row that fails the test and holds
+    // counts swaps its shared term for its own: + tabD[n-1] - D(A, n), - u tabP[n-1] + (A - 5 eps) P(A, n).  Its n comes from the
+    // tile's nrow bytes -- in LDS if the DMA waves staged them (they do behind a tile with a failing row), else from the plan in
+    // HBM.  Compute wave w checks contexts [PLN_CHUNK w, PLN_CHUNK (w + 1)) before it draws its work units: no ticket for that.  A
+    // lane takes two ADJACENT contexts: their ten doubles are 80 contiguous, 16-byte aligned bytes = five 16-byte LDS reads
+    // (conflict-free at this stride) instead of ten 8-byte ones
+    static_assert(PLN_CHUNK == 128, "two adjacent contexts per lane");
+    for (uint32_t c = wave; GEN && c * PLN_CHUNK < rows; c += PLN_WAVES - PLN_DMA_WAVES) {   // (one pass at PLN_THREADS 1024)
+      const uint32_t row0c = c * PLN_CHUNK + 2u * lane;
+      const uint32_t rr = row0c < rows ? row0c : 0u;          // rows is a multiple of 4 except in the table's last tile: a
+      const double2 *src = reinterpret_cast<const double2 *>(&B.pri[rr * 5]);   // pair may end one row past it (still inside pri)
+      const double2 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4];
+      const double S5[2] = {((v0.x + v0.y) + (v1.x + v1.y)) + v2.x, ((v2.y + v3.x) + (v3.y + v4.x)) + v4.y};
+      bool bad[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) bad[q] = row0c + q < rows && !(__builtin_fabs(S5[q] - 1.0) <= SRT_SUM1_TOL);
+      if (__builtin_amdgcn_ballot_w64(bad[0] || bad[1])) {
+        if (lane == 0) S.sum_fail[slot] = (uint32_t)(j + 1);   // the DMA waves: stage the nrow bytes of the tile after next
+        uint32_t nn_[2];
+        if (!PLN_GEN_NROW_ON_DEMAND || srt_uniform(S.nrow_in[slot])) {
+#pragma unroll
+          for (int q = 0; q < 2; ++q) nn_[q] = bad[q] ? (uint32_t)nrow[rr + q] : 0u;
+        } else {
+          const uint8_t *g = pv.stream + (size_t)cur.off16 * 16 + L.nrow;
+#pragma unroll
+          for (int q = 0; q < 2; ++q) nn_[q] = bad[q] ? (uint32_t)g[rr + q] : 0u;
+        }
+#pragma unroll
+        for (int q = 0; q < PLN_CHUNK / 64; ++q) {
+          const uint32_t own = nn_[q] == 255u ? 0u : nn_[q];  // 0: empty context; 255: total beyond SRT_CL (heavy lists)
+          if (__builtin_amdgcn_ballot_w64(own != 0)) {
+            uint32_t cm = own;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+              const uint32_t o2 = (uint32_t)__shfl_xor((int)cm, off, 64);
+              cm = o2 > cm ? o2 : cm;
+            }
+            const double xa[1] = {own ? __builtin_fma(S5[q], u, eps5) : 1.0};
+            const uint32_t ca[1] = {own};
+            bear_dp o[1];
+            srt_light<1>(xa, ca, 0u, srt_uniform(cm), S.logtab, o);
+            if (own) {
+              acc[0] += S.tabD[own - 1] - o[0].D;
+              acc[1] = __builtin_fma(xa[0] - eps5, o[0].P, __builtin_fma(-u, S.tabP[own - 1], acc[1]));
+            }
+          }
+        }
+      }
+    }
     PLN_FOR_UNITS_F(w, &S.ticket[slot], n_work, wave, PLN_WAVES - PLN_DMA_WAVES) {      // (the DMA waves never get here)
 #ifdef PLN_STAMPS
       {
         const unsigned long long now = __builtin_amdgcn_s_memtime();
         tph[prev_kind] += now - t_prev;  // the previous work item incl. the ticket draw that followed it
         t_prev = now;
-        prev_kind = w < n_heavy ? 5 : (w < n_heavy + n_units ? 6 : 7);
+        prev_kind = w < n_heavy ? 5 : 6;
       }
 #endif
       if (w < n_hcu) {  // large-count column items of this tile
@@ -995,7 +1081,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
         }
         continue;
       }
-      if (NORM || AR || w < n_heavy + n_units) {
+      {
         // ---- D: one unit of column items
         const uint32_t un = n_heavy + n_units - 1u - w;
         uint32_t cmin, cmax;
@@ -1011,49 +1097,6 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
         acc[0] += o[0].D;
         acc[1] = __builtin_fma(eps - x[0], o[0].P, acc[1]);
         continue;
-      }
-      // ---- A: context terms  -D(A, n), (A - 5 eps) P(A, n)   with A = S u + 5 eps; PLN_CHUNK contexts per ticket, a lane
-      // takes two ADJACENT contexts: their ten doubles are 80 contiguous, 16-byte aligned bytes = five 16-byte LDS reads
-      // (conflict-free at this stride) instead of ten 8-byte ones
-      static_assert(PLN_CHUNK == 128, "two adjacent contexts per lane");
-      const uint32_t row0c = (w - n_heavy - n_units) * PLN_CHUNK + 2u * lane;
-      double S5[2];
-      uint32_t nn_[2];
-      {
-        const uint32_t rr = row0c < rows ? row0c : 0u;          // rows is a multiple of 4 except in the table's last tile: a
-        const double2 *src = reinterpret_cast<const double2 *>(&B.pri[rr * 5]);   // pair may end one row past it (still inside pri)
-        const double2 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3], v4 = src[4];
-        S5[0] = ((v0.x + v0.y) + (v1.x + v1.y)) + v2.x;
-        S5[1] = ((v2.y + v3.x) + (v3.y + v4.x)) + v4.y;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const uint32_t n = row0c + q < rows ? (uint32_t)nrow[rr + q] : 0u;  // 0: empty context; 255: total beyond SRT_CL (heavy lists)
-          nn_[q] = n == 255u ? 0u : n;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < PLN_CHUNK / 64; ++q) {
-        const uint32_t n = nn_[q];
-        const bool shared = __builtin_fabs(S5[q] - 1.0) <= SRT_SUM1_TOL;
-        if (n != 0 && shared) {
-          acc[0] -= S.tabD[n - 1];
-          acc[1] = __builtin_fma(u, S.tabP[n - 1], acc[1]);
-        }
-        const uint32_t own = (n != 0 && !shared) ? n : 0u;  // general concentrations: own A
-        if (__builtin_amdgcn_ballot_w64(own != 0)) {
-          uint32_t cm = own;
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t o2 = (uint32_t)__shfl_xor((int)cm, off, 64);
-            cm = o2 > cm ? o2 : cm;
-          }
-          const double xa[1] = {own ? __builtin_fma(S5[q], u, eps5) : 1.0};
-          const uint32_t ca[1] = {own};
-          bear_dp o[1];
-          srt_light<1>(xa, ca, 0u, srt_uniform(cm), S.logtab, o);
-          acc[0] -= o[0].D;
-          acc[1] = __builtin_fma(xa[0] - eps5, o[0].P, acc[1]);
-        }
       }
     }
     cur = nxt;
@@ -1087,7 +1130,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_prior_plan_kernel(const dou
     acc[0] -= o.D;
     acc[1] = __builtin_fma(A - eps5, o.P, acc[1]);
   }
-  if (NORM && !AR && blockIdx.x == 0 && tid < SRT_CL) {  // context terms with the shared A, weighted by their multiplicity
+  if (!AR && blockIdx.x == 0 && tid < SRT_CL) {  // context terms with the shared A, weighted by their multiplicity
     const double m = (double)pv.hist[tid];
     acc[0] -= m * S.tabD[tid];
     acc[1] = __builtin_fma(u * m, S.tabP[tid], acc[1]);
