@@ -23,7 +23,7 @@ def _deterministic_requested():
 # parameter gradients over per call; BEAR_AMD_LIB: developer A/B builds.
 LIB_PATH = os.environ.get("BEAR_AMD_LIB") or os.path.join(_HERE, "libbear_hip_det.so" if _deterministic_requested() else "libbear_hip.so")
 
-ABI_VERSION = 6   # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
+ABI_VERSION = 7   # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
 
 SYMBOLS = [
     "bear_abi_version", "bear_strerror", "bear_last_hip_error", "bear_ws_create", "bear_ws_destroy",
@@ -39,6 +39,7 @@ SYMBOLS = [
     "bear_kmer_order_u64", "bear_gather_rows", "bear_plan_pair_contexts", "bear_plan_pair_info", "bear_plan_attach_cnn_levels", "bear_plan_cnn_level_rows", "bear_cnn_forward_plan_f64",
     "bear_plan_count_total", "bear_plan_set_count_bound", "bear_deterministic_build", "bear_plan_cnn_window_rows",
     "bear_plan_create_auto",
+    "bear_dm_prior_wide_f64", "bear_eval_wide_f64", "bear_parse_counts_tsv_wide", "bear_parse_counts_tsv_shard_wide",
 ]
 
 
@@ -157,6 +158,11 @@ def _load():
     L.bear_count_rows.argtypes = [ctypes.c_char_p, ctypes.POINTER(u64)]
     L.bear_count_newlines.argtypes = [ctypes.c_char_p, ctypes.POINTER(u64)]
     L.bear_parse_counts_tsv.argtypes = [ctypes.c_char_p, cint, cint, u64, vp, vp, ctypes.POINTER(u64)]
+    L.bear_dm_prior_wide_f64.argtypes = [vp, vp, vp, u64, cint, vp, dbl, cint, vp, vp, vp]
+    L.bear_eval_wide_f64.argtypes = [vp, vp, vp, vp, u64, cint, vp, cint, cint, vp, cint, dbl, u64, u64, vp, vp]
+    L.bear_parse_counts_tsv_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, u64, vp, vp, ctypes.POINTER(u64)]
+    L.bear_parse_counts_tsv_shard_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, u64, u64, u64, u64, cint, cint, u64, vp, vp,
+                                                   ctypes.POINTER(u64), ctypes.POINTER(u64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name in ("bear_plan_bytes", "bear_shuffle_source_row", "bear_eval_plan_bytes"):

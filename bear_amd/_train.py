@@ -164,12 +164,12 @@ class _Ready:
 
 def hbm_budget_check(data, n_columns, want_codes, device, rows=None, per_row_extra=0):
     """Raises before the first byte goes up when this rank's share of the epoch cannot stay resident: every batch is kept in HBM
-    for all epochs (counts 20 B per column and context, k-mer letters, packed codes, ~7 B of plan, per-context scratch of a
+    for all epochs (counts 4 W B per column and context -- W = 5, or 21 for the protein alphabet --, k-mer letters, packed codes, ~7 B of plan, per-context scratch of a
     fused AR function), and a table that does not fit is a matter of more ranks (rows shard: `python -m torch.distributed.run
     --nproc-per-node N ...`), not of a slower path."""
     rows = data.local_rows if rows is None else rows
     lag = data.lag
-    need = rows * (20 * n_columns + (lag + 8 if want_codes else 0) + 8 + per_row_extra)
+    need = rows * (4 * row_width(data) * n_columns + (lag + 8 if want_codes else 0) + 8 + per_row_extra)
     # (the k-mer sort's scratch, ~20 B per row of ONE batch at a time, is a torch tensor and fits the 15 % margin below)
     need = int(need * 1.15) + (256 << 20)           # the upload holds a column next to its compacted copy for a moment
     # blocks the caching allocator holds but nobody uses (an earlier train() call's slabs, allocated on another Uploader's side
@@ -183,6 +183,12 @@ def hbm_budget_check(data, n_columns, want_codes, device, rows=None, per_row_ext
                           f"{', k-mer codes' if want_codes else ''}, plans), {free / 2**30:.1f} of {total / 2**30:.1f} GiB are free: "
                           "shard the rows over more GPUs (python -m torch.distributed.run --nproc-per-node N ...)")
     return need
+
+
+def row_width(data):
+    """Counts per row of a dataset column: 5 (dna / rna) or 21 (prot).  Tables of any width but 5 take the width-generic kernels
+    (``kernels.dm_prior_wide`` / ``evaluate_wide``): no plans, no fused heads."""
+    return int(getattr(data, "width", 5))
 
 
 def sort_by_kmer(codes, lag):
@@ -218,6 +224,10 @@ class ResidentBatches:
         if not isinstance(data, CountDataset):
             raise TypeError("train / evaluation expect the CountDataset returned by bear_amd.dataloader")
         self.data, self.device = data, device
+        self.width = row_width(data)
+        if self.width != 5:
+            prebuild = ()                   # plans are 5-wide: a wider table's steps stream the rows (kernels.dm_prior_wide)
+            kmer_order = False              # (packed k-mers hold 3 bits per letter: the 4-letter alphabets' fused heads only)
         self.batches = []
         # k-mer letter codes: the ASCII bytes go up as they were parsed and are encoded on the device
         fast_codes = want_codes and data.alphabet in ("dna", "rna") and data.lag > 0
@@ -261,8 +271,9 @@ class ResidentBatches:
                     warnings.warn("another rank has to stream its share of the epoch: this rank streams too (the ranks run the same loop)")
                 self.streaming = True
         LAST_RUN["streaming"] = self.streaming
+        row_bytes = 4 * self.width
         up = None if on_dev else Uploader(device, expect_bytes=max(
-            [(g1 - g0) * 20 for _, (g0, g1, _) in pieces] + [data.local_rows * 20 if data.shuffle_seed is not None else 0, 1]))
+            [(g1 - g0) * row_bytes for _, (g0, g1, _) in pieces] + [data.local_rows * row_bytes if data.shuffle_seed is not None else 0, 1]))
         self.upload_bytes = 0
 
         def device_column(col, lo, hi):
@@ -437,6 +448,8 @@ class ResidentBatches:
         evaluations of the same shard)."""
         e = self.batches[k]
         key = ("eval", column, train_column)
+        if self.width != 5:
+            raise NotImplementedError(f"evaluation plans are built for 5-wide rows; this table's rows are {self.width} wide")
         if key not in e["plans"]:
             e["plans"][key] = kernels.EvalPlan(e[column], e.get(train_column))
         return e["plans"][key]
@@ -448,6 +461,8 @@ class ResidentBatches:
         a table of large counts gets the plan's dense form (``kernels.Plan(..., rows_if_dense=True)``)."""
         e = self.batches[k]
         key = (column, ncol, ref_column)
+        if self.width != 5:
+            raise NotImplementedError(f"kernel plans are built for 5-wide rows; this table's rows are {self.width} wide")
         if key not in e["plans"]:
             if ncol == ROWS_IF_DENSE:
                 e["plans"][key] = kernels.Plan(e[column], 5, rows_if_dense=True)
@@ -738,8 +753,12 @@ def run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, repeats, lear
                     check_normalized_rows(prior, "the AR function")
                     promise_checked[0] = True
                 need_rows = prior.requires_grad                    # parameter-free AR function (stop): nothing to feed back
-                r = kernels.dm_prior_planned_dev(res.plan(k, "train", ROWS_IF_DENSE), prior.detach(), h_dev, out=out, want_grad=need_rows,
-                                                 train_ar=train_ar, normalized=normalized)
+                if res.width != 5:                                 # protein rows: streamed by the width-generic kernel, no plan
+                    r = kernels.dm_prior_wide(e["train"], prior.detach().contiguous(), h_dev, out=out, want_grad=need_rows,
+                                              train_ar=train_ar)
+                else:
+                    r = kernels.dm_prior_planned_dev(res.plan(k, "train", ROWS_IF_DENSE), prior.detach(), h_dev, out=out,
+                                                     want_grad=need_rows, train_ar=train_ar, normalized=normalized)
                 if need_rows:
                     prior.backward(r[1])                           # d sum LL / d AR parameters
             else:
@@ -803,15 +822,21 @@ class EvaluationSums:
         self.outs = [[] for _ in range(0, max(self.hs.size, 1), self.step)]
 
     def add(self, test, prior, train=None, row_base=0, plan=None, row_ids=None):
-        """test / train: uint32 [n,5] device slabs; prior: float64 [n,5] = ar_func rows.  ``row_base`` is the global index of row 0
+        """test / train: uint32 [n,W] device slabs; prior: float64 [n,W] = ar_func rows (W = 5, or 21 for the protein alphabet).  ``row_base`` is the global index of row 0
         (``row_ids``: of a compacted batch, row i is table row ``row_base + row_ids[i]``), so the arg-max noise stream does not
         depend on how the rows are sharded or compacted."""
         if row_ids is not None and plan is None:
             raise ValueError("row_ids go with a planned evaluation (resident batches)")
+        wide = test.shape[-1] != 5
+        if wide and plan is not None:
+            raise ValueError("evaluation plans are 5-wide: rows of another width are evaluated unplanned")
         for c, k in enumerate(range(0, max(self.hs.size, 1), self.step)):
             hk = self.hs[k:k + self.step]
             first = k == 0
-            if plan is not None:      # resident table: the sorted plan of the test column (kernels_evalplan.h)
+            if wide:                  # protein rows (kernels_wide.h)
+                out = kernels.evaluate_wide(test, prior, hk, self.van if first else None, train, eps=self.eps, with_ar=first,
+                                            noise_seed=self.noise_seed + k, row_base=row_base)
+            elif plan is not None:    # resident table: the sorted plan of the test column (kernels_evalplan.h)
                 out = kernels.evaluate_planned(plan, prior, hk, self.van if first else None, eps=self.eps, with_ar=first,
                                                noise_seed=self.noise_seed + k, row_base=row_base, row_ids=row_ids)
             else:

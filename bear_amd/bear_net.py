@@ -57,7 +57,7 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
     # batches land, while the next batch is still being uploaded.
     res = _train.ResidentBatches(data, {"train": ds_loc}, device, want_codes=True, drop_empty="train", kmer_order=fused,
                                  prebuild=[("train", 5 if fused else _train.ROWS_IF_DENSE, None)],     # (+ paired lists of the linear head / prefix levels of the cnn step)
-                                 per_row_extra=(8 + (208 + 64 if cnn_ok else 4)) if fused else 80)
+                                 per_row_extra=(8 + (208 + 64 if cnn_ok else 4)) if fused else 16 * (alphabet_size + 1))
     scales = [-(num_kmers / e["global_rows"]) for e in res.batches]       # bear_net.py:190-191 with the global batch
     if fused:
         # theta = {h_signed, flattened AR parameters} lives on the device for the whole run: one step is constants-from-theta ->
@@ -137,19 +137,23 @@ def _eval(data, ds_loc_train, ds_loc_test, alphabet, h, ar_func, van_reg, dtype,
     cols = {"test": ds_loc_test}
     if use_train:
         cols["train"] = ds_loc_train
-    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids)
-    res = _train.ResidentBatches(data, cols, device, want_codes=True, drop_empty="test", per_row_extra=60,   # prior rows + plan
+    width = _train.row_width(data)
+    wide = width != 5
+    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids);
+    # rows wider than 5 are evaluated unplanned, in table order (row_base + i is the key of their tie-breaking noise)
+    res = _train.ResidentBatches(data, cols, device, want_codes=True, drop_empty=None if wide else "test",
+                                 per_row_extra=8 * width + 20,   # prior rows + plan
                                  kmer_order=ar_funcs.wants_kmer_order(ar_func))
     sums = _train.EvaluationSums(h, van_reg, noise_seed=seed)     # the batches' sums stay on the device until all are enqueued
     with torch.no_grad():
         for k, e in res.loaded():
             if not e["rows"]:
-                prior = torch.zeros((0, 5), dtype=dtype, device=device)
+                prior = torch.zeros((0, width), dtype=dtype, device=device)
             else:                                        # prior rows of the contexts with held-out counts: nothing else enters a sum
                 live = _train.live_rows(e, "codes", by="test")
                 out = ar_func(e["codes"] if live is None else e["codes_live_test"])
-                prior = out.expand(e["rows"], 5).contiguous() if live is None or out.shape[0] == 1 else _train.scatter_live(out, live, e["rows"])
-            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] else None,
+                prior = out.expand(e["rows"], width).contiguous() if live is None or out.shape[0] == 1 else _train.scatter_live(out, live, e["rows"])
+            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] and not wide else None,
                      row_ids=e.get("row_ids") if e["rows"] else None)
     res.close()
     ar_funcs.release_ar_func_cache(ar_func)

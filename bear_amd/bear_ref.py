@@ -102,7 +102,8 @@ def train(data, num_kmers, epochs, ds_loc, ds_loc_ref, alphabet, lag, make_ar_fu
     else:
         params, h_signed, ar_func = change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params_restart, dtype, device)
     dist.broadcast_params(params)                    # mirrored variables: every rank starts from rank 0's values (bear_ref.py:310-321)
-    if not ar_func.net_is_stop:
+    if not ar_func.net_is_stop or _train.row_width(data) != 5:
+        # (the planned mode-R step is 5-wide: a protein table mixes in torch ops and takes the width-generic mode-N kernel)
         return _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, optimizer_name, train_ar, acc_steps, writer,
                               loss_save, ds_loc, ds_loc_ref, device)
     # stop net function: theta = (h_signed, tau_signed, net_weight_signed) lives on the device for the whole run; one step is
@@ -146,7 +147,7 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     # (the sums do not depend on the order; cnn forward + backward 70 instead of 137 ms per 1e8 contexts, linear backward 1.45 / 2.0)
     res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, want_codes=True, drop_empty="train",
                                  kmer_order=bool(getattr(getattr(ar_func, "net_func", None), "fused", False)),
-                                 prebuild=[("train", 5, None)], per_row_extra=120)
+                                 prebuild=[("train", 5, None)], per_row_extra=24 * _train.row_width(data))
 
     def prior_fn_inputs(e):
         if "ref_in" not in e:
@@ -162,7 +163,7 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     # (bear_dm_refmix_plan_grad_f64: one launch instead of mix-forward, gradient rows, mix-backward); BEAR_AMD_UNFUSED_MIX=1 keeps
     # the three launches (tests compare the two)
     ref_mix = None
-    if (ar_func.normalized_rows and getattr(ar_func, "net_func", None) is not None and params[1] is ar_func.tau_signed
+    if (ar_func.normalized_rows and _train.row_width(data) == 5 and getattr(ar_func, "net_func", None) is not None and params[1] is ar_func.tau_signed
             and params[2] is ar_func.net_weight_signed and not os.environ.get("BEAR_AMD_UNFUSED_MIX")):
         def net_fn(e):
             prior_fn_inputs(e)
@@ -191,24 +192,28 @@ def evaluation(data, ds_loc_train, ds_loc_test, ds_loc_ref, alphabet, h, ar_func
     cols = {"test": ds_loc_test, "ref": ds_loc_ref}
     if use_train:
         cols["train"] = ds_loc_train
-    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids)
-    res = _train.ResidentBatches(data, cols, device, want_codes=True, drop_empty="test", per_row_extra=60,   # prior rows + plan
+    width = _train.row_width(data)
+    wide = width != 5
+    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids);
+    # rows wider than 5 are evaluated unplanned, in table order (row_base + i is the key of their tie-breaking noise)
+    res = _train.ResidentBatches(data, cols, device, want_codes=True, drop_empty=None if wide else "test",
+                                 per_row_extra=8 * width + 20,   # prior rows + plan
                                  kmer_order=_ar_funcs.wants_kmer_order(getattr(ar_func, "net_func", ar_func)))
     hv = float(torch.as_tensor(h).item()) if np.ndim(torch.as_tensor(h).detach().cpu().numpy()) == 0 else torch.as_tensor(h).detach().cpu().numpy()
     sums = _train.EvaluationSums(hv, van_reg, noise_seed=seed)     # the batches' sums stay on the device until all are enqueued
     with torch.no_grad():
         for k, e in res.loaded():
             if not e["rows"]:
-                prior = torch.zeros((0, 5), dtype=dtype, device=device)
+                prior = torch.zeros((0, width), dtype=dtype, device=device)
             else:                                        # prior rows of the contexts with held-out counts: nothing else enters a sum
                 if "ref_in" not in e:
                     e["ref_in"] = _ref_input(e["ref"], dtype)
                 live = _train.live_rows(e, "codes", "ref_in", by="test")
                 if live is None:
-                    prior = ar_func(e["codes"], e["ref_in"]).expand(e["rows"], 5).contiguous()
+                    prior = ar_func(e["codes"], e["ref_in"]).expand(e["rows"], width).contiguous()
                 else:
                     prior = _train.scatter_live(ar_func(e["codes_live_test"], e["ref_in_live_test"]), live, e["rows"])
-            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] else None,
+            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] and not wide else None,
                      row_ids=e.get("row_ids") if e["rows"] else None)
     res.close()
     _ar_funcs.release_ar_func_cache(getattr(ar_func, "net_func", ar_func))

@@ -27,6 +27,7 @@
 #include "kernels_cnn.h"
 #include "kernels_evalplan.h"
 #include "kernels_refplan.h"
+#include "kernels_wide.h"
 
 #ifdef EVP_STAMPS
 #define EVP_DBG_ARG , ws->dbg
@@ -1581,6 +1582,92 @@ int bear_eval_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, cons
   st = eval_make_args(test, train, prior, n_rows, h, n_h, with_ar, van_reg, n_van, eps, noise_seed, row_base, out, &A);
   if (st != BEAR_OK) return st;
   return launch_eval(ws, test, train, prior, n_rows, A, out, static_cast<hipStream_t>(stream));
+}
+
+// ---- rows wider than 5: the protein alphabet (kernels_wide.h) ------------------------------------------------------------
+static bool wide_width_ok(int width) { return width == 5 || width == 21; }
+
+int bear_dm_prior_wide_f64(bear_ws *ws, const uint32_t *counts, const double *prior, uint64_t n_rows, int width,
+                           const double *h_signed_dev, double eps, int train_ar, double *out, double *grad_prior, void *stream) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!out || (n_rows && (!counts || !prior)) || (!h_signed_dev && !train_ar)) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(counts) || misaligned(prior) || misaligned(grad_prior) || misaligned8(out) || misaligned8(h_signed_dev))
+    return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  bear_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.inv_h = 1.0;           // (AR mode without h_signed_dev: never read)
+  prm.eps = eps;
+  const uint64_t tile = (uint64_t)(width == 21 ? WIDE_TILE(21) : WIDE_TILE(5));
+  uint64_t g = (uint64_t)ws->num_cu * WIDE_BLOCKS_PER_CU, tiles = (n_rows + tile - 1) / tile;
+  if (g > (uint64_t)ws->max_blocks) g = ws->max_blocks;
+  if (tiles < g) g = tiles;
+  const int grid = g < 1 ? 1 : (int)g;
+  const bear_step_io io = ws_io(ws, h_signed_dev, BEAR_THETA_NET, out);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+#define WIDE_LAUNCH(W, AR, GRAD) \
+  hipLaunchKernelGGL((dm_wide_kernel<W, AR, GRAD>), dim3(grid), dim3(WIDE_THREADS), 0, s, counts, prior, n_rows, prm, grad_prior, lt, ws->partials, io)
+#define WIDE_LAUNCH_W(W)                                          \
+  do {                                                            \
+    if (train_ar) {                                               \
+      if (grad_prior) WIDE_LAUNCH(W, true, true);                 \
+      else WIDE_LAUNCH(W, true, false);                           \
+    } else {                                                      \
+      if (grad_prior) WIDE_LAUNCH(W, false, true);                \
+      else WIDE_LAUNCH(W, false, false);                          \
+    }                                                             \
+  } while (0)
+  if (width == 21) WIDE_LAUNCH_W(21);
+  else WIDE_LAUNCH_W(5);
+#undef WIDE_LAUNCH_W
+#undef WIDE_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows, int width,
+                       const double *h, int n_h, int with_ar, const double *van_reg, int n_van, double eps,
+                       uint64_t noise_seed, uint64_t row_base, double *out, void *stream) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  evl_args A;
+  st = eval_make_args(test, train, prior, n_rows, h, n_h, with_ar, van_reg, n_van, eps, noise_seed, row_base, out, &A);
+  if (st != BEAR_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the slot layout of launch_eval: at most EVS_CHUNK DM models per launch, the first launch also carries the AR model and the total
+  const int n_models = A.n_h + A.n_van;
+  const uint64_t tiles = (n_rows + EVW_THREADS - 1) / EVW_THREADS;
+  const int grid = (int)(tiles < (uint64_t)ws->eval_blocks ? (tiles ? tiles : 1) : (uint64_t)ws->eval_blocks);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+  for (int m0 = 0; m0 == 0 || m0 < n_models; m0 += EVS_CHUNK) {
+    const int m_cnt = n_models - m0 < EVS_CHUNK ? n_models - m0 : EVS_CHUNK;
+    const int common = m0 == 0;
+    evs_slots S;
+    for (int k = 0; k < EVS_NOUT; ++k) S.slot[k] = -1;
+    for (int k = 0; k < m_cnt; ++k) {
+      const int m = m0 + k;
+      const int ll_slot = m < A.n_h ? m : m + 1;
+      S.slot[k] = ll_slot;
+      S.slot[EVS_CHUNK + k] = n_models + 1 + ll_slot;
+    }
+    if (common) {
+      S.slot[2 * EVS_CHUNK] = A.n_h;
+      S.slot[2 * EVS_CHUNK + 1] = n_models + 1 + A.n_h;
+      S.slot[2 * EVS_CHUNK + 2] = 2 * n_models + 2;
+    }
+    if (width == 21)
+      hipLaunchKernelGGL(eval_wide_kernel<21>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common, lt,
+                         ws->eval_partials);
+    else
+      hipLaunchKernelGGL(eval_wide_kernel<5>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common, lt,
+                         ws->eval_partials);
+    hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
+  }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
 }
 
 // ---- evaluation on a sorted plan of the test column (kernels_evalplan.h) ------------------------------------------------

@@ -78,10 +78,11 @@ namespace {
 struct keep_all {
   bool operator()(uint64_t) const { return true; }
 };
-template <class Keep>
+// RW: the row width (BEAR_ROW_WIDTH; 21 for the protein alphabet, bear_parse_counts_tsv_wide).
+template <class Keep, int RW = BEAR_ROW_WIDTH>
 int parse_range(const char *p, const char *end, int num_ds, int lag, uint64_t max_rows, uint64_t row, uint64_t row_limit,
                 char *kmers, uint32_t *counts, uint64_t *rows_done, uint64_t g0 = 0, Keep keep = Keep()) {
-  const int per_row = num_ds * BEAR_ROW_WIDTH;
+  const int per_row = num_ds * RW;
   const uint64_t row_begin = row;
   uint64_t g = g0;
   while (p < end && row < row_limit) {
@@ -114,8 +115,8 @@ int parse_range(const char *p, const char *end, int num_ds, int lag, uint64_t ma
           while (q < le && *q == '0') ++q;
         }
         if (got >= per_row) return BEAR_ERR_PARSE;
-        const int ds = got / BEAR_ROW_WIDTH, b = got % BEAR_ROW_WIDTH;
-        counts[((uint64_t)ds * max_rows + row) * BEAR_ROW_WIDTH + b] = (uint32_t)v;
+        const int ds = got / RW, b = got % RW;
+        counts[((uint64_t)ds * max_rows + row) * RW + b] = (uint32_t)v;
         ++got;
       } else if (ch == '[' || ch == ']' || ch == ',' || ch == ' ' || ch == '\r') {
         ++q;
@@ -206,8 +207,9 @@ extern "C" int bear_count_newlines(const char *path, uint64_t *n_out) {
 // Text decoding is the first-epoch cost of a large table (~60-80 GB of text at 1e9 rows), so the file is
 // cut at line boundaries into one chunk per hardware thread: pass 1 counts the rows of each chunk, a prefix sum gives
 // every chunk its first row, pass 2 parses the chunks in place into the shared output arrays.
-extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_rows, char *kmers,
-                                     uint32_t *counts, uint64_t *n_rows_out) {
+template <int RW>
+static int parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_rows, char *kmers, uint32_t *counts,
+                            uint64_t *n_rows_out) {
   if (!path || !counts || !n_rows_out || num_ds < 1 || lag < 0) return BEAR_ERR_INVALID_ARG;
   *n_rows_out = 0;
   mapped_file f;
@@ -232,7 +234,7 @@ extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint
   std::vector<uint64_t> first(nt + 1, 0), done(nt, 0);
   std::vector<int> status(nt, BEAR_OK);
   if (nt == 1) {
-    st = parse_range<keep_all>(base, end, num_ds, lag, max_rows, 0, max_rows, kmers, counts, &done[0]);
+    st = parse_range<keep_all, RW>(base, end, num_ds, lag, max_rows, 0, max_rows, kmers, counts, &done[0]);
     if (st != BEAR_OK) return st;
     *n_rows_out = done[0];
     return BEAR_OK;
@@ -253,7 +255,7 @@ extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint
       th.emplace_back([&, k] {
         const uint64_t lim = first[k + 1] < max_rows ? first[k + 1] : max_rows;
         if (first[k] >= lim) return;
-        status[k] = parse_range<keep_all>(cut[k], cut[k + 1], num_ds, lag, max_rows, first[k], lim, kmers, counts, &done[k]);
+        status[k] = parse_range<keep_all, RW>(cut[k], cut[k + 1], num_ds, lag, max_rows, first[k], lim, kmers, counts, &done[k]);
       });
     for (auto &t : th) t.join();
   }
@@ -264,6 +266,18 @@ extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint
   }
   *n_rows_out = total;
   return BEAR_OK;
+}
+
+extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_rows, char *kmers,
+                                     uint32_t *counts, uint64_t *n_rows_out) {
+  return parse_counts_tsv<BEAR_ROW_WIDTH>(path, num_ds, lag, max_rows, kmers, counts, n_rows_out);
+}
+
+extern "C" int bear_parse_counts_tsv_wide(const char *path, int num_ds, int width, int lag, uint64_t max_rows, char *kmers,
+                                          uint32_t *counts, uint64_t *n_rows_out) {
+  if (width == BEAR_ROW_WIDTH) return parse_counts_tsv<BEAR_ROW_WIDTH>(path, num_ds, lag, max_rows, kmers, counts, n_rows_out);
+  if (width == 21) return parse_counts_tsv<21>(path, num_ds, lag, max_rows, kmers, counts, n_rows_out);
+  return BEAR_ERR_INVALID_ARG;
 }
 
 // ------------------------------------------------------------------ the sparse row format
@@ -379,9 +393,10 @@ extern "C" int bear_shard_rows_count(uint64_t row_base, uint64_t file_rows, uint
   return BEAR_OK;
 }
 
-extern "C" int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base,
-                                           uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
-                                           char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
+template <int RW>
+static int parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base, uint64_t total_rows,
+                                  uint64_t batch_rows, int rank, int world, uint64_t max_rows, char *kmers, uint32_t *counts,
+                                  uint64_t *n_local_out, uint64_t *n_file_rows_out) {
   if (!path || !counts || !n_local_out || num_ds < 1 || lag < 0 || batch_rows == 0 || world < 1 || rank < 0 || rank >= world)
     return BEAR_ERR_INVALID_ARG;
   *n_local_out = 0;
@@ -432,8 +447,8 @@ extern "C" int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag
       th.emplace_back([&, k] {
         const uint64_t out0 = S.below(row_base + first[k]) - l0, out1 = S.below(row_base + first[k + 1]) - l0;
         if (out0 >= out1) return;
-        status[k] = parse_range<keep_shard>(cut[k], cut[k + 1], num_ds, lag, max_rows, out0, out1, kmers, counts, &done[k], first[k],
-                                            keep_shard{S, row_base});
+        status[k] = parse_range<keep_shard, RW>(cut[k], cut[k + 1], num_ds, lag, max_rows, out0, out1, kmers, counts, &done[k], first[k],
+                                                keep_shard{S, row_base});
       });
     for (auto &t : th) t.join();
   }
@@ -444,6 +459,25 @@ extern "C" int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag
   }
   *n_local_out = total;
   return BEAR_OK;
+}
+
+extern "C" int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base,
+                                           uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
+                                           char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
+  return parse_counts_tsv_shard<BEAR_ROW_WIDTH>(path, num_ds, lag, skip_lines, row_base, total_rows, batch_rows, rank, world, max_rows,
+                                                kmers, counts, n_local_out, n_file_rows_out);
+}
+
+extern "C" int bear_parse_counts_tsv_shard_wide(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t row_base,
+                                                uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
+                                                char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
+  if (width == BEAR_ROW_WIDTH)
+    return parse_counts_tsv_shard<BEAR_ROW_WIDTH>(path, num_ds, lag, skip_lines, row_base, total_rows, batch_rows, rank, world, max_rows,
+                                                  kmers, counts, n_local_out, n_file_rows_out);
+  if (width == 21)
+    return parse_counts_tsv_shard<21>(path, num_ds, lag, skip_lines, row_base, total_rows, batch_rows, rank, world, max_rows, kmers,
+                                      counts, n_local_out, n_file_rows_out);
+  return BEAR_ERR_INVALID_ARG;
 }
 
 // ------------------------------------------------------------------ binary cache of a parsed table

@@ -61,6 +61,11 @@ class CountDataset:
     def lag(self):
         return self.kmers.shape[1]
 
+    @property
+    def width(self):
+        """Counts per row and column: alphabet size + 1 (5 for dna / rna, 21 for prot)."""
+        return self.counts.shape[2]
+
     def batch_bounds(self):
         """Row ranges of the batches of one epoch (last one short: no drop_remainder, dataloader.py:37)."""
         B, N = self.batch_size, self.num_rows
@@ -160,7 +165,7 @@ class CountDataset:
         return core.encode_kmers(self.kmers, self.alphabet)
 
     def device_column(self, ds_loc, device, rows=None):
-        """uint32 [n, 5] slab of one dataset column on `device` (int32 storage), cached."""
+        """uint32 [n, W] slab of one dataset column on `device` (int32 storage), cached."""
         key = (int(ds_loc), str(device), rows)
         t = self._device_cache.get(key)
         if t is None:
@@ -258,6 +263,7 @@ class DeviceCountDataset(CountDataset):
     local_rows = property(lambda self: self.counts_dev.shape[1])
     num_ds = property(lambda self: self.counts_dev.shape[0])
     lag = property(lambda self: self.kmers_dev.shape[1])
+    width = property(lambda self: self.counts_dev.shape[2])
 
     def repeat(self, epochs):
         return DeviceCountDataset(self.kmers_dev, self.counts_dev, self.alphabet, self.batch_size, self.dtype,
@@ -371,12 +377,24 @@ def dataloader(file, alphabet, batch_size, num_ds, cache=True, header=False, n_p
     -- and so the pieces -- are cut on the whole table); by default the file is the table."""
     L = _lib.lib()
     A1 = len(core.alphabets_tf[alphabet])
-    if A1 != 5:
-        raise NotImplementedError("the HIP kernels are built for 4-letter alphabets (+ stop): dna / rna")
     deal_kmer = shard == "kmer"
+    if A1 != 5 and deal_kmer:
+        raise NotImplementedError(f"alphabet {alphabet!r}: shard='kmer' (rows dealt by k-mer range) reads 5-wide rows only (dna / rna)")
     if shard in ("auto", "kmer"):
         from . import dist
         shard = dist.world() if dist.world()[1] > 1 else None
+    if A1 != 5:
+        # rows of A1 counts per column (the protein alphabet: 21) through the width-taking reader; what keeps a table on disk or
+        # reads a rank's rows of it is 5-wide
+        if shard is not None:
+            raise NotImplementedError(f"alphabet {alphabet!r}: the sharded reader (shard=...) reads 5-wide rows only (dna / rna); "
+                                      "load the table unsharded")
+        if binary_cache or (binary_cache is None and os.environ.get("BEAR_AMD_CACHE_DIR")):
+            raise NotImplementedError(f"alphabet {alphabet!r}: the binary cache (binary_cache / BEAR_AMD_CACHE_DIR) holds 5-wide rows "
+                                      "only (dna / rna)")
+        if row_base or total_rows is not None:
+            raise ValueError("row_base / total_rows place a file inside a sharded table")
+        return _load_wide(file, alphabet, A1, batch_size, int(num_ds), header, dtype)
     if deal_kmer and shard is not None:
         # rows dealt to the ranks by k-mer range (KmerDealtDataset): every rank parses the whole table and keeps its range
         whole = dataloader(file, alphabet, batch_size, num_ds, cache=cache, header=header, n_par=n_par, dtype=dtype,
@@ -412,6 +430,27 @@ def dataloader(file, alphabet, batch_size, num_ds, cache=True, header=False, n_p
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         _lib.check(L.bear_cache_write(path.encode(), kmers.ctypes.data, counts.ctypes.data, n_rows, int(lag), int(num_ds),
                                       fsz.value, fmt.value), "bear_cache_write")
+    return CountDataset(kmers, counts, alphabet, batch_size, dtype)
+
+
+def _load_wide(file, alphabet, width, batch_size, num_ds, header, dtype):
+    """The whole table with rows of ``width`` counts per dataset column (``bear_parse_counts_tsv_wide``; with a header line the
+    one-rank form of the sharded reader, as ``dataloader`` does for 5-wide rows)."""
+    L = _lib.lib()
+    n_rows = count_rows(file, header)
+    lag = _sniff_lag(file, header, b"\t")
+    kmers = np.zeros((n_rows, lag), dtype=np.uint8)
+    counts = np.zeros((num_ds, n_rows, width), dtype=np.uint32)
+    got = ctypes.c_uint64()
+    if header:
+        _lib.check(L.bear_parse_counts_tsv_shard_wide(str(file).encode(), num_ds, width, int(lag), 1, 0, n_rows, max(n_rows, 1), 0, 1,
+                                                      n_rows, kmers.ctypes.data, counts.ctypes.data, ctypes.byref(got), None),
+                   "bear_parse_counts_tsv_shard_wide")
+    else:
+        _lib.check(L.bear_parse_counts_tsv_wide(str(file).encode(), num_ds, width, int(lag), n_rows, kmers.ctypes.data,
+                                                counts.ctypes.data, ctypes.byref(got)), "bear_parse_counts_tsv_wide")
+    if got.value != n_rows:
+        raise RuntimeError(f"{file}: {got.value} rows parsed, {n_rows} counted (did the file change while it was read?)")
     return CountDataset(kmers, counts, alphabet, batch_size, dtype)
 
 
@@ -500,6 +539,10 @@ def bmm_likelihood(data, alpha, dtype=torch.float64, device=None):
         data = data.source
     if not isinstance(data, CountDataset):
         raise TypeError("bmm_likelihood expects the CountDataset returned by dataloader() (or its .map(...) view)")
+    if data.width != 5:
+        # bear_bmm_f64 reads 5-wide rows: a wider table would be read as garbage
+        raise NotImplementedError(f"bmm_likelihood: rows of {data.width} counts (alphabet {data.alphabet!r}); the BMM kernel reads "
+                                  "5-wide rows only (dna / rna)")
     device = torch.device(device or "cuda")
     alpha = np.atleast_1d(np.asarray(alpha, dtype=np.float64))
     out = torch.zeros((data.num_ds, len(alpha)), dtype=torch.float64)

@@ -72,6 +72,21 @@ def _check_rows(t, dtype, name):
     return t
 
 
+WIDE_WIDTHS = (5, 21)   # row widths of the *_wide entry points: the protein alphabet (20 letters + stop), and 5 for cross-checks
+
+
+def _check_rows_wide(t, dtype, name, width=None):
+    """``_check_rows`` for rows of any supported width (the width of ``t``, or ``width``)."""
+    w = t.shape[-1] if (t.dim() == 2 and width is None) else width
+    if not (t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == w and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous CUDA tensor of shape [N, W] and dtype {dtype}")
+    if w not in WIDE_WIDTHS:
+        raise ValueError(f"{name}: rows of width {w}; the wide kernels take {WIDE_WIDTHS}")
+    if t.data_ptr() % 16:
+        t = t.clone()
+    return t
+
+
 def counts_dtype():
     """Counts travel as 32-bit words (KMC's counter range, summarize.py:66-67). torch has no
     general uint32 arithmetic, so int32 storage is used and reinterpreted by the kernel."""
@@ -93,6 +108,30 @@ def dm_prior(counts, prior, h_signed, eps=EPSILON, train_ar=False, want_grad=Fal
         st = _lib.lib().bear_dm_prior_f64(ws.handle, _ptr(counts), _ptr(prior), counts.shape[0], float(h_signed), float(eps),
                                           int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
     _lib.check(st, "bear_dm_prior_f64")
+    return out, grad
+
+
+def dm_prior_wide(counts, prior, h_signed_dev, eps=EPSILON, train_ar=False, want_grad=False, out=None, ws=None):
+    """``bear_dm_prior_wide_f64``: ``dm_prior`` for rows of width W = ``counts.shape[-1]`` (21: the protein alphabet), with h_signed
+    read from the device tensor ``h_signed_dev`` [1] (a step is enqueued without a host read-back and can be captured).
+    Returns (out[2] device tensor = sum LL, d/dh_signed; grad_prior [N, W] or None)."""
+    counts = _check_rows_wide(counts, torch.int32, "counts")
+    width = counts.shape[1]
+    prior = _check_rows_wide(prior, torch.float64, "prior", width)
+    if counts.shape[0] != prior.shape[0]:
+        raise ValueError("counts and prior must have the same number of rows")
+    if h_signed_dev is not None:
+        _f64_vec(h_signed_dev, 1, "h_signed_dev")
+    elif not train_ar:
+        raise ValueError("h_signed_dev is needed in BEAR mode")
+    ws = ws or default_workspace(counts.device)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=counts.device)
+    grad = torch.empty_like(prior) if want_grad else None
+    with torch.cuda.device(counts.device):
+        st = _lib.lib().bear_dm_prior_wide_f64(ws.handle, _ptr(counts), _ptr(prior), counts.shape[0], width, _ptr(h_signed_dev),
+                                               float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
+    _lib.check(st, "bear_dm_prior_wide_f64")
     return out, grad
 
 
@@ -385,6 +424,29 @@ def evaluate(test, prior, h, van_reg, train=None, eps=EPSILON, with_ar=True, noi
         st = _lib.lib().bear_eval_f64(ws.handle, _ptr(test), _ptr(train), _ptr(prior), n, hp, hs.size, int(bool(with_ar)), vp,
                                       vs.size, float(eps), int(noise_seed), int(row_base), _ptr(out), _stream())
     _lib.check(st, "bear_eval_f64")
+    return out
+
+
+def evaluate_wide(test, prior, h, van_reg, train=None, eps=EPSILON, with_ar=True, noise_seed=0, row_base=0, ws=None):
+    """``bear_eval_wide_f64``: ``evaluate`` for rows of width W = ``test.shape[-1]`` (21: the protein alphabet); the same output
+    vector, the tie-breaking noise keyed by ``row * W + letter``."""
+    test = _check_rows_wide(test, torch.int32, "test")
+    n, width = test.shape
+    if train is not None:
+        train = _check_rows_wide(train, torch.int32, "train", width)
+    if prior is not None:
+        prior = _check_rows_wide(prior, torch.float64, "prior", width)
+    for t in (train, prior):
+        if t is not None and t.shape[0] != n:
+            raise ValueError("test, train and prior must have the same number of rows")
+    hs, hp = _host_f64(h) if h is not None else (np.zeros(0), ctypes.c_void_p(0))
+    vs, vp = _host_f64(van_reg) if van_reg is not None else (np.zeros(0), ctypes.c_void_p(0))
+    ws = ws or default_workspace(test.device)
+    out = torch.empty(2 * (hs.size + vs.size) + 3, dtype=torch.float64, device=test.device)
+    with torch.cuda.device(test.device):
+        st = _lib.lib().bear_eval_wide_f64(ws.handle, _ptr(test), _ptr(train), _ptr(prior), n, width, hp, hs.size, int(bool(with_ar)),
+                                           vp, vs.size, float(eps), int(noise_seed), int(row_base), _ptr(out), _stream())
+    _lib.check(st, "bear_eval_wide_f64")
     return out
 
 

@@ -22,7 +22,8 @@
  *     by two streams at once.
  *   - the calling thread's current HIP device must be the workspace's device.
  *   - count rows are 5 wide: A, C, G, T (or U) and the stop symbol, in the order of
- *     bear_model/core.py:146-147; counts are uint32 (KMC's counter limit, summarize.py:66-67).
+ *     bear_model/core.py:146-147; counts are uint32 (KMC's counter limit, summarize.py:66-67).  The *_wide entry points take
+ *     the row width as an argument: 21 for the protein alphabet (20 letters + stop, core.py:142-145), or 5.
  *   - there is NO CPU fallback: without a gfx950 device the compute entry points fail
  *     with BEAR_ERR_NO_DEVICE.
  */
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define BEAR_ABI_VERSION 6 /* 6: + bear_plan_create_auto; bear_plan_create_ref may hand back the plan's dense form (round 6) */
+#define BEAR_ABI_VERSION 7 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -415,6 +416,27 @@ int bear_eval_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, cons
                   uint64_t noise_seed, uint64_t row_base, double *out, void *stream);
 
 /*
+ * Rows of any supported width W (`width`: 21 for the protein alphabet, 5 for checking against the entry points above; anything
+ * else is BEAR_ERR_INVALID_ARG).  DNA / RNA training and evaluation keep their 5-wide kernels and plans; these are the path of
+ * a 21-letter table (kernels_wide.h: row tiles staged through LDS, one item per NON-ZERO cell, the row term once per context).
+ *
+ * bear_dm_prior_wide_f64: what bear_dm_prior_f64 computes, at width W, in ONE launch with nothing on the host in between:
+ *   counts [dev] uint32 [n_rows, W], prior [dev] double [n_rows, W], grad_prior [dev] double [n_rows, W] or NULL -- 16-byte aligned
+ *   h_signed_dev [dev] double [1], 8-byte aligned: read by the kernel (capturable into a HIP graph; may be NULL when train_ar)
+ *   out [dev] double [2], 8-byte aligned: { sum LL, d sum LL / d h_signed } written by the last block in a fixed order (the
+ *   same bits for the same inputs and n_rows).  BEAR mode alpha = prior / exp(h_signed) + eps; train_ar: probs = prior + eps,
+ *   d/dh = 0, gradient rows c / probs.
+ * bear_eval_wide_f64: bear_eval_f64 at width W -- same arguments, limits (n_h + n_van <= 64), alignment and output vector; the
+ *   tie-breaking noise is the same counter-based stream with the cell key row * W + letter (oracle/bear_oracle.py:eval_noise with
+ *   width = W), so at W = 5 every accuracy equals bear_eval_f64's.
+ */
+int bear_dm_prior_wide_f64(bear_ws *ws, const uint32_t *counts, const double *prior, uint64_t n_rows, int width,
+                           const double *h_signed_dev, double eps, int train_ar, double *out, double *grad_prior, void *stream);
+int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows, int width,
+                       const double *h, int n_h, int with_ar, const double *van_reg, int n_van, double eps,
+                       uint64_t noise_seed, uint64_t row_base, double *out, void *stream);
+
+/*
  * The same on a sorted plan of the TEST column, for a table that stays resident (a held-out evaluation after training, the
  * train-set evaluation, every value of an h_scan): bear_eval_plan_create lists, per tile of 448 contexts, the cells and the rows
  * with a non-zero test count sorted by count, the rows whose largest TRAINING counts tie (their vanilla arg-max is decided
@@ -533,6 +555,13 @@ int bear_shard_rows_count(uint64_t row_base, uint64_t file_rows, uint64_t total_
 int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base, uint64_t total_rows,
                                 uint64_t batch_rows, int rank, int world, uint64_t max_rows, char *kmers, uint32_t *counts,
                                 uint64_t *n_local_out, uint64_t *n_file_rows_out);
+/* bear_parse_counts_tsv and bear_parse_counts_tsv_shard for rows of `width` counts per dataset column (21: the protein alphabet;
+ * 5: the readers above): counts [host] uint32 [num_ds, max_rows, width].  Any other width: BEAR_ERR_INVALID_ARG. */
+int bear_parse_counts_tsv_wide(const char *path, int num_ds, int width, int lag, uint64_t max_rows, char *kmers, uint32_t *counts,
+                               uint64_t *n_rows_out);
+int bear_parse_counts_tsv_shard_wide(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t row_base,
+                                     uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows, char *kmers,
+                                     uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out);
 
 /*
  * Binary cache of a parsed count table: what bear_parse_counts_tsv produced, stored as it is uploaded,
