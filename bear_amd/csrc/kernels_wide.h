@@ -81,7 +81,10 @@ __global__ __launch_bounds__(WIDE_THREADS) void dm_wide_kernel(const uint32_t *_
           const int b = __builtin_ctz(nz);
           nz &= nz - 1u;
           const double p = f[b] + prm.eps, cb = (double)c[b];
-          acc[0] += cb * (p > 0.0 ? bear_log_tab(p, s_log) : bear_log(p));
+          // the table log is exact to ~1e-16 ABSOLUTE (e ln2 - log r_i cancel for p just above 1): at p = 1 + eps (a one-hot prior
+          // row) that is 1e-9 of log p.  Near 1 the polynomial on p - 1 (exact there) keeps it relative.
+          const double lp = fabs(p - 1.0) < 0x1p-8 ? bear_log1p_small(p - 1.0) : (p > 0.0 ? bear_log_tab(p, s_log) : bear_log(p));
+          acc[0] += cb * lp;
           if (GRAD) f[b] = cb * bear_rcp(p);
         }
       } else {

@@ -276,3 +276,187 @@ void oracle_dm_ref_mass_f64(const uint32_t *train, const uint32_t *ref, uint64_t
   mass[1] = m1;
   mass[2] = m2;
 }
+
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Width-generic mode N (any row width W <= 32: the protein alphabet's 21, and 5 for cross-checks).  Not a restatement of the
+ * 5-wide functions above (those keep their bits for the golden tests): every item D(x, c) = lgamma(x + c) - lgamma(x) and
+ * P(x, c) = psi(x + c) - psi(x) is evaluated in long double on its own, independent of the product / Stirling switch of the
+ * kernels, so that it stays accurate at the concentrations the kernels' edge tests reach (x up to ~1e9 at h_signed = -20, counts
+ * up to 2^32 - 1, rows whose total exceeds 2^32):
+ *   c <= 64 : direct sums of log(x + j) and 1 / (x + j);
+ *   c >  64 : the same sums up to y = x + k >= 32, then the Stirling series difference between y and y + c - k, written with
+ *             log1p((c - k) / y) so that no large terms cancel (lgamma / digamma themselves differ by less than they weigh when
+ *             x >> c: their difference would lose the digits this oracle is there to keep).
+ * tests/test_oracle.py holds the items to mpmath.
+ */
+typedef long double ldbl;
+
+static ldbl stir_S(ldbl y) { /* lgamma(y) - (y - 1/2) log y + y - log(2 pi) / 2 */
+  const ldbl r = 1.0L / y, r2 = r * r;
+  return r * (1.0L / 12 + r2 * (-1.0L / 360 + r2 * (1.0L / 1260 + r2 * (-1.0L / 1680 + r2 * (1.0L / 1188 + r2 * (-691.0L / 360360
+         + r2 * (1.0L / 156 + r2 * (-3617.0L / 122400))))))));
+}
+
+static ldbl stir_T(ldbl y) { /* log y - 1/(2y) - psi(y) */
+  const ldbl r2 = 1.0L / (y * y);
+  return r2 * (1.0L / 12 + r2 * (-1.0L / 120 + r2 * (1.0L / 252 + r2 * (-1.0L / 240 + r2 * (1.0L / 132 + r2 * (-691.0L / 32760
+         + r2 * (1.0L / 12 + r2 * (-3617.0L / 8160))))))));
+}
+
+/* D(x, c) and P(x, c) for x > 0, c >= 0 an integer (a count, or a row total below 2^53) */
+static void item_w(double x_d, double c_d, ldbl *D, ldbl *P) {
+  ldbl x = x_d, d = 0.0L, p = 0.0L;
+  uint64_t c = (uint64_t)c_d, k = c <= 64 ? c : 0;
+  if (c > 64)
+    while (x + (ldbl)k < 32.0L) ++k;
+  for (uint64_t j = 0; j < k; ++j) {
+    d += logl(x + (ldbl)j);
+    p += 1.0L / (x + (ldbl)j);
+  }
+  if (c > k) {
+    const ldbl y = x + (ldbl)k, m = (ldbl)(c - k), z = y + m;
+    d += (y - 0.5L) * log1pl(m / y) + m * logl(z) - m + (stir_S(z) - stir_S(y));
+    p += log1pl(m / y) + m / (2.0L * y * z) - (stir_T(z) - stir_T(y));
+  }
+  *D = d;
+  *P = p;
+}
+
+/* The items of item_w, for the tests (D and P rounded to double). */
+void oracle_dm_item_w(double x, double c, double *D, double *P) {
+  ldbl d, p;
+  item_w(x, c, &d, &p);
+  *D = (double)d;
+  *P = (double)p;
+}
+
+/*
+ * One row of width W in mode N.  Returns the row's LL; *dh its d/dh_signed term; g (nullable) the gradient row dLL/dprior;
+ * with mass != NULL also mass[0] += the row's share of the L1 mass of d/dh_signed, mass[1] += that of sum LL (|row term| + sum of
+ * |items|), and gmass (nullable) the per-entry gradient-row mass (|psi(a+c) - psi(a)| + |psi(A+n) - psi(A)|) / h (AR mode: c / p,
+ * the one term of that entry).
+ */
+static ldbl dm_row_w(const uint32_t *cnt, const double *f, int W, double h, double eps, int train_ar, ldbl *dh, double *g,
+                     ldbl *mass, double *gmass) {
+  ldbl ll = 0.0L;
+  *dh = 0.0L;
+  if (train_ar) {
+    for (int b = 0; b < W; ++b) {
+      const double p = f[b] + eps, c = (double)cnt[b];
+      const ldbl t = c != 0.0 ? (ldbl)c * logl((ldbl)p) : 0.0L;
+      ll += t;
+      if (g) g[b] = (double)((ldbl)c / (ldbl)p);
+      if (mass) mass[1] += fabsl(t);
+      if (gmass) gmass[b] = (double)((ldbl)c / (ldbl)p);
+    }
+    return ll;
+  }
+  double a[32];
+  double A = 0.0, n = 0.0;
+  for (int b = 0; b < W; ++b) {
+    a[b] = f[b] / h + eps;
+    A += a[b];
+    n += (double)cnt[b];
+  }
+  ldbl Dn, Pn;
+  item_w(A, n, &Dn, &Pn);
+  ll = -Dn;
+  if (mass) mass[1] += fabsl(Dn);
+  for (int b = 0; b < W; ++b) {
+    ldbl Db, Pb;
+    item_w(a[b], (double)cnt[b], &Db, &Pb);
+    ll += Db;
+    const ldbl gb = Pb - Pn; /* dLL / d alpha_b */
+    *dh += gb * (-(ldbl)f[b] / (ldbl)h);
+    if (g) g[b] = (double)(gb / (ldbl)h);
+    if (mass) {
+      mass[0] += (fabsl(Pb) + fabsl(Pn)) * fabsl((ldbl)f[b] / (ldbl)h);
+      mass[1] += fabsl(Db);
+    }
+    if (gmass) gmass[b] = (double)((fabsl(Pb) + fabsl(Pn)) / (ldbl)h);
+  }
+  return ll;
+}
+
+/*
+ * oracle_dm_prior_f64 for rows of width W <= 32: out[0] = sum LL, out[1] = d sum LL / d h_signed (0 in AR mode), grad_prior
+ * (nullable) [n, W].  Per-thread long double partials summed in thread order (deterministic for a fixed thread count).
+ */
+int oracle_dm_prior_w_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, int W, double h_signed, double eps,
+                          int train_ar, double *out, double *grad_prior, int nthreads) {
+  if (W < 1 || W > 32) return -1;
+  const double h = exp(h_signed);
+  if (nthreads < 1) nthreads = 1;
+  ldbl *part = (ldbl *)calloc((size_t)nthreads * 2, sizeof(ldbl));
+#ifdef _OPENMP
+#pragma omp parallel num_threads(nthreads)
+#endif
+  {
+#ifdef _OPENMP
+    int tid = omp_get_thread_num();
+#else
+    int tid = 0;
+#endif
+    ldbl ll = 0.0L, dh = 0.0L, d;
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int64_t i = 0; i < (int64_t)n_rows; ++i) {
+      const size_t o = (size_t)i * W;
+      ll += dm_row_w(counts + o, prior + o, W, h, eps, train_ar, &d, grad_prior ? grad_prior + o : NULL, NULL, NULL);
+      dh += d;
+    }
+    part[2 * tid] = ll;
+    part[2 * tid + 1] = dh;
+  }
+  ldbl s0 = 0.0L, s1 = 0.0L;
+  for (int t = 0; t < nthreads; ++t) {
+    s0 += part[2 * t];
+    s1 += part[2 * t + 1];
+  }
+  out[0] = (double)s0;
+  out[1] = (double)s1;
+  free(part);
+  return 0;
+}
+
+/*
+ * L1 masses at width W: mass[0] = of d/dh_signed (0 in AR mode), mass[1] = of sum LL; grad_mass (nullable) [n, W] = of each
+ * gradient-row entry (see dm_row_w).  The tests bound an error by a multiple of the mass of what is compared.
+ */
+int oracle_dm_prior_mass_w_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, int W, double h_signed, double eps,
+                               int train_ar, double *mass, double *grad_mass, int nthreads) {
+  if (W < 1 || W > 32) return -1;
+  const double h = exp(h_signed);
+  if (nthreads < 1) nthreads = 1;
+  ldbl *part = (ldbl *)calloc((size_t)nthreads * 2, sizeof(ldbl));
+#ifdef _OPENMP
+#pragma omp parallel num_threads(nthreads)
+#endif
+  {
+#ifdef _OPENMP
+    int tid = omp_get_thread_num();
+#else
+    int tid = 0;
+#endif
+    ldbl m[2] = {0.0L, 0.0L}, d;
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int64_t i = 0; i < (int64_t)n_rows; ++i) {
+      const size_t o = (size_t)i * W;
+      dm_row_w(counts + o, prior + o, W, h, eps, train_ar, &d, NULL, m, grad_mass ? grad_mass + o : NULL);
+    }
+    part[2 * tid] = m[0];
+    part[2 * tid + 1] = m[1];
+  }
+  ldbl s0 = 0.0L, s1 = 0.0L;
+  for (int t = 0; t < nthreads; ++t) {
+    s0 += part[2 * t];
+    s1 += part[2 * t + 1];
+  }
+  mass[0] = (double)s0;
+  mass[1] = (double)s1;
+  free(part);
+  return 0;
+}

@@ -14,10 +14,15 @@ def build():
     subprocess.run(["make", "-C", _HERE, "-s"], check=True)
 
 
+def _stale():
+    """No library yet, or one older than its source (a stale build would lack the newer entry points)."""
+    return not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, "bear_oracle.c"))
+
+
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_SO):
+        if _stale():
             build()
         L = ctypes.CDLL(_SO)
         u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -34,6 +39,14 @@ def lib():
         L.oracle_dm_ref_mass_f64.argtypes = [u32p, u32p, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_int, f64p, ctypes.c_int]
         L.oracle_dm_ref_mass_f64.restype = None
+        L.oracle_dm_prior_w_f64.argtypes = [u32p, f64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_int, f64p, f64p, ctypes.c_int]
+        L.oracle_dm_prior_w_f64.restype = ctypes.c_int
+        L.oracle_dm_prior_mass_w_f64.argtypes = [u32p, f64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_int, f64p, f64p, ctypes.c_int]
+        L.oracle_dm_prior_mass_w_f64.restype = ctypes.c_int
+        L.oracle_dm_item_w.argtypes = [ctypes.c_double, ctypes.c_double, f64p, f64p]
+        L.oracle_dm_item_w.restype = None
         _lib = L
     return _lib
 
@@ -91,3 +104,38 @@ def dm_ref_mass(train, ref, h_signed, tau_signed, nu_signed, eps=1e-7, train_ar=
     out, op = _f64(np.zeros(3))
     lib().oracle_dm_ref_mass_f64(cp, rp, c.shape[0], h_signed, tau_signed, nu_signed, eps, int(train_ar), op, nthreads)
     return out
+
+
+def _rows_w(counts, prior):
+    c, cp = _u32(counts)
+    f, fp = _f64(prior)
+    assert c.ndim == 2 and c.shape == f.shape and 1 <= c.shape[1] <= 32
+    return c, cp, f, fp
+
+
+def dm_prior_w(counts, prior, h_signed, eps=1e-7, train_ar=False, want_grad=False, nthreads=1):
+    """``dm_prior`` for rows of any width W <= 32, every lgamma / digamma difference in long double (bear_oracle.c,
+    oracle_dm_prior_w_f64).  Returns (out[2] = sum LL, d/dh_signed; grad_prior [N, W] or None)."""
+    c, cp, f, fp = _rows_w(counts, prior)
+    out, op = _f64(np.zeros(2))
+    g, gp = _f64(np.zeros(c.shape)) if want_grad else (None, None)
+    assert lib().oracle_dm_prior_w_f64(cp, fp, c.shape[0], c.shape[1], h_signed, eps, int(train_ar), op, gp, nthreads) == 0
+    return out, g
+
+
+def dm_prior_mass_w(counts, prior, h_signed, eps=1e-7, train_ar=False, want_grad=False, nthreads=1):
+    """L1 masses of ``dm_prior_w``'s outputs: (mass[2] = of d/dh_signed (0 in AR mode), of sum LL; grad_mass [N, W] or None =
+    of each gradient-row entry, (|psi(a+c) - psi(a)| + |psi(A+n) - psi(A)|) / h, or c / p in AR mode)."""
+    c, cp, f, fp = _rows_w(counts, prior)
+    out, op = _f64(np.zeros(2))
+    g, gp = _f64(np.zeros(c.shape)) if want_grad else (None, None)
+    assert lib().oracle_dm_prior_mass_w_f64(cp, fp, c.shape[0], c.shape[1], h_signed, eps, int(train_ar), op, gp, nthreads) == 0
+    return out, g
+
+
+def dm_item_w(x, c):
+    """(lgamma(x + c) - lgamma(x), psi(x + c) - psi(x)) as the width-generic oracle evaluates them."""
+    d, dp = _f64(np.zeros(1))
+    p, pp = _f64(np.zeros(1))
+    lib().oracle_dm_item_w(float(x), float(c), dp, pp)
+    return float(d[0]), float(p[0])

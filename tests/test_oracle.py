@@ -6,7 +6,7 @@ from scipy.special import loggamma
 
 import bear_oracle as o
 import c_oracle as co
-from util import edge_table, prior_rows, sparse_table
+from util import PRIOR_KINDS, edge_table, edge_table_wide, prior_rows, prior_rows_wide, sparse_table
 
 
 def test_dataloader_golden_first_batch(ysd1):
@@ -146,3 +146,75 @@ def test_one_hot_and_linear():
     assert np.allclose(f.sum(-1), 1.0)
     z = mat[0, 0] + mat[1, 1] + mat[2, 4]
     assert np.allclose(f[0], np.exp(z) / np.exp(z).sum())
+
+
+# ---- the width-generic oracle (oracle_dm_prior_w_f64): what the wide kernels are held to
+H_GRID = (-20.0, -6.0, -3.0, 0.0, 0.37, 2.5, 6.0, 10.0)      # the h_signed values of tests/test_wide_kernels_gpu.py
+
+
+@pytest.mark.parametrize("train_ar", [False, True])
+def test_oracle_w_matches_numpy_at_21(train_ar):
+    from test_prot_cpu import make_prot_table
+    _, counts = make_prot_table(seed=5, n=1037)
+    c = counts[0]
+    # (one-hot and unnormalised rows put cells of 1e5 .. 3e6 on concentrations near eps, where SciPy's gammaln difference itself is
+    # off by ~1.5e-13 of the sum: those are held to mpmath item by item, below)
+    for kind in ("softmax", "tiny"):
+        f = prior_rows_wide(len(c), 21, kind, seed=3)
+        want = o.bear_net_step(c, f, 0.37, train_ar=train_ar)
+        out, g = co.dm_prior_w(c, f, 0.37, train_ar=train_ar, want_grad=True, nthreads=3)
+        mass, gmass = co.dm_prior_mass_w(c, f, 0.37, train_ar=train_ar, want_grad=True)
+        assert abs(out[0] - want["ll"]) <= 1e-13 * abs(want["ll"]), kind
+        if train_ar:
+            assert out[1] == 0.0 and mass[0] == 0.0
+            np.testing.assert_allclose(g, want["d_prior"], rtol=1e-13, atol=0)
+        else:
+            assert abs(out[1] - want["d_h_signed"]) <= 1e-13 * mass[0], kind
+            assert (np.abs(g - want["d_prior"]) <= 1e-13 * gmass).all(), kind
+        # the thread count changes the order of the sum only
+        out1, g1 = co.dm_prior_w(c, f, 0.37, train_ar=train_ar, want_grad=True, nthreads=1)
+        assert np.allclose(out1, out, rtol=1e-15, atol=1e-15 * mass[0]) and np.array_equal(g1, g)
+
+
+@pytest.mark.parametrize("train_ar", [False, True])
+def test_oracle_w_matches_c_oracle_at_5(train_ar, ysd1):
+    _, counts = ysd1
+    for c in (counts[:, 0].astype(np.uint32), edge_table(), sparse_table(3001, 4)[0]):
+        f = prior_rows(len(c), 5)
+        for h_s in (-3.0, -0.4, 2.5):
+            want, wg = co.dm_prior(c, f, h_s, train_ar=train_ar, want_grad=True, nthreads=2)
+            got, g = co.dm_prior_w(c, f, h_s, train_ar=train_ar, want_grad=True, nthreads=2)
+            mass, gmass = co.dm_prior_mass_w(c, f, h_s, train_ar=train_ar, want_grad=True, nthreads=2)
+            assert abs(got[0] - want[0]) <= 1e-14 * abs(want[0])
+            assert abs(got[1] - want[1]) <= 1e-14 * mass[0]
+            assert (np.abs(g - wg) <= 1e-14 * gmass).all()
+
+
+def _item_sample():
+    """~200 (x, c) pairs of the GPU tests' own edges: concentrations f / h + eps of every prior kind over the h_signed grid, with
+    cells and row totals of the edge tables (counts 1 .. 2^32 - 1, row totals above 2^32)."""
+    rng = np.random.default_rng(17)
+    t = edge_table_wide(21)
+    cells = np.unique(np.r_[t[t > 0], t.sum(1, dtype=np.uint64)[t.sum(1) > 0].astype(np.float64), 64, 65, 66])
+    fs = np.concatenate([prior_rows_wide(8, 21, k, seed=2).ravel() for k in PRIOR_KINDS])
+    pairs = []
+    for h_s in H_GRID:
+        h = np.exp(h_s)
+        x = fs[rng.integers(0, fs.size, 25)] / h + 1e-7
+        x[:3] = [1e-7, 21 / h + 21e-7, 3.0 / h + 1e-7]                # an empty cell, a row total A, a scaled row's largest cell
+        pairs += list(zip(x, rng.choice(cells, x.size)))
+    return pairs
+
+
+def test_oracle_w_items_match_mpmath():
+    mp = pytest.importorskip("mpmath")
+    mp.mp.dps = 40
+    pairs = _item_sample()
+    assert len(pairs) >= 200
+    for x, c in pairs:
+        D, P = co.dm_item_w(x, c)
+        X, C = mp.mpf(float(x)), mp.mpf(float(c))
+        wD = mp.loggamma(X + C) - mp.loggamma(X)
+        wP = mp.digamma(X + C) - mp.digamma(X)
+        assert abs(D - float(wD)) <= 1e-14 * abs(float(wD)), (x, c, D, float(wD))
+        assert abs(P - float(wP)) <= 1e-14 * abs(float(wP)), (x, c, P, float(wP))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import bear_oracle as o
+import c_oracle as co
 from bear_amd import _lib, _train, ar_funcs, bear_net, bear_ref, core, dataloader, kernels
 from conftest import ROOT, YSD1
 from test_prot_cpu import make_prot_table, write_prot_tsv
@@ -84,6 +85,10 @@ def test_dm_prior_wide_matches_oracle(table, train_ar, want_grad):
         g = grad.cpu().numpy()
         assert g.shape == c.shape
         assert np.abs(g - want["d_prior"]).max() <= 2e-13 * np.abs(want["d_prior"]).sum()
+        # and every entry within 1e-12 of its own mass (AR mode: relative), against the width-generic C oracle
+        _, wg = co.dm_prior_w(c, f, h_signed, train_ar=train_ar, want_grad=True)
+        _, gm = co.dm_prior_mass_w(c, f, h_signed, train_ar=train_ar, want_grad=True)
+        assert (np.abs(g - wg) <= 1e-12 * (np.abs(wg) if train_ar else gm)).all()
         assert (g[c.sum(1) == 0] == 0).all()
     else:
         assert grad is None

@@ -44,3 +44,87 @@ def edge_table(seed=0):
     ]
     extra = rng.integers(0, 40, size=(48, 5))
     return np.asarray(rows + extra.tolist(), dtype=np.uint32)
+
+
+U32_MAX = 4294967295
+
+
+def edge_table_wide(W, seed=0):
+    """Count rows of width W that force every branch of the wide kernels: no counts; one count in the first and in the last letter
+    (the top bit of the non-zero mask); every cell 1; every cell 2^32 - 1 (a row total above 2^32); cells at the product / Stirling
+    switch (16, 17) and above it (24, 25); cells of 1e5 to 3e6; random sparse and dense fills."""
+    rng = np.random.default_rng(seed)
+    z = np.zeros(W, np.int64)
+
+    def one(b, v):
+        r = z.copy()
+        r[b] = v
+        return r
+
+    rows = [z, one(0, 1), one(W - 1, 1), np.ones(W, np.int64), np.full(W, U32_MAX), one(W - 1, U32_MAX), one(0, U32_MAX)]
+    for v in (16, 17, 24, 25):
+        rows += [np.full(W, v), one(v % W, v), one(W - 1, v)]
+    rows.append(np.resize([16, 17, 24, 25, 0], W))
+    rows.append(np.resize([0, 25, 1, 16, 24, 17], W))
+    rows.append(rng.integers(100_000, 3_000_001, W))
+    rows.append(np.where(rng.random(W) < 0.3, rng.integers(100_000, 3_000_001, W), 0))
+    r = z.copy()
+    r[W - 1], r[0] = U32_MAX, 1
+    rows.append(r)
+    for _ in range(12):                                           # random fill: sparse, dense, mixed magnitudes
+        p = rng.choice([0.1, 0.5, 1.0])
+        v = rng.integers(1, rng.choice([3, 40, 1000]), W)
+        rows.append(np.where(rng.random(W) < p, v, 0))
+    return np.asarray(rows, dtype=np.uint32)
+
+
+PRIOR_KINDS = ("softmax", "onehot", "tiny", "scaled")
+
+
+def prior_rows_wide(n, W, kind, seed=0):
+    """Prior rows [n, W]: 'softmax' (normalised, spread over ~3 orders of magnitude), 'onehot' (one cell 1, the others exactly 0),
+    'tiny' (softmax rows with cells of 1e-300 and 5e-324, the smallest subnormal), 'scaled' (softmax rows times 0.5 .. 3: not
+    normalised)."""
+    rng = np.random.default_rng(seed + 7919)
+    z = rng.normal(size=(n, W)) * 2.0
+    f = np.exp(z - z.max(1, keepdims=True))
+    f /= f.sum(1, keepdims=True)
+    if kind == "softmax":
+        return f
+    if kind == "onehot":
+        f = np.zeros((n, W))
+        hot = rng.integers(0, W, n)
+        hot[:2] = [0, W - 1][:n]
+        f[np.arange(n), hot] = 1.0
+        return f
+    if kind == "tiny":
+        u = rng.random((n, W))
+        f[u < 0.15] = 1e-300
+        f[u > 0.85] = 5e-324
+        return f
+    if kind == "scaled":
+        return f * rng.uniform(0.5, 3.0, (n, 1))
+    raise ValueError(kind)
+
+
+def tile_rows(table, n, seed=0):
+    """n rows drawn from ``table``: every row of it first (in a seeded order), then repeats -- so that the edge rows land in every
+    position of a tile."""
+    rng = np.random.default_rng(seed)
+    idx = np.r_[rng.permutation(len(table)), rng.integers(0, len(table), max(0, n - len(table)))][:n]
+    return np.ascontiguousarray(table[idx])
+
+
+def wide_scale_table(n, W, dense=False, seed=0):
+    """A large seeded count table of width W (vectorised: no k-mer strings).  Sparse: ~15 % non-zero cells of Poisson counts, a
+    few rows with counts of 1e5 .. 3e6, ~4 % empty rows; dense: every cell non-zero, counts up to ~3e4."""
+    rng = np.random.default_rng(seed)
+    lam = rng.uniform(0.5, 40.0, (n, 1))
+    if dense:
+        c = rng.poisson(lam * rng.uniform(1.0, 800.0, (n, 1)), (n, W)) + 1
+    else:
+        c = np.where(rng.random((n, W)) < 0.15, rng.poisson(lam, (n, W)), 0)
+        big = rng.choice(n, max(1, n // 5000), replace=False)
+        c[big, rng.integers(0, W, big.size)] = rng.integers(100_000, 3_000_000, big.size)
+        c[rng.choice(n, max(1, n // 24), replace=False)] = 0
+    return c.astype(np.uint32)
