@@ -23,7 +23,7 @@ def _deterministic_requested():
 # parameter gradients over per call; BEAR_AMD_LIB: developer A/B builds.
 LIB_PATH = os.environ.get("BEAR_AMD_LIB") or os.path.join(_HERE, "libbear_hip_det.so" if _deterministic_requested() else "libbear_hip.so")
 
-ABI_VERSION = 7   # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
+ABI_VERSION = 8   # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
 
 SYMBOLS = [
     "bear_abi_version", "bear_strerror", "bear_last_hip_error", "bear_ws_create", "bear_ws_destroy",
@@ -40,6 +40,7 @@ SYMBOLS = [
     "bear_plan_count_total", "bear_plan_set_count_bound", "bear_deterministic_build", "bear_plan_cnn_window_rows",
     "bear_plan_create_auto",
     "bear_dm_prior_wide_f64", "bear_eval_wide_f64", "bear_parse_counts_tsv_wide", "bear_parse_counts_tsv_shard_wide",
+    "bear_logdir_sample_wide_f64",
 ]
 
 
@@ -163,6 +164,7 @@ def _load():
     L.bear_parse_counts_tsv_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, u64, vp, vp, ctypes.POINTER(u64)]
     L.bear_parse_counts_tsv_shard_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, u64, u64, u64, u64, cint, cint, u64, vp, vp,
                                                    ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.bear_logdir_sample_wide_f64.argtypes = [vp, vp, u64, cint, vp, cint, cint, vp, cint, cint, cint, u64, u64, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name in ("bear_plan_bytes", "bear_shuffle_source_row", "bear_eval_plan_bytes"):

@@ -1875,9 +1875,10 @@ int bear_log_gamma_f64(const double *conc, uint64_t n, uint64_t n_samples, uint6
   return BEAR_OK;
 }
 
-int bear_logdir_sample_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, const double *h, int n_h,
-                           int with_ar, const double *van, int n_van, int mc_samples, int map, uint64_t seed,
-                           uint64_t row_base, double *out, void *stream) {
+// bear_logdir_sample_f64 and its width-taking twin: rows of `width` letters (5 or 21)
+static int logdir_sample_launch(const uint32_t *counts, const double *prior, uint64_t n_rows, int width, const double *h,
+                                int n_h, int with_ar, const double *van, int n_van, int mc_samples, int map, uint64_t seed,
+                                uint64_t row_base, double *out, void *stream) {
   if (n_h < 0 || n_van < 0 || n_h + n_van > SMP_MAX_MODELS || (n_h && !h) || (n_van && !van)) return BEAR_ERR_INVALID_ARG;
   if (with_ar && !map) return BEAR_ERR_INVALID_ARG;   // the AR model enters only the MAP table (get_var_probs.py:150-153)
   if (map) mc_samples = 1;                            // get_var_probs.py:131-132
@@ -1902,13 +1903,30 @@ int bear_logdir_sample_f64(const uint32_t *counts, const double *prior, uint64_t
   }
   for (int k = 0; k < n_van; ++k) A.w[n_h + k] = van[k];
   const uint64_t per_row = (uint64_t)M * (uint64_t)mc_samples;
-  if (per_row > 0xffffffffull || n_rows > (~0ull) / (5 * per_row)) return BEAR_ERR_INVALID_ARG;
+  if (per_row > 0xffffffffull || n_rows > (~0ull) / ((uint64_t)width * per_row)) return BEAR_ERR_INVALID_ARG;
   uint64_t blocks = (n_rows * per_row + SMP_THREADS - 1) / SMP_THREADS;
   if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(logdir_sample_kernel, dim3((unsigned)blocks), dim3(SMP_THREADS), 0, static_cast<hipStream_t>(stream), counts,
-                     prior, n_rows, A, out);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (width == 21)
+    hipLaunchKernelGGL(logdir_sample_kernel<21>, dim3((unsigned)blocks), dim3(SMP_THREADS), 0, s, counts, prior, n_rows, A, out);
+  else
+    hipLaunchKernelGGL(logdir_sample_kernel<5>, dim3((unsigned)blocks), dim3(SMP_THREADS), 0, s, counts, prior, n_rows, A, out);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
+}
+
+int bear_logdir_sample_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, const double *h, int n_h,
+                           int with_ar, const double *van, int n_van, int mc_samples, int map, uint64_t seed,
+                           uint64_t row_base, double *out, void *stream) {
+  return logdir_sample_launch(counts, prior, n_rows, 5, h, n_h, with_ar, van, n_van, mc_samples, map, seed, row_base, out, stream);
+}
+
+int bear_logdir_sample_wide_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, int width, const double *h,
+                                int n_h, int with_ar, const double *van, int n_van, int mc_samples, int map, uint64_t seed,
+                                uint64_t row_base, double *out, void *stream) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  return logdir_sample_launch(counts, prior, n_rows, width, h, n_h, with_ar, van, n_van, mc_samples, map, seed, row_base, out,
+                              stream);
 }
 
 int bear_shuffle_rows(const void *src, void *dst, uint64_t n_rows, uint32_t row_bytes, uint64_t seed, void *stream) {

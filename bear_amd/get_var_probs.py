@@ -5,7 +5,8 @@ Same functions and argument meaning as the reference: ``get_pdf`` (get_var_probs
 (:58-82), ``load_ds`` (:36-56).  The numerical part of ``get_pdf`` -- concentrations of every model, the
 log-Gamma draws of ``log_gamma.log_gamma`` and their normalisation, or the MAP table -- is one launch of
 ``bear_logdir_sample_f64`` over the batch of k-mers (``kernels_sample.h``); the exact marginal term
-(``get_marg``) is one launch of ``bear_eval_f64``.  The k+1-mer bookkeeping stays on the host as in the
+(``get_marg``) is one launch of ``bear_eval_f64``.  The protein alphabet (rows of 21: 20 letters + stop) takes their
+width-taking twins, ``bear_logdir_sample_wide_f64`` and ``bear_eval_wide_f64``.  The k+1-mer bookkeeping stays on the host as in the
 reference (string windows, a lookup table indexed by k+1-mer).
 
 Differences a user can see: draws come from a counter-based stream (``seed`` argument; ``None`` takes a fresh
@@ -115,8 +116,9 @@ def get_pdf(kmers, counts, h, ar_func, mc_samples, vans, train_col, alphabet_nam
     assert not (get_marg and output != "func"), "not implemented"
     alphabet = core.alphabets_en[alphabet_name]
     A1 = len(alphabet)
-    if A1 != 5:
-        raise NotImplementedError("the HIP kernels are built for 4-letter alphabets (+ stop): dna / rna")
+    if A1 not in kernels.WIDE_WIDTHS:
+        raise NotImplementedError("the HIP kernels are built for 4-letter alphabets (+ stop): dna / rna, "
+                                  "and for the protein alphabet (20 letters + stop)")
     if get_map or get_marg:
         mc_samples = 1
     device = _device()
@@ -145,15 +147,17 @@ def get_pdf(kmers, counts, h, ar_func, mc_samples, vans, train_col, alphabet_nam
         def prob_func(q_kmers, q_counts):
             idx = torch.as_tensor([table_index[str(k)] for k in q_kmers], dtype=torch.long, device=device)
             q = torch.as_tensor(np.asarray(q_counts), dtype=torch.int64).reshape(len(idx), A1).to(torch.int32).to(device)
-            out = kernels.evaluate(q.contiguous(), prior[idx].contiguous() if prior is not None else None,
-                                   hs if hs.size else None, vans if vans.size else None, col_dev[idx].contiguous(),
-                                   eps=0.0, with_ar=False).cpu().numpy()
+            evaluate = kernels.evaluate if A1 == 5 else kernels.evaluate_wide
+            out = evaluate(q.contiguous(), prior[idx].contiguous() if prior is not None else None,
+                           hs if hs.size else None, vans if vans.size else None, col_dev[idx].contiguous(),
+                           eps=0.0, with_ar=False).cpu().numpy()
             return np.concatenate([out[:hs.size], out[hs.size + 1:hs.size + 1 + vans.size]])
         return prob_func
 
     if K:
-        log_probs = kernels.logdir_sample(col_dev, prior, hs, vans, mc_samples, get_map=get_map, with_ar=with_ar,
-                                          seed=_next_seed() if seed is None else seed, row_base=row_base).cpu().numpy()
+        sample = kernels.logdir_sample if A1 == 5 else kernels.logdir_sample_wide
+        log_probs = sample(col_dev, prior, hs, vans, mc_samples, get_map=get_map, with_ar=with_ar,
+                           seed=_next_seed() if seed is None else seed, row_base=row_base).cpu().numpy()
     else:
         log_probs = np.zeros((0, A1, num_models, mc_samples))
     if output == "numpy":

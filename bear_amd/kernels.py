@@ -608,6 +608,36 @@ def logdir_sample(counts, prior, h, vans, mc_samples, get_map=False, with_ar=Fal
     return out
 
 
+def logdir_sample_wide(counts, prior, h, vans, mc_samples, get_map=False, with_ar=False, seed=0, row_base=0, n_rows=None,
+                       device=None, width=None):
+    """``bear_logdir_sample_wide_f64``: ``logdir_sample`` for rows of width W in ``WIDE_WIDTHS`` (21: the protein alphabet) ->
+    [n_rows, W, n_models, mc_samples]; the draw of a cell is keyed by ``(row_base + row) * W + letter``.  W is the width of the
+    rows, or ``width`` when both ``counts`` and ``prior`` are None (unseen k-mers, vanilla models only)."""
+    if counts is not None:
+        counts = _check_rows_wide(counts, torch.int32, "counts", width)
+        n, device, width = counts.shape[0], counts.device, counts.shape[1]
+    if prior is not None:
+        prior = _check_rows_wide(prior, torch.float64, "prior", width)
+        if counts is not None and prior.shape[0] != n:
+            raise ValueError("counts and prior must have the same number of rows")
+        n, device, width = prior.shape[0], prior.device, prior.shape[1]
+    if counts is None and prior is None:
+        if width not in WIDE_WIDTHS:
+            raise ValueError(f"width {width}: the wide kernels take {WIDE_WIDTHS}")
+        n, device = int(n_rows), torch.device(device or "cuda")
+    hs, hp = _host_f64(h) if h is not None and np.size(h) else (np.zeros(0), ctypes.c_void_p(0))
+    vs, vp = _host_f64(vans) if vans is not None and np.size(vans) else (np.zeros(0), ctypes.c_void_p(0))
+    mc = 1 if get_map else int(mc_samples)
+    M = int(bool(with_ar)) + hs.size + vs.size
+    out = torch.empty((n, width, M, mc), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        st = _lib.lib().bear_logdir_sample_wide_f64(_ptr(counts), _ptr(prior), n, int(width), hp, hs.size, int(bool(with_ar)), vp,
+                                                    vs.size, mc, int(bool(get_map)), int(seed) & (2 ** 64 - 1), int(row_base),
+                                                    _ptr(out), _stream())
+    _lib.check(st, "bear_logdir_sample_wide_f64")
+    return out
+
+
 def shuffle_rows(src, seed):
     """One launch of ``bear_shuffle_rows``: a new tensor with ``dst[i] = src[perm_seed(i)]`` along dim 0."""
     if not (src.is_cuda and src.is_contiguous() and src.dim() >= 1):

@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define BEAR_ABI_VERSION 7 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein) */
+#define BEAR_ABI_VERSION 8 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
+                              8: + bear_logdir_sample_wide_f64 */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -501,11 +502,19 @@ int bear_dm_items_f64(bear_ws *ws, const double *x, const uint32_t *c, uint64_t 
  *   out [dev] double [n_rows, 5, n_models, mc_samples]  normalised log transition probabilities
  *   a draw is a pure function of (seed, model, sample, row_base + row, letter): any sharding of the rows
  *   reproduces the same table.
+ *
+ * bear_logdir_sample_wide_f64: bear_logdir_sample_f64 for rows of `width` letters (21: the protein alphabet; 5 gives
+ *   bear_logdir_sample_f64's output bit for bit) -- the same arguments, limits and model order; counts, prior [n_rows, width],
+ *   out [n_rows, width, n_models, mc_samples]; the draw of a cell is keyed by (seed, model, sample, (row_base + row) * width +
+ *   letter).  Any other width is BEAR_ERR_INVALID_ARG.
  */
 int bear_log_gamma_f64(const double *conc, uint64_t n, uint64_t n_samples, uint64_t seed, double *out, void *stream);
 int bear_logdir_sample_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, const double *h, int n_h,
                            int with_ar, const double *van, int n_van, int mc_samples, int map, uint64_t seed,
                            uint64_t row_base, double *out, void *stream);
+int bear_logdir_sample_wide_f64(const uint32_t *counts, const double *prior, uint64_t n_rows, int width, const double *h,
+                                int n_h, int with_ar, const double *van, int n_van, int mc_samples, int map, uint64_t seed,
+                                uint64_t row_base, double *out, void *stream);
 
 /*
  * Synthetic "k=13 sparse" count table for measurement: rows
