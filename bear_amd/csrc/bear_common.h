@@ -14,7 +14,7 @@
 #define BEAR_ROWS_PER_THREAD (BEAR_TILE_ROWS / BEAR_THREADS)
 #define BEAR_MAX_OUT 4
 
-static thread_local int g_last_hip_error = 0;
+extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // one per thread for the whole library (bear_hip.hip): bear_last_hip_error()
 
 #define HIP_TRY(expr)                      \
   do {                                     \
@@ -133,7 +133,7 @@ __device__ __forceinline__ void block_store_partials(double (&acc)[NOUT], double
 #define BEAR_THETA_NET 1   // theta = {h_signed, ...}                      (bear_net.py:43)
 #define BEAR_THETA_REF 2   // theta = {h_signed, tau_signed, net_weight_signed}  (bear_ref.py:45-47, 106)
 // The arrival word of a workspace and the stamp of THIS launch.  The word is `epoch << 24 | blocks arrived`, zero between
-// launches; every launch is handed the next epoch by the host (ws_arrival, bear_hip.hip).  A block first raises the word to its
+// launches; every launch is handed the next epoch by the host (ws_arrival, bear_host.h).  A block first raises the word to its
 // own stamp (atomic max: a count left behind by an EARLIER launch -- one that faulted half way, or that overlapped on this
 // workspace -- is discarded there instead of silently breaking the last-block detection of every later launch), then counts
 // itself in: two one-way atomics per block, no retry loop (a compare-and-swap loop over 256 blocks that finish together cost
@@ -317,23 +317,3 @@ __device__ __forceinline__ void block_finish(double (&acc)[NOUT], double *partia
     bear_apply_in_block(apply, io.out);
   }
 }
-
-// ------------------------------------------------------------------ finalize: fixed-order sum of block partials
-__global__ __launch_bounds__(256) void finalize_kernel(const double *__restrict__ partials, int n_blocks,
-                                                       int n_out, double *__restrict__ out) {
-  __shared__ double red[4][BEAR_MAX_OUT];
-  double acc[BEAR_MAX_OUT] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < n_blocks; b += 256)
-#pragma unroll
-    for (int k = 0; k < BEAR_MAX_OUT; ++k)
-      if (k < n_out) acc[k] += partials[(size_t)b * BEAR_MAX_OUT + k];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < BEAR_MAX_OUT; ++k) {
-    double v = bear_wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < n_out) out[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-

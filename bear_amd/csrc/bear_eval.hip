@@ -1,0 +1,318 @@
+// bear_eval.hip -- held-out evaluation and the BMM marginal (kernels_eval.h), their 21-wide forms and the wide DM step
+// (kernels_wide.h), evaluation on a sorted plan of the test column (kernels_evalplan.h).  The other units: bear_host.h.
+#include "bear_host.h"
+#include "kernels_eval.h"
+#include "kernels_wide.h"
+#include "kernels_evalplan.h"
+
+#ifdef EVP_STAMPS
+#define EVP_DBG_ARG , ws->dbg
+#else
+#define EVP_DBG_ARG
+#endif
+
+int eval_ws_setup(bear_ws *ws) {
+  const int st = allow_dynamic_lds({BEAR_KFN(eval_plan_kernel<0, 4>), BEAR_KFN(eval_plan_kernel<1, 0>), BEAR_KFN(eval_plan_kernel<1, 4>),
+                                    BEAR_KFN(eval_plan_kernel<4, 0>)},
+                                   sizeof(evp_lds));
+  if (st != BEAR_OK) return st;
+  HIP_TRY(hipMalloc(&ws->eval_partials, sizeof(double) * EVL_MAX_OUT * (size_t)ws->eval_blocks));
+  HIP_TRY(hipMalloc(&ws->eval_out, sizeof(double) * EVL_MAX_OUT));
+  return BEAR_OK;
+}
+
+// Where the compact sums of one launch -- the DM models [m0, m0 + m_cnt), m_cnt <= EVS_CHUNK, and with the first chunk the AR model
+// and the total length -- go in the result vector: ll_ear[n_h], ll_arm, ll_van[n_van], cor_ear[n_h], cor_arm, cor_van[n_van], total
+static evs_slots eval_chunk_slots(const evl_args &A, int m0, int m_cnt) {
+  const int n_models = A.n_h + A.n_van;
+  evs_slots S;
+  for (int k = 0; k < EVS_NOUT; ++k) S.slot[k] = -1;
+  for (int k = 0; k < m_cnt; ++k) {
+    const int m = m0 + k;
+    const int ll_slot = m < A.n_h ? m : m + 1;                 // ll_arm sits between the BEAR and vanilla blocks
+    S.slot[k] = ll_slot;
+    S.slot[EVS_CHUNK + k] = n_models + 1 + ll_slot;
+  }
+  if (m0 == 0) {
+    S.slot[2 * EVS_CHUNK] = A.n_h;
+    S.slot[2 * EVS_CHUNK + 1] = n_models + 1 + A.n_h;
+    S.slot[2 * EVS_CHUNK + 2] = 2 * n_models + 2;
+  }
+  return S;
+}
+
+static int launch_eval(bear_ws *ws, const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows,
+                       const evl_args &A, double *out, hipStream_t s) {
+  // sorted formulation (kernels_eval.h): at most EVS_CHUNK DM models per launch; the first launch also carries the AR
+  // model and the total length (eval_chunk_slots)
+  const int n_models = A.n_h + A.n_van;
+  const int grid = grid_capped((n_rows + EVS_THREADS - 1) / EVS_THREADS, (uint64_t)ws->eval_blocks);
+  static_assert(EVS_NOUT <= EVL_MAX_OUT, "compact partials fit the evaluation partial buffer");
+  for (int m0 = 0; m0 == 0 || m0 < n_models; m0 += EVS_CHUNK) {
+    const int m_cnt = n_models - m0 < EVS_CHUNK ? n_models - m0 : EVS_CHUNK;
+    const int common = m0 == 0;
+    const evs_slots S = eval_chunk_slots(A, m0, m_cnt);
+    hipLaunchKernelGGL(eval_sorted_kernel, dim3(grid), dim3(EVS_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common,
+                       reinterpret_cast<const double2 *>(ws->logtab), ws->eval_partials);
+    hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
+  }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+static int eval_make_args(const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h,
+                          int with_ar, const double *van_reg, int n_van, double eps, uint64_t noise_seed, uint64_t row_base,
+                          const double *out, evl_args *Aout) {
+  if (!out || n_h < 0 || n_van < 0 || n_h + n_van > EVL_MAX_MODELS || (n_h && !h) || (n_van && !van_reg))
+    return BEAR_ERR_INVALID_ARG;
+  if ((n_h || with_ar) && !prior && n_rows) return BEAR_ERR_INVALID_ARG;
+  if (n_rows && !test) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(test) || misaligned(train) || misaligned(prior)) return BEAR_ERR_INVALID_ARG;
+  if (!(eps >= 0.0)) return BEAR_ERR_INVALID_ARG;
+  evl_args &A = *Aout;
+  memset(&A, 0, sizeof(A));
+  A.n_h = n_h;
+  A.n_van = n_van;
+  A.arm = with_ar ? 1 : 0;
+  A.has_train = train ? 1 : 0;
+  A.has_prior = prior ? 1 : 0;
+  A.eps = eps;
+  A.seed = noise_seed;
+  A.row_base = row_base;
+  for (int j = 0; j < n_h; ++j) {
+    if (!(h[j] > 0.0)) return BEAR_ERR_INVALID_ARG;
+    A.inv_h[j] = 1.0 / h[j];
+  }
+  for (int k = 0; k < n_van; ++k) A.inv_h[n_h + k] = van_reg[k];
+  return BEAR_OK;
+}
+
+int bear_eval_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows,
+                  const double *h, int n_h, int with_ar, const double *van_reg, int n_van, double eps,
+                  uint64_t noise_seed, uint64_t row_base, double *out, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  evl_args A;
+  st = eval_make_args(test, train, prior, n_rows, h, n_h, with_ar, van_reg, n_van, eps, noise_seed, row_base, out, &A);
+  if (st != BEAR_OK) return st;
+  return launch_eval(ws, test, train, prior, n_rows, A, out, static_cast<hipStream_t>(stream));
+}
+
+
+int bear_dm_prior_wide_f64(bear_ws *ws, const uint32_t *counts, const double *prior, uint64_t n_rows, int width,
+                           const double *h_signed_dev, double eps, int train_ar, double *out, double *grad_prior, void *stream) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!out || (n_rows && (!counts || !prior)) || (!h_signed_dev && !train_ar)) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(counts) || misaligned(prior) || misaligned(grad_prior) || misaligned8(out) || misaligned8(h_signed_dev))
+    return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  bear_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.inv_h = 1.0;           // (AR mode without h_signed_dev: never read)
+  prm.eps = eps;
+  const uint64_t tile = (uint64_t)(width == 21 ? WIDE_TILE(21) : WIDE_TILE(5));
+  const int grid = grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, WIDE_BLOCKS_PER_CU));
+  const bear_step_io io = ws_io(ws, h_signed_dev, BEAR_THETA_NET, out);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+#define WIDE_LAUNCH(W, AR, GRAD) \
+  hipLaunchKernelGGL((dm_wide_kernel<W, AR, GRAD>), dim3(grid), dim3(WIDE_THREADS), 0, s, counts, prior, n_rows, prm, grad_prior, lt, ws->partials, io)
+#define WIDE_LAUNCH_21(AR, GRAD) WIDE_LAUNCH(21, AR, GRAD)
+#define WIDE_LAUNCH_5(AR, GRAD) WIDE_LAUNCH(5, AR, GRAD)
+  if (width == 21) BEAR_DISPATCH_2(train_ar, grad_prior, WIDE_LAUNCH_21);
+  else BEAR_DISPATCH_2(train_ar, grad_prior, WIDE_LAUNCH_5);
+#undef WIDE_LAUNCH_5
+#undef WIDE_LAUNCH_21
+#undef WIDE_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows, int width,
+                       const double *h, int n_h, int with_ar, const double *van_reg, int n_van, double eps,
+                       uint64_t noise_seed, uint64_t row_base, double *out, void *stream) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  evl_args A;
+  st = eval_make_args(test, train, prior, n_rows, h, n_h, with_ar, van_reg, n_van, eps, noise_seed, row_base, out, &A);
+  if (st != BEAR_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // launch_eval's chunks of models and slot layout
+  const int n_models = A.n_h + A.n_van;
+  const int grid = grid_capped((n_rows + EVW_THREADS - 1) / EVW_THREADS, (uint64_t)ws->eval_blocks);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+  for (int m0 = 0; m0 == 0 || m0 < n_models; m0 += EVS_CHUNK) {
+    const int m_cnt = n_models - m0 < EVS_CHUNK ? n_models - m0 : EVS_CHUNK;
+    const int common = m0 == 0;
+    const evs_slots S = eval_chunk_slots(A, m0, m_cnt);
+    if (width == 21)
+      hipLaunchKernelGGL(eval_wide_kernel<21>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common, lt,
+                         ws->eval_partials);
+    else
+      hipLaunchKernelGGL(eval_wide_kernel<5>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common, lt,
+                         ws->eval_partials);
+    hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
+  }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// ---- evaluation on a sorted plan of the test column (kernels_evalplan.h) ------------------------------------------------
+struct bear_eval_plan {
+  int device;
+  uint64_t n_rows, n_tiles;
+  const uint32_t *test, *train;  // the buffers the plan was built from (identity check only; train may be NULL)
+  uint16_t *items;       // [n_tiles][EVP_ITEMS_CAP]
+  uint2 *tile_info;      // [n_tiles]
+  unsigned long long *consts;   // [EVP_NCONST]: what the vanilla models, the total length need of the table as a whole (kernels_evalplan.h, EVP_C_*)
+  uint64_t bytes;
+};
+
+int bear_eval_plan_create(bear_ws *ws, const uint32_t *test, const uint32_t *train, uint64_t n_rows, bear_eval_plan **out, void *stream) {
+  if (!out) return BEAR_ERR_INVALID_ARG;
+  *out = nullptr;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if ((n_rows && !test) || misaligned(test) || misaligned(train)) return BEAR_ERR_INVALID_ARG;
+  bear_eval_plan *p = new (std::nothrow) bear_eval_plan();
+  if (!p) return BEAR_ERR_NOMEM;
+  memset(p, 0, sizeof(*p));
+  p->device = ws->device;
+  p->n_rows = n_rows;
+  p->test = test;
+  p->train = train;
+  p->n_tiles = (n_rows + EVP_ROWS - 1) / EVP_ROWS;
+  if (p->n_tiles) {
+    // + 1 KiB: the last DMA piece of a tile's lists may be issued for a partial KiB
+    const size_t ibytes = sizeof(uint16_t) * EVP_ITEMS_CAP * (size_t)p->n_tiles + 1024;
+    hipError_t e = hipMalloc(&p->items, ibytes);
+    if (e == hipSuccess) e = hipMalloc(&p->tile_info, sizeof(uint2) * ((size_t)p->n_tiles + 2));
+    if (e == hipSuccess) e = hipMalloc(&p->consts, sizeof(unsigned long long) * EVP_NCONST);
+    if (e == hipSuccess) e = hipMemsetAsync(p->tile_info, 0, sizeof(uint2) * ((size_t)p->n_tiles + 2), static_cast<hipStream_t>(stream));
+    if (e == hipSuccess) e = hipMemsetAsync(p->consts, 0, sizeof(unsigned long long) * EVP_NCONST, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+      (void)hipFree(p->items);
+      (void)hipFree(p->tile_info);
+      (void)hipFree(p->consts);
+      delete p;
+      g_last_hip_error = (int)e;
+      return e == hipErrorOutOfMemory ? BEAR_ERR_NOMEM : BEAR_ERR_HIP;
+    }
+    const int grid = grid_capped(p->n_tiles, (uint64_t)ws->num_cu * 16);
+    hipLaunchKernelGGL(evp_build_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), test, train, n_rows, p->n_tiles,
+                       p->items, p->tile_info, p->consts);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+      (void)hipFree(p->items);
+      (void)hipFree(p->tile_info);
+      (void)hipFree(p->consts);
+      delete p;
+      g_last_hip_error = (int)e;
+      return BEAR_ERR_HIP;
+    }
+    p->bytes = ibytes + sizeof(uint2) * ((size_t)p->n_tiles + 2) + sizeof(unsigned long long) * EVP_NCONST;
+  }
+  *out = p;
+  return BEAR_OK;
+}
+
+int bear_eval_plan_destroy(bear_eval_plan *plan) {
+  if (!plan) return BEAR_OK;
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(plan->device);
+  (void)hipFree(plan->items);
+  (void)hipFree(plan->tile_info);
+  (void)hipFree(plan->consts);
+  (void)hipSetDevice(prev);
+  delete plan;
+  return BEAR_OK;
+}
+
+uint64_t bear_eval_plan_bytes(const bear_eval_plan *plan) { return plan ? plan->bytes : 0; }
+
+int bear_eval_plan_f64(bear_ws *ws, const bear_eval_plan *plan, const uint32_t *test, const uint32_t *train, const double *prior,
+                       uint64_t n_rows, const double *h, int n_h, int with_ar, const double *van_reg, int n_van, double eps,
+                       uint64_t noise_seed, uint64_t row_base, const uint32_t *row_ids, double *out, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!plan || plan->test != test || plan->train != train || plan->n_rows != n_rows || plan->device != ws->device)
+    return BEAR_ERR_INVALID_ARG;
+  if (misaligned(row_ids)) return BEAR_ERR_INVALID_ARG;
+  evl_args A;
+  st = eval_make_args(test, train, prior, n_rows, h, n_h, with_ar, van_reg, n_van, eps, noise_seed, row_base, out, &A);
+  if (st != BEAR_OK) return st;
+  A.has_rid = row_ids ? 1 : 0;
+  // The plan decides the vanilla models' arg-max on the INTEGER training counts (a letter a whole count below the top cannot win):
+  // that is the arg-max of count + van_reg + eps + noise only while 17.5 sigma = 1750 eps stays below a count and the sum keeps
+  // the counts apart (bear_eval_f64 takes any values).
+  if (A.n_van && !(1750.0 * eps < 0.5)) return BEAR_ERR_INVALID_ARG;
+  for (int k = 0; k < A.n_van; ++k)
+    if (!(van_reg[k] >= 0.0 && van_reg[k] <= 0x1p30)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n_models = A.n_h + A.n_van;
+  const uint64_t nt = plan->n_tiles;
+  const int grid = grid_capped(nt, (uint64_t)ws->num_cu);   // one resident 768-thread block per CU
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+  // launches: BEAR models (product path) four at a time, vanilla models (lgamma tables) four at a time -- a BEAR group and a
+  // vanilla group share a launch; the first launch also carries the AR model and the total length.
+  int h0 = 0, v0 = 0;
+  bool first = true;
+  while (first || h0 < A.n_h || v0 < A.n_van) {
+    const int nh = A.n_h - h0 < EVP_MAXH ? A.n_h - h0 : EVP_MAXH;
+    int nv = A.n_van - v0 < EVP_MAXV ? A.n_van - v0 : EVP_MAXV;
+    if (nh > 1) nv = 0;   // four BEAR models fill the register file (168 per lane at three waves per SIMD): the vanilla group follows
+    int common = first ? 1 : 0;
+    evs_slots S;
+    for (int k = 0; k < EVS_NOUT; ++k) S.slot[k] = -1;
+    for (int k = 0; k < nh; ++k) {            // output: ll_ear[n_h], ll_arm, ll_van[n_van], cor_ear[n_h], cor_arm, cor_van[n_van], total
+      S.slot[k] = h0 + k;
+      S.slot[EVS_CHUNK + k] = n_models + 1 + h0 + k;
+    }
+    for (int k = 0; k < nv; ++k) {
+      S.slot[EVP_SLOT_VAN + k] = A.n_h + 1 + v0 + k;
+      S.slot[EVS_CHUNK + EVP_SLOT_VAN + k] = n_models + 1 + A.n_h + 1 + v0 + k;
+    }
+    if (common) {
+      S.slot[2 * EVS_CHUNK] = A.n_h;
+      S.slot[2 * EVS_CHUNK + 1] = n_models + 1 + A.n_h;
+      S.slot[2 * EVS_CHUNK + 2] = 2 * n_models + 2;
+    }
+#define EVP_LAUNCH(NH_, NV_)                                                                                                        \
+  hipLaunchKernelGGL((eval_plan_kernel<NH_, NV_>), dim3(grid), dim3(EVP_THREADS), sizeof(evp_lds), s, test, train, prior, row_ids, n_rows, A, \
+                     h0, nh, v0, nv, common, plan->items, plan->tile_info, plan->consts, nt, lt, ws->eval_partials EVP_DBG_ARG)
+    if (nh == 0) EVP_LAUNCH(0, 4);
+    else if (nh == 1 && nv == 0) EVP_LAUNCH(1, 0);
+    else if (nh == 1) EVP_LAUNCH(1, 4);
+    else EVP_LAUNCH(4, 0);
+#undef EVP_LAUNCH
+    hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
+    h0 += nh;
+    v0 += nv;
+    first = false;
+  }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_bmm_f64(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, const double *alpha, int n_alpha, double *out,
+                 void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!out || !alpha || n_alpha <= 0 || n_alpha > EVL_MAX_MODELS || (n_rows && !counts) || misaligned(counts))
+    return BEAR_ERR_INVALID_ARG;
+  evl_args A;
+  memset(&A, 0, sizeof(A));
+  A.n_van = n_alpha;
+  for (int k = 0; k < n_alpha; ++k) {
+    if (!(alpha[k] > 0.0)) return BEAR_ERR_INVALID_ARG;
+    A.inv_h[k] = alpha[k];
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  st = launch_eval(ws, counts, nullptr, nullptr, n_rows, A, ws->eval_out, s);
+  if (st != BEAR_OK) return st;
+  // result vector layout: [ll_arm (unused), ll_van[n_alpha], ...]
+  HIP_TRY(hipMemcpyAsync(out, ws->eval_out + 1, sizeof(double) * (size_t)n_alpha, hipMemcpyDeviceToDevice, s));
+  return BEAR_OK;
+}

@@ -1,8 +1,13 @@
 // bear_levels.h -- internal: one prefix level of a k-mer-sorted batch (kernels_cnn.h, cnn_level_io), built in bear_count.hip
-// (rocPRIM scan) and owned by a plan (bear_hip.hip).
+// (rocPRIM scan) and owned by a plan (bear_host.h; attached and walked in bear_cnn.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+// the limits of the convolutional AR function (kernels_cnn.h) that size a plan's arrays of levels and window tables: here, so that
+// the units that hold a plan without launching that family's kernels need not include them
+#define CNN_MAX_LAG 21
+#define CNN_MAX_WIN 6             // window tables a launch may read (the positions the contexts themselves would evaluate)
 
 struct bear_level_dev {
   uint64_t n;                  // rows of this level: the distinct prefixes of `letters` letters of the rows below, in their order

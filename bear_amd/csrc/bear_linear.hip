@@ -1,0 +1,380 @@
+// bear_linear.hip -- the linear AR head: k-mer packing and index words, the paired context lists of a plan, the fused DM step
+// (kernels_linear.h), the head as rows (kernels_linrows.h), and the optimizer update as a launch of its own (adam_vec_kernel).
+// The other units: bear_host.h.
+#include "bear_host.h"
+#include "kernels_linear.h"
+#include "kernels_linrows.h"
+
+int linear_ws_setup(bear_ws *ws) {
+#define LIN_ALL_NGK(AR, PAIRED, DET)                                                                          \
+  BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 0>), BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 2>), \
+      BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 6>), BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 7>)
+  const int st = allow_dynamic_lds({LIN_ALL_NGK(false, false, false), LIN_ALL_NGK(true, false, false), LIN_ALL_NGK(false, true, false),
+                                    LIN_ALL_NGK(true, true, false), LIN_ALL_NGK(false, false, true), LIN_ALL_NGK(true, false, true),
+                                    LIN_ALL_NGK(false, true, true), LIN_ALL_NGK(true, true, true)},
+                                   sizeof(pln_lds_lin));
+#undef LIN_ALL_NGK
+  if (st != BEAR_OK) return st;
+  HIP_TRY(hipMalloc(&ws->lin_partials, sizeof(double) * LIN_MAX_GRAD * (size_t)ws->num_cu * PLN_BLOCKS_PER_CU));
+  HIP_TRY(hipMalloc(&ws->lin_accum, sizeof(double) * LIN_MAX_GRAD));
+  HIP_TRY(hipMemset(ws->lin_accum, 0, sizeof(double) * LIN_MAX_GRAD));
+  return BEAR_OK;
+}
+
+#ifdef LIN_STAMPS
+extern "C" int bear_dbg_lin_stamps(unsigned long long *host_out, int reset) {   // developer build only
+  if (host_out) HIP_TRY(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(lin_stamp_sums), sizeof(unsigned long long) * 8));
+  if (reset) {
+    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(lin_stamp_sums), z, sizeof(z)));
+  }
+  return BEAR_OK;
+}
+extern "C" int bear_dbg_lin_pe_stamps(unsigned long long *host_out) {   // prologue / epilogue sections of the last launch (12 words)
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(lin_pe_stamps), sizeof(unsigned long long) * 12));
+  return BEAR_OK;
+}
+#endif
+
+// ---- fused linear AR head (kernels_linear.h) -----------------------------------------------------------
+int bear_pack_kmers_u64(const int8_t *codes, uint64_t n_rows, int lag, uint64_t *packed, void *stream) {
+  if (lag < 1 || lag > LIN_MAX_LAG) return BEAR_ERR_INVALID_ARG;
+  if (n_rows == 0) return BEAR_OK;
+  if (!codes || !packed) return BEAR_ERR_INVALID_ARG;
+  const uint64_t blocks = (n_rows + 255) / 256;
+  if (blocks > 0x7fffffffull) return BEAR_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(pack_kmers_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), codes, n_rows, lag,
+                     reinterpret_cast<unsigned long long *>(packed));
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_linear_index_u64(const uint64_t *kmer_code, uint64_t n_rows, int lag, uint64_t *kmer_index, void *stream) {
+  if (lag < 1 || lag > LIN_MAX_LAG) return BEAR_ERR_INVALID_ARG;
+  if (n_rows == 0) return BEAR_OK;
+  if (!kmer_code || !kmer_index) return BEAR_ERR_INVALID_ARG;
+  uint64_t blocks = (n_rows + 255) / 256;
+  if (blocks > 1u << 20) blocks = 1u << 20;
+  hipLaunchKernelGGL(linear_index_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, lag, reinterpret_cast<unsigned long long *>(kmer_index));
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_encode_kmers_i8(const uint8_t *ascii, uint64_t n_rows, int lag, int rna, int8_t *codes, void *stream) {
+  if (lag < 1) return BEAR_ERR_INVALID_ARG;
+  if (n_rows == 0) return BEAR_OK;
+  if (!ascii || !codes) return BEAR_ERR_INVALID_ARG;
+  const uint64_t n_bytes = n_rows * (uint64_t)lag;
+  uint64_t blocks = (n_bytes + 255) / 256;
+  if (blocks > 1u << 20) blocks = 1u << 20;
+  hipLaunchKernelGGL(encode_kmers_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), ascii, n_bytes, rna,
+                     codes);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// The fused step's launch.  A plan paired for exactly these index words (bear_plan_pair_contexts): the PAIRED form of the kernel
+// over the paired tiles and, when some tiles kept their plain list, a second launch of the plain form over those, which adds
+// its sums to the first one's (same stream: the workspace is free again when it starts).
+static void launch_linear(bear_ws *ws, const bear_plan *plan, const uint64_t *kmer_code, const double *mat, int lag, const bear_params &prm,
+                          int train_ar, const bear_step_io &io, double *grad_mat, hipStream_t s, const bear_apply_io &apply = NO_APPLY) {
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+  const unsigned long long *kc = reinterpret_cast<const unsigned long long *>(kmer_code);
+  const bool paired = plan->live2 && plan->pair_codes == kmer_code && plan->pair_lag == lag && !getenv("BEAR_AMD_LINEAR_UNPAIRED");
+  // BEAR_AMD_DETERMINISTIC: fixed-point gradient tables (kernels_linear.h, lin_fx); the kernel derives their scale from these bounds
+  const bool det = bear_deterministic() && plan->count_bound[0] >= 1.0 && plan->count_bound[0] < 0x1p50;
+  const lin_fx_bound gt_bound = {plan->count_bound[0], plan->count_bound[1], log(plan->count_bound[2] > 1.0 ? plan->count_bound[2] : 1.0)};
+  // (the update, if any, goes with the step's LAST launch: the one that completes the sums)
+#define LIN_LAUNCH_K(AR, PAIRED, DET, NGK, PV, NT, ACC)                                                                                     \
+  hipLaunchKernelGGL((dm_linear_plan_kernel<AR, PAIRED, DET, NGK>), dim3(grid_plan(ws, NT)), dim3(PLN_THREADS), sizeof(pln_lds_lin), s, kc, \
+                     mat, lag, prm, PV, lt, ws->partials, ws->lin_accum, (ACC) == 1 ? io2 : io, grad_mat, ACC, gt_bound,                    \
+                     ((ACC) == 1 || !two_launches) ? apply : NO_APPLY)
+  // the group count as a compile-time constant for the lags 12 / 13 (6 groups: BASELINE's k = 13), 14 / 15 (7) and 4 / 5 (2: the
+  // bundled table); every other lag takes the kernel that finds it at run time (distinct13: 0.847 -> 0.833 ms, 128 -> 97 registers)
+#define LIN_LAUNCH_D(AR, PAIRED, DET, PV, NT, ACC)                       \
+  do {                                                                   \
+    if (n_groups == 6) LIN_LAUNCH_K(AR, PAIRED, DET, 6, PV, NT, ACC);    \
+    else if (n_groups == 7) LIN_LAUNCH_K(AR, PAIRED, DET, 7, PV, NT, ACC); \
+    else if (n_groups == 2) LIN_LAUNCH_K(AR, PAIRED, DET, 2, PV, NT, ACC); \
+    else LIN_LAUNCH_K(AR, PAIRED, DET, 0, PV, NT, ACC);                  \
+  } while (0)
+#define LIN_LAUNCH(AR, PAIRED, PV, NT, ACC)                    \
+  do {                                                         \
+    if (det) LIN_LAUNCH_D(AR, PAIRED, true, PV, NT, ACC);      \
+    else LIN_LAUNCH_D(AR, PAIRED, false, PV, NT, ACC);         \
+  } while (0)
+  bear_step_io io2 = io;      // the second launch of a step: its own stamp on the arrival word
+  io2.epoch = ws_arrival(ws).epoch;
+  pln_view pv = plan_view(plan);
+  const bool two_launches = paired && plan->n_tiles_u != 0;
+  // (BEAR_AMD_LINEAR_GENERIC=1: always the kernel that takes the group count at run time; tests compare the two)
+  const int n_groups = getenv("BEAR_AMD_LINEAR_GENERIC") ? 0 : lin_make_geom(lag).ng;
+  if (!paired) {
+    if (train_ar) LIN_LAUNCH(true, false, pv, plan->n_tiles, 0);
+    else LIN_LAUNCH(false, false, pv, plan->n_tiles, 0);
+    return;
+  }
+  pln_view pp = pv;           // the paired tiles; the plan's global lists and histogram go with this launch
+  pp.tiles = plan->tiles_p;
+  pp.n_tiles = plan->n_tiles_p;
+  pp.subset = 1;
+  if (two_launches) {
+    if (train_ar) LIN_LAUNCH(true, true, pp, plan->n_tiles_p, 2);
+    else LIN_LAUNCH(false, true, pp, plan->n_tiles_p, 2);
+  } else if (train_ar) LIN_LAUNCH(true, true, pp, plan->n_tiles_p, 0);
+  else LIN_LAUNCH(false, true, pp, plan->n_tiles_p, 0);
+  if (plan->n_tiles_u == 0) return;
+  pln_view pu = pv;           // the rest: tiles only
+  pu.tiles = plan->tiles_u;
+  pu.n_tiles = plan->n_tiles_u;
+  pu.subset = 1;
+  pu.n_heavy_col = pu.n_heavy_row = pu.n_heavy_stop = 0;
+  pu.hist = nullptr;
+  pu.hist_big = nullptr;
+  if (train_ar) LIN_LAUNCH(true, false, pu, plan->n_tiles_u, 1);
+  else LIN_LAUNCH(false, false, pu, plan->n_tiles_u, 1);
+#undef LIN_LAUNCH
+#undef LIN_LAUNCH_D
+#undef LIN_LAUNCH_K
+}
+
+static void plan_unpair(bear_plan *plan) {
+  if (!plan->live2) return;
+  plan->bytes -= plan->n_tiles * LIN_LIVE2_STRIDE * sizeof(uint16_t) + (plan->n_tiles + 2 * PLN_DESC_PAD) * sizeof(pln_tile);
+  (void)hipFree(plan->live2);
+  (void)hipFree(plan->tiles_p);
+  (void)hipFree(plan->tiles_u);
+  plan->live2 = nullptr;
+  plan->tiles_p = plan->tiles_u = nullptr;
+  plan->n_tiles_p = plan->n_tiles_u = 0;
+  plan->pair_codes = nullptr;
+}
+
+// Pairs the contexts of every tile's list for the fused linear step (kernels_linear.h, LIN_PAIR_CAP): kmer_index are the index
+// words the step will be called with (bear_linear_index_u64 for `lag`), in the row order of the plan's count slab.
+int bear_plan_pair_contexts(bear_plan *plan, const uint64_t *kmer_index, int lag, int *paired, void *stream) {
+  if (paired) *paired = 0;
+  if (!plan || plan->ncol != 5 || lag < 1 || lag > LIN_MAX_LAG) return BEAR_ERR_INVALID_ARG;
+  if (plan->n_rows && (!kmer_index || misaligned(kmer_index))) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (plan->live2) {           // a plan holds one pairing: the new one replaces it
+    HIP_TRY(hipStreamSynchronize(s));
+    plan_unpair(plan);
+  }
+  const uint64_t nt = plan->n_tiles;
+  if (nt == 0 || !plan->live) return BEAR_OK;
+  uint16_t *live2 = nullptr, *n_ent_dev = nullptr;
+  pln_tile *tp = nullptr, *tu = nullptr;
+  std::vector<uint16_t> n_ent;
+  std::vector<pln_tile> host, hp, hu;
+  try {
+    n_ent.resize(nt);
+    host.resize(nt);
+  } catch (const std::bad_alloc &) {
+    return BEAR_ERR_NOMEM;
+  }
+  hipError_t e = hipMalloc(&live2, nt * LIN_LIVE2_STRIDE * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(&n_ent_dev, nt * sizeof(uint16_t));
+  if (e == hipSuccess) {
+    uint64_t blocks = nt;                   // one wave per tile
+    if (blocks > (1u << 18)) blocks = 1u << 18;
+    hipLaunchKernelGGL(plan_pair_kernel, dim3((unsigned)blocks), dim3(64), 0, s, plan->tiles, nt, plan->live,
+                       reinterpret_cast<const unsigned long long *>(kmer_index), lag, live2, n_ent_dev,
+                       getenv("BEAR_AMD_PAIR_NO_EMPTY") ? 0 : 1);     // (developer switch: the dealt order without the extra empty slots)
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(n_ent.data(), n_ent_dev, nt * sizeof(uint16_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), plan->tiles, nt * sizeof(pln_tile), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(n_ent_dev);
+  uint64_t n_p = 0;
+  bool keep = false;
+  if (e == hipSuccess) {
+    try {
+      for (uint64_t t = 0; t < nt; ++t) {
+        pln_tile d = host[t];
+        const bool fits = n_ent[t] != 0xffffu;         // (a tile without live contexts fits with 0 entries)
+        d.pad = (t << 32) | (fits ? n_ent[t] : 0u);
+        (fits ? hp : hu).push_back(d);
+      }
+      n_p = hp.size();
+      // fewer than half of the tiles paired (a sparse table: runs of one context): nothing to gain, the plan stays as it was
+      keep = 2 * n_p >= nt;
+      if (keep) {
+        const pln_tile zero = {};
+        hp.insert(hp.end(), PLN_DESC_PAD, zero);
+        hu.insert(hu.end(), PLN_DESC_PAD, zero);
+      }
+    } catch (const std::bad_alloc &) {
+      (void)hipFree(live2);
+      return BEAR_ERR_NOMEM;
+    }
+  }
+  if (e == hipSuccess && keep) e = hipMalloc(&tp, hp.size() * sizeof(pln_tile));
+  if (e == hipSuccess && keep) e = hipMalloc(&tu, hu.size() * sizeof(pln_tile));
+  if (e == hipSuccess && keep) e = hipMemcpy(tp, hp.data(), hp.size() * sizeof(pln_tile), hipMemcpyHostToDevice);
+  if (e == hipSuccess && keep) e = hipMemcpy(tu, hu.data(), hu.size() * sizeof(pln_tile), hipMemcpyHostToDevice);
+  if (e != hipSuccess || !keep) {
+    (void)hipFree(live2);
+    (void)hipFree(tp);
+    (void)hipFree(tu);
+    if (e != hipSuccess) {
+      g_last_hip_error = (int)e;
+      return e == hipErrorOutOfMemory ? BEAR_ERR_NOMEM : BEAR_ERR_HIP;
+    }
+    return BEAR_OK;
+  }
+  plan->live2 = live2;
+  plan->tiles_p = tp;
+  plan->tiles_u = tu;
+  plan->n_tiles_p = n_p;
+  plan->n_tiles_u = nt - n_p;
+  plan->pair_codes = kmer_index;
+  plan->pair_lag = lag;
+  plan->bytes += nt * LIN_LIVE2_STRIDE * sizeof(uint16_t) + (nt + 2 * PLN_DESC_PAD) * sizeof(pln_tile);
+  if (paired) *paired = 1;
+  return BEAR_OK;
+}
+
+int bear_plan_pair_info(const bear_plan *plan, uint64_t *paired_tiles, uint64_t *plain_tiles) {
+  if (!plan) return BEAR_ERR_INVALID_ARG;
+  if (paired_tiles) *paired_tiles = plan->live2 ? plan->n_tiles_p : 0;
+  if (plain_tiles) *plain_tiles = plan->live2 ? plan->n_tiles_u : plan->n_tiles;
+  return plan->live2 ? 1 : 0;
+}
+
+int bear_dm_linear_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code,
+                       const double *mat, int lag, uint64_t n_rows, double h_signed, double eps, int train_ar,
+                       double *out, double *grad_mat, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!plan || !out || !grad_mat || !mat || lag < 1 || lag > LIN_MAX_LAG) return BEAR_ERR_INVALID_ARG;
+  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
+  if ((n_rows && !kmer_code) || misaligned(kmer_code) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (!(eps >= 0.0) || !isfinite(h_signed)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  bear_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.inv_h = 1.0 / exp(h_signed);
+  prm.eps = eps;
+  const bear_step_io io = ws_io(ws, nullptr, BEAR_THETA_NET, out);   // one launch: the last block sums the partials
+  launch_linear(ws, plan, kmer_code, mat, lag, prm, train_ar, io, grad_mat, s);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// ---- the linear AR function as rows (kernels_linrows.h): evaluation, bear_ref with the linear net function ------------
+static int linrows_grid(const bear_ws *ws, uint64_t n_rows) {
+  return grid_capped((n_rows + LNR_THREADS - 1) / LNR_THREADS, (uint64_t)ws->num_cu);   // lin_partials holds num_cu blocks
+}
+
+int bear_linear_forward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows, int lag, const double *mat, double *prior,
+                            void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (lag < 1 || lag > LIN_MAX_LAG || !mat) return BEAR_ERR_INVALID_ARG;
+  if (n_rows == 0) return BEAR_OK;
+  if (!kmer_code || !prior || misaligned(prior) || (reinterpret_cast<uintptr_t>(kmer_code) & 7u) || (reinterpret_cast<uintptr_t>(mat) & 7u))
+    return BEAR_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(linear_rows_forward_kernel, dim3(linrows_grid(ws, n_rows)), dim3(LNR_THREADS), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, mat, lag, prior);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_linear_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows, int lag, const double *prior,
+                             const double *grad_prior, double *grad_mat, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (lag < 1 || lag > LIN_MAX_LAG || !grad_mat || (reinterpret_cast<uintptr_t>(grad_mat) & 7u)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_rows == 0) {
+    HIP_TRY(hipMemsetAsync(grad_mat, 0, sizeof(double) * (size_t)lag * 25, s));
+    return BEAR_OK;
+  }
+  if (!kmer_code || !prior || !grad_prior) return BEAR_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(kmer_code) | reinterpret_cast<uintptr_t>(prior) | reinterpret_cast<uintptr_t>(grad_prior)) & 7u)
+    return BEAR_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(linear_rows_backward_kernel, dim3(linrows_grid(ws, n_rows)), dim3(LNR_THREADS), 0, s,
+                     reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, lag, prior, grad_prior, ws->lin_partials,
+                     ws_arrival(ws), grad_mat);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_net_linear_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, int lag,
+                                     uint64_t n_rows, const double *theta, double eps, int train_ar, double *packed, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!plan || !packed || !theta || lag < 1 || lag > LIN_MAX_LAG || !n_rows) return BEAR_ERR_INVALID_ARG;
+  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
+  if (!kmer_code || misaligned(kmer_code) || (reinterpret_cast<uintptr_t>(packed) & 7u)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  bear_params dummy;
+  memset(&dummy, 0, sizeof(dummy));
+  dummy.eps = eps;
+  const double *mat = theta + 1;
+  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, packed);   // constants from theta, sums by the last block: one launch
+  launch_linear(ws, plan, kmer_code, mat, lag, dummy, train_ar, io, packed + 2, s);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_net_linear_train_step_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, int lag,
+                                   uint64_t n_rows, double *theta, double *adam_m, double *adam_v, double *adam_t, double *packed,
+                                   double eps, int train_ar, double learning_rate, double scale, double *loss_buf,
+                                   uint64_t loss_cap, void *stream) {
+  if (!adam_m || !adam_v || !adam_t) return BEAR_ERR_INVALID_ARG;
+  if (two_launch_step()) {
+    int st = bear_net_linear_train_reduce_f64(ws, plan, counts, kmer_code, lag, n_rows, theta, eps, train_ar, packed, stream);
+    if (st != BEAR_OK) return st;
+    return launch_train_apply(theta, 1 + lag * 25, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap,
+                              static_cast<hipStream_t>(stream));
+  }
+  // ONE launch: the last block of the step's (last) kernel runs the update behind its sums
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!plan || !packed || !theta || lag < 1 || lag > LIN_MAX_LAG || !n_rows) return BEAR_ERR_INVALID_ARG;
+  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
+  if (!kmer_code || misaligned(kmer_code) || (reinterpret_cast<uintptr_t>(packed) & 7u)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  bear_params dummy;
+  memset(&dummy, 0, sizeof(dummy));
+  dummy.eps = eps;
+  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, packed);
+  launch_linear(ws, plan, kmer_code, theta + 1, lag, dummy, train_ar, io, packed + 2, s,
+                make_apply(theta, 1 + lag * 25, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int launch_train_apply(double *theta, int n_theta, const double *packed, double *adam_m, double *adam_v, double *adam_t,
+                              double learning_rate, double scale, int train_ar, double *loss_buf, uint64_t loss_cap, hipStream_t s) {
+  hipLaunchKernelGGL(adam_vec_kernel, dim3(1), dim3(1024), 0, s,
+                     make_apply(theta, n_theta, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap), packed);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_train_apply_f64(double *theta, int n_theta, const double *packed, double *adam_m, double *adam_v, double *adam_t,
+                         double learning_rate, double scale, int train_ar, double *loss_buf, uint64_t loss_cap, void *stream) {
+  if (!theta || !packed || !adam_m || !adam_v || !adam_t || n_theta < 1) return BEAR_ERR_INVALID_ARG;
+  return launch_train_apply(theta, n_theta, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap,
+                            static_cast<hipStream_t>(stream));
+}
+
+// Developer probe: the paired lists (bear_plan_pair_contexts) of tiles [first, first + n) and their first rows, to the host
+// (scripts/dev/pair_conflicts.py counts the bank-pair collisions of the triple adds from them).  A row is LIN_LIVE2_STRIDE uint16:
+// [0] = entries m, [1] = 0, m entries, then lin_lev_len(m) level words; a call with lists == NULL returns that stride instead.
+extern "C" int bear_debug_pair_lists(const bear_plan *plan, uint64_t first, uint64_t n, uint16_t *lists, uint64_t *row0) {
+  if (!lists) return (int)LIN_LIVE2_STRIDE;
+  if (!plan || !plan->live2 || !lists || !row0 || first + n > plan->n_tiles) return BEAR_ERR_INVALID_ARG;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(lists, plan->live2 + first * LIN_LIVE2_STRIDE, n * LIN_LIVE2_STRIDE * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  std::vector<pln_tile> t(n);
+  HIP_TRY(hipMemcpy(t.data(), plan->tiles + first, n * sizeof(pln_tile), hipMemcpyDeviceToHost));
+  for (uint64_t k = 0; k < n; ++k) row0[k] = t[k].row0;
+  return BEAR_OK;
+}

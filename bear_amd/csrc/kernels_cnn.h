@@ -24,12 +24,12 @@
 //   intercept2 [5] | scale0 [P][nf] | scale1 [l1]
 #pragma once
 #include "bear_common.h"
-#include "kernels_plan.h"   // pln_tile, PLN_LIVE_STRIDE: the training step runs over the plan's lists of contexts that hold counts
+#include "bear_levels.h"   // CNN_MAX_LAG, CNN_MAX_WIN: the plan keeps that many levels and window tables
+#include "plan_common.h"   // pln_tile, PLN_LIVE_STRIDE: the training step runs over the plan's lists of contexts that hold counts
 
 #define CNN_NF 30
 #define CNN_L1 16
 #define CNN_THREADS 256
-#define CNN_MAX_LAG 21
 #define CNN_LN_EPS 1e-5
 #ifndef CNN_SHARED_RUNS
 #define CNN_SHARED_RUNS 6            // backward: a position is done per distinct window when a tile holds at most this many (cnn_backward_shared_window)
@@ -70,7 +70,6 @@ static inline cnn_dims cnn_make_dims(int lag, int fw) {
 // positions that are left).  Forward runs the levels from the shortest prefixes down to the contexts; backward runs them the
 // other way, a level's dT1 rows being the sums of its children's (everything a position does with dT1 is linear in it).  Both
 // are the kernels below with a position range and a row source: a dense sorted table does ~1.3 positions per context, not 6.
-#define CNN_MAX_WIN 6             // window tables a launch may read (the positions the contexts themselves would evaluate)
 struct cnn_level_io {
   int p_lo, p_hi;                 // the positions this launch evaluates
   int head;                       // 1: the rows are contexts -- layer 1 onwards (forward: prior rows; backward: dT1 from the head)

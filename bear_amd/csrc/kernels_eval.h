@@ -16,7 +16,7 @@
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"
-#include "kernels_synth.h"
+#include "synth_hash.h"
 
 #define EVL_THREADS 256
 #define EVL_WAVES (EVL_THREADS / 64)

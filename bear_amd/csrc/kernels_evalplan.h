@@ -40,7 +40,7 @@
 // Sums: per-thread fp64 accumulators -> wave shuffle -> LDS -> one partial per block -> fixed-order finalize kernel.
 #pragma once
 #include "kernels_eval.h"
-#include "kernels_plan.h"
+#include "plan_common.h"
 
 #ifndef EVP_THREADS
 #define EVP_THREADS 1024   // round 3: the <1,4> instantiation fits 128 registers, so 16 waves (14 compute) fit a CU: -10 % on a compacted batch

@@ -30,7 +30,7 @@
 // Note: LDS floating-point atomics make the summation order inside a block run-dependent (last-bit jitter in
 // grad_mat); the ELBO and d/dh sums keep the fixed-order reduction of the other kernels.
 #pragma once
-#include "kernels_plan.h"
+#include "plan_common.h"
 #include <type_traits>
 #ifndef LIN_MAX_LAG
 #define LIN_MAX_LAG 21

@@ -21,7 +21,7 @@
 // criterion and its closed-form Beta expectations); the oracle restates this hash sampler bit for bit.
 #pragma once
 #include "bear_common.h"
-#include "kernels_synth.h"
+#include "synth_hash.h"
 
 #define SMP_THREADS 256
 #define SMP_MAX_MODELS 64

@@ -9,7 +9,7 @@
 // lag for k-mer bytes).
 #pragma once
 #include "bear_common.h"
-#include "kernels_synth.h"
+#include "synth_hash.h"
 
 __host__ __device__ __forceinline__ uint64_t shf_mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

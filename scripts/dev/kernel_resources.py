@@ -1,8 +1,10 @@
 """Developer: registers / occupancy / scratch of every kernel before and after a change, from two device assembly dumps:
-    hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off --cuda-device-only -S -o before.s bear_amd/csrc/bear_hip.hip   (each side)
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off --cuda-device-only -S -o before.s bear_amd/csrc/bear_hip.hip   (each side; the unit that
+    launches the kernel: bear_hip / bear_linear / bear_cnn / bear_eval .hip, bear_host.h)
     python scripts/dev/kernel_resources.py before.s after.s
 Prints the kernels whose numbers differ, with a mark where the waves per SIMD changed (round 6: two more vector registers in a
-shared helper moved dm_ref_items_kernel from 6 waves per SIMD to 5 and configs[3] from 128 to 164 us per step)."""
+shared helper moved dm_ref_items_kernel from 6 waves per SIMD to 5 and configs[3] from 128 to 164 us per step).
+kernel_table.py, next to this file, reads registers, scratch, LDS and code size of every kernel out of a built library instead."""
 import re
 import sys
 

@@ -25,7 +25,7 @@ ELBO_RTOL, MASS_RTOL, ROW_RTOL = 1e-11, 2e-13, 1e-12
 # held to 1e-11 of itself PLUS 1e-15 of its L1 mass (c_oracle.dm_prior_mass_w: |row term| + sum |items|, the scale of its
 # rounding).  Observed on such rows: 1e-17 .. 7e-17 of the mass.
 COND_RTOL = 1e-15
-# kernels_wide.h / bear_hip.hip: rows per tile of dm_wide_kernel, its blocks per CU; eval_wide_kernel's rows per tile, blocks per CU
+# kernels_wide.h / bear_eval.hip: rows per tile of dm_wide_kernel, its blocks per CU; eval_wide_kernel's rows per tile, blocks per CU
 WIDE_TILE = {21: 128, 5: 512}
 WIDE_BLOCKS_PER_CU, EVW_ROWS, EVAL_BLOCKS_PER_CU = 4, 128, 8
 
