@@ -23,7 +23,7 @@ def _deterministic_requested():
 # parameter gradients over per call; BEAR_AMD_LIB: developer A/B builds.
 LIB_PATH = os.environ.get("BEAR_AMD_LIB") or os.path.join(_HERE, "libbear_hip_det.so" if _deterministic_requested() else "libbear_hip.so")
 
-ABI_VERSION = 8   # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
+ABI_VERSION = 9   # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
 
 SYMBOLS = [
     "bear_abi_version", "bear_strerror", "bear_last_hip_error", "bear_ws_create", "bear_ws_destroy",
@@ -41,6 +41,7 @@ SYMBOLS = [
     "bear_plan_create_auto",
     "bear_dm_prior_wide_f64", "bear_eval_wide_f64", "bear_parse_counts_tsv_wide", "bear_parse_counts_tsv_shard_wide",
     "bear_logdir_sample_wide_f64",
+    "bear_kmer_sort_create_wide", "bear_fastx_size_wide", "bear_fastx_encode_wide", "bear_write_counts_tsv_wide",
 ]
 
 
@@ -165,6 +166,10 @@ def _load():
     L.bear_parse_counts_tsv_shard_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, u64, u64, u64, u64, cint, cint, u64, vp, vp,
                                                    ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.bear_logdir_sample_wide_f64.argtypes = [vp, vp, u64, cint, vp, cint, cint, vp, cint, cint, cint, u64, u64, vp, vp]
+    L.bear_kmer_sort_create_wide.argtypes = [vp, vp, u64, cint, cint, ctypes.POINTER(vp), ctypes.POINTER(u64), vp]
+    L.bear_fastx_size_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.bear_fastx_encode_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, cint, u64, vp, vp, ctypes.POINTER(u64)]
+    L.bear_write_counts_tsv_wide.argtypes = [ctypes.c_char_p, vp, vp, u64, cint, cint, cint, u64, u64, cint]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name in ("bear_plan_bytes", "bear_shuffle_source_row", "bear_eval_plan_bytes"):

@@ -230,7 +230,7 @@ class ResidentBatches:
             kmer_order = False              # (packed k-mers hold 3 bits per letter: the 4-letter alphabets' fused heads only)
         self.batches = []
         # k-mer letter codes: the ASCII bytes go up as they were parsed and are encoded on the device
-        fast_codes = want_codes and data.alphabet in ("dna", "rna") and data.lag > 0
+        fast_codes = want_codes and data.alphabet in ("dna", "rna", "prot") and data.lag > 0
         on_dev = getattr(data, "counts_dev", None) is not None       # DeviceCountDataset: the table is in HBM already
         codes = data.codes() if (want_codes and not fast_codes) else None
         rank, world = dist.world()

@@ -15,7 +15,8 @@
 // Text layout [dev]: per sequence  5 (start marker), letters 0..3 (6 = any other character), 4 (stop).  A transition sits
 // at every position holding 0..4; its context is the L codes before it, read back until the start marker, the rest
 // filled with the start symbol.  Transitions whose context or next letter contains a 6 are dropped (KMC drops k-mers
-// with non-ACGT letters likewise).
+// with non-ACGT letters likewise).  The protein alphabet takes the same pass with 5 bits per letter and rows of 21
+// (bear_kmer_sort_create_wide: residues 0..19, stop 20, start marker 21, 22 = any other character; value group * 21 + next).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -36,43 +37,65 @@ thread_local int g_count_hip_error = 0;
     }                                    \
   } while (0)
 
-// dropped transitions carry a key with only bit 3*lag set: it sorts behind every context, and the radix sort needs to
-// look at 3*lag + 1 bits only (5 passes instead of 8 at lag 13)
-__host__ __device__ inline uint64_t cnt_invalid(int lag) { return 1ull << (3 * lag); }
+// The same pass serves two alphabets (template over bits per letter and row width W; the start marker is W, the stop and
+// the '[' of a context are both W - 1, any other character is W + 1):
+//   W = 5,  3 bits: A,C,G,T = 0..3, stop 4, start marker 5, other 6            (bear_kmer_sort_create, lags 1..21)
+//   W = 21, 5 bits: ARNDCEQGHILKMFPSTWYV = 0..19, stop 20, start marker 21, other 22   (bear_kmer_sort_create_wide, lags 1..12)
+template <int BITS, int W>
+struct cnt_alphabet;
+template <>
+struct cnt_alphabet<3, 5> {
+  static constexpr int MAX_LAG = 21;
+  __device__ static uint8_t ascii(uint32_t c) { return (uint8_t)("ACGT["[c]); }
+};
+template <>
+struct cnt_alphabet<5, 21> {
+  static constexpr int MAX_LAG = 12;
+  __device__ static uint8_t ascii(uint32_t c) { return (uint8_t)("ARNDCEQGHILKMFPSTWYV["[c < 21u ? c : 20u]); }
+};
 
-// key: the context as the packed k-mer code of bear_pack_kmers_u64 (letter l of the k-mer in bits [3l, 3l+3); 4 = '[')
+// dropped transitions carry a key with only bit BITS*lag set: it sorts behind every context, and the radix sort needs to
+// look at BITS*lag + 1 bits only (5 passes instead of 8 at lag 13 of the 3-bit alphabet)
+template <int BITS>
+__host__ __device__ inline uint64_t cnt_invalid(int lag) { return 1ull << (BITS * lag); }
+
+// key: the context as the packed k-mer code (letter l of the k-mer in bits [BITS l, BITS l + BITS); W - 1 = '['): at 3 bits
+// the code of bear_pack_kmers_u64
+template <int BITS, int W>
 __global__ __launch_bounds__(256) void cnt_emit_kernel(const uint8_t *__restrict__ text, const uint8_t *__restrict__ grp,
                                                        uint64_t n_pos, int lag, uint64_t *__restrict__ keys,
                                                        uint32_t *__restrict__ vals) {
+  constexpr uint32_t STOP = W - 1, START = W;
   for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n_pos; t += (uint64_t)gridDim.x * 256) {
     const uint32_t nx = text[t];
-    const uint64_t CNT_INVALID = cnt_invalid(lag);
+    const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
     uint64_t key = CNT_INVALID;
-    if (nx <= 4u) {
+    if (nx <= STOP) {
       key = 0;
       bool started = false, bad = false;
       for (int i = 1; i <= lag; ++i) {                 // letter lag - i of the k-mer
-        uint32_t c = 4u;
+        uint32_t c = STOP;
         if (!started) {
-          c = (t >= (uint64_t)i) ? text[t - i] : 5u;
-          if (c == 5u) {
+          c = (t >= (uint64_t)i) ? text[t - i] : START;
+          if (c == START) {
             started = true;
-            c = 4u;
+            c = STOP;
           }
         }
-        bad |= c > 4u;
-        key |= (uint64_t)c << (3 * (lag - i));
+        bad |= c > STOP;
+        key |= (uint64_t)c << (BITS * (lag - i));
       }
       if (bad) key = CNT_INVALID;
     }
     keys[t] = key;
-    vals[t] = (uint32_t)grp[t] * 5u + (nx <= 4u ? nx : 0u);
+    vals[t] = (uint32_t)grp[t] * (uint32_t)W + (nx <= STOP ? nx : 0u);
   }
 }
 
+template <int BITS>
 __global__ __launch_bounds__(256) void cnt_flag_kernel(const uint64_t *__restrict__ keys, uint64_t n, int lag,
                                                        uint32_t *__restrict__ flags) {
-  const uint64_t CNT_INVALID = cnt_invalid(lag);
+  const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
   for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (uint64_t)gridDim.x * 256) {
     const uint64_t k = keys[t];
     flags[t] = (k != CNT_INVALID && (t == 0 || keys[t - 1] != k)) ? 1u : 0u;
@@ -80,25 +103,28 @@ __global__ __launch_bounds__(256) void cnt_flag_kernel(const uint64_t *__restric
 }
 
 // rows: inclusive scan of the run-start flags (row index + 1).  One thread per sorted pair.
+template <int BITS, int W>
 __global__ __launch_bounds__(256) void cnt_scatter_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                           const uint32_t *__restrict__ rows, uint64_t n, uint64_t n_rows, int lag,
                                                           uint32_t n_groups, uint8_t *__restrict__ kmers, uint64_t *__restrict__ codes,
                                                           uint32_t *__restrict__ counts) {
-  const uint64_t CNT_INVALID = cnt_invalid(lag);
+  const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
+  constexpr uint32_t UW = W;
   for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (uint64_t)gridDim.x * 256) {
     const uint64_t k = keys[t];
     if (k == CNT_INVALID) continue;
     const uint64_t row = (uint64_t)rows[t] - 1u;
     const uint32_t v = vals[t];
-    if (v / 5u < n_groups) atomicAdd(&counts[((uint64_t)(v / 5u) * n_rows + row) * 5u + (v % 5u)], 1u);   // group ids beyond n_groups are ignored
+    if (v / UW < n_groups) atomicAdd(&counts[((uint64_t)(v / UW) * n_rows + row) * UW + (v % UW)], 1u);   // group ids beyond n_groups are ignored
     if (t == 0 || keys[t - 1] != k) {                // run start: name the row
-      if (codes) {
+      if (BITS == 3 && codes) {                      // (the packed code belongs to the 4-letter fused heads: the host passes none at 5 bits)
         uint64_t packed = k;
         for (int l = lag; l < 21; ++l) packed |= 5ull << (3 * l);     // positions >= lag hold 5 (bear_pack_kmers_u64)
         codes[row] = packed;
       }
       if (kmers)
-        for (int l = 0; l < lag; ++l) kmers[row * (uint64_t)lag + l] = (uint8_t)("ACGT["[(k >> (3 * l)) & 7ull]);
+        for (int l = 0; l < lag; ++l)
+          kmers[row * (uint64_t)lag + l] = cnt_alphabet<BITS, W>::ascii((uint32_t)(k >> (BITS * l)) & ((1u << BITS) - 1u));
     }
   }
 }
@@ -111,34 +137,29 @@ unsigned grid_for(uint64_t n) {
 
 struct bear_kmer_sort {
   uint64_t n_pos, n_rows;
-  int lag;
+  int lag, width;   // width: counts per row, 5 (3-bit keys) or 21 (5-bit keys)
   uint64_t *keys;   // sorted
   uint32_t *vals;   // sorted with the keys
   uint32_t *rows;   // inclusive scan of run starts
 };
 
-extern "C" {
-
-int bear_count_last_hip_error(void) { return g_count_hip_error; }
-
-int bear_kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, bear_kmer_sort **out,
-                          uint64_t *n_rows_out, void *stream) {
-  if (!out || !n_rows_out || lag < 1 || lag > 21) return BEAR_ERR_INVALID_ARG;
-  *out = nullptr;
-  *n_rows_out = 0;
-  if (n_pos && (!text || !group)) return BEAR_ERR_INVALID_ARG;
-  if (n_pos >= 0xffffffffull) return BEAR_ERR_INVALID_ARG;   // row indices are 32-bit: shard the text above 4e9 positions
+namespace {
+// emit + sort + run starts of one lag (every argument checked by the caller, before any device call)
+template <int BITS, int W>
+int kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, bear_kmer_sort **out, uint64_t *n_rows_out,
+                     hipStream_t s) {
   int st = BEAR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   bear_kmer_sort *h = new (std::nothrow) bear_kmer_sort();
   if (!h) return BEAR_ERR_NOMEM;
   h->n_pos = n_pos;
   h->lag = lag;
+  h->width = W;
   uint64_t *keys_in = nullptr;
   uint32_t *vals_in = nullptr, *flags = nullptr;
   void *temp = nullptr;
   size_t tb_sort = 0, tb_scan = 0;
   uint32_t last = 0;
+  const unsigned key_bits = (unsigned)(BITS * lag + 1);
   if (n_pos == 0) {
     *out = h;
     return BEAR_OK;
@@ -147,11 +168,11 @@ int bear_kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_
   CNT_TRY(hipMalloc(&vals_in, n_pos * 4));
   CNT_TRY(hipMalloc(&h->keys, n_pos * 8));
   CNT_TRY(hipMalloc(&h->vals, n_pos * 4));
-  hipLaunchKernelGGL(cnt_emit_kernel, dim3(grid_for(n_pos)), dim3(256), 0, s, text, group, n_pos, lag, keys_in, vals_in);
+  hipLaunchKernelGGL((cnt_emit_kernel<BITS, W>), dim3(grid_for(n_pos)), dim3(256), 0, s, text, group, n_pos, lag, keys_in, vals_in);
   CNT_TRY(hipGetLastError());
-  CNT_TRY(rocprim::radix_sort_pairs(nullptr, tb_sort, keys_in, h->keys, vals_in, h->vals, n_pos, 0u, (unsigned)(3 * lag + 1), s));
+  CNT_TRY(rocprim::radix_sort_pairs(nullptr, tb_sort, keys_in, h->keys, vals_in, h->vals, n_pos, 0u, key_bits, s));
   CNT_TRY(hipMalloc(&temp, tb_sort ? tb_sort : 8));
-  CNT_TRY(rocprim::radix_sort_pairs(temp, tb_sort, keys_in, h->keys, vals_in, h->vals, n_pos, 0u, (unsigned)(3 * lag + 1), s));
+  CNT_TRY(rocprim::radix_sort_pairs(temp, tb_sort, keys_in, h->keys, vals_in, h->vals, n_pos, 0u, key_bits, s));
   CNT_TRY(hipStreamSynchronize(s));
   (void)hipFree(temp);
   temp = nullptr;
@@ -160,7 +181,7 @@ int bear_kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_
   flags = vals_in;   // reuse
   vals_in = nullptr;
   CNT_TRY(hipMalloc(&h->rows, n_pos * 4));
-  hipLaunchKernelGGL(cnt_flag_kernel, dim3(grid_for(n_pos)), dim3(256), 0, s, h->keys, n_pos, lag, flags);
+  hipLaunchKernelGGL((cnt_flag_kernel<BITS>), dim3(grid_for(n_pos)), dim3(256), 0, s, h->keys, n_pos, lag, flags);
   CNT_TRY(hipGetLastError());
   CNT_TRY(rocprim::inclusive_scan(nullptr, tb_scan, flags, h->rows, n_pos, rocprim::plus<uint32_t>(), s));
   CNT_TRY(hipMalloc(&temp, tb_scan ? tb_scan : 8));
@@ -185,15 +206,50 @@ done:
   return BEAR_OK;
 }
 
+bool sort_args_ok(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, int max_lag, bear_kmer_sort **out,
+                  uint64_t *n_rows_out) {
+  if (!out || !n_rows_out || lag < 1 || lag > max_lag) return false;
+  *out = nullptr;
+  *n_rows_out = 0;
+  if (n_pos && (!text || !group)) return false;
+  return n_pos < 0xffffffffull;   // row indices are 32-bit: shard the text above 4e9 positions
+}
+}  // namespace
+
+extern "C" {
+
+int bear_count_last_hip_error(void) { return g_count_hip_error; }
+
+int bear_kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, bear_kmer_sort **out,
+                          uint64_t *n_rows_out, void *stream) {
+  if (!sort_args_ok(text, group, n_pos, lag, cnt_alphabet<3, 5>::MAX_LAG, out, n_rows_out)) return BEAR_ERR_INVALID_ARG;
+  return kmer_sort_create<3, 5>(text, group, n_pos, lag, out, n_rows_out, static_cast<hipStream_t>(stream));
+}
+
+int bear_kmer_sort_create_wide(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, int width, bear_kmer_sort **out,
+                               uint64_t *n_rows_out, void *stream) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  const int max_lag = width == 5 ? cnt_alphabet<3, 5>::MAX_LAG : cnt_alphabet<5, 21>::MAX_LAG;   // 5 * 12 + 1 key bits fill one uint64
+  if (!sort_args_ok(text, group, n_pos, lag, max_lag, out, n_rows_out)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return width == 5 ? kmer_sort_create<3, 5>(text, group, n_pos, lag, out, n_rows_out, s)
+                    : kmer_sort_create<5, 21>(text, group, n_pos, lag, out, n_rows_out, s);
+}
+
 int bear_kmer_sort_reduce(const bear_kmer_sort *h, int n_groups, uint8_t *kmers, uint64_t *kmer_code, uint32_t *counts,
                           void *stream) {
   if (!h || n_groups < 1 || n_groups > 255) return BEAR_ERR_INVALID_ARG;
+  if (h->width != 5 && kmer_code) return BEAR_ERR_INVALID_ARG;   // the packed 3-bit code is the 4-letter fused heads' only
   if (h->n_rows == 0) return BEAR_OK;
   if (!counts) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(counts, 0, (size_t)n_groups * h->n_rows * 5 * 4, s) != hipSuccess) return BEAR_ERR_HIP;
-  hipLaunchKernelGGL(cnt_scatter_kernel, dim3(grid_for(h->n_pos)), dim3(256), 0, s, h->keys, h->vals, h->rows, h->n_pos, h->n_rows,
-                     h->lag, (uint32_t)n_groups, kmers, kmer_code, counts);
+  if (hipMemsetAsync(counts, 0, (size_t)n_groups * h->n_rows * (size_t)h->width * 4, s) != hipSuccess) return BEAR_ERR_HIP;
+  if (h->width == 5)
+    hipLaunchKernelGGL((cnt_scatter_kernel<3, 5>), dim3(grid_for(h->n_pos)), dim3(256), 0, s, h->keys, h->vals, h->rows, h->n_pos,
+                       h->n_rows, h->lag, (uint32_t)n_groups, kmers, kmer_code, counts);
+  else
+    hipLaunchKernelGGL((cnt_scatter_kernel<5, 21>), dim3(grid_for(h->n_pos)), dim3(256), 0, s, h->keys, h->vals, h->rows, h->n_pos,
+                       h->n_rows, h->lag, (uint32_t)n_groups, kmers, kmer_code, counts);
   if (hipGetLastError() != hipSuccess) return BEAR_ERR_HIP;
   return BEAR_OK;
 }

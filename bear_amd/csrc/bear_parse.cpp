@@ -609,17 +609,17 @@ inline int dec_digits(uint32_t v) {
   return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7
          : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
 }
-// bytes of one row: kmer \t [ [a,b,c,d,e] , [..] ... ] \n
-inline size_t row_bytes(const uint32_t *counts, uint64_t n_rows, uint64_t r, int lag, int num_ds) {
+// bytes of one row: kmer \t [ [a,b,c,d,e] , [..] ... ] \n   (width counts per group: 5, or 21 for the protein alphabet)
+inline size_t row_bytes(const uint32_t *counts, uint64_t n_rows, uint64_t r, int lag, int num_ds, int width) {
   size_t n = (size_t)lag + 1 + 1 + 1 + 1;                       // kmer, tab, outer [ ... ], newline
   for (int d = 0; d < num_ds; ++d) {
-    const uint32_t *c = counts + ((uint64_t)d * n_rows + r) * BEAR_ROW_WIDTH;
-    n += 2 + (BEAR_ROW_WIDTH - 1) + (d ? 1 : 0);                // [ ] , the commas inside, the comma in front of a later group
-    for (int b = 0; b < BEAR_ROW_WIDTH; ++b) n += (size_t)dec_digits(c[b]);
+    const uint32_t *c = counts + ((uint64_t)d * n_rows + r) * (uint64_t)width;
+    n += 2 + (size_t)(width - 1) + (d ? 1 : 0);                 // [ ] , the commas inside, the comma in front of a later group
+    for (int b = 0; b < width; ++b) n += (size_t)dec_digits(c[b]);
   }
   return n;
 }
-inline char *format_row(char *o, const char *kmers, const uint32_t *counts, uint64_t n_rows, uint64_t r, int lag, int num_ds) {
+inline char *format_row(char *o, const char *kmers, const uint32_t *counts, uint64_t n_rows, uint64_t r, int lag, int num_ds, int width) {
   memcpy(o, kmers + r * (uint64_t)lag, (size_t)lag);
   o += lag;
   *o++ = '\t';
@@ -627,8 +627,8 @@ inline char *format_row(char *o, const char *kmers, const uint32_t *counts, uint
   for (int d = 0; d < num_ds; ++d) {
     if (d) *o++ = ',';
     *o++ = '[';
-    const uint32_t *c = counts + ((uint64_t)d * n_rows + r) * BEAR_ROW_WIDTH;
-    for (int b = 0; b < BEAR_ROW_WIDTH; ++b) {
+    const uint32_t *c = counts + ((uint64_t)d * n_rows + r) * (uint64_t)width;
+    for (int b = 0; b < width; ++b) {
       if (b) *o++ = ',';
       uint32_t v = c[b];
       const int k = dec_digits(v);
@@ -649,8 +649,8 @@ inline char *format_row(char *o, const char *kmers, const uint32_t *counts, uint
 // Two passes over the selected rows, both cut into one contiguous range per hardware thread: the byte length of every range
 // (digit counting), a prefix sum, then each thread formats its range into 4 MiB pieces and writes them at its own file offset
 // (pwrite) -- the text of a 1e8-row, three-column table (5 GB) in seconds instead of the half minute of one thread.
-extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag,
-                                     int num_ds, uint64_t row_begin, uint64_t row_step, int append) {
+static int write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag, int num_ds, int width,
+                            uint64_t row_begin, uint64_t row_step, int append) {
   if (!path || !counts || (!kmers && lag > 0 && n_rows) || lag < 0 || num_ds < 1 || row_step == 0) return BEAR_ERR_INVALID_ARG;
   const int fd = open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
   if (fd < 0) return BEAR_ERR_IO;
@@ -672,7 +672,7 @@ extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const 
   for (unsigned t = 0; t <= nt; ++t) first[t] = n_sel * t / nt;
   auto measure = [&](unsigned t) {
     size_t n = 0;
-    for (uint64_t i = first[t]; i < first[t + 1]; ++i) n += row_bytes(counts, n_rows, row_begin + i * row_step, lag, num_ds);
+    for (uint64_t i = first[t]; i < first[t + 1]; ++i) n += row_bytes(counts, n_rows, row_begin + i * row_step, lag, num_ds, width);
     bytes[t + 1] = n;
   };
   {
@@ -685,7 +685,7 @@ extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const 
   std::vector<int> status(nt, BEAR_OK);
   auto emit = [&](unsigned t) {
     static const size_t PIECE = 4u << 20;
-    const size_t slack = 64 + (size_t)lag + (size_t)num_ds * 64;
+    const size_t slack = 64 + (size_t)lag + (size_t)num_ds * (4 + 11 * (size_t)width);   // one row beyond PIECE at most
     char *buf = static_cast<char *>(malloc(PIECE + slack));
     if (!buf) {
       status[t] = BEAR_ERR_NOMEM;
@@ -707,7 +707,7 @@ extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const 
       o = buf;
     };
     for (uint64_t i = first[t]; i < first[t + 1] && status[t] == BEAR_OK; ++i) {
-      o = format_row(o, kmers, counts, n_rows, row_begin + i * row_step, lag, num_ds);
+      o = format_row(o, kmers, counts, n_rows, row_begin + i * row_step, lag, num_ds, width);
       if ((size_t)(o - buf) >= PIECE) flush();
     }
     if (status[t] == BEAR_OK && o != buf) flush();
@@ -727,11 +727,38 @@ extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const 
   return st;
 }
 
+extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag,
+                                     int num_ds, uint64_t row_begin, uint64_t row_step, int append) {
+  return write_counts_tsv(path, kmers, counts, n_rows, lag, num_ds, BEAR_ROW_WIDTH, row_begin, row_step, append);
+}
+
+extern "C" int bear_write_counts_tsv_wide(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag,
+                                          int num_ds, int width, uint64_t row_begin, uint64_t row_step, int append) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  return write_counts_tsv(path, kmers, counts, n_rows, lag, num_ds, width, row_begin, row_step, append);
+}
+
 // ------------------------------------------------------------------ FASTA / FASTQ -> device code text (summarize path)
 // Replaces summarize.py's stage 1 readers (Biopython SimpleFastaParser / FastqGeneralIterator, summarize.py:96-100) for
 // the device pipeline: per sequence  5 (start marker), letters A,C,G,T -> 0..3 (any other character 6), 4 (stop); with
 // `reverse` every sequence is followed by its reverse complement (summarize.py:202-207).  Two calls: size, then fill.
+// The `_wide` twins take the row width of the alphabet: 5 is the text above; 21 is the protein text -- start marker 21, residues
+// ARNDCEQGHILKMFPSTWYV -> 0..19 (any other character 22), stop 20, no reverse complement.  A '*' that ends a record is the stop
+// the encoder writes anyway and is left out (by both passes); a '*' anywhere else is an ordinary "other" character.
 namespace {
+struct prot_lut {
+  uint8_t code[256];
+  prot_lut() {
+    memset(code, 22, sizeof code);
+    const char *letters = "ARNDCEQGHILKMFPSTWYV";
+    for (int i = 0; i < 20; ++i) {
+      code[(unsigned char)letters[i]] = (uint8_t)i;
+      code[(unsigned char)(letters[i] + ('a' - 'A'))] = (uint8_t)i;
+    }
+  }
+};
+const prot_lut PROT_LUT;
+
 inline uint8_t letter_code(unsigned char ch) {
   switch (ch) {
     case 'A': case 'a': return 0;
@@ -785,13 +812,26 @@ int walk_fastx(const mapped_file &f, int fastq, Seg seg, End end_record) {
 }
 }  // namespace
 
-extern "C" int bear_fastx_size(const char *path, int fastq, int reverse, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
-  if (!path || !n_pos_out) return BEAR_ERR_INVALID_ARG;
+// width 5 or 21.  `prot`: a '*' is held back until the next character of the record arrives; the record's end drops it.
+static int fastx_size(const char *path, int fastq, int reverse, int width, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
+  if (!path || !n_pos_out || (width != 5 && width != 21) || (width == 21 && reverse)) return BEAR_ERR_INVALID_ARG;
   mapped_file f;
   int st = f.open_ro(path);
   if (st != BEAR_OK) return st;
   uint64_t letters = 0, seqs = 0;
-  st = walk_fastx(f, fastq, [&](const char *b, const char *e) { letters += (uint64_t)(e - b); }, [&] { ++seqs; });
+  bool last_star = false;      // the last character of the open record so far is a '*'
+  const bool prot = width == 21;
+  st = walk_fastx(
+      f, fastq,
+      [&](const char *b, const char *e) {
+        letters += (uint64_t)(e - b);
+        if (e > b) last_star = e[-1] == '*';
+      },
+      [&] {
+        ++seqs;
+        if (prot && last_star) --letters;
+        last_star = false;
+      });
   if (st != BEAR_OK) return st;
   const uint64_t mult = reverse ? 2 : 1;
   *n_pos_out = mult * (letters + 2 * seqs);
@@ -799,14 +839,17 @@ extern "C" int bear_fastx_size(const char *path, int fastq, int reverse, uint64_
   return BEAR_OK;
 }
 
-extern "C" int bear_fastx_encode(const char *path, int fastq, int reverse, int group, uint64_t capacity, uint8_t *text,
-                                 uint8_t *group_out, uint64_t *n_pos_out) {
-  if (!path || !text || !n_pos_out || group < 0 || group > 254) return BEAR_ERR_INVALID_ARG;
+static int fastx_encode(const char *path, int fastq, int reverse, int width, int group, uint64_t capacity, uint8_t *text,
+                        uint8_t *group_out, uint64_t *n_pos_out) {
+  if (!path || !text || !n_pos_out || group < 0 || group > 254 || (width != 5 && width != 21) || (width == 21 && reverse))
+    return BEAR_ERR_INVALID_ARG;
   mapped_file f;
   int st = f.open_ro(path);
   if (st != BEAR_OK) return st;
+  const bool prot = width == 21;
+  const uint8_t START = (uint8_t)width, STOP = (uint8_t)(width - 1);
   uint64_t pos = 0, start = 0;
-  bool overflow = false, in_seq = false;
+  bool overflow = false, in_seq = false, held_star = false;
   auto put = [&](uint8_t v) {
     if (pos < capacity) text[pos] = v;
     else overflow = true;
@@ -817,17 +860,26 @@ extern "C" int bear_fastx_encode(const char *path, int fastq, int reverse, int g
       [&](const char *b, const char *e) {
         if (!in_seq) {
           start = pos;
-          put(5);
+          put(START);
           in_seq = true;
         }
-        for (const char *q = b; q < e; ++q) put(letter_code((unsigned char)*q));
+        if (!prot) {
+          for (const char *q = b; q < e; ++q) put(letter_code((unsigned char)*q));
+          return;
+        }
+        for (const char *q = b; q < e; ++q) {
+          if (held_star) put(22);          // it was not the record's last character
+          held_star = *q == '*';
+          if (!held_star) put(PROT_LUT.code[(unsigned char)*q]);
+        }
       },
       [&] {
         if (!in_seq) {   // empty record: start + stop
           start = pos;
-          put(5);
+          put(START);
         }
-        put(4);
+        held_star = false;
+        put(STOP);
         in_seq = false;
         if (reverse && !overflow) {
           const uint64_t first = start + 1, last = pos - 1;   // letters in [first, last)
@@ -844,4 +896,22 @@ extern "C" int bear_fastx_encode(const char *path, int fastq, int reverse, int g
   if (group_out) memset(group_out, group, (size_t)pos);
   *n_pos_out = pos;
   return BEAR_OK;
+}
+
+extern "C" int bear_fastx_size(const char *path, int fastq, int reverse, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
+  return fastx_size(path, fastq, reverse, BEAR_ROW_WIDTH, n_pos_out, n_seqs_out);
+}
+
+extern "C" int bear_fastx_size_wide(const char *path, int fastq, int reverse, int width, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
+  return fastx_size(path, fastq, reverse, width, n_pos_out, n_seqs_out);
+}
+
+extern "C" int bear_fastx_encode(const char *path, int fastq, int reverse, int group, uint64_t capacity, uint8_t *text,
+                                 uint8_t *group_out, uint64_t *n_pos_out) {
+  return fastx_encode(path, fastq, reverse, BEAR_ROW_WIDTH, group, capacity, text, group_out, n_pos_out);
+}
+
+extern "C" int bear_fastx_encode_wide(const char *path, int fastq, int reverse, int width, int group, uint64_t capacity, uint8_t *text,
+                                      uint8_t *group_out, uint64_t *n_pos_out) {
+  return fastx_encode(path, fastq, reverse, width, group, capacity, text, group_out, n_pos_out);
 }

@@ -131,9 +131,19 @@ __global__ void pack_kmers_kernel(const int8_t *__restrict__ codes, uint64_t n, 
 
 // ASCII k-mers as they sit in the count file -> int8 letter codes (core.tf_one_hot's alphabet order, core.py:146-153:
 // 0..3 letters, 4 = start symbol '[', -1 = anything else) -- the host LUT of a 1e9-row table took longer than an epoch.
+// rna == 2: the protein alphabet (core.alphabets_tf['prot']: ARNDCEQGHILKMFPSTWYV -> 0..19, '[' -> 20, -1 = anything else).
+__device__ inline int8_t encode_prot_letter(uint8_t ch) {
+  // 'A' .. '[' in ASCII order: A B C D E F G H I J K L M N O P Q R S T U V W X Y Z [
+  constexpr int8_t LUT[27] = {0, -1, 4, 3, 5, 13, 7, 8, 9, -1, 11, 10, 12, 2, -1, 14, 6, 1, 15, 16, -1, 19, 17, -1, 18, -1, 20};
+  return (ch >= 'A' && ch <= '[') ? LUT[ch - 'A'] : (int8_t)-1;
+}
 __global__ void encode_kmers_kernel(const uint8_t *__restrict__ ascii, uint64_t n_bytes, int rna, int8_t *__restrict__ codes) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_bytes; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint8_t ch = ascii[i];
+    if (rna == 2) {
+      codes[i] = encode_prot_letter(ch);
+      continue;
+    }
     int8_t c = -1;
     if (ch == 'A') c = 0;
     else if (ch == 'C') c = 1;

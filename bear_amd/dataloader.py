@@ -241,7 +241,7 @@ class MappedDataset:
 
 class DeviceCountDataset(CountDataset):
     """A count table that already lives in HBM (e.g. built by ``bear_amd.summarize`` on the device): ``kmers_dev`` uint8
-    [N, lag] and ``counts_dev`` int32-storage uint32 [num_ds, N, 5].  Training and evaluation use the device tensors
+    [N, lag] and ``counts_dev`` int32-storage uint32 [num_ds, N, 5] (21 for a protein table).  Training and evaluation use the device tensors
     directly (no upload); the host views ``kmers`` / ``counts`` are downloaded on first use."""
 
     def __init__(self, kmers_dev, counts_dev, alphabet, batch_size, dtype=torch.float64, repeats=1, shuffle_seed=None):
@@ -556,7 +556,8 @@ def bmm_likelihood(data, alpha, dtype=torch.float64, device=None):
 def write_counts_tsv(path, kmers, counts):
     """Writes a dense count table in the summarize.py row format (summarize.py:429-449):
     ``kmer \\t [[g0 A,C,G,T,$],[g1 ...],...]``.  kmers: sequence of str/bytes or uint8 [N, lag];
-    counts: integer array [num_ds, N, 5] (planar, as CountDataset.counts) or [N, num_ds, 5]."""
+    counts: integer array [num_ds, N, 5] (planar, as CountDataset.counts) or [N, num_ds, 5]; rows of 21 (the protein
+    alphabet) are written the same way, 21 counts per group."""
     counts = np.asarray(counts)
     if isinstance(kmers, np.ndarray) and kmers.dtype == np.uint8 and kmers.ndim == 2:
         km = np.ascontiguousarray(kmers)
@@ -566,8 +567,8 @@ def write_counts_tsv(path, kmers, counts):
             raise ValueError("write_counts_tsv: k-mers of one table have one length")
         km = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), len(rows[0]) if rows else 0).copy()
     n = km.shape[0]
-    if counts.ndim != 3 or counts.shape[2] != 5:
-        raise ValueError("write_counts_tsv: counts must be [num_ds, N, 5] or [N, num_ds, 5]")
+    if counts.ndim != 3 or counts.shape[2] not in (5, 21):
+        raise ValueError("write_counts_tsv: counts must be [num_ds, N, 5] or [N, num_ds, 5] (or rows of 21: the protein alphabet)")
     if counts.shape[0] == n:                          # [N, num_ds, 5] (takes precedence when both forms fit, as before) -> planar
         counts = counts.transpose(1, 0, 2)
     if counts.shape[1] != n:
@@ -576,5 +577,9 @@ def write_counts_tsv(path, kmers, counts):
         raise ValueError("write_counts_tsv: counts must fit uint32 (KMC's counter range, summarize.py:66-67)")
     planar = np.ascontiguousarray(counts, dtype=np.uint32)
     # the native writer of the summarize stage (csrc/bear_parse.cpp): formats in C++ instead of one Python call per number
-    st = _lib.lib().bear_write_counts_tsv(os.fsencode(path), km.ctypes.data, planar.ctypes.data, n, km.shape[1], planar.shape[0], 0, 1, 0)
+    if planar.shape[2] == 5:
+        st = _lib.lib().bear_write_counts_tsv(os.fsencode(path), km.ctypes.data, planar.ctypes.data, n, km.shape[1], planar.shape[0], 0, 1, 0)
+    else:
+        st = _lib.lib().bear_write_counts_tsv_wide(os.fsencode(path), km.ctypes.data, planar.ctypes.data, n, km.shape[1], planar.shape[0],
+                                                   planar.shape[2], 0, 1, 0)
     _lib.check(st, "bear_write_counts_tsv")

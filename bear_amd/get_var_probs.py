@@ -183,18 +183,22 @@ def make_kmc_genome_counter(path, lag, reverse=True, no_end=False):
     raise NotImplementedError("KMC database look-ups are outside this build; use make_sequence_counter")
 
 
-def make_sequence_counter(seqs, lag, reverse=True, no_end=False, device=None):
+def make_sequence_counter(seqs, lag, reverse=True, no_end=False, device=None, alphabet_name="dna"):
     """The counter of ``make_kmc_genome_counter`` (get_var_probs.py:213-290: k-mer strings -> transition counts
     ``[..., alphabet_size + 1]``) without KMC: the lag-``lag`` transition table of the sequences, counted on the device
     (``bear_amd.summarize``), as a look-up.  ``seqs``: sequences (list of str) or a summarize-style csv of
     ``FILE, GROUP, TYPE`` rows (all groups are pooled, as one KMC database is).  ``reverse`` adds the counts of the reverse
-    complements (:246-248, 271-278); ``no_end`` drops the stop counts and serves only full-length contexts (:240-252)."""
+    complements (:246-248, 271-278); ``no_end`` drops the stop counts and serves only full-length contexts (:240-252).
+    ``alphabet_name='prot'``: residues, rows of 21 counts, lags up to 12; there is no reverse complement, so ``reverse=False``
+    has to be passed."""
     from . import summarize
+    if alphabet_name == "prot" and reverse:
+        raise ValueError("make_sequence_counter: the protein alphabet has no reverse complement, pass reverse=False")
     if isinstance(seqs, str):
         seqs, _ = summarize._load_sequences(seqs)
     seqs = [str(s) for s in seqs]
-    text, grp = summarize.encode_sequences(seqs, [0] * len(seqs), reverse=reverse)
-    kmers, counts = summarize.count_transitions(text, grp, lag, 1, device=device)
+    text, grp = summarize.encode_sequences(seqs, [0] * len(seqs), reverse=reverse, alphabet=alphabet_name)
+    kmers, counts = summarize.count_transitions(text, grp, lag, 1, device=device, alphabet=alphabet_name)
     table = {bytes(k).decode(): counts[0, i].astype(np.float64) for i, k in enumerate(kmers)}
     A1 = counts.shape[-1]
 

@@ -10,6 +10,10 @@ code text and every lag is one emit + radix sort + run-length reduce (``bear_kme
 counted is what the reference's test defines (tests/test_summarize.py:88-115).  ``count_tables`` returns the tables as
 ``CountDataset`` objects without writing text at all.
 
+``alphabet='prot'`` (command line ``-a prot``) counts residues instead: the same pass with 5 bits per letter and rows of 21
+counts (``bear_kmer_sort_create_wide``), for lags up to 12, without reverse complements.  The reference has no such path (KMC is
+DNA-only); the rule is the same one over another alphabet.
+
 Rows come out sorted by packed k-mer code and are dealt round-robin to the output bins (the reference assigns rows to
 random bins, summarize.py:439,447, and states that the order carries no meaning, :72); shuffle before training
 (``CountDataset.shuffle`` or ``shuf``) exactly as with the reference's files.
@@ -31,6 +35,30 @@ _LUT = np.full(256, _OTHER, dtype=np.uint8)
 for _ch, _v in (("A", 0), ("C", 1), ("G", 2), ("T", 3)):
     _LUT[ord(_ch)] = _v
 _COMP = np.array([3, 2, 1, 0, 4, 5, 6], dtype=np.uint8)    # reverse complement on codes
+
+# the protein code text: residues in the order of core.alphabets_en['prot'], stop 20, start marker 21, any other character 22
+PROT_LETTERS = "ARNDCEQGHILKMFPSTWYV"
+_PROT_START, _PROT_STOP, _PROT_OTHER = 21, 20, 22
+_PROT_LUT = np.full(256, _PROT_OTHER, dtype=np.uint8)
+for _v, _ch in enumerate(PROT_LETTERS):
+    _PROT_LUT[ord(_ch)] = _v
+WIDTHS = {"dna": 5, "prot": 21}
+MAX_LAG = {"dna": 21, "prot": 12}       # 3 lag + 1 resp. 5 lag + 1 key bits in one uint64
+
+
+def _width(alphabet, reverse=False):
+    if alphabet not in WIDTHS:
+        raise ValueError(f"summarize counts the alphabets {tuple(WIDTHS)}, not {alphabet!r}")
+    if alphabet == "prot" and reverse:
+        raise ValueError("the protein alphabet has no reverse complement: pass reverse=False (no -r)")
+    return WIDTHS[alphabet]
+
+
+def _check_lag(lag, alphabet):
+    """The protein limit, with its reason (the 4-letter path keeps reporting the library's status for a lag beyond 21)."""
+    if alphabet == "prot" and not 1 <= int(lag) <= MAX_LAG["prot"]:
+        raise ValueError(f"lag {lag}: protein tables are counted for lags 1..{MAX_LAG['prot']} "
+                         "(5 bits per residue: a longer context does not fit the 64-bit sort key)")
 
 
 def load_input(in_file, file_type):
@@ -72,27 +100,34 @@ def read_file_list(seq_list_file):
     return rows
 
 
-def encode_sequences(seqs, groups, reverse=False):
+def encode_sequences(seqs, groups, reverse=False, alphabet="dna"):
     """Sequences (str) with their group ids -> the device text of bear_kmer_sort_create: per sequence a start marker,
     the letter codes and the stop code; with ``reverse`` every sequence is followed by its reverse complement
-    (summarize.py:202-207).  Returns ``(text uint8 [n_pos], group uint8 [n_pos])``."""
+    (summarize.py:202-207).  ``alphabet='prot'``: the 21-wide text (a ``*`` that ends a sequence is the stop and is left
+    out).  Returns ``(text uint8 [n_pos], group uint8 [n_pos])``."""
+    prot = _width(alphabet, reverse) == 21
+    lut, start, stop = (_PROT_LUT, _PROT_START, _PROT_STOP) if prot else (_LUT, _START, _STOP)
     parts, gparts = [], []
     for seq, g in zip(seqs, groups):
         if not 0 <= int(g) <= 254:
             raise ValueError("group ids must lie in [0, 254]")
-        codes = _LUT[np.frombuffer(seq.upper().encode("ascii", "replace"), dtype=np.uint8)]
+        if prot and seq.endswith("*"):
+            seq = seq[:-1]
+        codes = lut[np.frombuffer(seq.upper().encode("ascii", "replace"), dtype=np.uint8)]
         for c in ((codes, _COMP[codes[::-1]]) if reverse else (codes,)):
-            parts.append(np.concatenate([[_START], c, [_STOP]]).astype(np.uint8))
+            parts.append(np.concatenate([[start], c, [stop]]).astype(np.uint8))
             gparts.append(np.full(c.size + 2, int(g), dtype=np.uint8))
     if not parts:
         return np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8)
     return np.concatenate(parts), np.concatenate(gparts)
 
 
-def count_transitions(text, group, lag, n_groups, device=None, on_device=False):
+def count_transitions(text, group, lag, n_groups, device=None, on_device=False, alphabet="dna"):
     """One lag on the device.  text / group: uint8 arrays or CUDA tensors.  Returns
     ``(kmers uint8 [n_rows, lag] ASCII, counts uint32 [n_groups, n_rows, 5])`` as numpy arrays, or with ``on_device`` as
-    CUDA tensors (counts in int32 storage)."""
+    CUDA tensors (counts in int32 storage).  ``alphabet='prot'``: rows of 21, lags up to 12."""
+    width = _width(alphabet)
+    _check_lag(lag, alphabet)
     if not torch.cuda.is_available():
         raise RuntimeError("bear_amd counts on an MI355X only (libbear_hip.so has no CPU fallback)")
     device = torch.device(device or "cuda")
@@ -104,12 +139,16 @@ def count_transitions(text, group, lag, n_groups, device=None, on_device=False):
     h, n_rows = ctypes.c_void_p(), ctypes.c_uint64()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     with torch.cuda.device(t.device):
-        _lib.check(L.bear_kmer_sort_create(t.data_ptr(), g.data_ptr(), t.numel(), int(lag), ctypes.byref(h), ctypes.byref(n_rows),
-                                           stream), "bear_kmer_sort_create")
+        if width == 5:
+            _lib.check(L.bear_kmer_sort_create(t.data_ptr(), g.data_ptr(), t.numel(), int(lag), ctypes.byref(h), ctypes.byref(n_rows),
+                                               stream), "bear_kmer_sort_create")
+        else:
+            _lib.check(L.bear_kmer_sort_create_wide(t.data_ptr(), g.data_ptr(), t.numel(), int(lag), width, ctypes.byref(h),
+                                                    ctypes.byref(n_rows), stream), "bear_kmer_sort_create_wide")
         try:
             n = n_rows.value
             kmers = torch.empty((n, lag), dtype=torch.uint8, device=t.device)
-            counts = torch.empty((n_groups, n, 5), dtype=torch.int32, device=t.device)
+            counts = torch.empty((n_groups, n, width), dtype=torch.int32, device=t.device)
             _lib.check(L.bear_kmer_sort_reduce(h, int(n_groups), kmers.data_ptr(), None, counts.data_ptr(), stream),
                        "bear_kmer_sort_reduce")
             torch.cuda.current_stream().synchronize()
@@ -130,20 +169,28 @@ def _load_sequences(seq_list_file):
     return seqs, groups
 
 
-def load_text(seq_list_file, reverse=False):
-    """Every file of the list as the device code text (C++ readers, ``bear_fastx_encode``): ``(text, group, n_groups)``."""
+def load_text(seq_list_file, reverse=False, alphabet="dna"):
+    """Every file of the list as the device code text (C++ readers, ``bear_fastx_encode`` / ``_wide``): ``(text, group, n_groups)``."""
+    width = _width(alphabet, reverse)
     L = _lib.lib()
     parts, gparts, groups = [], [], []
     for path, group, ftype in read_file_list(seq_list_file):
         if ftype not in ("fa", "fq"):
             raise ValueError("file type must be 'fa' or 'fq'")
         n = ctypes.c_uint64()
-        _lib.check(L.bear_fastx_size(path.encode(), int(ftype == "fq"), int(bool(reverse)), ctypes.byref(n), None), "bear_fastx_size")
+        if width == 5:
+            _lib.check(L.bear_fastx_size(path.encode(), int(ftype == "fq"), int(bool(reverse)), ctypes.byref(n), None), "bear_fastx_size")
+        else:       # (the sizing pass leaves a record's closing '*' out, as the encoding pass does)
+            _lib.check(L.bear_fastx_size_wide(path.encode(), int(ftype == "fq"), 0, width, ctypes.byref(n), None), "bear_fastx_size_wide")
         text = np.empty(n.value, dtype=np.uint8)
         grp = np.empty(n.value, dtype=np.uint8)
         got = ctypes.c_uint64()
-        _lib.check(L.bear_fastx_encode(path.encode(), int(ftype == "fq"), int(bool(reverse)), int(group), n.value, text.ctypes.data,
-                                       grp.ctypes.data, ctypes.byref(got)), "bear_fastx_encode")
+        if width == 5:
+            _lib.check(L.bear_fastx_encode(path.encode(), int(ftype == "fq"), int(bool(reverse)), int(group), n.value, text.ctypes.data,
+                                           grp.ctypes.data, ctypes.byref(got)), "bear_fastx_encode")
+        else:
+            _lib.check(L.bear_fastx_encode_wide(path.encode(), int(ftype == "fq"), 0, width, int(group), n.value, text.ctypes.data,
+                                                grp.ctypes.data, ctypes.byref(got)), "bear_fastx_encode_wide")
         if got.value != n.value:      # the file changed between the sizing pass and the encoding pass
             raise RuntimeError(f"{path}: {got.value} positions encoded, {n.value} counted")
         parts.append(text)
@@ -154,16 +201,20 @@ def load_text(seq_list_file, reverse=False):
     return np.concatenate(parts), np.concatenate(gparts), max(groups) + 1
 
 
-def count_tables(seq_list_file, max_lag, reverse=False, batch_size=1 << 30, device=None, on_device=False):
+def count_tables(seq_list_file, max_lag, reverse=False, batch_size=1 << 30, device=None, on_device=False, alphabet="dna"):
     """The tables of every lag 1..max_lag as ``CountDataset`` objects (index L-1), never written as text; with
-    ``on_device`` as ``DeviceCountDataset`` objects that never leave HBM (count -> shuffle -> plan -> train)."""
-    text, grp, n_groups = load_text(seq_list_file, reverse)
+    ``on_device`` as ``DeviceCountDataset`` objects that never leave HBM (count -> shuffle -> plan -> train).
+    ``alphabet='prot'``: tables with ``alphabet == 'prot'`` and rows of 21 (max_lag <= 12, no ``reverse``)."""
+    _width(alphabet, reverse)
+    if max_lag >= 1:
+        _check_lag(max_lag, alphabet)
+    text, grp, n_groups = load_text(seq_list_file, reverse, alphabet)
     device = torch.device(device or "cuda")
     t, g = torch.from_numpy(text).to(device), torch.from_numpy(grp).to(device)
     out = []
     for lag in range(1, max_lag + 1):
-        kmers, counts = count_transitions(t, g, lag, n_groups, on_device=on_device)
-        out.append(DeviceCountDataset(kmers, counts, "dna", batch_size) if on_device else CountDataset(kmers, counts, "dna", batch_size))
+        kmers, counts = count_transitions(t, g, lag, n_groups, on_device=on_device, alphabet=alphabet)
+        out.append(DeviceCountDataset(kmers, counts, alphabet, batch_size) if on_device else CountDataset(kmers, counts, alphabet, batch_size))
     return out
 
 
@@ -182,14 +233,18 @@ def write_tables(tables, out_prefix, n_bins):
         cn = np.ascontiguousarray(d.counts)
         for b in range(n_bins):
             path = "{}_lag_{}_file_{}.tsv".format(out_prefix, li + 1, b)
-            _lib.check(L.bear_write_counts_tsv(path.encode(), km.ctypes.data, cn.ctypes.data, d.num_rows, li + 1, d.num_ds,
-                                               b, n_bins, 0), "bear_write_counts_tsv")
+            if d.width == 5:
+                _lib.check(L.bear_write_counts_tsv(path.encode(), km.ctypes.data, cn.ctypes.data, d.num_rows, li + 1, d.num_ds,
+                                                   b, n_bins, 0), "bear_write_counts_tsv")
+            else:
+                _lib.check(L.bear_write_counts_tsv_wide(path.encode(), km.ctypes.data, cn.ctypes.data, d.num_rows, li + 1, d.num_ds,
+                                                        int(d.width), b, n_bins, 0), "bear_write_counts_tsv_wide")
 
 
 def run(args):
     """summarize.py:622-645: all stages for one direction."""
     print("Start: counting on the device...", datetime.datetime.now())
-    tables = count_tables(args.file, args.l, reverse=bool(args.r))
+    tables = count_tables(args.file, args.l, reverse=bool(args.r), alphabet=getattr(args, "a", "dna"))
     n_groups = tables[0].num_ds if tables else 1
     # the reference sizes the bins from the KMC dump sizes (kmer \\t count \\n per distinct k+1-mer); same formula
     total_size = sum(int((d.counts > 0).sum()) * (li + 2 + 4) for li, d in enumerate(tables))
@@ -203,6 +258,7 @@ def main(args):
     """summarize.py:648-665: forward tables under ``out_prefix``, with ``-r`` forward + reverse-complement tables under
     ``out_prefix + '_rev'``.  Returns ``(n_bins, n_bins_rev)``."""
     store_r, prefix = bool(getattr(args, "r", False)), args.out_prefix
+    _width(getattr(args, "a", "dna"), store_r)       # -r with -a prot: refused before any file is read
     n_bins = n_bins_rev = None
     if not getattr(args, "nf", False):
         args.r = False
@@ -221,6 +277,7 @@ if __name__ == "__main__":
     parser.add_argument("file")
     parser.add_argument("out_prefix")
     parser.add_argument("-l", default=10, type=int)
+    parser.add_argument("-a", default="dna", choices=["dna", "prot"], help="alphabet of the sequences (prot: rows of 21, -l <= 12, no -r)")
     parser.add_argument("-mk", default=12, type=float)
     parser.add_argument("-mf", default=0.1, type=float)
     parser.add_argument("-p", default="")

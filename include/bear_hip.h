@@ -36,8 +36,10 @@
 extern "C" {
 #endif
 
-#define BEAR_ABI_VERSION 8 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
-                              8: + bear_logdir_sample_wide_f64 */
+#define BEAR_ABI_VERSION 9 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
+                              8: + bear_logdir_sample_wide_f64;
+                              9: + bear_kmer_sort_create_wide, bear_fastx_size_wide, bear_fastx_encode_wide, bear_write_counts_tsv_wide,
+                                 bear_encode_kmers_i8 mode 2 (protein count tables from sequence files) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -273,7 +275,8 @@ int bear_net_cnn_train_step_f64(bear_ws *ws, const bear_plan *plan, const uint32
 int bear_pack_kmers_u64(const int8_t *codes, uint64_t n_rows, int lag, uint64_t *packed, void *stream);
 int bear_linear_index_u64(const uint64_t *kmer_code, uint64_t n_rows, int lag, uint64_t *kmer_index, void *stream);
 /* ASCII k-mer bytes as parsed from the count file [dev] uint8 [n_rows, lag] -> int8 letter codes [dev] [n_rows, lag]:
- * 0..3 = A, C, G, T (U when rna != 0), 4 = '[', -1 = anything else (the all-zero one-hot row of core.py:173). */
+ * 0..3 = A, C, G, T (U when rna == 1), 4 = '[', -1 = anything else (the all-zero one-hot row of core.py:173).
+ * rna == 2 selects the protein alphabet instead: ARNDCEQGHILKMFPSTWYV -> 0..19, 20 = '[', -1 = anything else. */
 int bear_encode_kmers_i8(const uint8_t *ascii, uint64_t n_rows, int lag, int rna, int8_t *codes, void *stream);
 int bear_dm_linear_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_index,
                        const double *mat, int lag, uint64_t n_rows, double h_signed, double eps, int train_ar,
@@ -634,6 +637,18 @@ int bear_gather_rows(const void *src, const uint32_t *perm, void *dst, uint64_t 
  * bear_fastx_size / bear_fastx_encode [host]: a FASTA (fastq == 0) or FASTQ file as that code text (replacing the Biopython
  *   readers of summarize.py:96-100); reverse != 0 appends every sequence's reverse complement (summarize.py:202-207);
  *   group_out [nullable] receives `group` at every position.  Size first, then fill (`capacity` positions).
+ *
+ * The protein alphabet (rows of 21): the `_wide` twins take the row width, 5 or 21 (anything else BEAR_ERR_INVALID_ARG, checked
+ * with every other argument before any device call); width 5 is the entry above, bit for bit.  At width 21
+ *   text  per sequence: 21 (start), residues ARNDCEQGHILKMFPSTWYV -> 0..19 (22 = any other character), 20 (stop)
+ *   key   5 bits per letter, letter l of the context in bits [5l, 5l + 5), 20 = '['; the sort reads 5 lag + 1 bits: lag <= 12
+ *   value group * 21 + next letter;  a transition whose context or next letter holds a 22 is dropped, the others count
+ *   bear_kmer_sort_reduce on such a handle (it remembers its width): kmers ASCII from "ARNDCEQGHILKMFPSTWYV[", counts uint32
+ *     [n_groups, n_rows, 21] (the layout of bear_parse_counts_tsv_wide), rows ascending in the key; kmer_code must be NULL
+ *     (the packed 3-bit code belongs to the 4-letter fused heads)
+ *   bear_fastx_size_wide / bear_fastx_encode_wide: reverse != 0 is refused (no complement); a '*' that is the last character
+ *     of a record is the stop the encoder writes anyway and is left out by both passes, any other '*' is a 22
+ *   bear_write_counts_tsv_wide: the same rows with `width` counts per group (what bear_parse_counts_tsv_wide reads)
  */
 int bear_fastx_size(const char *path, int fastq, int reverse, uint64_t *n_pos_out, uint64_t *n_seqs_out);
 int bear_fastx_encode(const char *path, int fastq, int reverse, int group, uint64_t capacity, uint8_t *text,
@@ -647,6 +662,13 @@ int bear_kmer_sort_destroy(bear_kmer_sort *h);
 int bear_count_last_hip_error(void);
 int bear_write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag, int num_ds,
                           uint64_t row_begin, uint64_t row_step, int append);
+int bear_fastx_size_wide(const char *path, int fastq, int reverse, int width, uint64_t *n_pos_out, uint64_t *n_seqs_out);
+int bear_fastx_encode_wide(const char *path, int fastq, int reverse, int width, int group, uint64_t capacity, uint8_t *text,
+                           uint8_t *group_out, uint64_t *n_pos_out);
+int bear_kmer_sort_create_wide(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, int width, bear_kmer_sort **out,
+                               uint64_t *n_rows_out, void *stream);
+int bear_write_counts_tsv_wide(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag, int num_ds,
+                               int width, uint64_t row_begin, uint64_t row_step, int append);
 
 #ifdef __cplusplus
 }
