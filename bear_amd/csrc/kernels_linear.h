@@ -1250,7 +1250,7 @@ __device__ unsigned long long lin_pe_stamps[12];
 #define LIN_STAMP(k)
 #define LIN_PE(k)
 #endif
-// DET (BEAR_AMD_DETERMINISTIC): the gradient tables hold fixed-point integers, gt_scale = 2^50 / bound (see lin_fx above)
+// DET (BEAR_AMD_DETERMINISTIC): the gradient tables hold fixed-point integers, gt_scale = 2^62 / bound (see lin_fx above)
 // NGK: the number of letter groups as a compile-time constant (0: taken from `lag` at run time through LIN_FOR_NG).  With it a
 // launch's kernel holds ONE form of phases A and C instead of ten behind a switch inside the tile loop: a tenth of the code (the
 // instruction cache), no dispatch, and the register allocator sees one variant (round 6).

@@ -8,7 +8,7 @@ import torch
 
 import bear_oracle as o
 import c_oracle as co
-from util import dense_table, edge_table, prior_rows, sparse_table
+from util import dense_table, edge_table, mixed_heavy_table, prior_rows, sparse_table
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +64,7 @@ CASES_REF = {
     "dense": lambda: dense_table(3001, 13),
     "edge": lambda: (edge_table(), edge_table(1) // 9),
     "one_row": lambda: (np.array([[3, 0, 1, 0, 0]], np.uint32), np.array([[1, 0, 0, 0, 0]], np.uint32)),
+    "mixed_heavy": mixed_heavy_table,      # tiles whose large-count lists overflow (test_mixed_heavy_reaches_the_caps)
 }
 PARAMS = [(0.0, np.log(1 / 30), -np.log(100)), (-4.2, -1.0, 0.3), (2.5, 1.2, -7.0)]
 
@@ -245,7 +246,7 @@ def test_sorted_kernel_matches_rows_kernel(dev):
     assert abs(dh - a.cpu().numpy()[1]) <= 1e-10 * abs(dh)
 
 
-@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row"])
+@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row", "mixed_heavy"])
 def test_planned_kernels_parity(case, dev, ysd1):
     """The planned (sort-at-load-time) kernels against the oracle, and against the unplanned
     kernels, on every case incl. ragged tiles, Stirling-path items and uint32-range counts."""
@@ -287,7 +288,30 @@ def test_planned_kernels_parity(case, dev, ysd1):
             _mass_close(got[1], want[1], mass_h, (case, seed, "normalized"))
 
 
-@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row"])
+def test_mixed_heavy_reaches_the_caps(dev):
+    """What the `mixed_heavy` case is in the parametrisations for, as a condition on the plan the library really cuts: at least one
+    tile is full (PLN_RMAX = 1664 contexts), holds more large-count cells (count > SRT_CL = 24) and more large-total rows than a
+    tile keeps inside (PLN_HCAP = 128) -- so the in-tile lists fill and the surplus goes to the plan's global lists -- and has such
+    cells and rows on both sides of context 1024 of the tile: a thread of plan_fill_kernel meets them in its first AND its second
+    pass, and the second pass of the deterministic build's scan starts from a non-zero base."""
+    from bear_amd import kernels
+    RMAX, HCAP, CL = 1664, 128, 24
+    tr, _ = CASES_REF["mixed_heavy"]()
+    for ncol in (5, 4):
+        row0, rows, items, _ = kernels.Plan(_to_dev(tr, dev), ncol).tiles()
+        assert int(rows.sum()) == len(tr) and int(items.max()) <= 2048
+        hit = []
+        for r0, nr in zip(row0.astype(np.int64), rows.astype(np.int64)):
+            t = tr[r0:r0 + nr]
+            cells = (t[:, :ncol] > CL).sum(1)
+            heavy = t.sum(1, dtype=np.uint64) > CL
+            hit.append(nr == RMAX and cells.sum() > HCAP and heavy.sum() > HCAP
+                       and cells[:1024].sum() > HCAP and cells[1024:].sum() > HCAP    # either pass alone would fill the in-tile list
+                       and heavy[:1024].sum() > 0 and heavy[1024:].sum() > 0)
+        assert any(hit), (ncol, list(zip(row0, rows, items)))
+
+
+@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row", "mixed_heavy"])
 def test_dense_form_of_the_plan(case, dev, ysd1):
     """bear_plan_create_auto: the dense tables (the reference's own ysd1 table, SURVEY 8d's dense stress table) get the plan's dense
     form -- nothing kept per item, the mode-N entry points stream the count and prior rows -- and the sparse ones the sorted
@@ -333,7 +357,7 @@ def test_dense_form_of_the_plan(case, dev, ysd1):
         assert np.allclose(g.cpu().numpy(), wantg_ar, rtol=1e-12, atol=1e-12 * (np.abs(wantg_ar).max() + 1e-300)), (case, seed, "ar")
 
 
-@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row"])
+@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row", "mixed_heavy"])
 def test_planned_ar_mode_parity(case, dev, ysd1):
     """train_ar (multinomial, core.py:138-139) on the plan: sum c log(f + eps), gradients w.r.t. tau_s, nu_s
     (mode R) and the prior rows (mode N) against the oracle."""
@@ -434,7 +458,7 @@ def _linear_oracle(tr, codes, mat, h_s, train_ar):
     return np.append(out, mass_h), np.einsum("njk,nl->jkl", onehot, gz)
 
 
-@pytest.mark.parametrize("case", ["sparse", "sparse_hot", "dense", "edge", "ysd1"])
+@pytest.mark.parametrize("case", ["sparse", "sparse_hot", "dense", "edge", "ysd1", "mixed_heavy"])
 @pytest.mark.parametrize("lag", [5, 13, 21])
 def test_fused_linear_head_parity(case, lag, dev, ysd1):
     """bear_dm_linear_f64: ELBO, d/dh and d/d mat of the whole linear-head step against the oracle chain
@@ -474,7 +498,7 @@ def _sorted_by_kmer(codes):
 
 
 @pytest.mark.parametrize("lag", [1, 2, 3, 4, 5, 8, 13, 21])
-@pytest.mark.parametrize("case", ["sparse", "dense", "ysd1"])
+@pytest.mark.parametrize("case", ["sparse", "dense", "ysd1", "mixed_heavy"])
 def test_fused_linear_head_paired_contexts(case, lag, dev, ysd1, monkeypatch):
     """bear_plan_pair_contexts: the fused step over PAIRED lists (two neighbouring contexts with equal leading letters per
     thread) against the oracle chain and against the plain form of the same launch -- k-mer-sorted tables whose runs of equal
@@ -999,7 +1023,7 @@ def test_eval_plan_full_size_properties(dev):
     assert np.array_equal(parts[5:], got[5:]) and np.allclose(parts[:5], got[:5], rtol=1e-12)
 
 
-@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row", "no_ref", "all_ref"])
+@pytest.mark.parametrize("case", ["ysd1", "sparse", "sparse_hot", "dense", "edge", "one_row", "no_ref", "all_ref", "mixed_heavy"])
 @pytest.mark.parametrize("train_ar", [False, True])
 def test_reference_aware_plan_parity(case, train_ar, dev, ysd1):
     """bear_plan_create_ref (kernels_refplan.h): contexts without reference counts folded into a histogram, the others streamed

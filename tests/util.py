@@ -26,6 +26,17 @@ def dense_table(n, seed=0):
     return train, ref
 
 
+def mixed_heavy_table(n=6000, seed=1):
+    """A sparse table with ~6 % of its rows replaced by dense ones: full tiles (1664 contexts) that each hold several times more
+    large-count cells and large-total rows than a tile keeps inside (PLN_HCAP = 128), many of them among the contexts a thread
+    meets in its second pass (>= 1024 of the tile) -- the in-tile lists AND the plan's global lists fill.  (train, ref)."""
+    train, _, ref = sparse_table(n, 5, lam_scale=1.0)
+    dense, _ = dense_table(n, 7)
+    m = np.random.default_rng(seed).random(n) < 0.06
+    train[m] = dense[m]
+    return train, ref
+
+
 def prior_rows(n, seed=0, conc=1.0):
     rng = np.random.default_rng(seed + 1000)
     return rng.dirichlet(np.full(5, conc), size=n)
