@@ -170,12 +170,6 @@ def _load():
     L.bear_fastx_size_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.bear_fastx_encode_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, cint, u64, vp, vp, ctypes.POINTER(u64)]
     L.bear_write_counts_tsv_wide.argtypes = [ctypes.c_char_p, vp, vp, u64, cint, cint, cint, u64, u64, cint]
-    for name in SYMBOLS:
-        fn = getattr(L, name)
-        if name in ("bear_plan_bytes", "bear_shuffle_source_row", "bear_eval_plan_bytes"):
-            continue
-        if fn.restype is ctypes.c_int and name not in ("bear_abi_version", "bear_last_hip_error"):
-            fn.restype = cint
     _lib = L
     return L
 

@@ -39,7 +39,7 @@ int bear_cnn_forward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows
   int st = cnn_check(ws, lag, filter_width, num_filters, layer1_width);
   if (st != BEAR_OK) return st;
   if (n_rows == 0) return BEAR_OK;
-  if (!kmer_code || !params || !prior || misaligned(t1_save) || (reinterpret_cast<uintptr_t>(prior) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (!kmer_code || !params || !prior || misaligned(t1_save) || misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
   const cnn_dims D = cnn_make_dims(lag, filter_width);
   const size_t lds = sizeof(double) * (BEAR_EXPTAB_N + (size_t)filter_width * 6 * CNN_NF + (CNN_THREADS / 64) * CNN_FWD_SCRATCH);
   const int blocks = grid_capped((n_rows + CNN_THREADS - 1) / CNN_THREADS, (uint64_t)ws->num_cu * 16);
@@ -211,10 +211,7 @@ static int cnn_train_reduce_levels(bear_ws *ws, const bear_plan *plan, const cnn
   const bool recompute_t1 = io0.p_lo >= io0.p_hi && !getenv("BEAR_AMD_CNN_KEEP_T1");
   st = cnn_forward_levels(ws, plan, D, kmer_code, n_rows, params, prior_buf, recompute_t1 ? nullptr : t1_buf, s);
   if (st != BEAR_OK) return st;
-  bear_params only_eps;
-  memset(&only_eps, 0, sizeof(only_eps));
-  only_eps.eps = eps;
-  st = launch_prior_plan_grad(ws, plan, prior_buf, only_eps, theta, train_ar, 1, packed, grad_rows_buf, s);   // softmax rows: normalised
+  st = launch_prior_plan_grad(ws, plan, prior_buf, params_eps(eps), theta, train_ar, 1, packed, grad_rows_buf, s);   // softmax rows: normalised
   if (st != BEAR_OK) return st;
   const uint64_t per_block = (uint64_t)cnnq<2>::TILE * (uint64_t)bw_waves;
   bool first_launch = true;      // the first backward launch writes every row of the partial buffer the finalize reads, the others add
@@ -422,7 +419,7 @@ int bear_cnn_forward_plan_f64(bear_ws *ws, const bear_plan *plan, const uint64_t
   if (st != BEAR_OK) return st;
   if (!plan || plan->n_rows != n_rows || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
   if (n_rows == 0) return BEAR_OK;
-  if (!kmer_code || !params || !prior || !t1_save || misaligned(t1_save) || (reinterpret_cast<uintptr_t>(prior) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (!kmer_code || !params || !prior || !t1_save || misaligned(t1_save) || misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
   if (!((plan->n_cnn_levels > 0 || plan->n_cnn_windows > 0) && plan->cnn_codes == kmer_code && plan->cnn_lag == lag && plan->cnn_fw == filter_width) ||
       getenv("BEAR_AMD_CNN_NO_LEVELS"))
     return bear_cnn_forward_f64(ws, kmer_code, n_rows, lag, filter_width, num_filters, layer1_width, params, prior, t1_save, stream);
@@ -435,9 +432,8 @@ int bear_net_cnn_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint
   int st = cnn_check(ws, lag, filter_width, num_filters, layer1_width);
   if (st != BEAR_OK) return st;
   if (!plan || !packed || !theta || !prior_buf || !t1_buf || !grad_rows_buf || !n_rows || !kmer_code) return BEAR_ERR_INVALID_ARG;
-  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
-  if (misaligned(prior_buf) || misaligned(t1_buf) || misaligned(grad_rows_buf) || (reinterpret_cast<uintptr_t>(packed) & 7u))
-    return BEAR_ERR_INVALID_ARG;
+  if (check_plan_step(ws, plan, counts, n_rows, 5) != BEAR_OK) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(prior_buf) || misaligned(t1_buf) || misaligned(grad_rows_buf) || misaligned8(packed)) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const cnn_dims D = cnn_make_dims(lag, filter_width);
   const double *params = theta + 1;
@@ -460,10 +456,7 @@ int bear_net_cnn_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint
                        reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, D, params, prior_buf, t1_buf,
                        lists ? plan->tiles : nullptr, lists ? plan->live : nullptr, groups, cnn_all_positions(D));
   }
-  bear_params only_eps;
-  memset(&only_eps, 0, sizeof(only_eps));
-  only_eps.eps = eps;
-  st = launch_prior_plan_grad(ws, plan, prior_buf, only_eps, theta, train_ar, 1, packed, grad_rows_buf, s);   // softmax rows: normalised
+  st = launch_prior_plan_grad(ws, plan, prior_buf, params_eps(eps), theta, train_ar, 1, packed, grad_rows_buf, s);   // softmax rows: normalised
   if (st != BEAR_OK) return st;
   return launch_cnn_backward(ws, D, kmer_code, n_rows, filter_width, params, t1_buf, prior_buf, grad_rows_buf, packed + 2, s, 0, plan);
 }

@@ -164,13 +164,9 @@ int bear_dm_prior_f64(bear_ws *ws, const uint32_t *counts, const double *prior, 
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!out || (n_rows && (!counts || !prior))) return BEAR_ERR_INVALID_ARG;
-  if (misaligned(counts) || misaligned(prior) || misaligned(grad_prior) || (reinterpret_cast<uintptr_t>(out) & 7u))
-    return BEAR_ERR_INVALID_ARG;
+  if (misaligned(counts) || misaligned(prior) || misaligned(grad_prior) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params prm;
-  memset(&prm, 0, sizeof(prm));
-  prm.inv_h = 1.0 / exp(h_signed);
-  prm.eps = eps;
+  const bear_params prm = params_net(h_signed, eps);
   int grid = grid_rows(ws, n_rows);
   if (!train_ar && !grad_prior) {
     grid = grid_sorted(ws, n_rows);
@@ -202,26 +198,18 @@ int bear_dm_ref_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uin
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!out || (n_rows && (!train || !ref))) return BEAR_ERR_INVALID_ARG;
-  if (misaligned(train) || misaligned(ref) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(train) || misaligned(ref) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params prm;
-  const double tau = exp(tau_signed), nw = exp(nu_signed);
-  prm.inv_h = 1.0 / exp(h_signed);
-  prm.eps = eps;
-  prm.E = exp(-tau);
-  prm.tauE = tau * prm.E;
-  prm.tau = tau;
-  prm.V = 1.0 / (nw + 1.0);
-  prm.nw = nw;
+  const bear_params prm = params_ref(h_signed, tau_signed, nu_signed, eps);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
   int grid = grid_rows(ws, n_rows);
-  if (train_ar) {
-    hipLaunchKernelGGL((dm_ref_kernel<true>), dim3(grid), dim3(BEAR_THREADS), 0, s, train, ref, n_rows, prm, reinterpret_cast<const double2 *>(ws->logtab), ws->partials);
-  } else if (getenv("BEAR_ROWS_KERNEL")) {  // developer switch: v1 row-per-thread kernel (A/B measurements)
-    hipLaunchKernelGGL((dm_ref_kernel<false>), dim3(grid), dim3(BEAR_THREADS), 0, s, train, ref, n_rows, prm, reinterpret_cast<const double2 *>(ws->logtab), ws->partials);
+  if (train_ar || getenv("BEAR_ROWS_KERNEL")) {  // (BEAR mode: developer switch, the v1 row-per-thread kernel for A/B measurements)
+#define REF_LAUNCH(AR) hipLaunchKernelGGL((dm_ref_kernel<AR>), dim3(grid), dim3(BEAR_THREADS), 0, s, train, ref, n_rows, prm, lt, ws->partials)
+    BEAR_DISPATCH_1(train_ar, REF_LAUNCH);
+#undef REF_LAUNCH
   } else {
     grid = grid_sorted(ws, n_rows);
-    hipLaunchKernelGGL(dm_ref_sorted_kernel, dim3(grid), dim3(SRT_THREADS), sizeof(srt_lds_r), s, train, ref, n_rows, prm,
-                       reinterpret_cast<const double2 *>(ws->logtab), ws->partials);
+    hipLaunchKernelGGL(dm_ref_sorted_kernel, dim3(grid), dim3(SRT_THREADS), sizeof(srt_lds_r), s, train, ref, n_rows, prm, lt, ws->partials);
   }
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, ws->partials, grid, 4, out);
@@ -458,10 +446,8 @@ int bear_plan_destroy(bear_plan *plan) {
 uint64_t bear_plan_bytes(const bear_plan *plan) { return plan ? plan->bytes : 0; }
 
 // ---- the dense form: a five-column plan that keeps nothing per item (kernels_rows.h, dm_prior_rows_kernel).  Internally ncol =
-// PLAN_ROWS: every entry point that walks a plan's tiles and lists asks for ncol == 5 and so turns such a plan away; the mode-N
-// entry points (bear_dm_prior_plan_f64 / _grad_f64 / _dev_f64) take both.
-#define PLAN_ROWS 15
-static bool plan_is_rows(const bear_plan *p) { return p->ncol == PLAN_ROWS; }
+// PLAN_ROWS (bear_host.h): every entry point that walks a plan's tiles and lists asks for ncol == 5 and so turns such a plan away;
+// the mode-N entry points (bear_dm_prior_plan_f64 / _grad_f64 / _dev_f64) take both.
 int bear_plan_create_auto(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, int *rowwise, bear_plan **out) {
   if (rowwise) *rowwise = 0;
   int st = bear_plan_create(ws, counts, n_rows, 5, out);
@@ -634,13 +620,8 @@ int bear_dm_prior_plan_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *c
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!plan || !out || (n_rows && (!counts || !prior))) return BEAR_ERR_INVALID_ARG;
-  if ((plan->ncol != 5 && !plan_is_rows(plan)) || plan->n_rows != n_rows || plan->counts != counts || plan->device != ws->device)
-    return BEAR_ERR_INVALID_ARG;
-  if (misaligned(prior) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
-  bear_params prm;
-  memset(&prm, 0, sizeof(prm));
-  prm.inv_h = 1.0 / exp(h_signed);
-  prm.eps = eps;
+  if (check_plan_step(ws, plan, counts, n_rows, 5, true) != BEAR_OK || misaligned(prior) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
+  const bear_params prm = params_net(h_signed, eps);
   if (plan_is_rows(plan)) return launch_prior_rows(ws, plan, prior, prm, nullptr, train_ar, out, nullptr, static_cast<hipStream_t>(stream));
   return launch_prior_plan(ws, plan, prior, n_rows, prm, nullptr, train_ar, prior_normalized, out, static_cast<hipStream_t>(stream));
 }
@@ -686,13 +667,9 @@ int bear_dm_prior_plan_grad_f64(bear_ws *ws, const bear_plan *plan, const uint32
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!plan || !out || !grad_prior || (n_rows && (!counts || !prior))) return BEAR_ERR_INVALID_ARG;
-  if ((plan->ncol != 5 && !plan_is_rows(plan)) || plan->n_rows != n_rows || plan->counts != counts || plan->device != ws->device)
-    return BEAR_ERR_INVALID_ARG;
-  if (misaligned(prior) || misaligned(grad_prior) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
-  bear_params prm;
-  memset(&prm, 0, sizeof(prm));
-  prm.inv_h = 1.0 / exp(h_signed);
-  prm.eps = eps;
+  if (check_plan_step(ws, plan, counts, n_rows, 5, true) != BEAR_OK) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(prior) || misaligned(grad_prior) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
+  const bear_params prm = params_net(h_signed, eps);
   if (plan_is_rows(plan)) return launch_prior_rows(ws, plan, prior, prm, nullptr, train_ar, out, grad_prior, static_cast<hipStream_t>(stream));
   return launch_prior_plan_grad(ws, plan, prior, prm, nullptr, train_ar, prior_normalized, out, grad_prior,
                                 static_cast<hipStream_t>(stream));
@@ -706,13 +683,10 @@ int bear_dm_prior_plan_dev_f64(bear_ws *ws, const bear_plan *plan, const uint32_
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!plan || !out || !h_signed_dev || (n_rows && (!counts || !prior))) return BEAR_ERR_INVALID_ARG;
-  if ((plan->ncol != 5 && !plan_is_rows(plan)) || plan->n_rows != n_rows || plan->counts != counts || plan->device != ws->device)
-    return BEAR_ERR_INVALID_ARG;
-  if (misaligned(prior) || misaligned(grad_prior) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (check_plan_step(ws, plan, counts, n_rows, 5, true) != BEAR_OK) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(prior) || misaligned(grad_prior) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params only_eps;
-  memset(&only_eps, 0, sizeof(only_eps));
-  only_eps.eps = eps;
+  const bear_params only_eps = params_eps(eps);
   if (plan_is_rows(plan)) return launch_prior_rows(ws, plan, prior, only_eps, h_signed_dev, train_ar, out, grad_prior, s);
   if (grad_prior) return launch_prior_plan_grad(ws, plan, prior, only_eps, h_signed_dev, train_ar, prior_normalized, out, grad_prior, s);
   return launch_prior_plan(ws, plan, prior, n_rows, only_eps, h_signed_dev, train_ar, prior_normalized, out, s);
@@ -727,7 +701,7 @@ int bear_dm_refmix_plan_grad_f64(bear_ws *ws, const bear_plan *plan, const uint3
   if (st != BEAR_OK) return st;
   if (!plan || !out || !h_signed_dev || !tau_signed_dev || !net_weight_signed_dev) return BEAR_ERR_INVALID_ARG;
   if (n_rows && (!counts || !net_rows || !ref_rows || !grad_net_rows)) return BEAR_ERR_INVALID_ARG;
-  if (plan->ncol != 5 || plan->n_rows != n_rows || plan->counts != counts || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
+  if (check_plan_step(ws, plan, counts, n_rows, 5) != BEAR_OK) return BEAR_ERR_INVALID_ARG;
   if (misaligned(net_rows) || misaligned(ref_rows) || misaligned(grad_net_rows) || misaligned8(out) || misaligned8(h_signed_dev) ||
       misaligned8(tau_signed_dev) || misaligned8(net_weight_signed_dev) || !(eps >= 0.0))
     return BEAR_ERR_INVALID_ARG;
@@ -736,22 +710,20 @@ int bear_dm_refmix_plan_grad_f64(bear_ws *ws, const bear_plan *plan, const uint3
   const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
   const pln_view pv = plan_view(plan);
   const bear_step_io io = ws_io(ws, nullptr, BEAR_THETA_REF, out);
-  if (train_ar)
-    hipLaunchKernelGGL(dm_refmix_plan_grad_kernel<true>, dim3(grid), dim3(PLN_THREADS), sizeof(pln_lds_g), s, net_rows, ref_rows,
-                       h_signed_dev, tau_signed_dev, net_weight_signed_dev, eps, pv, lt, grad_net_rows, ws->partials, io);
-  else
-    hipLaunchKernelGGL(dm_refmix_plan_grad_kernel<false>, dim3(grid), dim3(PLN_THREADS), sizeof(pln_lds_g), s, net_rows, ref_rows,
-                       h_signed_dev, tau_signed_dev, net_weight_signed_dev, eps, pv, lt, grad_net_rows, ws->partials, io);
+#define MIX_LAUNCH(AR)                                                                                                            \
+  hipLaunchKernelGGL(dm_refmix_plan_grad_kernel<AR>, dim3(grid), dim3(PLN_THREADS), sizeof(pln_lds_g), s, net_rows, ref_rows, \
+                     h_signed_dev, tau_signed_dev, net_weight_signed_dev, eps, pv, lt, grad_net_rows, ws->partials, io)
+  BEAR_DISPATCH_1(train_ar, MIX_LAUNCH);
+#undef MIX_LAUNCH
   HIP_TRY(hipGetLastError());
   if (pv.n_heavy_col + pv.n_heavy_row) {
     const uint64_t nh = pv.n_heavy_col + pv.n_heavy_row;
     const int g2 = grid_capped((nh + 255) / 256, (uint64_t)ws->num_cu * 4);
-    if (train_ar)
-      hipLaunchKernelGGL(dm_refmix_fixup_kernel<true>, dim3(g2), dim3(256), 0, s, net_rows, ref_rows, h_signed_dev, tau_signed_dev,
-                         net_weight_signed_dev, eps, pv, lt, grad_net_rows);
-    else
-      hipLaunchKernelGGL(dm_refmix_fixup_kernel<false>, dim3(g2), dim3(256), 0, s, net_rows, ref_rows, h_signed_dev, tau_signed_dev,
-                         net_weight_signed_dev, eps, pv, lt, grad_net_rows);
+#define MIX_FIXUP(AR)                                                                                                      \
+  hipLaunchKernelGGL(dm_refmix_fixup_kernel<AR>, dim3(g2), dim3(256), 0, s, net_rows, ref_rows, h_signed_dev, tau_signed_dev, \
+                     net_weight_signed_dev, eps, pv, lt, grad_net_rows)
+    BEAR_DISPATCH_1(train_ar, MIX_FIXUP);
+#undef MIX_FIXUP
     HIP_TRY(hipGetLastError());
   }
   return BEAR_OK;
@@ -768,10 +740,10 @@ static int launch_ref_plan(bear_ws *ws, const bear_plan *plan, const uint32_t *r
   if (plan->rows_ref) {       // the dense form: rows streamed (kernels_rows.h)
     if (plan->ref != ref) return BEAR_ERR_INVALID_ARG;
     grid = grid_dense(ws, n_rows);
-    if (train_ar)
-      hipLaunchKernelGGL(dm_ref_rows_kernel<true>, dim3(grid), dim3(BEAR_THREADS), 0, s, plan->counts, ref, n_rows, prm, lt, ws->partials, io, apply);
-    else
-      hipLaunchKernelGGL(dm_ref_rows_kernel<false>, dim3(grid), dim3(BEAR_THREADS), 0, s, plan->counts, ref, n_rows, prm, lt, ws->partials, io, apply);
+#define REF_ROWS(AR) \
+  hipLaunchKernelGGL(dm_ref_rows_kernel<AR>, dim3(grid), dim3(BEAR_THREADS), 0, s, plan->counts, ref, n_rows, prm, lt, ws->partials, io, apply)
+    BEAR_DISPATCH_1(train_ar, REF_ROWS);
+#undef REF_ROWS
   } else if (plan->ref) {
     if (plan->ref != ref) return BEAR_ERR_INVALID_ARG;   // the plan is valid for the reference buffer it was built from
     rpl_view rv;
@@ -787,21 +759,19 @@ static int launch_ref_plan(bear_ws *ws, const bear_plan *plan, const uint32_t *r
     // contexts, ~4e5 units) 160 / 154 / 174 / 196 / 256 us
     const uint64_t units = (plan->n_ref_items + 63) / 64, want = (units + 3) / 4 + 2, cap = (uint64_t)ws->num_cu * (units > 131072 ? 6 : 4);
     grid = grid_capped(want, cap);
-    if (train_ar)
-      hipLaunchKernelGGL(dm_ref_items_kernel<true>, dim3(grid), dim3(256), 0, s, prm, rv, plan_view(plan), lt, ws->partials, io, apply);
-    else
-      hipLaunchKernelGGL(dm_ref_items_kernel<false>, dim3(grid), dim3(256), 0, s, prm, rv, plan_view(plan), lt, ws->partials, io, apply);
+#define REF_ITEMS(AR) \
+  hipLaunchKernelGGL(dm_ref_items_kernel<AR>, dim3(grid), dim3(256), 0, s, prm, rv, plan_view(plan), lt, ws->partials, io, apply)
+    BEAR_DISPATCH_1(train_ar, REF_ITEMS);
+#undef REF_ITEMS
   } else {
     grid = grid_plan(ws, plan->n_tiles);
-    if (train_ar)
-      hipLaunchKernelGGL(dm_ref_plan_kernel<true>, dim3(grid), dim3(PLN_THREADS), sizeof(pln_lds_r), s, ref, n_rows, prm, plan_view(plan), lt,
-                         ws->partials, io, apply);
-    else
-      hipLaunchKernelGGL(dm_ref_plan_kernel<false>, dim3(grid), dim3(PLN_THREADS), sizeof(pln_lds_r), s, ref, n_rows, prm, plan_view(plan), lt,
-                         ws->partials, io, apply);
+#define REF_PLAN(AR)                                                                                                                     \
+  hipLaunchKernelGGL(dm_ref_plan_kernel<AR>, dim3(grid), dim3(PLN_THREADS), sizeof(pln_lds_r), s, ref, n_rows, prm, plan_view(plan), lt, \
+                     ws->partials, io, apply)
+    BEAR_DISPATCH_1(train_ar, REF_PLAN);
+#undef REF_PLAN
   }
   HIP_TRY(hipGetLastError());
-  (void)grid;
   return BEAR_OK;
 }
 
@@ -811,58 +781,39 @@ int bear_dm_ref_plan_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *tra
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!plan || !out || (n_rows && (!train || !ref))) return BEAR_ERR_INVALID_ARG;
-  if (plan->ncol != 4 || plan->n_rows != n_rows || plan->counts != train || plan->device != ws->device)
-    return BEAR_ERR_INVALID_ARG;
-  if (misaligned(ref) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params prm;
-  const double tau = exp(tau_signed), nw = exp(nu_signed);
-  prm.inv_h = 1.0 / exp(h_signed);
-  prm.eps = eps;
-  prm.E = exp(-tau);
-  prm.tauE = tau * prm.E;
-  prm.tau = tau;
-  prm.V = 1.0 / (nw + 1.0);
-  prm.nw = nw;
-  return launch_ref_plan(ws, plan, ref, n_rows, prm, nullptr, train_ar, out, s);
+  if (check_plan_step(ws, plan, train, n_rows, 4) != BEAR_OK || misaligned(ref) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
+  return launch_ref_plan(ws, plan, ref, n_rows, params_ref(h_signed, tau_signed, nu_signed, eps), nullptr, train_ar, out,
+                         static_cast<hipStream_t>(stream));
+}
+
+// the shard's reduce of bear_ref's own step, constants from theta; with `apply` the last block runs the update behind its sums
+static int ref_reduce(bear_ws *ws, const bear_plan *plan, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, const double *theta,
+                      double eps, int train_ar, double *packed, hipStream_t s, const bear_apply_io &apply) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!plan || !packed || !theta || !n_rows || !train || !ref) return BEAR_ERR_INVALID_ARG;
+  if (check_plan_step(ws, plan, train, n_rows, 4) != BEAR_OK || misaligned(ref) || misaligned8(packed)) return BEAR_ERR_INVALID_ARG;
+  return launch_ref_plan(ws, plan, ref, n_rows, params_eps(eps), theta, train_ar, packed, s, apply);
 }
 
 int bear_ref_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *train, const uint32_t *ref, uint64_t n_rows,
                               const double *theta, double eps, int train_ar, double *packed, void *stream) {
-  int st = check_ws(ws);
-  if (st != BEAR_OK) return st;
-  if (!plan || !packed || !theta || !n_rows || !train || !ref) return BEAR_ERR_INVALID_ARG;
-  if (plan->ncol != 4 || plan->n_rows != n_rows || plan->counts != train || plan->device != ws->device)
-    return BEAR_ERR_INVALID_ARG;
-  if (misaligned(ref) || (reinterpret_cast<uintptr_t>(packed) & 7u)) return BEAR_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params only_eps;
-  memset(&only_eps, 0, sizeof(only_eps));
-  only_eps.eps = eps;
-  return launch_ref_plan(ws, plan, ref, n_rows, only_eps, theta, train_ar, packed, s);
+  return ref_reduce(ws, plan, train, ref, n_rows, theta, eps, train_ar, packed, static_cast<hipStream_t>(stream), NO_APPLY);
 }
 
 int bear_ref_train_step_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *train, const uint32_t *ref, uint64_t n_rows,
                             double *theta, double *adam_m, double *adam_v, double *adam_t, double eps, int train_ar,
                             double learning_rate, double scale, double *out, double *loss_buf, uint64_t loss_cap, void *stream) {
   if (!adam_m || !adam_v || !adam_t) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   if (two_launch_step()) {
-    int st = bear_ref_train_reduce_f64(ws, plan, train, ref, n_rows, theta, eps, train_ar, out, stream);
+    int st = ref_reduce(ws, plan, train, ref, n_rows, theta, eps, train_ar, out, s, NO_APPLY);
     if (st != BEAR_OK) return st;
-    return launch_train_apply(theta, 3, out, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap,
-                              static_cast<hipStream_t>(stream));
+    return launch_train_apply(theta, 3, out, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap, s);
   }
   // ONE launch: the last block of the reduce kernel runs the update behind its sums (bear_apply_in_block)
-  int st = check_ws(ws);
-  if (st != BEAR_OK) return st;
-  if (!plan || !out || !theta || !n_rows || !train || !ref) return BEAR_ERR_INVALID_ARG;
-  if (plan->ncol != 4 || plan->n_rows != n_rows || plan->counts != train || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
-  if (misaligned(ref) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
-  bear_params only_eps;
-  memset(&only_eps, 0, sizeof(only_eps));
-  only_eps.eps = eps;
-  return launch_ref_plan(ws, plan, ref, n_rows, only_eps, theta, train_ar, out, static_cast<hipStream_t>(stream),
-                         make_apply(theta, 3, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
+  return ref_reduce(ws, plan, train, ref, n_rows, theta, eps, train_ar, out, s,
+                    make_apply(theta, 3, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
 }
 
 int bear_dm_items_f64(bear_ws *ws, const double *x, const uint32_t *c, uint64_t n, int path, double *D, double *P,

@@ -49,6 +49,37 @@ static inline bool wide_width_ok(int width) { return width == 5 || width == 21; 
     }                            \
   } while (0)
 
+// F(A) with one run-time flag as a compile-time boolean
+#define BEAR_DISPATCH_1(a, F) \
+  do {                        \
+    if (a) F(true);           \
+    else F(false);            \
+  } while (0)
+
+// ------------------------------------------------------------------ kernel parameters by value (bear_common.h, bear_params)
+// every field a kernel does not read is zero.  params_eps: the constants come from device-resident parameters (bear_params_of)
+static inline bear_params params_eps(double eps) {
+  bear_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.eps = eps;
+  return prm;
+}
+static inline bear_params params_net(double h_signed, double eps) {
+  bear_params prm = params_eps(eps);
+  prm.inv_h = 1.0 / exp(h_signed);
+  return prm;
+}
+static inline bear_params params_ref(double h_signed, double tau_signed, double nu_signed, double eps) {
+  bear_params prm = params_net(h_signed, eps);
+  const double tau = exp(tau_signed), nw = exp(nu_signed);
+  prm.E = exp(-tau);
+  prm.tauE = tau * prm.E;
+  prm.tau = tau;
+  prm.V = 1.0 / (nw + 1.0);
+  prm.nw = nw;
+  return prm;
+}
+
 // ------------------------------------------------------------------ grids
 // Every grid-stride launch takes min(work, cap) blocks, and at least one.  The block partials are summed in a fixed order PER GRID:
 // a different grid is different bits, so a cap is part of a kernel's results, not a tuning detail of its call site.
@@ -197,6 +228,17 @@ static inline pln_view plan_view(const bear_plan *p) {
   v.n_heavy_row = p->n_heavy[1];
   v.n_heavy_stop = p->n_heavy[2];
   return v;
+}
+
+// A step on a plan takes the table the plan was built from, on the workspace's device.  ncol: 5 (mode N) or 4 (mode R);
+// or_rows: the entry also takes the dense form of a five-column plan (bear_plan_create_auto).
+#define PLAN_ROWS 15      // ncol of that form: every entry that walks a plan's tiles and lists asks for 5 and so turns it away
+static inline bool plan_is_rows(const bear_plan *p) { return p->ncol == PLAN_ROWS; }
+static inline int check_plan_step(const bear_ws *ws, const bear_plan *plan, const uint32_t *counts, uint64_t n_rows, int ncol,
+                                  bool or_rows = false) {
+  if (plan->ncol != ncol && !(or_rows && plan_is_rows(plan))) return BEAR_ERR_INVALID_ARG;
+  if (plan->counts != counts || plan->n_rows != n_rows || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
+  return BEAR_OK;
 }
 
 // ------------------------------------------------------------------ across units

@@ -251,16 +251,11 @@ int bear_dm_linear_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *count
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!plan || !out || !grad_mat || !mat || lag < 1 || lag > LIN_MAX_LAG) return BEAR_ERR_INVALID_ARG;
-  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
-  if ((n_rows && !kmer_code) || misaligned(kmer_code) || (reinterpret_cast<uintptr_t>(out) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (check_plan_step(ws, plan, counts, n_rows, 5) != BEAR_OK) return BEAR_ERR_INVALID_ARG;
+  if ((n_rows && !kmer_code) || misaligned(kmer_code) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
   if (!(eps >= 0.0) || !isfinite(h_signed)) return BEAR_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params prm;
-  memset(&prm, 0, sizeof(prm));
-  prm.inv_h = 1.0 / exp(h_signed);
-  prm.eps = eps;
   const bear_step_io io = ws_io(ws, nullptr, BEAR_THETA_NET, out);   // one launch: the last block sums the partials
-  launch_linear(ws, plan, kmer_code, mat, lag, prm, train_ar, io, grad_mat, s);
+  launch_linear(ws, plan, kmer_code, mat, lag, params_net(h_signed, eps), train_ar, io, grad_mat, static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
@@ -276,7 +271,7 @@ int bear_linear_forward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_r
   if (st != BEAR_OK) return st;
   if (lag < 1 || lag > LIN_MAX_LAG || !mat) return BEAR_ERR_INVALID_ARG;
   if (n_rows == 0) return BEAR_OK;
-  if (!kmer_code || !prior || misaligned(prior) || (reinterpret_cast<uintptr_t>(kmer_code) & 7u) || (reinterpret_cast<uintptr_t>(mat) & 7u))
+  if (!kmer_code || !prior || misaligned(prior) || misaligned8(kmer_code) || misaligned8(mat))
     return BEAR_ERR_INVALID_ARG;
   hipLaunchKernelGGL(linear_rows_forward_kernel, dim3(linrows_grid(ws, n_rows)), dim3(LNR_THREADS), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, mat, lag, prior);
@@ -288,15 +283,14 @@ int bear_linear_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_
                              const double *grad_prior, double *grad_mat, void *stream) {
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
-  if (lag < 1 || lag > LIN_MAX_LAG || !grad_mat || (reinterpret_cast<uintptr_t>(grad_mat) & 7u)) return BEAR_ERR_INVALID_ARG;
+  if (lag < 1 || lag > LIN_MAX_LAG || !grad_mat || misaligned8(grad_mat)) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_rows == 0) {
     HIP_TRY(hipMemsetAsync(grad_mat, 0, sizeof(double) * (size_t)lag * 25, s));
     return BEAR_OK;
   }
   if (!kmer_code || !prior || !grad_prior) return BEAR_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(kmer_code) | reinterpret_cast<uintptr_t>(prior) | reinterpret_cast<uintptr_t>(grad_prior)) & 7u)
-    return BEAR_ERR_INVALID_ARG;
+  if (misaligned8(kmer_code) || misaligned8(prior) || misaligned8(grad_prior)) return BEAR_ERR_INVALID_ARG;
   hipLaunchKernelGGL(linear_rows_backward_kernel, dim3(linrows_grid(ws, n_rows)), dim3(LNR_THREADS), 0, s,
                      reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, lag, prior, grad_prior, ws->lin_partials,
                      ws_arrival(ws), grad_mat);
@@ -304,22 +298,24 @@ int bear_linear_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_
   return BEAR_OK;
 }
 
-int bear_net_linear_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, int lag,
-                                     uint64_t n_rows, const double *theta, double eps, int train_ar, double *packed, void *stream) {
+// the shard's reduce of the linear head's step: constants from theta, sums by the last block (one launch, or two on a partly
+// paired plan); with `apply` the last block of the step's last kernel runs the update behind its sums
+static int linear_reduce(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, int lag, uint64_t n_rows,
+                         const double *theta, double eps, int train_ar, double *packed, hipStream_t s, const bear_apply_io &apply) {
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if (!plan || !packed || !theta || lag < 1 || lag > LIN_MAX_LAG || !n_rows) return BEAR_ERR_INVALID_ARG;
-  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
-  if (!kmer_code || misaligned(kmer_code) || (reinterpret_cast<uintptr_t>(packed) & 7u)) return BEAR_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params dummy;
-  memset(&dummy, 0, sizeof(dummy));
-  dummy.eps = eps;
-  const double *mat = theta + 1;
-  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, packed);   // constants from theta, sums by the last block: one launch
-  launch_linear(ws, plan, kmer_code, mat, lag, dummy, train_ar, io, packed + 2, s);
+  if (check_plan_step(ws, plan, counts, n_rows, 5) != BEAR_OK) return BEAR_ERR_INVALID_ARG;
+  if (!kmer_code || misaligned(kmer_code) || misaligned8(packed)) return BEAR_ERR_INVALID_ARG;
+  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, packed);
+  launch_linear(ws, plan, kmer_code, theta + 1, lag, params_eps(eps), train_ar, io, packed + 2, s, apply);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
+}
+
+int bear_net_linear_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, int lag,
+                                     uint64_t n_rows, const double *theta, double eps, int train_ar, double *packed, void *stream) {
+  return linear_reduce(ws, plan, counts, kmer_code, lag, n_rows, theta, eps, train_ar, packed, static_cast<hipStream_t>(stream), NO_APPLY);
 }
 
 int bear_net_linear_train_step_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, int lag,
@@ -327,27 +323,14 @@ int bear_net_linear_train_step_f64(bear_ws *ws, const bear_plan *plan, const uin
                                    double eps, int train_ar, double learning_rate, double scale, double *loss_buf,
                                    uint64_t loss_cap, void *stream) {
   if (!adam_m || !adam_v || !adam_t) return BEAR_ERR_INVALID_ARG;
-  if (two_launch_step()) {
-    int st = bear_net_linear_train_reduce_f64(ws, plan, counts, kmer_code, lag, n_rows, theta, eps, train_ar, packed, stream);
-    if (st != BEAR_OK) return st;
-    return launch_train_apply(theta, 1 + lag * 25, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap,
-                              static_cast<hipStream_t>(stream));
-  }
-  // ONE launch: the last block of the step's (last) kernel runs the update behind its sums
-  int st = check_ws(ws);
-  if (st != BEAR_OK) return st;
-  if (!plan || !packed || !theta || lag < 1 || lag > LIN_MAX_LAG || !n_rows) return BEAR_ERR_INVALID_ARG;
-  if (plan->counts != counts || plan->n_rows != n_rows || plan->ncol != 5 || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
-  if (!kmer_code || misaligned(kmer_code) || (reinterpret_cast<uintptr_t>(packed) & 7u)) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  bear_params dummy;
-  memset(&dummy, 0, sizeof(dummy));
-  dummy.eps = eps;
-  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, packed);
-  launch_linear(ws, plan, kmer_code, theta + 1, lag, dummy, train_ar, io, packed + 2, s,
-                make_apply(theta, 1 + lag * 25, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
-  HIP_TRY(hipGetLastError());
-  return BEAR_OK;
+  if (two_launch_step()) {
+    int st = linear_reduce(ws, plan, counts, kmer_code, lag, n_rows, theta, eps, train_ar, packed, s, NO_APPLY);
+    if (st != BEAR_OK) return st;
+    return launch_train_apply(theta, 1 + lag * 25, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap, s);
+  }
+  return linear_reduce(ws, plan, counts, kmer_code, lag, n_rows, theta, eps, train_ar, packed, s,
+                       make_apply(theta, 1 + lag * 25, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
 }
 
 int launch_train_apply(double *theta, int n_theta, const double *packed, double *adam_m, double *adam_v, double *adam_t,

@@ -3,7 +3,7 @@
 // trusted 5-wide entry points (bear_dm_prior_f64, bear_eval_f64); production DNA / RNA keep their own kernels and plans.
 //
 //   tile   = WIDE_TILE(W) contexts: count rows (4 W B) and prior rows (8 W B) fetched as one flat stream of 16-byte lane loads
-//            into LDS (wide_stage), then each thread reads its own row back.  Stride W dwords (W odd) is conflict-free for
+//            into LDS (stage_dwords), then each thread reads its own row back.  Stride W dwords (W odd) is conflict-free for
 //            ds_read_b32 (bank (a/4) mod 32); stride W doubles = 2W dwords for ds_read_b64 (bank (a/4) mod 64, 32 lanes per
 //            LDS cycle): 2W i mod 64 = 2 (W i mod 32) is distinct for 32 lanes when W is odd, and the pair {2k, 2k+1} covers
 //            every bank once -- no padding needed.  Gradient rows (GRAD) are written in place into the staged prior rows (a
@@ -26,16 +26,6 @@
 // half.  Measured 0.16 of 8 TB/s at 13 % non-zero cells: bound by the fp64 items, not the bytes.
 #define WIDE_TILE(W) ((W) > 8 ? 128 : 512)
 #define WIDE_BLOCKS_PER_CU 4
-
-// stage_dwords for a block of NT threads (stage_dwords strides by BEAR_THREADS)
-template <int NT>
-__device__ __forceinline__ void wide_stage(uint32_t *lds, const uint32_t *src, uint32_t n_dwords) {
-  const uint32_t n_vec = n_dwords >> 2;
-  const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-  uint4 *d4 = reinterpret_cast<uint4 *>(lds);
-  for (uint32_t i = threadIdx.x; i < n_vec; i += NT) d4[i] = s4[i];
-  for (uint32_t i = (n_vec << 2) + threadIdx.x; i < n_dwords; i += NT) lds[i] = src[i];
-}
 
 template <int W>
 __device__ __forceinline__ uint32_t wide_nz_mask(const uint32_t *row) {
@@ -63,8 +53,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void dm_wide_kernel(const uint32_t *_
     const uint64_t row0 = tile * T;
     const uint32_t rows = (uint32_t)((n_rows - row0 < (uint64_t)T) ? (n_rows - row0) : (uint64_t)T);
     __syncthreads();  // previous tile consumed and written back (and the log table is in place)
-    wide_stage<WIDE_THREADS>(s_cnt, counts + row0 * W, rows * W);
-    wide_stage<WIDE_THREADS>(reinterpret_cast<uint32_t *>(s_pri), reinterpret_cast<const uint32_t *>(prior + row0 * W), rows * W * 2);
+    stage_dwords<WIDE_THREADS>(s_cnt, counts + row0 * W, rows * W);
+    stage_dwords<WIDE_THREADS>(reinterpret_cast<uint32_t *>(s_pri), reinterpret_cast<const uint32_t *>(prior + row0 * W), rows * W * 2);
     __syncthreads();
 #pragma unroll 1
     for (uint32_t r = threadIdx.x; r < rows; r += WIDE_THREADS) {
@@ -225,10 +215,10 @@ __global__ __launch_bounds__(EVW_THREADS) void eval_wide_kernel(const uint32_t *
     const uint64_t row0 = tile * T;
     const uint32_t rows = (uint32_t)((n_rows - row0 < (uint64_t)T) ? (n_rows - row0) : (uint64_t)T);
     __syncthreads();
-    wide_stage<EVW_THREADS>(s_tst, test + row0 * W, rows * W);
-    if (A.has_train) wide_stage<EVW_THREADS>(s_trn, train + row0 * W, rows * W);
+    stage_dwords<EVW_THREADS>(s_tst, test + row0 * W, rows * W);
+    if (A.has_train) stage_dwords<EVW_THREADS>(s_trn, train + row0 * W, rows * W);
     if (A.has_prior)
-      wide_stage<EVW_THREADS>(reinterpret_cast<uint32_t *>(s_pri), reinterpret_cast<const uint32_t *>(prior + row0 * W), rows * W * 2);
+      stage_dwords<EVW_THREADS>(reinterpret_cast<uint32_t *>(s_pri), reinterpret_cast<const uint32_t *>(prior + row0 * W), rows * W * 2);
     __syncthreads();
     if (tid >= rows) continue;
     const uint32_t *t = s_tst + tid * W;

@@ -280,7 +280,6 @@ class Plan:
 
     def tiles(self):
         """Diagnostics (``bear_plan_tile_info``): (row0 [T] uint64, rows [T] uint32, items [T] uint32, stream_offset [T] uint64)."""
-        import numpy as np
         n = int(_lib.lib().bear_plan_tile_count(self._h))
         row0, rows, items, off = np.empty(n, np.uint64), np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.uint64)
         _lib.check(_lib.lib().bear_plan_tile_info(self._h, 0, n, row0.ctypes.data, rows.ctypes.data, items.ctypes.data, off.ctypes.data),
@@ -754,9 +753,6 @@ def cnn_backward(kmer_code, flat_params, lag, filter_width, t1, prior, grad_prio
                                               _ptr(grad), _stream())
     _lib.check(st, "bear_cnn_backward_f64")
     return grad
-
-
-LINEAR_MAX_LAG = 21
 
 
 def linear_supported(lag, alphabet_size):
