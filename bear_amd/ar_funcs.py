@@ -7,7 +7,8 @@ of the DM kernels).  Contexts are accepted in the reference's one-hot form ``[..
 avoid materialising 5.2 GB of one-hot at 1e7 contexts, as integer codes ``[..., lag]``
 (-1 = unknown letter = all-zero one-hot row).  Parameters are torch tensors with ``requires_grad``.  On
 integer codes bear_net.train fuses the linear function into the DM step (``bear_dm_linear_f64``); called on its own
-(evaluation, bear_ref.train, get_var_probs) it runs as ``bear_linear_forward_f64`` / ``bear_linear_backward_f64`` and the
+(evaluation, bear_ref.train, get_var_probs) it runs as ``bear_linear_forward_f64`` / ``bear_linear_backward_f64`` (at the protein
+alphabet's width, where no step is fused: ``bear_linear_forward_wide_f64`` / ``bear_linear_backward_wide_f64``) and the
 convolutional one as ``bear_cnn_forward_f64`` / ``bear_cnn_backward_f64``, both behind torch autograd; one-hot input (and
 shapes the kernels do not cover) takes the PyTorch-ROCm formulation, the DM kernels consume the rows either way.
 """
@@ -71,6 +72,36 @@ class _FusedLinear(torch.autograd.Function):
         return None, None, kernels.linear_backward(packed, ctx.lag, prior, grad_rows.reshape(-1, 5).to(torch.float64).contiguous())
 
 
+class _FusedLinearWide(torch.autograd.Function):
+    """The linear AR function of the protein alphabet (rows of 21) on int8 context codes as one HIP launch per direction
+    (``bear_linear_forward_wide_f64`` / ``bear_linear_backward_wide_f64``, kernels_linrows_wide.h) behind torch autograd.  Keeps the
+    codes and the forward rows for the backward pass; the no-grad path (make_ar_func_linear) does not come through here."""
+
+    @staticmethod
+    def forward(ctx, codes, lag, mat):
+        from . import kernels
+        prior = kernels.linear_forward_wide(codes, mat.detach().contiguous(), lag)
+        ctx.lag = lag
+        ctx.save_for_backward(codes, prior)
+        return prior
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        from . import kernels
+        codes, prior = ctx.saved_tensors
+        return None, None, kernels.linear_backward_wide(codes, ctx.lag, prior, grad_rows.to(torch.float64).contiguous())
+
+
+def _linear_wide(kmers, lag, mat):
+    from . import kernels
+    codes = kmers.reshape(-1, lag).to(torch.int8).contiguous()
+    if torch.is_grad_enabled() and mat.requires_grad:
+        prior = _FusedLinearWide.apply(codes, lag, mat)
+    else:
+        prior = kernels.linear_forward_wide(codes, mat.detach().contiguous(), lag)     # nothing is saved
+    return prior.reshape(kmers.shape[:-1] + (kernels.LINEAR_WIDE_WIDTH,))
+
+
 def wants_kmer_order(ar_func):
     """One forward pass (an evaluation) pays for sorting the batch by k-mer only where the forward kernel shares work between
     neighbouring contexts: the fused convolutional function (18 instead of 33 ms per 1e8 contexts).  The sums of an evaluation do
@@ -103,6 +134,8 @@ def make_ar_func_linear(lag, alphabet_size, dtype=torch.float64, device=None, ge
 
     def ar_func(kmers):
         if fused_ok and _is_codes(kmers) and kmers.is_cuda and mat.is_cuda and kmers.shape[-1] == lag and kmers.numel():
+            if alphabet_size == 20:
+                return _linear_wide(kmers, lag, mat)
             return _FusedLinear.apply(kmers, lag, mat)
         if _is_codes(kmers):
             # sum_l mat[l, a_l]: an embedding-bag over the flattened [lag * (A+1), A+1] table (unknown letters

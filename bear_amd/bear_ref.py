@@ -144,9 +144,10 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     three launches instead: ``bear_ref_mix_forward_f64``, the planned kernel with gradient rows, ``bear_ref_mix_backward_f64``
     through autograd -- the same loop as bear_net.train with two more parameters."""
     # a fused net function (linear rows / cnn kernels) shares work between neighbouring contexts: batches are kept in k-mer order
-    # (the sums do not depend on the order; cnn forward + backward 70 instead of 137 ms per 1e8 contexts, linear backward 1.45 / 2.0)
+    # (the sums do not depend on the order; cnn forward + backward 70 instead of 137 ms per 1e8 contexts, linear backward 1.45 / 2.0);
+    # the 4-letter kernels only: the rows of 21 (kernels_linrows_wide.h) share nothing between neighbours, and the sort packs 3 bits
     res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, want_codes=True, drop_empty="train",
-                                 kmer_order=bool(getattr(getattr(ar_func, "net_func", None), "fused", False)),
+                                 kmer_order=bool(getattr(getattr(ar_func, "net_func", None), "fused", False)) and _train.row_width(data) == 5,
                                  prebuild=[("train", 5, None)], per_row_extra=24 * _train.row_width(data))
 
     def prior_fn_inputs(e):

@@ -71,6 +71,7 @@ static void ws_release(bear_ws *ws) {
   (void)hipFree(ws->eval_partials);
   (void)hipFree(ws->eval_out);
   (void)hipFree(ws->lin_partials);
+  (void)hipFree(ws->linw_partials);
   (void)hipFree(ws->lin_accum);
   (void)hipFree(ws->cnn_partials);
   (void)hipFree(ws->arrive);

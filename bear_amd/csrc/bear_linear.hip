@@ -1,20 +1,25 @@
 // bear_linear.hip -- the linear AR head: k-mer packing and index words, the paired context lists of a plan, the fused DM step
-// (kernels_linear.h), the head as rows (kernels_linrows.h), and the optimizer update as a launch of its own (adam_vec_kernel).
+// (kernels_linear.h), the head as rows (kernels_linrows.h; kernels_linrows_wide.h at the protein alphabet's width), and the optimizer
+// update as a launch of its own (adam_vec_kernel).
 // The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_linear.h"
 #include "kernels_linrows.h"
+#include "kernels_linrows_wide.h"
 
 int linear_ws_setup(bear_ws *ws) {
 #define LIN_ALL_NGK(AR, PAIRED, DET)                                                                          \
   BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 0>), BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 2>), \
       BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 6>), BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 7>)
-  const int st = allow_dynamic_lds({LIN_ALL_NGK(false, false, false), LIN_ALL_NGK(true, false, false), LIN_ALL_NGK(false, true, false),
+  int st = allow_dynamic_lds({LIN_ALL_NGK(false, false, false), LIN_ALL_NGK(true, false, false), LIN_ALL_NGK(false, true, false),
                                     LIN_ALL_NGK(true, true, false), LIN_ALL_NGK(false, false, true), LIN_ALL_NGK(true, false, true),
                                     LIN_ALL_NGK(false, true, true), LIN_ALL_NGK(true, true, true)},
                                    sizeof(pln_lds_lin));
 #undef LIN_ALL_NGK
   if (st != BEAR_OK) return st;
+  st = allow_dynamic_lds({BEAR_KFN(linear_wide_forward_kernel)}, LNW_FWD_LDS(LINEAR_WIDE_MAX_LAG));
+  if (st != BEAR_OK) return st;
+  HIP_TRY(hipMalloc(&ws->linw_partials, sizeof(double) * LNW_MAX_GRAD * LNW_PARTIAL_ROWS(ws->num_cu)));
   HIP_TRY(hipMalloc(&ws->lin_partials, sizeof(double) * LIN_MAX_GRAD * (size_t)ws->num_cu * PLN_BLOCKS_PER_CU));
   HIP_TRY(hipMalloc(&ws->lin_accum, sizeof(double) * LIN_MAX_GRAD));
   HIP_TRY(hipMemset(ws->lin_accum, 0, sizeof(double) * LIN_MAX_GRAD));
@@ -294,6 +299,45 @@ int bear_linear_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_
   hipLaunchKernelGGL(linear_rows_backward_kernel, dim3(linrows_grid(ws, n_rows)), dim3(LNR_THREADS), 0, s,
                      reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, lag, prior, grad_prior, ws->lin_partials,
                      ws_arrival(ws), grad_mat);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// ---- ... and at the protein alphabet's width (kernels_linrows_wide.h): int8 code rows, mat [lag, 21, 21] in LDS ----------------
+// the backward grid is part of its result (the block partials are summed in a fixed order per grid); linw_partials holds its rows
+static int linwide_bwd_grid(const bear_ws *ws, uint64_t n_rows) {
+  return grid_capped((n_rows + LNW_BWD_TILE - 1) / LNW_BWD_TILE, (uint64_t)ws->num_cu * LNW_BWD_BLOCKS_PER_CU);
+}
+
+int bear_linear_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int width, const double *mat, double *prior,
+                                 void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (width != LNW_W || lag < 1 || lag > LINEAR_WIDE_MAX_LAG || !mat || misaligned8(mat)) return BEAR_ERR_INVALID_ARG;
+  if (n_rows == 0) return BEAR_OK;
+  if (!codes || !prior || misaligned(prior)) return BEAR_ERR_INVALID_ARG;
+  // one resident block per CU (its LDS holds mat and a tile of rows); the rows do not depend on the grid
+  const int grid = grid_capped((n_rows + LNW_FWD_TILE - 1) / LNW_FWD_TILE, (uint64_t)ws->num_cu);
+  hipLaunchKernelGGL(linear_wide_forward_kernel, dim3(grid), dim3(LNW_FWD_THREADS), LNW_FWD_LDS(lag), static_cast<hipStream_t>(stream),
+                     codes, n_rows, lag, mat, prior);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_linear_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int width, const double *prior,
+                                  const double *grad_prior, double *grad_mat, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (width != LNW_W || lag < 1 || lag > LINEAR_WIDE_MAX_LAG || !grad_mat || misaligned8(grad_mat)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_rows == 0) {
+    HIP_TRY(hipMemsetAsync(grad_mat, 0, sizeof(double) * (size_t)lag * LNW_MAT, s));
+    return BEAR_OK;
+  }
+  if (!codes || !prior || !grad_prior) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(codes) || misaligned(prior) || misaligned(grad_prior)) return BEAR_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(linear_wide_backward_kernel, dim3(linwide_bwd_grid(ws, n_rows)), dim3(LNW_BWD_THREADS), 0, s, codes, n_rows, lag, prior,
+                     grad_prior, ws->linw_partials, ws_arrival(ws), grad_mat);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }

@@ -755,7 +755,14 @@ def cnn_backward(kmer_code, flat_params, lag, filter_width, t1, prior, grad_prio
     return grad
 
 
+LINEAR_WIDE_MAX_LAG = 16   # LINEAR_WIDE_MAX_LAG of include/bear_hip.h (mat [lag, 21, 21] lives in LDS)
+LINEAR_WIDE_WIDTH = 21     # the protein alphabet: 20 letters + stop
+
+
 def linear_supported(lag, alphabet_size):
+    """The linear AR function has HIP rows for the 4-letter alphabets (packed contexts) and for the protein alphabet (int8 codes)."""
+    if alphabet_size == 20:
+        return 1 <= lag <= LINEAR_WIDE_MAX_LAG
     return alphabet_size == 4 and 1 <= lag <= LINEAR_MAX_LAG
 
 
@@ -790,6 +797,49 @@ def linear_backward(kmer_code, lag, prior, grad_prior, ws=None):
         st = _lib.lib().bear_linear_backward_f64(ws.handle, _ptr(kmer_code), n, int(lag), _ptr(prior), _ptr(grad_prior), _ptr(grad),
                                                  _stream())
     _lib.check(st, "bear_linear_backward_f64")
+    return grad
+
+
+def _check_codes_wide(codes, lag):
+    if not (codes.is_cuda and codes.dtype == torch.int8 and codes.dim() == 2 and codes.shape[1] == lag and codes.is_contiguous()):
+        raise ValueError("codes must be a contiguous CUDA int8 tensor [n, lag]")
+    if codes.data_ptr() % 16:
+        codes = codes.clone()
+    return codes
+
+
+def linear_forward_wide(codes, mat, lag, ws=None):
+    """One launch of ``bear_linear_forward_wide_f64``: the rows softmax(sum_l mat[l, codes[l], :]) [n, 21] of protein contexts
+    (int8 codes: 0..19 residues, 20 = '[', -1 = unknown letter)."""
+    W = LINEAR_WIDE_WIDTH
+    codes = _check_codes_wide(codes, lag)
+    if not (mat.is_cuda and mat.dtype == torch.float64 and mat.is_contiguous() and tuple(mat.shape) == (lag, W, W)):
+        raise ValueError(f"mat must be a contiguous CUDA float64 tensor [lag, {W}, {W}]")
+    n = codes.shape[0]
+    ws = ws or default_workspace(codes.device)
+    prior = torch.empty((n, W), dtype=torch.float64, device=codes.device)
+    with torch.cuda.device(codes.device):
+        st = _lib.lib().bear_linear_forward_wide_f64(ws.handle, _ptr(codes), n, int(lag), W, _ptr(mat), _ptr(prior), _stream())
+    _lib.check(st, "bear_linear_forward_wide_f64")
+    return prior
+
+
+def linear_backward_wide(codes, lag, prior, grad_prior, ws=None):
+    """One launch of ``bear_linear_backward_wide_f64``: d L / d mat [lag, 21, 21] from the forward rows and d L / d prior.  No
+    floating-point atomics: the same inputs give the same bits."""
+    W = LINEAR_WIDE_WIDTH
+    codes = _check_codes_wide(codes, lag)
+    n = codes.shape[0]
+    prior = _check_rows_wide(prior, torch.float64, "prior", W)
+    grad_prior = _check_rows_wide(grad_prior, torch.float64, "grad_prior", W)
+    if prior.shape[0] != n or grad_prior.shape[0] != n:
+        raise ValueError("codes, prior and grad_prior must have the same number of rows")
+    ws = ws or default_workspace(codes.device)
+    grad = torch.empty((lag, W, W), dtype=torch.float64, device=codes.device)
+    with torch.cuda.device(codes.device):
+        st = _lib.lib().bear_linear_backward_wide_f64(ws.handle, _ptr(codes), n, int(lag), W, _ptr(prior), _ptr(grad_prior), _ptr(grad),
+                                                      _stream())
+    _lib.check(st, "bear_linear_backward_wide_f64")
     return grad
 
 

@@ -36,10 +36,11 @@
 extern "C" {
 #endif
 
-#define BEAR_ABI_VERSION 9 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
+#define BEAR_ABI_VERSION 10 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
                               8: + bear_logdir_sample_wide_f64;
                               9: + bear_kmer_sort_create_wide, bear_fastx_size_wide, bear_fastx_encode_wide, bear_write_counts_tsv_wide,
-                                 bear_encode_kmers_i8 mode 2 (protein count tables from sequence files) */
+                                 bear_encode_kmers_i8 mode 2 (protein count tables from sequence files);
+                              10: + bear_linear_forward_wide_f64, bear_linear_backward_wide_f64 (the linear AR function as rows of 21) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -337,6 +338,25 @@ int bear_linear_forward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_r
                             void *stream);
 int bear_linear_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows, int lag, const double *prior,
                              const double *grad_prior, double *grad_mat, void *stream);
+
+/*
+ * The same at the protein alphabet's row width (20 letters + stop): make_ar_func_linear(lag, 20)'s ar_func and its gradient.
+ *   codes      [dev] int8 [n_rows,lag]   context letters, 16-byte aligned: 0..19 residues, 20 = '[', anything else (-1) an unknown
+ *                                        letter = an all-zero one-hot row (bear_encode_kmers_i8 mode 2); there is no packed form
+ *   width      21 (anything else: BEAR_ERR_INVALID_ARG); lag 1 .. LINEAR_WIDE_MAX_LAG (mat lives in LDS; else BEAR_ERR_INVALID_ARG)
+ *   mat        [dev] double [lag,21,21]  the AR parameter
+ *   forward:   prior [dev] double [n_rows,21] = softmax(sum_l mat[l, codes[l], :]) (max-shifted), 16-byte aligned
+ *   backward:  prior = the forward rows, grad_prior [dev] double [n_rows,21] = d L / d prior (both 16-byte aligned);
+ *              grad_mat [dev] double [lag,21,21] = d L / d mat, overwritten (n_rows == 0: zeros).  An fp64 matrix product per block,
+ *              block partials summed in a fixed order: NO floating-point atomics -- the same inputs give the same bits from run to
+ *              run for a given device (grid: min(n_rows / 128, 2 x CUs) blocks), identically in both builds of the library.
+ * Row order: any.  Asynchronous on `stream`, nothing is read back to the host (both can be captured into a HIP graph); one launch each.
+ */
+#define LINEAR_WIDE_MAX_LAG 16
+int bear_linear_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int width, const double *mat,
+                                 double *prior, void *stream);
+int bear_linear_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int width, const double *prior,
+                                  const double *grad_prior, double *grad_mat, void *stream);
 
 /*
  * bear_ref's prior rows for a net function with parameters (linear, cnn): replaces the arithmetic of _make_ref_ar_func's ar_func
