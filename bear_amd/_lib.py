@@ -23,7 +23,7 @@ def _deterministic_requested():
 # parameter gradients over per call; BEAR_AMD_LIB: developer A/B builds.
 LIB_PATH = os.environ.get("BEAR_AMD_LIB") or os.path.join(_HERE, "libbear_hip_det.so" if _deterministic_requested() else "libbear_hip.so")
 
-ABI_VERSION = 10  # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
+ABI_VERSION = 11  # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
 
 SYMBOLS = [
     "bear_abi_version", "bear_strerror", "bear_last_hip_error", "bear_ws_create", "bear_ws_destroy",
@@ -43,6 +43,7 @@ SYMBOLS = [
     "bear_logdir_sample_wide_f64",
     "bear_kmer_sort_create_wide", "bear_fastx_size_wide", "bear_fastx_encode_wide", "bear_write_counts_tsv_wide",
     "bear_linear_forward_wide_f64", "bear_linear_backward_wide_f64",
+    "bear_cnn_param_count_wide", "bear_cnn_forward_wide_f64", "bear_cnn_backward_wide_f64",
 ]
 
 
@@ -117,6 +118,9 @@ def _load():
     L.bear_cnn_param_count.argtypes = [cint, cint, cint, cint]
     L.bear_cnn_forward_f64.argtypes = [vp, vp, u64, cint, cint, cint, cint, vp, vp, vp, vp]
     L.bear_cnn_backward_f64.argtypes = [vp, vp, u64, cint, cint, cint, cint, vp, vp, vp, vp, vp, vp]
+    L.bear_cnn_param_count_wide.argtypes = [cint, cint, cint, cint, cint]
+    L.bear_cnn_forward_wide_f64.argtypes = [vp, vp, u64, cint, cint, cint, cint, cint, vp, vp, vp, vp]
+    L.bear_cnn_backward_wide_f64.argtypes = [vp, vp, u64, cint, cint, cint, cint, cint, vp, vp, vp, vp, vp, vp]
     L.bear_linear_forward_f64.argtypes = [vp, vp, u64, cint, vp, vp, vp]
     L.bear_linear_backward_f64.argtypes = [vp, vp, u64, cint, vp, vp, vp, vp]
     L.bear_linear_forward_wide_f64.argtypes = [vp, vp, u64, cint, cint, vp, vp, vp]

@@ -9,7 +9,8 @@ avoid materialising 5.2 GB of one-hot at 1e7 contexts, as integer co
 integer codes bear_net.train fuses the linear function into the DM step (``bear_dm_linear_f64``); called on its own
 (evaluation, bear_ref.train, get_var_probs) it runs as ``bear_linear_forward_f64`` / ``bear_linear_backward_f64`` (at the protein
 alphabet's width, where no step is fused: ``bear_linear_forward_wide_f64`` / ``bear_linear_backward_wide_f64``) and the
-convolutional one as ``bear_cnn_forward_f64`` / ``bear_cnn_backward_f64``, both behind torch autograd; one-hot input (and
+convolutional one as ``bear_cnn_forward_f64`` / ``bear_cnn_backward_f64`` (protein: ``bear_cnn_forward_wide_f64`` /
+``bear_cnn_backward_wide_f64``), both behind torch autograd; one-hot input (and
 shapes the kernels do not cover) takes the PyTorch-ROCm formulation, the DM kernels consume the rows either way.
 """
 import numpy as np
@@ -100,6 +101,45 @@ def _linear_wide(kmers, lag, mat):
     else:
         prior = kernels.linear_forward_wide(codes, mat.detach().contiguous(), lag)     # nothing is saved
     return prior.reshape(kmers.shape[:-1] + (kernels.LINEAR_WIDE_WIDTH,))
+
+
+class _FusedCnnWide(torch.autograd.Function):
+    """The convolutional AR function of the protein alphabet (rows of 21) on int8 context codes as one HIP launch per direction
+    (``bear_cnn_forward_wide_f64`` / ``bear_cnn_backward_wide_f64``, kernels_cnn_wide.h) behind torch autograd.  Keeps the codes, the
+    flat parameters, the layer-1 sums and the forward rows for the backward pass; the no-grad path (_cnn_wide) does not come
+    through here."""
+
+    @staticmethod
+    def forward(ctx, codes, lag, filter_width, *params):
+        from . import kernels
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+        prior, t1 = kernels.cnn_forward_wide(codes, flat, lag, filter_width, save=True)
+        ctx.lag, ctx.fw, ctx.shapes = lag, filter_width, [p.shape for p in params]
+        ctx.save_for_backward(codes, flat, t1, prior)
+        return prior
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        from . import kernels
+        codes, flat, t1, prior = ctx.saved_tensors
+        g = kernels.cnn_backward_wide(codes, flat, ctx.lag, ctx.fw, t1, prior, grad_rows.to(torch.float64).contiguous())
+        out, k = [], 0
+        for shp in ctx.shapes:
+            n = int(np.prod(shp))
+            out.append(g[k:k + n].reshape(shp))
+            k += n
+        return (None, None, None) + tuple(out)
+
+
+def _cnn_wide(data, lag, filter_width, params):
+    from . import kernels
+    codes = data.reshape(-1, lag).to(torch.int8).contiguous()
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        prior = _FusedCnnWide.apply(codes, lag, filter_width, *params)
+    else:
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+        prior = kernels.cnn_forward_wide(codes, flat, lag, filter_width, save=False)[0]     # nothing is saved
+    return prior.reshape(data.shape[:-1] + (kernels.LINEAR_WIDE_WIDTH,))
 
 
 def wants_kmer_order(ar_func):
@@ -197,7 +237,10 @@ def make_ar_func_cnn(lag, alphabet_size, filter_width=8, num_filters=30, kmer_la
     fused_ok = dtype == torch.float64 and kernels.cnn_supported(lag, alphabet_size, filter_width, num_filters, kmer_layer1_width)
 
     def ar_func(data):
-        if fused_ok and _is_codes(data) and data.is_cuda and data.shape[-1] == lag:
+        if fused_ok and alphabet_size == 20:
+            if _is_codes(data) and data.is_cuda and filters.is_cuda and data.shape[-1] == lag and data.numel():
+                return _cnn_wide(data, lag, filter_width, params)
+        elif fused_ok and _is_codes(data) and data.is_cuda and data.shape[-1] == lag:
             if torch.is_grad_enabled() and any(p.requires_grad for p in params):
                 return _FusedCnn.apply(data, lag, filter_width, *params)
             flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()

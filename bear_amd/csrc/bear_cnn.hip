@@ -1,9 +1,25 @@
 // bear_cnn.hip -- the convolutional AR head (kernels_cnn.h): forward and backward passes, the prefix levels and window tables a
-// plan keeps for it (bear_levels.h), and its training step around the planned DM step of bear_hip.hip.  The other units: bear_host.h.
+// plan keeps for it (bear_levels.h), and its training step around the planned DM step of bear_hip.hip; the head as rows at the
+// protein alphabet's width (kernels_cnn_wide.h).  The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_cnn.h"
+#include "kernels_cnn_wide.h"
 
-int cnn_ws_setup(bear_ws *) { return allow_dynamic_lds({BEAR_KFN(cnn_backward_head_kernel)}, cnh_lds_bytes()); }
+int cnn_ws_setup(bear_ws *ws) {
+  int st = allow_dynamic_lds({BEAR_KFN(cnn_backward_head_kernel)}, cnh_lds_bytes());
+  if (st != BEAR_OK) return st;
+  // (linear in the filter width at a given lag: the ends are the extremes)
+  const size_t fwd_lds = cnw_fwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG) > cnw_fwd_lds(CNN_WIDE_MAX_LAG, 1) ? cnw_fwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG)
+                                                                                                             : cnw_fwd_lds(CNN_WIDE_MAX_LAG, 1);
+  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_forward_kernel)}, fwd_lds);
+  if (st != BEAR_OK) return st;
+  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_backward_kernel)}, cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG) > cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1)
+                                                                    ? cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG)
+                                                                    : cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1));
+  if (st != BEAR_OK) return st;
+  HIP_TRY(hipMalloc(&ws->cnnw_partials, sizeof(double) * CNW_MAX_TOTAL * CNW_PARTIAL_ROWS(ws->num_cu)));
+  return BEAR_OK;
+}
 
 #ifdef CNN_STAMPS
 extern "C" int bear_dbg_cnn_stamps(unsigned long long *host_out, int reset) {   // developer build only
@@ -473,4 +489,59 @@ int bear_net_cnn_train_step_f64(bear_ws *ws, const bear_plan *plan, const uint32
   const cnn_dims D = cnn_make_dims(lag, filter_width);
   return launch_train_apply(theta, 1 + D.total, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap,
                             static_cast<hipStream_t>(stream));
+}
+
+// ---- the convolutional AR function as rows at the protein alphabet's width (kernels_cnn_wide.h): int8 code rows, no plan ----------
+static bool cnn_wide_shape_ok(int lag, int fw, int nf, int l1, int width) {
+  return width == CNW_W && nf == CNN_NF && l1 == CNN_L1 && fw >= 1 && fw <= lag && lag <= CNN_WIDE_MAX_LAG;
+}
+
+int bear_cnn_param_count_wide(int lag, int filter_width, int num_filters, int layer1_width, int width) {
+  if (!cnn_wide_shape_ok(lag, filter_width, num_filters, layer1_width, width)) return BEAR_ERR_INVALID_ARG;
+  return cnw_make_dims(lag, filter_width).total;
+}
+
+// the backward grid is part of its result (the block partials are summed in a fixed order per grid); cnnw_partials holds its rows
+static int cnnwide_bwd_grid(const bear_ws *ws, uint64_t n_rows) {
+  return grid_capped((n_rows + CNW_BWD_TILE - 1) / CNW_BWD_TILE, (uint64_t)ws->num_cu * CNW_BWD_BLOCKS_PER_CU);
+}
+
+int bear_cnn_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int filter_width, int num_filters,
+                              int layer1_width, int width, const double *params, double *prior, double *t1_save, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!cnn_wide_shape_ok(lag, filter_width, num_filters, layer1_width, width) || !params || misaligned8(params)) return BEAR_ERR_INVALID_ARG;
+  if (n_rows == 0) return BEAR_OK;
+  if (!codes || !prior || misaligned(codes) || misaligned(prior) || misaligned(t1_save)) return BEAR_ERR_INVALID_ARG;
+  const cnn_dims D = cnw_make_dims(lag, filter_width);
+  // two resident blocks per CU where their LDS lets them in (short filters), else one; the rows do not depend on the grid
+  const size_t lds = cnw_fwd_lds(lag, filter_width);
+  const uint64_t per_cu = 2 * lds <= 160u * 1024u ? 2 : 1;
+  const int grid = grid_capped((n_rows + CNW_FWD_TILE - 1) / CNW_FWD_TILE, (uint64_t)ws->num_cu * per_cu);
+  hipLaunchKernelGGL(cnn_wide_forward_kernel, dim3(grid), dim3(CNW_FWD_THREADS), lds, static_cast<hipStream_t>(stream), codes, n_rows, D,
+                     params, prior, t1_save);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_cnn_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int filter_width, int num_filters,
+                               int layer1_width, int width, const double *params, const double *t1_save, const double *prior,
+                               const double *grad_prior, double *grad_params, void *stream) {
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!cnn_wide_shape_ok(lag, filter_width, num_filters, layer1_width, width) || !params || !grad_params || misaligned8(params) ||
+      misaligned8(grad_params))
+    return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const cnn_dims D = cnw_make_dims(lag, filter_width);
+  if (n_rows == 0) {
+    HIP_TRY(hipMemsetAsync(grad_params, 0, sizeof(double) * (size_t)D.total, s));
+    return BEAR_OK;
+  }
+  if (!codes || !t1_save || !prior || !grad_prior) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(codes) || misaligned(t1_save) || misaligned(prior) || misaligned(grad_prior)) return BEAR_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(cnn_wide_backward_kernel, dim3(cnnwide_bwd_grid(ws, n_rows)), dim3(CNW_BWD_THREADS), cnw_bwd_lds(lag, filter_width), s, codes,
+                     n_rows, D, params, t1_save, prior, grad_prior, ws->cnnw_partials, ws_arrival(ws), grad_params);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
 }

@@ -43,6 +43,7 @@ struct bear_ws {
   unsigned epoch;                  // host side: the stamp of the last launch that used `arrive` (never 0)
   double *cnn_partials;     // [cnn_blocks][cnn total] parameter-gradient partials (kernels_cnn.h), grown on demand
   size_t cnn_partials_cap;  // doubles
+  double *cnnw_partials;    // [num_cu + 16][CNW_MAX_TOTAL] parameter-gradient partials at width 21 (kernels_cnn_wide.h)
 };
 
 struct bear_params {

@@ -74,6 +74,7 @@ static void ws_release(bear_ws *ws) {
   (void)hipFree(ws->linw_partials);
   (void)hipFree(ws->lin_accum);
   (void)hipFree(ws->cnn_partials);
+  (void)hipFree(ws->cnnw_partials);
   (void)hipFree(ws->arrive);
   delete ws;
 }

@@ -25,25 +25,10 @@
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"
+#include "rows_wide_common.h"   // LNW_W, lnw_store_tile, lnw_sum_rows / lnw_sum_partials
 
-#define LNW_W 21
 #define LNW_MAT (LNW_W * LNW_W)                        // doubles of mat per position
 #define LNW_MAX_GRAD (LINEAR_WIDE_MAX_LAG * LNW_MAT)
-
-typedef double lnw_d4 __attribute__((ext_vector_type(4)));
-typedef uint32_t lnw_v4u __attribute__((ext_vector_type(4)));
-
-// rows [0, rows) of an LDS tile of 21-wide fp64 rows to dst (16-byte aligned) as 16-byte stores; nontemporal: not read again here
-template <int NT>
-__device__ __forceinline__ void lnw_store_tile(const double *tile, double *__restrict__ dst, uint32_t rows) {
-  const uint32_t n_dw = rows * LNW_W * 2, n_vec = n_dw >> 2;
-  const lnw_v4u *s4 = reinterpret_cast<const lnw_v4u *>(tile);
-  lnw_v4u *d4 = reinterpret_cast<lnw_v4u *>(dst);
-  for (uint32_t i = threadIdx.x; i < n_vec; i += NT) __builtin_nontemporal_store(s4[i], d4 + i);
-  const uint32_t *s1 = reinterpret_cast<const uint32_t *>(tile);
-  uint32_t *d1 = reinterpret_cast<uint32_t *>(dst);
-  for (uint32_t i = (n_vec << 2) + threadIdx.x; i < n_dw; i += NT) d1[i] = s1[i];
-}
 
 // ------------------------------------------------------------------ forward
 #define LNW_FWD_THREADS 512
@@ -108,24 +93,6 @@ __global__ __launch_bounds__(LNW_FWD_THREADS) void linear_wide_forward_kernel(co
 #define LNW_RT_PER_WAVE ((LNW_MAX_RT + LNW_BWD_WAVES - 1) / LNW_BWD_WAVES)
 // rows of the partials buffer: one per block, then one per residue class of the block numbers (bear_arrive_last's counters)
 #define LNW_PARTIAL_ROWS(num_cu) ((size_t)(num_cu) * LNW_BWD_BLOCKS_PER_CU + BEAR_ARRIVE_SUBS)
-
-// dst[k] = src[first][k] + src[first + step][k] + ... (cnt rows of n_grad doubles, in that order), k over the block's threads
-template <bool AGENT>
-__device__ __forceinline__ void lnw_sum_rows(const double *__restrict__ src, uint32_t first, uint32_t step, uint32_t cnt, int n_grad,
-                                             double *__restrict__ dst) {
-  for (int k = threadIdx.x; k < n_grad; k += LNW_BWD_THREADS) {
-    double s = 0.0;
-    for (uint32_t i = 0; i < cnt; i += 8) {              // eight independent loads in flight, added in order
-      double v[8];
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) v[j] = i + j < cnt ? src[(size_t)(first + (i + j) * step) * n_grad + k] : 0.0;
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) s += v[j];
-    }
-    if (AGENT) bear_store_agent(&dst[k], s);
-    else dst[k] = s;
-  }
-}
 
 __global__ __launch_bounds__(LNW_BWD_THREADS) void linear_wide_backward_kernel(const int8_t *__restrict__ codes, uint64_t n, int lag,
                                                                                const double *__restrict__ prior,
@@ -218,27 +185,6 @@ __global__ __launch_bounds__(LNW_BWD_THREADS) void linear_wide_backward_kernel(c
         if (lr < LNW_W - 16) bear_store_agent(&mine[row * LNW_W + 16 + (int)lr], acc[j][1][r]);
       }
     }
-  // ---- fixed-order sum in two levels over the counters of bear_arrive_last: a block arrives at the counter of its number mod 16;
-  // the last one there sums that class, ascending, into the row behind the blocks' and arrives at the top word; the last one
-  // there sums the class rows.  Which block does either is arbitrary, what it adds in which order is not.
-  const unsigned grid = gridDim.x, sub = blockIdx.x % BEAR_ARRIVE_SUBS;
-  const unsigned in_sub = (grid - sub + BEAR_ARRIVE_SUBS - 1u) / BEAR_ARRIVE_SUBS;
-  const unsigned subs = grid < BEAR_ARRIVE_SUBS ? grid : BEAR_ARRIVE_SUBS;
-  const unsigned long long tag = (unsigned long long)arrive.epoch << 24;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this block's partials are acknowledged (bear_arrive_last)
-  __syncthreads();
-  if (tid == 0) s_flag = bear_arrive_count(arrive.word + (1u + sub) * BEAR_ARRIVE_STRIDE, tag, in_sub) ? 1u : 0u;
-  __syncthreads();
-  if (!s_flag) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  double *classes = partials + (size_t)grid * n_grad;
-  lnw_sum_rows<true>(partials, sub, BEAR_ARRIVE_SUBS, in_sub, n_grad, classes + (size_t)sub * n_grad);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) s_flag = bear_arrive_count(arrive.word, tag, subs) ? 1u : 0u;
-  __syncthreads();
-  if (!s_flag) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  lnw_sum_rows<false>(classes, 0, 1, subs, n_grad, grad_mat);
-  if (tid == 0) bear_arrive_reset(arrive);
+  // ---- fixed-order sum in two levels over the counters of bear_arrive_last (rows_wide_common.h)
+  lnw_sum_partials<LNW_BWD_THREADS>(partials, n_grad, arrive, &s_flag, grad_mat);
 }

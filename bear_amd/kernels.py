@@ -694,9 +694,19 @@ def shuffle_source_row(i, n_rows, seed):
 CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, CNN_MAX_LAG = 30, 16, 21   # CNN_NF / CNN_L1 / CNN_MAX_LAG of kernels_cnn.h
 
 
+CNN_WIDE_MAX_LAG = 16      # CNN_WIDE_MAX_LAG of include/bear_hip.h (the filter image and a tile's staged rows live in LDS)
+
+
 def cnn_supported(lag, alphabet_size, filter_width, num_filters, kmer_layer1_width):
-    return (alphabet_size == 4 and num_filters == CNN_NUM_FILTERS and kmer_layer1_width == CNN_LAYER1_WIDTH
-            and 1 <= filter_width <= lag <= CNN_MAX_LAG)
+    """The convolutional AR function has HIP kernels for the 4-letter alphabets (packed contexts) and, as rows, for the protein
+    alphabet (int8 codes).  At width 21, forward + backward measured 13x to 100x faster than the torch formulation at every shape
+    timed -- lag / filter width 1/1, 4/1, 5/3, 12/8, 16/8 at 1e6 and 1e7 contexts (profiles/prot_cnn_time.jsonl) --
+    so every shape the kernels take is covered."""
+    if not (num_filters == CNN_NUM_FILTERS and kmer_layer1_width == CNN_LAYER1_WIDTH):
+        return False
+    if alphabet_size == 20:
+        return 1 <= filter_width <= lag <= CNN_WIDE_MAX_LAG
+    return alphabet_size == 4 and 1 <= filter_width <= lag <= CNN_MAX_LAG
 
 
 def cnn_param_count(lag, filter_width):
@@ -840,6 +850,59 @@ def linear_backward_wide(codes, lag, prior, grad_prior, ws=None):
         st = _lib.lib().bear_linear_backward_wide_f64(ws.handle, _ptr(codes), n, int(lag), W, _ptr(prior), _ptr(grad_prior), _ptr(grad),
                                                       _stream())
     _lib.check(st, "bear_linear_backward_wide_f64")
+    return grad
+
+
+def cnn_param_count_wide(lag, filter_width):
+    n = _lib.lib().bear_cnn_param_count_wide(int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, LINEAR_WIDE_WIDTH)
+    _lib.check(min(n, 0), "bear_cnn_param_count_wide")
+    return n
+
+
+def _check_params_wide(flat_params, lag, filter_width):
+    if not (flat_params.is_cuda and flat_params.dtype == torch.float64 and flat_params.dim() == 1 and flat_params.is_contiguous()
+            and flat_params.numel() == cnn_param_count_wide(lag, filter_width)):
+        raise ValueError("flat_params must be the contiguous CUDA float64 parameter vector of bear_cnn_param_count_wide elements")
+
+
+def cnn_forward_wide(codes, flat_params, lag, filter_width, save=True, ws=None):
+    """One launch of ``bear_cnn_forward_wide_f64``: (prior [n, 21], t1 [n, 16] or None) of protein contexts (int8 codes: 0..19
+    residues, 20 = '[', -1 = unknown letter)."""
+    W = LINEAR_WIDE_WIDTH
+    codes = _check_codes_wide(codes, lag)
+    _check_params_wide(flat_params, lag, filter_width)
+    n = codes.shape[0]
+    ws = ws or default_workspace(codes.device)
+    prior = torch.empty((n, W), dtype=torch.float64, device=codes.device)
+    t1 = torch.empty((n, CNN_LAYER1_WIDTH), dtype=torch.float64, device=codes.device) if save else None
+    with torch.cuda.device(codes.device):
+        st = _lib.lib().bear_cnn_forward_wide_f64(ws.handle, _ptr(codes), n, int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH,
+                                                  W, _ptr(flat_params), _ptr(prior), _ptr(t1), _stream())
+    _lib.check(st, "bear_cnn_forward_wide_f64")
+    return prior, t1
+
+
+def cnn_backward_wide(codes, flat_params, lag, filter_width, t1, prior, grad_prior, ws=None):
+    """One launch of ``bear_cnn_backward_wide_f64``: d L / d flat_params from the forward rows, the kept layer-1 sums and
+    d L / d prior.  No floating-point atomics: the same inputs give the same bits."""
+    W = LINEAR_WIDE_WIDTH
+    codes = _check_codes_wide(codes, lag)
+    _check_params_wide(flat_params, lag, filter_width)
+    n = codes.shape[0]
+    prior = _check_rows_wide(prior, torch.float64, "prior", W)
+    grad_prior = _check_rows_wide(grad_prior, torch.float64, "grad_prior", W)
+    if not (t1.is_cuda and t1.dtype == torch.float64 and t1.dim() == 2 and t1.shape[1] == CNN_LAYER1_WIDTH and t1.is_contiguous()):
+        raise ValueError("t1 must be a contiguous CUDA float64 tensor [n, 16] (cnn_forward_wide with save=True)")
+    if t1.data_ptr() % 16:
+        t1 = t1.clone()
+    if prior.shape[0] != n or grad_prior.shape[0] != n or t1.shape[0] != n:
+        raise ValueError("codes, t1, prior and grad_prior must have the same number of rows")
+    ws = ws or default_workspace(codes.device)
+    grad = torch.empty_like(flat_params)
+    with torch.cuda.device(codes.device):
+        st = _lib.lib().bear_cnn_backward_wide_f64(ws.handle, _ptr(codes), n, int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH,
+                                                   W, _ptr(flat_params), _ptr(t1), _ptr(prior), _ptr(grad_prior), _ptr(grad), _stream())
+    _lib.check(st, "bear_cnn_backward_wide_f64")
     return grad
 
 

@@ -36,11 +36,13 @@
 extern "C" {
 #endif
 
-#define BEAR_ABI_VERSION 10 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
+#define BEAR_ABI_VERSION 11 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
                               8: + bear_logdir_sample_wide_f64;
                               9: + bear_kmer_sort_create_wide, bear_fastx_size_wide, bear_fastx_encode_wide, bear_write_counts_tsv_wide,
                                  bear_encode_kmers_i8 mode 2 (protein count tables from sequence files);
-                              10: + bear_linear_forward_wide_f64, bear_linear_backward_wide_f64 (the linear AR function as rows of 21) */
+                              10: + bear_linear_forward_wide_f64, bear_linear_backward_wide_f64 (the linear AR function as rows of 21);
+                              11: + bear_cnn_param_count_wide, bear_cnn_forward_wide_f64, bear_cnn_backward_wide_f64 (the convolutional AR
+                                  function as rows of 21) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -421,6 +423,37 @@ int bear_cnn_forward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows
 int bear_cnn_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows, int lag, int filter_width, int num_filters,
                           int layer1_width, const double *params, const double *t1_save, const double *prior,
                           const double *grad_prior, double *grad_params, void *stream);
+
+/*
+ * The same at the protein alphabet's row width (20 letters + stop): make_ar_func_cnn(lag, 20)'s ar_func and its gradient, as a plain
+ * pair of row kernels (protein batches are not k-mer sorted and share no windows: no plan, no prefix levels).
+ *   codes      [dev] int8 [n_rows,lag]   context letters, 16-byte aligned: 0..19 residues, 20 = '[', anything else (-1) an unknown
+ *                                        letter = an all-zero one-hot row; there is no packed form
+ *   width 21, num_filters 30, layer1_width 16, 1 <= filter_width <= lag <= CNN_WIDE_MAX_LAG; anything else: BEAR_ERR_INVALID_ARG
+ *              (bear_cnn_param_count_wide returns the same code).  CNN_WIDE_MAX_LAG: the backward kernel keeps the filter image of
+ *              filter_width taps (5208 B each, rows of 30 at a stride of 31) and the weights of the positions (4320 B each) next
+ *              to the staged rows of a tile of 64 contexts (72 KiB) in a CU's 160 KiB of LDS -- 158 KiB at filter_width = lag =
+ *              16, 17 taps do not fit -- and the positions are the 16 rows of one matrix tile.
+ *   params     [dev] double [bear_cnn_param_count_wide(...)]  the reference's order: filters [fw,21,nf], intercept0 [P,nf],
+ *              weights1 [P,nf,l1], intercept1 [l1], weights2 [l1,21], intercept2 [21], scale0 [P,nf], scale1 [l1];  P = lag - fw + 1
+ *   forward:   prior [dev] double [n_rows,21] = ar_func rows; t1_save [dev, nullable] double [n_rows,16] = the layer-1
+ *              pre-normalisation sums for the backward entry (both 16-byte aligned)
+ *   backward:  prior, t1_save = what the forward entry wrote; grad_prior [dev] double [n_rows,21] = d L / d prior (16-byte aligned);
+ *              grad_params [dev] double [param_count] = d L / d params, overwritten (n_rows == 0: zeros, nothing is launched).
+ *              Every sum over contexts is an fp64 matrix product per block; block partials are summed in a fixed order: NO
+ *              floating-point atomics -- the same inputs give the same bits from run to run for a given device (grid:
+ *              min(ceil(n_rows / 64), CUs) blocks, at least one), identically in both builds of the library.  A tile of 64 contexts whose grad_prior
+ *              rows are all zero is skipped.
+ * Row order: any.  Asynchronous on `stream`, no allocation, nothing is read back to the host (both can be captured into a HIP
+ * graph); one launch each.
+ */
+#define CNN_WIDE_MAX_LAG 16
+int bear_cnn_param_count_wide(int lag, int filter_width, int num_filters, int layer1_width, int width);
+int bear_cnn_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int filter_width, int num_filters,
+                              int layer1_width, int width, const double *params, double *prior, double *t1_save, void *stream);
+int bear_cnn_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int filter_width, int num_filters,
+                               int layer1_width, int width, const double *params, const double *t1_save, const double *prior,
+                               const double *grad_prior, double *grad_params, void *stream);
 
 /*
  * Held-out evaluation, one pass over a row range: replaces _evaluation_step of bear_model/bear_net.py:323-371
