@@ -23,7 +23,7 @@ def _deterministic_requested():
 # parameter gradients over per call; BEAR_AMD_LIB: developer A/B builds.
 LIB_PATH = os.environ.get("BEAR_AMD_LIB") or os.path.join(_HERE, "libbear_hip_det.so" if _deterministic_requested() else "libbear_hip.so")
 
-ABI_VERSION = 11  # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
+ABI_VERSION = 12  # BEAR_ABI_VERSION of include/bear_hip.h the argtypes below were written against
 
 SYMBOLS = [
     "bear_abi_version", "bear_strerror", "bear_last_hip_error", "bear_ws_create", "bear_ws_destroy",
@@ -44,6 +44,7 @@ SYMBOLS = [
     "bear_kmer_sort_create_wide", "bear_fastx_size_wide", "bear_fastx_encode_wide", "bear_write_counts_tsv_wide",
     "bear_linear_forward_wide_f64", "bear_linear_backward_wide_f64",
     "bear_cnn_param_count_wide", "bear_cnn_forward_wide_f64", "bear_cnn_backward_wide_f64",
+    "bear_dm_ref_wide_f64", "bear_ref_train_reduce_wide_f64", "bear_ref_train_step_wide_f64", "bear_dm_refmix_wide_grad_f64",
 ]
 
 
@@ -177,6 +178,10 @@ def _load():
     L.bear_fastx_size_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.bear_fastx_encode_wide.argtypes = [ctypes.c_char_p, cint, cint, cint, cint, u64, vp, vp, ctypes.POINTER(u64)]
     L.bear_write_counts_tsv_wide.argtypes = [ctypes.c_char_p, vp, vp, u64, cint, cint, cint, u64, u64, cint]
+    L.bear_dm_ref_wide_f64.argtypes = [vp, vp, vp, u64, cint, dbl, dbl, dbl, dbl, cint, vp, vp]
+    L.bear_ref_train_reduce_wide_f64.argtypes = [vp, vp, vp, u64, cint, vp, dbl, cint, vp, vp]
+    L.bear_ref_train_step_wide_f64.argtypes = [vp, vp, vp, u64, cint, vp, vp, vp, vp, dbl, cint, dbl, dbl, vp, vp, u64, vp]
+    L.bear_dm_refmix_wide_grad_f64.argtypes = [vp, vp, vp, vp, u64, cint, vp, vp, vp, dbl, cint, vp, vp, vp]
     _lib = L
     return L
 

@@ -710,7 +710,8 @@ def run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, repeats, lear
     ``ref_mix = (net_fn, ref_fn, tau_signed, net_weight_signed)`` (bear_ref with a net function that has parameters and
     normalised rows): ``net_fn(batch entry)`` are the NET rows (autograd), ``ref_fn(batch entry)`` the reference rows, and the
     mixing of bear_ref.py:63-68 happens inside the DM kernel (``bear_dm_refmix_plan_grad_f64``), which also returns the gradients
-    of the two mixing parameters; ``prior_fn`` is then not called."""
+    of the two mixing parameters; ``prior_fn`` is then not called.  On rows of 21 the kernel is ``bear_dm_refmix_wide_grad_f64``,
+    ``ref_fn`` returns the reference COUNT rows and the net rows need not be normalised."""
     with torch.no_grad():
         theta = torch.cat([p.detach().reshape(-1).to(device=device, dtype=torch.float64) for p in params]).contiguous()
         k = 0
@@ -736,12 +737,17 @@ def run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, repeats, lear
             if e["rows"] and ref_mix is not None:
                 net_fn, ref_fn, tau_p, nw_p = ref_mix
                 net = net_fn(e)
-                if not promise_checked[0]:
+                if not promise_checked[0] and res.width == 5:      # (the wide kernel forms the rows' sums itself: nothing promised)
                     check_normalized_rows(net, "the net function")
                     promise_checked[0] = True
-                _, grad_net = kernels.dm_refmix_planned_dev(res.plan(k, "train", 5), net.detach().contiguous(), ref_fn(e), h_dev,
-                                                            tau_p.detach().reshape(1), nw_p.detach().reshape(1), out=out4,
-                                                            train_ar=train_ar)
+                if res.width != 5:                                 # protein rows: no plan, the reference as its uint32 count rows
+                    _, grad_net = kernels.dm_refmix_wide_dev(e["train"], net.detach().contiguous(), ref_fn(e), h_dev,
+                                                             tau_p.detach().reshape(1), nw_p.detach().reshape(1), out=out4,
+                                                             train_ar=train_ar)
+                else:
+                    _, grad_net = kernels.dm_refmix_planned_dev(res.plan(k, "train", 5), net.detach().contiguous(), ref_fn(e), h_dev,
+                                                                tau_p.detach().reshape(1), nw_p.detach().reshape(1), out=out4,
+                                                                train_ar=train_ar)
                 if net.requires_grad:
                     net.backward(grad_net)                         # d sum LL / d net parameters
                 tau_p.grad = out4[2].reshape(tau_p.shape)

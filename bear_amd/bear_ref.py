@@ -102,12 +102,16 @@ def train(data, num_kmers, epochs, ds_loc, ds_loc_ref, alphabet, lag, make_ar_fu
     else:
         params, h_signed, ar_func = change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params_restart, dtype, device)
     dist.broadcast_params(params)                    # mirrored variables: every rank starts from rank 0's values (bear_ref.py:310-321)
-    if not ar_func.net_is_stop or _train.row_width(data) != 5:
-        # (the planned mode-R step is 5-wide: a protein table mixes in torch ops and takes the width-generic mode-N kernel)
+    width = _train.row_width(data)
+    wide = width != 5
+    if not ar_func.net_is_stop or (wide and (width not in kernels.WIDE_WIDTHS or os.environ.get("BEAR_AMD_UNFUSED_MIX"))):
+        # (a net function with parameters; or, BEAR_AMD_UNFUSED_MIX=1, a protein table the former way: the mixing as torch ops around
+        # the width-generic mode-N kernel -- tests and scripts/prot_ref_time.py compare the two)
         return _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, optimizer_name, train_ar, acc_steps, writer,
                               loss_save, ds_loc, ds_loc_ref, device)
     # stop net function: theta = (h_signed, tau_signed, net_weight_signed) lives on the device for the whole run; one step is
-    # constants-from-theta -> planned mode-R kernel -> finalize [-> all-reduce of 4 doubles] -> Adam, no host round trip
+    # constants-from-theta -> mode-R kernel (planned; rows of 21: dm_ref_wide_kernel on the count rows, no plan) -> finalize
+    # [-> all-reduce of 4 doubles] -> Adam, no host round trip
     res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, drop_empty="train",
                                  prebuild=[("train", 4, "ref")])       # plans cut while the next batch is still crossing PCIe
     theta = torch.stack([p.detach().reshape(()) for p in params[:3]]).to(device=device, dtype=torch.float64).contiguous()
@@ -116,6 +120,11 @@ def train(data, num_kmers, epochs, ds_loc, ds_loc_ref, alphabet, lag, make_ar_fu
         e = res.load(k)
         if e["rows"] == 0:
             return lambda packed: packed.zero_()
+        if wide:
+            return _train.StepFns(
+                lambda packed: kernels.ref_train_reduce_wide(e["train"], e["ref"], theta, packed, train_ar=train_ar),
+                lambda packed, m, v, t, lr, scale, loss_buf: kernels.ref_train_step_wide(e["train"], e["ref"], theta, m, v, t, lr, scale,
+                                                                                         packed, loss_buf, train_ar=train_ar))
         # built here, before any capture (plan creation allocates and synchronises); the reference column is resident too, so the
         # plan folds the contexts without reference counts into a histogram and a step streams only the others' items
         plan = res.plan(k, "train", 4, ref_column="ref")
@@ -142,13 +151,17 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     -- the mixing ``(nw net + jukes_cantor(ref, tau)) / (nw + 1)``, sum LL, d/dh, d/dtau, d/dnet_weight and d/d(net rows) -- and
     the net function's backward launch.  Net rows that are not asserted normalised (a plugin without ``normalized_rows``) take
     three launches instead: ``bear_ref_mix_forward_f64``, the planned kernel with gradient rows, ``bear_ref_mix_backward_f64``
-    through autograd -- the same loop as bear_net.train with two more parameters."""
+    through autograd -- the same loop as bear_net.train with two more parameters.  A protein table (rows of 21) takes
+    ``bear_dm_refmix_wide_grad_f64`` in the place of the planned launch, on the count rows of both columns; with
+    BEAR_AMD_UNFUSED_MIX=1 it mixes in torch ops around ``bear_dm_prior_wide_f64`` (with the stop net function too)."""
     # a fused net function (linear rows / cnn kernels) shares work between neighbouring contexts: batches are kept in k-mer order
     # (the sums do not depend on the order; cnn forward + backward 70 instead of 137 ms per 1e8 contexts, linear backward 1.45 / 2.0);
     # the 4-letter kernels only: the rows of 21 (kernels_linrows_wide.h) share nothing between neighbours, and the sort packs 3 bits
     res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, want_codes=True, drop_empty="train",
                                  kmer_order=bool(getattr(getattr(ar_func, "net_func", None), "fused", False)) and _train.row_width(data) == 5,
                                  prebuild=[("train", 5, None)], per_row_extra=24 * _train.row_width(data))
+
+    width = _train.row_width(data)
 
     def prior_fn_inputs(e):
         if "ref_in" not in e:
@@ -163,16 +176,20 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     # normalised net rows, the reference's own mixing parameters: the mixing runs inside the DM kernel
     # (bear_dm_refmix_plan_grad_f64: one launch instead of mix-forward, gradient rows, mix-backward); BEAR_AMD_UNFUSED_MIX=1 keeps
     # the three launches (tests compare the two)
+    # Rows of 21: the same in bear_dm_refmix_wide_grad_f64, from the reference COUNTS (no fp64 reference rows exist) and for any
+    # non-negative net rows (the kernel forms their sums itself: no normalized_rows promise needed)
     ref_mix = None
-    if (ar_func.normalized_rows and _train.row_width(data) == 5 and getattr(ar_func, "net_func", None) is not None and params[1] is ar_func.tau_signed
-            and params[2] is ar_func.net_weight_signed and not os.environ.get("BEAR_AMD_UNFUSED_MIX")):
+    own_mix = (getattr(ar_func, "net_func", None) is not None and params[1] is ar_func.tau_signed and params[2] is ar_func.net_weight_signed
+               and not os.environ.get("BEAR_AMD_UNFUSED_MIX"))
+    if own_mix and (ar_func.normalized_rows if width == 5 else width in kernels.WIDE_WIDTHS):
         def net_fn(e):
-            prior_fn_inputs(e)
-            live = _train.live_rows(e, "codes", "ref_in")
+            if width == 5:
+                prior_fn_inputs(e)
+            live = _train.live_rows(e, "codes", *(("ref_in",) if width == 5 else ()))
             if live is None:
                 return ar_func.net_func(e["codes"])
             return _train.scatter_live(ar_func.net_func(e["codes_live_train"]), live, e["rows"])
-        ref_mix = (net_fn, lambda e: e["ref_in"], params[1], params[2])
+        ref_mix = (net_fn, (lambda e: e["ref_in"]) if width == 5 else (lambda e: e["ref"]), params[1], params[2])
     losses = _train.run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, data.repeats, learning_rate, optimizer_name, train_ar,
                                        acc_steps, ar_func.normalized_rows, device, ref_mix=ref_mix)
     res.close()

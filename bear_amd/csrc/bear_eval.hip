@@ -1,8 +1,10 @@
 // bear_eval.hip -- held-out evaluation and the BMM marginal (kernels_eval.h), their 21-wide forms and the wide DM step
-// (kernels_wide.h), evaluation on a sorted plan of the test column (kernels_evalplan.h).  The other units: bear_host.h.
+// (kernels_wide.h), bear_ref's wide steps (kernels_refmix_wide.h), evaluation on a sorted plan of the test column
+// (kernels_evalplan.h).  The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_eval.h"
 #include "kernels_wide.h"
+#include "kernels_refmix_wide.h"
 #include "kernels_evalplan.h"
 
 #ifdef EVP_STAMPS
@@ -154,6 +156,92 @@ int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train,
                          ws->eval_partials);
     hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
   }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// ---- bear_ref's step at width W (kernels_refmix_wide.h) ------------------------------------------------------------------
+// the stop net function: the checks and the launch of bear_dm_ref_wide_f64 and of bear_ref_train_{reduce,step}_wide_f64 (theta != NULL:
+// the constants from the device-resident parameters; `apply`: the last block runs the update behind its sums)
+static int launch_ref_wide(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width, const bear_params &prm,
+                           const double *theta, int train_ar, double *out, hipStream_t s, const bear_apply_io &apply) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!out || (n_rows && (!train || !ref))) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(train) || misaligned(ref) || misaligned8(out) || misaligned8(theta) || !(prm.eps >= 0.0)) return BEAR_ERR_INVALID_ARG;
+  const uint64_t tile = (uint64_t)(width == 21 ? RFW_TILE(21) : RFW_TILE(5));
+  const int grid = grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, RFW_BLOCKS_PER_CU));
+  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_REF, out);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+#define REF_WIDE(W, AR) \
+  hipLaunchKernelGGL((dm_ref_wide_kernel<W, AR>), dim3(grid), dim3(RFW_THREADS), 0, s, train, ref, n_rows, prm, lt, ws->partials, io, apply)
+#define REF_WIDE_21(AR) REF_WIDE(21, AR)
+#define REF_WIDE_5(AR) REF_WIDE(5, AR)
+  if (width == 21) BEAR_DISPATCH_1(train_ar, REF_WIDE_21);
+  else BEAR_DISPATCH_1(train_ar, REF_WIDE_5);
+#undef REF_WIDE_5
+#undef REF_WIDE_21
+#undef REF_WIDE
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_dm_ref_wide_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width, double h_signed,
+                         double tau_signed, double nu_signed, double eps, int train_ar, double *out, void *stream) {
+  return launch_ref_wide(ws, train, ref, n_rows, width, params_ref(h_signed, tau_signed, nu_signed, eps), nullptr, train_ar, out,
+                         static_cast<hipStream_t>(stream), NO_APPLY);
+}
+
+int bear_ref_train_reduce_wide_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width,
+                                   const double *theta, double eps, int train_ar, double *packed, void *stream) {
+  if (!theta) return BEAR_ERR_INVALID_ARG;
+  return launch_ref_wide(ws, train, ref, n_rows, width, params_eps(eps), theta, train_ar, packed, static_cast<hipStream_t>(stream), NO_APPLY);
+}
+
+int bear_ref_train_step_wide_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width, double *theta,
+                                 double *adam_m, double *adam_v, double *adam_t, double eps, int train_ar, double learning_rate,
+                                 double scale, double *out, double *loss_buf, uint64_t loss_cap, void *stream) {
+  if (!theta || !adam_m || !adam_v || !adam_t) return BEAR_ERR_INVALID_ARG;
+  if (misaligned8(adam_m) || misaligned8(adam_v) || misaligned8(adam_t) || misaligned8(loss_buf)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (two_launch_step()) {
+    int st = launch_ref_wide(ws, train, ref, n_rows, width, params_eps(eps), theta, train_ar, out, s, NO_APPLY);
+    if (st != BEAR_OK) return st;
+    return launch_train_apply(theta, 3, out, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap, s);
+  }
+  // ONE launch: the last block of the reduce kernel runs the update behind its sums (bear_apply_in_block)
+  return launch_ref_wide(ws, train, ref, n_rows, width, params_eps(eps), theta, train_ar, out, s,
+                         make_apply(theta, 3, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
+}
+
+// a net function with parameters: the mixing inside the DM step, gradient rows over the net rows
+int bear_dm_refmix_wide_grad_f64(bear_ws *ws, const uint32_t *counts, const double *net_rows, const uint32_t *ref, uint64_t n_rows,
+                                 int width, const double *h_signed_dev, const double *tau_signed_dev, const double *net_weight_signed_dev,
+                                 double eps, int train_ar, double *out, double *grad_net_rows, void *stream) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!out || !h_signed_dev || !tau_signed_dev || !net_weight_signed_dev) return BEAR_ERR_INVALID_ARG;
+  if (n_rows && (!counts || !net_rows || !ref || !grad_net_rows)) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(counts) || misaligned(net_rows) || misaligned(ref) || misaligned(grad_net_rows) || misaligned8(out) ||
+      misaligned8(h_signed_dev) || misaligned8(tau_signed_dev) || misaligned8(net_weight_signed_dev) || !(eps >= 0.0))
+    return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint64_t tile = (uint64_t)(width == 21 ? RMW_TILE(21) : RMW_TILE(5));
+  const int grid = grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, RMW_BLOCKS_PER_CU));
+  const bear_step_io io = ws_io(ws, nullptr, BEAR_THETA_REF, out);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+#define MIX_WIDE(W, AR)                                                                                                             \
+  hipLaunchKernelGGL((dm_refmix_wide_kernel<W, AR>), dim3(grid), dim3(RFW_THREADS), 0, s, counts, net_rows, ref, n_rows, h_signed_dev, \
+                     tau_signed_dev, net_weight_signed_dev, eps, lt, grad_net_rows, ws->partials, io)
+#define MIX_WIDE_21(AR) MIX_WIDE(21, AR)
+#define MIX_WIDE_5(AR) MIX_WIDE(5, AR)
+  if (width == 21) BEAR_DISPATCH_1(train_ar, MIX_WIDE_21);
+  else BEAR_DISPATCH_1(train_ar, MIX_WIDE_5);
+#undef MIX_WIDE_5
+#undef MIX_WIDE_21
+#undef MIX_WIDE
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }

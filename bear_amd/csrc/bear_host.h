@@ -5,7 +5,7 @@
 //                    planned, reference-aware, ref-mix) and the plan itself
 //   bear_linear.hip  k-mer packing, the paired lists, the linear AR head (fused step and rows, rows of 21), the Adam launch
 //   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21
-//   bear_eval.hip    held-out evaluation (5- and 21-wide), the evaluation plan, the BMM marginal
+//   bear_eval.hip    held-out evaluation (5- and 21-wide), the wide DM step and bear_ref's wide steps, the evaluation plan, the BMM marginal
 // What a unit needs of another goes through the declarations at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>

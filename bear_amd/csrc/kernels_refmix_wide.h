@@ -1,0 +1,303 @@
+// kernels_refmix_wide.h -- bear_ref's training step at a row width W other than 5 (the protein alphabet, W = 21): the reference
+// mixing of bear_ref.py:63-68 inside the DM step, from the uint32 count rows the resident batches hold.  Instantiated for W = 5
+// too, so that the tests can hold these kernels against the trusted 5-wide entries (bear_dm_ref_f64, bear_dm_refmix_plan_grad_f64).
+//
+// With A = W - 1 letters and the stop column last (oracle/bear_oracle.py: bear_ref_step):
+//   r_b   = ref_b + eps (b < A), r_A = 0;   R = sum_b r_b;   dev_b = r_b / R - 1/A (b < A), dev_A = 0
+//   jc_b  = [b < A] / A + E dev_b;   f_b = (nw g_b + jc_b) V;   E = exp(-tau), V = 1 / (nw + 1), tau = exp(tau_signed), nw = exp(nu_signed)
+//   d f_b / d tau_signed = -tau E dev_b V;   d f_b / d nu_signed = nw (g_b - f_b) V
+//   BEAR mode: alpha_b = f_b / h + eps, d LL / d f_b = (P_b [c_b > 0] - P_n) / h;   AR mode: p_b = f_b + eps, d LL / d f_b = c_b / p_b
+//
+//   dm_ref_wide_kernel     the stop net function (g = one-hot at the stop column): train and reference rows in (8 W B per context),
+//                          [sum LL, d/dh_signed, d/dtau_signed, d/dnu_signed] out; no prior row exists anywhere.  The finish is
+//                          dm_ref_rows_kernel's: the last block's fixed-order sum and, for a whole step, the Adam update behind it.
+//   dm_refmix_wide_kernel  a net function with parameters: its rows g (fp64) in as well, the same four sums and
+//                          d sum LL / d g = d LL / d f  nw V out, written in place over the staged rows (16 W B in, 8 W B out).
+//                          Nothing is assumed of g but g >= 0: sum g and sum f are formed from the row.
+//
+// Both have dm_wide_kernel's structure (kernels_wide.h): tiles through LDS as 16-byte lane loads (stride W dwords / W doubles, W odd:
+// conflict-free), a context per lane, a dm_row_item per NON-ZERO training cell (the bit mask of the row) and one for the row term; a
+// context without training counts adds exact zeros and costs its bytes only.  A zero cell needs no item: its d LL / d f is the row
+// term -P_n / h alone, so the zero cells' share of a gradient is the row term times (the sum over ALL cells) - (the sum over the
+// non-zero cells) of d f / d parameter -- and the sums over all cells are sum dev, sum g and sum f, which one static pass over the
+// row yields without an item.
+// sum dev is formed, not taken as zero: for a reference row that is flat (a context the reference never saw: all eps) every dev_b is
+// the same rounding residue of r / R - 1/A, the gradient of tau is that residue times a sum of O(1) terms, and only the residue the
+// oracle's arithmetic leaves is "right" to the 2e-13 of the L1 mass the tests hold a gradient to.  So R is summed in the order NumPy
+// sums a row (rfw_ref_total), r / R is rounded as a division rounds it (rfw_dev) and 1/A is subtracted unfused.
+// No floating-point atomics: block partials and block_finish only -- equal inputs, equal bits for a given grid, in both builds.
+#pragma once
+#include "bear_common.h"
+#include "kernels_rows.h"
+#include "kernels_wide.h"
+
+#define RFW_THREADS 256
+// dm_ref_wide_kernel, W = 21: 256 contexts = two count tiles of 21 KiB (+ 2 KiB log table): a context on every thread, three blocks
+// per CU by LDS and by registers alike (profiles/kernel_table_refmix_wide.txt).
+#define RFW_TILE(W) ((W) > 8 ? 256 : 512)
+#define RFW_BLOCKS_PER_CU 3
+// dm_refmix_wide_kernel, W = 21: 128 contexts = 21 KiB of counts + 21 KiB of net rows: three blocks per CU; the upper half of the
+// block stages and writes back only (as dm_wide_kernel).
+#define RMW_TILE(W) ((W) > 8 ? 128 : 512)
+#define RMW_BLOCKS_PER_CU 3
+
+// R = sum of the letters' r_b = ref_b + eps over a row whose stop entry is zero, added in the order NumPy's add.reduce takes over W
+// contiguous doubles: below 8 entries one after the other; else eight running sums over the whole blocks of eight, combined pairwise,
+// then the rest one after the other.  (The zero of the stop column changes no partial sum: r >= 0.)
+template <int W>
+__device__ __forceinline__ double rfw_ref_total(const uint32_t *ref, double eps) {
+  constexpr int A = W - 1;
+  if (W < 8) {
+    double s = (double)ref[0] + eps;
+#pragma unroll
+    for (int b = 1; b < A; ++b) s += (double)ref[b] + eps;
+    return s;
+  }
+  constexpr int FULL = W - W % 8;
+  double q[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] = j < A ? (double)ref[j] + eps : 0.0;
+#pragma unroll
+  for (int i = 8; i < FULL; i += 8)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (i + j < A) q[j] += (double)ref[i + j] + eps;
+  double s = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+#pragma unroll
+  for (int i = FULL; i < A; ++i) s += (double)ref[i] + eps;
+  return s;
+}
+
+// dev = r / R - 1/A with the quotient rounded as the division rounds it: q = r invR (invR = 1 / R correctly rounded) is within an
+// ulp, the remainder r - q R is exact in one fma, and one step on it gives the rounded quotient -- three instructions instead of a
+// division sequence per cell.  The subtraction is not fused (the Makefile's -ffp-contract=off).
+template <int W>
+__device__ __forceinline__ double rfw_dev(double r, double R, double invR) {
+  const double q = r * invR;
+  const double q1 = __builtin_fma(__builtin_fma(-q, R, r), invR, q);
+  return q1 - 1.0 / (W - 1);
+}
+
+// sum_b dev_b over the letters (all W cells: dev of the stop column is zero)
+template <int W>
+__device__ __forceinline__ double rfw_dev_total(const uint32_t *ref, double eps, double R, double invR) {
+  double s = 0.0;
+#pragma unroll
+  for (int b = 0; b < W - 1; ++b) s += rfw_dev<W>((double)ref[b] + eps, R, invR);
+  return s;
+}
+
+// cell b of a row whose net entry is g: f_b, d f_b / d tau_signed, d f_b / d nu_signed
+struct rfw_cell {
+  double f, dft, dfn;
+};
+template <int W>
+__device__ __forceinline__ rfw_cell rfw_mix_cell(const uint32_t *ref, int b, double g, double R, double invR, const bear_params &prm) {
+  const bool letter = b < W - 1;
+  const double dev = letter ? rfw_dev<W>((double)ref[b] + prm.eps, R, invR) : 0.0;
+  const double jc = __builtin_fma(prm.E, dev, letter ? 1.0 / (W - 1) : 0.0);
+  rfw_cell o;
+  o.f = __builtin_fma(prm.nw, g, jc) * prm.V;
+  o.dft = -prm.tauE * dev * prm.V;
+  o.dfn = prm.nw * (g - o.f) * prm.V;
+  return o;
+}
+
+// c log p of the multinomial mode, as dm_wide_kernel forms it (near p = 1 -- the stop entry under a large net weight -- the
+// polynomial on p - 1 keeps the table log's absolute error relative)
+__device__ __forceinline__ double rfw_log(double p, const double2 *s_log) {
+  return fabs(p - 1.0) < 0x1p-8 ? bear_log1p_small(p - 1.0) : (p > 0.0 ? bear_log_tab(p, s_log) : bear_log(p));
+}
+
+// the constants of a step from three device-resident parameters (bear_params_of reads them from one vector)
+__device__ __forceinline__ bear_params rfw_params(const double *__restrict__ h_s, const double *__restrict__ tau_s,
+                                                  const double *__restrict__ nw_s, double eps) {
+  bear_params p;
+  const double tau = exp(tau_s[0]), nw = exp(nw_s[0]);
+  const double E = exp(-tau);
+  p.eps = eps;
+  p.inv_h = bear_uniform_f64(1.0 / exp(h_s[0]));
+  p.E = bear_uniform_f64(E);
+  p.tauE = bear_uniform_f64(tau * E);
+  p.tau = bear_uniform_f64(tau);
+  p.V = bear_uniform_f64(1.0 / (nw + 1.0));
+  p.nw = bear_uniform_f64(nw);
+  return p;
+}
+
+// ------------------------------------------------------------------ the stop net function
+template <int W, bool AR>
+__global__ __launch_bounds__(RFW_THREADS) void dm_ref_wide_kernel(const uint32_t *__restrict__ train, const uint32_t *__restrict__ ref,
+                                                                 uint64_t n_rows, bear_params prm_arg, const double2 *__restrict__ logtab_g,
+                                                                 double *__restrict__ partials, const bear_step_io io,
+                                                                 const bear_apply_io apply) {
+  static_assert(W <= 32, "the non-zero cells of a row are a 32-bit mask");
+  constexpr int T = RFW_TILE(W);
+  __shared__ __attribute__((aligned(16))) uint32_t s_trn[T * W];
+  __shared__ __attribute__((aligned(16))) uint32_t s_ref[T * W];
+  __shared__ double2 s_log[BEAR_LOGTAB_N];
+  const bear_params prm = bear_params_of(prm_arg, io);
+  if (threadIdx.x < BEAR_LOGTAB_N) s_log[threadIdx.x] = logtab_g[threadIdx.x];
+  const uint64_t n_tiles = (n_rows + T - 1) / T;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const uint64_t row0 = tile * T;
+    const uint32_t rows = (uint32_t)((n_rows - row0 < (uint64_t)T) ? (n_rows - row0) : (uint64_t)T);
+    __syncthreads();  // previous tile consumed (and the log table is in place)
+    stage_dwords<RFW_THREADS>(s_trn, train + row0 * W, rows * W);
+    stage_dwords<RFW_THREADS>(s_ref, ref + row0 * W, rows * W);
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t r = threadIdx.x; r < rows; r += RFW_THREADS) {
+      const uint32_t *c = s_trn + r * W;
+      const uint32_t *rf = s_ref + r * W;
+      uint32_t nz = wide_nz_mask<W>(c);
+      if (!nz) continue;               // no training counts: nothing of this context enters any sum
+      const double R = rfw_ref_total<W>(rf, prm.eps), invR = 1.0 / R;
+      double ll = 0.0, dh = 0.0, dt = 0.0, dn = 0.0, scale = 1.0;   // sums over the cells of P_b (AR: c_b / p_b) times f, df/dtau, df/dnu
+      bear_dp tn = {0.0, 0.0};
+      if (!AR) {
+        double n = 0.0;
+#pragma unroll
+        for (int b = 0; b < W; ++b) n += (double)c[b];
+        const double sdev = rfw_dev_total<W>(rf, prm.eps, R, invR);
+        const double sf = (prm.nw + __builtin_fma(prm.E, sdev, 1.0)) * prm.V;     // sum g = 1
+        tn = dm_row_item(__builtin_fma(sf, prm.inv_h, (double)W * prm.eps), n, s_log);
+        ll = -tn.D;
+        dh = -tn.P * sf;
+        dt = tn.P * (prm.tauE * prm.V * sdev);
+        dn = -tn.P * (prm.nw * prm.V * (1.0 - sf));
+        scale = prm.inv_h;
+      }
+      while (nz) {
+        const int b = __builtin_ctz(nz);
+        nz &= nz - 1u;
+        const double cb = (double)c[b];
+        const rfw_cell m = rfw_mix_cell<W>(rf, b, b == W - 1 ? 1.0 : 0.0, R, invR, prm);
+        double q;
+        if (AR) {
+          const double p = m.f + prm.eps;
+          ll = __builtin_fma(cb, rfw_log(p, s_log), ll);
+          q = cb * bear_rcp(p);
+        } else {
+          const bear_dp tb = dm_row_item(__builtin_fma(m.f, prm.inv_h, prm.eps), cb, s_log);
+          ll += tb.D;
+          q = tb.P;
+          dh = __builtin_fma(q, m.f, dh);
+        }
+        dt = __builtin_fma(q, m.dft, dt);
+        dn = __builtin_fma(q, m.dfn, dn);
+      }
+      acc[0] += ll;
+      acc[1] -= dh * scale;            // d alpha_b / d h_signed = -f_b / h (AR: dh stays zero)
+      acc[2] += dt * scale;
+      acc[3] += dn * scale;
+    }
+  }
+  __syncthreads();
+  block_finish<4>(acc, partials, io, apply);
+}
+
+// ------------------------------------------------------------------ a net function with parameters
+template <int W, bool AR>
+__global__ __launch_bounds__(RFW_THREADS) void dm_refmix_wide_kernel(const uint32_t *__restrict__ counts, const double *__restrict__ net_rows,
+                                                                    const uint32_t *__restrict__ ref, uint64_t n_rows,
+                                                                    const double *__restrict__ h_s, const double *__restrict__ tau_s,
+                                                                    const double *__restrict__ nw_s, double eps,
+                                                                    const double2 *__restrict__ logtab_g, double *__restrict__ grad_net_rows,
+                                                                    double *__restrict__ partials, const bear_step_io io) {
+  static_assert(W <= 32, "the non-zero cells of a row are a 32-bit mask");
+  constexpr int T = RMW_TILE(W);
+  __shared__ __attribute__((aligned(16))) uint32_t s_cnt[T * W];
+  __shared__ __attribute__((aligned(16))) uint32_t s_ref[T * W];
+  __shared__ __attribute__((aligned(16))) double s_net[T * W];   // g in, d sum LL / d g out
+  __shared__ double2 s_log[BEAR_LOGTAB_N];
+  const bear_params prm = rfw_params(h_s, tau_s, nw_s, eps);
+  const double nwV = prm.nw * prm.V;
+  if (threadIdx.x < BEAR_LOGTAB_N) s_log[threadIdx.x] = logtab_g[threadIdx.x];
+  const uint64_t n_tiles = (n_rows + T - 1) / T;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const uint64_t row0 = tile * T;
+    const uint32_t rows = (uint32_t)((n_rows - row0 < (uint64_t)T) ? (n_rows - row0) : (uint64_t)T);
+    __syncthreads();  // previous tile consumed and written back (and the log table is in place)
+    stage_dwords<RFW_THREADS>(s_cnt, counts + row0 * W, rows * W);
+    stage_dwords<RFW_THREADS>(s_ref, ref + row0 * W, rows * W);
+    stage_dwords<RFW_THREADS>(reinterpret_cast<uint32_t *>(s_net), reinterpret_cast<const uint32_t *>(net_rows + row0 * W), rows * W * 2);
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t r = threadIdx.x; r < rows; r += RFW_THREADS) {
+      const uint32_t *c = s_cnt + r * W;
+      const uint32_t *rf = s_ref + r * W;
+      double *g = s_net + r * W;
+      uint32_t nz = wide_nz_mask<W>(c);
+      if (!nz) {                       // no training counts: a row of exact zeros, nothing else
+#pragma unroll
+        for (int b = 0; b < W; ++b) g[b] = 0.0;
+        continue;
+      }
+      const double R = rfw_ref_total<W>(rf, prm.eps), invR = 1.0 / R;
+      double ll = 0.0, dh = 0.0, dt = 0.0, dn = 0.0, scale = 1.0, g0 = 0.0;
+      bear_dp tn = {0.0, 0.0};
+      if (!AR) {
+        double n = 0.0, sg = 0.0;
+#pragma unroll
+        for (int b = 0; b < W; ++b) {
+          n += (double)c[b];
+          sg += g[b];
+        }
+        const double sdev = rfw_dev_total<W>(rf, prm.eps, R, invR);
+        const double sf = __builtin_fma(prm.nw, sg, __builtin_fma(prm.E, sdev, 1.0)) * prm.V;
+        tn = dm_row_item(__builtin_fma(sf, prm.inv_h, (double)W * prm.eps), n, s_log);
+        ll = -tn.D;
+        dh = -tn.P * sf;
+        dt = tn.P * (prm.tauE * prm.V * sdev);
+        dn = -tn.P * (nwV * (sg - sf));
+        scale = prm.inv_h;
+        g0 = -tn.P * prm.inv_h * nwV;
+      }
+#pragma unroll
+      for (int b = 0; b < W; ++b)
+        if (!((nz >> b) & 1u)) g[b] = g0;
+      while (nz) {
+        const int b = __builtin_ctz(nz);
+        nz &= nz - 1u;
+        const double cb = (double)c[b];
+        const rfw_cell m = rfw_mix_cell<W>(rf, b, g[b], R, invR, prm);
+        double q;
+        if (AR) {
+          const double p = m.f + prm.eps;
+          ll = __builtin_fma(cb, rfw_log(p, s_log), ll);
+          q = cb * bear_rcp(p);
+          g[b] = q * nwV;
+        } else {
+          const bear_dp tb = dm_row_item(__builtin_fma(m.f, prm.inv_h, prm.eps), cb, s_log);
+          ll += tb.D;
+          q = tb.P;
+          dh = __builtin_fma(q, m.f, dh);
+          g[b] = (tb.P - tn.P) * prm.inv_h * nwV;
+        }
+        dt = __builtin_fma(q, m.dft, dt);
+        dn = __builtin_fma(q, m.dfn, dn);
+      }
+      acc[0] += ll;
+      acc[1] -= dh * scale;
+      acc[2] += dt * scale;
+      acc[3] += dn * scale;
+    }
+    __syncthreads();   // every row of the tile holds its gradient: 16-byte stores of the whole tile
+    {
+      const uint32_t n_dw = rows * W * 2, n_vec = n_dw >> 2;
+      typedef uint32_t rfw_v4u __attribute__((ext_vector_type(4)));
+      const rfw_v4u *s4 = reinterpret_cast<const rfw_v4u *>(s_net);
+      rfw_v4u *d4 = reinterpret_cast<rfw_v4u *>(grad_net_rows + row0 * W);
+      // nontemporal: the rows are not read again by this kernel
+      for (uint32_t i = threadIdx.x; i < n_vec; i += RFW_THREADS) __builtin_nontemporal_store(s4[i], d4 + i);
+      const uint32_t *s1 = reinterpret_cast<const uint32_t *>(s_net);
+      uint32_t *d1 = reinterpret_cast<uint32_t *>(grad_net_rows + row0 * W);
+      for (uint32_t i = (n_vec << 2) + threadIdx.x; i < n_dw; i += RFW_THREADS) d1[i] = s1[i];
+    }
+  }
+  __syncthreads();
+  block_finish<4>(acc, partials, io);
+}

@@ -135,6 +135,93 @@ def dm_prior_wide(counts, prior, h_signed_dev, eps=EPSILON, train_ar=False, want
     return out, grad
 
 
+# tiles and resident blocks per CU of the bear_ref kernels at a wide row (kernels_refmix_wide.h: RFW_TILE / RMW_TILE and
+# *_BLOCKS_PER_CU): a launch takes min(tiles, blocks per CU * CUs) blocks -- tests size a table beyond that from these
+REF_WIDE_TILE = {21: 256, 5: 512}
+REFMIX_WIDE_TILE = {21: 128, 5: 512}
+REF_WIDE_BLOCKS_PER_CU = 3
+REFMIX_WIDE_BLOCKS_PER_CU = 3
+
+
+def _check_ref_wide(train, ref):
+    train = _check_rows_wide(train, torch.int32, "train")
+    ref = _check_rows_wide(ref, torch.int32, "ref", train.shape[1])
+    if train.shape[0] != ref.shape[0]:
+        raise ValueError("train and ref must have the same number of rows")
+    return train, ref
+
+
+def dm_ref_wide(train, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, train_ar=False, out=None, ws=None):
+    """``bear_dm_ref_wide_f64``: ``dm_ref`` for rows of width W = ``train.shape[-1]`` (21: the protein alphabet) -- the stop net
+    function, the reference mixing inside the DM kernel, no prior rows.  Returns out [4] = sum LL, d/dh_signed, d/dtau_signed,
+    d/dnet_weight_signed."""
+    train, ref = _check_ref_wide(train, ref)
+    ws = ws or default_workspace(train.device)
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=train.device)
+    _f64_vec(out, 4, "out")
+    with torch.cuda.device(train.device):
+        st = _lib.lib().bear_dm_ref_wide_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], float(h_signed),
+                                             float(tau_signed), float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out), _stream())
+    _lib.check(st, "bear_dm_ref_wide_f64")
+    return out
+
+
+def ref_train_reduce_wide(train, ref, theta, packed, eps=EPSILON, train_ar=False, ws=None):
+    """Enqueues ``bear_ref_train_reduce_wide_f64``: ``ref_train_reduce`` for rows of 21 (or 5), without a plan -- this shard's
+    packed = [sum LL, d/dh_s, d/dtau_s, d/dnu_s], the kernel constants from the device-resident theta."""
+    train, ref = _check_ref_wide(train, ref)
+    _f64_vec(theta, 3, "theta")
+    _f64_vec(packed, 4, "packed")
+    ws = ws or default_workspace(train.device)
+    with torch.cuda.device(train.device):
+        st = _lib.lib().bear_ref_train_reduce_wide_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], _ptr(theta),
+                                                       float(eps), int(bool(train_ar)), _ptr(packed), _stream())
+    _lib.check(st, "bear_ref_train_reduce_wide_f64")
+
+
+def ref_train_step_wide(train, ref, theta, adam_m, adam_v, adam_t, learning_rate, scale, out, loss_buf=None, eps=EPSILON, train_ar=False,
+                        ws=None):
+    """Enqueues one ``bear_ref_train_step_wide_f64``: ``ref_train_step`` for rows of 21 (or 5), without a plan -- constants from
+    theta, the wide mode-R kernel, its last block's sums and Adam on theta in one launch; capturable in a HIP graph."""
+    train, ref = _check_ref_wide(train, ref)
+    for t, n, name in ((theta, 3, "theta"), (adam_m, 3, "adam_m"), (adam_v, 3, "adam_v"), (adam_t, 1, "adam_t"), (out, 4, "out")):
+        _f64_vec(t, n, name)
+    if loss_buf is not None:
+        _f64_vec(loss_buf, loss_buf.numel(), "loss_buf")
+    ws = ws or default_workspace(train.device)
+    with torch.cuda.device(train.device):
+        st = _lib.lib().bear_ref_train_step_wide_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], _ptr(theta),
+                                                     _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)),
+                                                     float(learning_rate), float(scale), _ptr(out), _ptr(loss_buf),
+                                                     0 if loss_buf is None else loss_buf.numel(), _stream())
+    _lib.check(st, "bear_ref_train_step_wide_f64")
+
+
+def dm_refmix_wide_dev(counts, net_rows, ref, h_signed_dev, tau_signed_dev, net_weight_signed_dev, eps=EPSILON, out=None, train_ar=False,
+                       ws=None):
+    """``bear_dm_refmix_wide_grad_f64``: bear_ref's step for a net function with parameters on rows of width W =
+    ``counts.shape[-1]`` -- the reference mixing inside the DM kernel.  ``ref`` are the reference COUNTS (int32 storage, as
+    ``counts``), ``net_rows`` [n, W] the net function's rows (any non-negative rows: not assumed normalised).
+    Returns (out [4] = sum LL, d/dh_signed, d/dtau_signed, d/dnet_weight_signed; d sum LL / d net_rows [n, W])."""
+    counts, ref = _check_ref_wide(counts, ref)
+    net_rows = _check_rows_wide(net_rows, torch.float64, "net_rows", counts.shape[1])
+    if net_rows.shape[0] != counts.shape[0]:
+        raise ValueError("counts and net_rows must have the same number of rows")
+    _check_scalar_param(h_signed_dev=h_signed_dev, tau_signed_dev=tau_signed_dev, net_weight_signed_dev=net_weight_signed_dev)
+    ws = ws or default_workspace(counts.device)
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=counts.device)
+    _f64_vec(out, 4, "out")
+    grad = torch.empty_like(net_rows)
+    with torch.cuda.device(counts.device):
+        st = _lib.lib().bear_dm_refmix_wide_grad_f64(ws.handle, _ptr(counts), _ptr(net_rows), _ptr(ref), counts.shape[0], counts.shape[1],
+                                                     _ptr(h_signed_dev), _ptr(tau_signed_dev), _ptr(net_weight_signed_dev), float(eps),
+                                                     int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
+    _lib.check(st, "bear_dm_refmix_wide_grad_f64")
+    return out, grad
+
+
 def dm_ref(train, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, train_ar=False, out=None, ws=None):
     """[sum LL, d/dh_signed, d/dtau_signed, d/dnet_weight_signed] (bear_ref._train_step
     arithmetic with the stop net function, bear_ref.py:207-259)."""

@@ -36,13 +36,15 @@
 extern "C" {
 #endif
 
-#define BEAR_ABI_VERSION 11 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
+#define BEAR_ABI_VERSION 12 /* 7: + bear_dm_prior_wide_f64, bear_eval_wide_f64, bear_parse_counts_tsv[_shard]_wide (rows of 21: protein);
                               8: + bear_logdir_sample_wide_f64;
                               9: + bear_kmer_sort_create_wide, bear_fastx_size_wide, bear_fastx_encode_wide, bear_write_counts_tsv_wide,
                                  bear_encode_kmers_i8 mode 2 (protein count tables from sequence files);
                               10: + bear_linear_forward_wide_f64, bear_linear_backward_wide_f64 (the linear AR function as rows of 21);
                               11: + bear_cnn_param_count_wide, bear_cnn_forward_wide_f64, bear_cnn_backward_wide_f64 (the convolutional AR
-                                  function as rows of 21) */
+                                  function as rows of 21);
+                              12: + bear_dm_ref_wide_f64, bear_ref_train_reduce_wide_f64, bear_ref_train_step_wide_f64,
+                                  bear_dm_refmix_wide_grad_f64 (bear_ref's training step on rows of 21) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -492,6 +494,34 @@ int bear_dm_prior_wide_f64(bear_ws *ws, const uint32_t *counts, const double *pr
 int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train, const double *prior, uint64_t n_rows, int width,
                        const double *h, int n_h, int with_ar, const double *van_reg, int n_van, double eps,
                        uint64_t noise_seed, uint64_t row_base, double *out, void *stream);
+
+/*
+ * bear_ref._train_step at width W (kernels_refmix_wide.h): the reference mixing of bear_ref.py:63-68 inside the DM step, from the
+ * uint32 rows of the training and the reference column (no fp64 reference rows, no prior rows).  `width` as above; every row
+ * pointer 16-byte aligned, out / packed / theta / the Adam state and the parameter pointers 8-byte aligned; n_rows = 0 writes zero
+ * sums.  One launch each; the sums are written by the last block in a fixed order (the same bits for the same inputs and n_rows).
+ *
+ * bear_dm_ref_wide_f64: bear_dm_ref_f64 at width W -- the stop net function, parameters by value;
+ *   out [dev] double [4] = { sum LL, d/d h_signed, d/d tau_signed, d/d net_weight_signed }.
+ * bear_ref_train_reduce_wide_f64 / bear_ref_train_step_wide_f64: bear_ref_train_reduce_f64 / bear_ref_train_step_f64 without a plan:
+ *   the constants from the device-resident theta [3] = { h_signed, tau_signed, net_weight_signed }; the step runs tf.keras Adam
+ *   behind the sums in the same launch (BEAR_AMD_TWO_LAUNCH_STEP=1: reduce, then bear_train_apply_f64), capturable into a HIP graph.
+ * bear_dm_refmix_wide_grad_f64: bear_dm_refmix_plan_grad_f64 at width W without a plan -- a net function with parameters:
+ *   net_rows [dev] double [n_rows, W] its rows g (non-negative; NOT assumed normalised), ref [dev] uint32 [n_rows, W] the reference
+ *   COUNTS (the kernel adds eps and drops the stop column itself), the three parameters read from device memory;
+ *   out [4] as above, grad_net_rows [dev] double [n_rows, W] = d out[0] / d net_rows (rows of contexts without training counts are
+ *   exact zeros).
+ */
+int bear_dm_ref_wide_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width, double h_signed,
+                         double tau_signed, double nu_signed, double eps, int train_ar, double *out, void *stream);
+int bear_ref_train_reduce_wide_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width,
+                                   const double *theta, double eps, int train_ar, double *packed, void *stream);
+int bear_ref_train_step_wide_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uint64_t n_rows, int width, double *theta,
+                                 double *adam_m, double *adam_v, double *adam_t, double eps, int train_ar, double learning_rate,
+                                 double scale, double *out, double *loss_buf, uint64_t loss_cap, void *stream);
+int bear_dm_refmix_wide_grad_f64(bear_ws *ws, const uint32_t *counts, const double *net_rows, const uint32_t *ref, uint64_t n_rows,
+                                 int width, const double *h_signed_dev, const double *tau_signed_dev, const double *net_weight_signed_dev,
+                                 double eps, int train_ar, double *out, double *grad_net_rows, void *stream);
 
 /*
  * The same on a sorted plan of the TEST column, for a table that stays resident (a held-out evaluation after training, the
