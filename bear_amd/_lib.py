@@ -45,7 +45,11 @@ SYMBOLS = [
     "bear_linear_forward_wide_f64", "bear_linear_backward_wide_f64",
     "bear_cnn_param_count_wide", "bear_cnn_forward_wide_f64", "bear_cnn_backward_wide_f64",
     "bear_dm_ref_wide_f64", "bear_ref_train_reduce_wide_f64", "bear_ref_train_step_wide_f64", "bear_dm_refmix_wide_grad_f64",
+    "bear_dm_linear_wide_f64", "bear_net_linear_train_reduce_wide_f64", "bear_net_linear_train_step_wide_f64",
 ]
+
+# added without a new ABI version (nothing changed, include/bear_hip.h): a library built before them still answers 12
+SYMBOLS_ADDED_AT_12 = SYMBOLS[-3:]
 
 
 ERR_NOMEM = -5   # BEAR_ERR_NOMEM (include/bear_hip.h)
@@ -77,6 +81,9 @@ def _load():
         # a library from another tree may export every symbol and still take its arguments in another order
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.bear_abi_version()}, this binding was written for {ABI_VERSION}: "
                           f"rebuild it with `make -C {os.path.join(_HERE, 'csrc')}`")
+    for name in SYMBOLS_ADDED_AT_12:
+        if not hasattr(L, name):
+            raise ImportError(f"{LIB_PATH} is stale: it does not export {name}; rebuild it with `make -C {os.path.join(_HERE, 'csrc')}`")
     L.bear_strerror.restype = ctypes.c_char_p
     L.bear_strerror.argtypes = [cint]
     L.bear_last_hip_error.restype = cint
@@ -182,6 +189,9 @@ def _load():
     L.bear_ref_train_reduce_wide_f64.argtypes = [vp, vp, vp, u64, cint, vp, dbl, cint, vp, vp]
     L.bear_ref_train_step_wide_f64.argtypes = [vp, vp, vp, u64, cint, vp, vp, vp, vp, dbl, cint, dbl, dbl, vp, vp, u64, vp]
     L.bear_dm_refmix_wide_grad_f64.argtypes = [vp, vp, vp, vp, u64, cint, vp, vp, vp, dbl, cint, vp, vp, vp]
+    L.bear_dm_linear_wide_f64.argtypes = [vp, vp, vp, u64, cint, cint, vp, dbl, dbl, cint, vp, vp, vp]
+    L.bear_net_linear_train_reduce_wide_f64.argtypes = [vp, vp, vp, u64, cint, cint, vp, dbl, cint, vp, vp]
+    L.bear_net_linear_train_step_wide_f64.argtypes = [vp, vp, vp, u64, cint, cint, vp, vp, vp, vp, dbl, cint, dbl, dbl, vp, vp, u64, vp]
     _lib = L
     return L
 

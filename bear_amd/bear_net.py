@@ -6,6 +6,8 @@ AR rows come from the plugin (``ar_funcs``, PyTorch-ROCm ops with autograd), and
 log-likelihood, its gradient w.r.t. ``h_signed`` and w.r.t. the AR rows come from one launch of
 ``bear_dm_prior_f64``; the row gradient is fed back through ``ar_func`` by ``Tensor.backward``.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -30,6 +32,16 @@ def change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params, dty
     return new, h_signed, ar_func
 
 
+def linear_wide_step_selected(alphabet_size, lag, own_mat, width):
+    """Whether ``train`` runs the protein alphabet's linear step as one launch per optimizer step (``bear_net_linear_train_step_wide_f64``,
+    theta device-resident): the 20-letter alphabet on a 21-wide table, a lag whose mat fits the kernel's LDS, and an AR function
+    whose only parameter is the linear mat itself (``own_mat``: ``ar_func.linear_mat is ar_params[0]``).
+    BEAR_AMD_UNFUSED_LINEAR_WIDE=1 keeps the three row kernels under autograd (tests and scripts/prot_linear_step_time.py compare)."""
+    unfused = os.environ.get("BEAR_AMD_UNFUSED_LINEAR_WIDE", "")
+    return bool(alphabet_size == 20 and width == kernels.LINEAR_WIDE_WIDTH and 1 <= lag <= kernels.LINEAR_WIDE_MAX_LAG and own_mat
+                and not (unfused and unfused != "0"))
+
+
 def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwargs,
           learning_rate, optimizer_name, train_ar, acc_steps=1,
           params_restart=None, writer=None, loss_save=None, dtype=torch.float64):
@@ -50,6 +62,10 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
     cnn_ok = (getattr(ar_func, "fused", False) and alphabet_size == 4 and len(ar_params) == 8
               and all(a is b for a, b in zip(getattr(ar_func, "cnn_params", []), ar_params)))
     fused = fused_mat is not None or cnn_ok
+    # ... and on the protein alphabet: the same, on int8 codes in table order (no plan, no k-mer sort: kernels_linear_wide.h)
+    wide_mat = getattr(ar_func, "linear_mat", None)
+    wide_step = linear_wide_step_selected(alphabet_size, lag, wide_mat is not None and len(ar_params) == 1 and wide_mat is ar_params[0],
+                                          _train.row_width(data))
     # Fused heads: the sums of a step do not depend on the order of a batch's rows, so every batch is kept sorted by k-mer (first
     # letter most significant) -- consecutive contexts share all but their last letters: the fused linear kernel adds whole waves /
     # quads of them to d/d mat at once instead of one LDS atomic per context, letter and position (kernels_linear.h), the
@@ -57,9 +73,9 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
     # batches land, while the next batch is still being uploaded.
     res = _train.ResidentBatches(data, {"train": ds_loc}, device, want_codes=True, drop_empty="train", kmer_order=fused,
                                  prebuild=[("train", 5 if fused else _train.ROWS_IF_DENSE, None)],     # (+ paired lists of the linear head / prefix levels of the cnn step)
-                                 per_row_extra=(8 + (208 + 64 if cnn_ok else 4)) if fused else 16 * (alphabet_size + 1))
+                                 per_row_extra=(8 + (208 + 64 if cnn_ok else 4)) if fused else 0 if wide_step else 16 * (alphabet_size + 1))
     scales = [-(num_kmers / e["global_rows"]) for e in res.batches]       # bear_net.py:190-191 with the global batch
-    if fused:
+    if fused or wide_step:
         # theta = {h_signed, flattened AR parameters} lives on the device for the whole run: one step is constants-from-theta ->
         # fused kernels [-> all-reduce of the packed vector] -> Adam, no host round trip (_train.run_device_steps)
         theta = torch.cat([h_signed.detach().reshape(1)] + [p.detach().reshape(-1) for p in ar_params]).to(
@@ -105,9 +121,25 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
                 lambda packed: kernels.net_linear_train_reduce(plan, pack, lag, theta, packed, train_ar=train_ar),
                 lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_linear_train_step(plan, pack, lag, theta, m, v, t, packed, lr, scale,
                                                                                            loss_buf, train_ar=train_ar))
-        reduce_fns = _train.reducers(res, reducer)
+
+        def reducer_wide(k):
+            e = res.load(k)
+            if not e["rows"]:
+                return lambda packed: packed.zero_()
+            counts, codes = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (e["train"].contiguous(), e["codes"].contiguous()))
+            return _train.StepFns(
+                lambda packed: kernels.net_linear_train_reduce_wide(counts, codes, lag, theta, packed, train_ar=train_ar),
+                lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_linear_train_step_wide(counts, codes, lag, theta, m, v, t, packed, lr,
+                                                                                                scale, loss_buf, train_ar=train_ar))
+        graph_ok = not res.streaming
+        if wide_step:
+            # the fused step pins no autograd intermediates in a graph's pool: no row cap of its own, but one that is set is honoured
+            # (the tests force the eager loop of a protein run with BEAR_AMD_GRAPH_MAX_ROWS=0)
+            cap = os.environ.get("BEAR_AMD_GRAPH_MAX_ROWS")
+            graph_ok = graph_ok and (cap is None or max([e["global_rows"] for e in res.batches] + [0]) <= int(cap))
+        reduce_fns = _train.reducers(res, reducer_wide if wide_step else reducer)
         losses = _train.run_device_steps(reduce_fns, scales, theta, data.repeats, learning_rate, optimizer_name, train_ar, acc_steps, device,
-                                         graph_ok=not res.streaming)
+                                         graph_ok=graph_ok)
         with torch.no_grad():
             k = 0
             for p in params:

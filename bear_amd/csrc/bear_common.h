@@ -37,7 +37,9 @@ struct bear_ws {
   double *eval_out;         // [EVL_MAX_OUT] scratch result vector (bear_bmm_f64)
   int eval_blocks;
   double *lin_partials;     // [num_cu][LIN_MAX_GRAD] d/d mat partials (kernels_linrows.h)
-  double *linw_partials;    // [2 num_cu + 16][LNW_MAX_GRAD] d/d mat partials at width 21 (kernels_linrows_wide.h)
+  double *linw_partials;    // [2 num_cu + 16][2 + LNW_MAX_GRAD] block partials at width 21: d/d mat (kernels_linrows_wide.h), or the
+                            // packed rows [sum LL, d/dh, d/d mat] of the fused step (kernels_linear_wide.h) -- one launch at a time
+  double *linw_packed;      // [2 + LNW_MAX_GRAD] the fused step's sums when the caller wants them in two places (bear_dm_linear_wide_f64)
   double *lin_accum;        // [LIN_MAX_GRAD] d/d mat accumulator of the fused linear step (kernels_linear.h): zero between launches
   unsigned long long *arrive;      // arrival word of the launch that owns `partials` (bear_arrival: epoch << 24 | blocks arrived)
   unsigned epoch;                  // host side: the stamp of the last launch that used `arrive` (never 0)

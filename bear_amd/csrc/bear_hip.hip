@@ -72,6 +72,7 @@ static void ws_release(bear_ws *ws) {
   (void)hipFree(ws->eval_out);
   (void)hipFree(ws->lin_partials);
   (void)hipFree(ws->linw_partials);
+  (void)hipFree(ws->linw_packed);
   (void)hipFree(ws->lin_accum);
   (void)hipFree(ws->cnn_partials);
   (void)hipFree(ws->cnnw_partials);

@@ -3,7 +3,7 @@
 // One unit per kernel family, each the only one to include -- and so to emit -- the kernels it launches:
 //   bear_hip.hip     status strings, the workspace, synthetic tables, samplers, the row shuffle; the DM steps (rows, sorted,
 //                    planned, reference-aware, ref-mix) and the plan itself
-//   bear_linear.hip  k-mer packing, the paired lists, the linear AR head (fused step and rows, rows of 21), the Adam launch
+//   bear_linear.hip  k-mer packing, the paired lists, the linear AR head (fused step and rows, both also at rows of 21), the Adam launch
 //   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21
 //   bear_eval.hip    held-out evaluation (5- and 21-wide), the wide DM step and bear_ref's wide steps, the evaluation plan, the BMM marginal
 // What a unit needs of another goes through the declarations at the end of this file.
@@ -244,7 +244,7 @@ static inline int check_plan_step(const bear_ws *ws, const bear_plan *plan, cons
 // ------------------------------------------------------------------ across units
 // bear_ws_create: each family sets the dynamic-LDS limit of its own kernels and allocates the buffers of the workspace that only it
 // uses; BEAR_OK or BEAR_ERR_HIP (bear_last_hip_error).  What they allocated goes with the workspace (ws_release, bear_hip.hip).
-BEAR_INTERNAL int linear_ws_setup(bear_ws *ws);      // lin_partials, lin_accum, linw_partials
+BEAR_INTERNAL int linear_ws_setup(bear_ws *ws);      // lin_partials, lin_accum, linw_partials, linw_packed
 BEAR_INTERNAL int cnn_ws_setup(bear_ws *ws);         // cnnw_partials (cnn_partials grows on demand: cnn_backward_grid)
 BEAR_INTERNAL int eval_ws_setup(bear_ws *ws);        // eval_partials, eval_out
 

@@ -1,11 +1,12 @@
 // bear_linear.hip -- the linear AR head: k-mer packing and index words, the paired context lists of a plan, the fused DM step
-// (kernels_linear.h), the head as rows (kernels_linrows.h; kernels_linrows_wide.h at the protein alphabet's width), and the optimizer
-// update as a launch of its own (adam_vec_kernel).
+// (kernels_linear.h; kernels_linear_wide.h at the protein alphabet's width), the head as rows (kernels_linrows.h;
+// kernels_linrows_wide.h at that width), and the optimizer update as a launch of its own (adam_vec_kernel).
 // The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_linear.h"
 #include "kernels_linrows.h"
 #include "kernels_linrows_wide.h"
+#include "kernels_linear_wide.h"
 
 int linear_ws_setup(bear_ws *ws) {
 #define LIN_ALL_NGK(AR, PAIRED, DET)                                                                          \
@@ -19,7 +20,11 @@ int linear_ws_setup(bear_ws *ws) {
   if (st != BEAR_OK) return st;
   st = allow_dynamic_lds({BEAR_KFN(linear_wide_forward_kernel)}, LNW_FWD_LDS(LINEAR_WIDE_MAX_LAG));
   if (st != BEAR_OK) return st;
-  HIP_TRY(hipMalloc(&ws->linw_partials, sizeof(double) * LNW_MAX_GRAD * LNW_PARTIAL_ROWS(ws->num_cu)));
+  st = allow_dynamic_lds({BEAR_KFN(dm_linear_wide_kernel<false>), BEAR_KFN(dm_linear_wide_kernel<true>)}, LSW_LDS(LINEAR_WIDE_MAX_LAG));
+  if (st != BEAR_OK) return st;
+  static_assert(LSW_PARTIAL_ROWS(1) == LNW_PARTIAL_ROWS(1), "linw_partials: one buffer for the backward rows and the fused step");
+  HIP_TRY(hipMalloc(&ws->linw_partials, sizeof(double) * LSW_MAX_PACKED * LSW_PARTIAL_ROWS(ws->num_cu)));
+  HIP_TRY(hipMalloc(&ws->linw_packed, sizeof(double) * LSW_MAX_PACKED));
   HIP_TRY(hipMalloc(&ws->lin_partials, sizeof(double) * LIN_MAX_GRAD * (size_t)ws->num_cu * PLN_BLOCKS_PER_CU));
   HIP_TRY(hipMalloc(&ws->lin_accum, sizeof(double) * LIN_MAX_GRAD));
   HIP_TRY(hipMemset(ws->lin_accum, 0, sizeof(double) * LIN_MAX_GRAD));
@@ -340,6 +345,71 @@ int bear_linear_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_r
                      grad_prior, ws->linw_partials, ws_arrival(ws), grad_mat);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
+}
+
+// ---- bear_net's step with the linear AR function at the protein alphabet's width as one launch (kernels_linear_wide.h) ------------
+// the grid is part of the result (block partials summed in a fixed order per grid); linw_partials holds a row per block
+static int linstep_wide_grid(const bear_ws *ws, uint64_t n_rows) {
+  return grid_capped((n_rows + LSW_TILE - 1) / LSW_TILE, (uint64_t)ws->num_cu * LSW_BLOCKS_PER_CU);
+}
+
+// the checks and the launch of all three entries: theta != NULL: h_signed and mat from the device-resident parameters (prm: eps only);
+// `apply`: the block that sums the partials runs the update behind them.  n_rows == 0: one block, zeros (and the update).
+static int launch_linear_wide(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                              const double *mat, const double *theta, const bear_params &prm, int train_ar, double *packed, hipStream_t s,
+                              const bear_apply_io &apply) {
+  if (width != LNW_W || lag < 1 || lag > LINEAR_WIDE_MAX_LAG) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!packed || !mat || (n_rows && (!counts || !codes))) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(counts) || misaligned(codes) || misaligned8(mat) || misaligned8(packed) || !(prm.eps >= 0.0)) return BEAR_ERR_INVALID_ARG;
+  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, packed);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+#define LIN_WIDE(AR)                                                                                                                   \
+  hipLaunchKernelGGL((dm_linear_wide_kernel<AR>), dim3(linstep_wide_grid(ws, n_rows)), dim3(LSW_THREADS), LSW_LDS(lag), s, counts, codes, \
+                     n_rows, lag, mat, prm, lt, ws->linw_partials, io, apply)
+  BEAR_DISPATCH_1(train_ar, LIN_WIDE);
+#undef LIN_WIDE
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_dm_linear_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                            const double *mat, double h_signed, double eps, int train_ar, double *out, double *grad_mat, void *stream) {
+  if (!out || !grad_mat || misaligned8(out) || misaligned8(grad_mat) || !isfinite(h_signed)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the kernel leaves its sums as one packed vector: through the workspace, then to the caller's two arrays (same stream)
+  int st = launch_linear_wide(ws, counts, codes, n_rows, lag, width, mat, nullptr, params_net(h_signed, eps), train_ar, ws ? ws->linw_packed : out,
+                              s, NO_APPLY);
+  if (st != BEAR_OK) return st;
+  HIP_TRY(hipMemcpyAsync(out, ws->linw_packed, sizeof(double) * 2, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(grad_mat, ws->linw_packed + 2, sizeof(double) * (size_t)lag * LNW_MAT, hipMemcpyDeviceToDevice, s));
+  return BEAR_OK;
+}
+
+int bear_net_linear_train_reduce_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                                          const double *theta, double eps, int train_ar, double *packed, void *stream) {
+  if (!theta || misaligned8(theta)) return BEAR_ERR_INVALID_ARG;
+  return launch_linear_wide(ws, counts, codes, n_rows, lag, width, theta + 1, theta, params_eps(eps), train_ar, packed,
+                            static_cast<hipStream_t>(stream), NO_APPLY);
+}
+
+int bear_net_linear_train_step_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                                        double *theta, double *adam_m, double *adam_v, double *adam_t, double eps, int train_ar,
+                                        double learning_rate, double scale, double *packed, double *loss_buf, uint64_t loss_cap,
+                                        void *stream) {
+  if (!theta || !adam_m || !adam_v || !adam_t) return BEAR_ERR_INVALID_ARG;
+  if (misaligned8(theta) || misaligned8(adam_m) || misaligned8(adam_v) || misaligned8(adam_t) || misaligned8(loss_buf))
+    return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (two_launch_step()) {
+    int st = launch_linear_wide(ws, counts, codes, n_rows, lag, width, theta + 1, theta, params_eps(eps), train_ar, packed, s, NO_APPLY);
+    if (st != BEAR_OK) return st;
+    return launch_train_apply(theta, 1 + lag * LNW_MAT, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap, s);
+  }
+  // ONE launch: the block that sums the partials runs the update behind them (bear_apply_in_block)
+  return launch_linear_wide(ws, counts, codes, n_rows, lag, width, theta + 1, theta, params_eps(eps), train_ar, packed, s,
+                            make_apply(theta, 1 + lag * LNW_MAT, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
 }
 
 // the shard's reduce of the linear head's step: constants from theta, sums by the last block (one launch, or two on a partly

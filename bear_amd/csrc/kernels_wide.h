@@ -19,6 +19,7 @@
 #include "bear_common.h"
 #include "kernels_eval.h"
 #include "kernels_rows.h"
+#include "rows_wide_common.h"   // wide_nz_mask, wide_dm_row
 
 #define WIDE_THREADS 256
 // W = 21: 128 contexts = 10.5 KiB of counts + 21 KiB of prior rows (+ 2 KiB log table): LDS for four blocks per CU (160 KiB); the
@@ -26,14 +27,6 @@
 // half.  Measured 0.16 of 8 TB/s at 13 % non-zero cells: bound by the fp64 items, not the bytes.
 #define WIDE_TILE(W) ((W) > 8 ? 128 : 512)
 #define WIDE_BLOCKS_PER_CU 4
-
-template <int W>
-__device__ __forceinline__ uint32_t wide_nz_mask(const uint32_t *row) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int b = 0; b < W; ++b) m |= (row[b] != 0u ? 1u : 0u) << b;
-  return m;
-}
 
 template <int W, bool AR, bool GRAD>
 __global__ __launch_bounds__(WIDE_THREADS) void dm_wide_kernel(const uint32_t *__restrict__ counts, const double *__restrict__ prior,
@@ -58,60 +51,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void dm_wide_kernel(const uint32_t *_
     __syncthreads();
 #pragma unroll 1
     for (uint32_t r = threadIdx.x; r < rows; r += WIDE_THREADS) {
-      const uint32_t *c = s_cnt + r * W;
       double *f = s_pri + r * W;
-      uint32_t nz = wide_nz_mask<W>(c);
-      if (AR) {      // core.py:138-139 with probs = prior + eps (bear_net.py:68)
-        if (GRAD) {
-#pragma unroll
-          for (int b = 0; b < W; ++b)
-            if (!((nz >> b) & 1u)) f[b] = 0.0;
-        }
-        while (nz) {
-          const int b = __builtin_ctz(nz);
-          nz &= nz - 1u;
-          const double p = f[b] + prm.eps, cb = (double)c[b];
-          // the table log is exact to ~1e-16 ABSOLUTE (e ln2 - log r_i cancel for p just above 1): at p = 1 + eps (a one-hot prior
-          // row) that is 1e-9 of log p.  Near 1 the polynomial on p - 1 (exact there) keeps it relative.
-          const double lp = fabs(p - 1.0) < 0x1p-8 ? bear_log1p_small(p - 1.0) : (p > 0.0 ? bear_log_tab(p, s_log) : bear_log(p));
-          acc[0] += cb * lp;
-          if (GRAD) f[b] = cb * bear_rcp(p);
-        }
-      } else {
-        double n = 0.0, A = 0.0, sf = 0.0;
-#pragma unroll
-        for (int b = 0; b < W; ++b) {
-          n += (double)c[b];
-          A += __builtin_fma(f[b], prm.inv_h, prm.eps);
-          sf += f[b];
-        }
-        if (n == 0.0) {
-          if (GRAD) {
-#pragma unroll
-            for (int b = 0; b < W; ++b) f[b] = 0.0;
-          }
-          continue;
-        }
-        const bear_dp tn = dm_row_item(A, n, s_log);
-        double ll = -tn.D, dh = -tn.P * sf;          // dh = sum_b g_b f_b with g_b = -tn.P + [c_b > 0] item_b.P
-        const double g0 = -tn.P * prm.inv_h;
-        if (GRAD) {
-#pragma unroll
-          for (int b = 0; b < W; ++b)
-            if (!((nz >> b) & 1u)) f[b] = g0;
-        }
-        while (nz) {
-          const int b = __builtin_ctz(nz);
-          nz &= nz - 1u;
-          const double fb = f[b];
-          const bear_dp tb = dm_row_item(__builtin_fma(fb, prm.inv_h, prm.eps), (double)c[b], s_log);
-          ll += tb.D;
-          dh = __builtin_fma(tb.P, fb, dh);
-          if (GRAD) f[b] = (tb.P - tn.P) * prm.inv_h;
-        }
-        acc[0] += ll;
-        acc[1] -= dh * prm.inv_h;  // d alpha_b / d h_signed = -f_b / h
-      }
+      wide_dm_row<W, AR, GRAD>(s_cnt + r * W, f, f, prm, s_log, acc);   // the gradient row in place
     }
     if (GRAD) {
       __syncthreads();   // every row of the tile holds its gradient: 16-byte stores of the whole tile

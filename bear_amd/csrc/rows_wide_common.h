@@ -1,12 +1,83 @@
-// rows_wide_common.h -- device routines the row kernels of the protein alphabet's width share (kernels_linrows_wide.h,
-// kernels_cnn_wide.h): a tile of 21-wide rows out of LDS, and the fixed-order sum over rows of block partials.  No kernels here.
+// rows_wide_common.h -- device routines the kernels of the protein alphabet's width share (kernels_wide.h, kernels_linrows_wide.h,
+// kernels_cnn_wide.h, kernels_linear_wide.h): the DM step of one staged context (the sparse item walk), a tile of 21-wide rows out of
+// LDS, and the fixed-order sum over rows of block partials.  No kernels here.
 #pragma once
 #include "bear_common.h"
+#include "kernels_rows.h"   // dm_row_item
 
 #define LNW_W 21
 
 typedef double lnw_d4 __attribute__((ext_vector_type(4)));
 typedef uint32_t lnw_v4u __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------ the DM step of one context at width W
+template <int W>
+__device__ __forceinline__ uint32_t wide_nz_mask(const uint32_t *row) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int b = 0; b < W; ++b) m |= (row[b] != 0u ? 1u : 0u) << b;
+  return m;
+}
+
+// Mode N of one context out of LDS: counts c[W], prior row f[W]; acc[0] += LL, acc[1] += d LL / d h_signed (BEAR mode), and with GRAD
+// the row q[W] = d LL / d f.  A lane walks the bit mask of ITS non-zero cells (kernels_wide.h, "sparse"); a zero cell gets the shared
+// row term only.  q may be f itself (dm_wide_kernel: the gradient row in place): every cell is read before it is written.
+template <int W, bool AR, bool GRAD>
+__device__ __forceinline__ void wide_dm_row(const uint32_t *c, const double *f, double *q, const bear_params &prm, const double2 *s_log,
+                                            double (&acc)[2]) {
+  uint32_t nz = wide_nz_mask<W>(c);
+  if (AR) {      // core.py:138-139 with probs = prior + eps (bear_net.py:68)
+    if (GRAD) {
+#pragma unroll
+      for (int b = 0; b < W; ++b)
+        if (!((nz >> b) & 1u)) q[b] = 0.0;
+    }
+    while (nz) {
+      const int b = __builtin_ctz(nz);
+      nz &= nz - 1u;
+      const double p = f[b] + prm.eps, cb = (double)c[b];
+      // the table log is exact to ~1e-16 ABSOLUTE (e ln2 - log r_i cancel for p just above 1): at p = 1 + eps (a one-hot prior
+      // row) that is 1e-9 of log p.  Near 1 the polynomial on p - 1 (exact there) keeps it relative.
+      const double lp = fabs(p - 1.0) < 0x1p-8 ? bear_log1p_small(p - 1.0) : (p > 0.0 ? bear_log_tab(p, s_log) : bear_log(p));
+      acc[0] += cb * lp;
+      if (GRAD) q[b] = cb * bear_rcp(p);
+    }
+  } else {
+    double n = 0.0, A = 0.0, sf = 0.0;
+#pragma unroll
+    for (int b = 0; b < W; ++b) {
+      n += (double)c[b];
+      A += __builtin_fma(f[b], prm.inv_h, prm.eps);
+      sf += f[b];
+    }
+    if (n == 0.0) {
+      if (GRAD) {
+#pragma unroll
+        for (int b = 0; b < W; ++b) q[b] = 0.0;
+      }
+      return;
+    }
+    const bear_dp tn = dm_row_item(A, n, s_log);
+    double ll = -tn.D, dh = -tn.P * sf;          // dh = sum_b g_b f_b with g_b = -tn.P + [c_b > 0] item_b.P
+    const double g0 = -tn.P * prm.inv_h;
+    if (GRAD) {
+#pragma unroll
+      for (int b = 0; b < W; ++b)
+        if (!((nz >> b) & 1u)) q[b] = g0;
+    }
+    while (nz) {
+      const int b = __builtin_ctz(nz);
+      nz &= nz - 1u;
+      const double fb = f[b];
+      const bear_dp tb = dm_row_item(__builtin_fma(fb, prm.inv_h, prm.eps), (double)c[b], s_log);
+      ll += tb.D;
+      dh = __builtin_fma(tb.P, fb, dh);
+      if (GRAD) q[b] = (tb.P - tn.P) * prm.inv_h;
+    }
+    acc[0] += ll;
+    acc[1] -= dh * prm.inv_h;  // d alpha_b / d h_signed = -f_b / h
+  }
+}
 
 // rows [0, rows) of an LDS tile of 21-wide fp64 rows to dst (16-byte aligned) as 16-byte stores; nontemporal: not read again here
 template <int NT>
@@ -42,9 +113,10 @@ __device__ __forceinline__ void lnw_sum_rows(const double *__restrict__ src, uin
 // bear_store_agent; 16 more rows behind them) in two levels over the counters of bear_arrive_last: a block arrives at the counter
 // of its number mod 16; the last one there sums that class, ascending, into the row behind the blocks' and arrives at the top
 // word; the last one there sums the class rows into `out`.  Which block does either is arbitrary, what it adds in which order is
-// not.  Called by every thread of every block once its own row is stored; s_flag: a word of the block's LDS.
+// not.  Called by every thread of every block once its own row is stored; s_flag: a word of the block's LDS.  True (block-uniform)
+// in the block that wrote `out`.
 template <int NT>
-__device__ __forceinline__ void lnw_sum_partials(double *__restrict__ partials, int n_grad, const bear_arrival &arrive, unsigned *s_flag,
+__device__ __forceinline__ bool lnw_sum_partials(double *__restrict__ partials, int n_grad, const bear_arrival &arrive, unsigned *s_flag,
                                                  double *__restrict__ out) {
   const uint32_t tid = threadIdx.x;
   const unsigned grid = gridDim.x, sub = blockIdx.x % BEAR_ARRIVE_SUBS;
@@ -55,7 +127,7 @@ __device__ __forceinline__ void lnw_sum_partials(double *__restrict__ partials, 
   __syncthreads();
   if (tid == 0) *s_flag = bear_arrive_count(arrive.word + (1u + sub) * BEAR_ARRIVE_STRIDE, tag, in_sub) ? 1u : 0u;
   __syncthreads();
-  if (!*s_flag) return;
+  if (!*s_flag) return false;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   double *classes = partials + (size_t)grid * n_grad;
   lnw_sum_rows<NT, true>(partials, sub, BEAR_ARRIVE_SUBS, in_sub, n_grad, classes + (size_t)sub * n_grad);
@@ -63,8 +135,9 @@ __device__ __forceinline__ void lnw_sum_partials(double *__restrict__ partials, 
   __syncthreads();
   if (tid == 0) *s_flag = bear_arrive_count(arrive.word, tag, subs) ? 1u : 0u;
   __syncthreads();
-  if (!*s_flag) return;
+  if (!*s_flag) return false;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   lnw_sum_rows<NT, false>(classes, 0, 1, subs, n_grad, out);
   if (tid == 0) bear_arrive_reset(arrive);
+  return true;
 }

@@ -1184,6 +1184,88 @@ def net_linear_train_step(plan, kmer_code, lag, theta, adam_m, adam_v, adam_t, p
     _lib.check(st, "bear_net_linear_train_step_f64")
 
 
+# tile and resident blocks per CU of the fused linear step at width 21 (kernels_linear_wide.h: LSW_TILE, LSW_BLOCKS_PER_CU): a launch
+# takes min(tiles, blocks per CU * CUs) blocks -- tests size a table beyond that from these
+LINEAR_STEP_WIDE_TILE = 128
+LINEAR_STEP_WIDE_BLOCKS_PER_CU = 2
+
+
+def _check_linear_step_wide(counts, codes, lag):
+    W = LINEAR_WIDE_WIDTH
+    if not 1 <= int(lag) <= LINEAR_WIDE_MAX_LAG:
+        raise ValueError(f"lag must be 1..{LINEAR_WIDE_MAX_LAG} (mat [lag, {W}, {W}] lives in LDS)")
+    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.dim() == 2 and counts.shape[1] == W and counts.is_contiguous()):
+        raise ValueError(f"counts must be a contiguous CUDA int32 tensor [n, {W}]")
+    if not (codes.is_cuda and codes.dtype == torch.int8 and codes.dim() == 2 and codes.shape[1] == lag and codes.is_contiguous()):
+        raise ValueError("codes must be a contiguous CUDA int8 tensor [n, lag]")
+    if codes.shape[0] != counts.shape[0] or codes.device != counts.device:
+        raise ValueError("counts and codes must have the same number of rows, on one device")
+    if counts.data_ptr() % 16:
+        counts = counts.clone()
+    if codes.data_ptr() % 16:
+        codes = codes.clone()
+    return counts, codes
+
+
+def dm_linear_wide(counts, codes, mat, h_signed, eps=EPSILON, train_ar=False, out=None, ws=None):
+    """One launch of ``bear_dm_linear_wide_f64``: ``dm_linear`` on protein rows without a plan -- the linear AR function, the DM step
+    and the gradient of mat in one kernel (what ``linear_forward_wide``, ``dm_prior_wide(want_grad=True)`` and ``linear_backward_wide``
+    compute in three).  Returns (out [2] = sum LL, d/dh_signed; d sum LL / d mat [lag, 21, 21])."""
+    W = LINEAR_WIDE_WIDTH
+    if not (mat.dim() == 3 and tuple(mat.shape[1:]) == (W, W)):
+        raise ValueError(f"mat must be a contiguous CUDA float64 tensor [lag, {W}, {W}]")
+    lag = mat.shape[0]
+    counts, codes = _check_linear_step_wide(counts, codes, lag)
+    if not (mat.is_cuda and mat.dtype == torch.float64 and mat.is_contiguous() and mat.device == counts.device):
+        raise ValueError(f"mat must be a contiguous CUDA float64 tensor [lag, {W}, {W}]")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=counts.device)
+    _f64_vec(out, 2, "out")
+    ws = ws or default_workspace(counts.device)
+    grad = torch.empty_like(mat)
+    with torch.cuda.device(counts.device):
+        st = _lib.lib().bear_dm_linear_wide_f64(ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag), W, _ptr(mat),
+                                                float(h_signed), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
+    _lib.check(st, "bear_dm_linear_wide_f64")
+    return out, grad
+
+
+def net_linear_train_reduce_wide(counts, codes, lag, theta, packed, eps=EPSILON, train_ar=False, ws=None):
+    """Enqueues ``bear_net_linear_train_reduce_wide_f64``: packed = [sum LL, d/dh_s, d/d mat (lag*441)] of these rows, theta =
+    {h_signed, mat} device-resident."""
+    counts, codes = _check_linear_step_wide(counts, codes, lag)
+    size = 1 + lag * LINEAR_WIDE_WIDTH * LINEAR_WIDE_WIDTH
+    _f64_vec(theta, size, "theta")
+    _f64_vec(packed, size + 1, "packed")
+    ws = ws or default_workspace(counts.device)
+    with torch.cuda.device(counts.device):
+        st = _lib.lib().bear_net_linear_train_reduce_wide_f64(ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
+                                                              LINEAR_WIDE_WIDTH, _ptr(theta), float(eps), int(bool(train_ar)),
+                                                              _ptr(packed), _stream())
+    _lib.check(st, "bear_net_linear_train_reduce_wide_f64")
+
+
+def net_linear_train_step_wide(counts, codes, lag, theta, adam_m, adam_v, adam_t, packed, learning_rate, scale, loss_buf=None,
+                               eps=EPSILON, train_ar=False, ws=None):
+    """Enqueues one ``bear_net_linear_train_step_wide_f64`` (HIP-graph capturable): the reduce and tf.keras Adam on theta =
+    {h_signed, mat [lag, 21, 21]} in one launch."""
+    counts, codes = _check_linear_step_wide(counts, codes, lag)
+    size = 1 + lag * LINEAR_WIDE_WIDTH * LINEAR_WIDE_WIDTH
+    for t, k, name in ((theta, size, "theta"), (adam_m, size, "adam_m"), (adam_v, size, "adam_v"), (adam_t, 1, "adam_t"),
+                       (packed, size + 1, "packed")):
+        _f64_vec(t, k, name)
+    if loss_buf is not None:
+        _f64_vec(loss_buf, loss_buf.numel(), "loss_buf")
+    ws = ws or default_workspace(counts.device)
+    with torch.cuda.device(counts.device):
+        st = _lib.lib().bear_net_linear_train_step_wide_f64(ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
+                                                            LINEAR_WIDE_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t),
+                                                            float(eps), int(bool(train_ar)), float(learning_rate), float(scale),
+                                                            _ptr(packed), _ptr(loss_buf), 0 if loss_buf is None else loss_buf.numel(),
+                                                            _stream())
+    _lib.check(st, "bear_net_linear_train_step_wide_f64")
+
+
 def net_cnn_train_reduce(plan, kmer_code, lag, filter_width, theta, bufs, packed, eps=EPSILON, train_ar=False):
     """Enqueues ``bear_net_cnn_train_reduce_f64``: forward, planned DM kernel with gradient rows, backward;
     packed = [sum LL, d/dh_s, d/d params] of this shard.  ``bufs`` = (prior [n,5], t1 [n,16], grad_rows [n,5]) from ``cnn_step_buffers``."""

@@ -44,7 +44,10 @@ extern "C" {
                               11: + bear_cnn_param_count_wide, bear_cnn_forward_wide_f64, bear_cnn_backward_wide_f64 (the convolutional AR
                                   function as rows of 21);
                               12: + bear_dm_ref_wide_f64, bear_ref_train_reduce_wide_f64, bear_ref_train_step_wide_f64,
-                                  bear_dm_refmix_wide_grad_f64 (bear_ref's training step on rows of 21) */
+                                  bear_dm_refmix_wide_grad_f64 (bear_ref's training step on rows of 21);
+                                  still 12 (symbols added, nothing changed): + bear_dm_linear_wide_f64,
+                                  bear_net_linear_train_reduce_wide_f64, bear_net_linear_train_step_wide_f64 (bear_net's step with the
+                                  linear AR function on rows of 21 as one launch) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -361,6 +364,33 @@ int bear_linear_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_ro
                                  double *prior, void *stream);
 int bear_linear_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int width, const double *prior,
                                   const double *grad_prior, double *grad_mat, void *stream);
+
+/*
+ * bear_net's training step with the linear AR function at the protein alphabet's width as ONE launch (kernels_linear_wide.h): what
+ * bear_linear_forward_wide_f64, bear_dm_prior_wide_f64 with gradient rows and bear_linear_backward_wide_f64 compute in three, without a
+ * row ever reaching memory.  No plan, any row order.
+ *   counts     [dev] uint32 [n_rows,21]  16-byte aligned;  codes [dev] int8 [n_rows,lag], 16-byte aligned (as above)
+ *   width      21, lag 1 .. LINEAR_WIDE_MAX_LAG (anything else: BEAR_ERR_INVALID_ARG, nothing is launched)
+ * bear_dm_linear_wide_f64: the primitive, constants by value (bear_dm_linear_f64 without a plan):
+ *   mat [dev] double [lag,21,21];  out [dev] double [2] = {sum LL, d sum LL / d h_signed (0 with train_ar)};
+ *   grad_mat [dev] double [lag,21,21] = d sum LL / d mat, overwritten.
+ * bear_net_linear_train_reduce_wide_f64 / bear_net_linear_train_step_wide_f64: bear_net_linear_train_reduce_f64 /
+ *   bear_net_linear_train_step_f64 at this width: theta [dev] double [1 + 441 lag] = {h_signed, mat...}, read on the device;
+ *   packed [dev] double [2 + 441 lag] = {sum LL, d/dh, d/d mat...}.  The step form runs the tf.keras Adam update of theta (adam_m,
+ *   adam_v [1 + 441 lag], adam_t [1]) and the loss record (bear_train_apply_f64's arguments) in the block that sums the partials:
+ *   the same bits as reduce followed by bear_train_apply_f64, which is what BEAR_AMD_TWO_LAUNCH_STEP=1 makes of it.
+ * n_rows == 0: zeros (the step form still updates and records).  No floating-point atomics: block partials are summed in a fixed
+ * order, the same inputs give the same bits from run to run for a given device (grid: min(n_rows / 128, 2 x CUs) blocks), identically
+ * in both builds of the library.  Asynchronous on `stream`, nothing is read back to the host: all three can be captured into a HIP graph.
+ */
+int bear_dm_linear_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                            const double *mat, double h_signed, double eps, int train_ar, double *out, double *grad_mat, void *stream);
+int bear_net_linear_train_reduce_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                                          const double *theta, double eps, int train_ar, double *packed, void *stream);
+int bear_net_linear_train_step_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int width,
+                                        double *theta, double *adam_m, double *adam_v, double *adam_t, double eps, int train_ar,
+                                        double learning_rate, double scale, double *packed, double *loss_buf, uint64_t loss_cap,
+                                        void *stream);
 
 /*
  * bear_ref's prior rows for a net function with parameters (linear, cnn): replaces the arithmetic of _make_ref_ar_func's ar_func
