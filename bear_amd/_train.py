@@ -7,7 +7,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, core, dist, kernels
+from . import _lib, ar_funcs, core, dist, kernels
 from .dataloader import CountDataset
 
 epsilon = core.epsilon
@@ -873,6 +873,44 @@ def evaluation_sums(test, prior, h, van_reg, train=None, eps=epsilon, noise_seed
     sums = EvaluationSums(h, van_reg, eps=eps, noise_seed=noise_seed)
     sums.add(test, prior, train, row_base=row_base, plan=plan, row_ids=row_ids)
     return sums.result()
+
+
+def evaluate_resident(data, cols, h, van_reg, seed, dtype, device, prior_rows, net_func):
+    """The evaluation loop of both drivers (bear_net.py:387-463, bear_ref.py:453-539): this rank's sums over the resident batches of
+    the columns ``cols`` (test, and the conditioning column when there is one).  ``prior_rows(e, suffix)`` gives the AR rows of a
+    batch entry's contexts from its columns ``<name> + suffix``: "" for all of them, "_live_test" for the ones with held-out
+    counts.  ``net_func``: the AR function whose k-mer order and cache the batches follow."""
+    width = row_width(data)
+    wide = width != 5
+    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids);
+    # rows wider than 5 are evaluated unplanned, in table order (row_base + i is the key of their tie-breaking noise)
+    res = ResidentBatches(data, cols, device, want_codes=True, drop_empty=None if wide else "test",
+                          per_row_extra=8 * width + 20,   # prior rows + plan
+                          kmer_order=ar_funcs.wants_kmer_order(net_func))
+    sums = EvaluationSums(h, van_reg, noise_seed=seed)     # the batches' sums stay on the device until all are enqueued
+    with torch.no_grad():
+        for k, e in res.loaded():
+            if not e["rows"]:
+                prior = torch.zeros((0, width), dtype=dtype, device=device)
+            else:                                        # prior rows of the contexts with held-out counts: nothing else enters a sum
+                live = live_rows(e, "codes", by="test")
+                out = prior_rows(e, "" if live is None else "_live_test")
+                # (a parameter-free AR function may return one row for all contexts)
+                prior = out.expand(e["rows"], width).contiguous() if live is None or out.shape[0] == 1 else scatter_live(out, live, e["rows"])
+            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] and not wide else None,
+                     row_ids=e.get("row_ids") if e["rows"] else None)
+    res.close()
+    ar_funcs.release_ar_func_cache(net_func)
+    return sums.result()
+
+
+def restore_params(created, saved):
+    """``change_scope_params`` of both drivers (bear_net.py:103-143, bear_ref.py:166-204): the (params, h_signed, ar_func) that a
+    driver's ``_create_params`` made, its parameters set to the ``saved`` values."""
+    with torch.no_grad():
+        for p, q in zip(created[0], saved):
+            p.copy_(torch.as_tensor(q, dtype=p.dtype))
+    return created
 
 
 def reduce_evaluation(parts, device, scalar_h):

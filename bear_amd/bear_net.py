@@ -25,11 +25,7 @@ def _create_params(lag, alphabet_size, make_ar_func, af_kwargs, dtype=torch.floa
 
 def change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params, dtype=torch.float64, device=None):
     """bear_net.py:103-143."""
-    new, h_signed, ar_func = _create_params(lag, alphabet_size, make_ar_func, af_kwargs, dtype, device)
-    with torch.no_grad():
-        for p, q in zip(new, params):
-            p.copy_(torch.as_tensor(q, dtype=p.dtype))
-    return new, h_signed, ar_func
+    return _train.restore_params(_create_params(lag, alphabet_size, make_ar_func, af_kwargs, dtype, device), params)
 
 
 def linear_wide_step_selected(alphabet_size, lag, own_mat, width):
@@ -165,31 +161,9 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
 def _eval(data, ds_loc_train, ds_loc_test, alphabet, h, ar_func, van_reg, dtype, seed):
     dtype = _train.compute_dtype(dtype)
     device = _train.require_device()
-    use_train = ds_loc_train >= 0
-    cols = {"test": ds_loc_test}
-    if use_train:
-        cols["train"] = ds_loc_train
-    width = _train.row_width(data)
-    wide = width != 5
-    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids);
-    # rows wider than 5 are evaluated unplanned, in table order (row_base + i is the key of their tie-breaking noise)
-    res = _train.ResidentBatches(data, cols, device, want_codes=True, drop_empty=None if wide else "test",
-                                 per_row_extra=8 * width + 20,   # prior rows + plan
-                                 kmer_order=ar_funcs.wants_kmer_order(ar_func))
-    sums = _train.EvaluationSums(h, van_reg, noise_seed=seed)     # the batches' sums stay on the device until all are enqueued
-    with torch.no_grad():
-        for k, e in res.loaded():
-            if not e["rows"]:
-                prior = torch.zeros((0, width), dtype=dtype, device=device)
-            else:                                        # prior rows of the contexts with held-out counts: nothing else enters a sum
-                live = _train.live_rows(e, "codes", by="test")
-                out = ar_func(e["codes"] if live is None else e["codes_live_test"])
-                prior = out.expand(e["rows"], width).contiguous() if live is None or out.shape[0] == 1 else _train.scatter_live(out, live, e["rows"])
-            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] and not wide else None,
-                     row_ids=e.get("row_ids") if e["rows"] else None)
-    res.close()
-    ar_funcs.release_ar_func_cache(ar_func)
-    return sums.result(), device
+    cols = {"test": ds_loc_test, **({"train": ds_loc_train} if ds_loc_train >= 0 else {})}
+    total = _train.evaluate_resident(data, cols, h, van_reg, seed, dtype, device, lambda e, suffix: ar_func(e["codes" + suffix]), ar_func)
+    return total, device
 
 
 def evaluation(data, ds_loc_train, ds_loc_test, alphabet, h, ar_func, van_reg, dtype=torch.float64, seed=0):

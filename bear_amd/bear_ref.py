@@ -74,11 +74,7 @@ def _create_params(lag, alphabet_size, make_ar_func, af_kwargs, dtype=torch.floa
 
 def change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params, dtype=torch.float64, device=None):
     """bear_ref.py:166-204: rebuilds (params, h_signed, ar_func) from a saved parameter list."""
-    new, h_signed, ar_func = _create_params(lag, alphabet_size, make_ar_func, af_kwargs, dtype, device)
-    with torch.no_grad():
-        for p, q in zip(new, params):
-            p.copy_(torch.as_tensor(q, dtype=p.dtype))
-    return new, h_signed, ar_func
+    return _train.restore_params(_create_params(lag, alphabet_size, make_ar_func, af_kwargs, dtype, device), params)
 
 
 def _ref_input(ref_slab, dtype=torch.float64):
@@ -206,33 +202,13 @@ def evaluation(data, ds_loc_train, ds_loc_test, ds_loc_ref, alphabet, h, ar_func
     bear_ref.py:397 vs bear_net.py:327)."""
     dtype = _train.compute_dtype(dtype)
     device = _train.require_device()
-    use_train = ds_loc_train >= 0
-    cols = {"test": ds_loc_test, "ref": ds_loc_ref}
-    if use_train:
-        cols["train"] = ds_loc_train
-    width = _train.row_width(data)
-    wide = width != 5
-    # only the contexts with held-out counts are kept resident: nothing else enters any sum (their table rows travel as row_ids);
-    # rows wider than 5 are evaluated unplanned, in table order (row_base + i is the key of their tie-breaking noise)
-    res = _train.ResidentBatches(data, cols, device, want_codes=True, drop_empty=None if wide else "test",
-                                 per_row_extra=8 * width + 20,   # prior rows + plan
-                                 kmer_order=_ar_funcs.wants_kmer_order(getattr(ar_func, "net_func", ar_func)))
+    cols = {"test": ds_loc_test, "ref": ds_loc_ref, **({"train": ds_loc_train} if ds_loc_train >= 0 else {})}
     hv = float(torch.as_tensor(h).item()) if np.ndim(torch.as_tensor(h).detach().cpu().numpy()) == 0 else torch.as_tensor(h).detach().cpu().numpy()
-    sums = _train.EvaluationSums(hv, van_reg, noise_seed=seed)     # the batches' sums stay on the device until all are enqueued
-    with torch.no_grad():
-        for k, e in res.loaded():
-            if not e["rows"]:
-                prior = torch.zeros((0, width), dtype=dtype, device=device)
-            else:                                        # prior rows of the contexts with held-out counts: nothing else enters a sum
-                if "ref_in" not in e:
-                    e["ref_in"] = _ref_input(e["ref"], dtype)
-                live = _train.live_rows(e, "codes", "ref_in", by="test")
-                if live is None:
-                    prior = ar_func(e["codes"], e["ref_in"]).expand(e["rows"], width).contiguous()
-                else:
-                    prior = _train.scatter_live(ar_func(e["codes_live_test"], e["ref_in_live_test"]), live, e["rows"])
-            sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] and not wide else None,
-                     row_ids=e.get("row_ids") if e["rows"] else None)
-    res.close()
-    _ar_funcs.release_ar_func_cache(getattr(ar_func, "net_func", ar_func))
-    return _train.reduce_evaluation(sums.result(), device, np.ndim(hv) == 0)
+
+    def prior_rows(e, suffix):
+        if "ref_in" not in e:
+            e["ref_in"] = _ref_input(e["ref"], dtype)
+        _train.live_rows(e, "ref_in", by="test")         # (gathers the live contexts' reference rows next to their codes)
+        return ar_func(e["codes" + suffix], e["ref_in" + suffix])
+    total = _train.evaluate_resident(data, cols, hv, van_reg, seed, dtype, device, prior_rows, getattr(ar_func, "net_func", ar_func))
+    return _train.reduce_evaluation(total, device, np.ndim(hv) == 0)

@@ -318,20 +318,13 @@ def cache_path_for(file, binary_cache):
 
 def _load_cache(path, file, num_ds, rows=None):
     """The parsed table from a valid, fresh binary cache, or None."""
-    L = _lib.lib()
-    n, lag, nds, ssz, smt = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64(), ctypes.c_int64()
-    if not os.path.exists(path) or L.bear_cache_info(path.encode(), ctypes.byref(n), ctypes.byref(lag), ctypes.byref(nds),
-                                                     ctypes.byref(ssz), ctypes.byref(smt)) != 0:
+    meta = _cache_meta(path, file, num_ds)
+    if meta is None:
         return None
-    fsz, fmt = ctypes.c_uint64(), ctypes.c_int64()
-    if L.bear_stat_source(str(file).encode(), ctypes.byref(fsz), ctypes.byref(fmt)) != 0:
-        return None
-    if (fsz.value, fmt.value) != (ssz.value, smt.value) or nds.value != num_ds:
-        return None      # stale (source rewritten) or parsed with another num_ds
-    a, b = rows if rows is not None else (0, n.value)
-    kmers = np.zeros((b - a, lag.value), dtype=np.uint8)
+    a, b = rows if rows is not None else (0, meta[0])
+    kmers = np.zeros((b - a, meta[1]), dtype=np.uint8)
     counts = np.zeros((num_ds, b - a, 5), dtype=np.uint32)
-    _lib.check(L.bear_cache_read(path.encode(), a, b - a, kmers.ctypes.data, counts.ctypes.data), "bear_cache_read")
+    _lib.call("bear_cache_read", path.encode(), a, b - a, kmers.ctypes.data, counts.ctypes.data)
     return kmers, counts
 
 
@@ -346,21 +339,21 @@ def _cache_meta(path, file, num_ds):
     if L.bear_stat_source(str(file).encode(), ctypes.byref(fsz), ctypes.byref(fmt)) != 0:
         return None
     if (fsz.value, fmt.value) != (ssz.value, smt.value) or nds.value != num_ds:
-        return None
+        return None      # stale (source rewritten) or parsed with another num_ds
     return n.value, lag.value
 
 
 def count_rows(file, header=False):
     """Number of table rows of a count file (non-empty lines, minus the header line)."""
     n = ctypes.c_uint64()
-    _lib.check(_lib.lib().bear_count_rows(str(file).encode(), ctypes.byref(n)), "bear_count_rows")
+    _lib.call("bear_count_rows", str(file).encode(), ctypes.byref(n))
     return n.value - (1 if header and n.value else 0)
 
 
 def count_newlines(file):
     """``wc -l`` of a file on all host threads (the reference's ``num_kmers``, models/train_bear_net.py:52-55)."""
     n = ctypes.c_uint64()
-    _lib.check(_lib.lib().bear_count_newlines(str(file).encode(), ctypes.byref(n)), "bear_count_newlines")
+    _lib.call("bear_count_newlines", str(file).encode(), ctypes.byref(n))
     return n.value
 
 
@@ -375,7 +368,6 @@ def dataloader(file, alphabet, batch_size, num_ds, cache=True, header=False, n_p
     whole table and no rank of a sharded run has it; build it once with an unsharded ``dataloader(..., binary_cache=...)`` call
     (``models/_driver.py`` does that on rank 0 when ``[data] binary_cache`` is set and the table fits its host memory).  ``row_base`` / ``total_rows`` place the file inside a table made of several files (the batches
     -- and so the pieces -- are cut on the whole table); by default the file is the table."""
-    L = _lib.lib()
     A1 = len(core.alphabets_tf[alphabet])
     deal_kmer = shard == "kmer"
     if A1 != 5 and deal_kmer:
@@ -394,7 +386,7 @@ def dataloader(file, alphabet, batch_size, num_ds, cache=True, header=False, n_p
                                       "only (dna / rna)")
         if row_base or total_rows is not None:
             raise ValueError("row_base / total_rows place a file inside a sharded table")
-        return _load_wide(file, alphabet, A1, batch_size, int(num_ds), header, dtype)
+        return CountDataset(*_parse_table(file, int(num_ds), A1, header), alphabet, batch_size, dtype)
     if deal_kmer and shard is not None:
         # rows dealt to the ranks by k-mer range (KmerDealtDataset): every rank parses the whole table and keeps its range
         whole = dataloader(file, alphabet, batch_size, num_ds, cache=cache, header=header, n_par=n_par, dtype=dtype,
@@ -410,48 +402,36 @@ def dataloader(file, alphabet, batch_size, num_ds, cache=True, header=False, n_p
         hit = _load_cache(cache_path_for(file, binary_cache), file, num_ds)
         if hit is not None:
             return CountDataset(hit[0], hit[1], alphabet, batch_size, dtype)
-    n_rows = count_rows(file, header)
-    lag = _sniff_lag(file, header, b"\t")
-    kmers = np.zeros((n_rows, lag), dtype=np.uint8)
-    counts = np.zeros((num_ds, n_rows, A1), dtype=np.uint32)
-    got = ctypes.c_uint64()
-    if header:      # the sharded reader with one rank is the plain reader with a header line
-        _lib.check(L.bear_parse_counts_tsv_shard(str(file).encode(), int(num_ds), int(lag), 1, 0, n_rows, max(n_rows, 1), 0, 1, n_rows,
-                                                 kmers.ctypes.data, counts.ctypes.data, ctypes.byref(got), None), "bear_parse_counts_tsv_shard")
-    else:
-        _lib.check(L.bear_parse_counts_tsv(str(file).encode(), int(num_ds), int(lag), n_rows, kmers.ctypes.data,
-                                           counts.ctypes.data, ctypes.byref(got)), "bear_parse_counts_tsv")
-    if got.value != n_rows:
-        raise RuntimeError(f"{file}: {got.value} rows parsed, {n_rows} counted (did the file change while it was read?)")
+    kmers, counts = _parse_table(file, int(num_ds), A1, header)
     if binary_cache:
         fsz, fmt = ctypes.c_uint64(), ctypes.c_int64()
-        _lib.check(L.bear_stat_source(str(file).encode(), ctypes.byref(fsz), ctypes.byref(fmt)), "bear_stat_source")
+        _lib.call("bear_stat_source", str(file).encode(), ctypes.byref(fsz), ctypes.byref(fmt))
         path = cache_path_for(file, binary_cache)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        _lib.check(L.bear_cache_write(path.encode(), kmers.ctypes.data, counts.ctypes.data, n_rows, int(lag), int(num_ds),
-                                      fsz.value, fmt.value), "bear_cache_write")
+        _lib.call("bear_cache_write", path.encode(), kmers.ctypes.data, counts.ctypes.data, kmers.shape[0], kmers.shape[1], int(num_ds),
+                  fsz.value, fmt.value)
     return CountDataset(kmers, counts, alphabet, batch_size, dtype)
 
 
-def _load_wide(file, alphabet, width, batch_size, num_ds, header, dtype):
-    """The whole table with rows of ``width`` counts per dataset column (``bear_parse_counts_tsv_wide``; with a header line the
-    one-rank form of the sharded reader, as ``dataloader`` does for 5-wide rows)."""
-    L = _lib.lib()
+def _parse_table(file, num_ds, width, header):
+    """(kmers, counts) of the whole table: ``bear_parse_counts_tsv``, or its ``_wide`` twin for rows of ``width`` != 5 counts per
+    dataset column; with a header line the one-rank form of the sharded reader, which is the plain reader behind a header."""
     n_rows = count_rows(file, header)
     lag = _sniff_lag(file, header, b"\t")
     kmers = np.zeros((n_rows, lag), dtype=np.uint8)
     counts = np.zeros((num_ds, n_rows, width), dtype=np.uint32)
     got = ctypes.c_uint64()
-    if header:
-        _lib.check(L.bear_parse_counts_tsv_shard_wide(str(file).encode(), num_ds, width, int(lag), 1, 0, n_rows, max(n_rows, 1), 0, 1,
-                                                      n_rows, kmers.ctypes.data, counts.ctypes.data, ctypes.byref(got), None),
-                   "bear_parse_counts_tsv_shard_wide")
+    if width == 5:
+        plain, shard, head = "bear_parse_counts_tsv", "bear_parse_counts_tsv_shard", (str(file).encode(), num_ds, int(lag))
     else:
-        _lib.check(L.bear_parse_counts_tsv_wide(str(file).encode(), num_ds, width, int(lag), n_rows, kmers.ctypes.data,
-                                                counts.ctypes.data, ctypes.byref(got)), "bear_parse_counts_tsv_wide")
+        plain, shard, head = "bear_parse_counts_tsv_wide", "bear_parse_counts_tsv_shard_wide", (str(file).encode(), num_ds, width, int(lag))
+    if header:
+        _lib.call(shard, *head, 1, 0, n_rows, max(n_rows, 1), 0, 1, n_rows, kmers.ctypes.data, counts.ctypes.data, ctypes.byref(got), None)
+    else:
+        _lib.call(plain, *head, n_rows, kmers.ctypes.data, counts.ctypes.data, ctypes.byref(got))
     if got.value != n_rows:
         raise RuntimeError(f"{file}: {got.value} rows parsed, {n_rows} counted (did the file change while it was read?)")
-    return CountDataset(kmers, counts, alphabet, batch_size, dtype)
+    return kmers, counts
 
 
 def _load_shard(file, alphabet, batch_size, num_ds, header, dtype, binary_cache, shard, row_base, total_rows):
@@ -459,15 +439,13 @@ def _load_shard(file, alphabet, batch_size, num_ds, header, dtype, binary_cache,
     binary cache when there is one (one ranged read per batch piece), else by the sharded text reader (every rank walks the
     file, decodes 1 / world of the lines)."""
     from . import dist
-    L = _lib.lib()
     rank, world = int(shard[0]), int(shard[1])
     meta = _cache_meta(cache_path_for(file, binary_cache), file, num_ds) if binary_cache else None
     file_rows = meta[0] if meta else count_rows(file, header)
     if total_rows is None:
         total_rows = row_base + file_rows
     n_local = ctypes.c_uint64()
-    _lib.check(L.bear_shard_rows_count(row_base, file_rows, int(total_rows), batch_size, rank, world, ctypes.byref(n_local)),
-               "bear_shard_rows_count")
+    _lib.call("bear_shard_rows_count", row_base, file_rows, int(total_rows), batch_size, rank, world, ctypes.byref(n_local))
     lag = meta[1] if meta else _sniff_lag(file, header, b"\t")
     kmers = np.zeros((n_local.value, lag), dtype=np.uint8)
     counts = np.zeros((num_ds, n_local.value, 5), dtype=np.uint32)
@@ -481,16 +459,15 @@ def _load_shard(file, alphabet, batch_size, num_ds, header, dtype, binary_cache,
                 continue
             n = g1 - g0
             tmp = np.zeros((num_ds, n, 5), dtype=np.uint32)
-            _lib.check(L.bear_cache_read(path, g0 - row_base, n, kmers[off:off + n].ctypes.data, tmp.ctypes.data), "bear_cache_read")
+            _lib.call("bear_cache_read", path, g0 - row_base, n, kmers[off:off + n].ctypes.data, tmp.ctypes.data)
             counts[:, off:off + n] = tmp
             off += n
         if off != n_local.value:
             raise RuntimeError(f"{file}: the binary cache returned {off} rows for this rank, expected {n_local.value}")
     else:
         got, seen = ctypes.c_uint64(), ctypes.c_uint64()
-        _lib.check(L.bear_parse_counts_tsv_shard(str(file).encode(), num_ds, int(lag), 1 if header else 0, row_base, int(total_rows),
-                                                 batch_size, rank, world, n_local.value, kmers.ctypes.data, counts.ctypes.data,
-                                                 ctypes.byref(got), ctypes.byref(seen)), "bear_parse_counts_tsv_shard")
+        _lib.call("bear_parse_counts_tsv_shard", str(file).encode(), num_ds, int(lag), 1 if header else 0, row_base, int(total_rows),
+                  batch_size, rank, world, n_local.value, kmers.ctypes.data, counts.ctypes.data, ctypes.byref(got), ctypes.byref(seen))
         if got.value != n_local.value or seen.value != file_rows:
             raise RuntimeError(f"{file}: the sharded reader kept {got.value} of {seen.value} rows, expected {n_local.value} of {file_rows} "
                                "(did the file change while it was read?)")
@@ -523,9 +500,8 @@ def sparse_dataloader(file, alphabet, batch_size, num_ds, cache=False, header=Tr
     km = np.empty((n_rows, lag), dtype=np.uint8)
     counts = np.empty((num_ds, n_rows, A1), dtype=np.uint32)
     got = ctypes.c_uint64()
-    st = _lib.lib().bear_parse_sparse_counts(os.fsencode(file), int(num_ds), A1, lag, 1 if header else 0, n_rows,
-                                             km.ctypes.data, counts.ctypes.data, ctypes.byref(got))
-    _lib.check(st, "bear_parse_sparse_counts")
+    _lib.call("bear_parse_sparse_counts", os.fsencode(file), int(num_ds), A1, lag, 1 if header else 0, n_rows, km.ctypes.data,
+              counts.ctypes.data, ctypes.byref(got))
     if got.value != n_rows:
         raise ValueError(f"{file}: {got.value} rows parsed, {n_rows} expected")
     return CountDataset(km, np.ascontiguousarray(counts), alphabet, batch_size, dtype)
@@ -577,9 +553,8 @@ def write_counts_tsv(path, kmers, counts):
         raise ValueError("write_counts_tsv: counts must fit uint32 (KMC's counter range, summarize.py:66-67)")
     planar = np.ascontiguousarray(counts, dtype=np.uint32)
     # the native writer of the summarize stage (csrc/bear_parse.cpp): formats in C++ instead of one Python call per number
+    head = (os.fsencode(path), km.ctypes.data, planar.ctypes.data, n, km.shape[1], planar.shape[0])
     if planar.shape[2] == 5:
-        st = _lib.lib().bear_write_counts_tsv(os.fsencode(path), km.ctypes.data, planar.ctypes.data, n, km.shape[1], planar.shape[0], 0, 1, 0)
+        _lib.call("bear_write_counts_tsv", *head, 0, 1, 0)
     else:
-        st = _lib.lib().bear_write_counts_tsv_wide(os.fsencode(path), km.ctypes.data, planar.ctypes.data, n, km.shape[1], planar.shape[0],
-                                                   planar.shape[2], 0, 1, 0)
-    _lib.check(st, "bear_write_counts_tsv")
+        _lib.call("bear_write_counts_tsv_wide", *head, planar.shape[2], 0, 1, 0)

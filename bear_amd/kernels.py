@@ -11,24 +11,34 @@ from . import _lib
 EPSILON = 1e-7  # keras epsilon, bear_model/core.py:8
 
 
-class Workspace:
-    """Owns a bear_ws handle for one device (per-block partial sums)."""
+class _Handle:
+    """Owner of one handle of the library: ``_create`` fills ``_h`` through the out-parameter that the create entry ``name`` takes
+    behind ``args`` (and, when given, ahead of ``after``); the entry ``_destroy`` names releases it with the object."""
+    _destroy = None
 
-    def __init__(self, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("bear_amd requires an MI355X (HIP) device; there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
+    def _create(self, name, *args, after=()):
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().bear_ws_create(self.device.index, ctypes.byref(h)), "bear_ws_create")
+        _lib.call(name, *args, ctypes.byref(h), *after)
         self._h = h
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             try:
-                _lib.lib().bear_ws_destroy(h)
+                getattr(_lib.lib(), self._destroy)(h)
             except Exception:
                 pass
+
+
+class Workspace(_Handle):
+    """Owns a bear_ws handle for one device (per-block partial sums)."""
+    _destroy = "bear_ws_destroy"
+
+    def __init__(self, device=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("bear_amd requires an MI355X (HIP) device; there is no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
+        self._create("bear_ws_create", self.device.index)
 
     @property
     def handle(self):
@@ -63,26 +73,30 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _check_rows(t, dtype, name):
-    if not (t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 5 and t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous CUDA tensor of shape [N, 5] and dtype {dtype}")
-    if t.data_ptr() % 16:
-        # the C ABI wants 16-byte aligned rows; a slice of a [N,5] tensor may start on any row
-        t = t.clone()
-    return t
+def _launch(device, name, *args):
+    """The entry point ``name`` with ``device`` current, on the current torch stream (every launching entry's last argument)."""
+    with torch.cuda.device(device):
+        _lib.call(name, *args, _stream())
 
 
 WIDE_WIDTHS = (5, 21)   # row widths of the *_wide entry points: the protein alphabet (20 letters + stop), and 5 for cross-checks
 
 
-def _check_rows_wide(t, dtype, name, width=None):
-    """``_check_rows`` for rows of any supported width (the width of ``t``, or ``width``)."""
-    w = t.shape[-1] if (t.dim() == 2 and width is None) else width
-    if not (t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == w and t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous CUDA tensor of shape [N, W] and dtype {dtype}")
-    if w not in WIDE_WIDTHS:
-        raise ValueError(f"{name}: rows of width {w}; the wide kernels take {WIDE_WIDTHS}")
+def _check_rows(t, dtype, name, width=5, n=None, clone=True):
+    """``t`` as the C ABI takes rows: a contiguous CUDA tensor [N, width] (``n``: [n, width]) of ``dtype``, 16-byte aligned.
+    ``width`` None: the width ``t`` has, for the *_wide entries; every width is one of ``WIDE_WIDTHS``.  A misaligned ``t`` (a slice
+    of such a tensor may start on any row) comes back as a copy; ``clone=False`` refuses it instead -- where the kernel must see
+    the caller's own buffer (a plan is tied to it, or the kernel writes it)."""
+    if width is None and t.dim() == 2:
+        width = t.shape[1]
+    if not (t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == width and t.is_contiguous()
+            and (n is None or t.shape[0] == n)):
+        raise ValueError(f"{name} must be a contiguous CUDA tensor of shape [{'N' if n is None else n}, {width or 'W'}] and dtype {dtype}")
+    if width not in WIDE_WIDTHS:
+        raise ValueError(f"{name}: rows of width {width}; the kernels take {WIDE_WIDTHS}")
     if t.data_ptr() % 16:
+        if not clone:
+            raise ValueError(f"{name} must be 16-byte aligned")
         t = t.clone()
     return t
 
@@ -104,10 +118,8 @@ def dm_prior(counts, prior, h_signed, eps=EPSILON, train_ar=False, want_grad=Fal
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=counts.device)
     grad = torch.empty_like(prior) if want_grad else None
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_prior_f64(ws.handle, _ptr(counts), _ptr(prior), counts.shape[0], float(h_signed), float(eps),
-                                          int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_prior_f64")
+    _launch(counts.device, "bear_dm_prior_f64", ws.handle, _ptr(counts), _ptr(prior), counts.shape[0], float(h_signed), float(eps),
+            int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
 
@@ -115,9 +127,9 @@ def dm_prior_wide(counts, prior, h_signed_dev, eps=EPSILON, train_ar=False, want
     """``bear_dm_prior_wide_f64``: ``dm_prior`` for rows of width W = ``counts.shape[-1]`` (21: the protein alphabet), with h_signed
     read from the device tensor ``h_signed_dev`` [1] (a step is enqueued without a host read-back and can be captured).
     Returns (out[2] device tensor = sum LL, d/dh_signed; grad_prior [N, W] or None)."""
-    counts = _check_rows_wide(counts, torch.int32, "counts")
+    counts = _check_rows(counts, torch.int32, "counts", None)
     width = counts.shape[1]
-    prior = _check_rows_wide(prior, torch.float64, "prior", width)
+    prior = _check_rows(prior, torch.float64, "prior", width)
     if counts.shape[0] != prior.shape[0]:
         raise ValueError("counts and prior must have the same number of rows")
     if h_signed_dev is not None:
@@ -128,10 +140,8 @@ def dm_prior_wide(counts, prior, h_signed_dev, eps=EPSILON, train_ar=False, want
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=counts.device)
     grad = torch.empty_like(prior) if want_grad else None
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_prior_wide_f64(ws.handle, _ptr(counts), _ptr(prior), counts.shape[0], width, _ptr(h_signed_dev),
-                                               float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_prior_wide_f64")
+    _launch(counts.device, "bear_dm_prior_wide_f64", ws.handle, _ptr(counts), _ptr(prior), counts.shape[0], width, _ptr(h_signed_dev),
+            float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
 
@@ -144,8 +154,8 @@ REFMIX_WIDE_BLOCKS_PER_CU = 3
 
 
 def _check_ref_wide(train, ref):
-    train = _check_rows_wide(train, torch.int32, "train")
-    ref = _check_rows_wide(ref, torch.int32, "ref", train.shape[1])
+    train = _check_rows(train, torch.int32, "train", None)
+    ref = _check_rows(ref, torch.int32, "ref", train.shape[1])
     if train.shape[0] != ref.shape[0]:
         raise ValueError("train and ref must have the same number of rows")
     return train, ref
@@ -160,10 +170,8 @@ def dm_ref_wide(train, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, train_
     if out is None:
         out = torch.empty(4, dtype=torch.float64, device=train.device)
     _f64_vec(out, 4, "out")
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_dm_ref_wide_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], float(h_signed),
-                                             float(tau_signed), float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out), _stream())
-    _lib.check(st, "bear_dm_ref_wide_f64")
+    _launch(train.device, "bear_dm_ref_wide_f64", ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], float(h_signed),
+            float(tau_signed), float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out))
     return out
 
 
@@ -174,10 +182,8 @@ def ref_train_reduce_wide(train, ref, theta, packed, eps=EPSILON, train_ar=False
     _f64_vec(theta, 3, "theta")
     _f64_vec(packed, 4, "packed")
     ws = ws or default_workspace(train.device)
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_ref_train_reduce_wide_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], _ptr(theta),
-                                                       float(eps), int(bool(train_ar)), _ptr(packed), _stream())
-    _lib.check(st, "bear_ref_train_reduce_wide_f64")
+    _launch(train.device, "bear_ref_train_reduce_wide_f64", ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], _ptr(theta),
+            float(eps), int(bool(train_ar)), _ptr(packed))
 
 
 def ref_train_step_wide(train, ref, theta, adam_m, adam_v, adam_t, learning_rate, scale, out, loss_buf=None, eps=EPSILON, train_ar=False,
@@ -190,12 +196,9 @@ def ref_train_step_wide(train, ref, theta, adam_m, adam_v, adam_t, learning_rate
     if loss_buf is not None:
         _f64_vec(loss_buf, loss_buf.numel(), "loss_buf")
     ws = ws or default_workspace(train.device)
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_ref_train_step_wide_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], _ptr(theta),
-                                                     _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)),
-                                                     float(learning_rate), float(scale), _ptr(out), _ptr(loss_buf),
-                                                     0 if loss_buf is None else loss_buf.numel(), _stream())
-    _lib.check(st, "bear_ref_train_step_wide_f64")
+    _launch(train.device, "bear_ref_train_step_wide_f64", ws.handle, _ptr(train), _ptr(ref), train.shape[0], train.shape[1], _ptr(theta),
+            _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)), float(learning_rate), float(scale), _ptr(out),
+            *_loss(loss_buf))
 
 
 def dm_refmix_wide_dev(counts, net_rows, ref, h_signed_dev, tau_signed_dev, net_weight_signed_dev, eps=EPSILON, out=None, train_ar=False,
@@ -205,7 +208,7 @@ def dm_refmix_wide_dev(counts, net_rows, ref, h_signed_dev, tau_signed_dev, net_
     ``counts``), ``net_rows`` [n, W] the net function's rows (any non-negative rows: not assumed normalised).
     Returns (out [4] = sum LL, d/dh_signed, d/dtau_signed, d/dnet_weight_signed; d sum LL / d net_rows [n, W])."""
     counts, ref = _check_ref_wide(counts, ref)
-    net_rows = _check_rows_wide(net_rows, torch.float64, "net_rows", counts.shape[1])
+    net_rows = _check_rows(net_rows, torch.float64, "net_rows", counts.shape[1])
     if net_rows.shape[0] != counts.shape[0]:
         raise ValueError("counts and net_rows must have the same number of rows")
     _check_scalar_param(h_signed_dev=h_signed_dev, tau_signed_dev=tau_signed_dev, net_weight_signed_dev=net_weight_signed_dev)
@@ -214,11 +217,9 @@ def dm_refmix_wide_dev(counts, net_rows, ref, h_signed_dev, tau_signed_dev, net_
         out = torch.empty(4, dtype=torch.float64, device=counts.device)
     _f64_vec(out, 4, "out")
     grad = torch.empty_like(net_rows)
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_refmix_wide_grad_f64(ws.handle, _ptr(counts), _ptr(net_rows), _ptr(ref), counts.shape[0], counts.shape[1],
-                                                     _ptr(h_signed_dev), _ptr(tau_signed_dev), _ptr(net_weight_signed_dev), float(eps),
-                                                     int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_refmix_wide_grad_f64")
+    _launch(counts.device, "bear_dm_refmix_wide_grad_f64", ws.handle, _ptr(counts), _ptr(net_rows), _ptr(ref), counts.shape[0],
+            counts.shape[1], _ptr(h_signed_dev), _ptr(tau_signed_dev), _ptr(net_weight_signed_dev), float(eps), int(bool(train_ar)),
+            _ptr(out), _ptr(grad))
     return out, grad
 
 
@@ -232,16 +233,15 @@ def dm_ref(train, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, train_ar=Fa
     ws = ws or default_workspace(train.device)
     if out is None:
         out = torch.empty(4, dtype=torch.float64, device=train.device)
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_dm_ref_f64(ws.handle, _ptr(train), _ptr(ref), train.shape[0], float(h_signed), float(tau_signed),
-                                        float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out), _stream())
-    _lib.check(st, "bear_dm_ref_f64")
+    _launch(train.device, "bear_dm_ref_f64", ws.handle, _ptr(train), _ptr(ref), train.shape[0], float(h_signed), float(tau_signed),
+            float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out))
     return out
 
 
-class Plan:
+class Plan(_Handle):
     """Count-dependent part of the hot path for a table that stays resident across optimizer steps
     (work items sorted by count; include/bear_hip.h "Planned variants").  Keeps the count tensor alive."""
+    _destroy = "bear_plan_destroy"
 
     def __init__(self, counts, ncol, ws=None, ref=None, rows_if_dense=False):
         """ref (ncol = 4 only): the reference column the planned mode-R entries will be called with -- the plan then folds the
@@ -255,31 +255,39 @@ class Plan:
         self.ref = None
         self.rowwise = False
         self.ws = ws or default_workspace(counts.device)
-        h = ctypes.c_void_p()
         with torch.cuda.device(counts.device):
             torch.cuda.current_stream().synchronize()  # plan construction runs on the default stream
             if ref is not None:
-                ref = _check_rows(ref, torch.int32, "ref")
-                if self.ncol != 4 or ref.shape[0] != counts.shape[0] or ref.data_ptr() % 16:
-                    raise ValueError("a reference-aware plan needs ncol = 4 and a 16-byte aligned ref slab with one row per context")
-                self.ref = ref
-                st = _lib.lib().bear_plan_create_ref(self.ws.handle, _ptr(counts), _ptr(ref), counts.shape[0], ctypes.byref(h))
-                _lib.check(st, "bear_plan_create_ref")
+                if self.ncol != 4:
+                    raise ValueError("a reference-aware plan needs ncol = 4")
+                self.ref = ref = _check_rows(ref, torch.int32, "ref", n=counts.shape[0], clone=False)
+                self._create("bear_plan_create_ref", self.ws.handle, _ptr(counts), _ptr(ref), counts.shape[0])
             elif rows_if_dense:
                 if self.ncol != 5:
                     raise ValueError("rows_if_dense: five-column plans")
                 rw = ctypes.c_int(0)
-                st = _lib.lib().bear_plan_create_auto(self.ws.handle, _ptr(counts), counts.shape[0], ctypes.byref(rw), ctypes.byref(h))
-                _lib.check(st, "bear_plan_create_auto")
+                self._create("bear_plan_create_auto", self.ws.handle, _ptr(counts), counts.shape[0], ctypes.byref(rw))
                 self.rowwise = bool(rw.value)
             else:
-                st = _lib.lib().bear_plan_create(self.ws.handle, _ptr(counts), counts.shape[0], self.ncol, ctypes.byref(h))
-                _lib.check(st, "bear_plan_create")
-        self._h = h
+                self._create("bear_plan_create", self.ws.handle, _ptr(counts), counts.shape[0], self.ncol)
 
     @property
     def nbytes(self):
         return int(_lib.lib().bear_plan_bytes(self._h))
+
+    def _optional(self, name, *args):
+        """The set-up entry ``name`` of this plan, an optional speed-up that allocates with hipMalloc: out of memory, it is tried
+        once more with the torch allocator's cached slabs given back (they are out of hipMalloc's reach).  Given back only then --
+        emptying the cache on every call made a streamed epoch pay hipFree / hipMalloc (device-wide synchronisations that serialise
+        with the side stream's prefetch) on every batch load.  False when it still ran out: the caller goes without."""
+        with torch.cuda.device(self.counts.device):
+            st = getattr(_lib.lib(), name)(self._h, *args, _stream())
+            if st == _lib.ERR_NOMEM:
+                torch.cuda.empty_cache()
+                st = getattr(_lib.lib(), name)(self._h, *args, _stream())
+        if st != _lib.ERR_NOMEM:
+            _lib.check(st, name)
+        return st == 0
 
     def pair_contexts(self, kmer_index, lag):
         """``bear_plan_pair_contexts``: ties this (five-column) plan to the index words ``kmer_index`` (``linear_index``) of its rows
@@ -289,19 +297,11 @@ class Plan:
         if kmer_index.shape[0] != self.counts.shape[0] or kmer_index.data_ptr() % 16:
             raise ValueError("kmer_index: one 16-byte aligned index word per row of the plan's count slab")
         ok = ctypes.c_int(0)
-        with torch.cuda.device(self.counts.device):
-            st = _lib.lib().bear_plan_pair_contexts(self._h, _ptr(kmer_index), int(lag), ctypes.byref(ok), _stream())
-            if st == _lib.ERR_NOMEM:
-                # the lists come from hipMalloc: slabs the torch allocator has cached are out of its reach.  Given back only now --
-                # emptying the cache on every call made a streamed epoch pay hipFree / hipMalloc (device-wide synchronisations that
-                # serialise with the side stream's prefetch) on every batch load
-                torch.cuda.empty_cache()
-                st = _lib.lib().bear_plan_pair_contexts(self._h, _ptr(kmer_index), int(lag), ctypes.byref(ok), _stream())
-        if st == _lib.ERR_NOMEM:         # an optional speed-up: a table close to the card's capacity runs the plain step
+        if not self._optional("bear_plan_pair_contexts", _ptr(kmer_index), int(lag), ctypes.byref(ok)):
+            # a table close to the card's capacity runs the plain step
             warnings.warn("bear_plan_pair_contexts: out of device memory, the linear step keeps its plain lists")
             self.paired_codes = None
             return False
-        _lib.check(st, "bear_plan_pair_contexts")
         self.paired_codes = kmer_index if ok.value else None
         return bool(ok.value)
 
@@ -309,14 +309,14 @@ class Plan:
         """(total, bound) -- each [sum of all counts, cells that hold a count, largest count]: of the plan's table, and the values in
         force for the deterministic mode's fixed-point scale (``bear_plan_count_total``)."""
         a, b = (ctypes.c_double * 3)(), (ctypes.c_double * 3)()
-        _lib.check(_lib.lib().bear_plan_count_total(self._h, a, b), "bear_plan_count_total")
+        _lib.call("bear_plan_count_total", self._h, a, b)
         return list(a), list(b)
 
     def set_count_bound(self, bound):
         """``bear_plan_set_count_bound``: [sum of counts, non-zero cells, largest count] of EVERYTHING that is added into one gradient
         together with this plan's rows (BEAR_AMD_DETERMINISTIC: the scale of the fixed-point gradient tables; ranks that share a batch
         must agree on it: sums of the first two, maximum of the third)."""
-        _lib.check(_lib.lib().bear_plan_set_count_bound(self._h, (ctypes.c_double * 3)(*[float(x) for x in bound])), "bear_plan_set_count_bound")
+        _lib.call("bear_plan_set_count_bound", self._h, (ctypes.c_double * 3)(*[float(x) for x in bound]))
 
     def pair_info(self):
         """(tiles that take the paired form of the linear step, tiles that keep their plain list) -- ``bear_plan_pair_info``."""
@@ -332,16 +332,10 @@ class Plan:
         if kmer_code.shape[0] != self.counts.shape[0] or kmer_code.data_ptr() % 16:
             raise ValueError("kmer_code: one 16-byte aligned packed context per row of the plan's count slab")
         n = ctypes.c_int(0)
-        with torch.cuda.device(self.counts.device):
-            st = _lib.lib().bear_plan_attach_cnn_levels(self._h, _ptr(kmer_code), int(lag), int(filter_width), ctypes.byref(n), _stream())
-            if st == _lib.ERR_NOMEM:
-                torch.cuda.empty_cache()     # (as in pair_contexts: only when the first attempt ran out)
-                st = _lib.lib().bear_plan_attach_cnn_levels(self._h, _ptr(kmer_code), int(lag), int(filter_width), ctypes.byref(n), _stream())
-        if st == _lib.ERR_NOMEM:
+        if not self._optional("bear_plan_attach_cnn_levels", _ptr(kmer_code), int(lag), int(filter_width), ctypes.byref(n)):
             warnings.warn("bear_plan_attach_cnn_levels: out of device memory, the convolutional step runs without prefix levels")
             self.cnn_codes = None
             return 0
-        _lib.check(st, "bear_plan_attach_cnn_levels")
         self.cnn_codes = kmer_code if (n.value or self.cnn_window_rows()) else None     # (kept alive: levels and window tables are tied to it)
         return int(n.value)
 
@@ -369,17 +363,15 @@ class Plan:
         """Diagnostics (``bear_plan_tile_info``): (row0 [T] uint64, rows [T] uint32, items [T] uint32, stream_offset [T] uint64)."""
         n = int(_lib.lib().bear_plan_tile_count(self._h))
         row0, rows, items, off = np.empty(n, np.uint64), np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.uint64)
-        _lib.check(_lib.lib().bear_plan_tile_info(self._h, 0, n, row0.ctypes.data, rows.ctypes.data, items.ctypes.data, off.ctypes.data),
-                   "bear_plan_tile_info")
+        _lib.call("bear_plan_tile_info", self._h, 0, n, row0.ctypes.data, rows.ctypes.data, items.ctypes.data, off.ctypes.data)
         return row0, rows, items, off
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().bear_plan_destroy(h)
-            except Exception:
-                pass
+
+def _check_planned(plan, ncol, rows, dtype, name):
+    """``rows``: the caller's aligned buffer with one row per context of a plan of ``ncol`` columns."""
+    if plan.ncol != ncol:
+        raise ValueError(f"a plan with ncol={ncol} is needed, this one has ncol={plan.ncol}")
+    _check_rows(rows, dtype, name, n=plan.counts.shape[0], clone=False)
 
 
 def dm_prior_planned(plan, prior, h_signed, eps=EPSILON, out=None, normalized=False, want_grad=False, train_ar=False):
@@ -387,39 +379,27 @@ def dm_prior_planned(plan, prior, h_signed, eps=EPSILON, out=None, normalized=Fa
     d sum LL / d prior, returned as (out, grad).  normalized=True asserts that every prior row sums to one
     (any softmax output)."""
     counts = plan.counts
-    _check_rows(prior, torch.float64, "prior")
-    if prior.data_ptr() % 16 or prior.shape[0] != counts.shape[0] or plan.ncol != 5:
-        raise ValueError("prior must be 16-byte aligned with one row per planned context (plan ncol=5)")
+    _check_planned(plan, 5, prior, torch.float64, "prior")
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=counts.device)
     if want_grad:
         grad = torch.empty_like(prior)
-        with torch.cuda.device(counts.device):
-            st = _lib.lib().bear_dm_prior_plan_grad_f64(plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
-                                                        float(h_signed), float(eps), int(bool(train_ar)), int(bool(normalized)),
-                                                        _ptr(out), _ptr(grad), _stream())
-        _lib.check(st, "bear_dm_prior_plan_grad_f64")
+        _launch(counts.device, "bear_dm_prior_plan_grad_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
+                float(h_signed), float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out), _ptr(grad))
         return out, grad
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_prior_plan_f64(plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
-                                               float(h_signed), float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out),
-                                               _stream())
-    _lib.check(st, "bear_dm_prior_plan_f64")
+    _launch(counts.device, "bear_dm_prior_plan_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0], float(h_signed),
+            float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out))
     return out
 
 
 def dm_ref_planned(plan, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, out=None, train_ar=False):
     """Planned twin of dm_ref (BEAR mode): [sum LL, d/dh_signed, d/dtau_signed, d/dnet_weight_signed]."""
     train = plan.counts
-    _check_rows(ref, torch.int32, "ref")
-    if ref.data_ptr() % 16 or ref.shape[0] != train.shape[0] or plan.ncol != 4:
-        raise ValueError("ref must be 16-byte aligned with one row per planned context (plan ncol=4)")
+    _check_planned(plan, 4, ref, torch.int32, "ref")
     if out is None:
         out = torch.empty(4, dtype=torch.float64, device=train.device)
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_dm_ref_plan_f64(plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], float(h_signed),
-                                             float(tau_signed), float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out), _stream())
-    _lib.check(st, "bear_dm_ref_plan_f64")
+    _launch(train.device, "bear_dm_ref_plan_f64", plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], float(h_signed),
+            float(tau_signed), float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out))
     return out
 
 
@@ -430,9 +410,7 @@ def dm_items(x, c, path=0, ws=None):
         raise ValueError("x: contiguous CUDA float64 [n]; c: contiguous CUDA int32 [n]")
     ws = ws or default_workspace(x.device)
     D, P = torch.empty_like(x), torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        st = _lib.lib().bear_dm_items_f64(ws.handle, _ptr(x), _ptr(c), x.shape[0], int(path), _ptr(D), _ptr(P), _stream())
-    _lib.check(st, "bear_dm_items_f64")
+    _launch(x.device, "bear_dm_items_f64", ws.handle, _ptr(x), _ptr(c), x.shape[0], int(path), _ptr(D), _ptr(P))
     return D, P
 
 
@@ -444,21 +422,16 @@ def pack_kmers(codes):
     if not (codes.is_cuda and codes.dtype == torch.int8 and codes.dim() == 2 and codes.is_contiguous()):
         raise ValueError("codes must be a contiguous CUDA int8 tensor [n, lag]")
     out = torch.empty(codes.shape[0], dtype=torch.int64, device=codes.device)
-    with torch.cuda.device(codes.device):
-        st = _lib.lib().bear_pack_kmers_u64(_ptr(codes), codes.shape[0], codes.shape[1], _ptr(out), _stream())
-    _lib.check(st, "bear_pack_kmers_u64")
+    _launch(codes.device, "bear_pack_kmers_u64", _ptr(codes), codes.shape[0], codes.shape[1], _ptr(out))
     return out
 
 
 def linear_index(kmer_code, lag):
     """Packed contexts (``pack_kmers``) -> the table-row words the fused linear head reads (``bear_linear_index_u64``); once per
     batch, the contexts do not change between steps."""
-    if not (kmer_code.is_cuda and kmer_code.dtype == torch.int64 and kmer_code.dim() == 1 and kmer_code.is_contiguous()):
-        raise ValueError("kmer_code must be a contiguous CUDA int64 tensor [n_rows] (pack_kmers)")
+    _check_codes(kmer_code)
     out = torch.empty_like(kmer_code)
-    with torch.cuda.device(kmer_code.device):
-        st = _lib.lib().bear_linear_index_u64(_ptr(kmer_code), kmer_code.shape[0], int(lag), _ptr(out), _stream())
-    _lib.check(st, "bear_linear_index_u64")
+    _launch(kmer_code.device, "bear_linear_index_u64", _ptr(kmer_code), kmer_code.shape[0], int(lag), _ptr(out))
     return out
 
 
@@ -478,68 +451,54 @@ def dm_linear(plan, kmer_index, mat, h_signed, eps=EPSILON, train_ar=False, out=
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=mat.device)
     grad = torch.empty_like(mat)
-    with torch.cuda.device(mat.device):
-        st = _lib.lib().bear_dm_linear_f64(plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), _ptr(mat), mat.shape[0], n,
-                                           float(h_signed), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_linear_f64")
+    _launch(mat.device, "bear_dm_linear_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), _ptr(mat), mat.shape[0], n,
+            float(h_signed), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
 
 def _host_f64(values):
+    """(array, its address) of host float64 values for a call; None or no values: an empty array and NULL."""
+    if values is None or not np.size(values):
+        return np.zeros(0), ctypes.c_void_p(0)
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float64)))
     return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _evaluate(wide, test, prior, h, van_reg, train, eps, with_ar, noise_seed, row_base, ws):
+    test = _check_rows(test, torch.int32, "test", None if wide else 5)
+    n, width = test.shape
+    if train is not None:
+        train = _check_rows(train, torch.int32, "train", width)
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", width)
+    for t in (train, prior):
+        if t is not None and t.shape[0] != n:
+            raise ValueError("test, train and prior must have the same number of rows")
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(van_reg)
+    ws = ws or default_workspace(test.device)
+    out = torch.empty(2 * (hs.size + vs.size) + 3, dtype=torch.float64, device=test.device)
+    _launch(test.device, "bear_eval_wide_f64" if wide else "bear_eval_f64", ws.handle, _ptr(test), _ptr(train), _ptr(prior), n,
+            *((width,) if wide else ()), hp, hs.size, int(bool(with_ar)), vp, vs.size, float(eps), int(noise_seed), int(row_base), _ptr(out))
+    return out
 
 
 def evaluate(test, prior, h, van_reg, train=None, eps=EPSILON, with_ar=True, noise_seed=0, row_base=0, ws=None):
     """One launch of ``bear_eval_f64``: the 7 partial sums of ``_evaluation_step`` (bear_net.py:323-371).
     Returns a device float64 vector {ll_ear[H], ll_arm, ll_van[V], cor_ear[H], cor_arm, cor_van[V], total_len}."""
-    test = _check_rows(test, torch.int32, "test")
-    n = test.shape[0]
-    if train is not None:
-        train = _check_rows(train, torch.int32, "train")
-    if prior is not None:
-        prior = _check_rows(prior, torch.float64, "prior")
-    for t in (train, prior):
-        if t is not None and t.shape[0] != n:
-            raise ValueError("test, train and prior must have the same number of rows")
-    hs, hp = _host_f64(h) if h is not None else (np.zeros(0), ctypes.c_void_p(0))
-    vs, vp = _host_f64(van_reg) if van_reg is not None else (np.zeros(0), ctypes.c_void_p(0))
-    ws = ws or default_workspace(test.device)
-    out = torch.empty(2 * (hs.size + vs.size) + 3, dtype=torch.float64, device=test.device)
-    with torch.cuda.device(test.device):
-        st = _lib.lib().bear_eval_f64(ws.handle, _ptr(test), _ptr(train), _ptr(prior), n, hp, hs.size, int(bool(with_ar)), vp,
-                                      vs.size, float(eps), int(noise_seed), int(row_base), _ptr(out), _stream())
-    _lib.check(st, "bear_eval_f64")
-    return out
+    return _evaluate(False, test, prior, h, van_reg, train, eps, with_ar, noise_seed, row_base, ws)
 
 
 def evaluate_wide(test, prior, h, van_reg, train=None, eps=EPSILON, with_ar=True, noise_seed=0, row_base=0, ws=None):
     """``bear_eval_wide_f64``: ``evaluate`` for rows of width W = ``test.shape[-1]`` (21: the protein alphabet); the same output
     vector, the tie-breaking noise keyed by ``row * W + letter``."""
-    test = _check_rows_wide(test, torch.int32, "test")
-    n, width = test.shape
-    if train is not None:
-        train = _check_rows_wide(train, torch.int32, "train", width)
-    if prior is not None:
-        prior = _check_rows_wide(prior, torch.float64, "prior", width)
-    for t in (train, prior):
-        if t is not None and t.shape[0] != n:
-            raise ValueError("test, train and prior must have the same number of rows")
-    hs, hp = _host_f64(h) if h is not None else (np.zeros(0), ctypes.c_void_p(0))
-    vs, vp = _host_f64(van_reg) if van_reg is not None else (np.zeros(0), ctypes.c_void_p(0))
-    ws = ws or default_workspace(test.device)
-    out = torch.empty(2 * (hs.size + vs.size) + 3, dtype=torch.float64, device=test.device)
-    with torch.cuda.device(test.device):
-        st = _lib.lib().bear_eval_wide_f64(ws.handle, _ptr(test), _ptr(train), _ptr(prior), n, width, hp, hs.size, int(bool(with_ar)),
-                                           vp, vs.size, float(eps), int(noise_seed), int(row_base), _ptr(out), _stream())
-    _lib.check(st, "bear_eval_wide_f64")
-    return out
+    return _evaluate(True, test, prior, h, van_reg, train, eps, with_ar, noise_seed, row_base, ws)
 
 
-class EvalPlan:
+class EvalPlan(_Handle):
     """Sorted plan of a resident TEST column (``bear_eval_plan_create``): per tile the cells and row totals with a non-zero
     count, sorted by count, and the rows whose largest counts in the conditioning column ``train`` tie.  Keeps the count
     tensors alive; built asynchronously on the current stream."""
+    _destroy = "bear_eval_plan_destroy"
 
     def __init__(self, test, train=None, ws=None):
         test = _check_rows(test, torch.int32, "test")
@@ -549,23 +508,12 @@ class EvalPlan:
                 raise ValueError("test and train must have the same number of rows")
         self.test, self.train = test, train
         self.ws = ws or default_workspace(test.device)
-        h = ctypes.c_void_p()
         with torch.cuda.device(test.device):
-            st = _lib.lib().bear_eval_plan_create(self.ws.handle, _ptr(test), _ptr(train), test.shape[0], ctypes.byref(h), _stream())
-        _lib.check(st, "bear_eval_plan_create")
-        self._h = h
+            self._create("bear_eval_plan_create", self.ws.handle, _ptr(test), _ptr(train), test.shape[0], after=(_stream(),))
 
     @property
     def nbytes(self):
         return int(_lib.lib().bear_eval_plan_bytes(self._h))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().bear_eval_plan_destroy(h)
-            except Exception:
-                pass
 
 
 def evaluate_planned(plan, prior, h, van_reg, eps=EPSILON, with_ar=True, noise_seed=0, row_base=0, row_ids=None):
@@ -578,19 +526,14 @@ def evaluate_planned(plan, prior, h, van_reg, eps=EPSILON, with_ar=True, noise_s
                                     and row_ids.shape == (n,) and row_ids.data_ptr() % 16 == 0):
         raise ValueError("row_ids must be a contiguous, 16-byte aligned CUDA int32 tensor [n_rows]")
     if prior is not None:
-        _check_rows(prior, torch.float64, "prior")
-        if prior.shape[0] != n or prior.data_ptr() % 16:
-            raise ValueError("prior must be 16-byte aligned with one row per planned context")
-    hs, hp = _host_f64(h) if h is not None else (np.zeros(0), ctypes.c_void_p(0))
-    vs, vp = _host_f64(van_reg) if van_reg is not None else (np.zeros(0), ctypes.c_void_p(0))
+        _check_rows(prior, torch.float64, "prior", n=n, clone=False)
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(van_reg)
     if vs.size and not (1750.0 * float(eps) < 0.5 and (vs >= 0.0).all() and (vs <= 2.0 ** 30).all()):
         raise ValueError("a planned evaluation decides the vanilla models' arg-max on the integer counts: it needs 1750 eps < 0.5 "
                          "and 0 <= van_reg <= 2^30 (kernels.evaluate takes any values)")
     out = torch.empty(2 * (hs.size + vs.size) + 3, dtype=torch.float64, device=test.device)
-    with torch.cuda.device(test.device):
-        st = _lib.lib().bear_eval_plan_f64(plan.ws.handle, plan._h, _ptr(test), _ptr(train), _ptr(prior), n, hp, hs.size, int(bool(with_ar)),
-                                           vp, vs.size, float(eps), int(noise_seed), int(row_base), _ptr(row_ids), _ptr(out), _stream())
-    _lib.check(st, "bear_eval_plan_f64")
+    _launch(test.device, "bear_eval_plan_f64", plan.ws.handle, plan._h, _ptr(test), _ptr(train), _ptr(prior), n, hp, hs.size,
+            int(bool(with_ar)), vp, vs.size, float(eps), int(noise_seed), int(row_base), _ptr(row_ids), _ptr(out))
     return out
 
 
@@ -600,27 +543,21 @@ def bmm(counts, alpha, ws=None):
     al, ap = _host_f64(alpha)
     ws = ws or default_workspace(counts.device)
     out = torch.empty(al.size, dtype=torch.float64, device=counts.device)
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_bmm_f64(ws.handle, _ptr(counts), counts.shape[0], ap, al.size, _ptr(out), _stream())
-    _lib.check(st, "bear_bmm_f64")
+    _launch(counts.device, "bear_bmm_f64", ws.handle, _ptr(counts), counts.shape[0], ap, al.size, _ptr(out))
     return out
 
 
 def synth_counts(seed, row0, n_rows, device, dense=False, want=("train", "test", "ref")):
     """Rows [row0, row0+n_rows) of the synthetic k=13 table, generated on the device."""
     bufs = {k: torch.empty((n_rows, 5), dtype=torch.int32, device=device) for k in want}
-    with torch.cuda.device(device):
-        st = _lib.lib().bear_synth_counts_u32(int(seed), int(row0), int(n_rows), int(bool(dense)), _ptr(bufs.get("train")),
-                                              _ptr(bufs.get("test")), _ptr(bufs.get("ref")), _stream())
-    _lib.check(st, "bear_synth_counts_u32")
+    _launch(device, "bear_synth_counts_u32", int(seed), int(row0), int(n_rows), int(bool(dense)), _ptr(bufs.get("train")),
+            _ptr(bufs.get("test")), _ptr(bufs.get("ref")))
     return bufs
 
 
 def synth_prior(seed, row0, n_rows, device):
     prior = torch.empty((n_rows, 5), dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        st = _lib.lib().bear_synth_prior_f64(int(seed), int(row0), int(n_rows), _ptr(prior), _stream())
-    _lib.check(st, "bear_synth_prior_f64")
+    _launch(device, "bear_synth_prior_f64", int(seed), int(row0), int(n_rows), _ptr(prior))
     return prior
 
 
@@ -663,9 +600,31 @@ def log_gamma(conc, n_samples, seed):
     if not (conc.is_cuda and conc.dtype == torch.float64 and conc.dim() == 1 and conc.is_contiguous()):
         raise ValueError("conc must be a contiguous CUDA float64 vector")
     out = torch.empty((int(n_samples), conc.shape[0]), dtype=torch.float64, device=conc.device)
-    with torch.cuda.device(conc.device):
-        st = _lib.lib().bear_log_gamma_f64(_ptr(conc), conc.shape[0], int(n_samples), int(seed) & (2 ** 64 - 1), _ptr(out), _stream())
-    _lib.check(st, "bear_log_gamma_f64")
+    _launch(conc.device, "bear_log_gamma_f64", _ptr(conc), conc.shape[0], int(n_samples), int(seed) & (2 ** 64 - 1), _ptr(out))
+    return out
+
+
+def _logdir_sample(wide, counts, prior, h, vans, mc_samples, get_map, with_ar, seed, row_base, n_rows, device, width):
+    n = None
+    if counts is not None:
+        counts = _check_rows(counts, torch.int32, "counts", width)
+        n, device, width = counts.shape[0], counts.device, counts.shape[1]
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", width)
+        if n is not None and prior.shape[0] != n:
+            raise ValueError("counts and prior must have the same number of rows")
+        n, device, width = prior.shape[0], prior.device, prior.shape[1]
+    if n is None:
+        if width not in WIDE_WIDTHS:
+            raise ValueError(f"width {width}: the wide kernels take {WIDE_WIDTHS}")
+        n, device = int(n_rows), torch.device(device or "cuda")
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
+    mc = 1 if get_map else int(mc_samples)
+    M = int(bool(with_ar)) + hs.size + vs.size
+    out = torch.empty((n, width, M, mc), dtype=torch.float64, device=device)
+    _launch(device, "bear_logdir_sample_wide_f64" if wide else "bear_logdir_sample_f64", _ptr(counts), _ptr(prior), n,
+            *((int(width),) if wide else ()), hp, hs.size, int(bool(with_ar)), vp, vs.size, mc, int(bool(get_map)),
+            int(seed) & (2 ** 64 - 1), int(row_base), _ptr(out))
     return out
 
 
@@ -673,25 +632,7 @@ def logdir_sample(counts, prior, h, vans, mc_samples, get_map=False, with_ar=Fal
                   device=None):
     """One launch of ``bear_logdir_sample_f64``: normalised log transition probabilities
     [n_rows, 5, n_models, mc_samples] (get_var_probs.get_pdf, output='numpy').  counts None = all-zero rows."""
-    n = None
-    for t, dt, name in ((counts, torch.int32, "counts"), (prior, torch.float64, "prior")):
-        if t is not None:
-            _check_rows(t, dt, name)
-            if n is not None and t.shape[0] != n:
-                raise ValueError("counts and prior must have the same number of rows")
-            n, device = t.shape[0], t.device
-    if n is None:
-        n, device = int(n_rows), torch.device(device or "cuda")
-    hs, hp = _host_f64(h) if h is not None and np.size(h) else (np.zeros(0), ctypes.c_void_p(0))
-    vs, vp = _host_f64(vans) if vans is not None and np.size(vans) else (np.zeros(0), ctypes.c_void_p(0))
-    mc = 1 if get_map else int(mc_samples)
-    M = int(bool(with_ar)) + hs.size + vs.size
-    out = torch.empty((n, 5, M, mc), dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        st = _lib.lib().bear_logdir_sample_f64(_ptr(counts), _ptr(prior), n, hp, hs.size, int(bool(with_ar)), vp, vs.size, mc,
-                                               int(bool(get_map)), int(seed) & (2 ** 64 - 1), int(row_base), _ptr(out), _stream())
-    _lib.check(st, "bear_logdir_sample_f64")
-    return out
+    return _logdir_sample(False, counts, prior, h, vans, mc_samples, get_map, with_ar, seed, row_base, n_rows, device, 5)
 
 
 def logdir_sample_wide(counts, prior, h, vans, mc_samples, get_map=False, with_ar=False, seed=0, row_base=0, n_rows=None,
@@ -699,29 +640,7 @@ def logdir_sample_wide(counts, prior, h, vans, mc_samples, get_map=False, with_a
     """``bear_logdir_sample_wide_f64``: ``logdir_sample`` for rows of width W in ``WIDE_WIDTHS`` (21: the protein alphabet) ->
     [n_rows, W, n_models, mc_samples]; the draw of a cell is keyed by ``(row_base + row) * W + letter``.  W is the width of the
     rows, or ``width`` when both ``counts`` and ``prior`` are None (unseen k-mers, vanilla models only)."""
-    if counts is not None:
-        counts = _check_rows_wide(counts, torch.int32, "counts", width)
-        n, device, width = counts.shape[0], counts.device, counts.shape[1]
-    if prior is not None:
-        prior = _check_rows_wide(prior, torch.float64, "prior", width)
-        if counts is not None and prior.shape[0] != n:
-            raise ValueError("counts and prior must have the same number of rows")
-        n, device, width = prior.shape[0], prior.device, prior.shape[1]
-    if counts is None and prior is None:
-        if width not in WIDE_WIDTHS:
-            raise ValueError(f"width {width}: the wide kernels take {WIDE_WIDTHS}")
-        n, device = int(n_rows), torch.device(device or "cuda")
-    hs, hp = _host_f64(h) if h is not None and np.size(h) else (np.zeros(0), ctypes.c_void_p(0))
-    vs, vp = _host_f64(vans) if vans is not None and np.size(vans) else (np.zeros(0), ctypes.c_void_p(0))
-    mc = 1 if get_map else int(mc_samples)
-    M = int(bool(with_ar)) + hs.size + vs.size
-    out = torch.empty((n, width, M, mc), dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        st = _lib.lib().bear_logdir_sample_wide_f64(_ptr(counts), _ptr(prior), n, int(width), hp, hs.size, int(bool(with_ar)), vp,
-                                                    vs.size, mc, int(bool(get_map)), int(seed) & (2 ** 64 - 1), int(row_base),
-                                                    _ptr(out), _stream())
-    _lib.check(st, "bear_logdir_sample_wide_f64")
-    return out
+    return _logdir_sample(True, counts, prior, h, vans, mc_samples, get_map, with_ar, seed, row_base, n_rows, device, width)
 
 
 def shuffle_rows(src, seed):
@@ -731,9 +650,7 @@ def shuffle_rows(src, seed):
     dst = torch.empty_like(src)
     n = src.shape[0]
     row_bytes = src.element_size() * (src.numel() // n) if n else 0
-    with torch.cuda.device(src.device):
-        st = _lib.lib().bear_shuffle_rows(_ptr(src), _ptr(dst), n, row_bytes, int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(st, "bear_shuffle_rows")
+    _launch(src.device, "bear_shuffle_rows", _ptr(src), _ptr(dst), n, row_bytes, int(seed) & (2 ** 64 - 1))
     return dst
 
 
@@ -746,16 +663,14 @@ def kmer_order(kmer_code, lag):
     perm = torch.empty(n, dtype=torch.int32, device=kmer_code.device)
     nbytes = ctypes.c_uint64(kmer_order_scratch_bytes(n, lag))
     scratch = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=kmer_code.device)
-    with torch.cuda.device(kmer_code.device):
-        st = _lib.lib().bear_kmer_order_u64(_ptr(kmer_code), n, int(lag), _ptr(perm), _ptr(scratch), ctypes.byref(nbytes), _stream())
-    _lib.check(st, "bear_kmer_order_u64")
+    _launch(kmer_code.device, "bear_kmer_order_u64", _ptr(kmer_code), n, int(lag), _ptr(perm), _ptr(scratch), ctypes.byref(nbytes))
     return perm
 
 
 def kmer_order_scratch_bytes(n_rows, lag):
     """Device scratch ``bear_kmer_order_u64`` asks of its caller for a batch of n_rows contexts."""
     nbytes = ctypes.c_uint64(0)
-    _lib.check(_lib.lib().bear_kmer_order_u64(None, int(n_rows), int(lag), None, None, ctypes.byref(nbytes), None), "bear_kmer_order_u64")
+    _lib.call("bear_kmer_order_u64", None, int(n_rows), int(lag), None, None, ctypes.byref(nbytes), None)
     return int(nbytes.value)
 
 
@@ -767,9 +682,7 @@ def gather_rows(src, perm):
     dst = torch.empty_like(src)
     n = src.shape[0]
     row_bytes = src.element_size() * (src.numel() // n) if n else 1
-    with torch.cuda.device(src.device):
-        st = _lib.lib().bear_gather_rows(_ptr(src), _ptr(perm), _ptr(dst), n, row_bytes, _stream())
-    _lib.check(st, "bear_gather_rows")
+    _launch(src.device, "bear_gather_rows", _ptr(src), _ptr(perm), _ptr(dst), n, row_bytes)
     return dst
 
 
@@ -796,10 +709,15 @@ def cnn_supported(lag, alphabet_size, filter_width, num_filters, kmer_layer1_wid
     return alphabet_size == 4 and 1 <= filter_width <= lag <= CNN_MAX_LAG
 
 
-def cnn_param_count(lag, filter_width):
-    n = _lib.lib().bear_cnn_param_count(int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH)
-    _lib.check(min(n, 0), "bear_cnn_param_count")
+def _count(name, *args):
+    """A size query: the entry ``name`` answers a count, or a negative status."""
+    n = getattr(_lib.lib(), name)(*args)
+    _lib.check(min(n, 0), name)
     return n
+
+
+def cnn_param_count(lag, filter_width):
+    return _count("bear_cnn_param_count", int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH)
 
 
 def _check_codes(kmer_code):
@@ -820,18 +738,14 @@ def cnn_forward(kmer_code, flat_params, lag, filter_width, save=True, ws=None, p
             raise ValueError("plan: built for another number of rows than kmer_code holds")
         prior = torch.empty((n, 5), dtype=torch.float64, device=kmer_code.device)
         t1 = torch.empty((n, CNN_LAYER1_WIDTH), dtype=torch.float64, device=kmer_code.device)
-        with torch.cuda.device(kmer_code.device):
-            st = _lib.lib().bear_cnn_forward_plan_f64(plan.ws.handle, plan._h, _ptr(kmer_code), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
-                                                      CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(prior), _ptr(t1), _stream())
-        _lib.check(st, "bear_cnn_forward_plan_f64")
+        _launch(kmer_code.device, "bear_cnn_forward_plan_f64", plan.ws.handle, plan._h, _ptr(kmer_code), n, int(lag), int(filter_width),
+                CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(prior), _ptr(t1))
         return prior, t1
     ws = ws or default_workspace(kmer_code.device)
     prior = torch.empty((n, 5), dtype=torch.float64, device=kmer_code.device)
     t1 = torch.empty((n, CNN_LAYER1_WIDTH), dtype=torch.float64, device=kmer_code.device) if save else None
-    with torch.cuda.device(kmer_code.device):
-        st = _lib.lib().bear_cnn_forward_f64(ws.handle, _ptr(kmer_code), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
-                                             CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(prior), _ptr(t1), _stream())
-    _lib.check(st, "bear_cnn_forward_f64")
+    _launch(kmer_code.device, "bear_cnn_forward_f64", ws.handle, _ptr(kmer_code), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
+            CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(prior), _ptr(t1))
     return prior, t1
 
 
@@ -844,11 +758,8 @@ def cnn_backward(kmer_code, flat_params, lag, filter_width, t1, prior, grad_prio
             raise ValueError("t1 [n,16], prior [n,5] and grad_prior [n,5] must be contiguous CUDA float64 tensors")
     ws = ws or default_workspace(kmer_code.device)
     grad = torch.empty_like(flat_params)
-    with torch.cuda.device(kmer_code.device):
-        st = _lib.lib().bear_cnn_backward_f64(ws.handle, _ptr(kmer_code), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
-                                              CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(t1), _ptr(prior), _ptr(grad_prior),
-                                              _ptr(grad), _stream())
-    _lib.check(st, "bear_cnn_backward_f64")
+    _launch(kmer_code.device, "bear_cnn_backward_f64", ws.handle, _ptr(kmer_code), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
+            CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(t1), _ptr(prior), _ptr(grad_prior), _ptr(grad))
     return grad
 
 
@@ -875,9 +786,7 @@ def linear_forward(kmer_code, mat, lag, ws=None):
     n = kmer_code.shape[0]
     ws = ws or default_workspace(kmer_code.device)
     prior = torch.empty((n, 5), dtype=torch.float64, device=kmer_code.device)
-    with torch.cuda.device(kmer_code.device):
-        st = _lib.lib().bear_linear_forward_f64(ws.handle, _ptr(kmer_code), n, int(lag), _ptr(mat), _ptr(prior), _stream())
-    _lib.check(st, "bear_linear_forward_f64")
+    _launch(kmer_code.device, "bear_linear_forward_f64", ws.handle, _ptr(kmer_code), n, int(lag), _ptr(mat), _ptr(prior))
     return prior
 
 
@@ -890,10 +799,8 @@ def linear_backward(kmer_code, lag, prior, grad_prior, ws=None):
             raise ValueError("prior and grad_prior must be contiguous CUDA float64 tensors [n, 5]")
     ws = ws or default_workspace(kmer_code.device)
     grad = torch.empty((lag, 5, 5), dtype=torch.float64, device=kmer_code.device)
-    with torch.cuda.device(kmer_code.device):
-        st = _lib.lib().bear_linear_backward_f64(ws.handle, _ptr(kmer_code), n, int(lag), _ptr(prior), _ptr(grad_prior), _ptr(grad),
-                                                 _stream())
-    _lib.check(st, "bear_linear_backward_f64")
+    _launch(kmer_code.device, "bear_linear_backward_f64", ws.handle, _ptr(kmer_code), n, int(lag), _ptr(prior), _ptr(grad_prior),
+            _ptr(grad))
     return grad
 
 
@@ -915,9 +822,7 @@ def linear_forward_wide(codes, mat, lag, ws=None):
     n = codes.shape[0]
     ws = ws or default_workspace(codes.device)
     prior = torch.empty((n, W), dtype=torch.float64, device=codes.device)
-    with torch.cuda.device(codes.device):
-        st = _lib.lib().bear_linear_forward_wide_f64(ws.handle, _ptr(codes), n, int(lag), W, _ptr(mat), _ptr(prior), _stream())
-    _lib.check(st, "bear_linear_forward_wide_f64")
+    _launch(codes.device, "bear_linear_forward_wide_f64", ws.handle, _ptr(codes), n, int(lag), W, _ptr(mat), _ptr(prior))
     return prior
 
 
@@ -927,23 +832,19 @@ def linear_backward_wide(codes, lag, prior, grad_prior, ws=None):
     W = LINEAR_WIDE_WIDTH
     codes = _check_codes_wide(codes, lag)
     n = codes.shape[0]
-    prior = _check_rows_wide(prior, torch.float64, "prior", W)
-    grad_prior = _check_rows_wide(grad_prior, torch.float64, "grad_prior", W)
+    prior = _check_rows(prior, torch.float64, "prior", W)
+    grad_prior = _check_rows(grad_prior, torch.float64, "grad_prior", W)
     if prior.shape[0] != n or grad_prior.shape[0] != n:
         raise ValueError("codes, prior and grad_prior must have the same number of rows")
     ws = ws or default_workspace(codes.device)
     grad = torch.empty((lag, W, W), dtype=torch.float64, device=codes.device)
-    with torch.cuda.device(codes.device):
-        st = _lib.lib().bear_linear_backward_wide_f64(ws.handle, _ptr(codes), n, int(lag), W, _ptr(prior), _ptr(grad_prior), _ptr(grad),
-                                                      _stream())
-    _lib.check(st, "bear_linear_backward_wide_f64")
+    _launch(codes.device, "bear_linear_backward_wide_f64", ws.handle, _ptr(codes), n, int(lag), W, _ptr(prior), _ptr(grad_prior),
+            _ptr(grad))
     return grad
 
 
 def cnn_param_count_wide(lag, filter_width):
-    n = _lib.lib().bear_cnn_param_count_wide(int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, LINEAR_WIDE_WIDTH)
-    _lib.check(min(n, 0), "bear_cnn_param_count_wide")
-    return n
+    return _count("bear_cnn_param_count_wide", int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, LINEAR_WIDE_WIDTH)
 
 
 def _check_params_wide(flat_params, lag, filter_width):
@@ -962,10 +863,8 @@ def cnn_forward_wide(codes, flat_params, lag, filter_width, save=True, ws=None):
     ws = ws or default_workspace(codes.device)
     prior = torch.empty((n, W), dtype=torch.float64, device=codes.device)
     t1 = torch.empty((n, CNN_LAYER1_WIDTH), dtype=torch.float64, device=codes.device) if save else None
-    with torch.cuda.device(codes.device):
-        st = _lib.lib().bear_cnn_forward_wide_f64(ws.handle, _ptr(codes), n, int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH,
-                                                  W, _ptr(flat_params), _ptr(prior), _ptr(t1), _stream())
-    _lib.check(st, "bear_cnn_forward_wide_f64")
+    _launch(codes.device, "bear_cnn_forward_wide_f64", ws.handle, _ptr(codes), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
+            CNN_LAYER1_WIDTH, W, _ptr(flat_params), _ptr(prior), _ptr(t1))
     return prior, t1
 
 
@@ -976,8 +875,8 @@ def cnn_backward_wide(codes, flat_params, lag, filter_width, t1, prior, grad_pri
     codes = _check_codes_wide(codes, lag)
     _check_params_wide(flat_params, lag, filter_width)
     n = codes.shape[0]
-    prior = _check_rows_wide(prior, torch.float64, "prior", W)
-    grad_prior = _check_rows_wide(grad_prior, torch.float64, "grad_prior", W)
+    prior = _check_rows(prior, torch.float64, "prior", W)
+    grad_prior = _check_rows(grad_prior, torch.float64, "grad_prior", W)
     if not (t1.is_cuda and t1.dtype == torch.float64 and t1.dim() == 2 and t1.shape[1] == CNN_LAYER1_WIDTH and t1.is_contiguous()):
         raise ValueError("t1 must be a contiguous CUDA float64 tensor [n, 16] (cnn_forward_wide with save=True)")
     if t1.data_ptr() % 16:
@@ -986,17 +885,9 @@ def cnn_backward_wide(codes, flat_params, lag, filter_width, t1, prior, grad_pri
         raise ValueError("codes, t1, prior and grad_prior must have the same number of rows")
     ws = ws or default_workspace(codes.device)
     grad = torch.empty_like(flat_params)
-    with torch.cuda.device(codes.device):
-        st = _lib.lib().bear_cnn_backward_wide_f64(ws.handle, _ptr(codes), n, int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH,
-                                                   W, _ptr(flat_params), _ptr(t1), _ptr(prior), _ptr(grad_prior), _ptr(grad), _stream())
-    _lib.check(st, "bear_cnn_backward_wide_f64")
+    _launch(codes.device, "bear_cnn_backward_wide_f64", ws.handle, _ptr(codes), n, int(lag), int(filter_width), CNN_NUM_FILTERS,
+            CNN_LAYER1_WIDTH, W, _ptr(flat_params), _ptr(t1), _ptr(prior), _ptr(grad_prior), _ptr(grad))
     return grad
-
-
-def _check_rows5(n, **tensors):
-    for name, t in tensors.items():
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (n, 5) and t.data_ptr() % 16 == 0):
-            raise ValueError(f"{name} must be a contiguous, 16-byte aligned CUDA float64 tensor [{n}, 5]")
 
 
 def _check_scalar_param(**tensors):
@@ -1008,38 +899,34 @@ def _check_scalar_param(**tensors):
 def ref_mix_forward(net_rows, ref_rows, tau_signed, net_weight_signed, ws=None):
     """One launch of ``bear_ref_mix_forward_f64``: (nw net_rows + jukes_cantor(ref_rows, tau)) / (nw + 1) (bear_ref.py:63-68)."""
     n = net_rows.shape[0]
-    _check_rows5(n, net_rows=net_rows, ref_rows=ref_rows)
+    for name, t in (("net_rows", net_rows), ("ref_rows", ref_rows)):
+        _check_rows(t, torch.float64, name, n=n, clone=False)
     _check_scalar_param(tau_signed=tau_signed, net_weight_signed=net_weight_signed)
     ws = ws or default_workspace(net_rows.device)
     prior = torch.empty_like(net_rows)
-    with torch.cuda.device(net_rows.device):
-        st = _lib.lib().bear_ref_mix_forward_f64(ws.handle, _ptr(net_rows), _ptr(ref_rows), n, _ptr(tau_signed), _ptr(net_weight_signed),
-                                                 _ptr(prior), _stream())
-    _lib.check(st, "bear_ref_mix_forward_f64")
+    _launch(net_rows.device, "bear_ref_mix_forward_f64", ws.handle, _ptr(net_rows), _ptr(ref_rows), n, _ptr(tau_signed),
+            _ptr(net_weight_signed), _ptr(prior))
     return prior
 
 
 def ref_mix_backward(net_rows, ref_rows, grad_prior, tau_signed, net_weight_signed, ws=None):
     """One launch of ``bear_ref_mix_backward_f64``: (d L / d net_rows [n, 5], [d L / d tau_signed, d L / d net_weight_signed])."""
     n = net_rows.shape[0]
-    _check_rows5(n, net_rows=net_rows, ref_rows=ref_rows, grad_prior=grad_prior)
+    for name, t in (("net_rows", net_rows), ("ref_rows", ref_rows), ("grad_prior", grad_prior)):
+        _check_rows(t, torch.float64, name, n=n, clone=False)
     _check_scalar_param(tau_signed=tau_signed, net_weight_signed=net_weight_signed)
     ws = ws or default_workspace(net_rows.device)
     grad_rows = torch.empty_like(net_rows)
     scalars = torch.empty(2, dtype=torch.float64, device=net_rows.device)
-    with torch.cuda.device(net_rows.device):
-        st = _lib.lib().bear_ref_mix_backward_f64(ws.handle, _ptr(net_rows), _ptr(ref_rows), _ptr(grad_prior), n, _ptr(tau_signed),
-                                                  _ptr(net_weight_signed), _ptr(grad_rows), _ptr(scalars), _stream())
-    _lib.check(st, "bear_ref_mix_backward_f64")
+    _launch(net_rows.device, "bear_ref_mix_backward_f64", ws.handle, _ptr(net_rows), _ptr(ref_rows), _ptr(grad_prior), n, _ptr(tau_signed),
+            _ptr(net_weight_signed), _ptr(grad_rows), _ptr(scalars))
     return grad_rows, scalars
 
 
 def stream_read(t, ws=None):
     """One launch of ``bear_stream_read`` over tensor ``t`` (measurement helper: a pure HBM read)."""
     ws = ws or default_workspace(t.device)
-    with torch.cuda.device(t.device):
-        st = _lib.lib().bear_stream_read(ws.handle, _ptr(t), t.numel() * t.element_size(), _stream())
-    _lib.check(st, "bear_stream_read")
+    _launch(t.device, "bear_stream_read", ws.handle, _ptr(t), t.numel() * t.element_size())
 
 
 def encode_kmers(ascii_kmers, alphabet="dna"):
@@ -1051,10 +938,7 @@ def encode_kmers(ascii_kmers, alphabet="dna"):
     if mode is None:
         raise NotImplementedError(f"device encoding covers the alphabets dna, rna and prot, not {alphabet!r}")
     codes = torch.empty(ascii_kmers.shape, dtype=torch.int8, device=ascii_kmers.device)
-    with torch.cuda.device(ascii_kmers.device):
-        st = _lib.lib().bear_encode_kmers_i8(_ptr(ascii_kmers), ascii_kmers.shape[0], ascii_kmers.shape[1], mode,
-                                             _ptr(codes), _stream())
-    _lib.check(st, "bear_encode_kmers_i8")
+    _launch(ascii_kmers.device, "bear_encode_kmers_i8", _ptr(ascii_kmers), ascii_kmers.shape[0], ascii_kmers.shape[1], mode, _ptr(codes))
     return codes
 
 
@@ -1063,21 +947,22 @@ def _f64_vec(t, n, name):
         raise ValueError(f"{name} must be a contiguous CUDA float64 tensor of {n} elements")
 
 
+def _loss(loss_buf):
+    """(loss_buf, loss_cap) of the step entries: the record of the losses and its length, or NULL and 0."""
+    return _ptr(loss_buf), 0 if loss_buf is None else loss_buf.numel()
+
+
 def dm_prior_planned_dev(plan, prior, h_signed_dev, eps=EPSILON, out=None, normalized=False, want_grad=False, train_ar=False):
     """``bear_dm_prior_plan_dev_f64``: dm_prior_planned with h_signed read from a device tensor, so a training step is
     enqueued without the host reading the parameter back.  Returns out, or (out, grad rows) with want_grad."""
     counts = plan.counts
-    _check_rows(prior, torch.float64, "prior")
-    if prior.data_ptr() % 16 or prior.shape[0] != counts.shape[0] or plan.ncol != 5:
-        raise ValueError("prior must be 16-byte aligned with one row per planned context (plan ncol=5)")
+    _check_planned(plan, 5, prior, torch.float64, "prior")
     _f64_vec(h_signed_dev, 1, "h_signed_dev")
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=counts.device)
     grad = torch.empty_like(prior) if want_grad else None
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_prior_plan_dev_f64(plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0], _ptr(h_signed_dev),
-                                                   float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_prior_plan_dev_f64")
+    _launch(counts.device, "bear_dm_prior_plan_dev_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
+            _ptr(h_signed_dev), float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out), _ptr(grad))
     return (out, grad) if want_grad else out
 
 
@@ -1087,7 +972,8 @@ def dm_refmix_planned_dev(plan, net_rows, ref_rows, h_signed_dev, tau_signed_dev
     Returns (out [4] = sum LL, d/dh_signed, d/dtau_signed, d/dnet_weight_signed; d sum LL / d net_rows [n, 5])."""
     counts = plan.counts
     n = counts.shape[0]
-    _check_rows5(n, net_rows=net_rows, ref_rows=ref_rows)
+    for name, t in (("net_rows", net_rows), ("ref_rows", ref_rows)):
+        _check_rows(t, torch.float64, name, n=n, clone=False)
     if plan.ncol != 5:
         raise ValueError("a five-column plan of the training counts is needed")
     _check_scalar_param(h_signed_dev=h_signed_dev, tau_signed_dev=tau_signed_dev, net_weight_signed_dev=net_weight_signed_dev)
@@ -1095,11 +981,8 @@ def dm_refmix_planned_dev(plan, net_rows, ref_rows, h_signed_dev, tau_signed_dev
         out = torch.empty(4, dtype=torch.float64, device=counts.device)
     _f64_vec(out, 4, "out")
     grad = torch.empty_like(net_rows)
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_refmix_plan_grad_f64(plan.ws.handle, plan._h, _ptr(counts), _ptr(net_rows), _ptr(ref_rows), n,
-                                                     _ptr(h_signed_dev), _ptr(tau_signed_dev), _ptr(net_weight_signed_dev), float(eps),
-                                                     int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_refmix_plan_grad_f64")
+    _launch(counts.device, "bear_dm_refmix_plan_grad_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(net_rows), _ptr(ref_rows), n,
+            _ptr(h_signed_dev), _ptr(tau_signed_dev), _ptr(net_weight_signed_dev), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
 
@@ -1109,44 +992,31 @@ def train_apply(theta, packed, adam_m, adam_v, adam_t, learning_rate, scale, los
     n = theta.numel()
     for t, k, name in ((theta, n, "theta"), (packed, n + 1, "packed"), (adam_m, n, "adam_m"), (adam_v, n, "adam_v"), (adam_t, 1, "adam_t")):
         _f64_vec(t, k, name)
-    with torch.cuda.device(theta.device):
-        st = _lib.lib().bear_train_apply_f64(_ptr(theta), n, _ptr(packed), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(learning_rate),
-                                             float(scale), int(bool(train_ar)), _ptr(loss_buf),
-                                             0 if loss_buf is None else loss_buf.numel(), _stream())
-    _lib.check(st, "bear_train_apply_f64")
+    _launch(theta.device, "bear_train_apply_f64", _ptr(theta), n, _ptr(packed), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t),
+            float(learning_rate), float(scale), int(bool(train_ar)), *_loss(loss_buf))
 
 
 def ref_train_reduce(plan, ref, theta, packed, eps=EPSILON, train_ar=False):
     """Enqueues ``bear_ref_train_reduce_f64``: this shard's packed = [sum LL, d/dh_s, d/dtau_s, d/dnu_s] with the kernel constants
     derived from the device-resident theta (no host round trip)."""
     train = plan.counts
-    _check_rows(ref, torch.int32, "ref")
+    _check_planned(plan, 4, ref, torch.int32, "ref")
     _f64_vec(theta, 3, "theta")
     _f64_vec(packed, 4, "packed")
-    if ref.data_ptr() % 16 or ref.shape[0] != train.shape[0] or plan.ncol != 4:
-        raise ValueError("ref must be 16-byte aligned with one row per planned context (plan ncol=4)")
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_ref_train_reduce_f64(plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta), float(eps),
-                                                  int(bool(train_ar)), _ptr(packed), _stream())
-    _lib.check(st, "bear_ref_train_reduce_f64")
+    _launch(train.device, "bear_ref_train_reduce_f64", plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta),
+            float(eps), int(bool(train_ar)), _ptr(packed))
 
 
 def ref_train_step(plan, ref, theta, adam_m, adam_v, adam_t, learning_rate, scale, out, loss_buf=None, eps=EPSILON, train_ar=False):
     """Enqueues one ``bear_ref_train_step_f64`` (constants from theta, planned mode-R kernel, finalize, Adam on theta): no host
     synchronisation, every argument device-resident -- capturable in a HIP graph (``torch.cuda.graph``)."""
     train = plan.counts
-    _check_rows(ref, torch.int32, "ref")
-    for t, n in ((theta, 3), (adam_m, 3), (adam_v, 3), (adam_t, 1), (out, 4)):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n):
-            raise ValueError("theta / adam_m / adam_v [3], adam_t [1], out [4] must be contiguous CUDA float64 tensors")
-    if ref.data_ptr() % 16 or ref.shape[0] != train.shape[0] or plan.ncol != 4:
-        raise ValueError("ref must be 16-byte aligned with one row per planned context (plan ncol=4)")
-    with torch.cuda.device(train.device):
-        st = _lib.lib().bear_ref_train_step_f64(plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta), _ptr(adam_m),
-                                                _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)), float(learning_rate),
-                                                float(scale), _ptr(out), _ptr(loss_buf), 0 if loss_buf is None else loss_buf.numel(),
-                                                _stream())
-    _lib.check(st, "bear_ref_train_step_f64")
+    _check_planned(plan, 4, ref, torch.int32, "ref")
+    for t, n, name in ((theta, 3, "theta"), (adam_m, 3, "adam_m"), (adam_v, 3, "adam_v"), (adam_t, 1, "adam_t"), (out, 4, "out")):
+        _f64_vec(t, n, name)
+    _launch(train.device, "bear_ref_train_step_f64", plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta),
+            _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)), float(learning_rate), float(scale), _ptr(out),
+            *_loss(loss_buf))
 
 
 def _check_linear_step(plan, kmer_code, lag, theta, packed):
@@ -1163,10 +1033,8 @@ def net_linear_train_reduce(plan, kmer_code, lag, theta, packed, eps=EPSILON, tr
     """Enqueues ``bear_net_linear_train_reduce_f64``: packed = [sum LL, d/dh_s, d/d mat (lag*25)] of this shard, theta = {h_signed, mat}
     device-resident."""
     n = _check_linear_step(plan, kmer_code, lag, theta, packed)
-    with torch.cuda.device(theta.device):
-        st = _lib.lib().bear_net_linear_train_reduce_f64(plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n, _ptr(theta),
-                                                         float(eps), int(bool(train_ar)), _ptr(packed), _stream())
-    _lib.check(st, "bear_net_linear_train_reduce_f64")
+    _launch(theta.device, "bear_net_linear_train_reduce_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n,
+            _ptr(theta), float(eps), int(bool(train_ar)), _ptr(packed))
 
 
 def net_linear_train_step(plan, kmer_code, lag, theta, adam_m, adam_v, adam_t, packed, learning_rate, scale, loss_buf=None,
@@ -1176,12 +1044,9 @@ def net_linear_train_step(plan, kmer_code, lag, theta, adam_m, adam_v, adam_t, p
     size = 1 + lag * 25
     for t, k in ((adam_m, size), (adam_v, size), (adam_t, 1)):
         _f64_vec(t, k, "adam state")
-    with torch.cuda.device(theta.device):
-        st = _lib.lib().bear_net_linear_train_step_f64(plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n, _ptr(theta),
-                                                       _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), _ptr(packed), float(eps),
-                                                       int(bool(train_ar)), float(learning_rate), float(scale),
-                                                       _ptr(loss_buf), 0 if loss_buf is None else loss_buf.numel(), _stream())
-    _lib.check(st, "bear_net_linear_train_step_f64")
+    _launch(theta.device, "bear_net_linear_train_step_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n,
+            _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), _ptr(packed), float(eps), int(bool(train_ar)), float(learning_rate),
+            float(scale), *_loss(loss_buf))
 
 
 # tile and resident blocks per CU of the fused linear step at width 21 (kernels_linear_wide.h: LSW_TILE, LSW_BLOCKS_PER_CU): a launch
@@ -1194,16 +1059,9 @@ def _check_linear_step_wide(counts, codes, lag):
     W = LINEAR_WIDE_WIDTH
     if not 1 <= int(lag) <= LINEAR_WIDE_MAX_LAG:
         raise ValueError(f"lag must be 1..{LINEAR_WIDE_MAX_LAG} (mat [lag, {W}, {W}] lives in LDS)")
-    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.dim() == 2 and counts.shape[1] == W and counts.is_contiguous()):
-        raise ValueError(f"counts must be a contiguous CUDA int32 tensor [n, {W}]")
-    if not (codes.is_cuda and codes.dtype == torch.int8 and codes.dim() == 2 and codes.shape[1] == lag and codes.is_contiguous()):
-        raise ValueError("codes must be a contiguous CUDA int8 tensor [n, lag]")
+    counts, codes = _check_rows(counts, torch.int32, "counts", W), _check_codes_wide(codes, lag)
     if codes.shape[0] != counts.shape[0] or codes.device != counts.device:
         raise ValueError("counts and codes must have the same number of rows, on one device")
-    if counts.data_ptr() % 16:
-        counts = counts.clone()
-    if codes.data_ptr() % 16:
-        codes = codes.clone()
     return counts, codes
 
 
@@ -1223,10 +1081,8 @@ def dm_linear_wide(counts, codes, mat, h_signed, eps=EPSILON, train_ar=False, ou
     _f64_vec(out, 2, "out")
     ws = ws or default_workspace(counts.device)
     grad = torch.empty_like(mat)
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_dm_linear_wide_f64(ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag), W, _ptr(mat),
-                                                float(h_signed), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad), _stream())
-    _lib.check(st, "bear_dm_linear_wide_f64")
+    _launch(counts.device, "bear_dm_linear_wide_f64", ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag), W, _ptr(mat),
+            float(h_signed), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
 
@@ -1238,11 +1094,8 @@ def net_linear_train_reduce_wide(counts, codes, lag, theta, packed, eps=EPSILON,
     _f64_vec(theta, size, "theta")
     _f64_vec(packed, size + 1, "packed")
     ws = ws or default_workspace(counts.device)
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_net_linear_train_reduce_wide_f64(ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
-                                                              LINEAR_WIDE_WIDTH, _ptr(theta), float(eps), int(bool(train_ar)),
-                                                              _ptr(packed), _stream())
-    _lib.check(st, "bear_net_linear_train_reduce_wide_f64")
+    _launch(counts.device, "bear_net_linear_train_reduce_wide_f64", ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
+            LINEAR_WIDE_WIDTH, _ptr(theta), float(eps), int(bool(train_ar)), _ptr(packed))
 
 
 def net_linear_train_step_wide(counts, codes, lag, theta, adam_m, adam_v, adam_t, packed, learning_rate, scale, loss_buf=None,
@@ -1257,13 +1110,9 @@ def net_linear_train_step_wide(counts, codes, lag, theta, adam_m, adam_v, adam_t
     if loss_buf is not None:
         _f64_vec(loss_buf, loss_buf.numel(), "loss_buf")
     ws = ws or default_workspace(counts.device)
-    with torch.cuda.device(counts.device):
-        st = _lib.lib().bear_net_linear_train_step_wide_f64(ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
-                                                            LINEAR_WIDE_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t),
-                                                            float(eps), int(bool(train_ar)), float(learning_rate), float(scale),
-                                                            _ptr(packed), _ptr(loss_buf), 0 if loss_buf is None else loss_buf.numel(),
-                                                            _stream())
-    _lib.check(st, "bear_net_linear_train_step_wide_f64")
+    _launch(counts.device, "bear_net_linear_train_step_wide_f64", ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
+            LINEAR_WIDE_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)), float(learning_rate),
+            float(scale), _ptr(packed), *_loss(loss_buf))
 
 
 def net_cnn_train_reduce(plan, kmer_code, lag, filter_width, theta, bufs, packed, eps=EPSILON, train_ar=False):
@@ -1274,11 +1123,9 @@ def net_cnn_train_reduce(plan, kmer_code, lag, filter_width, theta, bufs, packed
     np_ = cnn_param_count(lag, filter_width)
     _f64_vec(theta, 1 + np_, "theta")
     _f64_vec(packed, 2 + np_, "packed")
-    with torch.cuda.device(theta.device):
-        st = _lib.lib().bear_net_cnn_train_reduce_f64(plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag), int(filter_width),
-                                                      CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(theta), _ptr(prior), _ptr(t1), _ptr(grad_rows),
-                                                      float(eps), int(bool(train_ar)), _ptr(packed), _stream())
-    _lib.check(st, "bear_net_cnn_train_reduce_f64")
+    _launch(theta.device, "bear_net_cnn_train_reduce_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag),
+            int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(theta), _ptr(prior), _ptr(t1), _ptr(grad_rows), float(eps),
+            int(bool(train_ar)), _ptr(packed))
 
 
 def net_cnn_train_step(plan, kmer_code, lag, filter_width, theta, adam_m, adam_v, adam_t, bufs, packed, learning_rate, scale, loss_buf=None,
@@ -1290,13 +1137,9 @@ def net_cnn_train_step(plan, kmer_code, lag, filter_width, theta, adam_m, adam_v
     np_ = cnn_param_count(lag, filter_width)
     _f64_vec(theta, 1 + np_, "theta")
     _f64_vec(packed, 2 + np_, "packed")
-    with torch.cuda.device(theta.device):
-        st = _lib.lib().bear_net_cnn_train_step_f64(plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag), int(filter_width),
-                                                    CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t),
-                                                    _ptr(prior), _ptr(t1), _ptr(grad_rows), _ptr(packed), float(eps), int(bool(train_ar)),
-                                                    float(learning_rate), float(scale), _ptr(loss_buf),
-                                                    0 if loss_buf is None else loss_buf.numel(), _stream())
-    _lib.check(st, "bear_net_cnn_train_step_f64")
+    _launch(theta.device, "bear_net_cnn_train_step_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag),
+            int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), _ptr(prior),
+            _ptr(t1), _ptr(grad_rows), _ptr(packed), float(eps), int(bool(train_ar)), float(learning_rate), float(scale), *_loss(loss_buf))
 
 
 def cnn_step_buffers(n_rows, lag, filter_width, device, ws=None):
@@ -1305,8 +1148,7 @@ def cnn_step_buffers(n_rows, lag, filter_width, device, ws=None):
     batch serves every batch."""
     ws = ws or default_workspace(device)
     with torch.cuda.device(device):
-        _lib.check(_lib.lib().bear_cnn_reserve(ws.handle, int(n_rows), int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH),
-                   "bear_cnn_reserve")
+        _lib.call("bear_cnn_reserve", ws.handle, int(n_rows), int(lag), int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH)
     # zeros: the step only fills the rows of contexts that hold training counts (nothing reads the others: kept finite)
     return (torch.zeros((n_rows, 5), dtype=torch.float64, device=device), torch.zeros((n_rows, CNN_LAYER1_WIDTH), dtype=torch.float64, device=device),
             torch.zeros((n_rows, 5), dtype=torch.float64, device=device))

@@ -135,25 +135,22 @@ def count_transitions(text, group, lag, n_groups, device=None, on_device=False, 
     g = group if isinstance(group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(group)).to(device)
     if t.dtype != torch.uint8 or g.dtype != torch.uint8 or t.shape != g.shape or t.dim() != 1:
         raise ValueError("text and group must be uint8 vectors of the same length")
-    L = _lib.lib()
     h, n_rows = ctypes.c_void_p(), ctypes.c_uint64()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     with torch.cuda.device(t.device):
+        head, tail = (t.data_ptr(), g.data_ptr(), t.numel(), int(lag)), (ctypes.byref(h), ctypes.byref(n_rows), stream)
         if width == 5:
-            _lib.check(L.bear_kmer_sort_create(t.data_ptr(), g.data_ptr(), t.numel(), int(lag), ctypes.byref(h), ctypes.byref(n_rows),
-                                               stream), "bear_kmer_sort_create")
+            _lib.call("bear_kmer_sort_create", *head, *tail)
         else:
-            _lib.check(L.bear_kmer_sort_create_wide(t.data_ptr(), g.data_ptr(), t.numel(), int(lag), width, ctypes.byref(h),
-                                                    ctypes.byref(n_rows), stream), "bear_kmer_sort_create_wide")
+            _lib.call("bear_kmer_sort_create_wide", *head, width, *tail)
         try:
             n = n_rows.value
             kmers = torch.empty((n, lag), dtype=torch.uint8, device=t.device)
             counts = torch.empty((n_groups, n, width), dtype=torch.int32, device=t.device)
-            _lib.check(L.bear_kmer_sort_reduce(h, int(n_groups), kmers.data_ptr(), None, counts.data_ptr(), stream),
-                       "bear_kmer_sort_reduce")
+            _lib.call("bear_kmer_sort_reduce", h, int(n_groups), kmers.data_ptr(), None, counts.data_ptr(), stream)
             torch.cuda.current_stream().synchronize()
         finally:
-            L.bear_kmer_sort_destroy(h)
+            _lib.lib().bear_kmer_sort_destroy(h)
     if on_device:
         return kmers, counts
     return kmers.cpu().numpy(), counts.cpu().numpy().view(np.uint32)
@@ -172,25 +169,20 @@ def _load_sequences(seq_list_file):
 def load_text(seq_list_file, reverse=False, alphabet="dna"):
     """Every file of the list as the device code text (C++ readers, ``bear_fastx_encode`` / ``_wide``): ``(text, group, n_groups)``."""
     width = _width(alphabet, reverse)
-    L = _lib.lib()
     parts, gparts, groups = [], [], []
     for path, group, ftype in read_file_list(seq_list_file):
         if ftype not in ("fa", "fq"):
             raise ValueError("file type must be 'fa' or 'fq'")
         n = ctypes.c_uint64()
         if width == 5:
-            _lib.check(L.bear_fastx_size(path.encode(), int(ftype == "fq"), int(bool(reverse)), ctypes.byref(n), None), "bear_fastx_size")
-        else:       # (the sizing pass leaves a record's closing '*' out, as the encoding pass does)
-            _lib.check(L.bear_fastx_size_wide(path.encode(), int(ftype == "fq"), 0, width, ctypes.byref(n), None), "bear_fastx_size_wide")
+            size, encode, head = "bear_fastx_size", "bear_fastx_encode", (path.encode(), int(ftype == "fq"), int(bool(reverse)))
+        else:       # the wide twins take the width and refuse reverse
+            size, encode, head = "bear_fastx_size_wide", "bear_fastx_encode_wide", (path.encode(), int(ftype == "fq"), 0, width)
+        _lib.call(size, *head, ctypes.byref(n), None)    # (leaves a record's closing '*' out, as the encoding pass does)
         text = np.empty(n.value, dtype=np.uint8)
         grp = np.empty(n.value, dtype=np.uint8)
         got = ctypes.c_uint64()
-        if width == 5:
-            _lib.check(L.bear_fastx_encode(path.encode(), int(ftype == "fq"), int(bool(reverse)), int(group), n.value, text.ctypes.data,
-                                           grp.ctypes.data, ctypes.byref(got)), "bear_fastx_encode")
-        else:
-            _lib.check(L.bear_fastx_encode_wide(path.encode(), int(ftype == "fq"), 0, width, int(group), n.value, text.ctypes.data,
-                                                grp.ctypes.data, ctypes.byref(got)), "bear_fastx_encode_wide")
+        _lib.call(encode, *head, int(group), n.value, text.ctypes.data, grp.ctypes.data, ctypes.byref(got))
         if got.value != n.value:      # the file changed between the sizing pass and the encoding pass
             raise RuntimeError(f"{path}: {got.value} positions encoded, {n.value} counted")
         parts.append(text)
@@ -227,18 +219,16 @@ def compute_n_bin_bits(total_size, n_groups, mf):
 
 def write_tables(tables, out_prefix, n_bins):
     """``<out_prefix>_lag_<L>_file_<b>.tsv`` (summarize.py:472-473, 529-530), rows dealt round-robin to the bins."""
-    L = _lib.lib()
     for li, d in enumerate(tables):
         km = np.ascontiguousarray(d.kmers)
         cn = np.ascontiguousarray(d.counts)
         for b in range(n_bins):
             path = "{}_lag_{}_file_{}.tsv".format(out_prefix, li + 1, b)
+            head = (path.encode(), km.ctypes.data, cn.ctypes.data, d.num_rows, li + 1, d.num_ds)
             if d.width == 5:
-                _lib.check(L.bear_write_counts_tsv(path.encode(), km.ctypes.data, cn.ctypes.data, d.num_rows, li + 1, d.num_ds,
-                                                   b, n_bins, 0), "bear_write_counts_tsv")
+                _lib.call("bear_write_counts_tsv", *head, b, n_bins, 0)
             else:
-                _lib.check(L.bear_write_counts_tsv_wide(path.encode(), km.ctypes.data, cn.ctypes.data, d.num_rows, li + 1, d.num_ds,
-                                                        int(d.width), b, n_bins, 0), "bear_write_counts_tsv_wide")
+                _lib.call("bear_write_counts_tsv_wide", *head, int(d.width), b, n_bins, 0)
 
 
 def run(args):

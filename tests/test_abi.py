@@ -3,18 +3,16 @@ include/bear_hip.h declares, fails loudly without a device, and its host-side co
 parser reproduces the reference's golden first batch."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, YSD1
+from util import HEADER, abi_header
 
 
 def _declared_symbols():
-    src = open(os.path.join(ROOT, "include", "bear_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(bear_[a-z0-9_]+)\s*\(", src)))
+    return sorted(abi_header()[1])
 
 
 def test_library_exports_every_declared_symbol():
@@ -25,9 +23,73 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(L, n), f"{n} declared in include/bear_hip.h but not exported"
     assert sorted(_lib.SYMBOLS) == names
-    hdr = open(os.path.join(ROOT, "include", "bear_hip.h")).read()
-    assert L.bear_abi_version() == int(re.search(r"#define BEAR_ABI_VERSION (\d+)", hdr).group(1))
+    assert L.bear_abi_version() == abi_header()[0] == _lib.ABI_VERSION
     assert L.bear_strerror(0) == b"ok"
+
+
+def test_binding_takes_every_signature_from_the_header():
+    """Result and argument types of EVERY declared function, as the loader set them, against the tests' own reading of the header:
+    a scalar of the wrong width or a dropped argument would hand a kernel a garbage pointer or row count."""
+    from bear_amd import _lib
+    L = _lib.lib()
+    sigs = abi_header()[1]
+    assert len(sigs) >= 100
+    for name, (restype, argtypes) in sigs.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == argtypes, name
+
+
+def test_binding_of_each_type_class_by_hand():
+    """One function per type class, written out by hand from include/bear_hip.h (neither reader is trusted here)."""
+    from bear_amd import _lib
+    L = _lib.lib()
+    vp, cp, i, u64, i64, u32, dbl = (ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32,
+                                     ctypes.c_double)
+    out = ctypes.POINTER(vp)
+    want = {
+        "bear_parse_counts_tsv": (i, [cp, i, i, u64, vp, vp, vp]),                       # a path; the kmers buffer is an address
+        "bear_shuffle_rows": (i, [vp, vp, u64, u32, u64, vp]),
+        "bear_cache_write": (i, [cp, vp, vp, u64, i, i, u64, i64]),
+        "bear_stat_source": (i, [cp, vp, vp]),
+        "bear_ws_create": (i, [i, out]),
+        "bear_plan_create_auto": (i, [vp, vp, u64, vp, out]),
+        "bear_plan_bytes": (u64, [vp]),
+        "bear_shuffle_source_row": (u64, [u64, u64, u64]),
+        "bear_strerror": (cp, [i]),
+        "bear_abi_version": (i, []),
+        "bear_dm_ref_f64": (i, [vp, vp, vp, u64, dbl, dbl, dbl, dbl, i, vp, vp]),
+        "bear_net_cnn_train_step_f64": (i, [vp, vp, vp, vp, u64, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, dbl, i, dbl, dbl, vp, u64, vp]),
+    }
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+@pytest.mark.parametrize("decl,quoted", [
+    ("int bear_new_entry(bear_ws *ws, float scale, void *stream);", "float scale"),           # a parameter type outside the map
+    ("int bear_new_entry(bear_ws *ws, unsigned n);", "unsigned n"),
+    ("float bear_new_entry(bear_ws *ws);", "float bear_new_entry(bear_ws *ws)"),              # a result type outside the map
+    ("int bear_new_entry(int (*callback)(int));", "bear_new_entry"),                            # not the plain C the reader takes
+])
+def test_loader_refuses_a_declaration_it_cannot_map(tmp_path, decl, quoted):
+    """The loader never guesses: a header with a declaration outside its type map is an ImportError that quotes the declaration."""
+    from bear_amd import _lib
+    src = open(HEADER).read()
+    path = tmp_path / "bear_hip.h"
+    path.write_text(src.replace("int bear_abi_version(void);", "int bear_abi_version(void);\n" + decl))
+    with pytest.raises(ImportError) as err:
+        _lib.read_header(str(path))
+    assert quoted in str(err.value) and "bear_new_entry" in str(err.value)
+    version, sigs = _lib.read_header(HEADER)                                                     # the shipped header reads clean
+    assert (version, list(sigs)) == (_lib.ABI_VERSION, _lib.SYMBOLS)
+
+
+def test_missing_header_is_named(tmp_path):
+    from bear_amd import _lib
+    with pytest.raises(ImportError) as err:
+        _lib.read_header(str(tmp_path / "nowhere" / "bear_hip.h"))
+    assert str(tmp_path / "nowhere" / "bear_hip.h") in str(err.value)
 
 
 def test_deterministic_build_exports_the_same_abi():

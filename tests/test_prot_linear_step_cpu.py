@@ -11,6 +11,7 @@ import torch
 
 from bear_amd import _lib, bear_net, kernels
 from conftest import ROOT
+from util import abi_header
 
 NEW = ["bear_dm_linear_wide_f64", "bear_net_linear_train_reduce_wide_f64", "bear_net_linear_train_step_wide_f64"]
 W = 21
@@ -18,16 +19,13 @@ W = 21
 
 def test_both_builds_export_the_symbols_at_abi_12():
     L = _lib.lib()
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bear_hip.h")).read(), flags=re.S)
-    assert _lib.ABI_VERSION == 12 and L.bear_abi_version() == 12 and re.search(r"#define BEAR_ABI_VERSION 12\b", hdr)
+    version, sigs = abi_header()
+    assert _lib.ABI_VERSION == 12 and L.bear_abi_version() == 12 and version == 12
     det = ctypes.CDLL(os.path.join(ROOT, "bear_amd", "libbear_hip_det.so"))
     assert det.bear_abi_version() == 12
-    ctype_of = {"double": ctypes.c_double, "int": ctypes.c_int, "uint64_t": ctypes.c_uint64}
     for name in NEW:
-        assert name in _lib.SYMBOLS and name in _lib.SYMBOLS_ADDED_AT_12 and hasattr(L, name) and hasattr(det, name), name
-        args = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, hdr).group(1).split(",")
-        want = [ctypes.c_void_p if "*" in a else ctype_of[a.split()[-2]] for a in args]
-        assert list(getattr(L, name).argtypes) == want, name
+        assert name in _lib.SYMBOLS and hasattr(L, name) and hasattr(det, name), name
+        assert sigs[name][0] is ctypes.c_int and list(getattr(L, name).argtypes) == sigs[name][1], name
 
 
 def test_tile_constants_are_the_headers():
@@ -83,6 +81,18 @@ def test_dispatch_predicate(monkeypatch):
     assert sel(20, 4, True, 21) is True
 
 
+class _Stale:
+    """A loaded library without the symbols ``missing``."""
+
+    def __init__(self, real, missing):
+        self._real, self._missing = real, missing
+
+    def __getattr__(self, name):
+        if name in self._missing:
+            raise AttributeError(name)
+        return getattr(self._real, name)
+
+
 def test_stale_library_is_named(monkeypatch, tmp_path):
     """A library that answers ABI 12 but was built before the three symbols: the loader names the first one and the rebuild command."""
     class Stale:
@@ -97,4 +107,14 @@ def test_stale_library_is_named(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(ctypes, "CDLL", lambda path: Stale(real))
     with pytest.raises(ImportError, match=r"bear_dm_linear_wide_f64.*make -C"):
+        _lib._load()
+
+
+@pytest.mark.parametrize("missing", ["bear_ws_destroy", "bear_eval_plan_f64", "bear_cache_read", "bear_write_counts_tsv_wide"])
+def test_stale_library_is_named_for_any_declared_symbol(monkeypatch, missing):
+    """... and not only for the newest ones: any function the header declares and the library lacks is named."""
+    real = ctypes.CDLL(_lib.LIB_PATH)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(ctypes, "CDLL", lambda path: _Stale(real, {missing}))
+    with pytest.raises(ImportError, match=r"stale.*does not export %s;.*make -C" % missing):
         _lib._load()

@@ -9,6 +9,7 @@ import torch
 
 from bear_amd import _lib, kernels
 from conftest import ROOT
+from util import abi_header
 
 NEW = ["bear_dm_ref_wide_f64", "bear_ref_train_reduce_wide_f64", "bear_ref_train_step_wide_f64", "bear_dm_refmix_wide_grad_f64"]
 
@@ -45,22 +46,14 @@ def test_wrappers_refuse_before_any_launch(train, ref):
         kernels.dm_refmix_wide_dev(train, net.to(torch.float32), ref, _vec(1), _vec(1), _vec(1))
 
 
-def _header():
-    src = open(os.path.join(ROOT, "include", "bear_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
 def test_binding_declares_the_new_symbols():
     L = _lib.lib()
-    hdr = _header()
+    sigs = abi_header()[1]
     assert _lib.ABI_VERSION == 12 and L.bear_abi_version() == 12
     det = ctypes.CDLL(os.path.join(ROOT, "bear_amd", "libbear_hip_det.so"))
-    ctype_of = {"double": ctypes.c_double, "int": ctypes.c_int, "uint64_t": ctypes.c_uint64}
     for name in NEW:
         assert name in _lib.SYMBOLS and hasattr(L, name) and hasattr(det, name), name
-        args = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, hdr).group(1).split(",")
-        want = [ctypes.c_void_p if "*" in a else ctype_of[a.split()[-2]] for a in args]
-        assert list(getattr(L, name).argtypes) == want, name
+        assert sigs[name][0] is ctypes.c_int and list(getattr(L, name).argtypes) == sigs[name][1], name
 
 
 def test_tile_constants_are_the_headers():

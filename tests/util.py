@@ -1,5 +1,33 @@
-"""Seeded input generators shared by the CPU and GPU tests (NumPy only)."""
+"""Seeded input generators shared by the CPU and GPU tests (NumPy only), and the tests' own reader of the C ABI's header."""
+import ctypes
+import os
+import re
+
 import numpy as np
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "bear_hip.h")
+
+
+def abi_header(path=HEADER):
+    """(BEAR_ABI_VERSION, {function: (restype, [argtypes])}) as ``path`` declares them, in ctypes terms.  Written apart from the
+    reader of ``bear_amd._lib`` on purpose (the tests hold that one to this one): one pattern for a whole declaration, the
+    parameter's type from its first word."""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    scalar = {"int": ctypes.c_int, "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+              "double": ctypes.c_double}
+    result = {"int": ctypes.c_int, "uint64_t": ctypes.c_uint64, "const char *": ctypes.c_char_p}
+
+    def ctype(param):
+        if "**" in param.replace(" ", ""):
+            return ctypes.POINTER(ctypes.c_void_p)
+        if "*" in param:
+            return ctypes.c_char_p if re.fullmatch(r"\s*const\s+char\s*\*\s*path\s*", param) else ctypes.c_void_p
+        return scalar[param.split()[0]]
+    sigs = {}
+    for res, name, params in re.findall(r"^(int|uint64_t|const char \*) ?(bear_[a-z0-9_]+)\(([^()]*)\);", src, flags=re.M):
+        sigs[name] = (result[res], [] if params.strip() == "void" else [ctype(q) for q in params.split(",")])
+    assert sorted(sigs) == sorted(set(re.findall(r"\b(bear_[a-z0-9_]+)\s*\(", src))), "a declaration this reader does not understand"
+    return int(re.search(r"#define BEAR_ABI_VERSION (\d+)", src).group(1)), sigs
 
 
 def sparse_table(n, seed=0, lam_scale=1.0):
