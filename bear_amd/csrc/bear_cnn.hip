@@ -96,7 +96,7 @@ static int cnn_backward_grid(bear_ws *ws, const cnn_dims &D, uint64_t n_rows, in
   if (ws->cnn_partials_cap < need) {
     if (!may_alloc) return BEAR_ERR_INVALID_ARG;
     HIP_TRY(hipStreamSynchronize(s));
-    if (ws->cnn_partials) (void)hipFree(ws->cnn_partials);
+    (void)hipFree(ws->cnn_partials);        // the smaller buffer goes first: the two never stand side by side
     ws->cnn_partials = nullptr;
     ws->cnn_partials_cap = 0;
     HIP_TRY(hipMalloc(&ws->cnn_partials, sizeof(double) * need));
@@ -275,7 +275,7 @@ static int cnn_train_reduce_levels(bear_ws *ws, const bear_plan *plan, const cnn
 }
 
 // Prefix levels of the plan's (k-mer-sorted) contexts for the convolutional step: see include/bear_hip.h.
-static void plan_drop_cnn_levels(bear_plan *plan) {
+void plan_drop_cnn_levels(bear_plan *plan) {
   for (int k = 0; k < plan->n_cnn_levels; ++k) {
     plan->bytes -= plan->cnn_levels[k].bytes;
     bear_level_free(&plan->cnn_levels[k]);
@@ -312,7 +312,6 @@ int bear_plan_attach_cnn_levels(bear_plan *plan, const uint64_t *kmer_code, int 
     bear_level_dev lv;
     const int st = bear_level_build(below, n_below, lag - k, &lv, s);
     if (st != BEAR_OK) {
-      if (st == BEAR_ERR_HIP) g_last_hip_error = bear_count_last_hip_error();
       plan_drop_cnn_levels(plan);                      // the levels built so far go with it: the plan is as it was without levels
       return st;
     }
@@ -347,7 +346,6 @@ int bear_plan_attach_cnn_levels(bear_plan *plan, const uint64_t *kmer_code, int 
         bear_window_dev wt;
         const int st = bear_window_build(codes_k, n_k, p, filter_width, &wt, s);
         if (st != BEAR_OK) {
-          if (st == BEAR_ERR_HIP) g_last_hip_error = bear_count_last_hip_error();
           for (int q = 0; q < nb; ++q) bear_window_free(&built[q]);
           plan_drop_cnn_levels(plan);
           return st;

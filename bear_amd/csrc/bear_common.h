@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/bear_hip.h"
+#include "bear_dev.h"
 #include "bear_release_guard.h"
 #include "bear_math.h"
 
@@ -13,17 +14,6 @@
 #define BEAR_TILE_ROWS 1024
 #define BEAR_ROWS_PER_THREAD (BEAR_TILE_ROWS / BEAR_THREADS)
 #define BEAR_MAX_OUT 4
-
-extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // one per thread for the whole library (bear_hip.hip): bear_last_hip_error()
-
-#define HIP_TRY(expr)                      \
-  do {                                     \
-    hipError_t _e = (expr);                \
-    if (_e != hipSuccess) {                \
-      g_last_hip_error = (int)_e;          \
-      return BEAR_ERR_HIP;                 \
-    }                                      \
-  } while (0)
 
 struct bear_params;
 struct bear_ws {

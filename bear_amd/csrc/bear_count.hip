@@ -22,20 +22,23 @@
 #include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
 
-#include "../../include/bear_hip.h"
+#include <new>
+
+#include "bear_dev.h"
 #include "bear_levels.h"
 
 namespace {
-thread_local int g_count_hip_error = 0;
-#define CNT_TRY(expr)                    \
-  do {                                   \
-    hipError_t _e = (expr);              \
-    if (_e != hipSuccess) {              \
-      g_count_hip_error = (int)_e;       \
-      st = BEAR_ERR_HIP;                 \
-      goto done;                         \
-    }                                    \
-  } while (0)
+// rocPRIM's two calls: `call(NULL, bytes)` asks for the size of the temporary storage, `call(temp, bytes)` enqueues the work.
+// The caller owns `temp`: it is in use until the stream has been synchronised, and goes where the caller says.
+template <typename Call>
+hipError_t rocprim_run(dev_buf<unsigned char> &temp, Call call) {
+  size_t bytes = 0;
+  hipError_t e = call(nullptr, bytes);
+  if (e != hipSuccess) return e;
+  e = temp.alloc(bytes ? bytes : 8);
+  if (e != hipSuccess) return e;
+  return call(temp.get(), bytes);
+}
 
 // The same pass serves two alphabets (template over bits per letter and row width W; the start marker is W, the stop and
 // the '[' of a context are both W - 1, any other character is W + 1):
@@ -148,61 +151,37 @@ namespace {
 template <int BITS, int W>
 int kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, bear_kmer_sort **out, uint64_t *n_rows_out,
                      hipStream_t s) {
-  int st = BEAR_OK;
-  bear_kmer_sort *h = new (std::nothrow) bear_kmer_sort();
-  if (!h) return BEAR_ERR_NOMEM;
-  h->n_pos = n_pos;
-  h->lag = lag;
-  h->width = W;
-  uint64_t *keys_in = nullptr;
-  uint32_t *vals_in = nullptr, *flags = nullptr;
-  void *temp = nullptr;
-  size_t tb_sort = 0, tb_scan = 0;
+  dev_buf<uint64_t> keys_in, keys;
+  dev_buf<uint32_t> vals_in, vals, rows;
+  dev_buf<unsigned char> temp;
   uint32_t last = 0;
   const unsigned key_bits = (unsigned)(BITS * lag + 1);
-  if (n_pos == 0) {
-    *out = h;
-    return BEAR_OK;
+  if (n_pos) {
+    HIP_TRY(keys_in.alloc(n_pos));
+    HIP_TRY(vals_in.alloc(n_pos));
+    HIP_TRY(keys.alloc(n_pos));
+    HIP_TRY(vals.alloc(n_pos));
+    hipLaunchKernelGGL((cnt_emit_kernel<BITS, W>), dim3(grid_for(n_pos)), dim3(256), 0, s, text, group, n_pos, lag, keys_in.get(), vals_in.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
+      return rocprim::radix_sort_pairs(t, tb, keys_in.get(), keys.get(), vals_in.get(), vals.get(), n_pos, 0u, key_bits, s);
+    }));
+    HIP_TRY(hipStreamSynchronize(s));
+    temp.reset();            // the sort's storage and its input keys go before `rows` comes: the peak of the pass
+    keys_in.reset();
+    dev_buf<uint32_t> &flags = vals_in;   // reuse
+    HIP_TRY(rows.alloc(n_pos));
+    hipLaunchKernelGGL((cnt_flag_kernel<BITS>), dim3(grid_for(n_pos)), dim3(256), 0, s, keys.get(), n_pos, lag, flags.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
+      return rocprim::inclusive_scan(t, tb, flags.get(), rows.get(), n_pos, rocprim::plus<uint32_t>(), s);
+    }));
+    HIP_TRY(hipMemcpyAsync(&last, rows.get() + (n_pos - 1), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
-  CNT_TRY(hipMalloc(&keys_in, n_pos * 8));
-  CNT_TRY(hipMalloc(&vals_in, n_pos * 4));
-  CNT_TRY(hipMalloc(&h->keys, n_pos * 8));
-  CNT_TRY(hipMalloc(&h->vals, n_pos * 4));
-  hipLaunchKernelGGL((cnt_emit_kernel<BITS, W>), dim3(grid_for(n_pos)), dim3(256), 0, s, text, group, n_pos, lag, keys_in, vals_in);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(rocprim::radix_sort_pairs(nullptr, tb_sort, keys_in, h->keys, vals_in, h->vals, n_pos, 0u, key_bits, s));
-  CNT_TRY(hipMalloc(&temp, tb_sort ? tb_sort : 8));
-  CNT_TRY(rocprim::radix_sort_pairs(temp, tb_sort, keys_in, h->keys, vals_in, h->vals, n_pos, 0u, key_bits, s));
-  CNT_TRY(hipStreamSynchronize(s));
-  (void)hipFree(temp);
-  temp = nullptr;
-  (void)hipFree(keys_in);
-  keys_in = nullptr;
-  flags = vals_in;   // reuse
-  vals_in = nullptr;
-  CNT_TRY(hipMalloc(&h->rows, n_pos * 4));
-  hipLaunchKernelGGL((cnt_flag_kernel<BITS>), dim3(grid_for(n_pos)), dim3(256), 0, s, h->keys, n_pos, lag, flags);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(rocprim::inclusive_scan(nullptr, tb_scan, flags, h->rows, n_pos, rocprim::plus<uint32_t>(), s));
-  CNT_TRY(hipMalloc(&temp, tb_scan ? tb_scan : 8));
-  CNT_TRY(rocprim::inclusive_scan(temp, tb_scan, flags, h->rows, n_pos, rocprim::plus<uint32_t>(), s));
-  CNT_TRY(hipMemcpyAsync(&last, h->rows + (n_pos - 1), 4, hipMemcpyDeviceToHost, s));
-  CNT_TRY(hipStreamSynchronize(s));
-  h->n_rows = last;
-done:
-  if (temp) (void)hipFree(temp);
-  if (keys_in) (void)hipFree(keys_in);
-  if (vals_in) (void)hipFree(vals_in);
-  if (flags) (void)hipFree(flags);
-  if (st != BEAR_OK) {
-    if (h->keys) (void)hipFree(h->keys);
-    if (h->vals) (void)hipFree(h->vals);
-    if (h->rows) (void)hipFree(h->rows);
-    delete h;
-    return st;
-  }
-  *out = h;
-  *n_rows_out = h->n_rows;
+  *out = new (std::nothrow) bear_kmer_sort{n_pos, last, lag, W, keys.release(), vals.release(), rows.release()};
+  if (!*out) return BEAR_ERR_NOMEM;
+  *n_rows_out = last;
   return BEAR_OK;
 }
 
@@ -218,7 +197,7 @@ bool sort_args_ok(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int
 
 extern "C" {
 
-int bear_count_last_hip_error(void) { return g_count_hip_error; }
+int bear_count_last_hip_error(void) { return g_last_hip_error; }   // the library's one slot: bear_last_hip_error()
 
 int bear_kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, bear_kmer_sort **out,
                           uint64_t *n_rows_out, void *stream) {
@@ -243,14 +222,14 @@ int bear_kmer_sort_reduce(const bear_kmer_sort *h, int n_groups, uint8_t *kmers,
   if (h->n_rows == 0) return BEAR_OK;
   if (!counts) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(counts, 0, (size_t)n_groups * h->n_rows * (size_t)h->width * 4, s) != hipSuccess) return BEAR_ERR_HIP;
+  HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_groups * h->n_rows * (size_t)h->width * 4, s));
   if (h->width == 5)
     hipLaunchKernelGGL((cnt_scatter_kernel<3, 5>), dim3(grid_for(h->n_pos)), dim3(256), 0, s, h->keys, h->vals, h->rows, h->n_pos,
                        h->n_rows, h->lag, (uint32_t)n_groups, kmers, kmer_code, counts);
   else
     hipLaunchKernelGGL((cnt_scatter_kernel<5, 21>), dim3(grid_for(h->n_pos)), dim3(256), 0, s, h->keys, h->vals, h->rows, h->n_pos,
                        h->n_rows, h->lag, (uint32_t)n_groups, kmers, kmer_code, counts);
-  if (hipGetLastError() != hipSuccess) return BEAR_ERR_HIP;
+  HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
 
@@ -308,32 +287,28 @@ extern "C" int bear_kmer_order_u64(const uint64_t *kmer_code, uint64_t n_rows, i
   // caller-owned scratch: two key arrays, the identity values, rocPRIM's temporary storage (each piece 256-byte aligned)
   const uint64_t keys_b = (n_rows * 8 + 255) & ~255ull, vals_b = (n_rows * 4 + 255) & ~255ull;
   size_t tb = 0;
-  int st = BEAR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_rows)
-    CNT_TRY(rocprim::radix_sort_pairs(nullptr, tb, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
                                       (uint32_t *)nullptr, n_rows, 0u, (unsigned)(3 * lag), s));
-  {
-    const uint64_t need = n_rows ? 2 * keys_b + vals_b + (tb ? tb : 8) : 0;
-    if (!scratch) {            // size query
-      *scratch_bytes = need;
-      return BEAR_OK;
-    }
-    if (n_rows == 0) return BEAR_OK;
-    if (!kmer_code || !perm || *scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 255)) return BEAR_ERR_INVALID_ARG;
-    unsigned char *base = static_cast<unsigned char *>(scratch);
-    unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base);
-    unsigned long long *keys_out = reinterpret_cast<unsigned long long *>(base + keys_b);
-    uint32_t *vals_in = reinterpret_cast<uint32_t *>(base + 2 * keys_b);
-    void *temp = base + 2 * keys_b + vals_b;
-    hipLaunchKernelGGL(order_keys_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, reinterpret_cast<const unsigned long long *>(kmer_code),
-                       n_rows, lag, keys_in, vals_in);
-    CNT_TRY(hipGetLastError());
-    // stream-ordered from here on: the scratch is the caller's, nothing is freed and nothing waits on the host
-    CNT_TRY(rocprim::radix_sort_pairs(temp, tb, keys_in, keys_out, vals_in, perm, n_rows, 0u, (unsigned)(3 * lag), s));
+  const uint64_t need = n_rows ? 2 * keys_b + vals_b + (tb ? tb : 8) : 0;
+  if (!scratch) {            // size query
+    *scratch_bytes = need;
+    return BEAR_OK;
   }
-done:
-  return st;
+  if (n_rows == 0) return BEAR_OK;
+  if (!kmer_code || !perm || *scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 255)) return BEAR_ERR_INVALID_ARG;
+  unsigned char *base = static_cast<unsigned char *>(scratch);
+  unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base);
+  unsigned long long *keys_out = reinterpret_cast<unsigned long long *>(base + keys_b);
+  uint32_t *vals_in = reinterpret_cast<uint32_t *>(base + 2 * keys_b);
+  void *temp = base + 2 * keys_b + vals_b;
+  hipLaunchKernelGGL(order_keys_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, reinterpret_cast<const unsigned long long *>(kmer_code),
+                     n_rows, lag, keys_in, vals_in);
+  HIP_TRY(hipGetLastError());
+  // stream-ordered from here on: the scratch is the caller's, nothing is freed and nothing waits on the host
+  HIP_TRY(rocprim::radix_sort_pairs(temp, tb, keys_in, keys_out, vals_in, perm, n_rows, 0u, (unsigned)(3 * lag), s));
+  return BEAR_OK;
 }
 
 extern "C" int bear_gather_rows(const void *src, const uint32_t *perm, void *dst, uint64_t n_rows, uint32_t row_bytes, void *stream) {
@@ -342,7 +317,8 @@ extern "C" int bear_gather_rows(const void *src, const uint32_t *perm, void *dst
   hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(n_rows * ((row_bytes & 3u) ? row_bytes : row_bytes >> 2))), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const unsigned char *>(src), perm, static_cast<unsigned char *>(dst),
                      n_rows, row_bytes);
-  return hipGetLastError() == hipSuccess ? BEAR_OK : BEAR_ERR_HIP;
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
 }
 
 // ------------------------------------------------------------------ prefix levels of a sorted batch (bear_levels.h, kernels_cnn.h)
@@ -376,20 +352,13 @@ struct rec16_less {
 };
 template <typename T, typename Less>
 int canonical_sort(T *d, uint64_t n, Less less, hipStream_t s) {
-  int st = BEAR_OK;
-  void *temp = nullptr;
-  size_t tb = 0;
-  T *out = nullptr;
-  CNT_TRY(hipMalloc(&out, n * sizeof(T)));
-  CNT_TRY(rocprim::merge_sort(nullptr, tb, d, out, n, less, s));
-  CNT_TRY(hipMalloc(&temp, tb ? tb : 8));
-  CNT_TRY(rocprim::merge_sort(temp, tb, d, out, n, less, s));
-  CNT_TRY(hipMemcpyAsync(d, out, n * sizeof(T), hipMemcpyDeviceToDevice, s));
-  CNT_TRY(hipStreamSynchronize(s));
-done:
-  if (temp) (void)hipFree(temp);
-  if (out) (void)hipFree(out);
-  return st;
+  dev_buf<T> out;
+  dev_buf<unsigned char> temp;
+  HIP_TRY(out.alloc(n));
+  HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) { return rocprim::merge_sort(t, tb, d, out.get(), n, less, s); }));
+  HIP_TRY(hipMemcpyAsync(d, out.get(), n * sizeof(T), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return BEAR_OK;
 }
 }  // namespace
 
@@ -445,66 +414,56 @@ void bear_window_free(bear_window_dev *wt) {
 
 int bear_window_build(const unsigned long long *codes, uint64_t n_rows, int pos, int fw, bear_window_dev *out, hipStream_t s) {
   if (!codes || !out || n_rows == 0 || n_rows > 0xfffffffeull || pos < 0 || fw < 1 || pos + fw > 21) return BEAR_ERR_INVALID_ARG;
-  int st = BEAR_OK;
   const int shift = 3 * pos;
   const unsigned long long mask = (1ull << (3 * fw)) - 1ull;      // (fw <= 21: at most 63 bits)
   unsigned long long fill = 0ull;
   for (int l = 0; l < 21; ++l)
     if (l < pos || l >= pos + fw) fill |= 5ull << (3 * l);
-  unsigned long long *keys_in = nullptr, *keys = nullptr;
-  uint32_t *vals_in = nullptr, *flag = nullptr, *scan = nullptr, n_runs = 0;
-  void *temp = nullptr;
-  size_t tb = 0, tb2 = 0;
+  *out = bear_window_dev{};      // (what a failed build leaves)
   out->pos = pos;
-  out->n = 0;
-  out->codes = nullptr;
-  out->row_of_context = out->perm = out->child_start = nullptr;
-  out->rows = nullptr;
-  out->bytes = 0;
-  CNT_TRY(hipMalloc(&keys_in, n_rows * 8));
-  CNT_TRY(hipMalloc(&keys, n_rows * 8));
-  CNT_TRY(hipMalloc(&vals_in, n_rows * 4));
-  CNT_TRY(hipMalloc(&out->perm, n_rows * 4));
-  CNT_TRY(hipMalloc(&out->row_of_context, n_rows * 4));
-  hipLaunchKernelGGL(window_keys_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, codes, n_rows, shift, mask, keys_in, vals_in);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys, vals_in, out->perm, n_rows, 0u, (unsigned)(3 * fw), s));
-  CNT_TRY(hipMalloc(&temp, tb ? tb : 8));
-  CNT_TRY(rocprim::radix_sort_pairs(temp, tb, keys_in, keys, vals_in, out->perm, n_rows, 0u, (unsigned)(3 * fw), s));   // stable: ties keep row order
-  CNT_TRY(hipStreamSynchronize(s));
-  (void)hipFree(temp);
-  temp = nullptr;
-  (void)hipFree(keys_in);
-  keys_in = nullptr;
+  dev_buf<unsigned long long> keys_in, keys, win_codes;
+  dev_buf<uint32_t> vals_in, scan, perm, row_of_context, child_start;
+  dev_buf<double> rows;
+  dev_buf<unsigned char> temp;
+  uint32_t n_runs = 0;
+  HIP_TRY(keys_in.alloc(n_rows));
+  HIP_TRY(keys.alloc(n_rows));
+  HIP_TRY(vals_in.alloc(n_rows));
+  HIP_TRY(perm.alloc(n_rows));
+  HIP_TRY(row_of_context.alloc(n_rows));
+  hipLaunchKernelGGL(window_keys_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, codes, n_rows, shift, mask, keys_in.get(), vals_in.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {      // stable: ties keep row order
+    return rocprim::radix_sort_pairs(t, tb, keys_in.get(), keys.get(), vals_in.get(), perm.get(), n_rows, 0u, (unsigned)(3 * fw), s);
+  }));
+  HIP_TRY(hipStreamSynchronize(s));
+  temp.reset();            // the sort's storage and its input keys go before `scan` comes: the peak of the build
+  keys_in.reset();
   // runs of equal windows (the flag / scan of the prefix levels, on the sorted keys)
-  flag = vals_in;          // (the unsorted row numbers are no longer needed)
-  vals_in = nullptr;
-  CNT_TRY(hipMalloc(&scan, n_rows * 4));
-  hipLaunchKernelGGL(level_flag_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, keys, n_rows, ~0ull, flag);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(rocprim::inclusive_scan(nullptr, tb2, flag, scan, n_rows, rocprim::plus<uint32_t>(), s));
-  CNT_TRY(hipMalloc(&temp, tb2 ? tb2 : 8));
-  CNT_TRY(rocprim::inclusive_scan(temp, tb2, flag, scan, n_rows, rocprim::plus<uint32_t>(), s));
-  CNT_TRY(hipMemcpyAsync(&n_runs, scan + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  CNT_TRY(hipStreamSynchronize(s));
-  CNT_TRY(hipMalloc(&out->codes, (size_t)n_runs * 8));
-  CNT_TRY(hipMalloc(&out->child_start, ((size_t)n_runs + 1) * 4));
-  CNT_TRY(hipMalloc(&out->rows, (size_t)n_runs * 16 * sizeof(double)));
-  hipLaunchKernelGGL(window_compact_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, keys, out->perm, n_rows, shift, fill, flag, scan, out->codes,
-                     out->child_start, out->row_of_context, (uint64_t)n_runs);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(hipStreamSynchronize(s));
+  dev_buf<uint32_t> &flag = vals_in;          // (the unsorted row numbers are no longer needed)
+  HIP_TRY(scan.alloc(n_rows));
+  hipLaunchKernelGGL(level_flag_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, keys.get(), n_rows, ~0ull, flag.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
+    return rocprim::inclusive_scan(t, tb, flag.get(), scan.get(), n_rows, rocprim::plus<uint32_t>(), s);
+  }));
+  HIP_TRY(hipMemcpyAsync(&n_runs, scan.get() + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(win_codes.alloc(n_runs));
+  HIP_TRY(child_start.alloc((size_t)n_runs + 1));
+  HIP_TRY(rows.alloc((size_t)n_runs * 16));
+  hipLaunchKernelGGL(window_compact_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, keys.get(), perm.get(), n_rows, shift, fill, flag.get(),
+                     scan.get(), win_codes.get(), child_start.get(), row_of_context.get(), (uint64_t)n_runs);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
   out->n = n_runs;
+  out->codes = win_codes.release();
+  out->row_of_context = row_of_context.release();
+  out->perm = perm.release();
+  out->child_start = child_start.release();
+  out->rows = rows.release();
   out->bytes = (uint64_t)n_runs * (8 + 4 + 128) + n_rows * 8;
-done:
-  if (temp) (void)hipFree(temp);
-  if (keys_in) (void)hipFree(keys_in);
-  if (keys) (void)hipFree(keys);
-  if (vals_in) (void)hipFree(vals_in);
-  if (flag) (void)hipFree(flag);
-  if (scan) (void)hipFree(scan);
-  if (st != BEAR_OK) bear_window_free(out);
-  return st;
+  return BEAR_OK;
 }
 
 void bear_level_free(bear_level_dev *lv) {
@@ -523,43 +482,36 @@ void bear_level_free(bear_level_dev *lv) {
 
 int bear_level_build(const unsigned long long *codes_below, uint64_t n_below, int letters, bear_level_dev *out, hipStream_t s) {
   if (!codes_below || !out || n_below == 0 || n_below > 0xfffffffeull || letters < 1 || letters > 21) return BEAR_ERR_INVALID_ARG;
-  int st = BEAR_OK;
   const unsigned long long mask = (1ull << (3 * letters)) - 1ull;
   unsigned long long fill = 0ull;
   for (int l = letters; l < 22 && 3 * l < 64; ++l) fill |= 5ull << (3 * l);     // (bear_pack_kmers_u64 fills positions >= lag the same way)
-  uint32_t *flag = nullptr, *scan = nullptr, n_runs = 0;
-  void *temp = nullptr;
-  size_t tb = 0;
-  out->n = 0;
+  *out = bear_level_dev{};       // (what a failed build leaves)
   out->letters = letters;
-  out->codes = nullptr;
-  out->parent_of_below = nullptr;
-  out->child_start = nullptr;
-  out->rows = nullptr;
-  out->bytes = 0;
-  CNT_TRY(hipMalloc(&flag, n_below * sizeof(uint32_t)));
-  CNT_TRY(hipMalloc(&scan, n_below * sizeof(uint32_t)));
-  hipLaunchKernelGGL(level_flag_kernel, dim3(grid_for(n_below)), dim3(256), 0, s, codes_below, n_below, mask, flag);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(rocprim::inclusive_scan(nullptr, tb, flag, scan, n_below, rocprim::plus<uint32_t>(), s));
-  CNT_TRY(hipMalloc(&temp, tb ? tb : 8));
-  CNT_TRY(rocprim::inclusive_scan(temp, tb, flag, scan, n_below, rocprim::plus<uint32_t>(), s));
-  CNT_TRY(hipMemcpyAsync(&n_runs, scan + (n_below - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  CNT_TRY(hipStreamSynchronize(s));
-  CNT_TRY(hipMalloc(&out->codes, (size_t)n_runs * sizeof(unsigned long long)));
-  CNT_TRY(hipMalloc(&out->child_start, ((size_t)n_runs + 1) * sizeof(uint32_t)));
-  CNT_TRY(hipMalloc(&out->rows, (size_t)n_runs * 16 * sizeof(double)));
-  hipLaunchKernelGGL(level_compact_kernel, dim3(grid_for(n_below)), dim3(256), 0, s, codes_below, n_below, mask, fill, flag, scan, out->codes,
-                     out->child_start, (uint64_t)n_runs);
-  CNT_TRY(hipGetLastError());
-  CNT_TRY(hipStreamSynchronize(s));
+  dev_buf<uint32_t> flag, scan, child_start;
+  dev_buf<unsigned long long> run_codes;
+  dev_buf<double> rows;
+  dev_buf<unsigned char> temp;
+  uint32_t n_runs = 0;
+  HIP_TRY(flag.alloc(n_below));
+  HIP_TRY(scan.alloc(n_below));
+  hipLaunchKernelGGL(level_flag_kernel, dim3(grid_for(n_below)), dim3(256), 0, s, codes_below, n_below, mask, flag.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
+    return rocprim::inclusive_scan(t, tb, flag.get(), scan.get(), n_below, rocprim::plus<uint32_t>(), s);
+  }));
+  HIP_TRY(hipMemcpyAsync(&n_runs, scan.get() + (n_below - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(run_codes.alloc(n_runs));
+  HIP_TRY(child_start.alloc((size_t)n_runs + 1));
+  HIP_TRY(rows.alloc((size_t)n_runs * 16));
+  hipLaunchKernelGGL(level_compact_kernel, dim3(grid_for(n_below)), dim3(256), 0, s, codes_below, n_below, mask, fill, flag.get(), scan.get(),
+                     run_codes.get(), child_start.get(), (uint64_t)n_runs);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
   out->n = n_runs;
-  out->parent_of_below = scan;
-  scan = nullptr;
-done:
-  if (temp) (void)hipFree(temp);
-  if (flag) (void)hipFree(flag);
-  if (scan) (void)hipFree(scan);
-  if (st != BEAR_OK) bear_level_free(out);
-  return st;
+  out->codes = run_codes.release();
+  out->parent_of_below = scan.release();      // (the compaction turned the scan into the parents' rows)
+  out->child_start = child_start.release();
+  out->rows = rows.release();
+  return BEAR_OK;
 }

@@ -263,46 +263,27 @@ int bear_eval_plan_create(bear_ws *ws, const uint32_t *test, const uint32_t *tra
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if ((n_rows && !test) || misaligned(test) || misaligned(train)) return BEAR_ERR_INVALID_ARG;
-  bear_eval_plan *p = new (std::nothrow) bear_eval_plan();
-  if (!p) return BEAR_ERR_NOMEM;
-  memset(p, 0, sizeof(*p));
-  p->device = ws->device;
-  p->n_rows = n_rows;
-  p->test = test;
-  p->train = train;
-  p->n_tiles = (n_rows + EVP_ROWS - 1) / EVP_ROWS;
-  if (p->n_tiles) {
-    // + 1 KiB: the last DMA piece of a tile's lists may be issued for a partial KiB
-    const size_t ibytes = sizeof(uint16_t) * EVP_ITEMS_CAP * (size_t)p->n_tiles + 1024;
-    hipError_t e = hipMalloc(&p->items, ibytes);
-    if (e == hipSuccess) e = hipMalloc(&p->tile_info, sizeof(uint2) * ((size_t)p->n_tiles + 2));
-    if (e == hipSuccess) e = hipMalloc(&p->consts, sizeof(unsigned long long) * EVP_NCONST);
-    if (e == hipSuccess) e = hipMemsetAsync(p->tile_info, 0, sizeof(uint2) * ((size_t)p->n_tiles + 2), static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = hipMemsetAsync(p->consts, 0, sizeof(unsigned long long) * EVP_NCONST, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-      (void)hipFree(p->items);
-      (void)hipFree(p->tile_info);
-      (void)hipFree(p->consts);
-      delete p;
-      g_last_hip_error = (int)e;
-      return e == hipErrorOutOfMemory ? BEAR_ERR_NOMEM : BEAR_ERR_HIP;
-    }
-    const int grid = grid_capped(p->n_tiles, (uint64_t)ws->num_cu * 16);
-    hipLaunchKernelGGL(evp_build_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), test, train, n_rows, p->n_tiles,
-                       p->items, p->tile_info, p->consts);
-    e = hipGetLastError();
-    if (e != hipSuccess) {
-      (void)hipFree(p->items);
-      (void)hipFree(p->tile_info);
-      (void)hipFree(p->consts);
-      delete p;
-      g_last_hip_error = (int)e;
-      return BEAR_ERR_HIP;
-    }
-    p->bytes = ibytes + sizeof(uint2) * ((size_t)p->n_tiles + 2) + sizeof(unsigned long long) * EVP_NCONST;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint64_t n_tiles = (n_rows + EVP_ROWS - 1) / EVP_ROWS;
+  // + 1 KiB: the last DMA piece of a tile's lists may be issued for a partial KiB
+  const size_t n_items = EVP_ITEMS_CAP * (size_t)n_tiles + 1024 / sizeof(uint16_t), n_info = (size_t)n_tiles + 2;
+  dev_buf<uint16_t> items;
+  dev_buf<uint2> tile_info;
+  dev_buf<unsigned long long> consts;
+  if (n_tiles) {
+    HIP_TRY(items.alloc(n_items));
+    HIP_TRY(tile_info.alloc(n_info));
+    HIP_TRY(consts.alloc(EVP_NCONST));
+    HIP_TRY(hipMemsetAsync(tile_info.get(), 0, sizeof(uint2) * n_info, s));
+    HIP_TRY(hipMemsetAsync(consts.get(), 0, sizeof(unsigned long long) * EVP_NCONST, s));
+    const int grid = grid_capped(n_tiles, (uint64_t)ws->num_cu * 16);
+    hipLaunchKernelGGL(evp_build_kernel, dim3(grid), dim3(256), 0, s, test, train, n_rows, n_tiles, items.get(),
+                       tile_info.get(), consts.get());
+    HIP_TRY(hipGetLastError());
   }
-  *out = p;
-  return BEAR_OK;
+  const uint64_t bytes = n_tiles ? sizeof(uint16_t) * n_items + sizeof(uint2) * n_info + sizeof(unsigned long long) * EVP_NCONST : 0;
+  *out = new (std::nothrow) bear_eval_plan{ws->device, n_rows, n_tiles, test, train, items.release(), tile_info.release(), consts.release(), bytes};
+  return *out ? BEAR_OK : BEAR_ERR_NOMEM;
 }
 
 int bear_eval_plan_destroy(bear_eval_plan *plan) {

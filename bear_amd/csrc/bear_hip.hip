@@ -21,8 +21,6 @@
 #define PLN_DBG_ARG
 #endif
 
-thread_local int g_last_hip_error = 0;
-
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -102,6 +100,25 @@ static int ws_setup(bear_ws *ws) {
   return st;
 }
 
+struct ws_deleter {
+  void operator()(bear_ws *ws) const { ws_release(ws); }
+};
+
+// (the workspace's device is current)
+static int ws_create_on(int device, bear_ws **out) {
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  std::unique_ptr<bear_ws, ws_deleter> ws(new (std::nothrow) bear_ws());
+  if (!ws) return BEAR_ERR_NOMEM;
+  ws->device = device;
+  ws->num_cu = prop.multiProcessorCount;
+  ws->max_blocks = ws->num_cu * 8;
+  ws->eval_blocks = ws->num_cu * 8;
+  const int st = ws_setup(ws.get());
+  if (st == BEAR_OK) *out = ws.release();
+  return st;
+}
+
 int bear_ws_create(int device, bear_ws **out) {
   if (!out) return BEAR_ERR_INVALID_ARG;
   *out = nullptr;
@@ -111,27 +128,8 @@ int bear_ws_create(int device, bear_ws **out) {
   int prev = 0;
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  const hipError_t e = hipGetDeviceProperties(&prop, device);
-  bear_ws *ws = e == hipSuccess ? new (std::nothrow) bear_ws() : nullptr;
-  int st = ws ? BEAR_OK : BEAR_ERR_NOMEM;
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    st = BEAR_ERR_HIP;
-  }
-  if (ws) {
-    ws->device = device;
-    ws->num_cu = prop.multiProcessorCount;
-    ws->max_blocks = ws->num_cu * 8;
-    ws->eval_blocks = ws->num_cu * 8;
-    st = ws_setup(ws);
-    if (st != BEAR_OK) {
-      ws_release(ws);
-      ws = nullptr;
-    }
-  }
+  const int st = ws_create_on(device, out);
   (void)hipSetDevice(prev);
-  *out = ws;
   return st;
 }
 
@@ -221,26 +219,242 @@ int bear_dm_ref_f64(bear_ws *ws, const uint32_t *train, const uint32_t *ref, uin
 }
 
 // ------------------------------------------------------------------ plans (struct bear_plan: bear_host.h)
-static void plan_free(bear_plan *p) {
-  if (!p) return;
+// The sorted encoding of the table: tiles, their stream, the global lists.  Goes with the plan, or when a builder finds the table
+// dense (bear_plan_create_auto, bear_plan_create_ref): the histograms are then all the plan keeps.
+#define PLAN_HIST_WORDS (2 * SRT_NKEY + PLN_NBIG + 1)      // (+ the large totals' histogram)
+static void plan_drop_sorted(bear_plan *p) {
   (void)hipFree(p->tiles);
   (void)hipFree(p->stream);
   (void)hipFree(p->heavy_col);
   (void)hipFree(p->heavy_row);
   (void)hipFree(p->heavy_stop);
-  (void)hipFree(p->hist);
+  p->tiles = nullptr;
+  p->stream = nullptr;
+  p->heavy_col = nullptr;
+  p->heavy_row = nullptr;
+  p->heavy_stop = nullptr;
+  p->n_tiles = 0;
+  p->n_heavy[0] = p->n_heavy[1] = p->n_heavy[2] = 0;
+  p->bytes = sizeof(unsigned long long) * PLAN_HIST_WORDS;
+}
+// ... the live lists of a five-column plan
+static void plan_drop_live(bear_plan *p) {
   (void)hipFree(p->live);
-  for (int k = 0; k < p->n_cnn_levels; ++k) bear_level_free(&p->cnn_levels[k]);
-  for (int k = 0; k <= CNN_MAX_LAG; ++k)
-    for (int q = 0; q < p->n_cnn_win[k]; ++q) bear_window_free(&p->cnn_win[k][q]);
-  (void)hipFree(p->live2);
-  (void)hipFree(p->tiles_p);
-  (void)hipFree(p->tiles_u);
+  p->live = nullptr;
+}
+// ... the reference-aware extension (bear_plan_create_ref)
+static void plan_drop_ref(bear_plan *p) {
   (void)hipFree(p->ref_items);
   (void)hipFree(p->hist0_base);
   (void)hipFree(p->heavy0);
   (void)hipFree(p->sum0);
+  p->ref_items = nullptr;
+  p->hist0 = p->hist0_base = nullptr;
+  p->heavy0 = nullptr;
+  p->sum0 = nullptr;
+}
+
+// every family drops the fields it owns (bear_host.h)
+static void plan_free(bear_plan *p) {
+  if (!p) return;
+  plan_drop_sorted(p);
+  plan_drop_live(p);
+  (void)hipFree(p->hist);
+  plan_drop_cnn_levels(p);
+  plan_unpair(p);
+  plan_drop_ref(p);
   delete p;
+}
+struct plan_deleter {
+  void operator()(bear_plan *p) const { plan_free(p); }
+};
+using plan_guard = std::unique_ptr<bear_plan, plan_deleter>;      // holds a plan while it is built: a failed phase just returns
+
+// ---- bear_plan_create, phase by phase.  Each returns a status; what one hands to the next, beyond the plan's own fields:
+struct plan_scan {
+  uint64_t n_quads = 0;
+  dev_buf<uint8_t> quad;              // [3][n_quads] per group of PLN_QUAD contexts: product-path items, large-count cells, large-total rows
+  dev_buf<unsigned long long> cnt;    // [0..2] heavy counts, [3..5] fill cursors, [6..8] sum of all counts, cells that hold one, largest count
+  unsigned long long heavy[3] = {0, 0, 0};      // cnt[0..2] on the host: the sizes of the global lists
+};
+struct plan_cut {
+  dev_buf<pln_tile> tiles;
+  uint64_t n_tiles = 0, off16 = 0;    // off16: 16-byte units of the tiles' stream
+  // + PLN_DESC_PAD zeroed descriptors: the kernels fetch descriptors 32 at a time (1 KiB LDS-DMA pieces)
+  hipError_t alloc_tiles(uint64_t n) {
+    n_tiles = n;
+    return tiles.alloc_zeroed(n + PLN_DESC_PAD);
+  }
+};
+
+// pass A: product-path items per group of 4 contexts, heavy counts, histograms, the table's totals
+static int plan_scan_table(const bear_ws *ws, bear_plan *p, plan_scan &sc) {
+  sc.n_quads = (p->n_rows + PLN_QUAD - 1) / PLN_QUAD;
+  HIP_TRY(sc.quad.alloc(3 * sc.n_quads));
+  HIP_TRY(sc.cnt.alloc_zeroed(9));
+  const int grid = grid_capped((sc.n_quads + 255) / 256, (uint64_t)ws->num_cu * 8);
+  hipLaunchKernelGGL(plan_scan_kernel, dim3(grid), dim3(256), 0, 0, p->counts, p->n_rows, p->ncol, sc.quad.get(), sc.cnt.get(), p->hist);
+  HIP_TRY(hipGetLastError());
+  unsigned long long h_total[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpy(sc.heavy, sc.cnt.get(), sizeof(sc.heavy), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h_total, sc.cnt.get() + 6, sizeof(h_total), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 3; ++k) p->count_total[k] = p->count_bound[k] = (double)h_total[k];
+  return BEAR_OK;
+}
+
+// The tiles: greedy cut so that a tile holds <= PLN_NI items and <= PLN_RMAX contexts.  Either cut uses up the per-group counters.
+// BEAR_PLAN_CUT=host: the sequential host loop over them (the definition; used by the tests to compare)
+static int cut_on_host(const bear_plan *p, plan_scan &sc, plan_cut &cut) {
+  const uint64_t n_quads = sc.n_quads, n_rows = p->n_rows;
+  std::unique_ptr<uint8_t[]> h_quad(new (std::nothrow) uint8_t[3 * n_quads]);
+  if (!h_quad) return hip_status(hipErrorOutOfMemory);
+  HIP_TRY(hipMemcpy(h_quad.get(), sc.quad.get(), 3 * n_quads, hipMemcpyDeviceToHost));
+  std::vector<pln_tile> tiles;
+  uint64_t q = 0, off16 = 0;
+  while (q < n_quads) {
+    uint32_t items = 0, rows = 0, hcol = 0, hrow = 0;
+    const uint64_t q0 = q;
+    while (q < n_quads && rows + PLN_QUAD <= PLN_RMAX && items + h_quad[q] <= PLN_NI_CUT) {
+      items += h_quad[q];
+      hcol += h_quad[n_quads + q];
+      hrow += h_quad[2 * n_quads + q];
+      rows += PLN_QUAD;
+      ++q;
+    }
+    pln_tile ti;
+    memset(&ti, 0, sizeof(ti));
+    ti.row0 = q0 * PLN_QUAD;
+    if (ti.row0 + rows > n_rows) rows = (uint32_t)(n_rows - ti.row0);  // ragged end of the table
+    // large-count items evaluated inside the tile (their rows are in LDS anyway); the surplus of very dense
+    // tiles goes to the global lists.  Mode R needs no row data for large totals: they stay global.
+    const uint32_t hc = hcol < PLN_HCAP ? hcol : PLN_HCAP;
+    const uint32_t hr = p->ncol == 5 ? (hrow < PLN_HCAP ? hrow : PLN_HCAP) : 0u;
+    ti.rows_items = (rows << 16) | items;
+    ti.off16 = (uint32_t)off16;
+    ti.hc_hr = (hc << 16) | hr;
+    ti.blk16 = pln_block_layout(rows, items, hc, hr).end / 16;
+    off16 += ti.blk16;
+    if (off16 > 0xffffffffull) return hip_status(hipErrorOutOfMemory);     // plan stream beyond 2^32 16-byte units
+    tiles.push_back(ti);
+  }
+  cut.off16 = off16;
+  h_quad.reset();
+  sc.quad.reset();
+  HIP_TRY(cut.alloc_tiles(tiles.size()));
+  HIP_TRY(hipMemcpy(cut.tiles.get(), tiles.data(), sizeof(pln_tile) * tiles.size(), hipMemcpyHostToDevice));
+  return BEAR_OK;
+}
+
+// ... the same cut on the device (plan_cut_*_kernel): no per-group counters through the host
+static int cut_on_device(const bear_plan *p, plan_scan &sc, plan_cut &cut) {
+  const uint64_t n_quads = sc.n_quads;
+  const uint32_t chunk = plan_cut_chunk(n_quads);
+  const uint64_t n_chunks = (n_quads + chunk - 1) / chunk;
+  dev_buf<uint32_t> walk;
+  dev_buf<uint16_t> step;              // [n_quads] length of the tile that starts at a group
+  dev_buf<uint64_t> entry;             // [n_chunks] entry | [n_chunks] base
+  dev_buf<unsigned long long> meta;
+  unsigned long long h_meta[3] = {0, 0, 0};
+  HIP_TRY(walk.alloc(n_chunks * PLN_CUT_SPAN));
+  HIP_TRY(step.alloc(n_quads));
+  HIP_TRY(entry.alloc(2 * n_chunks));
+  HIP_TRY(meta.alloc_zeroed(3));
+  const uint64_t wb = (n_chunks * PLN_CUT_SPAN + 255) / 256;
+  const unsigned cb = (unsigned)((n_chunks + 255) / 256);
+  hipLaunchKernelGGL(plan_cut_step_kernel, dim3(cb), dim3(256), 0, 0, sc.quad.get(), n_quads, n_chunks, chunk, step.get());
+  hipLaunchKernelGGL(plan_cut_walk_kernel, dim3((unsigned)wb), dim3(256), 0, 0, step.get(), n_quads, n_chunks, chunk, walk.get());
+  hipLaunchKernelGGL(plan_cut_chain_kernel, dim3(1), dim3(1), 0, 0, walk.get(), n_chunks, chunk, entry.get(), entry.get() + n_chunks,
+                     meta.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(h_meta, meta.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_TRY(cut.alloc_tiles(h_meta[0]));
+  hipLaunchKernelGGL(plan_cut_write_kernel, dim3(cb), dim3(256), 0, 0, sc.quad.get(), n_quads, p->n_rows, p->ncol, n_chunks, chunk, entry.get(),
+                     entry.get() + n_chunks, cut.tiles.get());
+  hipLaunchKernelGGL(plan_cut_offsets_kernel, dim3(1), dim3(1024), 0, 0, cut.tiles.get(), cut.n_tiles, meta.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(h_meta, meta.get(), sizeof(h_meta), hipMemcpyDeviceToHost));
+  if (h_meta[2]) return hip_status(hipErrorOutOfMemory);     // plan stream beyond 2^32 16-byte units
+  cut.off16 = h_meta[1];
+  sc.quad.reset();
+  return BEAR_OK;
+}
+
+// pass B: the tiles' stream and the global lists of what a tile could not keep (through the cursors cnt[3..5])
+static int plan_fill(const bear_ws *ws, bear_plan *p, const plan_scan &sc, uint64_t stream_bytes) {
+  HIP_TRY(hipMalloc(&p->stream, stream_bytes));
+  HIP_TRY(hipMemset(p->stream, 0, stream_bytes));
+  if (sc.heavy[0]) HIP_TRY(hipMalloc(&p->heavy_col, sizeof(pln_heavy_col) * sc.heavy[0]));
+  if (sc.heavy[1]) HIP_TRY(hipMalloc(&p->heavy_row, sizeof(pln_heavy_row) * sc.heavy[1]));
+  if (sc.heavy[2]) HIP_TRY(hipMalloc(&p->heavy_stop, sizeof(uint64_t) * sc.heavy[2]));
+  const int grid = grid_capped(p->n_tiles, (uint64_t)ws->num_cu * 2);
+  hipLaunchKernelGGL(plan_fill_kernel, dim3(grid), dim3(1024), 0, 0, p->counts, p->n_rows, p->ncol, p->tiles, p->n_tiles, p->stream,
+                     p->heavy_col, p->heavy_row, p->heavy_stop, sc.cnt.get() + 3);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// five-column plans: per-tile lists of the contexts that hold counts
+static int plan_live_lists(const bear_ws *ws, bear_plan *p, uint64_t live_bytes) {
+  HIP_TRY(hipMalloc(&p->live, live_bytes));
+  HIP_TRY(hipMemset(p->live, 0, live_bytes));
+  const int grid = grid_capped(p->n_tiles, (uint64_t)ws->num_cu * 2);
+  hipLaunchKernelGGL(plan_live_kernel, dim3(grid), dim3(1024), 0, 0, p->tiles, p->n_tiles, p->stream, p->live);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// The global lists were filled through atomic cursors, in whatever order the blocks got there: into row order (bear_levels.h).
+// Neighbouring threads of the kernels that walk them then read neighbouring prior cells and -- the gradient fix-up -- update
+// neighbouring gradient cells without atomics; and the lists are the same bits in every build of the plan.
+// (lists of a few thousand entries -- every sparse k-mer table -- are left as they are: nothing to coalesce, and the sorts' set-up
+// would triple the plan's build time; the deterministic build sorts them all)
+static int plan_order_lists(bear_plan *p) {
+#ifdef BEAR_DET_BUILD
+  const uint64_t sort_from = 2;
+#else
+  const uint64_t sort_from = 1u << 16;
+#endif
+  int st = p->n_heavy[0] >= sort_from ? bear_canonical_order(p->heavy_col, p->n_heavy[0], 16, 0) : BEAR_OK;
+  if (st == BEAR_OK && p->n_heavy[1] >= sort_from) st = bear_canonical_order(p->heavy_row, p->n_heavy[1], 16, 0);
+  if (st == BEAR_OK && p->n_heavy[2] >= sort_from) st = bear_canonical_order(p->heavy_stop, p->n_heavy[2], 8, 0);
+  return st;
+}
+
+// five-column plans: rows with a total of 1..SRT_CL (histogram) + rows with a larger one
+static int plan_count_live_rows(bear_plan *p, const plan_scan &sc) {
+  unsigned long long h_hist[SRT_NKEY];
+  HIP_TRY(hipMemcpy(h_hist, p->hist, sizeof(h_hist), hipMemcpyDeviceToHost));
+  unsigned long long live_rows = sc.heavy[1];
+  for (int k = 0; k < SRT_NKEY; ++k) live_rows += h_hist[k];
+  p->n_live_rows = live_rows;
+  return BEAR_OK;
+}
+
+static int plan_build(const bear_ws *ws, bear_plan *p) {
+  plan_scan sc;
+  plan_cut cut;
+  int st = plan_scan_table(ws, p, sc);
+  if (st != BEAR_OK) return st;
+  const char *cut_env = getenv("BEAR_PLAN_CUT");
+  st = cut_env && cut_env[0] == 'h' ? cut_on_host(p, sc, cut) : cut_on_device(p, sc, cut);
+  if (st != BEAR_OK) return st;
+  p->tiles = cut.tiles.release();
+  p->n_tiles = cut.n_tiles;
+  const uint64_t stream_bytes = cut.off16 * 16 + 1024;  // slack: a DMA piece may be issued for a partial KiB
+  const uint64_t live_bytes = p->ncol == 5 ? sizeof(uint16_t) * PLN_LIVE_STRIDE * (p->n_tiles + 1) : 0;   // + 1: DMA pieces are whole KiB
+  st = plan_fill(ws, p, sc, stream_bytes);
+  if (st == BEAR_OK && live_bytes) st = plan_live_lists(ws, p, live_bytes);
+  if (st != BEAR_OK) return st;
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long h_used[3] = {0, 0, 0};  // entries that actually went to the global lists
+  HIP_TRY(hipMemcpy(h_used, sc.cnt.get() + 3, sizeof(h_used), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 3; ++k) p->n_heavy[k] = h_used[k];
+  st = plan_order_lists(p);
+  p->n_live_rows = p->n_rows;
+  if (st == BEAR_OK && p->ncol == 5) st = plan_count_live_rows(p, sc);
+  p->bytes = stream_bytes + live_bytes + sizeof(pln_tile) * p->n_tiles + sizeof(pln_heavy_col) * sc.heavy[0] +
+             sizeof(pln_heavy_row) * sc.heavy[1] + sizeof(uint64_t) * sc.heavy[2];
+  return st;
 }
 
 int bear_plan_create(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, int ncol, bear_plan **out) {
@@ -249,191 +463,18 @@ int bear_plan_create(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, int n
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   if ((ncol != 4 && ncol != 5) || (n_rows && !counts) || misaligned(counts)) return BEAR_ERR_INVALID_ARG;
-  bear_plan *p = new (std::nothrow) bear_plan();
+  plan_guard p(new (std::nothrow) bear_plan());
   if (!p) return BEAR_ERR_NOMEM;
-  memset(p, 0, sizeof(*p));
+  memset(p.get(), 0, sizeof(bear_plan));
   p->device = ws->device;
   p->ncol = ncol;
   p->n_rows = n_rows;
   p->counts = counts;
-  hipError_t e = hipMalloc(&p->hist, sizeof(unsigned long long) * (2 * SRT_NKEY + PLN_NBIG + 1));     // (+ the large totals' histogram)
-  if (e == hipSuccess) e = hipMemset(p->hist, 0, sizeof(unsigned long long) * (2 * SRT_NKEY + PLN_NBIG + 1));
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    plan_free(p);
-    return BEAR_ERR_HIP;
-  }
-  if (n_rows == 0) {
-    *out = p;
-    return BEAR_OK;
-  }
-  // ---- pass A: product-path items per group of 4 contexts, heavy counts, histograms
-  const uint64_t n_quads = (n_rows + PLN_QUAD - 1) / PLN_QUAD;
-  uint8_t *d_quad = nullptr, *h_quad = nullptr;
-  unsigned long long *d_cnt = nullptr;  // [0..2] heavy counts, [3..5] fill cursors, [6..8] sum of all counts, cells that hold one, largest count
-  std::vector<pln_tile> tiles;
-  e = hipMalloc(&d_quad, 3 * n_quads);
-  if (e == hipSuccess) e = hipMalloc(&d_cnt, sizeof(unsigned long long) * 9);
-  if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * 9);
-  if (e == hipSuccess) {
-    const int grid = grid_capped((n_quads + 255) / 256, (uint64_t)ws->num_cu * 8);
-    hipLaunchKernelGGL(plan_scan_kernel, dim3(grid), dim3(256), 0, 0, counts, n_rows, ncol, d_quad, d_cnt, p->hist);
-    e = hipGetLastError();
-  }
-  unsigned long long h_cnt[3] = {0, 0, 0}, h_total[3] = {0, 0, 0};
-  if (e == hipSuccess) e = hipMemcpy(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(h_total, d_cnt + 6, sizeof(h_total), hipMemcpyDeviceToHost);
-  for (int k = 0; k < 3; ++k) p->count_total[k] = p->count_bound[k] = (double)h_total[k];
-  // ---- tiles: greedy cut so that a tile holds <= PLN_NI items and <= PLN_RMAX contexts -- on the device (plan_cut_*_kernel);
-  // BEAR_PLAN_CUT=host keeps the sequential host loop over the per-group counters (the definition; used by the tests to compare)
-  uint64_t off16 = 0, n_tiles = 0;
-  const char *cut_env = getenv("BEAR_PLAN_CUT");
-  const bool host_cut = cut_env && cut_env[0] == 'h';
-  if (e == hipSuccess && host_cut) {
-    h_quad = (uint8_t *)malloc(3 * n_quads);
-    if (!h_quad) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMemcpy(h_quad, d_quad, 3 * n_quads, hipMemcpyDeviceToHost);
-  }
-  if (e == hipSuccess && host_cut) {
-    uint64_t q = 0;
-    while (q < n_quads) {
-      uint32_t items = 0, rows = 0, hcol = 0, hrow = 0;
-      const uint64_t q0 = q;
-      while (q < n_quads && rows + PLN_QUAD <= PLN_RMAX && items + h_quad[q] <= PLN_NI_CUT) {
-        items += h_quad[q];
-        hcol += h_quad[n_quads + q];
-        hrow += h_quad[2 * n_quads + q];
-        rows += PLN_QUAD;
-        ++q;
-      }
-      pln_tile ti;
-      memset(&ti, 0, sizeof(ti));
-      ti.row0 = q0 * PLN_QUAD;
-      if (ti.row0 + rows > n_rows) rows = (uint32_t)(n_rows - ti.row0);  // ragged end of the table
-      // large-count items evaluated inside the tile (their rows are in LDS anyway); the surplus of very dense
-      // tiles goes to the global lists.  Mode R needs no row data for large totals: they stay global.
-      const uint32_t hc = hcol < PLN_HCAP ? hcol : PLN_HCAP;
-      const uint32_t hr = ncol == 5 ? (hrow < PLN_HCAP ? hrow : PLN_HCAP) : 0u;
-      ti.rows_items = (rows << 16) | items;
-      ti.off16 = (uint32_t)off16;
-      ti.hc_hr = (hc << 16) | hr;
-      ti.blk16 = pln_block_layout(rows, items, hc, hr).end / 16;
-      off16 += ti.blk16;
-      if (off16 > 0xffffffffull) {
-        e = hipErrorOutOfMemory;
-        break;
-      }
-      tiles.push_back(ti);
-    }
-    n_tiles = tiles.size();
-  }
-  free(h_quad);
-  if (e == hipSuccess && !host_cut) {
-    const uint32_t chunk = plan_cut_chunk(n_quads);
-    const uint64_t n_chunks = (n_quads + chunk - 1) / chunk;
-    uint32_t *d_walk = nullptr;
-    uint16_t *d_step = nullptr;            // [n_quads] length of the tile that starts at a group
-    uint64_t *d_entry = nullptr;           // [n_chunks] entry | [n_chunks] base
-    unsigned long long *d_meta = nullptr, h_meta[3] = {0, 0, 0};
-    e = hipMalloc(&d_walk, sizeof(uint32_t) * n_chunks * PLN_CUT_SPAN);
-    if (e == hipSuccess) e = hipMalloc(&d_step, sizeof(uint16_t) * n_quads);
-    if (e == hipSuccess) e = hipMalloc(&d_entry, sizeof(uint64_t) * 2 * n_chunks);
-    if (e == hipSuccess) e = hipMalloc(&d_meta, sizeof(h_meta));
-    if (e == hipSuccess) e = hipMemset(d_meta, 0, sizeof(h_meta));
-    if (e == hipSuccess) {
-      const uint64_t wb = (n_chunks * PLN_CUT_SPAN + 255) / 256;
-      hipLaunchKernelGGL(plan_cut_step_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, 0, d_quad, n_quads, n_chunks, chunk, d_step);
-      hipLaunchKernelGGL(plan_cut_walk_kernel, dim3((unsigned)wb), dim3(256), 0, 0, d_step, n_quads, n_chunks, chunk, d_walk);
-      hipLaunchKernelGGL(plan_cut_chain_kernel, dim3(1), dim3(1), 0, 0, d_walk, n_chunks, chunk, d_entry, d_entry + n_chunks, d_meta);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h_meta, d_meta, sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    n_tiles = h_meta[0];
-    // + PLN_DESC_PAD zeroed descriptors: the kernels fetch descriptors 32 at a time (1 KiB LDS-DMA pieces)
-    if (e == hipSuccess) e = hipMalloc(&p->tiles, sizeof(pln_tile) * (n_tiles + PLN_DESC_PAD));
-    if (e == hipSuccess) e = hipMemset(p->tiles, 0, sizeof(pln_tile) * (n_tiles + PLN_DESC_PAD));
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(plan_cut_write_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, 0, d_quad, n_quads, n_rows, ncol,
-                         n_chunks, chunk, d_entry, d_entry + n_chunks, p->tiles);
-      hipLaunchKernelGGL(plan_cut_offsets_kernel, dim3(1), dim3(1024), 0, 0, p->tiles, n_tiles, d_meta);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h_meta, d_meta, sizeof(h_meta), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_meta[2]) e = hipErrorOutOfMemory;     // plan stream beyond 2^32 16-byte units
-    off16 = h_meta[1];
-    (void)hipFree(d_walk);
-    (void)hipFree(d_step);
-    (void)hipFree(d_entry);
-    (void)hipFree(d_meta);
-  }
-  (void)hipFree(d_quad);
-  p->n_tiles = n_tiles;
-  const uint64_t stream_bytes = off16 * 16 + 1024;  // slack: a DMA piece may be issued for a partial KiB
-  for (int k = 0; k < 3; ++k) p->n_heavy[k] = h_cnt[k];
-  if (host_cut) {   // + PLN_DESC_PAD zeroed descriptors: the kernels fetch descriptors 32 at a time (1 KiB LDS-DMA pieces)
-    if (e == hipSuccess) e = hipMalloc(&p->tiles, sizeof(pln_tile) * (tiles.size() + PLN_DESC_PAD));
-    if (e == hipSuccess) e = hipMemset(p->tiles, 0, sizeof(pln_tile) * (tiles.size() + PLN_DESC_PAD));
-    if (e == hipSuccess) e = hipMemcpy(p->tiles, tiles.data(), sizeof(pln_tile) * tiles.size(), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc(&p->stream, stream_bytes);
-  if (e == hipSuccess) e = hipMemset(p->stream, 0, stream_bytes);
-  if (e == hipSuccess && h_cnt[0]) e = hipMalloc(&p->heavy_col, sizeof(pln_heavy_col) * h_cnt[0]);
-  if (e == hipSuccess && h_cnt[1]) e = hipMalloc(&p->heavy_row, sizeof(pln_heavy_row) * h_cnt[1]);
-  if (e == hipSuccess && h_cnt[2]) e = hipMalloc(&p->heavy_stop, sizeof(uint64_t) * h_cnt[2]);
-  if (e == hipSuccess) {
-    const uint64_t nt = n_tiles;
-    const int grid = grid_capped(nt, (uint64_t)ws->num_cu * 2);
-    hipLaunchKernelGGL(plan_fill_kernel, dim3(grid), dim3(1024), 0, 0, counts, n_rows, ncol, p->tiles, nt, p->stream,
-                       p->heavy_col, p->heavy_row, p->heavy_stop, d_cnt + 3);
-    e = hipGetLastError();
-  }
-  const uint64_t live_bytes = ncol == 5 ? sizeof(uint16_t) * PLN_LIVE_STRIDE * (n_tiles + 1) : 0;   // + 1: DMA pieces are whole KiB
-  if (e == hipSuccess && live_bytes) e = hipMalloc(&p->live, live_bytes);
-  if (e == hipSuccess && live_bytes) e = hipMemset(p->live, 0, live_bytes);
-  if (e == hipSuccess && live_bytes) {
-    const uint64_t nt = n_tiles;
-    const int grid = grid_capped(nt, (uint64_t)ws->num_cu * 2);
-    hipLaunchKernelGGL(plan_live_kernel, dim3(grid), dim3(1024), 0, 0, p->tiles, nt, p->stream, p->live);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  unsigned long long h_used[3] = {0, 0, 0};  // entries that actually went to the global lists
-  if (e == hipSuccess) e = hipMemcpy(h_used, d_cnt + 3, sizeof(h_used), hipMemcpyDeviceToHost);
-  for (int k = 0; k < 3; ++k) p->n_heavy[k] = h_used[k];
-  // The global lists were filled through atomic cursors, in whatever order the blocks got there: into row order (bear_levels.h).
-  // Neighbouring threads of the kernels that walk them then read neighbouring prior cells and -- the gradient fix-up -- update
-  // neighbouring gradient cells without atomics; and the lists are the same bits in every build of the plan.
-  // (lists of a few thousand entries -- every sparse k-mer table -- are left as they are: nothing to coalesce, and the sorts' set-up
-  // would triple the plan's build time; the deterministic build sorts them all)
-#ifdef BEAR_DET_BUILD
-  const uint64_t sort_from = 2;
-#else
-  const uint64_t sort_from = 1u << 16;
-#endif
-  if (e == hipSuccess) {
-    int cst = h_used[0] >= sort_from ? bear_canonical_order(p->heavy_col, h_used[0], 16, 0) : BEAR_OK;
-    if (cst == BEAR_OK && h_used[1] >= sort_from) cst = bear_canonical_order(p->heavy_row, h_used[1], 16, 0);
-    if (cst == BEAR_OK && h_used[2] >= sort_from) cst = bear_canonical_order(p->heavy_stop, h_used[2], 8, 0);
-    if (cst != BEAR_OK) e = cst == BEAR_ERR_NOMEM ? hipErrorOutOfMemory : hipErrorUnknown;
-  }
-  p->n_live_rows = n_rows;
-  if (e == hipSuccess && ncol == 5) {        // rows with a total of 1..SRT_CL (histogram) + rows with a larger one
-    unsigned long long h_hist[SRT_NKEY];
-    e = hipMemcpy(h_hist, p->hist, sizeof(h_hist), hipMemcpyDeviceToHost);
-    unsigned long long live_rows = h_cnt[1];
-    for (int k = 0; k < SRT_NKEY; ++k) live_rows += h_hist[k];
-    p->n_live_rows = live_rows;
-  }
-  (void)hipFree(d_cnt);
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    plan_free(p);
-    return e == hipErrorOutOfMemory ? BEAR_ERR_NOMEM : BEAR_ERR_HIP;
-  }
-  p->bytes = stream_bytes + live_bytes + sizeof(pln_tile) * n_tiles + sizeof(pln_heavy_col) * h_cnt[0] +
-             sizeof(pln_heavy_row) * h_cnt[1] + sizeof(uint64_t) * h_cnt[2];
-  *out = p;
-  return BEAR_OK;
+  HIP_TRY(hipMalloc(&p->hist, sizeof(unsigned long long) * PLAN_HIST_WORDS));
+  HIP_TRY(hipMemset(p->hist, 0, sizeof(unsigned long long) * PLAN_HIST_WORDS));
+  if (n_rows) st = plan_build(ws, p.get());
+  if (st == BEAR_OK) *out = p.release();
+  return st;
 }
 
 int bear_plan_destroy(bear_plan *plan) {
@@ -460,22 +501,9 @@ int bear_plan_create_auto(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, 
   // large-count items): a table of large counts is all list
   const double cells = p->count_total[1], listed = (double)p->n_heavy[0];
   if (!(cells > 0.0) || listed * 2.0 <= cells) return BEAR_OK;
-  (void)hipFree(p->tiles);
-  (void)hipFree(p->stream);
-  (void)hipFree(p->heavy_col);
-  (void)hipFree(p->heavy_row);
-  (void)hipFree(p->heavy_stop);
-  (void)hipFree(p->live);
-  p->tiles = nullptr;
-  p->stream = nullptr;
-  p->heavy_col = nullptr;
-  p->heavy_row = nullptr;
-  p->heavy_stop = nullptr;
-  p->live = nullptr;
-  p->n_tiles = 0;
-  p->n_heavy[0] = p->n_heavy[1] = p->n_heavy[2] = 0;
+  plan_drop_sorted(p);             // (the histograms stay: nothing else does)
+  plan_drop_live(p);
   p->ncol = PLAN_ROWS;
-  p->bytes = sizeof(unsigned long long) * (2 * SRT_NKEY + PLN_NBIG + 1);      // (the histograms stay: nothing else does)
   if (rowwise) *rowwise = 1;
   return BEAR_OK;
 }
@@ -506,10 +534,7 @@ int bear_plan_tile_info(const bear_plan *plan, uint64_t first, uint64_t count, u
   (void)hipSetDevice(plan->device);
   const hipError_t e = hipMemcpy(h.data(), plan->tiles + first, sizeof(pln_tile) * count, hipMemcpyDeviceToHost);
   (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    return BEAR_ERR_HIP;
-  }
+  HIP_TRY(e);
   for (uint64_t k = 0; k < count; ++k) {
     row0[k] = h[k].row0;
     rows[k] = h[k].rows_items >> 16;
@@ -523,77 +548,58 @@ int bear_plan_create_ref(bear_ws *ws, const uint32_t *train, const uint32_t *ref
   if (!out) return BEAR_ERR_INVALID_ARG;
   *out = nullptr;
   if ((n_rows && !ref) || misaligned(ref)) return BEAR_ERR_INVALID_ARG;
-  bear_plan *p = nullptr;
-  int st = bear_plan_create(ws, train, n_rows, 4, &p);   // tiles, histograms of totals / stop counts, heavy lists
+  bear_plan *created = nullptr;
+  int st = bear_plan_create(ws, train, n_rows, 4, &created);   // tiles, histograms of totals / stop counts, heavy lists
   if (st != BEAR_OK) return st;
+  plan_guard p(created);
   p->ref = ref;
   // a table of large counts (more than half of its cells beyond the sorted encoding's tiles: bear_plan_create_auto's test) keeps
   // nothing per item: the mode-R step then streams the training and reference rows, a context per thread (dm_ref_rows_kernel)
   if (p->count_total[1] > 0.0 && (double)p->n_heavy[0] * 2.0 > p->count_total[1]) {
-    (void)hipFree(p->tiles);
-    (void)hipFree(p->stream);
-    (void)hipFree(p->heavy_col);
-    (void)hipFree(p->heavy_row);
-    (void)hipFree(p->heavy_stop);
-    p->tiles = nullptr;
-    p->stream = nullptr;
-    p->heavy_col = nullptr;
-    p->heavy_row = nullptr;
-    p->heavy_stop = nullptr;
-    p->n_tiles = 0;
-    p->n_heavy[0] = p->n_heavy[1] = p->n_heavy[2] = 0;
+    plan_drop_sorted(p.get());
     p->rows_ref = 1;
-    p->bytes = sizeof(unsigned long long) * (2 * SRT_NKEY + PLN_NBIG + 1);
-    *out = p;
+    *out = p.release();
     return BEAR_OK;
   }
-  unsigned long long *d_meta = nullptr;   // [0..31] bucket sizes / cursors, [32..63] hist0, [64] n_heavy0
-  hipError_t e = hipMalloc(&d_meta, sizeof(unsigned long long) * 72);
-  if (e == hipSuccess) e = hipMemset(d_meta, 0, sizeof(unsigned long long) * 72);
-  if (e == hipSuccess) e = hipMalloc(&p->sum0, sizeof(double));
-  if (e == hipSuccess) e = hipMemset(p->sum0, 0, sizeof(double));
-  p->hist0_base = d_meta;
+  HIP_TRY(hipMalloc(&p->hist0_base, sizeof(unsigned long long) * 72));
+  unsigned long long *d_meta = p->hist0_base;   // [0..31] bucket sizes / cursors, [32..63] hist0, [64] n_heavy0
+  HIP_TRY(hipMemset(d_meta, 0, sizeof(unsigned long long) * 72));
+  HIP_TRY(hipMalloc(&p->sum0, sizeof(double)));
+  HIP_TRY(hipMemset(p->sum0, 0, sizeof(double)));
   unsigned long long h_meta[72];
   memset(h_meta, 0, sizeof(h_meta));
   const int grid = grid_capped((n_rows + 1023) / 1024, (uint64_t)ws->num_cu * 8);
-  if (e == hipSuccess && n_rows) {
+  if (n_rows) {
     hipLaunchKernelGGL(rpl_build_kernel, dim3(grid), dim3(256), 0, 0, train, ref, n_rows, 0, d_meta, d_meta + 32, d_meta + 64, p->sum0,
                        static_cast<rpl_item *>(nullptr), static_cast<uint32_t *>(nullptr));
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(h_meta, d_meta, sizeof(h_meta), hipMemcpyDeviceToHost);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h_meta, d_meta, sizeof(h_meta), hipMemcpyDeviceToHost));
   }
-  if (e == hipSuccess) {
-    unsigned long long run = 0, cur[RPL_NKEY];
-    for (int k = 0; k < RPL_NKEY; ++k) {
-      cur[k] = run;
-      run += h_meta[k];
-    }
-    p->n_ref_items = run;
-    p->n_heavy0 = h_meta[64];
-    if (run) e = hipMalloc(&p->ref_items, sizeof(rpl_item) * run);
-    if (e == hipSuccess && p->n_heavy0) e = hipMalloc(&p->heavy0, sizeof(uint32_t) * p->n_heavy0);
-    if (e == hipSuccess) e = hipMemcpy(d_meta, cur, sizeof(cur), hipMemcpyHostToDevice);      // sizes -> cursors
-    if (e == hipSuccess) e = hipMemset(d_meta + 64, 0, sizeof(unsigned long long));
-    if (e == hipSuccess && n_rows && (run || p->n_heavy0)) {
-      hipLaunchKernelGGL(rpl_build_kernel, dim3(grid), dim3(256), 0, 0, train, ref, n_rows, 1, d_meta, d_meta + 32, d_meta + 64, p->sum0,
-                         p->ref_items, p->heavy0);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+  unsigned long long run = 0, cur[RPL_NKEY];
+  for (int k = 0; k < RPL_NKEY; ++k) {
+    cur[k] = run;
+    run += h_meta[k];
+  }
+  p->n_ref_items = run;
+  p->n_heavy0 = h_meta[64];
+  if (run) HIP_TRY(hipMalloc(&p->ref_items, sizeof(rpl_item) * run));
+  if (p->n_heavy0) HIP_TRY(hipMalloc(&p->heavy0, sizeof(uint32_t) * p->n_heavy0));
+  HIP_TRY(hipMemcpy(d_meta, cur, sizeof(cur), hipMemcpyHostToDevice));      // sizes -> cursors
+  HIP_TRY(hipMemset(d_meta + 64, 0, sizeof(unsigned long long)));
+  if (n_rows && (run || p->n_heavy0)) {
+    hipLaunchKernelGGL(rpl_build_kernel, dim3(grid), dim3(256), 0, 0, train, ref, n_rows, 1, d_meta, d_meta + 32, d_meta + 64, p->sum0,
+                       p->ref_items, p->heavy0);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipDeviceSynchronize());
 #ifdef BEAR_DET_BUILD      // the records of a bucket stand in the order of the blocks' cursor bumps: canonical order per bucket
-    for (int k = 0; k < RPL_NKEY && e == hipSuccess; ++k)
-      if (bear_canonical_order(p->ref_items + cur[k], h_meta[k], 16, 0) != BEAR_OK) e = hipErrorUnknown;
-    if (e == hipSuccess && bear_canonical_order(p->heavy0, p->n_heavy0, 4, 0) != BEAR_OK) e = hipErrorUnknown;
+  for (int k = 0; k < RPL_NKEY && st == BEAR_OK; ++k) st = bear_canonical_order(p->ref_items + cur[k], h_meta[k], 16, 0);
+  if (st == BEAR_OK) st = bear_canonical_order(p->heavy0, p->n_heavy0, 4, 0);
+  if (st != BEAR_OK) return st;
 #endif
-  }
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    plan_free(p);
-    return e == hipErrorOutOfMemory ? BEAR_ERR_NOMEM : BEAR_ERR_HIP;
-  }
   p->hist0 = d_meta + 32;
   p->bytes += sizeof(rpl_item) * p->n_ref_items + sizeof(uint32_t) * p->n_heavy0 + sizeof(unsigned long long) * 72;
-  *out = p;
+  *out = p.release();
   return BEAR_OK;
 }
 
@@ -903,7 +909,7 @@ int bear_debug_occupancy(int which) {
   hipError_t e = which == 0
       ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dm_prior_sorted_kernel<0>, SRT_THREADS, sizeof(srt_lds_n))
       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dm_ref_sorted_kernel, SRT_THREADS, sizeof(srt_lds_r));
-  return e == hipSuccess ? nb : -1000 - (int)e;
+  return e != hipSuccess ? -1000 - (int)e : nb;
 }
 
 int bear_log_gamma_f64(const double *conc, uint64_t n, uint64_t n_samples, uint64_t seed, double *out, void *stream) {

@@ -7,6 +7,12 @@
 //   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21
 //   bear_eval.hip    held-out evaluation (5- and 21-wide), the wide DM step and bear_ref's wide steps, the evaluation plan, the BMM marginal
 // What a unit needs of another goes through the declarations at the end of this file.
+//
+// Device memory and HIP errors, in every unit (bear_dev.h): a temporary sits in a dev_buf, which frees it when the function returns
+// (or where the function says reset(): hipFree waits for the device); a long-lived struct keeps raw pointers, which kernels and
+// views read, and is built either into dev_bufs that release() into it on success (bear_eval_plan, the pairing of a plan, levels,
+// window tables, bear_kmer_sort) or under a guard over its free function (bear_plan, bear_ws).  A failed HIP call leaves through
+// HIP_TRY: the error in bear_last_hip_error(), out of device memory as BEAR_ERR_NOMEM, anything else as BEAR_ERR_HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -15,10 +21,12 @@
 #include <string.h>
 
 #include <initializer_list>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "bear_common.h"
+#include "bear_dev.h"
 #include "bear_levels.h"
 #include "plan_common.h"
 
@@ -243,10 +251,13 @@ static inline int check_plan_step(const bear_ws *ws, const bear_plan *plan, cons
 
 // ------------------------------------------------------------------ across units
 // bear_ws_create: each family sets the dynamic-LDS limit of its own kernels and allocates the buffers of the workspace that only it
-// uses; BEAR_OK or BEAR_ERR_HIP (bear_last_hip_error).  What they allocated goes with the workspace (ws_release, bear_hip.hip).
+// uses; a status (bear_last_hip_error).  What they allocated goes with the workspace (ws_release, bear_hip.hip).
 BEAR_INTERNAL int linear_ws_setup(bear_ws *ws);      // lin_partials, lin_accum, linw_partials, linw_packed
 BEAR_INTERNAL int cnn_ws_setup(bear_ws *ws);         // cnnw_partials (cnn_partials grows on demand: cnn_backward_grid)
 BEAR_INTERNAL int eval_ws_setup(bear_ws *ws);        // eval_partials, eval_out
+// plan_free (bear_hip.hip): each family drops the fields of a plan that it owns, and takes them off plan->bytes
+BEAR_INTERNAL void plan_unpair(bear_plan *plan);            // bear_linear.hip: live2, tiles_p, tiles_u
+BEAR_INTERNAL void plan_drop_cnn_levels(bear_plan *plan);   // bear_cnn.hip: cnn_levels, cnn_win
 
 extern "C" {   // (bear_hip.hip defines everything inside one such block)
 // bear_hip.hip: the planned mode-N step with gradient rows (the convolutional step runs it between its forward and backward passes)

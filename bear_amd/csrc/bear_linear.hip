@@ -150,7 +150,7 @@ static void launch_linear(bear_ws *ws, const bear_plan *plan, const uint64_t *km
 #undef LIN_LAUNCH_K
 }
 
-static void plan_unpair(bear_plan *plan) {
+void plan_unpair(bear_plan *plan) {
   if (!plan->live2) return;
   plan->bytes -= plan->n_tiles * LIN_LIVE2_STRIDE * sizeof(uint16_t) + (plan->n_tiles + 2 * PLN_DESC_PAD) * sizeof(pln_tile);
   (void)hipFree(plan->live2);
@@ -175,8 +175,8 @@ int bear_plan_pair_contexts(bear_plan *plan, const uint64_t *kmer_index, int lag
   }
   const uint64_t nt = plan->n_tiles;
   if (nt == 0 || !plan->live) return BEAR_OK;
-  uint16_t *live2 = nullptr, *n_ent_dev = nullptr;
-  pln_tile *tp = nullptr, *tu = nullptr;
+  dev_buf<uint16_t> live2, n_ent_dev;
+  dev_buf<pln_tile> tp, tu;
   std::vector<uint16_t> n_ent;
   std::vector<pln_tile> host, hp, hu;
   try {
@@ -185,60 +185,42 @@ int bear_plan_pair_contexts(bear_plan *plan, const uint64_t *kmer_index, int lag
   } catch (const std::bad_alloc &) {
     return BEAR_ERR_NOMEM;
   }
-  hipError_t e = hipMalloc(&live2, nt * LIN_LIVE2_STRIDE * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc(&n_ent_dev, nt * sizeof(uint16_t));
-  if (e == hipSuccess) {
-    uint64_t blocks = nt;                   // one wave per tile
-    if (blocks > (1u << 18)) blocks = 1u << 18;
-    hipLaunchKernelGGL(plan_pair_kernel, dim3((unsigned)blocks), dim3(64), 0, s, plan->tiles, nt, plan->live,
-                       reinterpret_cast<const unsigned long long *>(kmer_index), lag, live2, n_ent_dev,
-                       getenv("BEAR_AMD_PAIR_NO_EMPTY") ? 0 : 1);     // (developer switch: the dealt order without the extra empty slots)
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(n_ent.data(), n_ent_dev, nt * sizeof(uint16_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), plan->tiles, nt * sizeof(pln_tile), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(n_ent_dev);
+  HIP_TRY(live2.alloc(nt * LIN_LIVE2_STRIDE));
+  HIP_TRY(n_ent_dev.alloc(nt));
+  uint64_t blocks = nt;                   // one wave per tile
+  if (blocks > (1u << 18)) blocks = 1u << 18;
+  hipLaunchKernelGGL(plan_pair_kernel, dim3((unsigned)blocks), dim3(64), 0, s, plan->tiles, nt, plan->live,
+                     reinterpret_cast<const unsigned long long *>(kmer_index), lag, live2.get(), n_ent_dev.get(),
+                     getenv("BEAR_AMD_PAIR_NO_EMPTY") ? 0 : 1);     // (developer switch: the dealt order without the extra empty slots)
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(n_ent.data(), n_ent_dev.get(), nt * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(host.data(), plan->tiles, nt * sizeof(pln_tile), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  n_ent_dev.reset();
   uint64_t n_p = 0;
-  bool keep = false;
-  if (e == hipSuccess) {
-    try {
-      for (uint64_t t = 0; t < nt; ++t) {
-        pln_tile d = host[t];
-        const bool fits = n_ent[t] != 0xffffu;         // (a tile without live contexts fits with 0 entries)
-        d.pad = (t << 32) | (fits ? n_ent[t] : 0u);
-        (fits ? hp : hu).push_back(d);
-      }
-      n_p = hp.size();
-      // fewer than half of the tiles paired (a sparse table: runs of one context): nothing to gain, the plan stays as it was
-      keep = 2 * n_p >= nt;
-      if (keep) {
-        const pln_tile zero = {};
-        hp.insert(hp.end(), PLN_DESC_PAD, zero);
-        hu.insert(hu.end(), PLN_DESC_PAD, zero);
-      }
-    } catch (const std::bad_alloc &) {
-      (void)hipFree(live2);
-      return BEAR_ERR_NOMEM;
+  try {
+    for (uint64_t t = 0; t < nt; ++t) {
+      pln_tile d = host[t];
+      const bool fits = n_ent[t] != 0xffffu;         // (a tile without live contexts fits with 0 entries)
+      d.pad = (t << 32) | (fits ? n_ent[t] : 0u);
+      (fits ? hp : hu).push_back(d);
     }
+    n_p = hp.size();
+    // fewer than half of the tiles paired (a sparse table: runs of one context): nothing to gain, the plan stays as it was
+    if (2 * n_p < nt) return BEAR_OK;
+    const pln_tile zero = {};
+    hp.insert(hp.end(), PLN_DESC_PAD, zero);
+    hu.insert(hu.end(), PLN_DESC_PAD, zero);
+  } catch (const std::bad_alloc &) {
+    return BEAR_ERR_NOMEM;
   }
-  if (e == hipSuccess && keep) e = hipMalloc(&tp, hp.size() * sizeof(pln_tile));
-  if (e == hipSuccess && keep) e = hipMalloc(&tu, hu.size() * sizeof(pln_tile));
-  if (e == hipSuccess && keep) e = hipMemcpy(tp, hp.data(), hp.size() * sizeof(pln_tile), hipMemcpyHostToDevice);
-  if (e == hipSuccess && keep) e = hipMemcpy(tu, hu.data(), hu.size() * sizeof(pln_tile), hipMemcpyHostToDevice);
-  if (e != hipSuccess || !keep) {
-    (void)hipFree(live2);
-    (void)hipFree(tp);
-    (void)hipFree(tu);
-    if (e != hipSuccess) {
-      g_last_hip_error = (int)e;
-      return e == hipErrorOutOfMemory ? BEAR_ERR_NOMEM : BEAR_ERR_HIP;
-    }
-    return BEAR_OK;
-  }
-  plan->live2 = live2;
-  plan->tiles_p = tp;
-  plan->tiles_u = tu;
+  HIP_TRY(tp.alloc(hp.size()));
+  HIP_TRY(tu.alloc(hu.size()));
+  HIP_TRY(hipMemcpy(tp.get(), hp.data(), hp.size() * sizeof(pln_tile), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(tu.get(), hu.data(), hu.size() * sizeof(pln_tile), hipMemcpyHostToDevice));
+  plan->live2 = live2.release();
+  plan->tiles_p = tp.release();
+  plan->tiles_u = tu.release();
   plan->n_tiles_p = n_p;
   plan->n_tiles_u = nt - n_p;
   plan->pair_codes = kmer_index;
