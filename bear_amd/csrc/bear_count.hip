@@ -63,35 +63,140 @@ template <int BITS>
 __host__ __device__ inline uint64_t cnt_invalid(int lag) { return 1ull << (BITS * lag); }
 
 // key: the context as the packed k-mer code (letter l of the k-mer in bits [BITS l, BITS l + BITS); W - 1 = '['): at 3 bits
-// the code of bear_pack_kmers_u64
+// the code of bear_pack_kmers_u64.  `nx` is text[t], `next` the letter of the pair's value (0 where nx is none); a dropped
+// transition gets cnt_invalid.  One routine for every kernel
+// that forms keys: the passes over key ranges below must cut the very order the single pass sorts into.
+template <int BITS, int W>
+__device__ __forceinline__ uint64_t cnt_key(const uint8_t *__restrict__ text, uint64_t t, uint32_t nx, int lag, uint32_t &next) {
+  constexpr uint32_t STOP = W - 1, START = W;
+  const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
+  uint64_t key = CNT_INVALID;
+  next = 0u;
+  if (nx <= STOP) {
+    next = nx;
+    key = 0;
+    bool started = false, bad = false;
+    for (int i = 1; i <= lag; ++i) {                 // letter lag - i of the k-mer
+      uint32_t c = STOP;
+      if (!started) {
+        c = (t >= (uint64_t)i) ? text[t - i] : START;
+        if (c == START) {
+          started = true;
+          c = STOP;
+        }
+      }
+      bad |= c > STOP;
+      key |= (uint64_t)c << (BITS * (lag - i));
+    }
+    if (bad) key = CNT_INVALID;
+  }
+  return key;
+}
+
 template <int BITS, int W>
 __global__ __launch_bounds__(256) void cnt_emit_kernel(const uint8_t *__restrict__ text, const uint8_t *__restrict__ grp,
                                                        uint64_t n_pos, int lag, uint64_t *__restrict__ keys,
                                                        uint32_t *__restrict__ vals) {
-  constexpr uint32_t STOP = W - 1, START = W;
   for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n_pos; t += (uint64_t)gridDim.x * 256) {
-    const uint32_t nx = text[t];
-    const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
-    uint64_t key = CNT_INVALID;
-    if (nx <= STOP) {
-      key = 0;
-      bool started = false, bad = false;
-      for (int i = 1; i <= lag; ++i) {                 // letter lag - i of the k-mer
-        uint32_t c = STOP;
-        if (!started) {
-          c = (t >= (uint64_t)i) ? text[t - i] : START;
-          if (c == START) {
-            started = true;
-            c = STOP;
-          }
-        }
-        bad |= c > STOP;
-        key |= (uint64_t)c << (BITS * (lag - i));
-      }
-      if (bad) key = CNT_INVALID;
+    uint32_t next;
+    keys[t] = cnt_key<BITS, W>(text, t, text[t], lag, next);
+    vals[t] = (uint32_t)grp[t] * (uint32_t)W + next;
+  }
+}
+
+// ---- counting in passes over key ranges.  The sort order is the key order, so the table of the keys whose leading bits fall
+// into [bin_lo, bin_hi) is a contiguous slice of the whole table, and the slices of disjoint ascending ranges, concatenated, are
+// the table: nothing is merged and nothing approximated.  The bin of a valid key is its top BITS * HL bits below the invalid
+// bit, HL = min(lag, BIN_LETTERS): the LAST letters of the context, the most significant ones of the sort.
+template <int BITS>
+struct cnt_bins;
+template <>
+struct cnt_bins<3> { static constexpr int LETTERS = BEAR_COUNT_BIN_LETTERS; };
+template <>
+struct cnt_bins<5> { static constexpr int LETTERS = BEAR_COUNT_BIN_LETTERS_WIDE; };
+template <int BITS>
+__host__ __device__ inline int cnt_bin_letters(int lag) { return lag < cnt_bins<BITS>::LETTERS ? lag : cnt_bins<BITS>::LETTERS; }
+template <int BITS>
+__host__ __device__ inline int cnt_bin_shift(int lag) { return BITS * (lag - cnt_bin_letters<BITS>(lag)); }
+constexpr uint64_t CNT_NO_BIN = ~0ull;      // the bin of a dropped transition: in no range, counted nowhere
+
+// Both kernels below run a loop that is uniform over the block (whole blocks of 256 positions, lanes past the end idle inside
+// it), so that every lane of a wave reaches the ballots.  Waves have 64 lanes on gfx950.
+//
+// hist[bin] += valid transitions of that bin.  The histogram (up to 2^18 bins of 8 bytes) does not fit LDS, so the adds go to
+// global memory; what is cheap to fold first is a run of neighbouring lanes with one bin (a homopolymer, the '[' contexts of
+// short reads): the first lane of a run adds the run's length.
+template <int BITS, int W>
+__global__ __launch_bounds__(256) void cnt_bin_hist_kernel(const uint8_t *__restrict__ text, uint64_t n_pos, int lag,
+                                                           unsigned long long *__restrict__ hist) {
+  const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
+  const int shift = cnt_bin_shift<BITS>(lag);
+  const unsigned lane = threadIdx.x & 63u;
+  for (uint64_t base = (uint64_t)blockIdx.x * 256; base < n_pos; base += (uint64_t)gridDim.x * 256) {
+    const uint64_t t = base + threadIdx.x;
+    uint64_t bin = CNT_NO_BIN;
+    if (t < n_pos) {
+      uint32_t next;
+      const uint64_t key = cnt_key<BITS, W>(text, t, text[t], lag, next);
+      if (key != CNT_INVALID) bin = key >> shift;
     }
-    keys[t] = key;
-    vals[t] = (uint32_t)grp[t] * (uint32_t)W + (nx <= STOP ? nx : 0u);
+    const uint64_t before = __shfl_up(bin, 1);
+    const bool head = lane == 0 || before != bin;
+    const unsigned long long heads = __ballot(head);
+    if (head && bin != CNT_NO_BIN) {
+      const unsigned long long later = heads & ~((2ull << lane) - 1ull);       // run starts above this lane
+      const unsigned next = later ? (unsigned)__ffsll((long long)later) - 1u : 64u;
+      atomicAdd(&hist[bin], (unsigned long long)(next - lane));
+    }
+  }
+}
+
+// The pairs of one bin range, compacted.  A wave takes CNT_RANGE_CHUNKS chunks of 64 positions per step: a ballot of the lanes
+// that write in each chunk, then ONE add on the 64-bit cursor, by lane 0, for all of them (every wave of the grid adds to that
+// one address and waits for the answer: one add per 64 positions alone took 20 ms per 1e8 positions, more than the sort), the
+// base broadcast, and each lane's slot from the chunks before its own and the writing lanes below it.  A slot at or beyond
+// `capacity` is not written, whatever the text holds; the host compares the final cursor with the capacity.  Dropped transitions
+// are not emitted, so the sort of a range reads BITS * lag bits.  The order of the pairs in front of the sort depends on which
+// wave reaches the cursor first; the table does not: the sort orders by key, pairs of equal keys differ only in their values,
+// and cnt_scatter_kernel adds each value's integer count to its cell -- a sum of ones, the same in any order.
+constexpr int CNT_RANGE_CHUNKS = 8;
+template <int BITS, int W>
+__global__ __launch_bounds__(256) void cnt_emit_range_kernel(const uint8_t *__restrict__ text, const uint8_t *__restrict__ grp,
+                                                             uint64_t n_pos, int lag, uint64_t bin_lo, uint64_t bin_hi,
+                                                             uint64_t capacity, unsigned long long *__restrict__ cursor,
+                                                             uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+  constexpr uint64_t STEP = 256ull * CNT_RANGE_CHUNKS;      // positions of a block per step: chunk c of a wave lies c * 256 further on
+  const uint64_t CNT_INVALID = cnt_invalid<BITS>(lag);
+  const int shift = cnt_bin_shift<BITS>(lag);
+  const unsigned lane = threadIdx.x & 63u;
+  for (uint64_t base = (uint64_t)blockIdx.x * STEP; base < n_pos; base += (uint64_t)gridDim.x * STEP) {
+    uint64_t key[CNT_RANGE_CHUNKS];
+    uint32_t next[CNT_RANGE_CHUNKS];
+    unsigned long long mask[CNT_RANGE_CHUNKS];
+    unsigned n_write = 0;
+#pragma unroll
+    for (int c = 0; c < CNT_RANGE_CHUNKS; ++c) {
+      const uint64_t t = base + (uint64_t)c * 256 + threadIdx.x;
+      key[c] = CNT_INVALID;
+      next[c] = 0;
+      if (t < n_pos) key[c] = cnt_key<BITS, W>(text, t, text[t], lag, next[c]);
+      if (key[c] != CNT_INVALID && ((key[c] >> shift) < bin_lo || (key[c] >> shift) >= bin_hi)) key[c] = CNT_INVALID;   // not this pass's
+      mask[c] = __ballot(key[c] != CNT_INVALID);
+      n_write += (unsigned)__popcll(mask[c]);
+    }
+    if (n_write == 0u) continue;                        // (uniform over the wave)
+    unsigned long long first = 0ull;
+    if (lane == 0) first = atomicAdd(cursor, (unsigned long long)n_write);
+    first = __shfl(first, 0);
+#pragma unroll
+    for (int c = 0; c < CNT_RANGE_CHUNKS; ++c) {
+      const uint64_t slot = first + (uint64_t)__popcll(mask[c] & ((1ull << lane) - 1ull));
+      if (key[c] != CNT_INVALID && slot < capacity) {
+        keys[slot] = key[c];
+        vals[slot] = (uint32_t)grp[base + (uint64_t)c * 256 + threadIdx.x] * (uint32_t)W + next[c];
+      }
+      first += (uint64_t)__popcll(mask[c]);
+    }
   }
 }
 
@@ -147,15 +252,46 @@ struct bear_kmer_sort {
 };
 
 namespace {
+// sort + run starts of `n` emitted pairs (n > 0), the common tail of a pass over the whole text and of a pass over one bin
+// range: keys / vals / rows are what the handle keeps, *last = the number of rows
+template <int BITS>
+int sort_and_rows(dev_buf<uint64_t> &keys_in, dev_buf<uint32_t> &vals_in, dev_buf<uint64_t> &keys, dev_buf<uint32_t> &vals,
+                  dev_buf<uint32_t> &rows, uint64_t n, unsigned key_bits, int lag, uint32_t *last, hipStream_t s) {
+  dev_buf<unsigned char> temp;
+  HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
+    return rocprim::radix_sort_pairs(t, tb, keys_in.get(), keys.get(), vals_in.get(), vals.get(), n, 0u, key_bits, s);
+  }));
+  HIP_TRY(hipStreamSynchronize(s));
+  temp.reset();            // the sort's storage and its input keys go before `rows` comes: the peak of the pass
+  keys_in.reset();
+  dev_buf<uint32_t> &flags = vals_in;   // reuse
+  HIP_TRY(rows.alloc(n));
+  hipLaunchKernelGGL((cnt_flag_kernel<BITS>), dim3(grid_for(n)), dim3(256), 0, s, keys.get(), n, lag, flags.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
+    return rocprim::inclusive_scan(t, tb, flags.get(), rows.get(), n, rocprim::plus<uint32_t>(), s);
+  }));
+  HIP_TRY(hipMemcpyAsync(last, rows.get() + (n - 1), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return BEAR_OK;
+}
+
+int new_handle(bear_kmer_sort **out, uint64_t *n_rows_out, uint64_t n, uint32_t n_rows, int lag, int width, dev_buf<uint64_t> &keys,
+               dev_buf<uint32_t> &vals, dev_buf<uint32_t> &rows) {
+  *out = new (std::nothrow) bear_kmer_sort{n, n_rows, lag, width, keys.get(), vals.get(), rows.get()};
+  if (!*out) return BEAR_ERR_NOMEM;
+  (void)keys.release(), (void)vals.release(), (void)rows.release();
+  *n_rows_out = n_rows;
+  return BEAR_OK;
+}
+
 // emit + sort + run starts of one lag (every argument checked by the caller, before any device call)
 template <int BITS, int W>
 int kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, bear_kmer_sort **out, uint64_t *n_rows_out,
                      hipStream_t s) {
   dev_buf<uint64_t> keys_in, keys;
   dev_buf<uint32_t> vals_in, vals, rows;
-  dev_buf<unsigned char> temp;
   uint32_t last = 0;
-  const unsigned key_bits = (unsigned)(BITS * lag + 1);
   if (n_pos) {
     HIP_TRY(keys_in.alloc(n_pos));
     HIP_TRY(vals_in.alloc(n_pos));
@@ -163,25 +299,57 @@ int kmer_sort_create(const uint8_t *text, const uint8_t *group, uint64_t n_pos, 
     HIP_TRY(vals.alloc(n_pos));
     hipLaunchKernelGGL((cnt_emit_kernel<BITS, W>), dim3(grid_for(n_pos)), dim3(256), 0, s, text, group, n_pos, lag, keys_in.get(), vals_in.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
-      return rocprim::radix_sort_pairs(t, tb, keys_in.get(), keys.get(), vals_in.get(), vals.get(), n_pos, 0u, key_bits, s);
-    }));
-    HIP_TRY(hipStreamSynchronize(s));
-    temp.reset();            // the sort's storage and its input keys go before `rows` comes: the peak of the pass
-    keys_in.reset();
-    dev_buf<uint32_t> &flags = vals_in;   // reuse
-    HIP_TRY(rows.alloc(n_pos));
-    hipLaunchKernelGGL((cnt_flag_kernel<BITS>), dim3(grid_for(n_pos)), dim3(256), 0, s, keys.get(), n_pos, lag, flags.get());
+    const int st = sort_and_rows<BITS>(keys_in, vals_in, keys, vals, rows, n_pos, (unsigned)(BITS * lag + 1), lag, &last, s);
+    if (st != BEAR_OK) return st;
+  }
+  return new_handle(out, n_rows_out, n_pos, last, lag, W, keys, vals, rows);
+}
+
+// the same over the transitions whose bin lies in [bin_lo, bin_hi): buffers for `capacity` pairs, not for n_pos positions, and
+// no invalid keys among them (BITS * lag key bits).  A pass that meets another number of pairs than `capacity` wrote at most
+// `capacity` of them and leaves no handle: the text and the histogram the capacity came from do not belong together.
+template <int BITS, int W>
+int kmer_sort_create_range(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, uint64_t bin_lo, uint64_t bin_hi,
+                           uint64_t capacity, bear_kmer_sort **out, uint64_t *n_rows_out, hipStream_t s) {
+  dev_buf<uint64_t> keys_in, keys;
+  dev_buf<uint32_t> vals_in, vals, rows;
+  dev_buf<unsigned long long> cursor;
+  unsigned long long n_pairs = 0;
+  uint32_t last = 0;
+  if (capacity) {
+    HIP_TRY(keys_in.alloc(capacity));
+    HIP_TRY(vals_in.alloc(capacity));
+    HIP_TRY(keys.alloc(capacity));
+    HIP_TRY(vals.alloc(capacity));
+  }
+  if (n_pos) {
+    HIP_TRY(cursor.alloc(1));
+    HIP_TRY(hipMemsetAsync(cursor.get(), 0, sizeof(unsigned long long), s));
+    const unsigned blocks = grid_for((n_pos + CNT_RANGE_CHUNKS - 1) / CNT_RANGE_CHUNKS);      // (a block takes 256 * CNT_RANGE_CHUNKS positions per step)
+    hipLaunchKernelGGL((cnt_emit_range_kernel<BITS, W>), dim3(blocks), dim3(256), 0, s, text, group, n_pos, lag, bin_lo, bin_hi, capacity,
+                       cursor.get(), keys_in.get(), vals_in.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(rocprim_run(temp, [&](void *t, size_t &tb) {
-      return rocprim::inclusive_scan(t, tb, flags.get(), rows.get(), n_pos, rocprim::plus<uint32_t>(), s);
-    }));
-    HIP_TRY(hipMemcpyAsync(&last, rows.get() + (n_pos - 1), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&n_pairs, cursor.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
-  *out = new (std::nothrow) bear_kmer_sort{n_pos, last, lag, W, keys.release(), vals.release(), rows.release()};
-  if (!*out) return BEAR_ERR_NOMEM;
-  *n_rows_out = last;
+  if (n_pairs != capacity) return BEAR_ERR_INVALID_ARG;
+  if (capacity) {
+    const int st = sort_and_rows<BITS>(keys_in, vals_in, keys, vals, rows, capacity, (unsigned)(BITS * lag), lag, &last, s);
+    if (st != BEAR_OK) return st;
+  }
+  return new_handle(out, n_rows_out, capacity, last, lag, W, keys, vals, rows);
+}
+
+// peak device bytes of a pass over n pairs: the four key / value buffers with the sort's storage, or, after the sort, what is
+// left of them with `rows` and the scan's storage -- the allocations of sort_and_rows, in its order
+template <int BITS>
+int kmer_sort_bytes(uint64_t n, int lag, uint64_t *bytes_out) {
+  size_t sort_b = 0, scan_b = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n, 0u,
+                                    (unsigned)(BITS * lag + 1), (hipStream_t) nullptr));
+  HIP_TRY(rocprim::inclusive_scan(nullptr, scan_b, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
+  const uint64_t at_sort = 24 * n + sort_b, at_scan = 20 * n + scan_b;
+  *bytes_out = at_sort > at_scan ? at_sort : at_scan;
   return BEAR_OK;
 }
 
@@ -192,6 +360,15 @@ bool sort_args_ok(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int
   *n_rows_out = 0;
   if (n_pos && (!text || !group)) return false;
   return n_pos < 0xffffffffull;   // row indices are 32-bit: shard the text above 4e9 positions
+}
+
+// the passes over bin ranges: width 5 or 21 with the lag limits of bear_kmer_sort_create_wide; the number of bins of a lag
+bool range_width_lag_ok(int lag, int width) {
+  if (width != 5 && width != 21) return false;
+  return lag >= 1 && lag <= (width == 5 ? cnt_alphabet<3, 5>::MAX_LAG : cnt_alphabet<5, 21>::MAX_LAG);
+}
+uint64_t range_n_bins(int lag, int width) {
+  return 1ull << (width == 5 ? 3 * cnt_bin_letters<3>(lag) : 5 * cnt_bin_letters<5>(lag));
 }
 }  // namespace
 
@@ -213,6 +390,39 @@ int bear_kmer_sort_create_wide(const uint8_t *text, const uint8_t *group, uint64
   hipStream_t s = static_cast<hipStream_t>(stream);
   return width == 5 ? kmer_sort_create<3, 5>(text, group, n_pos, lag, out, n_rows_out, s)
                     : kmer_sort_create<5, 21>(text, group, n_pos, lag, out, n_rows_out, s);
+}
+
+int bear_kmer_sort_bytes(uint64_t n_pairs, int lag, int width, uint64_t *bytes_out) {
+  if (!bytes_out || !range_width_lag_ok(lag, width) || n_pairs >= 0xffffffffull) return BEAR_ERR_INVALID_ARG;
+  *bytes_out = 0;
+  if (n_pairs == 0) return BEAR_OK;
+  return width == 5 ? kmer_sort_bytes<3>(n_pairs, lag, bytes_out) : kmer_sort_bytes<5>(n_pairs, lag, bytes_out);
+}
+
+int bear_kmer_bin_hist(const uint8_t *text, uint64_t n_pos, int lag, int width, uint64_t *hist, uint64_t n_bins, void *stream) {
+  if (!range_width_lag_ok(lag, width) || !hist || (n_pos && !text) || n_bins != range_n_bins(lag, width)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemsetAsync(hist, 0, n_bins * sizeof(uint64_t), s));
+  if (n_pos == 0) return BEAR_OK;
+  unsigned long long *h = reinterpret_cast<unsigned long long *>(hist);
+  if (width == 5)
+    hipLaunchKernelGGL((cnt_bin_hist_kernel<3, 5>), dim3(grid_for(n_pos)), dim3(256), 0, s, text, n_pos, lag, h);
+  else
+    hipLaunchKernelGGL((cnt_bin_hist_kernel<5, 21>), dim3(grid_for(n_pos)), dim3(256), 0, s, text, n_pos, lag, h);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_kmer_sort_create_range(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, int width, uint64_t bin_lo,
+                                uint64_t bin_hi, uint64_t capacity, bear_kmer_sort **out, uint64_t *n_rows_out, void *stream) {
+  if (!out || !n_rows_out) return BEAR_ERR_INVALID_ARG;
+  *out = nullptr;
+  *n_rows_out = 0;
+  if (!range_width_lag_ok(lag, width) || (n_pos && (!text || !group))) return BEAR_ERR_INVALID_ARG;
+  if (bin_lo >= bin_hi || bin_hi > range_n_bins(lag, width) || capacity >= 0xffffffffull) return BEAR_ERR_INVALID_ARG;   // (32-bit row indices)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return width == 5 ? kmer_sort_create_range<3, 5>(text, group, n_pos, lag, bin_lo, bin_hi, capacity, out, n_rows_out, s)
+                    : kmer_sort_create_range<5, 21>(text, group, n_pos, lag, bin_lo, bin_hi, capacity, out, n_rows_out, s);
 }
 
 int bear_kmer_sort_reduce(const bear_kmer_sort *h, int n_groups, uint8_t *kmers, uint64_t *kmer_code, uint32_t *counts,

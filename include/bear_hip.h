@@ -47,7 +47,9 @@ extern "C" {
                                   bear_dm_refmix_wide_grad_f64 (bear_ref's training step on rows of 21);
                                   still 12 (symbols added, nothing changed): + bear_dm_linear_wide_f64,
                                   bear_net_linear_train_reduce_wide_f64, bear_net_linear_train_step_wide_f64 (bear_net's step with the
-                                  linear AR function on rows of 21 as one launch) */
+                                  linear AR function on rows of 21 as one launch);
+                                  + bear_kmer_sort_bytes, bear_kmer_bin_hist, bear_kmer_sort_create_range (counting in passes over
+                                  key ranges) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -762,7 +764,25 @@ int bear_gather_rows(const void *src, const uint32_t *perm, void *dst, uint64_t 
  *   bear_fastx_size_wide / bear_fastx_encode_wide: reverse != 0 is refused (no complement); a '*' that is the last character
  *     of a record is the stop the encoder writes anyway and is left out by both passes, any other '*' is a 22
  *   bear_write_counts_tsv_wide: the same rows with `width` counts per group (what bear_parse_counts_tsv_wide reads)
+ *
+ * Counting in passes over key ranges, for a text beyond one device sort (n_pos >= 2^32 - 1, or about 30 B per position more than
+ * the device has).  The sort order is the key order, so the tables of disjoint ascending key ranges, concatenated, are the table.
+ *   bin        of a valid transition: the top BITS * HL bits of its context key, key >> (BITS * (lag - HL)), with BITS = 3 and
+ *              HL = min(lag, BEAR_COUNT_BIN_LETTERS) at width 5, BITS = 5 and HL = min(lag, BEAR_COUNT_BIN_LETTERS_WIDE) at width
+ *              21: the context's last HL letters.  n_bins = 1 << (BITS * HL), at most 2^18 resp. 2^15.
+ *   width      5 or 21, lag within the limits of bear_kmer_sort_create_wide; anything else is BEAR_ERR_INVALID_ARG
+ *   bear_kmer_sort_bytes: peak device bytes of one counting pass over n_pairs pairs (the buffers of bear_kmer_sort_create and
+ *              rocPRIM's temporary storage, asked of rocPRIM; nothing is allocated); n_pairs < 2^32 - 1
+ *   bear_kmer_bin_hist: hist [dev] uint64 [n_bins] = valid transitions per bin (a dropped transition is counted nowhere); zeroed
+ *              here; asynchronous on `stream`; n_bins must be the number the bin rule gives; n_pos may exceed 2^32
+ *   bear_kmer_sort_create_range: bear_kmer_sort_create[_wide] over the transitions whose bin lies in [bin_lo, bin_hi), with
+ *              bin_lo < bin_hi <= n_bins; capacity = their number (the histogram's sum over the range), < 2^32 - 1; synchronous.
+ *              If the pass meets another number of pairs it returns BEAR_ERR_INVALID_ARG and leaves *out NULL (the text and the
+ *              histogram do not belong together); it never writes beyond `capacity` pairs.  The handle goes to
+ *              bear_kmer_sort_reduce and bear_kmer_sort_destroy like any other; *n_rows_out = the rows of the range.
  */
+#define BEAR_COUNT_BIN_LETTERS 6      /* letters of a context that form its bin at 3 bits per letter (width 5) */
+#define BEAR_COUNT_BIN_LETTERS_WIDE 3 /* ... at 5 bits per letter (width 21) */
 int bear_fastx_size(const char *path, int fastq, int reverse, uint64_t *n_pos_out, uint64_t *n_seqs_out);
 int bear_fastx_encode(const char *path, int fastq, int reverse, int group, uint64_t capacity, uint8_t *text,
                       uint8_t *group_out, uint64_t *n_pos_out);
@@ -782,6 +802,10 @@ int bear_kmer_sort_create_wide(const uint8_t *text, const uint8_t *group, uint64
                                uint64_t *n_rows_out, void *stream);
 int bear_write_counts_tsv_wide(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag, int num_ds,
                                int width, uint64_t row_begin, uint64_t row_step, int append);
+int bear_kmer_sort_bytes(uint64_t n_pairs, int lag, int width, uint64_t *bytes_out);
+int bear_kmer_bin_hist(const uint8_t *text, uint64_t n_pos, int lag, int width, uint64_t *hist, uint64_t n_bins, void *stream);
+int bear_kmer_sort_create_range(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, int width, uint64_t bin_lo,
+                                uint64_t bin_hi, uint64_t capacity, bear_kmer_sort **out, uint64_t *n_rows_out, void *stream);
 
 #ifdef __cplusplus
 }

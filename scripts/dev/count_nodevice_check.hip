@@ -1,4 +1,5 @@
-// Developer check, for a machine WITHOUT a GPU: every allocating entry of the counting unit (bear_count.hip) with valid arguments.
+// Developer check, for a machine WITHOUT a GPU: every allocating entry of the counting unit (bear_count.hip) with valid arguments,
+// and the argument checks of the entries that count in passes over key ranges.
 // The first device call of each fails there, so this walks the error paths: a non-OK status, the out-handle NULL or emptied, the
 // HIP error recorded, and -- built with the host sanitizers -- nothing leaked or touched after its release on the way out.
 //
@@ -46,6 +47,42 @@ int main() {
     h = reinterpret_cast<bear_kmer_sort *>(1);
     failed("bear_kmer_sort_create_wide", bear_kmer_sort_create_wide(text, group, N, 3, width, &h, &n_rows, nullptr));
     expect(h == nullptr && n_rows == 0, "bear_kmer_sort_create_wide", "handle or row count left set");
+  }
+
+  // the passes over key ranges: first the argument checks, which come before any device call and leave no HIP error ...
+  uint64_t bytes = 7, hist[64];
+  auto refused = [&](const char *entry, int st) {
+    expect(st == BEAR_ERR_INVALID_ARG, entry, "a bad argument was not BEAR_ERR_INVALID_ARG");
+    expect(bear_count_last_hip_error() == 0, entry, "an argument check reached the device");
+  };
+  refused("bear_kmer_sort_bytes", bear_kmer_sort_bytes(N, 3, 7, &bytes));
+  refused("bear_kmer_sort_bytes", bear_kmer_sort_bytes(N, 13, 21, &bytes));
+  refused("bear_kmer_sort_bytes", bear_kmer_sort_bytes(N, 0, 5, &bytes));
+  refused("bear_kmer_sort_bytes", bear_kmer_sort_bytes(0xffffffffull, 3, 5, &bytes));
+  refused("bear_kmer_sort_bytes", bear_kmer_sort_bytes(N, 3, 5, nullptr));
+  expect(bear_kmer_sort_bytes(0, 3, 5, &bytes) == BEAR_OK && bytes == 0, "bear_kmer_sort_bytes", "no pairs need no bytes");
+  refused("bear_kmer_bin_hist", bear_kmer_bin_hist(text, N, 2, 5, hist, 63, nullptr));          // 2 letters of 3 bits: 64 bins
+  refused("bear_kmer_bin_hist", bear_kmer_bin_hist(text, N, 2, 7, hist, 64, nullptr));
+  refused("bear_kmer_bin_hist", bear_kmer_bin_hist(text, N, 22, 5, hist, 1 << 18, nullptr));
+  refused("bear_kmer_bin_hist", bear_kmer_bin_hist(text, N, 2, 5, nullptr, 64, nullptr));
+  refused("bear_kmer_bin_hist", bear_kmer_bin_hist(nullptr, N, 2, 5, hist, 64, nullptr));
+  struct { int lag, width; uint64_t lo, hi, cap; } bad[] = {{2, 5, 0, 65, 10}, {2, 5, 8, 8, 10},  {2, 5, 9, 8, 10}, {2, 7, 0, 64, 10},
+                                                           {13, 21, 0, 1, 10}, {0, 5, 0, 1, 10},  {2, 5, 0, 64, 0xffffffffull}};
+  for (const auto &b : bad) {
+    h = reinterpret_cast<bear_kmer_sort *>(1);
+    n_rows = 7;
+    refused("bear_kmer_sort_create_range", bear_kmer_sort_create_range(text, group, N, b.lag, b.width, b.lo, b.hi, b.cap, &h, &n_rows, nullptr));
+    expect(h == nullptr && n_rows == 0, "bear_kmer_sort_create_range", "handle or row count left set");
+  }
+  refused("bear_kmer_sort_create_range", bear_kmer_sort_create_range(text, group, N, 2, 5, 0, 64, 10, nullptr, &n_rows, nullptr));
+  refused("bear_kmer_sort_create_range", bear_kmer_sort_create_range(nullptr, group, N, 2, 5, 0, 64, 10, &h, &n_rows, nullptr));
+  // ... then valid arguments, which fail at the first device call
+  failed("bear_kmer_bin_hist", bear_kmer_bin_hist(text, N, 2, 5, hist, 64, nullptr));
+  for (int width : {5, 21}) {
+    h = reinterpret_cast<bear_kmer_sort *>(1);
+    n_rows = 7;
+    failed("bear_kmer_sort_create_range", bear_kmer_sort_create_range(text, group, N, 3, width, 0, 8, 100, &h, &n_rows, nullptr));
+    expect(h == nullptr && n_rows == 0, "bear_kmer_sort_create_range", "handle or row count left set");
   }
 
   bear_level_dev lv;
