@@ -1,5 +1,7 @@
 """Shared machinery of the bear_net / bear_ref drivers: resident shards, Keras-equivalent Adam,
 the per-step reduce, and the held-out evaluation built on the DM kernels."""
+import collections
+import concurrent.futures
 import math
 import os
 import warnings
@@ -142,7 +144,6 @@ class Uploader:
             np.copyto(view[:n], src[off:off + n])
             return
         if cls._copiers is None:
-            import concurrent.futures
             cls._copiers = concurrent.futures.ThreadPoolExecutor(cls.COPY_THREADS)
         step = -(-n // cls.COPY_THREADS)
         step += (-step) % 4096
@@ -197,6 +198,34 @@ def sort_by_kmer(codes, lag):
     return kernels.kmer_order(kernels.pack_kmers(codes.contiguous()), lag)
 
 
+# One batch as one rank sees it: rows [a, b) of the table are the batch, [g0, g1) this rank's piece of it, at ``off`` in the dataset's arrays
+Piece = collections.namedtuple("Piece", "a b g0 g1 off")
+
+
+def residency_status(check, epoch_rows, window_rows, asked, shuffled, n_pieces):
+    """(status, why): 0 = this rank's share of the epoch stays resident, 1 = streamed, 2 = neither works (``why``: the last refusal).
+    ``check(rows)`` raises MemoryError when that many rows do not fit (``hbm_budget_check``), asked in this order and no more often."""
+    status, why = (1 if asked else 0), None
+    if not asked:
+        try:
+            check(epoch_rows)
+        except MemoryError as err:
+            # (a shuffled epoch is permuted on the device as a whole; one batch cannot be streamed around itself)
+            status, why = (2 if shuffled or n_pieces < 2 else 1), str(err)
+    if status == 1 and not shuffled:
+        try:         # the window: the batch in use, the one landing, the blocks of the one just dropped (free once the steps that read them ran)
+            check(window_rows)
+        except MemoryError as err:
+            status, why = 2, str(err)
+    return status, why
+
+
+def unloaded_entry(piece):
+    """What ``ResidentBatches.batches`` holds of a streamed batch while it is not on the device: meta data only."""
+    rows = piece.g1 - piece.g0
+    return {"global_rows": piece.b - piece.a, "rows": rows, "uploaded_rows": rows, "row0": piece.g0, "plans": {}, "_loaded": False}
+
+
 class ResidentBatches:
     """This rank's row shard of every batch of one epoch, uploaded once: per batch the device slabs of the
     requested dataset columns, the k-mer codes, and (lazily) the kernel plans.
@@ -228,42 +257,34 @@ class ResidentBatches:
         if self.width != 5:
             prebuild = ()                   # plans are 5-wide: a wider table's steps stream the rows (kernels.dm_prior_wide)
             kmer_order = False              # (packed k-mers hold 3 bits per letter: the 4-letter alphabets' fused heads only)
+        self._columns, self._want_codes, self._drop_empty, self._kmer_order, self._prebuild = columns, want_codes, drop_empty, kmer_order, prebuild
+        self._names = list(columns) + (["codes"] if want_codes else [])
         self.batches = []
         # k-mer letter codes: the ASCII bytes go up as they were parsed and are encoded on the device
-        fast_codes = want_codes and data.alphabet in ("dna", "rna", "prot") and data.lag > 0
-        on_dev = getattr(data, "counts_dev", None) is not None       # DeviceCountDataset: the table is in HBM already
-        codes = data.codes() if (want_codes and not fast_codes) else None
+        self._fast_codes = want_codes and data.alphabet in ("dna", "rna", "prot") and data.lag > 0
+        self._on_dev = on_dev = getattr(data, "counts_dev", None) is not None       # DeviceCountDataset: the table is in HBM already
+        self._host_codes = data.codes() if (want_codes and not self._fast_codes) else None
+        self._row_index = getattr(data, "row_index", None)      # dataloader.KmerDealtDataset
         rank, world = dist.world()
-        pieces = list(zip(data.batch_bounds(), data.rank_pieces(rank, world)))
+        self._pieces = pieces = [Piece(a, b, *mine) for (a, b), mine in zip(data.batch_bounds(), data.rank_pieces(rank, world))]
+        piece_rows = [p.g1 - p.g0 for p in pieces]
+        shuffled = data.shuffle_seed is not None
         self.streaming = False
         self.loads = 0                      # streaming: batches made resident so far
         if not on_dev:
             if stream is None:
                 stream = bool(os.environ.get("BEAR_AMD_STREAM")) and os.environ.get("BEAR_AMD_STREAM") != "0"
-            largest = max([g1 - g0 for _, (g0, g1, _) in pieces] + [0])
-            # 0 = the epoch stays resident, 1 = streamed, 2 = neither works.  The RANKS AGREE on it (one MAX all-reduce): a rank
-            # that streams runs an eager loop, a resident one captures a graph and issues a warm-up all-reduce first -- with
-            # different decisions the ranks' collectives would pair up wrongly (and the job hang at its end)
-            status, why = (1 if stream else 0), None
-            if not stream:
-                try:
-                    hbm_budget_check(data, len(columns), want_codes, device, rows=sum(g1 - g0 for _, (g0, g1, _) in pieces),
-                                     per_row_extra=per_row_extra)
-                except MemoryError as err:
-                    # (a shuffled epoch is permuted on the device as a whole; one batch cannot be streamed around itself)
-                    status, why = (2 if data.shuffle_seed is not None or len(pieces) < 2 else 1), str(err)
-            if status == 1 and data.shuffle_seed is None:
-                # the window: the batch in use, the batch landing, and the blocks of the batch just dropped (free for the side
-                # stream only once the steps that read them have run)
-                try:
-                    hbm_budget_check(data, len(columns), want_codes, device, rows=3 * largest, per_row_extra=per_row_extra)
-                except MemoryError as err:
-                    status, why = 2, str(err)
+            # The RANKS AGREE on the status (one MAX all-reduce): a rank that streams runs an eager loop, a resident one captures
+            # a graph and issues a warm-up all-reduce first -- with different decisions the ranks' collectives would pair up
+            # wrongly (and the job hang at its end).  (hbm_budget_check: the module's, whatever it is when the check is made)
+            status, why = residency_status(
+                lambda rows: hbm_budget_check(data, len(columns), want_codes, device, rows=rows, per_row_extra=per_row_extra),
+                sum(piece_rows), 3 * max(piece_rows + [0]), stream, shuffled, len(pieces))
             agreed = dist.agree_max(status, device)
             if agreed == 2:
                 raise MemoryError(why or "another rank's share of the epoch fits its HBM neither resident nor streamed: every rank stops")
             if agreed == 1:
-                if data.shuffle_seed is not None:
+                if shuffled:
                     raise ValueError("a streamed epoch cannot be shuffled on the device (the shuffle permutes the whole shard in HBM)")
                 if why is not None:
                     warnings.warn(f"{why}  --  streaming the epoch instead: batches are re-uploaded every epoch (PCIe-bound)")
@@ -271,124 +292,115 @@ class ResidentBatches:
                     warnings.warn("another rank has to stream its share of the epoch: this rank streams too (the ranks run the same loop)")
                 self.streaming = True
         LAST_RUN["streaming"] = self.streaming
-        row_bytes = 4 * self.width
-        up = None if on_dev else Uploader(device, expect_bytes=max(
-            [(g1 - g0) * row_bytes for _, (g0, g1, _) in pieces] + [data.local_rows * row_bytes if data.shuffle_seed is not None else 0, 1]))
+        self._up = None if on_dev else Uploader(device, expect_bytes=max(
+            [4 * self.width * n for n in piece_rows] + [4 * self.width * data.local_rows if shuffled else 0, 1]))
         self.upload_bytes = 0
-
-        def device_column(col, lo, hi):
-            if on_dev:
-                return data.counts_dev[col, lo:hi].to(device).contiguous().clone()
-            return up.put(data.counts[col, lo:hi].view(np.int32), torch.int32)
-
-        def device_codes(lo, hi):
-            """-> (tensor, needs_encoding)"""
-            if fast_codes:
-                if on_dev:
-                    return data.kmers_dev[lo:hi].to(device).contiguous(), True
-                return up.put(data.kmers[lo:hi], torch.uint8), True
-            return up.put(codes[lo:hi], torch.int8), False
-        row_index = getattr(data, "row_index", None)      # dataloader.KmerDealtDataset
-        shuffled = {}
-        if data.shuffle_seed is not None and data.num_rows:
-            # whole columns go up once, are permuted by one gather pass each (same seed: columns stay aligned), and the
-            # batches below are slices of the permuted slabs
-            for name, col in columns.items():
-                t = device_column(col, 0, data.local_rows)
-                if up:
-                    up.wait()
-                shuffled[name] = kernels.shuffle_rows(t, data.shuffle_seed)
-                del t
-            if want_codes:
-                t, raw = device_codes(0, data.local_rows)
-                if up:
-                    up.wait()
-                shuffled["codes"] = kernels.shuffle_rows(kernels.encode_kmers(t, data.alphabet) if raw else t, data.shuffle_seed)
-                del t
-        if shuffled and data.shard is not None:
+        self._shuffled = self._upload_shuffled() if shuffled and data.num_rows else {}
+        if self._shuffled and data.shard is not None:
             raise ValueError("a sharded table cannot be shuffled on the device")
-        names = list(columns) + (["codes"] if want_codes else [])
-
-        def enqueue(k):
-            """Batch k's slabs: asynchronous uploads on the side stream (or slices of the shuffled columns)."""
-            (a, b), (g0, g1, off) = pieces[k]
-            lo, hi = off, off + (g1 - g0)           # this rank's piece of the batch inside the dataset's arrays
-            entry = {"global_rows": b - a, "rows": hi - lo, "row0": g0, "plans": {}}
-            if row_index is not None:           # rows dealt by k-mer range: row i of the piece is table row g0 + row_ids[i]
-                entry["row_ids"] = up.put(row_index[lo:hi], torch.int32)
-            for name, col in columns.items():
-                entry[name] = shuffled[name][lo:hi].clone() if shuffled else device_column(col, lo, hi)
-            if want_codes:
-                if shuffled:
-                    entry["codes"] = shuffled["codes"][lo:hi].clone()
-                else:
-                    entry["codes"], entry["_raw_codes"] = device_codes(lo, hi)
-            return entry
-
-        def finish(entry, slot=None):
-            """Everything of a landed batch that runs on the compute stream: encode, drop the empty rows, k-mer order, plans.
-            ``slot`` (streaming): the batch's place in ``self.batches`` -- its dict is refilled in place."""
-            if entry.pop("_raw_codes", False):
-                entry["codes"] = kernels.encode_kmers(entry["codes"], data.alphabet)
-            if drop_empty and entry["rows"] and not os.environ.get("BEAR_AMD_ALL_ROWS"):
-                keep = (entry[drop_empty] != 0).any(dim=1)
-                n_keep = int(keep.sum())
-                if n_keep < entry["rows"]:
-                    idx = keep.nonzero().squeeze(1)
-                    for name in names:
-                        entry[name] = entry[name].index_select(0, idx).contiguous()
-                    entry["rows"] = n_keep
-                    # row i of the compacted batch is row row0 + row_ids[i] of the table: the key of the evaluation's tie noise
-                    entry["row_ids"] = (entry["row_ids"].index_select(0, idx) if "row_ids" in entry else idx.to(torch.int32)).contiguous()
-                del keep
-            if kmer_order and want_codes and entry["rows"] > 1:
-                order = sort_by_kmer(entry["codes"], data.lag)
-                for name in names + (["row_ids"] if "row_ids" in entry else []):
-                    entry[name] = kernels.gather_rows(entry[name], order)
-                if "row_ids" not in entry:
-                    # no row was dropped, but row i is no longer table row row0 + i: the permutation itself says where each row sits
-                    # (the evaluation's tie-breaking noise is keyed by the table row, whatever the order or the sharding)
-                    entry["row_ids"] = order.to(torch.int32).contiguous()
-                del order
-            if slot is None:
-                self.batches.append(entry)
-                slot = len(self.batches) - 1
-            else:
-                entry["uploaded_rows"], entry["_loaded"] = self.batches[slot]["uploaded_rows"], True
-                self.batches[slot].clear()
-                self.batches[slot].update(entry)
-            if entry["rows"]:
-                for column, ncol, ref_column in prebuild:
-                    self.plan(slot, column, ncol, ref_column)
         if self.streaming:
-            import concurrent.futures
-            self._enqueue, self._finish, self._up = enqueue, finish, up
             self._pool = concurrent.futures.ThreadPoolExecutor(1)
             self._pending = None            # (batch, future of its enqueued upload)
-            for (a, b), (g0, g1, _) in pieces:
-                self.batches.append({"global_rows": b - a, "rows": g1 - g0, "uploaded_rows": g1 - g0, "row0": g0, "plans": {}, "_loaded": False})
-            return
+            self.batches = [unloaded_entry(p) for p in pieces]
+        else:
+            self._upload_all()
 
-        # one batch in flight: a worker thread feeds batch k + 1 through the staging ring (memcpy and waits release the GIL)
-        # while this thread compacts, sorts and plans batch k on the compute stream
-        import concurrent.futures
-        pool = concurrent.futures.ThreadPoolExecutor(1) if (up and len(pieces) > 1 and not shuffled) else None
+    def _slab(self, name, lo, hi):
+        """-> (rows [lo, hi) of a count column, or of the k-mer codes, on the device; whether these are ASCII bytes still to be encoded)"""
+        data, up = self.data, self._up
+        if name != "codes":
+            if self._on_dev:
+                return data.counts_dev[self._columns[name], lo:hi].to(self.device).contiguous().clone(), False
+            return up.put(data.counts[self._columns[name], lo:hi].view(np.int32), torch.int32), False
+        if not self._fast_codes:
+            return up.put(self._host_codes[lo:hi], torch.int8), False
+        if self._on_dev:
+            return data.kmers_dev[lo:hi].to(self.device).contiguous(), True
+        return up.put(data.kmers[lo:hi], torch.uint8), True
+
+    def _upload_shuffled(self):
+        """A shuffled epoch: whole columns go up once and are permuted by one gather pass each (same seed: columns stay
+        aligned); the batches are then slices of the permuted slabs."""
+        data, shuffled = self.data, {}
+        for name in self._names:
+            t, raw = self._slab(name, 0, data.local_rows)
+            if self._up:
+                self._up.wait()
+            shuffled[name] = kernels.shuffle_rows(kernels.encode_kmers(t, data.alphabet) if raw else t, data.shuffle_seed)
+            del t
+        return shuffled
+
+    def _enqueue(self, k):
+        """Batch k's slabs: asynchronous uploads on the side stream (or slices of the shuffled columns)."""
+        # INVARIANT: host tables in file order take this on the WORKER thread (``_upload_all``, ``_prefetch``), next to the compute
+        # stream's work on the batch before: nothing here may enqueue on the compute stream -- ``Uploader.put`` only.  (The slices of
+        # a shuffled epoch and of a table already in HBM are cut on the calling thread: no worker exists then.)
+        piece, shuffled = self._pieces[k], self._shuffled
+        lo, hi = piece.off, piece.off + (piece.g1 - piece.g0)          # this rank's piece of the batch inside the dataset's arrays
+        entry = {"global_rows": piece.b - piece.a, "rows": hi - lo, "row0": piece.g0, "plans": {}}
+        if self._row_index is not None:     # rows dealt by k-mer range: row i of the piece is table row g0 + row_ids[i]
+            entry["row_ids"] = self._up.put(self._row_index[lo:hi], torch.int32)
+        for name in self._names:
+            # (the codes come last: theirs is the flag that stays)
+            entry[name], entry["_raw_codes"] = (shuffled[name][lo:hi].clone(), False) if shuffled else self._slab(name, lo, hi)
+        return entry
+
+    def _finish(self, entry):
+        """Everything of a landed batch's slabs that runs on the compute stream: encode, drop the empty rows, k-mer order.
+        Returns the entry; where it goes (and its plans) is the caller's business."""
+        data, names, drop_empty = self.data, self._names, self._drop_empty
+        if entry.pop("_raw_codes", False):
+            entry["codes"] = kernels.encode_kmers(entry["codes"], data.alphabet)
+        if drop_empty and entry["rows"] and not os.environ.get("BEAR_AMD_ALL_ROWS"):
+            keep = (entry[drop_empty] != 0).any(dim=1)
+            n_keep = int(keep.sum())
+            if n_keep < entry["rows"]:
+                idx = keep.nonzero().squeeze(1)
+                for name in names:
+                    entry[name] = entry[name].index_select(0, idx).contiguous()
+                entry["rows"] = n_keep
+                # row i of the compacted batch is row row0 + row_ids[i] of the table: the key of the evaluation's tie noise
+                entry["row_ids"] = (entry["row_ids"].index_select(0, idx) if "row_ids" in entry else idx.to(torch.int32)).contiguous()
+            del keep
+        if self._kmer_order and self._want_codes and entry["rows"] > 1:
+            order = sort_by_kmer(entry["codes"], data.lag)
+            for name in names + (["row_ids"] if "row_ids" in entry else []):
+                entry[name] = kernels.gather_rows(entry[name], order)
+            if "row_ids" not in entry:
+                # no row was dropped, but row i is no longer table row row0 + i: the permutation itself says where each row sits
+                # (the evaluation's tie-breaking noise is keyed by the table row, whatever the order or the sharding)
+                entry["row_ids"] = order.to(torch.int32).contiguous()
+            del order
+        return entry
+
+    def _prebuild_plans(self, k):
+        if self.batches[k]["rows"]:
+            for column, ncol, ref_column in self._prebuild:
+                self.plan(k, column, ncol, ref_column)
+
+    def _upload_all(self):
+        """The resident epoch, one batch in flight: a worker thread feeds batch k + 1 through the staging ring (memcpy and waits
+        release the GIL) while this thread compacts, sorts and plans batch k on the compute stream."""
+        up, n = self._up, len(self._pieces)
+        pool = concurrent.futures.ThreadPoolExecutor(1) if (up and n > 1 and not self._shuffled) else None
         try:
-            submit = (lambda k: pool.submit(enqueue, k)) if pool else (lambda k: _Ready(enqueue(k)))
-            pending = submit(0) if pieces else None
-            for k in range(len(pieces)):
+            submit = (lambda k: pool.submit(self._enqueue, k)) if pool else (lambda k: _Ready(self._enqueue(k)))
+            pending = submit(0) if n else None
+            for k in range(n):
                 landed = pending.result()
                 if up:
                     up.wait()                              # the compute stream waits for batch k's copies (not the host)
-                pending = submit(k + 1) if k + 1 < len(pieces) else None
-                finish(landed)
+                pending = submit(k + 1) if k + 1 < n else None
+                self.batches.append(self._finish(landed))
+                self._prebuild_plans(k)
         finally:
             if pool:
                 pool.shutdown(wait=True)
-        del shuffled
+        self._shuffled = {}
         if up:
             self.upload_bytes = up.bytes
-            torch.cuda.current_stream(device).synchronize()    # the staging buffers go away with `up`
+            torch.cuda.current_stream(self.device).synchronize()    # the staging buffers go away with the uploader
+            self._up = None
 
     def load(self, k):
         """Batch k's entry with its slabs on the device.  Resident epochs: ``self.batches[k]``.  Streaming: see the class."""
@@ -397,11 +409,10 @@ class ResidentBatches:
             return e
         stream = torch.cuda.current_stream(self.device)
         if not e["_loaded"]:
-            for other in self.batches:              # (plans go with their entry: bear_plan_destroy synchronises the device)
+            for j, other in enumerate(self.batches):    # (plans go with their entry: bear_plan_destroy synchronises the device)
                 if other["_loaded"] and other is not e:
-                    keep = {key: other[key] for key in ("global_rows", "uploaded_rows", "row0")}
                     other.clear()
-                    other.update(keep, rows=keep["uploaded_rows"], plans={}, _loaded=False)
+                    other.update(unloaded_entry(self._pieces[j]))
             if self._pending is not None and self._pending[0] != k:
                 self._pending[1].result()           # a prefetch nobody asked for (batches taken out of order): dropped
                 self._pending = None
@@ -414,7 +425,13 @@ class ResidentBatches:
             self._up.wait()                         # the compute stream waits for the copies (not the host)
             # (starting the next batch's upload HERE, under this batch's compaction / sort / plans, was measured slower: 16.4 -> 23.8 ms
             # per 1e7-context batch -- the upload's host copies and this thread's set-up work get in each other's way)
-            self._finish(landed, slot=k)
+            landed = self._finish(landed)
+            landed["uploaded_rows"], landed["_loaded"] = e["uploaded_rows"], True
+            # INVARIANT: a streamed batch's dict is ONE object for the whole run, refilled in place -- ``reducers.lazy`` and
+            # ``run_autograd_steps`` hold references to it
+            e.clear()
+            e.update(landed)
+            self._prebuild_plans(k)
             self.loads += 1
             self.upload_bytes = self._up.bytes
         self._prefetch(k, stream)
@@ -681,6 +698,43 @@ def scatter_live(rows_live, live, n_rows):
     return full.index_copy(0, live, rows_live)
 
 
+def rows_on_live(e, fn, columns=("codes",), by="train", width=None):
+    """``fn(*columns)`` on the contexts of batch entry ``e`` with counts in column ``by``, scattered back into [e["rows"], W] (``live_rows``,
+    ``scatter_live``); on every row, unscattered, when (nearly) all have some.  ``width``: ``fn`` may return ONE row for all contexts (a
+    parameter-free AR function) -- then, and whenever all rows are live, the result is expanded to a contiguous [e["rows"], width]."""
+    live = live_rows(e, *columns, by=by)
+    suffix = "" if live is None else "_live_" + by
+    out = fn(*(e[c + suffix] for c in columns))
+    if width is not None and (live is None or out.shape[0] == 1):
+        return out.expand(e["rows"], width).contiguous()
+    return out if live is None else scatter_live(out, live, e["rows"])
+
+
+def pack_theta(params, device):
+    """The parameters, flattened in order, as ONE contiguous float64 device vector (a copy): what ``run_device_steps`` updates."""
+    with torch.no_grad():
+        return torch.cat([p.detach().reshape(-1).to(device=device, dtype=torch.float64) for p in params]).contiguous()
+
+
+def unpack_theta(theta, params):
+    """``pack_theta`` backwards: the vector's values into the parameters, in place."""
+    with torch.no_grad():
+        k = 0
+        for p in params:
+            p.copy_(theta[k:k + p.numel()].reshape(p.shape))
+            k += p.numel()
+
+
+def loss_scales(res, num_kmers):
+    """Per batch ``-(num_kmers / B)`` with the GLOBAL batch size: loss = scale * sum LL (bear_net.py:190-191, bear_ref.py:252-253)."""
+    return [-(num_kmers / e["global_rows"]) for e in res.batches]
+
+
+def zero_reduce(packed):
+    """The reduce of a batch of which this rank holds no row."""
+    packed.zero_()
+
+
 def check_normalized_rows(rows, what):
     """The plugin's ``normalized_rows`` promise, checked ONCE per train() call on the first batch's rows: the kernels that take it
     never form a row's sum (the concentration total is then shared by all contexts), so a wrong flag would give silently wrong
@@ -712,12 +766,11 @@ def run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, repeats, lear
     mixing of bear_ref.py:63-68 happens inside the DM kernel (``bear_dm_refmix_plan_grad_f64``), which also returns the gradients
     of the two mixing parameters; ``prior_fn`` is then not called.  On rows of 21 the kernel is ``bear_dm_refmix_wide_grad_f64``,
     ``ref_fn`` returns the reference COUNT rows and the net rows need not be normalised."""
-    with torch.no_grad():
-        theta = torch.cat([p.detach().reshape(-1).to(device=device, dtype=torch.float64) for p in params]).contiguous()
-        k = 0
-        for p in params:                     # the parameters live in theta from here on (and still do when the caller gets them back)
-            p.data = theta[k:k + p.numel()].view(p.shape)
-            k += p.numel()
+    theta = pack_theta(params, device)
+    k = 0
+    for p in params:                         # the parameters live in theta from here on (and still do when the caller gets them back)
+        p.data = theta[k:k + p.numel()].view(p.shape)
+        k += p.numel()
     rest = params[1:]
     out = torch.zeros(2, dtype=torch.float64, device=device)
     out4 = torch.zeros(4, dtype=torch.float64, device=device)
@@ -774,10 +827,9 @@ def run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, repeats, lear
                 p.grad = None                  # (inside a capture these are blocks of the graph's pool: nobody holds them between replays)
         return reduce
 
-    scales = [-(num_kmers / e["global_rows"]) for e in res.batches]       # bear_net.py:190-191 with the global batch
     max_rows = max([e["global_rows"] for e in res.batches] + [0])
-    return run_device_steps([reducer(k) for k in range(len(res.batches))], scales, theta, repeats, learning_rate, optimizer_name,
-                            train_ar, acc_steps, device, eager_first_period=True,
+    return run_device_steps([reducer(k) for k in range(len(res.batches))], loss_scales(res, num_kmers), theta, repeats, learning_rate,
+                            optimizer_name, train_ar, acc_steps, device, eager_first_period=True,
                             graph_ok=not res.streaming and max_rows <= int(os.environ.get("BEAR_AMD_GRAPH_MAX_ROWS", 1 << 22)))
 
 
@@ -787,7 +839,6 @@ def compute_dtype(dtype):
     if dtype in (torch.float64, None):
         return torch.float64
     if dtype == torch.float32:
-        import warnings
         warnings.warn("precision = float32: the HIP path computes and keeps its parameters in float64", stacklevel=3)
         return torch.float64
     raise NotImplementedError(f"precision {dtype}: the HIP kernels compute in float64")
@@ -893,10 +944,8 @@ def evaluate_resident(data, cols, h, van_reg, seed, dtype, device, prior_rows, n
             if not e["rows"]:
                 prior = torch.zeros((0, width), dtype=dtype, device=device)
             else:                                        # prior rows of the contexts with held-out counts: nothing else enters a sum
-                live = live_rows(e, "codes", by="test")
-                out = prior_rows(e, "" if live is None else "_live_test")
-                # (a parameter-free AR function may return one row for all contexts)
-                prior = out.expand(e["rows"], width).contiguous() if live is None or out.shape[0] == 1 else scatter_live(out, live, e["rows"])
+                # (``prior_rows`` reads the entry's columns by their suffix; the gathered codes it is handed say which)
+                prior = rows_on_live(e, lambda codes: prior_rows(e, "" if codes is e["codes"] else "_live_test"), by="test", width=width)
             sums.add(e["test"], prior, e.get("train"), row_base=e["row0"], plan=res.eval_plan(k) if e["rows"] and not wide else None,
                      row_ids=e.get("row_ids") if e["rows"] else None)
     res.close()

@@ -38,6 +38,100 @@ def linear_wide_step_selected(alphabet_size, lag, own_mat, width):
                 and not (unfused and unfused != "0"))
 
 
+def step_form(ar_func, ar_params, alphabet_size, lag, width):
+    """How ``train`` runs an optimizer step with this AR function, and the ``ResidentBatches`` keyword arguments that go with it:
+    ``"linear"`` / ``"cnn"`` (a 4-letter alphabet's fused heads: forward, ELBO and all gradients in one launch per batch),
+    ``"linear_wide"`` (the protein alphabet's linear step: ``linear_wide_step_selected``), or None (torch ops under autograd).
+    A fused form needs the AR function's parameters to BE the kernels' (identity, not equality)."""
+    mat = getattr(ar_func, "linear_mat", None)
+    # Fused heads: the sums of a step do not depend on the order of a batch's rows, so every batch is kept sorted by k-mer (first
+    # letter most significant) -- consecutive contexts share all but their last letters: the fused linear kernel adds whole waves /
+    # quads of them to d/d mat at once instead of one LDS atomic per context, letter and position (kernels_linear.h), the
+    # convolutional kernels evaluate a window that all contexts of a wave share once (kernels_cnn.h).  The plans are cut as the
+    # batches land, while the next batch is still being uploaded.  per_row_extra: plan + paired lists / prefix levels and buffers
+    if mat is not None and alphabet_size == 4 and lag <= kernels.LINEAR_MAX_LAG and mat is ar_params[0]:
+        return "linear", dict(kmer_order=True, prebuild=[("train", 5, None)], per_row_extra=8 + 4)
+    if (getattr(ar_func, "fused", False) and alphabet_size == 4 and len(ar_params) == 8
+            and all(a is b for a, b in zip(getattr(ar_func, "cnn_params", []), ar_params))):
+        return "cnn", dict(kmer_order=True, prebuild=[("train", 5, None)], per_row_extra=8 + 208 + 64)
+    # ... and on the protein alphabet: the linear head on int8 codes in table order (no plan, no k-mer sort: kernels_linear_wide.h)
+    if linear_wide_step_selected(alphabet_size, lag, mat is not None and len(ar_params) == 1 and mat is ar_params[0], width):
+        return "linear_wide", dict(kmer_order=False, prebuild=[("train", _train.ROWS_IF_DENSE, None)], per_row_extra=0)
+    return None, dict(kmer_order=False, prebuild=[("train", _train.ROWS_IF_DENSE, None)], per_row_extra=16 * (alphabet_size + 1))
+
+
+def _kmer_pack(e, lag, linear):
+    """The batch's k-mers as the fused kernels read them (kept with the batch): packed letters, or -- the linear head -- table-row words."""
+    if "pack" not in e:
+        q = kernels.pack_kmers(e["codes"].contiguous())
+        e["pack"] = kernels.linear_index(q, lag) if linear else q
+    return e["pack"]
+
+
+def _linear_step(res, theta, lag, train_ar, device):
+    """``make(k)`` of the fused linear form (``_train.reducers``)."""
+    def make(k):
+        e = res.load(k)
+        plan = res.plan(k, "train", 5) if e["rows"] else None     # built here, before any capture (plan creation allocates and synchronises)
+        if _train.deterministic_agreed(device):
+            # BEAR_AMD_DETERMINISTIC: the fixed-point scale of the linear step's gradient tables follows from the counts of the
+            # WHOLE batch -- every rank's piece -- so that d/d mat does not depend on the number of ranks (include/bear_hip.h);
+            # a rank whose piece of the batch is empty takes part in the two all-reduces with zeros
+            own = plan.count_total()[0] if plan is not None else [0.0, 0.0, 0.0]
+            tot, cmax = torch.tensor(own[:2], dtype=torch.float64, device=device), torch.tensor(own[2:], dtype=torch.float64, device=device)
+            dist.allreduce_sum_(tot)
+            dist.allreduce_max_(cmax)
+            if plan is not None:
+                plan.set_count_bound(tot.tolist() + cmax.tolist())
+        if plan is None:
+            return _train.zero_reduce
+        pack = _kmer_pack(e, lag, linear=True)
+        if pack.data_ptr() % 16 == 0:
+            # neighbours of the sorted batch that share all letters but the last three go through the step two at a time
+            # (kernels_linear.h, paired lists); declined by the library for tables too sparse to gain from it
+            plan.pair_contexts(pack, lag)
+        return _train.StepFns(
+            lambda packed: kernels.net_linear_train_reduce(plan, pack, lag, theta, packed, train_ar=train_ar),
+            lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_linear_train_step(plan, pack, lag, theta, m, v, t, packed, lr, scale,
+                                                                                       loss_buf, train_ar=train_ar))
+    return make
+
+
+def _cnn_step(res, theta, lag, fw, train_ar, device):
+    """``make(k)`` of the fused convolutional form: a reduce per batch (the update is ``run_device_steps``' own launch)."""
+    cnn_ws = kernels.default_workspace(device)     # the workspace the plans below are created on: the step's reservation lives there
+    bufs = kernels.cnn_step_buffers(max(max(e["rows"] for e in res.batches), 1), lag, fw, device, ws=cnn_ws)   # one set, largest batch
+
+    def make(k):
+        e = res.load(k)
+        plan = res.plan(k, "train", 5) if e["rows"] else None     # (before any capture, as above)
+        _train.deterministic_agreed(device)        # (the ranks' one-time agreement on the mode: its collectives come here in every fused form)
+        if plan is None:
+            return _train.zero_reduce
+        pack = _kmer_pack(e, lag, linear=False)
+        if pack.data_ptr() % 16 == 0:
+            # a position of the sorted batch once per distinct prefix (kernels_cnn.h, prefix levels); none attached when the
+            # prefixes of the table do not repeat
+            plan.attach_cnn_levels(pack, lag, fw)
+        views = tuple(b[:e["rows"]] for b in bufs)
+        return lambda packed: kernels.net_cnn_train_reduce(plan, pack, lag, fw, theta, views, packed, train_ar=train_ar)
+    return make
+
+
+def _linear_wide_step(res, theta, lag, train_ar):
+    """``make(k)`` of the protein alphabet's linear form: count rows and codes as they are, 16-byte aligned."""
+    def make(k):
+        e = res.load(k)
+        if not e["rows"]:
+            return _train.zero_reduce
+        counts, codes = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (e["train"].contiguous(), e["codes"].contiguous()))
+        return _train.StepFns(
+            lambda packed: kernels.net_linear_train_reduce_wide(counts, codes, lag, theta, packed, train_ar=train_ar),
+            lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_linear_train_step_wide(counts, codes, lag, theta, m, v, t, packed, lr,
+                                                                                            scale, loss_buf, train_ar=train_ar))
+    return make
+
+
 def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwargs,
           learning_rate, optimizer_name, train_ar, acc_steps=1,
           params_restart=None, writer=None, loss_save=None, dtype=torch.float64):
@@ -50,108 +144,31 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
     else:
         params, h_signed, ar_func = change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params_restart, dtype, device)
     dist.broadcast_params(params)                    # mirrored variables: every rank starts from rank 0's values (bear_net.py:246-256)
-    ar_params = params[1:]
-    # linear AR function on a DNA/RNA-sized alphabet: forward, ELBO and all gradients in one launch per batch
-    fused_mat = getattr(ar_func, "linear_mat", None)
-    if fused_mat is not None and not (alphabet_size == 4 and lag <= kernels.LINEAR_MAX_LAG and fused_mat is ar_params[0]):
-        fused_mat = None
-    cnn_ok = (getattr(ar_func, "fused", False) and alphabet_size == 4 and len(ar_params) == 8
-              and all(a is b for a, b in zip(getattr(ar_func, "cnn_params", []), ar_params)))
-    fused = fused_mat is not None or cnn_ok
-    # ... and on the protein alphabet: the same, on int8 codes in table order (no plan, no k-mer sort: kernels_linear_wide.h)
-    wide_mat = getattr(ar_func, "linear_mat", None)
-    wide_step = linear_wide_step_selected(alphabet_size, lag, wide_mat is not None and len(ar_params) == 1 and wide_mat is ar_params[0],
-                                          _train.row_width(data))
-    # Fused heads: the sums of a step do not depend on the order of a batch's rows, so every batch is kept sorted by k-mer (first
-    # letter most significant) -- consecutive contexts share all but their last letters: the fused linear kernel adds whole waves /
-    # quads of them to d/d mat at once instead of one LDS atomic per context, letter and position (kernels_linear.h), the
-    # convolutional kernels evaluate a window that all contexts of a wave share once (kernels_cnn.h).  The plans are cut as the
-    # batches land, while the next batch is still being uploaded.
-    res = _train.ResidentBatches(data, {"train": ds_loc}, device, want_codes=True, drop_empty="train", kmer_order=fused,
-                                 prebuild=[("train", 5 if fused else _train.ROWS_IF_DENSE, None)],     # (+ paired lists of the linear head / prefix levels of the cnn step)
-                                 per_row_extra=(8 + (208 + 64 if cnn_ok else 4)) if fused else 0 if wide_step else 16 * (alphabet_size + 1))
-    scales = [-(num_kmers / e["global_rows"]) for e in res.batches]       # bear_net.py:190-191 with the global batch
-    if fused or wide_step:
+    form, res_kw = step_form(ar_func, params[1:], alphabet_size, lag, _train.row_width(data))
+    res = _train.ResidentBatches(data, {"train": ds_loc}, device, want_codes=True, drop_empty="train", **res_kw)
+    if form is None:
+        normalized = bool(getattr(ar_func, "normalized_rows", False))   # every reference AR function ends in a softmax
+        # (contexts without training counts need no prior row; a parameter-free AR function may return one row for all contexts)
+        losses = _train.run_autograd_steps(res, lambda e: _train.rows_on_live(e, ar_func, width=alphabet_size + 1), params, h_signed,
+                                           num_kmers, data.repeats, learning_rate, optimizer_name, train_ar, acc_steps, normalized, device)
+    else:
         # theta = {h_signed, flattened AR parameters} lives on the device for the whole run: one step is constants-from-theta ->
         # fused kernels [-> all-reduce of the packed vector] -> Adam, no host round trip (_train.run_device_steps)
-        theta = torch.cat([h_signed.detach().reshape(1)] + [p.detach().reshape(-1) for p in ar_params]).to(
-            device=device, dtype=torch.float64).contiguous()
-        def pack_of(e):                 # the batch's k-mers as the fused kernels read them (kept with the batch)
-            if "pack" not in e:
-                q = kernels.pack_kmers(e["codes"].contiguous())
-                e["pack"] = kernels.linear_index(q, lag) if fused_mat is not None else q    # the linear head reads table-row words, not packed letters
-            return e["pack"]
-        if cnn_ok:
-            fw = ar_func.cnn_filter_width
-            cnn_ws = kernels.default_workspace(device)     # the workspace the plans below are created on: the step's reservation lives there
-            bufs = kernels.cnn_step_buffers(max(max(e["rows"] for e in res.batches), 1), lag, fw, device, ws=cnn_ws)   # one set, largest batch
-
-        def reducer(k):
-            e = res.load(k)
-            plan = res.plan(k, "train", 5) if e["rows"] else None     # built here, before any capture (plan creation allocates and synchronises)
-            if _train.deterministic_agreed(device) and fused_mat is not None:
-                # BEAR_AMD_DETERMINISTIC: the fixed-point scale of the linear step's gradient tables follows from the counts of the
-                # WHOLE batch -- every rank's piece -- so that d/d mat does not depend on the number of ranks (include/bear_hip.h);
-                # a rank whose piece of the batch is empty takes part in the two all-reduces with zeros
-                own = plan.count_total()[0] if plan is not None else [0.0, 0.0, 0.0]
-                tot, cmax = torch.tensor(own[:2], dtype=torch.float64, device=device), torch.tensor(own[2:], dtype=torch.float64, device=device)
-                dist.allreduce_sum_(tot)
-                dist.allreduce_max_(cmax)
-                if plan is not None:
-                    plan.set_count_bound(tot.tolist() + cmax.tolist())
-            if plan is None:
-                return lambda packed: packed.zero_()
-            pack = pack_of(e)
-            if fused_mat is not None and pack.data_ptr() % 16 == 0:
-                # neighbours of the sorted batch that share all letters but the last three go through the step two at a time
-                # (kernels_linear.h, paired lists); declined by the library for tables too sparse to gain from it
-                plan.pair_contexts(pack, lag)
-            if cnn_ok:
-                if pack.data_ptr() % 16 == 0:
-                    # a position of the sorted batch once per distinct prefix (kernels_cnn.h, prefix levels); none attached when the
-                    # prefixes of the table do not repeat
-                    plan.attach_cnn_levels(pack, lag, fw)
-                views = tuple(b[:e["rows"]] for b in bufs)
-                return lambda packed: kernels.net_cnn_train_reduce(plan, pack, lag, fw, theta, views, packed, train_ar=train_ar)
-            return _train.StepFns(
-                lambda packed: kernels.net_linear_train_reduce(plan, pack, lag, theta, packed, train_ar=train_ar),
-                lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_linear_train_step(plan, pack, lag, theta, m, v, t, packed, lr, scale,
-                                                                                           loss_buf, train_ar=train_ar))
-
-        def reducer_wide(k):
-            e = res.load(k)
-            if not e["rows"]:
-                return lambda packed: packed.zero_()
-            counts, codes = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (e["train"].contiguous(), e["codes"].contiguous()))
-            return _train.StepFns(
-                lambda packed: kernels.net_linear_train_reduce_wide(counts, codes, lag, theta, packed, train_ar=train_ar),
-                lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_linear_train_step_wide(counts, codes, lag, theta, m, v, t, packed, lr,
-                                                                                                scale, loss_buf, train_ar=train_ar))
+        theta = _train.pack_theta(params, device)
         graph_ok = not res.streaming
-        if wide_step:
+        if form == "linear":
+            make = _linear_step(res, theta, lag, train_ar, device)
+        elif form == "cnn":
+            make = _cnn_step(res, theta, lag, ar_func.cnn_filter_width, train_ar, device)
+        else:
+            make = _linear_wide_step(res, theta, lag, train_ar)
             # the fused step pins no autograd intermediates in a graph's pool: no row cap of its own, but one that is set is honoured
             # (the tests force the eager loop of a protein run with BEAR_AMD_GRAPH_MAX_ROWS=0)
             cap = os.environ.get("BEAR_AMD_GRAPH_MAX_ROWS")
             graph_ok = graph_ok and (cap is None or max([e["global_rows"] for e in res.batches] + [0]) <= int(cap))
-        reduce_fns = _train.reducers(res, reducer_wide if wide_step else reducer)
-        losses = _train.run_device_steps(reduce_fns, scales, theta, data.repeats, learning_rate, optimizer_name, train_ar, acc_steps, device,
-                                         graph_ok=graph_ok)
-        with torch.no_grad():
-            k = 0
-            for p in params:
-                p.copy_(theta[k:k + p.numel()].reshape(p.shape))
-                k += p.numel()
-    else:
-        normalized = bool(getattr(ar_func, "normalized_rows", False))   # every reference AR function ends in a softmax
-
-        def prior_fn(e):
-            live = _train.live_rows(e, "codes")          # contexts without training counts need no prior row
-            out = ar_func(e["codes"] if live is None else e["codes_live_train"])
-            if live is None or out.shape[0] == 1:        # (a parameter-free AR function may return one row for all contexts)
-                return out.expand(e["rows"], alphabet_size + 1).contiguous()
-            return _train.scatter_live(out, live, e["rows"])
-        losses = _train.run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, data.repeats, learning_rate, optimizer_name, train_ar,
-                                           acc_steps, normalized, device)
+        losses = _train.run_device_steps(_train.reducers(res, make), _train.loss_scales(res, num_kmers), theta, data.repeats, learning_rate,
+                                         optimizer_name, train_ar, acc_steps, device, graph_ok=graph_ok)
+        _train.unpack_theta(theta, params)
     res.close()
     ar_funcs.release_ar_func_cache(ar_func)
     _train.log_losses(losses, writer, loss_save, acc_steps)

@@ -84,6 +84,35 @@ def _ref_input(ref_slab, dtype=torch.float64):
     return r
 
 
+def _planned_step(res, theta, train_ar):
+    """``make(k)`` of the stop net function on 5-wide rows (``_train.reducers``): the mode-R kernel over a plan."""
+    def make(k):
+        e = res.load(k)
+        if e["rows"] == 0:
+            return _train.zero_reduce
+        # built here, before any capture (plan creation allocates and synchronises); the reference column is resident too, so the
+        # plan folds the contexts without reference counts into a histogram and a step streams only the others' items
+        plan = res.plan(k, "train", 4, ref_column="ref")
+        return _train.StepFns(
+            lambda packed: kernels.ref_train_reduce(plan, e["ref"], theta, packed, train_ar=train_ar),
+            lambda packed, m, v, t, lr, scale, loss_buf: kernels.ref_train_step(plan, e["ref"], theta, m, v, t, lr, scale, packed, loss_buf,
+                                                                                train_ar=train_ar))
+    return make
+
+
+def _wide_step(res, theta, train_ar):
+    """``make(k)`` of the stop net function on rows of 21: dm_ref_wide_kernel on the count rows, no plan."""
+    def make(k):
+        e = res.load(k)
+        if e["rows"] == 0:
+            return _train.zero_reduce
+        return _train.StepFns(
+            lambda packed: kernels.ref_train_reduce_wide(e["train"], e["ref"], theta, packed, train_ar=train_ar),
+            lambda packed, m, v, t, lr, scale, loss_buf: kernels.ref_train_step_wide(e["train"], e["ref"], theta, m, v, t, lr, scale,
+                                                                                     packed, loss_buf, train_ar=train_ar))
+    return make
+
+
 def train(data, num_kmers, epochs, ds_loc, ds_loc_ref, alphabet, lag, make_ar_func, af_kwargs,
           learning_rate, optimizer_name, train_ar, acc_steps=1,
           params_restart=None, writer=None, loss_save=None, dtype=torch.float64):
@@ -106,36 +135,15 @@ def train(data, num_kmers, epochs, ds_loc, ds_loc_ref, alphabet, lag, make_ar_fu
         return _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, optimizer_name, train_ar, acc_steps, writer,
                               loss_save, ds_loc, ds_loc_ref, device)
     # stop net function: theta = (h_signed, tau_signed, net_weight_signed) lives on the device for the whole run; one step is
-    # constants-from-theta -> mode-R kernel (planned; rows of 21: dm_ref_wide_kernel on the count rows, no plan) -> finalize
-    # [-> all-reduce of 4 doubles] -> Adam, no host round trip
+    # constants-from-theta -> mode-R kernel -> finalize [-> all-reduce of 4 doubles] -> Adam, no host round trip
     res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, drop_empty="train",
                                  prebuild=[("train", 4, "ref")])       # plans cut while the next batch is still crossing PCIe
-    theta = torch.stack([p.detach().reshape(()) for p in params[:3]]).to(device=device, dtype=torch.float64).contiguous()
-
-    def reducer(k):
-        e = res.load(k)
-        if e["rows"] == 0:
-            return lambda packed: packed.zero_()
-        if wide:
-            return _train.StepFns(
-                lambda packed: kernels.ref_train_reduce_wide(e["train"], e["ref"], theta, packed, train_ar=train_ar),
-                lambda packed, m, v, t, lr, scale, loss_buf: kernels.ref_train_step_wide(e["train"], e["ref"], theta, m, v, t, lr, scale,
-                                                                                         packed, loss_buf, train_ar=train_ar))
-        # built here, before any capture (plan creation allocates and synchronises); the reference column is resident too, so the
-        # plan folds the contexts without reference counts into a histogram and a step streams only the others' items
-        plan = res.plan(k, "train", 4, ref_column="ref")
-        return _train.StepFns(
-            lambda packed: kernels.ref_train_reduce(plan, e["ref"], theta, packed, train_ar=train_ar),
-            lambda packed, m, v, t, lr, scale, loss_buf: kernels.ref_train_step(plan, e["ref"], theta, m, v, t, lr, scale, packed, loss_buf,
-                                                                                train_ar=train_ar))
-    reduce_fns = _train.reducers(res, reducer)
-    scales = [-(num_kmers / e["global_rows"]) for e in res.batches]       # loss = -(num_kmers / B) sum LL, bear_ref.py:252-253
-    losses = _train.run_device_steps(reduce_fns, scales, theta, data.repeats, learning_rate, optimizer_name, train_ar, acc_steps, device,
-                                     graph_ok=not res.streaming)
+    theta = _train.pack_theta(params[:3], device)
+    make = _wide_step(res, theta, train_ar) if wide else _planned_step(res, theta, train_ar)
+    losses = _train.run_device_steps(_train.reducers(res, make), _train.loss_scales(res, num_kmers), theta, data.repeats, learning_rate,
+                                     optimizer_name, train_ar, acc_steps, device, graph_ok=not res.streaming)
     res.close()
-    with torch.no_grad():
-        for p, val in zip(params[:3], theta):
-            p.copy_(val)
+    _train.unpack_theta(theta, params[:3])
     _train.log_losses(losses, writer, loss_save, acc_steps)
     return params, h_signed, ar_func
 
@@ -153,22 +161,18 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     # a fused net function (linear rows / cnn kernels) shares work between neighbouring contexts: batches are kept in k-mer order
     # (the sums do not depend on the order; cnn forward + backward 70 instead of 137 ms per 1e8 contexts, linear backward 1.45 / 2.0);
     # the 4-letter kernels only: the rows of 21 (kernels_linrows_wide.h) share nothing between neighbours, and the sort packs 3 bits
-    res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, want_codes=True, drop_empty="train",
-                                 kmer_order=bool(getattr(getattr(ar_func, "net_func", None), "fused", False)) and _train.row_width(data) == 5,
-                                 prebuild=[("train", 5, None)], per_row_extra=24 * _train.row_width(data))
-
     width = _train.row_width(data)
+    res = _train.ResidentBatches(data, {"train": ds_loc, "ref": ds_loc_ref}, device, want_codes=True, drop_empty="train",
+                                 kmer_order=bool(getattr(getattr(ar_func, "net_func", None), "fused", False)) and width == 5,
+                                 prebuild=[("train", 5, None)], per_row_extra=24 * width)
 
-    def prior_fn_inputs(e):
+    def with_ref_in(e):
         if "ref_in" not in e:
             e["ref_in"] = _ref_input(e["ref"])
+        return e
 
-    def prior_fn(e):
-        prior_fn_inputs(e)
-        live = _train.live_rows(e, "codes", "ref_in")    # contexts without training counts need no prior row
-        if live is None:
-            return ar_func(e["codes"], e["ref_in"]).contiguous()
-        return _train.scatter_live(ar_func(e["codes_live_train"], e["ref_in_live_train"]), live, e["rows"])
+    def prior_fn(e):                 # (contexts without training counts need no prior row)
+        return _train.rows_on_live(with_ref_in(e), ar_func, columns=("codes", "ref_in")).contiguous()
     # normalised net rows, the reference's own mixing parameters: the mixing runs inside the DM kernel
     # (bear_dm_refmix_plan_grad_f64: one launch instead of mix-forward, gradient rows, mix-backward); BEAR_AMD_UNFUSED_MIX=1 keeps
     # the three launches (tests compare the two)
@@ -178,13 +182,10 @@ def _train_general(data, num_kmers, params, h_signed, ar_func, learning_rate, op
     own_mix = (getattr(ar_func, "net_func", None) is not None and params[1] is ar_func.tau_signed and params[2] is ar_func.net_weight_signed
                and not os.environ.get("BEAR_AMD_UNFUSED_MIX"))
     if own_mix and (ar_func.normalized_rows if width == 5 else width in kernels.WIDE_WIDTHS):
-        def net_fn(e):
-            if width == 5:
-                prior_fn_inputs(e)
-            live = _train.live_rows(e, "codes", *(("ref_in",) if width == 5 else ()))
-            if live is None:
-                return ar_func.net_func(e["codes"])
-            return _train.scatter_live(ar_func.net_func(e["codes_live_train"]), live, e["rows"])
+        if width == 5:               # (the live contexts' reference rows are gathered next to their codes, as for prior_fn)
+            net_fn = lambda e: _train.rows_on_live(with_ref_in(e), lambda codes, ref_in: ar_func.net_func(codes), columns=("codes", "ref_in"))
+        else:
+            net_fn = lambda e: _train.rows_on_live(e, ar_func.net_func)
         ref_mix = (net_fn, (lambda e: e["ref_in"]) if width == 5 else (lambda e: e["ref"]), params[1], params[2])
     losses = _train.run_autograd_steps(res, prior_fn, params, h_signed, num_kmers, data.repeats, learning_rate, optimizer_name, train_ar,
                                        acc_steps, ar_func.normalized_rows, device, ref_mix=ref_mix)
