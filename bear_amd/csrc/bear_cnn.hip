@@ -17,7 +17,7 @@ int cnn_ws_setup(bear_ws *ws) {
                                                                     ? cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG)
                                                                     : cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1));
   if (st != BEAR_OK) return st;
-  HIP_TRY(hipMalloc(&ws->cnnw_partials, sizeof(double) * CNW_MAX_TOTAL * CNW_PARTIAL_ROWS(ws->num_cu)));
+  HIP_TRY(hipMalloc(&ws->cnnw_partials, sizeof(double) * CNW_MAX_TOTAL * WIDE_PARTIAL_ROWS(ws->num_cu, CNW_BWD_BLOCKS_PER_CU)));
   return BEAR_OK;
 }
 

@@ -160,15 +160,16 @@ __device__ __forceinline__ double bear_uniform_f64(double v) {   // a wave-unifo
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// What bear_dm_ref_plan_f64 / bear_dm_prior_plan_f64 derive on the host, from parameters the optimizer moves on the device.
-__device__ __forceinline__ bear_params bear_params_of(const bear_params &arg, const bear_step_io &io) {
-  if (!io.theta) return arg;
+// The constants of a step from device-resident parameters, wherever each of them lives: h_signed, and for mode R (`ref`) tau_signed
+// and net_weight_signed as well (params_net / params_ref, bear_host.h, are the host's form).
+__device__ __forceinline__ bear_params bear_params_dev(double eps, bool ref, const double *__restrict__ h_s,
+                                                       const double *__restrict__ tau_s, const double *__restrict__ nw_s) {
   bear_params p;
-  p.eps = arg.eps;
-  p.inv_h = bear_uniform_f64(1.0 / exp(io.theta[0]));
+  p.eps = eps;
+  p.inv_h = bear_uniform_f64(1.0 / exp(h_s[0]));
   p.E = p.tauE = p.tau = p.V = p.nw = 0.0;
-  if (io.kind == BEAR_THETA_REF) {
-    const double tau = exp(io.theta[1]), nw = exp(io.theta[2]);
+  if (ref) {
+    const double tau = exp(tau_s[0]), nw = exp(nw_s[0]);
     const double E = exp(-tau);
     p.E = bear_uniform_f64(E);
     p.tauE = bear_uniform_f64(tau * E);
@@ -177,6 +178,12 @@ __device__ __forceinline__ bear_params bear_params_of(const bear_params &arg, co
     p.nw = bear_uniform_f64(nw);
   }
   return p;
+}
+
+// What bear_dm_ref_plan_f64 / bear_dm_prior_plan_f64 derive on the host, from parameters the optimizer moves on the device.
+__device__ __forceinline__ bear_params bear_params_of(const bear_params &arg, const bear_step_io &io) {
+  if (!io.theta) return arg;
+  return bear_params_dev(arg.eps, io.kind == BEAR_THETA_REF, io.theta, io.theta + 1, io.theta + 2);
 }
 
 // After its partials are stored (bear_store_agent) a block announces itself; true for the block that arrived last.  Every

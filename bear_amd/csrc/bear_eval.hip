@@ -113,18 +113,12 @@ int bear_dm_prior_wide_f64(bear_ws *ws, const uint32_t *counts, const double *pr
   memset(&prm, 0, sizeof(prm));
   prm.inv_h = 1.0;           // (AR mode without h_signed_dev: never read)
   prm.eps = eps;
-  const uint64_t tile = (uint64_t)(width == 21 ? WIDE_TILE(21) : WIDE_TILE(5));
-  const int grid = grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, WIDE_BLOCKS_PER_CU));
+  const int grid = wide_grid(ws, n_rows, WIDE_TILE(width), WIDE_BLOCKS_PER_CU);
   const bear_step_io io = ws_io(ws, h_signed_dev, BEAR_THETA_NET, out);
   const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
-#define WIDE_LAUNCH(W, AR, GRAD) \
+#define WIDE_LAUNCH(AR, GRAD) \
   hipLaunchKernelGGL((dm_wide_kernel<W, AR, GRAD>), dim3(grid), dim3(WIDE_THREADS), 0, s, counts, prior, n_rows, prm, grad_prior, lt, ws->partials, io)
-#define WIDE_LAUNCH_21(AR, GRAD) WIDE_LAUNCH(21, AR, GRAD)
-#define WIDE_LAUNCH_5(AR, GRAD) WIDE_LAUNCH(5, AR, GRAD)
-  if (width == 21) BEAR_DISPATCH_2(train_ar, grad_prior, WIDE_LAUNCH_21);
-  else BEAR_DISPATCH_2(train_ar, grad_prior, WIDE_LAUNCH_5);
-#undef WIDE_LAUNCH_5
-#undef WIDE_LAUNCH_21
+  BEAR_DISPATCH_W(width, BEAR_DISPATCH_2(train_ar, grad_prior, WIDE_LAUNCH));
 #undef WIDE_LAUNCH
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
@@ -148,12 +142,8 @@ int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train,
     const int m_cnt = n_models - m0 < EVS_CHUNK ? n_models - m0 : EVS_CHUNK;
     const int common = m0 == 0;
     const evs_slots S = eval_chunk_slots(A, m0, m_cnt);
-    if (width == 21)
-      hipLaunchKernelGGL(eval_wide_kernel<21>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common, lt,
-                         ws->eval_partials);
-    else
-      hipLaunchKernelGGL(eval_wide_kernel<5>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0, m_cnt, common, lt,
-                         ws->eval_partials);
+    BEAR_DISPATCH_W(width, hipLaunchKernelGGL(eval_wide_kernel<W>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0,
+                                              m_cnt, common, lt, ws->eval_partials));
     hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
   }
   HIP_TRY(hipGetLastError());
@@ -170,18 +160,12 @@ static int launch_ref_wide(bear_ws *ws, const uint32_t *train, const uint32_t *r
   if (st != BEAR_OK) return st;
   if (!out || (n_rows && (!train || !ref))) return BEAR_ERR_INVALID_ARG;
   if (misaligned(train) || misaligned(ref) || misaligned8(out) || misaligned8(theta) || !(prm.eps >= 0.0)) return BEAR_ERR_INVALID_ARG;
-  const uint64_t tile = (uint64_t)(width == 21 ? RFW_TILE(21) : RFW_TILE(5));
-  const int grid = grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, RFW_BLOCKS_PER_CU));
+  const int grid = wide_grid(ws, n_rows, RFW_TILE(width), RFW_BLOCKS_PER_CU);
   const bear_step_io io = ws_io(ws, theta, BEAR_THETA_REF, out);
   const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
-#define REF_WIDE(W, AR) \
+#define REF_WIDE(AR) \
   hipLaunchKernelGGL((dm_ref_wide_kernel<W, AR>), dim3(grid), dim3(RFW_THREADS), 0, s, train, ref, n_rows, prm, lt, ws->partials, io, apply)
-#define REF_WIDE_21(AR) REF_WIDE(21, AR)
-#define REF_WIDE_5(AR) REF_WIDE(5, AR)
-  if (width == 21) BEAR_DISPATCH_1(train_ar, REF_WIDE_21);
-  else BEAR_DISPATCH_1(train_ar, REF_WIDE_5);
-#undef REF_WIDE_5
-#undef REF_WIDE_21
+  BEAR_DISPATCH_W(width, BEAR_DISPATCH_1(train_ar, REF_WIDE));
 #undef REF_WIDE
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
@@ -228,19 +212,13 @@ int bear_dm_refmix_wide_grad_f64(bear_ws *ws, const uint32_t *counts, const doub
       misaligned8(h_signed_dev) || misaligned8(tau_signed_dev) || misaligned8(net_weight_signed_dev) || !(eps >= 0.0))
     return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const uint64_t tile = (uint64_t)(width == 21 ? RMW_TILE(21) : RMW_TILE(5));
-  const int grid = grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, RMW_BLOCKS_PER_CU));
+  const int grid = wide_grid(ws, n_rows, RMW_TILE(width), RMW_BLOCKS_PER_CU);
   const bear_step_io io = ws_io(ws, nullptr, BEAR_THETA_REF, out);
   const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
-#define MIX_WIDE(W, AR)                                                                                                             \
+#define MIX_WIDE(AR)                                                                                                                \
   hipLaunchKernelGGL((dm_refmix_wide_kernel<W, AR>), dim3(grid), dim3(RFW_THREADS), 0, s, counts, net_rows, ref, n_rows, h_signed_dev, \
                      tau_signed_dev, net_weight_signed_dev, eps, lt, grad_net_rows, ws->partials, io)
-#define MIX_WIDE_21(AR) MIX_WIDE(21, AR)
-#define MIX_WIDE_5(AR) MIX_WIDE(5, AR)
-  if (width == 21) BEAR_DISPATCH_1(train_ar, MIX_WIDE_21);
-  else BEAR_DISPATCH_1(train_ar, MIX_WIDE_5);
-#undef MIX_WIDE_5
-#undef MIX_WIDE_21
+  BEAR_DISPATCH_W(width, BEAR_DISPATCH_1(train_ar, MIX_WIDE));
 #undef MIX_WIDE
   HIP_TRY(hipGetLastError());
   return BEAR_OK;

@@ -957,10 +957,7 @@ static int logdir_sample_launch(const uint32_t *counts, const double *prior, uin
   uint64_t blocks = (n_rows * per_row + SMP_THREADS - 1) / SMP_THREADS;
   if (blocks > 65536) blocks = 65536;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (width == 21)
-    hipLaunchKernelGGL(logdir_sample_kernel<21>, dim3((unsigned)blocks), dim3(SMP_THREADS), 0, s, counts, prior, n_rows, A, out);
-  else
-    hipLaunchKernelGGL(logdir_sample_kernel<5>, dim3((unsigned)blocks), dim3(SMP_THREADS), 0, s, counts, prior, n_rows, A, out);
+  BEAR_DISPATCH_W(width, hipLaunchKernelGGL(logdir_sample_kernel<W>, dim3((unsigned)blocks), dim3(SMP_THREADS), 0, s, counts, prior, n_rows, A, out));
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }

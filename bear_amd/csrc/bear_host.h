@@ -64,6 +64,19 @@ static inline bool wide_width_ok(int width) { return width == 5 || width == 21; 
     else F(false);            \
   } while (0)
 
+// `launch` with the row width of an entry that takes one (wide_width_ok: 5 or 21) as the compile-time integer W: the first template
+// parameter of the width-generic kernels.  Around a BEAR_DISPATCH_1 / _2 the flags come behind it.
+#define BEAR_DISPATCH_W(width, launch) \
+  do {                                 \
+    if ((width) == 21) {               \
+      constexpr int W = 21;            \
+      launch;                          \
+    } else {                           \
+      constexpr int W = 5;             \
+      launch;                          \
+    }                                  \
+  } while (0)
+
 // ------------------------------------------------------------------ kernel parameters by value (bear_common.h, bear_params)
 // every field a kernel does not read is zero.  params_eps: the constants come from device-resident parameters (bear_params_of)
 static inline bear_params params_eps(double eps) {
@@ -99,6 +112,10 @@ static inline int grid_capped(uint64_t work, uint64_t cap) {
 static inline uint64_t ws_blocks(const bear_ws *ws, int per_cu) {
   const uint64_t g = (uint64_t)ws->num_cu * per_cu;
   return g > (uint64_t)ws->max_blocks ? (uint64_t)ws->max_blocks : g;
+}
+// ... the grid of a wide row kernel: tiles of `tile` contexts, per_cu resident blocks
+static inline int wide_grid(const bear_ws *ws, uint64_t n_rows, uint64_t tile, int per_cu) {
+  return grid_capped((n_rows + tile - 1) / tile, ws_blocks(ws, per_cu));
 }
 
 // the planned step kernels: one resident 1024-thread block per CU (LDS ring; the half-tile build: two of 512)

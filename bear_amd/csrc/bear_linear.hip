@@ -22,8 +22,8 @@ int linear_ws_setup(bear_ws *ws) {
   if (st != BEAR_OK) return st;
   st = allow_dynamic_lds({BEAR_KFN(dm_linear_wide_kernel<false>), BEAR_KFN(dm_linear_wide_kernel<true>)}, LSW_LDS(LINEAR_WIDE_MAX_LAG));
   if (st != BEAR_OK) return st;
-  static_assert(LSW_PARTIAL_ROWS(1) == LNW_PARTIAL_ROWS(1), "linw_partials: one buffer for the backward rows and the fused step");
-  HIP_TRY(hipMalloc(&ws->linw_partials, sizeof(double) * LSW_MAX_PACKED * LSW_PARTIAL_ROWS(ws->num_cu)));
+  // one buffer for the backward rows and the fused step: the same grid cap, the longer row
+  HIP_TRY(hipMalloc(&ws->linw_partials, sizeof(double) * LSW_MAX_PACKED * WIDE_PARTIAL_ROWS(ws->num_cu, LNW_BWD_BLOCKS_PER_CU)));
   HIP_TRY(hipMalloc(&ws->linw_packed, sizeof(double) * LSW_MAX_PACKED));
   HIP_TRY(hipMalloc(&ws->lin_partials, sizeof(double) * LIN_MAX_GRAD * (size_t)ws->num_cu * PLN_BLOCKS_PER_CU));
   HIP_TRY(hipMalloc(&ws->lin_accum, sizeof(double) * LIN_MAX_GRAD));
@@ -332,7 +332,7 @@ int bear_linear_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_r
 // ---- bear_net's step with the linear AR function at the protein alphabet's width as one launch (kernels_linear_wide.h) ------------
 // the grid is part of the result (block partials summed in a fixed order per grid); linw_partials holds a row per block
 static int linstep_wide_grid(const bear_ws *ws, uint64_t n_rows) {
-  return grid_capped((n_rows + LSW_TILE - 1) / LSW_TILE, (uint64_t)ws->num_cu * LSW_BLOCKS_PER_CU);
+  return grid_capped((n_rows + LNW_BWD_TILE - 1) / LNW_BWD_TILE, (uint64_t)ws->num_cu * LSW_BLOCKS_PER_CU);
 }
 
 // the checks and the launch of all three entries: theta != NULL: h_signed and mat from the device-resident parameters (prm: eps only);

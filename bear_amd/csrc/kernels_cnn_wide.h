@@ -16,7 +16,7 @@
 //   forward : one context per lane.  LDS: the filter image (a row (w, a) of 30 doubles at a stride of 31: rows of different letters
 //             start an odd number of doubles apart -- conflict-free ds_read_b64, lanes with the same letter broadcast), weights1,
 //             scale0 / intercept0 (read at wave-uniform addresses), the exp table, the tile's code bytes and its rows, which leave
-//             as 16-byte nontemporal stores (lnw_store_tile).  The rows do not depend on the grid.
+//             as 16-byte nontemporal stores (wide_store_tile).  The rows do not depend on the grid.
 //   backward: per tile of 64 contexts.  Wave 0 (lane = context) runs everything that is per context: softmax and layer-1 backward
 //             (-> dT1 [16]), then position by position the conv row again, its layer norm and elu, d e0 = dT1 weights1[p]^T and back
 //             through elu and layer norm to dconv [30]; it leaves its rows in LDS.  EVERY sum over contexts is then an fp64 matrix
@@ -40,7 +40,7 @@
 #include "bear_common.h"
 #include "kernels_cnn.h"          // cnn_dims, cnn_elu, cnn_rsqrt, cnn_layer1
 #include "kernels_rows.h"         // stage_dwords
-#include "rows_wide_common.h"     // lnw_store_tile, lnw_sum_partials
+#include "rows_wide_common.h"     // wide_store_tile, wide_stage_codes, lnw_sum_partials
 
 #define CNW_W 21
 #define CNW_FS 31                                      // doubles between the filter rows (w, a) in LDS: odd
@@ -71,9 +71,16 @@ static inline cnn_dims cnw_make_dims(int lag, int fw) {
 static_assert(cnw_total(12, 8) == 8129, "parameter count at lag 12, filter width 8");
 static_assert(cnw_total(CNN_WIDE_MAX_LAG, 1) <= CNW_MAX_TOTAL, "partials row");
 
-// the filter image: row (w, a) at CNW_FS doubles
+// what every position of every context reads, once per block into LDS: scale0 and intercept0 [P][30], weights1 [P][30][16] and the
+// filter image (row (w, a) at CNW_FS doubles)
 template <int NT>
-__device__ __forceinline__ void cnw_stage_filters(double *Fs, const double *__restrict__ params, const cnn_dims &D) {
+__device__ __forceinline__ void cnw_stage_params(double *S0, double *B0, double *W1, double *Fs, const double *__restrict__ params,
+                                                 const cnn_dims &D) {
+  for (int k = threadIdx.x; k < D.P * CNN_NF; k += NT) {
+    S0[k] = params[D.os0 + k];
+    B0[k] = params[D.ob0 + k];
+  }
+  for (int k = threadIdx.x; k < D.P * CNN_NF * CNN_L1; k += NT) W1[k] = params[D.oW1 + k];
   for (int k = threadIdx.x; k < CNW_FROWS(D.fw) * CNN_NF; k += NT) {
     const int r = k / CNN_NF, f = k - r * CNN_NF;
     Fs[r * CNW_FS + f] = params[D.oF + k];
@@ -138,24 +145,14 @@ __global__ __launch_bounds__(CNW_FWD_THREADS) void cnn_wide_forward_kernel(const
   double *Fs = W1 + D.P * CNN_NF * CNN_L1;
   const uint32_t tid = threadIdx.x;
   if (tid < BEAR_EXPTAB_N) exptab[tid] = exp2((double)tid * (1.0 / BEAR_EXPTAB_N));
-  for (int k = tid; k < D.P * CNN_NF; k += CNW_FWD_THREADS) {
-    S0[k] = params[D.os0 + k];
-    B0[k] = params[D.ob0 + k];
-  }
-  for (int k = tid; k < D.P * CNN_NF * CNN_L1; k += CNW_FWD_THREADS) W1[k] = params[D.oW1 + k];
-  cnw_stage_filters<CNW_FWD_THREADS>(Fs, params, D);
+  cnw_stage_params<CNW_FWD_THREADS>(S0, B0, W1, Fs, params, D);
   const int lag = D.lag;
   const uint64_t n_tiles = (n + CNW_FWD_TILE - 1) / CNW_FWD_TILE;
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const uint64_t row0 = tile * CNW_FWD_TILE;
     const uint32_t rows = (uint32_t)((n - row0 < (uint64_t)CNW_FWD_TILE) ? (n - row0) : (uint64_t)CNW_FWD_TILE);
     __syncthreads();   // the previous tile has left R and s_c (and the tables are in place)
-    {
-      const uint32_t n_bytes = rows * (uint32_t)lag;     // whole dwords as 16-byte loads, the last bytes one by one (nothing is read
-      const int8_t *src = codes + row0 * (uint64_t)lag;  // beyond the matrix; row0 lag is a multiple of 16)
-      stage_dwords<CNW_FWD_THREADS>(reinterpret_cast<uint32_t *>(s_c), reinterpret_cast<const uint32_t *>(src), n_bytes >> 2);
-      for (uint32_t i = (n_bytes & ~3u) + tid; i < n_bytes; i += CNW_FWD_THREADS) s_c[i] = src[i];
-    }
+    wide_stage_codes<CNW_FWD_THREADS>(s_c, codes, row0, rows, lag);
     __syncthreads();
     if (tid < rows) {
       const int8_t *c = s_c + tid * (uint32_t)lag;
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(CNW_FWD_THREADS) void cnn_wide_forward_kernel(const
       for (int b = 0; b < CNW_W; ++b) r[b] = z[b] * rt;
     }
     __syncthreads();
-    lnw_store_tile<CNW_FWD_THREADS>(R, prior + row0 * CNW_W, rows);
+    wide_store_tile<CNW_FWD_THREADS, CNW_W>(R, prior + row0 * CNW_W, rows);
   }
 }
 
@@ -220,8 +217,6 @@ __global__ __launch_bounds__(CNW_FWD_THREADS) void cnn_wide_forward_kernel(const
 #define CNW_RT_PER_WAVE ((CNW_MAX_RT + CNW_BWD_WAVES - 1) / CNW_BWD_WAVES)
 #define CNW_P_PER_WAVE ((CNN_WIDE_MAX_LAG + CNW_BWD_WAVES - 1) / CNW_BWD_WAVES)
 static_assert(CNN_WIDE_MAX_LAG <= 16, "d intercept0 | d scale0: the positions are the rows of one MFMA tile");
-// rows of the partials buffer: one per block, then one per residue class of the block numbers (bear_arrive_last's counters)
-#define CNW_PARTIAL_ROWS(num_cu) ((size_t)(num_cu) * CNW_BWD_BLOCKS_PER_CU + BEAR_ARRIVE_SUBS)
 // the staged rows of a tile (strides in doubles: odd, lane = context writes without conflicts).  The head's rows share their
 // place with the positions': the head's products are done before the first position is staged.
 #define CNW_TS 17                                      // dT1 [16]
@@ -270,12 +265,7 @@ __global__ __launch_bounds__(CNW_BWD_THREADS) void cnn_wide_backward_kernel(cons
   const int lag = D.lag, P = D.P;
   const int n_frows = CNW_FROWS(D.fw), n_rt = (n_frows + 15) / 16;
   if (tid < BEAR_EXPTAB_N) exptab[tid] = exp2((double)tid * (1.0 / BEAR_EXPTAB_N));
-  for (int k = tid; k < D.P * CNN_NF; k += CNW_BWD_THREADS) {
-    S0[k] = params[D.os0 + k];
-    B0[k] = params[D.ob0 + k];
-  }
-  for (int k = tid; k < D.P * CNN_NF * CNN_L1; k += CNW_BWD_THREADS) W1s[k] = params[D.oW1 + k];
-  cnw_stage_filters<CNW_BWD_THREADS>(Fs, params, D);
+  cnw_stage_params<CNW_BWD_THREADS>(S0, B0, W1s, Fs, params, D);
   // this lane's row of the one-hot operand in each of the wave's filter row tiles: tap and letter (a letter no code has beyond the end)
   int own_w[CNW_RT_PER_WAVE], own_a[CNW_RT_PER_WAVE];
   lnw_d4 accF[CNW_RT_PER_WAVE][2], accW[CNW_P_PER_WAVE][2], accH[4];
@@ -296,8 +286,8 @@ __global__ __launch_bounds__(CNW_BWD_THREADS) void cnn_wide_backward_kernel(cons
     const uint64_t row0 = tile * CNW_BWD_TILE;
     const uint32_t rows = (uint32_t)((n - row0 < (uint64_t)CNW_BWD_TILE) ? (n - row0) : (uint64_t)CNW_BWD_TILE);
     __syncthreads();   // the previous tile's products are done with the staged rows (and the tables are in place)
-    {
-      const uint32_t n_bytes = rows * (uint32_t)lag;     // (as the forward kernel)
+    {   // wide_stage_codes, written out: the call costs this kernel, at 256 + 196 registers, further spills of scalar registers
+      const uint32_t n_bytes = rows * (uint32_t)lag;
       const int8_t *src = codes + row0 * (uint64_t)lag;
       stage_dwords<CNW_BWD_THREADS>(reinterpret_cast<uint32_t *>(s_c), reinterpret_cast<const uint32_t *>(src), n_bytes >> 2);
       for (uint32_t i = (n_bytes & ~3u) + tid; i < n_bytes; i += CNW_BWD_THREADS) s_c[i] = src[i];

@@ -8,12 +8,13 @@
 //            device-resident theta = [h_signed, mat...] when the launch carries one (bear_params_of): the step can be captured.
 //   stage  = the tile's uint32 count rows (10.5 KiB) and int8 code bytes as 16-byte loads (stage_dwords).
 //   forward= one context per lane of the lower two waves.  A context without counts forms no row and no item (exact zeros).  Else the
-//            logits from the LDS rows of mat, the max-shifted softmax on the exp table: the arithmetic and operation order of
-//            linear_wide_forward_kernel -- the row f (LDS) has the bits of the row entry.
+//            logits from the LDS rows of mat, the max-shifted softmax on the exp table: the same routine as
+//            linear_wide_forward_kernel's (lnw_forward_row) -- the row f (LDS) has the bits of the row entry.
 //   DM     = wide_dm_row<21, AR, true> (rows_wide_common.h, the body of dm_wide_kernel) on the staged counts and f: q = d LL / d f into a
 //            second LDS row array, sum LL and d / d h per lane.
-//   back   = g = f (q - <f, q>) in place over q, then the fp64 MFMA product onehot^T g of linear_wide_backward_kernel: row tiles of 16
-//            over r = 21 l + a, column tiles 16 + 5, a wave owns the row tiles wave, wave + 4, ..., accumulators in registers for the
+//   back   = g = f (q - <f, q>) in place over q (lnw_softmax_back_row), then the fp64 MFMA product onehot^T g of
+//            linear_wide_backward_kernel (lnw_onehot_product, on that kernel's block and tile: LNW_BWD_*): row tiles of 16 over
+//            r = 21 l + a, column tiles 16 + 5, a wave owns the row tiles wave, wave + 4, ..., accumulators in registers for the
 //            whole grid-stride loop, the one-hot operand from the code bytes, a tile whose g is zero everywhere skipped.
 //   finish = no floating-point atomics.  A block leaves one partial row [sum LL, d/dh, d/d mat] (2 + 441 lag doubles: the packed layout)
 //            in the workspace; lnw_sum_partials sums the rows in a fixed order in two levels straight into `packed`; the block that does
@@ -23,16 +24,14 @@
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"
-#include "kernels_linrows_wide.h"   // LNW_MAT, LNW_MAX_GRAD; rows_wide_common.h
+#include "kernels_linrows_wide.h"   // LNW_MAT, LNW_MAX_GRAD, LNW_BWD_*, the row steps and the product; rows_wide_common.h
 
-#define LSW_THREADS 256
-#define LSW_WAVES (LSW_THREADS / 64)
+#define LSW_THREADS LNW_BWD_THREADS
+// the tile and the grid cap (part of the result) as kernels.py names them: those of the product, whose buffer linw_partials is
 #define LSW_TILE 128
-#define LSW_BLOCKS_PER_CU 2                            // the grid cap (part of the result) and the rows of the partials buffer
-#define LSW_MAX_RT ((LINEAR_WIDE_MAX_LAG * LNW_W + 15) / 16)
-#define LSW_RT_PER_WAVE ((LSW_MAX_RT + LSW_WAVES - 1) / LSW_WAVES)
+#define LSW_BLOCKS_PER_CU 2
+static_assert(LSW_TILE == LNW_BWD_TILE && LSW_BLOCKS_PER_CU == LNW_BWD_BLOCKS_PER_CU, "the fused step runs lnw_onehot_product");
 #define LSW_MAX_PACKED (2 + LNW_MAX_GRAD)              // doubles of a partial row and of `packed`
-#define LSW_PARTIAL_ROWS(num_cu) ((size_t)(num_cu) * LSW_BLOCKS_PER_CU + BEAR_ARRIVE_SUBS)
 #define LSW_LDS(lag) (sizeof(double) * (size_t)(lag) * LNW_MAT)     // dynamic: mat
 
 template <bool AR>
@@ -42,13 +41,13 @@ __global__ __launch_bounds__(LSW_THREADS, 2) void dm_linear_wide_kernel(const ui
                                                                      double *__restrict__ partials, const bear_step_io io,
                                                                      const bear_apply_io apply) {
   extern __shared__ __attribute__((aligned(16))) double lsw_mat[];
-  __shared__ __attribute__((aligned(16))) uint32_t s_cnt[LSW_TILE * LNW_W];
-  __shared__ __attribute__((aligned(16))) double s_f[LSW_TILE * LNW_W];
-  __shared__ __attribute__((aligned(16))) double s_g[LSW_TILE * LNW_W];          // q rows, then g in place
-  __shared__ __attribute__((aligned(16))) int8_t s_c[LSW_TILE * LINEAR_WIDE_MAX_LAG];
+  __shared__ __attribute__((aligned(16))) uint32_t s_cnt[LNW_BWD_TILE * LNW_W];
+  __shared__ __attribute__((aligned(16))) double s_f[LNW_BWD_TILE * LNW_W];
+  __shared__ __attribute__((aligned(16))) double s_g[LNW_BWD_TILE * LNW_W];      // q rows, then g in place
+  __shared__ __attribute__((aligned(16))) int8_t s_c[LNW_BWD_TILE * LINEAR_WIDE_MAX_LAG];
   __shared__ double2 s_log[BEAR_LOGTAB_N];
   __shared__ double s_exp[BEAR_EXPTAB_N];
-  __shared__ double s_red[LSW_WAVES][2];
+  __shared__ double s_red[LNW_BWD_WAVES][2];
   __shared__ unsigned s_flag;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -59,100 +58,40 @@ __global__ __launch_bounds__(LSW_THREADS, 2) void dm_linear_wide_kernel(const ui
   if (tid < BEAR_LOGTAB_N) s_log[tid] = logtab_g[tid];
   if (tid < BEAR_EXPTAB_N) s_exp[tid] = exp2((double)tid * (1.0 / BEAR_EXPTAB_N));
   for (int k = tid; k < n_grad; k += LSW_THREADS) lsw_mat[k] = mat[k];
-  lnw_d4 acc[LSW_RT_PER_WAVE][2];
+  lnw_d4 acc[LNW_RT_PER_WAVE][2];
 #pragma unroll
-  for (int j = 0; j < LSW_RT_PER_WAVE; ++j) acc[j][0] = acc[j][1] = lnw_d4{0.0, 0.0, 0.0, 0.0};
+  for (int j = 0; j < LNW_RT_PER_WAVE; ++j) acc[j][0] = acc[j][1] = lnw_d4{0.0, 0.0, 0.0, 0.0};
   double sums[2] = {0.0, 0.0};
-  const uint64_t n_tiles = (n + LSW_TILE - 1) / LSW_TILE;
+  const uint64_t n_tiles = (n + LNW_BWD_TILE - 1) / LNW_BWD_TILE;
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const uint64_t row0 = tile * LSW_TILE;
-    const uint32_t rows = (uint32_t)((n - row0 < (uint64_t)LSW_TILE) ? (n - row0) : (uint64_t)LSW_TILE);
+    const uint64_t row0 = tile * LNW_BWD_TILE;
+    const uint32_t rows = (uint32_t)((n - row0 < (uint64_t)LNW_BWD_TILE) ? (n - row0) : (uint64_t)LNW_BWD_TILE);
     __syncthreads();   // the previous tile's products are done with the LDS rows (and the tables are in place)
     stage_dwords<LSW_THREADS>(s_cnt, counts + row0 * LNW_W, rows * LNW_W);
-    {
-      const uint32_t n_bytes = rows * (uint32_t)lag;     // whole dwords as 16-byte loads, the last bytes one by one (nothing is read
-      const int8_t *src = codes + row0 * (uint64_t)lag;  // beyond the matrix)
-      stage_dwords<LSW_THREADS>(reinterpret_cast<uint32_t *>(s_c), reinterpret_cast<const uint32_t *>(src), n_bytes >> 2);
-      for (uint32_t i = (n_bytes & ~3u) + tid; i < n_bytes; i += LSW_THREADS) s_c[i] = src[i];
-    }
+    wide_stage_codes<LSW_THREADS>(s_c, codes, row0, rows, lag);
     __syncthreads();
     bool nz = false;
-    if (tid < LSW_TILE) {
+    if (tid < LNW_BWD_TILE) {
       const uint32_t *c = s_cnt + tid * LNW_W;
       double *f = s_f + tid * LNW_W;
       double *g = s_g + tid * LNW_W;
       if (tid < rows && wide_nz_mask<LNW_W>(c) != 0u) {
-        {   // ---- forward: linear_wide_forward_kernel's row
-          const int8_t *cd = s_c + tid * (uint32_t)lag;
-          double z[LNW_W];
-#pragma unroll
-          for (int b = 0; b < LNW_W; ++b) z[b] = 0.0;
-          for (int l = 0; l < lag; ++l) {
-            const uint32_t a = (uint32_t)(int)cd[l];
-            if (a < (uint32_t)LNW_W) {                   // anything else: an all-zero one-hot row
-              const double *m = lsw_mat + (l * LNW_W + (int)a) * LNW_W;
-#pragma unroll
-              for (int b = 0; b < LNW_W; ++b) z[b] += m[b];
-            }
-          }
-          double zmax = z[0];
-#pragma unroll
-          for (int b = 1; b < LNW_W; ++b) zmax = __builtin_fmax(zmax, z[b]);
-          double s = 0.0;
-#pragma unroll
-          for (int b = 0; b < LNW_W; ++b) {
-            z[b] = bear_exp_tab(z[b] - zmax, s_exp);
-            s += z[b];
-          }
-          const double inv = 1.0 / s;                    // s >= 1: the largest logit contributes exp(0)
-#pragma unroll
-          for (int b = 0; b < LNW_W; ++b) f[b] = z[b] * inv;
-        }
-        // ---- DM: q = d LL / d f into g's row
-        wide_dm_row<LNW_W, AR, true>(c, f, g, prm, s_log, sums);
-        // ---- softmax backward: g = f (q - <f, q>) = d LL / d logit
-        double s = 0.0;
-#pragma unroll
-        for (int b = 0; b < LNW_W; ++b) s = __builtin_fma(f[b], g[b], s);
-#pragma unroll
-        for (int b = 0; b < LNW_W; ++b) {
-          const double v = f[b] * (g[b] - s);
-          g[b] = v;
-          nz |= v != 0.0;
-        }
+        lnw_forward_row(s_c + tid * (uint32_t)lag, lag, lsw_mat, s_exp, f);
+        wide_dm_row<LNW_W, AR, true>(c, f, g, prm, s_log, sums);   // q = d LL / d f into g's row
+        nz = lnw_softmax_back_row(f, g);                           // g = d LL / d logit
       } else {                                           // no counts, or beyond the end: nothing forward, zeros backward
 #pragma unroll
         for (int b = 0; b < LNW_W; ++b) g[b] = 0.0;
       }
     }
     if (!__syncthreads_or(nz ? 1 : 0)) continue;         // contexts without counts: nothing to add (block-uniform)
-    // this lane's row of the one-hot operand in each of the wave's row tiles: position | letter << 8 (a letter no code has beyond the
-    // end).  Formed per tile, behind an opaque copy of the lane's coordinate: held across the item walk above, these registers and
-    // the 96 of the accumulators would not leave it the 256 of two blocks per CU without scratch.
+    // The lane's rows of the one-hot operand are formed per tile, behind an opaque copy of the lane's coordinate: held across the
+    // item walk above, these registers and the 96 of the accumulators would not leave it the 256 of two blocks per CU without scratch.
     uint32_t lr_t = lr;
     asm volatile("" : "+v"(lr_t));
-    int own[LSW_RT_PER_WAVE];
-#pragma unroll
-    for (int j = 0; j < LSW_RT_PER_WAVE; ++j) {
-      const int row = ((int)wave + LSW_WAVES * j) * 16 + (int)lr_t;
-      own[j] = row < n_rows_g ? (row / LNW_W) | ((row % LNW_W) << 8) : (1000 << 8);
-    }
-    // K = 4 contexts per product, contexts 16 apart per k index: 32 different double banks (kernels_linrows_wide.h)
-#pragma unroll 2
-    for (uint32_t ks = 0; ks < LSW_TILE / 4; ++ks) {
-      const uint32_t ctx = ((ks >> 4) << 6) + (ks & 15u) + 16u * lq;
-      const double b0 = s_g[ctx * LNW_W + lr];
-      const double b1 = lr < LNW_W - 16 ? s_g[ctx * LNW_W + 16 + lr] : 0.0;
-      const int8_t *cd = s_c + ctx * (uint32_t)lag;
-#pragma unroll
-      for (int j = 0; j < LSW_RT_PER_WAVE; ++j) {
-        if ((int)wave + LSW_WAVES * j < n_rt) {          // wave-uniform
-          const double a = (int)cd[own[j] & 255] == (own[j] >> 8) ? 1.0 : 0.0;
-          acc[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[j][1], 0, 0, 0);
-        }
-      }
-    }
+    int own[LNW_RT_PER_WAVE];
+    lnw_own_rows(wave, lr_t, n_rows_g, own);
+    lnw_onehot_product(s_g, s_c, lag, n_rt, wave, lq, lr, own, acc);
   }
   // ---- block partial in the packed layout: [sum LL, d/dh, d/d mat [lag * 21, 21]]
   const int n_packed = 2 + n_grad;
@@ -164,17 +103,7 @@ __global__ __launch_bounds__(LSW_THREADS, 2) void dm_linear_wide_kernel(const ui
   }
   __syncthreads();
   if (tid < 2) bear_store_agent(&mine[tid], (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]));
-  // result r of a lane is row lq + 4 r, column lr of its 16 x 16 tile
-#pragma unroll
-  for (int j = 0; j < LSW_RT_PER_WAVE; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = ((int)wave + LSW_WAVES * j) * 16 + (int)lq + 4 * r;
-      if (row < n_rows_g) {
-        bear_store_agent(&mine[2 + row * LNW_W + (int)lr], acc[j][0][r]);
-        if (lr < LNW_W - 16) bear_store_agent(&mine[2 + row * LNW_W + 16 + (int)lr], acc[j][1][r]);
-      }
-    }
+  lnw_store_acc(mine + 2, n_rows_g, wave, lq, lr, acc);
   // ---- fixed-order sum in two levels (rows_wide_common.h); the block that wrote `packed` runs the update behind it
   if (lnw_sum_partials<LSW_THREADS>(partials, n_packed, io.arrive(), &s_flag, io.out)) bear_apply_in_block(apply, io.out);
 }

@@ -22,13 +22,112 @@
 //             give the same bits, in both builds of the library (no deterministic twin).
 //             Grid: min(tiles of 128 contexts, 2 x CUs) blocks (bear_linear.hip, linwide_bwd_grid) -- part of the result.
 //             A tile whose g is zero everywhere (contexts without counts) is skipped.
+// The row steps (lnw_forward_row, lnw_softmax_back_row) and the product (lnw_own_rows, lnw_onehot_product, lnw_store_acc) are routines:
+// the fused step (kernels_linear_wide.h) runs the same ones on the same block and tile geometry (LNW_BWD_*).
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"
-#include "rows_wide_common.h"   // LNW_W, lnw_store_tile, lnw_sum_rows / lnw_sum_partials
+#include "rows_wide_common.h"   // LNW_W, wide_store_tile, wide_stage_codes, lnw_sum_rows / lnw_sum_partials
 
 #define LNW_MAT (LNW_W * LNW_W)                        // doubles of mat per position
 #define LNW_MAX_GRAD (LINEAR_WIDE_MAX_LAG * LNW_MAT)
+
+// the block of the backward kernel and of the fused step: four waves, tiles of 128 contexts, the (l, a) rows of d mat in tiles of 16
+#define LNW_BWD_THREADS 256
+#define LNW_BWD_WAVES (LNW_BWD_THREADS / 64)
+#define LNW_BWD_TILE 128                               // contexts per tile: 21 KiB of f rows + 21 KiB of q rows + the code bytes
+#define LNW_BWD_BLOCKS_PER_CU 2                        // the grid cap (part of the result) and the rows of the partials buffer
+#define LNW_MAX_RT ((LINEAR_WIDE_MAX_LAG * LNW_W + 15) / 16)                    // row tiles of 16 (l, a) pairs
+#define LNW_RT_PER_WAVE ((LNW_MAX_RT + LNW_BWD_WAVES - 1) / LNW_BWD_WAVES)
+
+// ------------------------------------------------------------------ the steps of one context
+// f = softmax_b(sum_l M[l, cd[l], b]): the logits from the LDS image M of mat, the max-shifted softmax on the exp table
+__device__ __forceinline__ void lnw_forward_row(const int8_t *cd, int lag, const double *M, const double *exptab, double *f) {
+  double z[LNW_W];
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) z[b] = 0.0;
+  for (int l = 0; l < lag; ++l) {
+    const uint32_t a = (uint32_t)(int)cd[l];
+    if (a < (uint32_t)LNW_W) {                           // anything else: an all-zero one-hot row
+      const double *m = M + (l * LNW_W + (int)a) * LNW_W;
+#pragma unroll
+      for (int b = 0; b < LNW_W; ++b) z[b] += m[b];
+    }
+  }
+  double zmax = z[0];
+#pragma unroll
+  for (int b = 1; b < LNW_W; ++b) zmax = __builtin_fmax(zmax, z[b]);
+  double s = 0.0;
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) {
+    z[b] = bear_exp_tab(z[b] - zmax, exptab);
+    s += z[b];
+  }
+  const double inv = 1.0 / s;                            // s >= 1: the largest logit contributes exp(0)
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) f[b] = z[b] * inv;
+}
+
+// softmax backward in place over the row q = d L / d f:  g = f (q - <f, q>) = d L / d logit; true if any entry is not zero
+__device__ __forceinline__ bool lnw_softmax_back_row(const double *f, double *g) {
+  double s = 0.0;
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) s = __builtin_fma(f[b], g[b], s);
+  bool nz = false;
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) {
+    const double v = f[b] * (g[b] - s);
+    g[b] = v;
+    nz |= v != 0.0;
+  }
+  return nz;
+}
+
+// ------------------------------------------------------------------ d mat += onehot^T g over one staged tile
+// this lane's row of the one-hot operand in each of the wave's row tiles: position | letter << 8 (a letter no code has beyond the end)
+__device__ __forceinline__ void lnw_own_rows(uint32_t wave, uint32_t lr, int n_rows_g, int (&own)[LNW_RT_PER_WAVE]) {
+#pragma unroll
+  for (int j = 0; j < LNW_RT_PER_WAVE; ++j) {
+    const int row = ((int)wave + LNW_BWD_WAVES * j) * 16 + (int)lr;
+    own[j] = row < n_rows_g ? (row / LNW_W) | ((row % LNW_W) << 8) : (1000 << 8);
+  }
+}
+
+// K = 4 contexts per product; product ks takes the contexts ks, ks + 16, ks + 32, ks + 48 of a group of 64 (k index lq): rows 16
+// apart are 336 doubles apart, 16 mod 32 -- the 32 lanes of an LDS cycle read 32 different double banks
+__device__ __forceinline__ void lnw_onehot_product(const double *s_g, const int8_t *s_c, int lag, int n_rt, uint32_t wave, uint32_t lq,
+                                                   uint32_t lr, const int (&own)[LNW_RT_PER_WAVE], lnw_d4 (&acc)[LNW_RT_PER_WAVE][2]) {
+#pragma unroll 2
+  for (uint32_t ks = 0; ks < LNW_BWD_TILE / 4; ++ks) {
+    const uint32_t ctx = ((ks >> 4) << 6) + (ks & 15u) + 16u * lq;
+    const double b0 = s_g[ctx * LNW_W + lr];
+    const double b1 = lr < LNW_W - 16 ? s_g[ctx * LNW_W + 16 + lr] : 0.0;
+    const int8_t *cd = s_c + ctx * (uint32_t)lag;
+#pragma unroll
+    for (int j = 0; j < LNW_RT_PER_WAVE; ++j) {
+      if ((int)wave + LNW_BWD_WAVES * j < n_rt) {        // wave-uniform
+        const double a = (int)cd[own[j] & 255] == (own[j] >> 8) ? 1.0 : 0.0;
+        acc[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[j][0], 0, 0, 0);
+        acc[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[j][1], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// the accumulators into the block's partial [lag * 21, 21] at dst: result r of a lane is row lq + 4 r, column lr of its 16 x 16 tile
+__device__ __forceinline__ void lnw_store_acc(double *dst, int n_rows_g, uint32_t wave, uint32_t lq, uint32_t lr,
+                                              const lnw_d4 (&acc)[LNW_RT_PER_WAVE][2]) {
+#pragma unroll
+  for (int j = 0; j < LNW_RT_PER_WAVE; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = ((int)wave + LNW_BWD_WAVES * j) * 16 + (int)lq + 4 * r;
+      if (row < n_rows_g) {
+        bear_store_agent(&dst[row * LNW_W + (int)lr], acc[j][0][r]);
+        if (lr < LNW_W - 16) bear_store_agent(&dst[row * LNW_W + 16 + (int)lr], acc[j][1][r]);
+      }
+    }
+}
 
 // ------------------------------------------------------------------ forward
 #define LNW_FWD_THREADS 512
@@ -52,48 +151,13 @@ __global__ __launch_bounds__(LNW_FWD_THREADS) void linear_wide_forward_kernel(co
     const uint64_t row0 = tile * LNW_FWD_TILE;
     const uint32_t rows = (uint32_t)((n - row0 < (uint64_t)LNW_FWD_TILE) ? (n - row0) : (uint64_t)LNW_FWD_TILE);
     __syncthreads();   // the previous tile has left R (and the tables are in place)
-    if (tid < rows) {
-      const int8_t *c = codes + (row0 + tid) * (uint64_t)lag;
-      double z[LNW_W];
-#pragma unroll
-      for (int b = 0; b < LNW_W; ++b) z[b] = 0.0;
-      for (int l = 0; l < lag; ++l) {
-        const uint32_t a = (uint32_t)(int)c[l];
-        if (a < (uint32_t)LNW_W) {                       // anything else: an all-zero one-hot row
-          const double *m = M + (l * LNW_W + (int)a) * LNW_W;
-#pragma unroll
-          for (int b = 0; b < LNW_W; ++b) z[b] += m[b];
-        }
-      }
-      double zmax = z[0];
-#pragma unroll
-      for (int b = 1; b < LNW_W; ++b) zmax = __builtin_fmax(zmax, z[b]);
-      double s = 0.0;
-#pragma unroll
-      for (int b = 0; b < LNW_W; ++b) {
-        z[b] = bear_exp_tab(z[b] - zmax, exptab);
-        s += z[b];
-      }
-      const double inv = 1.0 / s;                        // s >= 1: the largest logit contributes exp(0)
-      double *r = R + tid * LNW_W;
-#pragma unroll
-      for (int b = 0; b < LNW_W; ++b) r[b] = z[b] * inv;
-    }
+    if (tid < rows) lnw_forward_row(codes + (row0 + tid) * (uint64_t)lag, lag, M, exptab, R + tid * LNW_W);
     __syncthreads();
-    lnw_store_tile<LNW_FWD_THREADS>(R, prior + row0 * LNW_W, rows);
+    wide_store_tile<LNW_FWD_THREADS, LNW_W>(R, prior + row0 * LNW_W, rows);
   }
 }
 
 // ------------------------------------------------------------------ backward
-#define LNW_BWD_THREADS 256
-#define LNW_BWD_WAVES (LNW_BWD_THREADS / 64)
-#define LNW_BWD_TILE 128                               // contexts per tile: 21 KiB of f rows + 21 KiB of q rows + the code bytes
-#define LNW_BWD_BLOCKS_PER_CU 2                        // the grid cap (part of the result) and the rows of the partials buffer
-#define LNW_MAX_RT ((LINEAR_WIDE_MAX_LAG * LNW_W + 15) / 16)                    // row tiles of 16 (l, a) pairs
-#define LNW_RT_PER_WAVE ((LNW_MAX_RT + LNW_BWD_WAVES - 1) / LNW_BWD_WAVES)
-// rows of the partials buffer: one per block, then one per residue class of the block numbers (bear_arrive_last's counters)
-#define LNW_PARTIAL_ROWS(num_cu) ((size_t)(num_cu) * LNW_BWD_BLOCKS_PER_CU + BEAR_ARRIVE_SUBS)
-
 __global__ __launch_bounds__(LNW_BWD_THREADS) void linear_wide_backward_kernel(const int8_t *__restrict__ codes, uint64_t n, int lag,
                                                                                const double *__restrict__ prior,
                                                                                const double *__restrict__ grad_prior,
@@ -108,17 +172,11 @@ __global__ __launch_bounds__(LNW_BWD_THREADS) void linear_wide_backward_kernel(c
   const uint32_t lq = lane >> 4, lr = lane & 15u;        // MFMA lane coordinates: k / row-group index, row / column index
   const int n_grad = lag * LNW_MAT, n_rows_g = lag * LNW_W;
   const int n_rt = (n_rows_g + 15) / 16;
-  // this lane's row of the one-hot operand in each of the wave's row tiles: position and letter (a letter no code has beyond the end)
-  int own_l[LNW_RT_PER_WAVE], own_a[LNW_RT_PER_WAVE];
+  int own[LNW_RT_PER_WAVE];
+  lnw_own_rows(wave, lr, n_rows_g, own);
   lnw_d4 acc[LNW_RT_PER_WAVE][2];
 #pragma unroll
-  for (int j = 0; j < LNW_RT_PER_WAVE; ++j) {
-    const int row = ((int)wave + LNW_BWD_WAVES * j) * 16 + (int)lr;
-    const bool ok = row < n_rows_g;
-    own_l[j] = ok ? row / LNW_W : 0;
-    own_a[j] = ok ? row % LNW_W : 1000;
-    acc[j][0] = acc[j][1] = lnw_d4{0.0, 0.0, 0.0, 0.0};
-  }
+  for (int j = 0; j < LNW_RT_PER_WAVE; ++j) acc[j][0] = acc[j][1] = lnw_d4{0.0, 0.0, 0.0, 0.0};
   const uint64_t n_tiles = (n + LNW_BWD_TILE - 1) / LNW_BWD_TILE;
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const uint64_t row0 = tile * LNW_BWD_TILE;
@@ -128,63 +186,22 @@ __global__ __launch_bounds__(LNW_BWD_THREADS) void linear_wide_backward_kernel(c
                                   rows * LNW_W * 2);
     stage_dwords<LNW_BWD_THREADS>(reinterpret_cast<uint32_t *>(s_g), reinterpret_cast<const uint32_t *>(grad_prior + row0 * LNW_W),
                                   rows * LNW_W * 2);
-    {
-      const uint32_t n_bytes = rows * (uint32_t)lag;     // whole dwords as 16-byte loads, the last bytes one by one (nothing is read
-      const int8_t *src = codes + row0 * (uint64_t)lag;  // beyond the matrix)
-      stage_dwords<LNW_BWD_THREADS>(reinterpret_cast<uint32_t *>(s_c), reinterpret_cast<const uint32_t *>(src), n_bytes >> 2);
-      for (uint32_t i = (n_bytes & ~3u) + tid; i < n_bytes; i += LNW_BWD_THREADS) s_c[i] = src[i];
-    }
+    wide_stage_codes<LNW_BWD_THREADS>(s_c, codes, row0, rows, lag);
     __syncthreads();
     bool nz = false;
-    if (tid < LNW_BWD_TILE) {      // softmax backward of this thread's context: g = f (q - <f, q>) = d L / d logit, zero beyond the end
-      const double *f = s_f + tid * LNW_W;
+    if (tid < LNW_BWD_TILE) {      // this thread's context: g = d L / d logit, zero beyond the end
       double *g = s_g + tid * LNW_W;
       if (tid < rows) {
-        double s = 0.0;
-#pragma unroll
-        for (int b = 0; b < LNW_W; ++b) s = __builtin_fma(f[b], g[b], s);
-#pragma unroll
-        for (int b = 0; b < LNW_W; ++b) {
-          const double v = f[b] * (g[b] - s);
-          g[b] = v;
-          nz |= v != 0.0;
-        }
+        nz = lnw_softmax_back_row(s_f + tid * LNW_W, g);
       } else {
 #pragma unroll
         for (int b = 0; b < LNW_W; ++b) g[b] = 0.0;
       }
     }
     if (!__syncthreads_or(nz ? 1 : 0)) continue;         // contexts without counts: nothing to add (block-uniform)
-    // K = 4 contexts per product; product ks takes the contexts ks, ks + 16, ks + 32, ks + 48 of a group of 64 (k index lq): rows 16
-    // apart are 336 doubles apart, 16 mod 32 -- the 32 lanes of an LDS cycle read 32 different double banks
-#pragma unroll 2
-    for (uint32_t ks = 0; ks < LNW_BWD_TILE / 4; ++ks) {
-      const uint32_t ctx = ((ks >> 4) << 6) + (ks & 15u) + 16u * lq;
-      const double b0 = s_g[ctx * LNW_W + lr];
-      const double b1 = lr < LNW_W - 16 ? s_g[ctx * LNW_W + 16 + lr] : 0.0;
-      const int8_t *c = s_c + ctx * (uint32_t)lag;
-#pragma unroll
-      for (int j = 0; j < LNW_RT_PER_WAVE; ++j) {
-        if ((int)wave + LNW_BWD_WAVES * j < n_rt) {       // wave-uniform
-          const double a = (int)c[own_l[j]] == own_a[j] ? 1.0 : 0.0;
-          acc[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[j][0], 0, 0, 0);
-          acc[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[j][1], 0, 0, 0);
-        }
-      }
-    }
+    lnw_onehot_product(s_g, s_c, lag, n_rt, wave, lq, lr, own, acc);
   }
-  // block partial [lag * 21, 21]: result r of a lane is row lq + 4 r, column lr of its 16 x 16 tile
-  double *mine = partials + (size_t)blockIdx.x * n_grad;
-#pragma unroll
-  for (int j = 0; j < LNW_RT_PER_WAVE; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = ((int)wave + LNW_BWD_WAVES * j) * 16 + (int)lq + 4 * r;
-      if (row < n_rows_g) {
-        bear_store_agent(&mine[row * LNW_W + (int)lr], acc[j][0][r]);
-        if (lr < LNW_W - 16) bear_store_agent(&mine[row * LNW_W + 16 + (int)lr], acc[j][1][r]);
-      }
-    }
+  lnw_store_acc(partials + (size_t)blockIdx.x * n_grad, n_rows_g, wave, lq, lr, acc);
   // ---- fixed-order sum in two levels over the counters of bear_arrive_last (rows_wide_common.h)
   lnw_sum_partials<LNW_BWD_THREADS>(partials, n_grad, arrive, &s_flag, grad_mat);
 }

@@ -30,6 +30,7 @@
 #include "bear_common.h"
 #include "kernels_rows.h"
 #include "kernels_wide.h"
+#include "rows_wide_common.h"   // wide_nz_mask, wide_store_tile
 
 #define RFW_THREADS 256
 // dm_ref_wide_kernel, W = 21: 256 contexts = two count tiles of 21 KiB (+ 2 KiB log table): a context on every thread, three blocks
@@ -109,20 +110,72 @@ __device__ __forceinline__ double rfw_log(double p, const double2 *s_log) {
   return fabs(p - 1.0) < 0x1p-8 ? bear_log1p_small(p - 1.0) : (p > 0.0 ? bear_log_tab(p, s_log) : bear_log(p));
 }
 
-// the constants of a step from three device-resident parameters (bear_params_of reads them from one vector)
-__device__ __forceinline__ bear_params rfw_params(const double *__restrict__ h_s, const double *__restrict__ tau_s,
-                                                  const double *__restrict__ nw_s, double eps) {
-  bear_params p;
-  const double tau = exp(tau_s[0]), nw = exp(nw_s[0]);
-  const double E = exp(-tau);
-  p.eps = eps;
-  p.inv_h = bear_uniform_f64(1.0 / exp(h_s[0]));
-  p.E = bear_uniform_f64(E);
-  p.tauE = bear_uniform_f64(tau * E);
-  p.tau = bear_uniform_f64(tau);
-  p.V = bear_uniform_f64(1.0 / (nw + 1.0));
-  p.nw = bear_uniform_f64(nw);
-  return p;
+// One context of either kernel: c and rf its staged count and reference rows; acc += [LL, d/dh_signed, d/dtau_signed, d/dnu_signed].
+//   MIX   g its net row in, d sum LL / d g out in place (a context without training counts: exact zeros)
+//   else  the stop net function: g_b = [b == W - 1] and sum g = 1 are constants, g is not touched and no row is written.  The
+//         expressions are the same ones (no contraction: fma(nw, 1, x) is nw + x), so a stop row through MIX gives these bits.
+template <int W, bool AR, bool MIX>
+__device__ __forceinline__ void rfw_row(const uint32_t *c, const uint32_t *rf, double *g, const bear_params &prm, const double2 *s_log,
+                                        double (&acc)[4]) {
+  uint32_t nz = wide_nz_mask<W>(c);
+  if (!nz) {                         // no training counts: nothing of this context enters any sum
+    if (MIX) {
+#pragma unroll
+      for (int b = 0; b < W; ++b) g[b] = 0.0;
+    }
+    return;
+  }
+  const double nwV = prm.nw * prm.V;
+  const double R = rfw_ref_total<W>(rf, prm.eps), invR = 1.0 / R;
+  double ll = 0.0, dh = 0.0, dt = 0.0, dn = 0.0, scale = 1.0, g0 = 0.0;   // sums over the cells of P_b (AR: c_b / p_b) times f, df/dtau, df/dnu
+  bear_dp tn = {0.0, 0.0};
+  if (!AR) {
+    double n = 0.0, sg = MIX ? 0.0 : 1.0;
+#pragma unroll
+    for (int b = 0; b < W; ++b) {
+      n += (double)c[b];
+      if (MIX) sg += g[b];
+    }
+    const double sdev = rfw_dev_total<W>(rf, prm.eps, R, invR);
+    const double sf = __builtin_fma(prm.nw, sg, __builtin_fma(prm.E, sdev, 1.0)) * prm.V;
+    tn = dm_row_item(__builtin_fma(sf, prm.inv_h, (double)W * prm.eps), n, s_log);
+    ll = -tn.D;
+    dh = -tn.P * sf;
+    dt = tn.P * (prm.tauE * prm.V * sdev);
+    dn = -tn.P * (nwV * (sg - sf));
+    scale = prm.inv_h;
+    g0 = -tn.P * prm.inv_h * nwV;
+  }
+  if (MIX) {
+#pragma unroll
+    for (int b = 0; b < W; ++b)
+      if (!((nz >> b) & 1u)) g[b] = g0;
+  }
+  while (nz) {
+    const int b = __builtin_ctz(nz);
+    nz &= nz - 1u;
+    const double cb = (double)c[b];
+    const rfw_cell m = rfw_mix_cell<W>(rf, b, MIX ? g[b] : (b == W - 1 ? 1.0 : 0.0), R, invR, prm);
+    double q;
+    if (AR) {
+      const double p = m.f + prm.eps;
+      ll = __builtin_fma(cb, rfw_log(p, s_log), ll);
+      q = cb * bear_rcp(p);
+      if (MIX) g[b] = q * nwV;
+    } else {
+      const bear_dp tb = dm_row_item(__builtin_fma(m.f, prm.inv_h, prm.eps), cb, s_log);
+      ll += tb.D;
+      q = tb.P;
+      dh = __builtin_fma(q, m.f, dh);
+      if (MIX) g[b] = (tb.P - tn.P) * prm.inv_h * nwV;
+    }
+    dt = __builtin_fma(q, m.dft, dt);
+    dn = __builtin_fma(q, m.dfn, dn);
+  }
+  acc[0] += ll;
+  acc[1] -= dh * scale;              // d alpha_b / d h_signed = -f_b / h (AR: dh stays zero)
+  acc[2] += dt * scale;
+  acc[3] += dn * scale;
 }
 
 // ------------------------------------------------------------------ the stop net function
@@ -148,51 +201,8 @@ __global__ __launch_bounds__(RFW_THREADS) void dm_ref_wide_kernel(const uint32_t
     stage_dwords<RFW_THREADS>(s_ref, ref + row0 * W, rows * W);
     __syncthreads();
 #pragma unroll 1
-    for (uint32_t r = threadIdx.x; r < rows; r += RFW_THREADS) {
-      const uint32_t *c = s_trn + r * W;
-      const uint32_t *rf = s_ref + r * W;
-      uint32_t nz = wide_nz_mask<W>(c);
-      if (!nz) continue;               // no training counts: nothing of this context enters any sum
-      const double R = rfw_ref_total<W>(rf, prm.eps), invR = 1.0 / R;
-      double ll = 0.0, dh = 0.0, dt = 0.0, dn = 0.0, scale = 1.0;   // sums over the cells of P_b (AR: c_b / p_b) times f, df/dtau, df/dnu
-      bear_dp tn = {0.0, 0.0};
-      if (!AR) {
-        double n = 0.0;
-#pragma unroll
-        for (int b = 0; b < W; ++b) n += (double)c[b];
-        const double sdev = rfw_dev_total<W>(rf, prm.eps, R, invR);
-        const double sf = (prm.nw + __builtin_fma(prm.E, sdev, 1.0)) * prm.V;     // sum g = 1
-        tn = dm_row_item(__builtin_fma(sf, prm.inv_h, (double)W * prm.eps), n, s_log);
-        ll = -tn.D;
-        dh = -tn.P * sf;
-        dt = tn.P * (prm.tauE * prm.V * sdev);
-        dn = -tn.P * (prm.nw * prm.V * (1.0 - sf));
-        scale = prm.inv_h;
-      }
-      while (nz) {
-        const int b = __builtin_ctz(nz);
-        nz &= nz - 1u;
-        const double cb = (double)c[b];
-        const rfw_cell m = rfw_mix_cell<W>(rf, b, b == W - 1 ? 1.0 : 0.0, R, invR, prm);
-        double q;
-        if (AR) {
-          const double p = m.f + prm.eps;
-          ll = __builtin_fma(cb, rfw_log(p, s_log), ll);
-          q = cb * bear_rcp(p);
-        } else {
-          const bear_dp tb = dm_row_item(__builtin_fma(m.f, prm.inv_h, prm.eps), cb, s_log);
-          ll += tb.D;
-          q = tb.P;
-          dh = __builtin_fma(q, m.f, dh);
-        }
-        dt = __builtin_fma(q, m.dft, dt);
-        dn = __builtin_fma(q, m.dfn, dn);
-      }
-      acc[0] += ll;
-      acc[1] -= dh * scale;            // d alpha_b / d h_signed = -f_b / h (AR: dh stays zero)
-      acc[2] += dt * scale;
-      acc[3] += dn * scale;
-    }
+    for (uint32_t r = threadIdx.x; r < rows; r += RFW_THREADS)
+      rfw_row<W, AR, false>(s_trn + r * W, s_ref + r * W, nullptr, prm, s_log, acc);
   }
   __syncthreads();
   block_finish<4>(acc, partials, io, apply);
@@ -212,8 +222,7 @@ __global__ __launch_bounds__(RFW_THREADS) void dm_refmix_wide_kernel(const uint3
   __shared__ __attribute__((aligned(16))) uint32_t s_ref[T * W];
   __shared__ __attribute__((aligned(16))) double s_net[T * W];   // g in, d sum LL / d g out
   __shared__ double2 s_log[BEAR_LOGTAB_N];
-  const bear_params prm = rfw_params(h_s, tau_s, nw_s, eps);
-  const double nwV = prm.nw * prm.V;
+  const bear_params prm = bear_params_dev(eps, true, h_s, tau_s, nw_s);
   if (threadIdx.x < BEAR_LOGTAB_N) s_log[threadIdx.x] = logtab_g[threadIdx.x];
   const uint64_t n_tiles = (n_rows + T - 1) / T;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -226,77 +235,10 @@ __global__ __launch_bounds__(RFW_THREADS) void dm_refmix_wide_kernel(const uint3
     stage_dwords<RFW_THREADS>(reinterpret_cast<uint32_t *>(s_net), reinterpret_cast<const uint32_t *>(net_rows + row0 * W), rows * W * 2);
     __syncthreads();
 #pragma unroll 1
-    for (uint32_t r = threadIdx.x; r < rows; r += RFW_THREADS) {
-      const uint32_t *c = s_cnt + r * W;
-      const uint32_t *rf = s_ref + r * W;
-      double *g = s_net + r * W;
-      uint32_t nz = wide_nz_mask<W>(c);
-      if (!nz) {                       // no training counts: a row of exact zeros, nothing else
-#pragma unroll
-        for (int b = 0; b < W; ++b) g[b] = 0.0;
-        continue;
-      }
-      const double R = rfw_ref_total<W>(rf, prm.eps), invR = 1.0 / R;
-      double ll = 0.0, dh = 0.0, dt = 0.0, dn = 0.0, scale = 1.0, g0 = 0.0;
-      bear_dp tn = {0.0, 0.0};
-      if (!AR) {
-        double n = 0.0, sg = 0.0;
-#pragma unroll
-        for (int b = 0; b < W; ++b) {
-          n += (double)c[b];
-          sg += g[b];
-        }
-        const double sdev = rfw_dev_total<W>(rf, prm.eps, R, invR);
-        const double sf = __builtin_fma(prm.nw, sg, __builtin_fma(prm.E, sdev, 1.0)) * prm.V;
-        tn = dm_row_item(__builtin_fma(sf, prm.inv_h, (double)W * prm.eps), n, s_log);
-        ll = -tn.D;
-        dh = -tn.P * sf;
-        dt = tn.P * (prm.tauE * prm.V * sdev);
-        dn = -tn.P * (nwV * (sg - sf));
-        scale = prm.inv_h;
-        g0 = -tn.P * prm.inv_h * nwV;
-      }
-#pragma unroll
-      for (int b = 0; b < W; ++b)
-        if (!((nz >> b) & 1u)) g[b] = g0;
-      while (nz) {
-        const int b = __builtin_ctz(nz);
-        nz &= nz - 1u;
-        const double cb = (double)c[b];
-        const rfw_cell m = rfw_mix_cell<W>(rf, b, g[b], R, invR, prm);
-        double q;
-        if (AR) {
-          const double p = m.f + prm.eps;
-          ll = __builtin_fma(cb, rfw_log(p, s_log), ll);
-          q = cb * bear_rcp(p);
-          g[b] = q * nwV;
-        } else {
-          const bear_dp tb = dm_row_item(__builtin_fma(m.f, prm.inv_h, prm.eps), cb, s_log);
-          ll += tb.D;
-          q = tb.P;
-          dh = __builtin_fma(q, m.f, dh);
-          g[b] = (tb.P - tn.P) * prm.inv_h * nwV;
-        }
-        dt = __builtin_fma(q, m.dft, dt);
-        dn = __builtin_fma(q, m.dfn, dn);
-      }
-      acc[0] += ll;
-      acc[1] -= dh * scale;
-      acc[2] += dt * scale;
-      acc[3] += dn * scale;
-    }
+    for (uint32_t r = threadIdx.x; r < rows; r += RFW_THREADS)
+      rfw_row<W, AR, true>(s_cnt + r * W, s_ref + r * W, s_net + r * W, prm, s_log, acc);
     __syncthreads();   // every row of the tile holds its gradient: 16-byte stores of the whole tile
-    {
-      const uint32_t n_dw = rows * W * 2, n_vec = n_dw >> 2;
-      typedef uint32_t rfw_v4u __attribute__((ext_vector_type(4)));
-      const rfw_v4u *s4 = reinterpret_cast<const rfw_v4u *>(s_net);
-      rfw_v4u *d4 = reinterpret_cast<rfw_v4u *>(grad_net_rows + row0 * W);
-      // nontemporal: the rows are not read again by this kernel
-      for (uint32_t i = threadIdx.x; i < n_vec; i += RFW_THREADS) __builtin_nontemporal_store(s4[i], d4 + i);
-      const uint32_t *s1 = reinterpret_cast<const uint32_t *>(s_net);
-      uint32_t *d1 = reinterpret_cast<uint32_t *>(grad_net_rows + row0 * W);
-      for (uint32_t i = (n_vec << 2) + threadIdx.x; i < n_dw; i += RFW_THREADS) d1[i] = s1[i];
-    }
+    wide_store_tile<RFW_THREADS, W>(s_net, grad_net_rows + row0 * W, rows);
   }
   __syncthreads();
   block_finish<4>(acc, partials, io);

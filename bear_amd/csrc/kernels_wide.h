@@ -19,7 +19,7 @@
 #include "bear_common.h"
 #include "kernels_eval.h"
 #include "kernels_rows.h"
-#include "rows_wide_common.h"   // wide_nz_mask, wide_dm_row
+#include "rows_wide_common.h"   // wide_nz_mask, wide_dm_row, wide_store_tile
 
 #define WIDE_THREADS 256
 // W = 21: 128 contexts = 10.5 KiB of counts + 21 KiB of prior rows (+ 2 KiB log table): LDS for four blocks per CU (160 KiB); the
@@ -56,15 +56,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void dm_wide_kernel(const uint32_t *_
     }
     if (GRAD) {
       __syncthreads();   // every row of the tile holds its gradient: 16-byte stores of the whole tile
-      const uint32_t n_dw = rows * W * 2, n_vec = n_dw >> 2;
-      typedef uint32_t wide_v4u __attribute__((ext_vector_type(4)));
-      const wide_v4u *s4 = reinterpret_cast<const wide_v4u *>(s_pri);
-      wide_v4u *d4 = reinterpret_cast<wide_v4u *>(grad_prior + row0 * W);
-      // nontemporal: the rows are not read again by this kernel (as bear_wave_store_rows5)
-      for (uint32_t i = threadIdx.x; i < n_vec; i += WIDE_THREADS) __builtin_nontemporal_store(s4[i], d4 + i);
-      const uint32_t *s1 = reinterpret_cast<const uint32_t *>(s_pri);
-      uint32_t *d1 = reinterpret_cast<uint32_t *>(grad_prior + row0 * W);
-      for (uint32_t i = (n_vec << 2) + threadIdx.x; i < n_dw; i += WIDE_THREADS) d1[i] = s1[i];
+      wide_store_tile<WIDE_THREADS, W>(s_pri, grad_prior + row0 * W, rows);
     }
   }
   __syncthreads();

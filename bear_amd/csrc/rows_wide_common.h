@@ -1,6 +1,9 @@
-// rows_wide_common.h -- device routines the kernels of the protein alphabet's width share (kernels_wide.h, kernels_linrows_wide.h,
-// kernels_cnn_wide.h, kernels_linear_wide.h): the DM step of one staged context (the sparse item walk), a tile of 21-wide rows out of
-// LDS, and the fixed-order sum over rows of block partials.  No kernels here.
+// rows_wide_common.h -- device routines the kernels of the protein alphabet's width share (kernels_wide.h, kernels_refmix_wide.h,
+// kernels_linrows_wide.h, kernels_linear_wide.h, kernels_cnn_wide.h), each step written once: the DM step of one staged context (the
+// sparse item walk, wide_dm_row), a tile of fp64 rows out of LDS (wide_store_tile), a tile's int8 code bytes into LDS
+// (wide_stage_codes), the rows of a partials buffer (WIDE_PARTIAL_ROWS) and the fixed-order sum over them (lnw_sum_partials).  The
+// steps of the linear function, which need its MFMA geometry (lnw_forward_row, lnw_softmax_back_row, lnw_own_rows, lnw_onehot_product,
+// lnw_store_acc), sit at the top of kernels_linrows_wide.h.  No kernels here.
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"   // dm_row_item
@@ -79,10 +82,10 @@ __device__ __forceinline__ void wide_dm_row(const uint32_t *c, const double *f, 
   }
 }
 
-// rows [0, rows) of an LDS tile of 21-wide fp64 rows to dst (16-byte aligned) as 16-byte stores; nontemporal: not read again here
-template <int NT>
-__device__ __forceinline__ void lnw_store_tile(const double *tile, double *__restrict__ dst, uint32_t rows) {
-  const uint32_t n_dw = rows * LNW_W * 2, n_vec = n_dw >> 2;
+// rows [0, rows) of an LDS tile of W-wide fp64 rows to dst (16-byte aligned) as 16-byte stores; nontemporal: not read again here
+template <int NT, int W>
+__device__ __forceinline__ void wide_store_tile(const double *tile, double *__restrict__ dst, uint32_t rows) {
+  const uint32_t n_dw = rows * W * 2, n_vec = n_dw >> 2;
   const lnw_v4u *s4 = reinterpret_cast<const lnw_v4u *>(tile);
   lnw_v4u *d4 = reinterpret_cast<lnw_v4u *>(dst);
   for (uint32_t i = threadIdx.x; i < n_vec; i += NT) __builtin_nontemporal_store(s4[i], d4 + i);
@@ -90,6 +93,20 @@ __device__ __forceinline__ void lnw_store_tile(const double *tile, double *__res
   uint32_t *d1 = reinterpret_cast<uint32_t *>(dst);
   for (uint32_t i = (n_vec << 2) + threadIdx.x; i < n_dw; i += NT) d1[i] = s1[i];
 }
+
+// the code bytes of rows [row0, row0 + rows) of the int8 [n, lag] matrix into s_c (row0 lag a multiple of 16, codes 16-byte aligned):
+// whole dwords as 16-byte loads, the last bytes one by one -- nothing is read beyond the matrix
+template <int NT>
+__device__ __forceinline__ void wide_stage_codes(int8_t *s_c, const int8_t *__restrict__ codes, uint64_t row0, uint32_t rows, int lag) {
+  const uint32_t n_bytes = rows * (uint32_t)lag;
+  const int8_t *src = codes + row0 * (uint64_t)lag;
+  stage_dwords<NT>(reinterpret_cast<uint32_t *>(s_c), reinterpret_cast<const uint32_t *>(src), n_bytes >> 2);
+  for (uint32_t i = (n_bytes & ~3u) + threadIdx.x; i < n_bytes; i += NT) s_c[i] = src[i];
+}
+
+// rows of a partials buffer that lnw_sum_partials sums: one per block of a grid capped at blocks_per_cu per CU, then one per residue
+// class of the block numbers (bear_arrive_last's counters)
+#define WIDE_PARTIAL_ROWS(num_cu, blocks_per_cu) ((size_t)(num_cu) * (blocks_per_cu) + BEAR_ARRIVE_SUBS)
 
 // dst[k] = src[first][k] + src[first + step][k] + ... (cnt rows of n_grad doubles, in that order), k over the block's NT threads
 template <int NT, bool AGENT>

@@ -1,0 +1,137 @@
+"""Developer: the bits of every width-taking entry on seeded inputs, for holding one build of the library against another.
+    BEAR_AMD_LIB=before/libbear_hip.so python scripts/dev/wide_bits.py > before.json
+    BEAR_AMD_LIB=bear_amd/libbear_hip.so python scripts/dev/wide_bits.py > after.json        # then: cmp before.json after.json
+One SHA-256 per output buffer, as one JSON object (case -> digest).  These kernels use no floating-point atomics and the library is
+built without contraction: on one device two builds that compute the same thing give the same file, and any difference is a
+difference in the arithmetic or in its order.  Each build runs in a process of its own (the library is loaded once).
+
+Shapes: the smallest at which the routines the width-21 kernels share can go wrong -- the code bytes of a tile not a whole number
+of dwords, a ragged last tile and a second tile per block, rows of 3 tiles + 77 at either width, and per kernel one table with more
+tiles than its capped grid has blocks (cap * tile + tile + 3 rows)."""
+import hashlib
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from bear_amd import kernels  # noqa: E402
+
+OUT = {}
+POINT = (0.37, -1.2, -0.8)
+# tiles and grid caps (blocks per CU) that bear_amd.kernels does not name: kernels_wide.h (WIDE_TILE, WIDE_BLOCKS_PER_CU; EVW_THREADS
+# and the workspace's eval_blocks), kernels_linrows_wide.h (LNW_FWD_TILE, one block per CU), kernels_cnn_wide.h (CNW_FWD_TILE, at most
+# two blocks per CU; CNW_BWD_TILE, CNW_BWD_BLOCKS_PER_CU)
+PRIOR_TILE, PRIOR_PER_CU = {21: 128, 5: 512}, 4
+EVAL_TILE, EVAL_PER_CU = 128, 8
+LINEAR_FWD_TILE, LINEAR_FWD_PER_CU = 512, 1
+CNN_FWD_TILE, CNN_FWD_PER_CU = 256, 2
+CNN_BWD_TILE, CNN_BWD_PER_CU = 64, 1
+
+
+def beyond(cus, per_cu, tile):
+    """Rows of a table with more tiles than the capped grid has blocks: every block a second tile, one a ragged third."""
+    return cus * per_cu * tile + tile + 3
+
+
+def put(name, *tensors):
+    for i, t in enumerate(tensors):
+        OUT["%s/%d" % (name, i)] = hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def counts(rng, n, width, p=0.13, lam=6.0):
+    c = np.where(rng.random((n, width)) < p, rng.poisson(lam, (n, width)), 0).astype(np.uint32)
+    c[::7] = 0                                           # contexts without counts
+    return torch.from_numpy(c.view(np.int32)).cuda()
+
+
+def rows(rng, n, width):
+    z = rng.normal(size=(n, width)) * 2.0
+    g = np.exp(z - z.max(1, keepdims=True))
+    return torch.from_numpy(np.ascontiguousarray(g / g.sum(1, keepdims=True))).cuda()
+
+
+def codes(rng, n, lag):
+    c = rng.integers(0, 21, (n, lag)).astype(np.int8)
+    c[rng.random((n, lag)) < 0.05] = -1                  # unknown letters
+    return torch.from_numpy(c).cuda()
+
+
+def f64(*v):
+    return torch.tensor(v, dtype=torch.float64, device="cuda")
+
+
+def row_kernels(cus):
+    for width in kernels.WIDE_WIDTHS:
+        sizes = {"prior": [3 * PRIOR_TILE[width] + 77, beyond(cus, PRIOR_PER_CU, PRIOR_TILE[width])],
+                 "eval": [3 * EVAL_TILE + 77, beyond(cus, EVAL_PER_CU, EVAL_TILE)],
+                 "ref": [3 * kernels.REF_WIDE_TILE[width] + 77, beyond(cus, kernels.REF_WIDE_BLOCKS_PER_CU, kernels.REF_WIDE_TILE[width])],
+                 "mix": [3 * kernels.REFMIX_WIDE_TILE[width] + 77,
+                         beyond(cus, kernels.REFMIX_WIDE_BLOCKS_PER_CU, kernels.REFMIX_WIDE_TILE[width])]}
+        for n in sizes["prior"]:
+            rng = np.random.default_rng(n + width)
+            c, f, h = counts(rng, n, width), rows(rng, n, width), f64(-0.3)
+            for ar in (False, True):
+                for grad in (False, True):
+                    out, g = kernels.dm_prior_wide(c, f, h, train_ar=ar, want_grad=grad)
+                    put("dm_prior_wide/w%d/n%d/ar%d/grad%d" % (width, n, ar, grad), out, *([g] if grad else []))
+        for n in sizes["eval"]:
+            rng = np.random.default_rng(n + width + 1)
+            t, tr, f = counts(rng, n, width), counts(rng, n, width, 0.3), rows(rng, n, width)
+            put("eval_wide/w%d/n%d" % (width, n), kernels.evaluate_wide(t, f, [0.5, 2.0, 30.0], [0.1, 1.0], train=tr, noise_seed=3))
+        for n in sizes["ref"]:
+            rng = np.random.default_rng(n + width + 2)
+            c, rf, theta = counts(rng, n, width), counts(rng, n, width, 0.2, 9.0), f64(*POINT)
+            for ar in (False, True):
+                packed = torch.zeros(4, dtype=torch.float64, device="cuda")
+                kernels.ref_train_reduce_wide(c, rf, theta, packed, train_ar=ar)
+                put("dm_ref_wide/w%d/n%d/ar%d" % (width, n, ar), kernels.dm_ref_wide(c, rf, *POINT, train_ar=ar))
+                put("ref_train_reduce_wide/w%d/n%d/ar%d" % (width, n, ar), packed)
+        for n in sizes["mix"]:
+            rng = np.random.default_rng(n + width + 3)
+            c, rf, g = counts(rng, n, width), counts(rng, n, width, 0.2, 9.0), rows(rng, n, width)
+            for ar in (False, True):
+                put("dm_refmix_wide_grad/w%d/n%d/ar%d" % (width, n, ar),
+                    *kernels.dm_refmix_wide_dev(c, g, rf, f64(POINT[0]), f64(POINT[1]), f64(POINT[2]), train_ar=ar))
+
+
+def linear_kernels(cus):
+    # the last size is beyond the grid of the forward kernel (and so of the backward kernel and the fused step, whose tiles are smaller)
+    assert LINEAR_FWD_PER_CU * LINEAR_FWD_TILE >= kernels.LINEAR_STEP_WIDE_BLOCKS_PER_CU * kernels.LINEAR_STEP_WIDE_TILE
+    for lag, n in ((1, 1), (3, 129), (5, 70), (16, 257),
+                   (5, beyond(cus, kernels.LINEAR_STEP_WIDE_BLOCKS_PER_CU, kernels.LINEAR_STEP_WIDE_TILE)),
+                   (5, beyond(cus, LINEAR_FWD_PER_CU, LINEAR_FWD_TILE))):
+        rng = np.random.default_rng(1000 * lag + n)
+        cd, c, q = codes(rng, n, lag), counts(rng, n, 21), rows(rng, n, 21)
+        mat = torch.from_numpy(rng.normal(size=(lag, 21, 21))).cuda()
+        f = kernels.linear_forward_wide(cd, mat, lag)
+        put("linear_forward_wide/lag%d/n%d" % (lag, n), f)
+        put("linear_backward_wide/lag%d/n%d" % (lag, n), kernels.linear_backward_wide(cd, lag, f, q - 0.3))
+        theta = torch.cat([f64(-0.3), mat.reshape(-1)])
+        for ar in (False, True):
+            put("dm_linear_wide/lag%d/n%d/ar%d" % (lag, n, ar), *kernels.dm_linear_wide(c, cd, mat, -0.3, train_ar=ar))
+            packed = torch.zeros(theta.numel() + 1, dtype=torch.float64, device="cuda")
+            kernels.net_linear_train_reduce_wide(c, cd, lag, theta, packed, train_ar=ar)
+            put("net_linear_train_reduce_wide/lag%d/n%d/ar%d" % (lag, n, ar), packed)
+
+
+def cnn_kernels(cus):
+    for lag, fw, n in ((5, 3, 65), (16, 16, 257), (16, 1, 130), (5, 3, beyond(cus, CNN_BWD_PER_CU, CNN_BWD_TILE)),
+                       (5, 3, beyond(cus, CNN_FWD_PER_CU, CNN_FWD_TILE))):          # beyond the grid of either kernel
+        rng = np.random.default_rng(100 * lag + fw + n)
+        cd, q = codes(rng, n, lag), rows(rng, n, 21)
+        params = torch.from_numpy(rng.normal(size=kernels.cnn_param_count_wide(lag, fw)) * 0.3).cuda()
+        f, t1 = kernels.cnn_forward_wide(cd, params, lag, fw)
+        put("cnn_forward_wide/lag%d/fw%d/n%d" % (lag, fw, n), f, t1)
+        put("cnn_backward_wide/lag%d/fw%d/n%d" % (lag, fw, n), kernels.cnn_backward_wide(cd, params, lag, fw, t1, f, q - 0.3))
+
+
+if __name__ == "__main__":
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    row_kernels(cus)
+    linear_kernels(cus)
+    cnn_kernels(cus)
+    torch.cuda.synchronize()
+    print(json.dumps(OUT, indent=0, sort_keys=True))

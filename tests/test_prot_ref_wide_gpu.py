@@ -206,6 +206,34 @@ def test_more_tiles_than_blocks(kernel):
         _check_sums(got, want, mass, train_ar, (kernel, n, train_ar))
 
 
+# ------------------------------------------------------------------ 4b. the two kernels are one row body
+@pytest.mark.parametrize("train_ar", [False, True])
+@pytest.mark.parametrize("tiles", ["two_and_77", "more_than_blocks"])
+def test_refmix_of_stop_rows_is_the_stop_kernel_byte_for_byte(train_ar, tiles):
+    """rfw_row<W, AR, MIX> is the body of both kernels.  At width 5 both use tiles of 512 and three blocks per CU, so a context lands
+    on the same thread of the same block in both; with net rows equal to the stop row (1.0 in the last column) the ref-mix kernel
+    must leave the four sums of the stop kernel bit for bit.  Both read their parameters from device memory."""
+    assert kernels.REF_WIDE_TILE[5] == kernels.REFMIX_WIDE_TILE[5] == 512
+    assert kernels.REF_WIDE_BLOCKS_PER_CU == kernels.REFMIX_WIDE_BLOCKS_PER_CU
+    cap = torch.cuda.get_device_properties(0).multi_processor_count * kernels.REF_WIDE_BLOCKS_PER_CU
+    n = 2 * 512 + 77 if tiles == "two_and_77" else cap * 512 + 512 + 3
+    rng = np.random.default_rng(23)
+    c = np.where(rng.random((n, 5)) < 0.4, rng.poisson(6.0, (n, 5)), 0).astype(np.uint32)
+    rf = np.where(rng.random((n, 5)) < 0.5, rng.poisson(9.0, (n, 5)), 0).astype(np.uint32)
+    cd, rd = _dev_counts(c), _dev_counts(rf)
+    g = torch.zeros((n, 5), dtype=torch.float64, device="cuda")
+    g[:, 4] = 1.0
+    for point in POINTS:
+        theta = torch.tensor(point, dtype=torch.float64, device="cuda")
+        stop = torch.full((4,), np.nan, dtype=torch.float64, device="cuda")
+        kernels.ref_train_reduce_wide(cd, rd, theta, stop, train_ar=train_ar)
+        mix, _ = kernels.dm_refmix_wide_dev(cd, g, rd, theta[0:1], theta[1:2], theta[2:3], train_ar=train_ar)
+        stop, mix = stop.cpu().numpy(), mix.cpu().numpy()
+        print(tiles, train_ar, point, "stop", stop.tolist(), "mix", mix.tolist())
+        assert np.isfinite(stop).all() and stop[0] != 0.0
+        assert stop.tobytes() == mix.tobytes()
+
+
 # ------------------------------------------------------------------ 5. repeatability
 _REPEAT = (
     "import numpy as np, torch\nfrom bear_amd import kernels\nfrom test_prot_cpu import make_prot_table\n"
