@@ -5,17 +5,17 @@
 #include "kernels_cnn.h"
 #include "kernels_cnn_wide.h"
 
+static const size_t CU_LDS_BYTES = 160u * 1024u;      // the LDS of a CU: what one block may take
+
 int cnn_ws_setup(bear_ws *ws) {
   int st = allow_dynamic_lds({BEAR_KFN(cnn_backward_head_kernel)}, cnh_lds_bytes());
   if (st != BEAR_OK) return st;
   // (linear in the filter width at a given lag: the ends are the extremes)
-  const size_t fwd_lds = cnw_fwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG) > cnw_fwd_lds(CNN_WIDE_MAX_LAG, 1) ? cnw_fwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG)
-                                                                                                             : cnw_fwd_lds(CNN_WIDE_MAX_LAG, 1);
-  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_forward_kernel)}, fwd_lds);
+  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_forward_kernel)},
+                         std::max(cnw_fwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG), cnw_fwd_lds(CNN_WIDE_MAX_LAG, 1)));
   if (st != BEAR_OK) return st;
-  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_backward_kernel)}, cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG) > cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1)
-                                                                    ? cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG)
-                                                                    : cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1));
+  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_backward_kernel)},
+                         std::max(cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG), cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1)));
   if (st != BEAR_OK) return st;
   HIP_TRY(hipMalloc(&ws->cnnw_partials, sizeof(double) * CNW_MAX_TOTAL * WIDE_PARTIAL_ROWS(ws->num_cu, CNW_BWD_BLOCKS_PER_CU)));
   return BEAR_OK;
@@ -32,21 +32,32 @@ extern "C" int bear_dbg_cnn_stamps(unsigned long long *host_out, int reset) {   
 }
 #endif
 
-// the forward kernel over `groups` groups of 64 rows (or tiles of a plan): a wave per group
-static int cnn_forward_grid(const bear_ws *ws, uint64_t groups) {
-  return grid_capped((groups + CNN_THREADS / 64 - 1) / (CNN_THREADS / 64), (uint64_t)ws->num_cu * 16);
+// the forward kernel over `groups` groups of 64 rows (or tiles of a plan, with their lists): a wave per group
+static void launch_cnn_forward(const bear_ws *ws, const cnn_dims &D, const unsigned long long *codes, uint64_t n_rows, const double *params,
+                               double *prior, double *t1_save, const pln_tile *tiles, const uint16_t *live_lists, uint64_t groups,
+                               const cnn_level_io &io, hipStream_t s) {
+  const int blocks = grid_capped((groups + CNN_THREADS / 64 - 1) / (CNN_THREADS / 64), (uint64_t)ws->num_cu * 16);
+  hipLaunchKernelGGL(cnn_forward_kernel, dim3((unsigned)blocks), dim3(CNN_THREADS), cnn_fwd_lds_bytes(D.fw), s, codes, n_rows, D, params, prior,
+                     t1_save, tiles, live_lists, groups, io);
+}
+// ... over all rows in groups of 64, no plan
+static void launch_cnn_forward_rows(const bear_ws *ws, const cnn_dims &D, const unsigned long long *codes, uint64_t n_rows, const double *params,
+                                    double *prior, double *t1_save, const cnn_level_io &io, hipStream_t s) {
+  launch_cnn_forward(ws, D, codes, n_rows, params, prior, t1_save, nullptr, nullptr, (n_rows + 63) / 64, io, s);
+}
+
+static bool cnn_shape_ok(int lag, int fw, int nf, int l1) {
+  return lag >= 1 && lag <= CNN_MAX_LAG && fw >= 1 && fw <= lag && nf == CNN_NF && l1 == CNN_L1;
 }
 
 static int cnn_check(const bear_ws *ws, int lag, int fw, int nf, int l1) {
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
-  if (lag < 1 || lag > CNN_MAX_LAG || fw < 1 || fw > lag || nf != CNN_NF || l1 != CNN_L1) return BEAR_ERR_INVALID_ARG;
-  return BEAR_OK;
+  return cnn_shape_ok(lag, fw, nf, l1) ? BEAR_OK : BEAR_ERR_INVALID_ARG;
 }
 
 int bear_cnn_param_count(int lag, int filter_width, int num_filters, int layer1_width) {
-  if (lag < 1 || lag > CNN_MAX_LAG || filter_width < 1 || filter_width > lag || num_filters != CNN_NF || layer1_width != CNN_L1)
-    return BEAR_ERR_INVALID_ARG;
+  if (!cnn_shape_ok(lag, filter_width, num_filters, layer1_width)) return BEAR_ERR_INVALID_ARG;
   return cnn_make_dims(lag, filter_width).total;
 }
 
@@ -57,42 +68,49 @@ int bear_cnn_forward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_rows
   if (n_rows == 0) return BEAR_OK;
   if (!kmer_code || !params || !prior || misaligned(t1_save) || misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
   const cnn_dims D = cnn_make_dims(lag, filter_width);
-  const size_t lds = sizeof(double) * (BEAR_EXPTAB_N + (size_t)filter_width * 6 * CNN_NF + (CNN_THREADS / 64) * CNN_FWD_SCRATCH);
-  const int blocks = grid_capped((n_rows + CNN_THREADS - 1) / CNN_THREADS, (uint64_t)ws->num_cu * 16);
-  hipLaunchKernelGGL(cnn_forward_kernel, dim3((unsigned)blocks), dim3(CNN_THREADS), lds, static_cast<hipStream_t>(stream),
-                     reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, D, params, prior, t1_save,
-                     static_cast<const pln_tile *>(nullptr), static_cast<const uint16_t *>(nullptr), (n_rows + 63) / 64, cnn_all_positions(D));
+  launch_cnn_forward_rows(ws, D, reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, params, prior, t1_save, cnn_all_positions(D),
+                          static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
 
-// sizes the block-partial buffer of the CNN backward pass; returns the grid.  With may_alloc == 0 (inside a stream capture) a
-// buffer that is too small is an error: call bear_cnn_reserve first.
-static int cnn_backward_grid(bear_ws *ws, const cnn_dims &D, uint64_t n_rows, int filter_width, int *waves_out, int *parts_out,
-                             size_t *lds_out, uint64_t *blocks_out, hipStream_t s, int may_alloc) {
-  const size_t fixed = sizeof(double) * (BEAR_EXPTAB_N + (size_t)filter_width * 6 * CNN_NF + (size_t)((D.total + 1) & ~1));
-  // cnn_backward_parts_kernel<2>: two lanes per context, eight waves of 32-context tiles (two per SIMD), when the staging fits
-  // next to the filter, parameter and gradient images (every reference config); otherwise 64-context tiles, one wave per SIMD.
-  // `waves` names the form (8 / <= 4).  BEAR_CNN_BACKWARD=1 forces the second form (developer A/B runs, tests).
-  const size_t lds2 = sizeof(double) * (cnnq_fixed_doubles(D) + (size_t)cnnq<2>::WAVES * cnnq<2>::WAVE_DOUBLES);
+static bool cnn_parts_form_forced_off() {      // BEAR_CNN_BACKWARD=1: the 64-context form of the backward kernel (developer A/B runs, tests)
   const char *force = getenv("BEAR_CNN_BACKWARD");
+  return force && force[0] == '1';
+}
+
+// The backward pass's launch geometry.  cnn_backward_parts_kernel<2>: two lanes per context, eight waves of 32-context tiles (two
+// per SIMD), when the staging fits next to the filter, parameter and gradient images (every reference config); otherwise
+// cnn_backward_kernel: 64-context tiles, one wave per SIMD (as many of four as fit), and no position range.
+struct cnn_backward_geom {
+  bool parts;         // the form
+  int waves;          // per block
+  size_t lds;
+  uint64_t blocks;    // rows of the partial buffer the finalize reads
+  uint64_t rows_per_block() const { return (uint64_t)(parts ? cnnq<2>::TILE : 64) * (uint64_t)waves; }
+  int allow_lds() const {      // (not inside a stream capture)
+    return allow_dynamic_lds({parts ? BEAR_KFN(cnn_backward_parts_kernel<2>) : BEAR_KFN(cnn_backward_kernel)}, lds);
+  }
+};
+// sizes the block-partial buffer of the CNN backward pass; *g is the geometry.  With may_alloc == 0 (inside a stream capture) a
+// buffer that is too small is an error: call bear_cnn_reserve first.
+static int cnn_backward_grid(bear_ws *ws, const cnn_dims &D, uint64_t n_rows, cnn_backward_geom *g, hipStream_t s, int may_alloc) {
   // BEAR_AMD_DETERMINISTIC: ONE wave per block.  The block's gradient image takes LDS floating-point atomics from all its waves,
   // in whatever order they get there; with one wave the adds happen in program order, the blocks' images are summed in a fixed
   // order anyway (cnn_finalize_kernel) -- two runs of a step are bit-identical, at an eighth of the waves per CU.
   const bool det = bear_deterministic();
-  int waves = det ? 1 : 4, parts = 0;
-  while (waves > 1 && fixed + (size_t)waves * CNN_WAVE_DOUBLES * sizeof(double) > 160u * 1024u) waves >>= 1;
-  size_t lds = fixed + (size_t)waves * CNN_WAVE_DOUBLES * sizeof(double);
-  uint64_t per_block = (uint64_t)64 * waves;
-  if (lds2 <= 160u * 1024u && !(force && force[0] == '1')) {
-    parts = 1;
-    waves = det ? 1 : cnnq<2>::WAVES;
-    lds = sizeof(double) * (cnnq_fixed_doubles(D) + (size_t)waves * cnnq<2>::WAVE_DOUBLES);
-    per_block = (uint64_t)cnnq<2>::TILE * waves;
+  g->parts = cnnq_lds_bytes(D, cnnq<2>::WAVES) <= CU_LDS_BYTES && !cnn_parts_form_forced_off();
+  if (g->parts) {
+    g->waves = det ? 1 : cnnq<2>::WAVES;
+    g->lds = cnnq_lds_bytes(D, g->waves);
+  } else {
+    g->waves = det ? 1 : 4;
+    while (g->waves > 1 && cnn_bwd_lds_bytes(D, g->waves) > CU_LDS_BYTES) g->waves >>= 1;
+    g->lds = cnn_bwd_lds_bytes(D, g->waves);
   }
-  if (lds > 160u * 1024u) return BEAR_ERR_INVALID_ARG;
-  const uint64_t blocks = (uint64_t)grid_capped((n_rows + per_block - 1) / per_block, (uint64_t)ws->num_cu);
-  const size_t need = (size_t)blocks * D.total;
+  if (g->lds > CU_LDS_BYTES) return BEAR_ERR_INVALID_ARG;
+  g->blocks = (uint64_t)grid_capped((n_rows + g->rows_per_block() - 1) / g->rows_per_block(), (uint64_t)ws->num_cu);
+  const size_t need = (size_t)g->blocks * D.total;
   if (ws->cnn_partials_cap < need) {
     if (!may_alloc) return BEAR_ERR_INVALID_ARG;
     HIP_TRY(hipStreamSynchronize(s));
@@ -102,37 +120,29 @@ static int cnn_backward_grid(bear_ws *ws, const cnn_dims &D, uint64_t n_rows, in
     HIP_TRY(hipMalloc(&ws->cnn_partials, sizeof(double) * need));
     ws->cnn_partials_cap = need;
   }
-  *waves_out = waves;
-  *parts_out = parts;
-  *lds_out = lds;
-  *blocks_out = blocks;
   return BEAR_OK;
 }
 
 // live_plan [nullable]: a five-column plan of the table -- the part kernel then walks its lists of contexts that hold counts
-static int launch_cnn_backward(bear_ws *ws, const cnn_dims &D, const uint64_t *kmer_code, uint64_t n_rows, int filter_width,
-                               const double *params, const double *t1_save, const double *prior, const double *grad_prior,
-                               double *grad_params, hipStream_t s, int may_alloc, const bear_plan *live_plan = nullptr) {
-  int waves = 0, parts = 0;
-  size_t lds = 0;
-  uint64_t blocks = 0;
-  int st = cnn_backward_grid(ws, D, n_rows, filter_width, &waves, &parts, &lds, &blocks, s, may_alloc);
+static int launch_cnn_backward(bear_ws *ws, const cnn_dims &D, const uint64_t *kmer_code, uint64_t n_rows, const double *params,
+                               const double *t1_save, const double *prior, const double *grad_prior, double *grad_params, hipStream_t s,
+                               int may_alloc, const bear_plan *live_plan = nullptr) {
+  cnn_backward_geom g;
+  int st = cnn_backward_grid(ws, D, n_rows, &g, s, may_alloc);
   if (st != BEAR_OK) return st;
-  const bool parts2 = parts != 0;
-  const void *fn = parts2 ? reinterpret_cast<const void *>(cnn_backward_parts_kernel<2>) : reinterpret_cast<const void *>(cnn_backward_kernel);
-  if (may_alloc) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (may_alloc && (st = g.allow_lds()) != BEAR_OK) return st;
   const unsigned long long *kc = reinterpret_cast<const unsigned long long *>(kmer_code);
-  if (parts2) {
+  if (g.parts) {
     const bool lists = live_plan && live_plan->live && live_plan->n_live_rows < n_rows;   // all rows live: plain groups of rows
     const uint64_t groups = lists ? live_plan->n_tiles : (n_rows + cnnq<2>::TILE - 1) / cnnq<2>::TILE;
-    hipLaunchKernelGGL(cnn_backward_parts_kernel<2>, dim3((unsigned)blocks), dim3(64 * waves), lds, s, kc, n_rows, D, params, t1_save, prior,
+    hipLaunchKernelGGL(cnn_backward_parts_kernel<2>, dim3((unsigned)g.blocks), dim3(64 * g.waves), g.lds, s, kc, n_rows, D, params, t1_save, prior,
                        grad_prior, ws->cnn_partials, lists ? live_plan->tiles : nullptr, lists ? live_plan->live : nullptr, groups,
                        cnn_all_positions(D));
   }
   else
-    hipLaunchKernelGGL(cnn_backward_kernel, dim3((unsigned)blocks), dim3(64 * waves), lds, s, kc, n_rows, D, params, t1_save, prior,
+    hipLaunchKernelGGL(cnn_backward_kernel, dim3((unsigned)g.blocks), dim3(64 * g.waves), g.lds, s, kc, n_rows, D, params, t1_save, prior,
                        grad_prior, ws->cnn_partials);
-  hipLaunchKernelGGL(cnn_finalize_kernel, dim3((D.total + 3) / 4), dim3(256), 0, s, ws->cnn_partials, (int)blocks, D.total, grad_params);
+  hipLaunchKernelGGL(cnn_finalize_kernel, dim3((D.total + 3) / 4), dim3(256), 0, s, ws->cnn_partials, (int)g.blocks, D.total, grad_params);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
@@ -145,35 +155,45 @@ int bear_cnn_backward_f64(bear_ws *ws, const uint64_t *kmer_code, uint64_t n_row
   if (!params || !grad_params) return BEAR_ERR_INVALID_ARG;
   if (n_rows && (!kmer_code || !t1_save || !prior || !grad_prior || misaligned(t1_save))) return BEAR_ERR_INVALID_ARG;
   const cnn_dims D = cnn_make_dims(lag, filter_width);
-  return launch_cnn_backward(ws, D, kmer_code, n_rows, filter_width, params, t1_save, prior, grad_prior, grad_params,
-                             static_cast<hipStream_t>(stream), 1);
+  return launch_cnn_backward(ws, D, kmer_code, n_rows, params, t1_save, prior, grad_prior, grad_params, static_cast<hipStream_t>(stream), 1);
 }
 
 int bear_cnn_reserve(bear_ws *ws, uint64_t n_rows, int lag, int filter_width, int num_filters, int layer1_width) {
   int st = cnn_check(ws, lag, filter_width, num_filters, layer1_width);
   if (st != BEAR_OK) return st;
-  const cnn_dims D = cnn_make_dims(lag, filter_width);
-  int waves = 0, parts = 0;
-  size_t lds = 0;
-  uint64_t blocks = 0;
-  st = cnn_backward_grid(ws, D, n_rows, filter_width, &waves, &parts, &lds, &blocks, nullptr, 1);
+  cnn_backward_geom g;
+  st = cnn_backward_grid(ws, cnn_make_dims(lag, filter_width), n_rows, &g, nullptr, 1);
   if (st != BEAR_OK) return st;
-  HIP_TRY(hipFuncSetAttribute(parts ? reinterpret_cast<const void *>(cnn_backward_parts_kernel<2>)
-                                                      : reinterpret_cast<const void *>(cnn_backward_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return BEAR_OK;
+  return g.allow_lds();
 }
 
-static int cnn_forward_levels(bear_ws *ws, const bear_plan *plan, const cnn_dims &D, const uint64_t *kmer_code, uint64_t n_rows,
-                              const double *params, double *prior, double *t1_buf, hipStream_t s);
+// ---- prefix levels and window tables of a plan (kernels_cnn.h, cnn_level_io; bear_plan_attach_cnn_levels)
+// "the plan's levels and tables were built from these codes at this lag and filter width"
+static bool cnn_plan_has_levels_for(const bear_plan *plan, const uint64_t *kmer_code, int lag, int fw) {
+  return (plan->n_cnn_levels > 0 || plan->n_cnn_windows > 0) && plan->cnn_codes == kmer_code && plan->cnn_lag == lag && plan->cnn_fw == fw;
+}
+// level k as the walks see it; k = 0: the contexts, whose codes and rows buffer come from the caller
+struct cnn_level_view {
+  const unsigned long long *codes;
+  uint64_t n;
+  double *rows;         // [n][16] layer-1 sums (forward) / dT1 rows (backward)
+  int letters;          // prefix length
+};
+static cnn_level_view cnn_contexts(const uint64_t *kmer_code, uint64_t n_rows, double *t1_buf, int lag) {
+  return {reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, t1_buf, lag};
+}
+static cnn_level_view cnn_level(const bear_plan *plan, int k, const cnn_level_view &contexts) {
+  if (k == 0) return contexts;
+  const bear_level_dev &lv = plan->cnn_levels[k - 1];
+  return {lv.codes, lv.n, lv.rows, lv.letters};
+}
 // Level k's rows are prefixes of L_k letters (L_0 = lag: the contexts): it evaluates the positions whose window [p, p + fw) lies
 // inside its prefix but not inside the next level's shorter one -- p + fw in (L_{k+1}, L_k]; the last level takes what is left.
 static cnn_level_io cnn_level_positions(const bear_plan *plan, const cnn_dims &D, int k) {
-  const int K = plan->n_cnn_levels;
-  const int L = k == 0 ? D.lag : plan->cnn_levels[k - 1].letters;
+  const cnn_level_view ctx = cnn_contexts(nullptr, 0, nullptr, D.lag);
   cnn_level_io io = cnn_all_positions(D);
-  io.p_hi = L - D.fw + 1;
-  io.p_lo = k == K ? 0 : plan->cnn_levels[k].letters - D.fw + 1;
+  io.p_hi = cnn_level(plan, k, ctx).letters - D.fw + 1;
+  io.p_lo = k == plan->n_cnn_levels ? 0 : cnn_level(plan, k + 1, ctx).letters - D.fw + 1;
   io.head = k == 0;
   io.p_hi -= plan->n_cnn_win[k];          // the level's last positions come from its window tables
   return io;
@@ -198,11 +218,14 @@ static void cnn_level_sources(const bear_plan *plan, int k, cnn_level_io &io) {
     io.win_row_of[q] = plan->cnn_win[k][q].row_of_context;
   }
 }
-static bool cnn_parts_form_forced_off() {      // BEAR_CNN_BACKWARD=1 (cnn_backward_grid): the 64-context form of the backward kernel, which has no position range
-  const char *force = getenv("BEAR_CNN_BACKWARD");
-  return force && force[0] == '1';
-}
-// ---- the convolutional step over prefix levels (kernels_cnn.h, cnn_level_io): the forward kernel once per level from the shortest
+// a launch with no position of its own (all of them come from the parent level and the window tables)
+static bool cnn_no_own_positions(const cnn_level_io &io) { return io.p_lo >= io.p_hi; }
+// the contexts evaluate no position themselves: the head-only kernels (kernels_cnn.h) take level 0, forward and backward
+static bool cnn_level0_head_only(const cnn_level_io &io0) { return cnn_no_own_positions(io0) && !getenv("BEAR_AMD_CNN_NO_HEAD_KERNEL"); }
+
+static int cnn_forward_levels(bear_ws *ws, const bear_plan *plan, const cnn_dims &D, const uint64_t *kmer_code, uint64_t n_rows,
+                              const double *params, double *prior, double *t1_buf, hipStream_t s);
+// ---- the convolutional step over prefix levels: the forward kernel once per level from the shortest
 // prefixes down to the contexts, the planned DM kernel with gradient rows, the backward kernel once per level the other way with a
 // row-sum launch in between; block partials accumulate in the workspace's buffer (stream order), one finalize at the end.
 // Level k < K evaluates position P - 1 - k, the last level K the positions [0, P - K).
@@ -211,65 +234,61 @@ static int cnn_train_reduce_levels(bear_ws *ws, const bear_plan *plan, const cnn
                                    double *packed, hipStream_t s) {
   const int K = plan->n_cnn_levels;
   const double *params = theta + 1;
-  int bw_waves = 0, bw_parts = 0;
-  size_t bw_lds = 0;
-  uint64_t bw_blocks = 0;
-  int st = cnn_backward_grid(ws, D, n_rows, D.fw, &bw_waves, &bw_parts, &bw_lds, &bw_blocks, s, 0);
+  cnn_backward_geom bw;
+  int st = cnn_backward_grid(ws, D, n_rows, &bw, s, 0);
   if (st != BEAR_OK) return st;
-  if (!bw_parts) return BEAR_ERR_INVALID_ARG;      // (attach refuses shapes whose staging does not fit: not reached)
-  auto level_codes = [&](int k) { return k == 0 ? reinterpret_cast<const unsigned long long *>(kmer_code) : plan->cnn_levels[k - 1].codes; };
-  auto level_rows = [&](int k) { return k == 0 ? n_rows : plan->cnn_levels[k - 1].n; };
-  auto level_table = [&](int k) { return k == 0 ? t1_buf : plan->cnn_levels[k - 1].rows; };
-  auto level_io = [&](int k) { return cnn_level_positions(plan, D, k); };
-  // Level 0 evaluates no position itself (all of them come from its parent level and the window tables): the forward pass then keeps
-  // no layer-1 sums of the contexts -- the backward pass puts them together again from the same rows (cnn_backward_parts_kernel)
-  const cnn_level_io io0 = level_io(0);
-  const bool recompute_t1 = io0.p_lo >= io0.p_hi && !getenv("BEAR_AMD_CNN_KEEP_T1");
+  if (!bw.parts) return BEAR_ERR_INVALID_ARG;      // (attach refuses shapes whose staging does not fit: not reached)
+  const cnn_level_view ctx = cnn_contexts(kmer_code, n_rows, t1_buf, D.lag);
+  // Level 0 evaluates no position itself: the forward pass then keeps no layer-1 sums of the contexts -- the backward pass puts
+  // them together again from the same rows (cnn_gather_t1)
+  const cnn_level_io io0 = cnn_level_positions(plan, D, 0);
+  const bool recompute_t1 = cnn_no_own_positions(io0) && !getenv("BEAR_AMD_CNN_KEEP_T1");
+  const double *t1_of_contexts = recompute_t1 ? nullptr : t1_buf;
   st = cnn_forward_levels(ws, plan, D, kmer_code, n_rows, params, prior_buf, recompute_t1 ? nullptr : t1_buf, s);
   if (st != BEAR_OK) return st;
   st = launch_prior_plan_grad(ws, plan, prior_buf, params_eps(eps), theta, train_ar, 1, packed, grad_rows_buf, s);   // softmax rows: normalised
   if (st != BEAR_OK) return st;
-  const uint64_t per_block = (uint64_t)cnnq<2>::TILE * (uint64_t)bw_waves;
   bool first_launch = true;      // the first backward launch writes every row of the partial buffer the finalize reads, the others add
-  auto backward = [&](const unsigned long long *codes, uint64_t n, const double *t1_in, cnn_level_io io) {
-    const uint64_t blocks = first_launch ? bw_blocks : (uint64_t)grid_capped((n + per_block - 1) / per_block, bw_blocks);
+  auto next_launch = [&](cnn_level_io &io) {
     io.accumulate = first_launch ? 0 : 1;
     first_launch = false;
-    hipLaunchKernelGGL(cnn_backward_parts_kernel<2>, dim3((unsigned)blocks), dim3(64 * bw_waves), bw_lds, s, codes, n, D, params, t1_in, prior_buf,
+  };
+  auto backward = [&](const unsigned long long *codes, uint64_t n, const double *t1_in, cnn_level_io io) {
+    const uint64_t blocks = first_launch ? bw.blocks : (uint64_t)grid_capped((n + bw.rows_per_block() - 1) / bw.rows_per_block(), bw.blocks);
+    next_launch(io);
+    hipLaunchKernelGGL(cnn_backward_parts_kernel<2>, dim3((unsigned)blocks), dim3(64 * bw.waves), bw.lds, s, codes, n, D, params, t1_in, prior_buf,
                        grad_rows_buf, ws->cnn_partials, static_cast<const pln_tile *>(nullptr), static_cast<const uint16_t *>(nullptr),
                        (n + cnnq<2>::TILE - 1) / cnnq<2>::TILE, io);
   };
   for (int k = 0; k <= K; ++k) {
-    cnn_level_io io = level_io(k);
-    const uint64_t n = level_rows(k);
+    cnn_level_io io = cnn_level_positions(plan, D, k);
+    const cnn_level_view lv = cnn_level(plan, k, ctx);
     const int W = plan->n_cnn_win[k];
     if (k > 0) {        // this level's dT1 rows = the sums of its children's
-      const int sb = grid_capped((n * (CNN_L1 / 2) + 255) / 256, (uint64_t)ws->num_cu * 32);
-      hipLaunchKernelGGL(cnn_level_sum_kernel, dim3((unsigned)sb), dim3(256), 0, s, level_table(k - 1), plan->cnn_levels[k - 1].child_start,
-                         n, level_table(k));
+      const int sb = grid_capped((lv.n * (CNN_L1 / 2) + 255) / 256, (uint64_t)ws->num_cu * 32);
+      hipLaunchKernelGGL(cnn_level_sum_kernel, dim3((unsigned)sb), dim3(256), 0, s, cnn_level(plan, k - 1, ctx).rows,
+                         plan->cnn_levels[k - 1].child_start, lv.n, lv.rows);
     }
-    io.dT1 = (k == 0 && (K > 0 || W > 0)) ? t1_buf : (k > 0 ? level_table(k) : nullptr);   // level 0 leaves its dT1 rows where its t1 rows were
+    io.dT1 = (k == 0 && (K > 0 || W > 0)) ? t1_buf : (k > 0 ? lv.rows : nullptr);   // level 0 leaves its dT1 rows where its t1 rows were
     if (k == 0 && recompute_t1) cnn_level_sources(plan, 0, io);
     // (a level of prefixes whose positions all come from window tables has nothing to do itself: its dT1 rows feed the tables below)
-    if (k == 0 && io.p_lo >= io.p_hi && !getenv("BEAR_AMD_CNN_NO_HEAD_KERNEL")) {
-      // the contexts evaluate no position themselves: the head-only kernel (kernels_cnn.h); always the step's first backward launch
-      io.accumulate = first_launch ? 0 : 1;
-      first_launch = false;
-      hipLaunchKernelGGL(cnn_backward_head_kernel, dim3((unsigned)bw_blocks), dim3(CNH_WAVES * 64), cnh_lds_bytes(), s, n, D, params,
-                         recompute_t1 ? static_cast<const double *>(nullptr) : t1_buf, prior_buf, grad_rows_buf, ws->cnn_partials, io);
-    } else if (k == 0 || io.p_lo < io.p_hi) {
-      backward(level_codes(k), n, (k == 0 && recompute_t1) ? static_cast<const double *>(nullptr) : t1_buf, io);
+    if (k == 0 && cnn_level0_head_only(io)) {      // always the step's first backward launch
+      next_launch(io);
+      hipLaunchKernelGGL(cnn_backward_head_kernel, dim3((unsigned)bw.blocks), dim3(CNH_WAVES * 64), cnh_lds_bytes(), s, lv.n, D, params,
+                         t1_of_contexts, prior_buf, grad_rows_buf, ws->cnn_partials, io);
+    } else if (k == 0 || !cnn_no_own_positions(io)) {
+      backward(lv.codes, lv.n, k == 0 ? t1_of_contexts : t1_buf, io);
     }
     for (int q = 0; q < W; ++q) {      // the level's window tables: a window's dT1 row = the sum of its rows' (anywhere in the level)
       const bear_window_dev &wt = plan->cnn_win[k][q];
       const int sb = grid_capped((wt.n + 3) / 4, (uint64_t)ws->num_cu * 8);
-      hipLaunchKernelGGL(cnn_window_sum_kernel, dim3((unsigned)sb), dim3(256), 0, s, level_table(k), wt.perm, wt.child_start, wt.n, wt.rows);
+      hipLaunchKernelGGL(cnn_window_sum_kernel, dim3((unsigned)sb), dim3(256), 0, s, lv.rows, wt.perm, wt.child_start, wt.n, wt.rows);
       cnn_level_io wio = cnn_window_positions(D, wt);
       wio.dT1 = wt.rows;
       backward(wt.codes, wt.n, t1_buf, wio);
     }
   }
-  hipLaunchKernelGGL(cnn_finalize_kernel, dim3((D.total + 3) / 4), dim3(256), 0, s, ws->cnn_partials, (int)bw_blocks, D.total, packed + 2);
+  hipLaunchKernelGGL(cnn_finalize_kernel, dim3((D.total + 3) / 4), dim3(256), 0, s, ws->cnn_partials, (int)bw.blocks, D.total, packed + 2);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
@@ -294,20 +313,19 @@ void plan_drop_cnn_levels(bear_plan *plan) {
 
 int bear_plan_attach_cnn_levels(bear_plan *plan, const uint64_t *kmer_code, int lag, int filter_width, int *n_levels, void *stream) {
   if (n_levels) *n_levels = 0;
-  if (!plan || plan->ncol != 5 || lag < 1 || lag > CNN_MAX_LAG || filter_width < 1 || filter_width > lag) return BEAR_ERR_INVALID_ARG;
+  if (!plan || plan->ncol != 5 || !cnn_shape_ok(lag, filter_width, CNN_NF, CNN_L1)) return BEAR_ERR_INVALID_ARG;
   if (plan->n_rows && (!kmer_code || misaligned(kmer_code))) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipStreamSynchronize(s));
   plan_drop_cnn_levels(plan);                          // a plan holds one set of levels: the new one replaces it
   const cnn_dims D = cnn_make_dims(lag, filter_width);
   // (the part form of the backward kernel is the one with a position range: shapes whose staging does not fit keep the plain step)
-  if (sizeof(double) * (cnnq_fixed_doubles(D) + (size_t)cnnq<2>::WAVES * cnnq<2>::WAVE_DOUBLES) > 160u * 1024u) return BEAR_OK;
+  if (cnnq_lds_bytes(D, cnnq<2>::WAVES) > CU_LDS_BYTES) return BEAR_OK;
   if (plan->n_rows < 2 || plan->n_live_rows != plan->n_rows) return BEAR_OK;   // (the step walks the plan's lists instead: no levels)
   const unsigned long long *below = reinterpret_cast<const unsigned long long *>(kmer_code);
   uint64_t n_below = plan->n_rows;
   int misses = 0;
-  double keep_ratio = 0.6;
-  if (const char *r = getenv("BEAR_AMD_CNN_LEVEL_RATIO")) keep_ratio = atof(r);     // developer switch (scripts/dev/cnn_levels_time.py)
+  const double keep_ratio = 0.6;
   for (int k = 1; k <= D.P - 1 && misses < 3; ++k) {
     bear_level_dev lv;
     const int st = bear_level_build(below, n_below, lag - k, &lv, s);
@@ -334,23 +352,21 @@ int bear_plan_attach_cnn_levels(bear_plan *plan, const uint64_t *kmer_code, int 
   // each only while the level holds at least eight rows per distinct window (a table costs one position per window plus a 128-byte
   // gather per row and direction; a position evaluated per row costs ~25 times that gather).
   if (!getenv("BEAR_AMD_CNN_NO_WINDOWS")) {
-    const int K = plan->n_cnn_levels;
-    for (int k = 0; k <= K; ++k) {
-      const unsigned long long *codes_k = k == 0 ? reinterpret_cast<const unsigned long long *>(kmer_code) : plan->cnn_levels[k - 1].codes;
-      const uint64_t n_k = k == 0 ? plan->n_rows : plan->cnn_levels[k - 1].n;
-      const int L = k == 0 ? lag : plan->cnn_levels[k - 1].letters;
-      const int p_hi = L - filter_width + 1, p_lo = k == K ? 0 : plan->cnn_levels[k].letters - filter_width + 1;
+    const cnn_level_view ctx = cnn_contexts(kmer_code, plan->n_rows, nullptr, lag);
+    for (int k = 0; k <= plan->n_cnn_levels; ++k) {
+      const cnn_level_view lv = cnn_level(plan, k, ctx);
+      const cnn_level_io own = cnn_level_positions(plan, D, k);      // (no table attached yet: all the level's own positions)
       bear_window_dev built[CNN_MAX_WIN];
       int nb = 0;
-      for (int p = p_hi - 1; p >= p_lo && nb < CNN_MAX_WIN && n_k >= 64; --p) {
+      for (int p = own.p_hi - 1; p >= own.p_lo && nb < CNN_MAX_WIN && lv.n >= 64; --p) {
         bear_window_dev wt;
-        const int st = bear_window_build(codes_k, n_k, p, filter_width, &wt, s);
+        const int st = bear_window_build(lv.codes, lv.n, p, filter_width, &wt, s);
         if (st != BEAR_OK) {
           for (int q = 0; q < nb; ++q) bear_window_free(&built[q]);
           plan_drop_cnn_levels(plan);
           return st;
         }
-        if (wt.n * 8 > n_k) {
+        if (wt.n * 8 > lv.n) {
           bear_window_free(&wt);
           break;
         }
@@ -398,30 +414,21 @@ int bear_plan_cnn_level_rows(const bear_plan *plan, uint64_t *rows_out, int *let
 // The forward pass alone over a plan's prefix levels (evaluation-style callers, bench.py): prior rows and the contexts' layer-1 sums.
 static int cnn_forward_levels(bear_ws *ws, const bear_plan *plan, const cnn_dims &D, const uint64_t *kmer_code, uint64_t n_rows,
                               const double *params, double *prior, double *t1_buf, hipStream_t s) {
-  const int K = plan->n_cnn_levels;
-  const size_t fwd_lds = sizeof(double) * (BEAR_EXPTAB_N + (size_t)D.fw * 6 * CNN_NF + (CNN_THREADS / 64) * CNN_FWD_SCRATCH);
-  for (int k = K; k >= 0; --k) {
+  const cnn_level_view ctx = cnn_contexts(kmer_code, n_rows, t1_buf, D.lag);
+  for (int k = plan->n_cnn_levels; k >= 0; --k) {
     for (int q = 0; q < plan->n_cnn_win[k]; ++q) {          // the level's window tables first: one position over its distinct windows
       const bear_window_dev &wt = plan->cnn_win[k][q];
-      const uint64_t groups = (wt.n + 63) / 64;
-      const int blocks = cnn_forward_grid(ws, groups);
-      hipLaunchKernelGGL(cnn_forward_kernel, dim3((unsigned)blocks), dim3(CNN_THREADS), fwd_lds, s, wt.codes, wt.n, D, params,
-                         static_cast<double *>(nullptr), wt.rows, static_cast<const pln_tile *>(nullptr), static_cast<const uint16_t *>(nullptr),
-                         groups, cnn_window_positions(D, wt));
+      launch_cnn_forward_rows(ws, D, wt.codes, wt.n, params, nullptr, wt.rows, cnn_window_positions(D, wt), s);
     }
+    const cnn_level_view lv = cnn_level(plan, k, ctx);
     cnn_level_io io = cnn_level_positions(plan, D, k);
     cnn_level_sources(plan, k, io);
-    const uint64_t n = k == 0 ? n_rows : plan->cnn_levels[k - 1].n, groups = (n + 63) / 64;
-    const int blocks = cnn_forward_grid(ws, groups);
-    if (k == 0 && io.p_lo >= io.p_hi && !getenv("BEAR_AMD_CNN_NO_HEAD_KERNEL")) {      // the contexts evaluate no position themselves: the head alone
-      const int hb = grid_capped((n + 32 * 16 - 1) / (32 * 16), (uint64_t)ws->num_cu * 2);
-      hipLaunchKernelGGL(cnn_forward_head_kernel, dim3((unsigned)hb), dim3(1024), 0, s, n, D, params, prior, t1_buf, io);
+    if (k == 0 && cnn_level0_head_only(io)) {      // the head alone
+      const int hb = grid_capped((lv.n + 32 * 16 - 1) / (32 * 16), (uint64_t)ws->num_cu * 2);
+      hipLaunchKernelGGL(cnn_forward_head_kernel, dim3((unsigned)hb), dim3(1024), 0, s, lv.n, D, params, prior, t1_buf, io);
       continue;
     }
-    hipLaunchKernelGGL(cnn_forward_kernel, dim3((unsigned)blocks), dim3(CNN_THREADS), fwd_lds, s,
-                       k == 0 ? reinterpret_cast<const unsigned long long *>(kmer_code) : plan->cnn_levels[k - 1].codes, n, D, params,
-                       k == 0 ? prior : static_cast<double *>(nullptr), k == 0 ? t1_buf : plan->cnn_levels[k - 1].rows,
-                       static_cast<const pln_tile *>(nullptr), static_cast<const uint16_t *>(nullptr), groups, io);
+    launch_cnn_forward_rows(ws, D, lv.codes, lv.n, params, k == 0 ? prior : nullptr, lv.rows, io, s);
   }
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
@@ -434,8 +441,7 @@ int bear_cnn_forward_plan_f64(bear_ws *ws, const bear_plan *plan, const uint64_t
   if (!plan || plan->n_rows != n_rows || plan->device != ws->device) return BEAR_ERR_INVALID_ARG;
   if (n_rows == 0) return BEAR_OK;
   if (!kmer_code || !params || !prior || !t1_save || misaligned(t1_save) || misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
-  if (!((plan->n_cnn_levels > 0 || plan->n_cnn_windows > 0) && plan->cnn_codes == kmer_code && plan->cnn_lag == lag && plan->cnn_fw == filter_width) ||
-      getenv("BEAR_AMD_CNN_NO_LEVELS"))
+  if (!cnn_plan_has_levels_for(plan, kmer_code, lag, filter_width) || getenv("BEAR_AMD_CNN_NO_LEVELS"))
     return bear_cnn_forward_f64(ws, kmer_code, n_rows, lag, filter_width, num_filters, layer1_width, params, prior, t1_save, stream);
   return cnn_forward_levels(ws, plan, cnn_make_dims(lag, filter_width), kmer_code, n_rows, params, prior, t1_save, static_cast<hipStream_t>(stream));
 }
@@ -451,28 +457,23 @@ int bear_net_cnn_train_reduce_f64(bear_ws *ws, const bear_plan *plan, const uint
   hipStream_t s = static_cast<hipStream_t>(stream);
   const cnn_dims D = cnn_make_dims(lag, filter_width);
   const double *params = theta + 1;
-  if ((plan->n_cnn_levels > 0 || plan->n_cnn_windows > 0) && plan->cnn_codes == kmer_code && plan->cnn_lag == lag && plan->cnn_fw == filter_width &&
-      plan->n_live_rows == n_rows && !getenv("BEAR_AMD_CNN_NO_LEVELS") && !cnn_parts_form_forced_off())
+  if (cnn_plan_has_levels_for(plan, kmer_code, lag, filter_width) && plan->n_live_rows == n_rows && !getenv("BEAR_AMD_CNN_NO_LEVELS") &&
+      !cnn_parts_form_forced_off())
     return cnn_train_reduce_levels(ws, plan, D, kmer_code, n_rows, theta, prior_buf, t1_buf, grad_rows_buf, eps, train_ar, packed, s);
   {
-    const size_t lds = sizeof(double) * (BEAR_EXPTAB_N + (size_t)filter_width * 6 * CNN_NF + (CNN_THREADS / 64) * CNN_FWD_SCRATCH);
     // only the contexts that hold training counts: the DM kernel reads nobody else's prior row (their gradient rows are zero).
     // Only together with the backward kernel that walks the same lists (shapes whose LDS does not fit take all rows in both).
-    int bw_waves = 0, bw_parts = 0;
-    size_t bw_lds = 0;
-    uint64_t bw_blocks = 0;
-    st = cnn_backward_grid(ws, D, n_rows, filter_width, &bw_waves, &bw_parts, &bw_lds, &bw_blocks, s, 0);
+    cnn_backward_geom bw;
+    st = cnn_backward_grid(ws, D, n_rows, &bw, s, 0);
     if (st != BEAR_OK) return st;
-    const bool lists = plan->live && bw_parts && plan->n_live_rows < n_rows;   // all rows live: plain groups of rows
-    const uint64_t groups = lists ? plan->n_tiles : (n_rows + 63) / 64;
-    const int blocks = cnn_forward_grid(ws, groups);
-    hipLaunchKernelGGL(cnn_forward_kernel, dim3((unsigned)blocks), dim3(CNN_THREADS), lds, s,
-                       reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, D, params, prior_buf, t1_buf,
-                       lists ? plan->tiles : nullptr, lists ? plan->live : nullptr, groups, cnn_all_positions(D));
+    const bool lists = plan->live && bw.parts && plan->n_live_rows < n_rows;   // all rows live: plain groups of rows
+    launch_cnn_forward(ws, D, reinterpret_cast<const unsigned long long *>(kmer_code), n_rows, params, prior_buf, t1_buf,
+                       lists ? plan->tiles : nullptr, lists ? plan->live : nullptr, lists ? plan->n_tiles : (n_rows + 63) / 64,
+                       cnn_all_positions(D), s);
   }
   st = launch_prior_plan_grad(ws, plan, prior_buf, params_eps(eps), theta, train_ar, 1, packed, grad_rows_buf, s);   // softmax rows: normalised
   if (st != BEAR_OK) return st;
-  return launch_cnn_backward(ws, D, kmer_code, n_rows, filter_width, params, t1_buf, prior_buf, grad_rows_buf, packed + 2, s, 0, plan);
+  return launch_cnn_backward(ws, D, kmer_code, n_rows, params, t1_buf, prior_buf, grad_rows_buf, packed + 2, s, 0, plan);
 }
 
 int bear_net_cnn_train_step_f64(bear_ws *ws, const bear_plan *plan, const uint32_t *counts, const uint64_t *kmer_code, uint64_t n_rows,
@@ -514,7 +515,7 @@ int bear_cnn_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows,
   const cnn_dims D = cnw_make_dims(lag, filter_width);
   // two resident blocks per CU where their LDS lets them in (short filters), else one; the rows do not depend on the grid
   const size_t lds = cnw_fwd_lds(lag, filter_width);
-  const uint64_t per_cu = 2 * lds <= 160u * 1024u ? 2 : 1;
+  const uint64_t per_cu = 2 * lds <= CU_LDS_BYTES ? 2 : 1;
   const int grid = grid_capped((n_rows + CNW_FWD_TILE - 1) / CNW_FWD_TILE, (uint64_t)ws->num_cu * per_cu);
   hipLaunchKernelGGL(cnn_wide_forward_kernel, dim3(grid), dim3(CNW_FWD_THREADS), lds, static_cast<hipStream_t>(stream), codes, n_rows, D,
                      params, prior, t1_save);

@@ -100,11 +100,154 @@ static inline cnn_level_io cnn_all_positions(const cnn_dims &D) {
   return io;
 }
 
+// ---- what a block stages into LDS before its main loop.  `stride` is the block's thread count: blockDim.x in the backward kernels
+// (a block may be one wave), the constant CNN_THREADS in the forward kernel (with blockDim.x there it tripled its scratch).
+template <class Stride>
+__device__ __forceinline__ void cnn_stage_exptab(double *exptab, Stride stride) {     // [BEAR_EXPTAB_N] the table of cnn_exp_neg / bear_exp_tab
+  for (int k = threadIdx.x; k < BEAR_EXPTAB_N; k += stride) exptab[k] = exp2((double)k * (1.0 / BEAR_EXPTAB_N));
+}
 // LDS image of the filter bank: 6 letter rows per tap (row 5 = zeros: characters outside the alphabet, core.py:173)
-__device__ __forceinline__ void cnn_stage_filters(double *Fs, const double *__restrict__ params, const cnn_dims &D) {
-  for (int k = threadIdx.x; k < D.fw * 6 * CNN_NF; k += CNN_THREADS) {
+template <class Stride>
+__device__ __forceinline__ void cnn_stage_filters(double *Fs, const double *__restrict__ params, const cnn_dims &D, Stride stride) {
+  for (int k = threadIdx.x; k < D.fw * 6 * CNN_NF; k += stride) {
     const int w = k / (6 * CNN_NF), r = k - w * 6 * CNN_NF, a = r / CNN_NF, f = r - a * CNN_NF;
     Fs[k] = a < 5 ? params[D.oF + (w * 5 + a) * CNN_NF + f] : 0.0;
+  }
+}
+// the head's parameters that a lane reads at a part-dependent index: scale1 [16] | intercept1 [16] | weights2 [16][5]
+template <class Stride>
+__device__ __forceinline__ void cnn_stage_head_params(double *Ps1, double *Pb1, double *PW2, const double *__restrict__ params,
+                                                      const cnn_dims &D, Stride stride) {
+  for (int k = threadIdx.x; k < CNN_L1; k += stride) {
+    Ps1[k] = params[D.os1 + k];
+    Pb1[k] = params[D.ob1 + k];
+  }
+  for (int k = threadIdx.x; k < CNN_L1 * 5; k += stride) PW2[k] = params[D.oW2 + k];
+}
+
+// the packed context whose every letter is "other": a row of exact zeros in every filter product (the backward kernels' dead lanes)
+constexpr unsigned long long cnn_all_other_code() {
+  unsigned long long code = 0;
+  for (int l = 0; l < 21; ++l) code |= 5ull << (3 * l);
+  return code;
+}
+
+// ---- values that cross lanes
+template <int CTRL>
+__device__ __forceinline__ double cnn_dpp(double v) {
+  const long long q = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)q, CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(q >> 32), CTRL, 0xf, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (uint32_t)lo);
+}
+// v plus the value of the lane 16 (FAR = false: v_permlane16_swap) or 32 (FAR = true: v_permlane32_swap) lanes away, in every lane
+template <bool FAR>
+__device__ __forceinline__ double cnn_swap_add(double v) {
+  const long long q = __double_as_longlong(v);
+  const uint32_t lo = (uint32_t)q, hi = (uint32_t)(q >> 32);
+  const auto a = FAR ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false) : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto c = FAR ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false) : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  return __longlong_as_double(((long long)c[0] << 32) | a[0]) + __longlong_as_double(((long long)c[1] << 32) | a[1]);
+}
+// the same lane of the four rows of 16 summed (every lane gets the sum)
+__device__ __forceinline__ double cnn_rows_sum(double v) { return cnn_swap_add<true>(cnn_swap_add<false>(v)); }
+__device__ __forceinline__ double cnn_half_sum_all(double v) {   // every lane gets the sum over its half of the wave (32 lanes)
+  v += cnn_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += cnn_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += cnn_dpp<0x124>(v);   // row_ror:4
+  v += cnn_dpp<0x128>(v);   // row_ror:8
+  return cnn_swap_add<false>(v);
+}
+// v summed over the Q lanes of a context (lanes ctx, ctx + 64 / Q, ...): every one of them gets the sum
+template <int Q>
+__device__ __forceinline__ double cnnq_psum(double v) {
+  static_assert(Q == 1 || Q == 2 || Q == 4, "lanes per context");
+  if (Q == 4) v = cnn_swap_add<false>(v);
+  return Q == 1 ? v : cnn_swap_add<true>(v);
+}
+// a 64-bit value of the first active lane / of lane `src`, as a scalar
+__device__ __forceinline__ unsigned long long cnn_read_first(unsigned long long v) {
+  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+__device__ __forceinline__ unsigned long long cnn_read_lane(unsigned long long v, int src) {
+  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+}
+// the lanes of `rem` whose v is that of rem's first lane (*w)
+__device__ __forceinline__ unsigned long long cnn_next_run(unsigned long long v, unsigned long long rem, unsigned long long *w) {
+  *w = cnn_read_lane(v, __builtin_ctzll(rem));
+  return __builtin_amdgcn_ballot_w64(v == *w) & rem;
+}
+// the CONTIGUOUS range [lo, hi) of n_groups groups that wave `wave` of the block's n_waves takes
+struct cnn_range {
+  uint64_t lo, hi;
+};
+__device__ __forceinline__ cnn_range cnn_wave_groups(uint64_t n_groups, uint32_t wave, uint32_t n_waves) {
+  const uint64_t wave_id = (uint64_t)blockIdx.x * n_waves + wave, wave_cnt = (uint64_t)gridDim.x * n_waves;
+  return {n_groups * wave_id / wave_cnt, n_groups * (wave_id + 1) / wave_cnt};
+}
+
+// ---- a wave's walk over group g, TILE contexts at a time (the lane's slot c = lane % TILE): without lists, group g = rows [TILE g,
+// TILE g + TILE); with the plan's lists (the training step) group g = plan tile g and only its contexts that hold counts.  A chunk's
+// list entries are read one chunk ahead: its rows' loads then start at once.
+template <int TILE>
+struct cnn_group_walk {
+  const uint16_t *lst;
+  uint64_t base;
+  uint32_t cnt, row_next;
+  // PAST_FIRST: without lists a slot past the group's end names the group's first row (the forward kernel reads it), not a row past it
+  template <bool PAST_FIRST>
+  __device__ __forceinline__ void open(const pln_tile *__restrict__ tiles, const uint16_t *__restrict__ live_lists, uint64_t g, uint64_t n_rows,
+                                       uint32_t c) {
+    lst = live_lists ? live_lists + g * PLN_LIVE_STRIDE : nullptr;
+    base = lst ? tiles[g].row0 : g * TILE;
+    cnt = lst ? (uint32_t)lst[0] : (uint32_t)(n_rows - base < (uint64_t)TILE ? n_rows - base : (uint64_t)TILE);
+    row_next = lst ? (uint32_t)lst[1 + (c < cnt ? c : 0u)] : (PAST_FIRST ? (c < cnt ? c : 0u) : c);
+  }
+  // the row of slot c in the chunk at c0 (with lists, slots past the end: the chunk's first context); asks for the next chunk's entry
+  __device__ __forceinline__ uint64_t row(uint32_t c0, uint32_t c) {
+    const uint64_t i = base + (uint64_t)row_next;
+    if (lst && c0 + TILE < cnt) row_next = (uint32_t)lst[1 + (c0 + TILE + c < cnt ? c0 + TILE + c : 0u)];
+    return i;
+  }
+};
+
+// ---- rows of layer-1 sums: N consecutive units of a [..][16] table (16-byte aligned: N and the first unit are even)
+template <int N>
+__device__ __forceinline__ void cnn_load_row(double (&t)[N], const double *src) {
+  const double2 *s = reinterpret_cast<const double2 *>(src);
+#pragma unroll
+  for (int j = 0; j < N / 2; ++j) {
+    const double2 v = s[j];
+    t[2 * j] = v.x;
+    t[2 * j + 1] = v.y;
+  }
+}
+template <int N>
+__device__ __forceinline__ void cnn_add_row(double (&t)[N], const double *src) {
+  const double2 *s = reinterpret_cast<const double2 *>(src);
+#pragma unroll
+  for (int j = 0; j < N / 2; ++j) {
+    const double2 v = s[j];
+    t[2 * j] += v.x;
+    t[2 * j + 1] += v.y;
+  }
+}
+template <int N>
+__device__ __forceinline__ void cnn_store_row(double *dst, const double (&t)[N]) {
+  double2 *o = reinterpret_cast<double2 *>(dst);
+#pragma unroll
+  for (int j = 0; j < N / 2; ++j) o[j] = make_double2(t[2 * j], t[2 * j + 1]);
+}
+// units [first_unit, first_unit + N) of row i's layer-1 sums put together from what cnn_level_io names: the parent's row (the earlier
+// positions; neighbours share the parent), then one 128-byte gather per window table (the tables are a few MB).  t1 is zero on entry.
+template <int N>
+__device__ __forceinline__ void cnn_gather_t1(double (&t1)[N], const cnn_level_io &io, uint64_t i, uint32_t first_unit) {
+  if (io.t1_parent) cnn_load_row<N>(t1, io.t1_parent + (size_t)io.parent[i] * CNN_L1 + first_unit);
+#pragma unroll
+  for (int q = 0; q < CNN_MAX_WIN; ++q) {
+    if (q < io.n_win) cnn_add_row<N>(t1, io.win_rows[q] + (size_t)io.win_row_of[q][i] * CNN_L1 + first_unit);
   }
 }
 
@@ -169,21 +312,29 @@ __device__ __forceinline__ double cnn_conv_norm(const double *Fs, unsigned long 
   return r;
 }
 
-// layer 1 onwards: t1 -> normalised n1, e1 (+ derivative), 1/sigma
+// ---- the head with Q lanes per context, a lane holding CNN_L1 / Q of the 16 units (Q = 1: cnn_forward_kernel, cnn_backward_kernel;
+// Q = 2: the part kernel and the two head-only kernels)
+// layer-1 norm over the Q parts: c1 <- t1 - mean (NOT yet scaled), returns 1/sigma.  The callers scale where they use the value:
+// each has its own loop around the elu.
+template <int Q>
+__device__ __forceinline__ double cnnq_layer1_norm(const double (&t1)[CNN_L1 / Q], double (&c1)[CNN_L1 / Q]) {
+  double mu = 0.0;
+#pragma unroll
+  for (int j = 0; j < CNN_L1 / Q; ++j) mu += t1[j];
+  mu = cnnq_psum<Q>(mu) * (1.0 / CNN_L1);
+  double var = 0.0;
+#pragma unroll
+  for (int j = 0; j < CNN_L1 / Q; ++j) {
+    c1[j] = t1[j] - mu;
+    var = __builtin_fma(c1[j], c1[j], var);
+  }
+  return cnn_rsqrt(cnnq_psum<Q>(var) * (1.0 / CNN_L1) + CNN_LN_EPS);
+}
+// layer 1 onwards with one lane per context: t1 -> normalised n1, e1 (+ derivative), 1/sigma
 __device__ __forceinline__ double cnn_layer1(const double (&t1)[CNN_L1], const double *__restrict__ params, const cnn_dims &D,
                                              const double *exptab, double (&n1)[CNN_L1], double (&e1)[CNN_L1],
                                              double (&d1)[CNN_L1]) {
-  double mu = 0.0;
-#pragma unroll
-  for (int j = 0; j < CNN_L1; ++j) mu += t1[j];
-  mu *= 1.0 / CNN_L1;
-  double var = 0.0;
-#pragma unroll
-  for (int j = 0; j < CNN_L1; ++j) {
-    n1[j] = t1[j] - mu;
-    var = __builtin_fma(n1[j], n1[j], var);
-  }
-  const double r = cnn_rsqrt(var * (1.0 / CNN_L1) + CNN_LN_EPS);
+  const double r = cnnq_layer1_norm<1>(t1, n1);
 #pragma unroll
   for (int j = 0; j < CNN_L1; ++j) {
     n1[j] *= r;
@@ -191,30 +342,44 @@ __device__ __forceinline__ double cnn_layer1(const double (&t1)[CNN_L1], const d
   }
   return r;
 }
+// softmax backward: dz = pr (gp - <pr, gp>)
+__device__ __forceinline__ void cnn_softmax_back(const double (&pr)[5], const double (&gp)[5], double (&dz)[5]) {
+  double sg = 0.0;
+#pragma unroll
+  for (int b = 0; b < 5; ++b) sg = __builtin_fma(pr[b], gp[b], sg);
+#pragma unroll
+  for (int b = 0; b < 5; ++b) dz[b] = pr[b] * (gp[b] - sg);
+}
+// layer 2 and the layer-1 norm backward over a lane's CNN_L1 / Q units: dy1 = (weights2 dz) elu', dT1 = r1 (dn - mean dn - n1 mean(dn n1))
+// with dn = dy1 scale1.  W2 and s1 point at the lane's first unit.  elu_deriv(j) gives elu' of unit j and is called once per unit,
+// in order, before anything else of the unit is read: the head-only kernel scales n1[j] and evaluates the elu there.
+template <int Q, class EluDeriv>
+__device__ __forceinline__ void cnnq_layer2_back(const double (&dz)[5], const double *W2, const double *s1, const double (&n1)[CNN_L1 / Q],
+                                                 double r1, EluDeriv elu_deriv, double (&dy1)[CNN_L1 / Q], double (&dT1)[CNN_L1 / Q]) {
+  double ma = 0.0, mb = 0.0;
+#pragma unroll
+  for (int j = 0; j < CNN_L1 / Q; ++j) {
+    const double d1 = elu_deriv(j);
+    double de = 0.0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) de = __builtin_fma(W2[j * 5 + b], dz[b], de);
+    dy1[j] = de * d1;
+    const double dn = dy1[j] * s1[j];
+    dT1[j] = dn;
+    ma += dn;
+    mb = __builtin_fma(dn, n1[j], mb);
+  }
+  ma = cnnq_psum<Q>(ma) * (1.0 / CNN_L1);
+  mb = cnnq_psum<Q>(mb) * (1.0 / CNN_L1);
+#pragma unroll
+  for (int j = 0; j < CNN_L1 / Q; ++j) dT1[j] = r1 * (dT1[j] - ma - n1[j] * mb);
+}
 
 // One window shared by all 64 contexts of a wave (or by a run of them): its conv row, layer norm and elu once (lane = filter),
 // then its contribution to the 16 layer-1 sums (lane = unit).  Out of line: the forward kernel keeps its registers for the
 // per-context path.  TWO (position, window) items go through at once, one per half of the wave (lane & 31 = filter, then = unit): the work is a
 // chain of dependent steps, so the second item costs nothing.  Us: e0 of the items [0, 32) | [32, 64), their contributions
 // [64, 80) | [80, 96).
-__device__ __forceinline__ double cnn_fwd_half_sum(double v) {   // every lane gets the sum over its half of the wave (32 lanes)
-  auto dpp = [](double x, auto ctrl_tag) {
-    constexpr int CTRL = decltype(ctrl_tag)::value;
-    const long long q = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)q, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(q >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (uint32_t)lo);
-  };
-  v += dpp(v, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
-  v += dpp(v, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
-  v += dpp(v, std::integral_constant<int, 0x124>{});   // row_ror:4
-  v += dpp(v, std::integral_constant<int, 0x128>{});   // row_ror:8
-  const long long q = __double_as_longlong(v);
-  const uint32_t lo = (uint32_t)q, hi = (uint32_t)(q >> 32);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto c = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return __longlong_as_double(((long long)c[0] << 32) | a[0]) + __longlong_as_double(((long long)c[1] << 32) | a[1]);
-}
 __device__ __noinline__ void cnn_forward_shared_window2(const double *Fs, const double *exptab, double *Us, const double *__restrict__ s0_all,
                                                         const double *__restrict__ b0_all, const double *__restrict__ W1_all, int fw,
                                                         int p_a, unsigned long long win_a, int p_b, unsigned long long win_b, uint32_t lane) {
@@ -234,9 +399,9 @@ __device__ __noinline__ void cnn_forward_shared_window2(const double *Fs, const 
     c >>= 12;
   }
   const bool in = l32 < CNN_NF;
-  const double mu = cnn_fwd_half_sum(in ? xf : 0.0) * (1.0 / CNN_NF);
+  const double mu = cnn_half_sum_all(in ? xf : 0.0) * (1.0 / CNN_NF);
   const double d = xf - mu;
-  const double r = cnn_rsqrt(cnn_fwd_half_sum(in ? d * d : 0.0) * (1.0 / CNN_NF) + CNN_LN_EPS);
+  const double r = cnn_rsqrt(cnn_half_sum_all(in ? d * d : 0.0) * (1.0 / CNN_NF) + CNN_LN_EPS);
   double dv;
   const double e = cnn_elu(__builtin_fma(s0_all[p * CNN_NF + (int)f], d * r, b0_all[p * CNN_NF + (int)f]), exptab, dv);
   double *Ue = Us + (second ? 32 : 0);
@@ -251,6 +416,10 @@ __device__ __noinline__ void cnn_forward_shared_window2(const double *Fs, const 
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// its LDS: exp table | filter image | per-wave scratch
+static inline size_t cnn_fwd_lds_bytes(int fw) {
+  return sizeof(double) * (BEAR_EXPTAB_N + (size_t)fw * 6 * CNN_NF + (CNN_THREADS / 64) * CNN_FWD_SCRATCH);
+}
 __global__ __launch_bounds__(CNN_THREADS, 4) void cnn_forward_kernel(const unsigned long long *__restrict__ codes, uint64_t n_rows,
                                                                    cnn_dims D, const double *__restrict__ params,
                                                                    double *__restrict__ prior, double *__restrict__ t1_save,
@@ -259,8 +428,8 @@ __global__ __launch_bounds__(CNN_THREADS, 4) void cnn_forward_kernel(const unsig
   extern __shared__ __attribute__((aligned(16))) double cnn_lds[];
   double *exptab = cnn_lds;                       // [128]
   double *Fs = cnn_lds + BEAR_EXPTAB_N;           // [fw][6][nf]
-  for (int k = threadIdx.x; k < BEAR_EXPTAB_N; k += blockDim.x) exptab[k] = exp2((double)k * (1.0 / BEAR_EXPTAB_N));   // (a block may be one wave)
-  cnn_stage_filters(Fs, params, D);
+  cnn_stage_exptab(exptab, blockDim.x);
+  cnn_stage_filters(Fs, params, D, CNN_THREADS);
   __syncthreads();
   // A wave walks groups of contexts, 64 at a time: without lists, group g = rows [64 g, 64 g + 64); with the plan's lists
   // (the training step) group g = plan tile g and only its contexts that hold counts -- nothing reads the others' rows.
@@ -270,47 +439,24 @@ __global__ __launch_bounds__(CNN_THREADS, 4) void cnn_forward_kernel(const unsig
   const unsigned long long wmask = 3 * D.fw >= 64 ? ~0ull : (1ull << (3 * D.fw)) - 1ull;
   // A wave takes a CONTIGUOUS range of groups: in a k-mer-sorted table consecutive chunks share the windows of their leading
   // positions, and the contribution of such a window (16 layer-1 sums) is kept in LDS until the window changes.
-  const uint64_t wave_id = (uint64_t)blockIdx.x * n_waves + wave, wave_cnt = (uint64_t)gridDim.x * n_waves;
+  const cnn_range groups = cnn_wave_groups(n_groups, wave, n_waves);
   unsigned long long kept_w[CNN_FWD_KEEP] = {};
   uint32_t kept = 0;                          // bit p: Us[48 + 16 p ..) holds the contribution of window kept_w[p] at position p
-  for (uint64_t g = n_groups * wave_id / wave_cnt; g < n_groups * (wave_id + 1) / wave_cnt; ++g) {
-    const uint16_t *lst = live_lists ? live_lists + g * PLN_LIVE_STRIDE : nullptr;
-    const uint64_t base = lst ? tiles[g].row0 : g * 64;
-    const uint32_t cnt = lst ? (uint32_t)lst[0] : (uint32_t)(n_rows - base < 64 ? n_rows - base : 64);
-   uint32_t row_next = lst ? (uint32_t)lst[1 + (lane < cnt ? lane : 0u)] : (lane < cnt ? lane : 0u);   // a chunk's list entries are read one chunk ahead
-   for (uint32_t c0 = 0; c0 < cnt; c0 += 64) {
-    const bool live = c0 + lane < cnt;
-    const uint64_t i = base + (uint64_t)row_next;                                                        // lanes past the end: the first context
-    if (lst && c0 + 64 < cnt) row_next = (uint32_t)lst[1 + (c0 + 64 + lane < cnt ? c0 + 64 + lane : 0u)];
+  for (uint64_t g = groups.lo; g < groups.hi; ++g) {
+   cnn_group_walk<64> walk;
+   walk.open<true>(tiles, live_lists, g, n_rows, lane);
+   for (uint32_t c0 = 0; c0 < walk.cnt; c0 += 64) {
+    const bool live = c0 + lane < walk.cnt;
+    const uint64_t i = walk.row(c0, lane);                                                               // lanes past the end: the first context
     unsigned long long code = codes[i];              // lanes past the end repeat the chunk's first context (nothing is stored for them)
     {
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)code), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(code >> 32));
-      if (!live) code = ((unsigned long long)hi << 32) | lo;
+      const unsigned long long first = cnn_read_first(code);
+      if (!live) code = first;
     }
     double t1[CNN_L1];
 #pragma unroll
     for (int j = 0; j < CNN_L1; ++j) t1[j] = 0.0;
-    if (io.t1_parent) {      // a level's rows start from their parent's sums (the earlier positions); neighbours share the parent
-      const double2 *src = reinterpret_cast<const double2 *>(io.t1_parent + (size_t)io.parent[i] * CNN_L1);
-#pragma unroll
-      for (int j = 0; j < CNN_L1 / 2; ++j) {
-        const double2 v = src[j];
-        t1[2 * j] = v.x;
-        t1[2 * j + 1] = v.y;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < CNN_MAX_WIN; ++q) {      // positions that come from window tables: one 128-byte gather each (the tables are a few MB)
-      if (q < io.n_win) {
-        const double2 *src = reinterpret_cast<const double2 *>(io.win_rows[q] + (size_t)io.win_row_of[q][i] * CNN_L1);
-#pragma unroll
-        for (int j = 0; j < CNN_L1 / 2; ++j) {
-          const double2 v = src[j];
-          t1[2 * j] += v.x;
-          t1[2 * j + 1] += v.y;
-        }
-      }
-    }
+    cnn_gather_t1<CNN_L1>(t1, io, i, 0u);      // a level's rows start from their parent's sums, plus the positions that come from window tables
     // In a k-mer-sorted batch (bear_net.train sorts at upload) the 64 contexts of a wave share their leading letters: a window
     // [p, p + fw) that lies inside the shared prefix gives every context the SAME conv row, activations and layer-1
     // contribution.  Then 30 lanes compute the row once (lane = filter), 16 lanes the contribution (lane = unit), and every
@@ -339,22 +485,16 @@ __global__ __launch_bounds__(CNN_THREADS, 4) void cnn_forward_kernel(const unsig
       };
       for (int p = io.p_lo; p < io.p_hi; ++p) {
         const unsigned long long win = (code >> (3 * p)) & wmask;
-        auto next_run = [&](unsigned long long rem, unsigned long long *w) {   // the lanes that share the window of rem's first lane
-          const int leader = __builtin_ctzll(rem);
-          *w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(win >> 32), leader) << 32) |
-               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)win, leader);
-          return __builtin_amdgcn_ballot_w64(win == *w) & rem;
-        };
         unsigned long long rem = ~0ull, wv;
-        for (int runs = 0; rem != 0ull && runs < CNN_FWD_RUNS; ++runs) rem &= ~next_run(rem, &wv);
+        for (int runs = 0; rem != 0ull && runs < CNN_FWD_RUNS; ++runs) rem &= ~cnn_next_run(win, rem, &wv);
         if (rem != 0ull) {
           p_ctx = p;
           break;
         }
         for (rem = ~0ull; rem != 0ull;) {
-          const unsigned long long m = next_run(rem, &wv);
+          const unsigned long long m = cnn_next_run(win, rem, &wv);
           rem &= ~m;
-          const bool full = m == ~0ull && p < CNN_FWD_KEEP;   // the whole wave shares the window: kept from the previous chunk?
+          const bool full = m == ~0ull && p < CNN_FWD_KEEP;  // the whole wave shares the window: kept from the previous chunk?
           if (full) {
             bool have = false;
 #pragma unroll
@@ -412,11 +552,7 @@ __global__ __launch_bounds__(CNN_THREADS, 4) void cnn_forward_kernel(const unsig
       }
     }
     if (!io.head) {          // a level of prefixes: its rows of layer-1 sums are all there is
-      if (live) {
-        double2 *o = reinterpret_cast<double2 *>(t1_save + i * CNN_L1);
-#pragma unroll
-        for (int j = 0; j < CNN_L1 / 2; ++j) o[j] = make_double2(t1[2 * j], t1[2 * j + 1]);
-      }
+      if (live) cnn_store_row<CNN_L1>(t1_save + i * CNN_L1, t1);
       continue;
     }
     double n1[CNN_L1], e1[CNN_L1], d1[CNN_L1];
@@ -440,11 +576,7 @@ __global__ __launch_bounds__(CNN_THREADS, 4) void cnn_forward_kernel(const unsig
     if (live) {
 #pragma unroll
       for (int b = 0; b < 5; ++b) prior[i * 5 + b] = z[b] * rt;
-      if (t1_save) {
-        double2 *o = reinterpret_cast<double2 *>(t1_save + i * CNN_L1);
-#pragma unroll
-        for (int j = 0; j < CNN_L1 / 2; ++j) o[j] = make_double2(t1[2 * j], t1[2 * j + 1]);
-      }
+      if (t1_save) cnn_store_row<CNN_L1>(t1_save + i * CNN_L1, t1);
     }
    }
   }
@@ -467,6 +599,10 @@ typedef double cnn_d4 __attribute__((ext_vector_type(4)));
 #define CNN_E_DOUBLES (32 * CNN_ES)
 #define CNN_T_DOUBLES (16 * CNN_ES)
 #define CNN_WAVE_DOUBLES (CNN_E_DOUBLES + CNN_T_DOUBLES + 64)
+// LDS of cnn_backward_kernel with `waves` waves per block: exp table | filter image | gradient image | per-wave staging
+static inline size_t cnn_bwd_lds_bytes(const cnn_dims &D, int waves) {
+  return sizeof(double) * (BEAR_EXPTAB_N + (size_t)D.fw * 6 * CNN_NF + (size_t)((D.total + 1) & ~1) + (size_t)waves * CNN_WAVE_DOUBLES);
+}
 
 __device__ __forceinline__ void cnn_lds_add(double *addr, double v) { atomicAdd(addr, v); }
 
@@ -482,6 +618,10 @@ __device__ __forceinline__ void cnn_colsum_add(const double *E, double *dst, int
 
 #ifdef CNN_STAMPS   // developer build: clocks per phase of the backward tile loop, summed per wave (scripts/dev/cnn_stamps.py)
 __device__ unsigned long long cnn_stamp_sums[8];
+#define CNN_STAMP_BEGIN unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_amdgcn_s_memtime();
+#define CNN_STAMP_END                                             \
+  if (lane == 0)                                                  \
+    for (int k = 0; k < 8; ++k) atomicAdd(&cnn_stamp_sums[k], tph[k]);
 #define CNN_STAMP(k)                                              \
   {                                                               \
     const unsigned long long now = __builtin_amdgcn_s_memtime();  \
@@ -489,6 +629,8 @@ __device__ unsigned long long cnn_stamp_sums[8];
     t_prev = now;                                                 \
   }
 #else
+#define CNN_STAMP_BEGIN
+#define CNN_STAMP_END
 #define CNN_STAMP(k)
 #endif
 __global__ __launch_bounds__(CNN_THREADS) void cnn_backward_kernel(const unsigned long long *__restrict__ codes, uint64_t n_rows,
@@ -505,26 +647,21 @@ __global__ __launch_bounds__(CNN_THREADS) void cnn_backward_kernel(const unsigne
   double *E = G + ((D.total + 1) & ~1) + wave * CNN_WAVE_DOUBLES;   // [32][CNN_ES] staging
   double *T = E + CNN_E_DOUBLES;                                    // [16][CNN_ES] dT1
   unsigned long long *Cw = reinterpret_cast<unsigned long long *>(T + CNN_T_DOUBLES);   // [64] packed contexts
+  // (the table fill and the layer-2 backward below stay written out in this kernel: with cnn_stage_exptab / cnnq_layer2_back<1> its
+  // bits are the same, its code is not, and it measured 0.1 % slower in every round of both builds)
   for (int k = threadIdx.x; k < BEAR_EXPTAB_N; k += blockDim.x) exptab[k] = exp2((double)k * (1.0 / BEAR_EXPTAB_N));   // (a block may be one wave)
-  for (int k = threadIdx.x; k < D.fw * 6 * CNN_NF; k += blockDim.x) {
-    const int w = k / (6 * CNN_NF), r = k - w * 6 * CNN_NF, a = r / CNN_NF, f = r - a * CNN_NF;
-    Fs[k] = a < 5 ? params[D.oF + (w * 5 + a) * CNN_NF + f] : 0.0;
-  }
+  cnn_stage_filters(Fs, params, D, blockDim.x);
   for (int k = threadIdx.x; k < D.total; k += blockDim.x) G[k] = 0.0;
   __syncthreads();
   const uint64_t n_tiles = (n_rows + 63) / 64;
-#ifdef CNN_STAMPS
-  unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_amdgcn_s_memtime();
-#endif
+  CNN_STAMP_BEGIN
   const uint32_t lq = lane >> 4, lr = lane & 15u;     // MFMA lane coordinates: k / row-group index, row / column index
   const int n_mt = (4 * D.fw + 15) / 16;              // M tiles of the one-hot operand: rows (tap w, letter a < 4)
   for (uint64_t tile = (uint64_t)blockIdx.x * n_waves + wave; tile < n_tiles; tile += (uint64_t)gridDim.x * n_waves) {
     const uint64_t i = tile * 64 + lane;
     const bool live = i < n_rows;
     // dead lanes: every letter "other" and a zero gradient row -> all their contributions are exact zeros
-    unsigned long long code = 0;
-#pragma unroll
-    for (int l = 0; l < 21; ++l) code |= 5ull << (3 * l);
+    unsigned long long code = cnn_all_other_code();
     if (live) code = codes[i];
     Cw[lane] = code;
     double t1[CNN_L1], n1[CNN_L1], e1[CNN_L1], d1[CNN_L1];
@@ -537,13 +674,7 @@ __global__ __launch_bounds__(CNN_THREADS) void cnn_backward_kernel(const unsigne
       gp[b] = 0.0;
     }
     if (live) {
-      const double2 *src = reinterpret_cast<const double2 *>(t1_save + i * CNN_L1);
-#pragma unroll
-      for (int j = 0; j < CNN_L1 / 2; ++j) {
-        const double2 v = src[j];
-        t1[2 * j] = v.x;
-        t1[2 * j + 1] = v.y;
-      }
+      cnn_load_row<CNN_L1>(t1, t1_save + i * CNN_L1);
 #pragma unroll
       for (int b = 0; b < 5; ++b) {
         pr[b] = prior[i * 5 + b];
@@ -551,13 +682,9 @@ __global__ __launch_bounds__(CNN_THREADS) void cnn_backward_kernel(const unsigne
       }
     }
     const double r1 = cnn_layer1(t1, params, D, exptab, n1, e1, d1);
-    // softmax backward
-    double dz[5], sg = 0.0;
-#pragma unroll
-    for (int b = 0; b < 5; ++b) sg = __builtin_fma(pr[b], gp[b], sg);
-#pragma unroll
-    for (int b = 0; b < 5; ++b) dz[b] = pr[b] * (gp[b] - sg);
-    // layer 2 / layer-1 norm backward; the 117 small gradient columns leave through four 32-column rounds:
+    double dz[5];
+    cnn_softmax_back(pr, gp, dz);
+    // layer 2 / layer-1 norm backward (t1 <- dT1); the 117 small gradient columns leave through four 32-column rounds:
     //   round 0: d weights2[j][b], j < 6 (30 columns) ; round 1: j in [6,12) ; round 2: j in [12,16) + d intercept2 (25)
     //   round 3: d scale1 (16) + d intercept1 (16)
     double dy1[CNN_L1];
@@ -753,10 +880,7 @@ __global__ __launch_bounds__(CNN_THREADS) void cnn_backward_kernel(const unsigne
       CNN_STAMP(5)
     }
   }
-#ifdef CNN_STAMPS
-  if (lane == 0)
-    for (int k = 0; k < 8; ++k) atomicAdd(&cnn_stamp_sums[k], tph[k]);
-#endif
+  CNN_STAMP_END
   __syncthreads();
   for (int k = threadIdx.x; k < D.total; k += blockDim.x) partials[(size_t)blockIdx.x * D.total + k] = G[k];
 }
@@ -797,21 +921,11 @@ struct cnnq {
 static inline size_t cnnq_fixed_doubles(const cnn_dims &D) {
   return (size_t)BEAR_EXPTAB_N + (size_t)D.fw * 6 * CNN_NF + 2 * CNN_L1 + CNN_L1 * 5 + 2 * (size_t)D.P * CNN_NF + (size_t)((D.total + 1) & ~1);
 }
-
-// v summed over the Q lanes of a context (lanes ctx, ctx + TILE, ...): every one of them gets the sum
-template <int Q>
-__device__ __forceinline__ double cnnq_psum(double v) {
-#pragma unroll
-  for (int step = 0; step < (Q == 2 ? 1 : 2); ++step) {
-    const long long q = __double_as_longlong(v);
-    const uint32_t lo = (uint32_t)q, hi = (uint32_t)(q >> 32);
-    const bool s32 = Q == 2 || step == 1;
-    const auto a = s32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false) : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto c = s32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false) : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    v = __longlong_as_double(((long long)c[0] << 32) | a[0]) + __longlong_as_double(((long long)c[1] << 32) | a[1]);
-  }
-  return v;
+// LDS of cnn_backward_parts_kernel<2> with `waves` waves per block
+static inline size_t cnnq_lds_bytes(const cnn_dims &D, int waves) {
+  return sizeof(double) * (cnnq_fixed_doubles(D) + (size_t)waves * cnnq<2>::WAVE_DOUBLES);
 }
+
 // staged columns [column][context] (stride CS): lane (c = lane & 31, hh) returns the sum of column c over its half of the contexts
 template <int Q>
 __device__ __forceinline__ double cnnq_colsum(const double *E, uint32_t lane) {
@@ -830,36 +944,6 @@ __device__ __forceinline__ double cnnq_colsum(const double *E, uint32_t lane) {
 //   d weights1[p] = e0 (x) S,   d e0 = W1[p] S,   d scale0 / d intercept0 / d conv from d e0 as for one context,
 //   d filters[w][letter_w] += d conv for the window's letters
 // -- the position costs one context's worth of work (lane = filter) instead of the tile's.  Sx: [0, 16) S, [16, 48) scratch.
-template <int CTRL>
-__device__ __forceinline__ double cnn_dpp(double v) {
-  const long long q = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)q, CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(q >> 32), CTRL, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (uint32_t)lo);
-}
-// the same lane of the four rows of 16 summed (every lane gets the sum): v_permlane16_swap / v_permlane32_swap
-__device__ __forceinline__ double cnn_rows_sum(double v) {
-#pragma unroll
-  for (int step = 0; step < 2; ++step) {
-    const long long q = __double_as_longlong(v);
-    const uint32_t lo = (uint32_t)q, hi = (uint32_t)(q >> 32);
-    const auto a = step == 0 ? __builtin_amdgcn_permlane16_swap(lo, lo, false, false) : __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto c = step == 0 ? __builtin_amdgcn_permlane16_swap(hi, hi, false, false) : __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    v = __longlong_as_double(((long long)c[0] << 32) | a[0]) + __longlong_as_double(((long long)c[1] << 32) | a[1]);
-  }
-  return v;
-}
-__device__ __forceinline__ double cnn_half_sum_all(double v) {   // every lane gets the sum over its half of the wave (32 lanes)
-  v += cnn_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += cnn_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += cnn_dpp<0x124>(v);   // row_ror:4
-  v += cnn_dpp<0x128>(v);   // row_ror:8
-  const long long q = __double_as_longlong(v);
-  const uint32_t lo = (uint32_t)q, hi = (uint32_t)(q >> 32);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto c = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return __longlong_as_double(((long long)c[0] << 32) | a[0]) + __longlong_as_double(((long long)c[1] << 32) | a[1]);
-}
 // TWO (position, window) items per call, one per half of the wave (lane & 31 = filter): the work is a chain of dependent steps
 // (conv, two-pass norm, elu, norm backward), so a second item costs nothing.  Sx: per item 48 doubles, [0, 16) S, [16, 48) scratch.
 __device__ __forceinline__ void cnn_backward_shared_window(const double *Fs, const double *exptab, double *Sx, const double *Ps0,
@@ -953,40 +1037,29 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
   double *T = E + C::E_DOUBLES;                                     // [16][ES] dT1
   unsigned long long *Cw = reinterpret_cast<unsigned long long *>(T + C::T_DOUBLES);   // [TILE] packed contexts
   double *Cy = T + C::T_DOUBLES + TILE;                                                // carried column sums and windows
-  for (int k = threadIdx.x; k < BEAR_EXPTAB_N; k += blockDim.x) exptab[k] = exp2((double)k * (1.0 / BEAR_EXPTAB_N));   // (a block may be one wave)
-  for (int k = threadIdx.x; k < D.fw * 6 * CNN_NF; k += blockDim.x) {
-    const int w = k / (6 * CNN_NF), r = k - w * 6 * CNN_NF, a = r / CNN_NF, f = r - a * CNN_NF;
-    Fs[k] = a < 5 ? params[D.oF + (w * 5 + a) * CNN_NF + f] : 0.0;
-  }
-  for (int k = threadIdx.x; k < CNN_L1; k += blockDim.x) {
-    Ps1[k] = params[D.os1 + k];
-    Pb1[k] = params[D.ob1 + k];
-  }
-  for (int k = threadIdx.x; k < CNN_L1 * 5; k += blockDim.x) PW2[k] = params[D.oW2 + k];
+  cnn_stage_exptab(exptab, blockDim.x);
+  cnn_stage_filters(Fs, params, D, blockDim.x);
+  cnn_stage_head_params(Ps1, Pb1, PW2, params, D, blockDim.x);
   for (int k = threadIdx.x; k < D.P * CNN_NF; k += blockDim.x) {
     Ps0[k] = params[D.os0 + k];
     Pb0[k] = params[D.ob0 + k];
   }
   for (int k = threadIdx.x; k < D.total; k += blockDim.x) G[k] = 0.0;
   __syncthreads();
-#ifdef CNN_STAMPS
-  unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_amdgcn_s_memtime();
-#endif
+  CNN_STAMP_BEGIN
   // A wave walks groups of contexts, TILE at a time: without lists, group g = rows [TILE g, TILE g + TILE); with the plan's
   // lists (the training step) group g = plan tile g and only its contexts that hold counts (the others' gradient rows are zero)
   // A wave takes a CONTIGUOUS range of groups: in a k-mer-sorted table consecutive tiles share the windows of their leading
   // positions, and a fully shared window of position 0 or 1 that the next tile shares too is not worked off per tile -- its
   // column sums are carried in Cy (the wave's own LDS words: plain read-add-write) until the window changes.
-  const uint64_t wave_id = (uint64_t)blockIdx.x * n_waves + wave, wave_cnt = (uint64_t)gridDim.x * n_waves;
+  const cnn_range groups = cnn_wave_groups(n_groups, wave, n_waves);
   uint32_t carry = 0;                         // bit p: position p has a carried window
   // (position, window) items queue up in the wave's staging area E (free between position loops): slot k = E[48 k ..): S [16],
   // e0 scratch [30], and the window / the position as raw words at [46], [47]; drain_items works them off in pairs
   uint32_t n_items = 0;
   constexpr uint32_t MAX_ITEMS = 20;          // 48 * 20 <= the 1080 doubles of E
   auto word = [&](const double *q) {          // a word every lane reads from the same LDS address, as a scalar
-    const long long v = __double_as_longlong(*q);
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    return cnn_read_first((unsigned long long)__double_as_longlong(*q));
   };
   auto push_item = [&](int p, unsigned long long w, double val, uint32_t ln) {   // S[ln] = val from lanes 0..15
     double *slot = E + 48u * n_items;
@@ -1011,16 +1084,10 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
     push_item(q, word(Cy + C::CARRY_POS * CNN_L1 + q), ln < CNN_L1 ? Cy[q * CNN_L1 + (int)ln] : 0.0, ln);
     carry &= ~(1u << q);
   };
-  for (uint64_t g = n_groups * wave_id / wave_cnt; g < n_groups * (wave_id + 1) / wave_cnt; ++g) {
-    const uint16_t *lst = live_lists ? live_lists + g * PLN_LIVE_STRIDE : nullptr;
-    const uint64_t base = lst ? tiles[g].row0 : g * TILE;
-    const uint32_t cnt = lst ? (uint32_t)lst[0] : (uint32_t)(n_rows - base < (uint64_t)TILE ? n_rows - base : (uint64_t)TILE);
-   uint32_t row_next;                          // the list entry of a tile is read one tile ahead: its rows' loads then start at once
-   {
-     const uint32_t c = lane & (TILE - 1);
-     row_next = lst ? (uint32_t)lst[1 + (c < cnt ? c : 0u)] : c;
-   }
-   for (uint32_t c0 = 0; c0 < cnt; c0 += TILE) {
+  for (uint64_t g = groups.lo; g < groups.hi; ++g) {
+   cnn_group_walk<TILE> walk;
+   walk.template open<false>(tiles, live_lists, g, n_rows, lane & (TILE - 1));
+   for (uint32_t c0 = 0; c0 < walk.cnt; c0 += TILE) {
     // the lane's coordinates are derived HERE, from a laundered copy of the lane number: hoisted out of the group loop, the
     // addresses built on them took (and spilled) two dozen registers
     uint32_t lane_t = lane;
@@ -1028,13 +1095,10 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
     const uint32_t ctx = lane_t & (TILE - 1);
     const uint32_t h = lane_t / TILE;               // the lane's part: filters [FH h, FH h + FH), layer-1 units [JH h, JH h + JH)
     const uint32_t lq = lane_t >> 4, lr = lane_t & 15u;   // MFMA lane coordinates: k / row-group index, row / column index
-    const bool live = c0 + ctx < cnt;
-    const uint64_t i = base + (uint64_t)row_next;
-    if (lst && c0 + TILE < cnt) row_next = (uint32_t)lst[1 + (c0 + TILE + ctx < cnt ? c0 + TILE + ctx : 0u)];
+    const bool live = c0 + ctx < walk.cnt;
+    const uint64_t i = walk.row(c0, ctx);
     // dead lanes: every letter "other" and a zero gradient row -> all their contributions are exact zeros
-    unsigned long long code = 0;
-#pragma unroll
-    for (int l = 0; l < 21; ++l) code |= 5ull << (3 * l);
+    unsigned long long code = cnn_all_other_code();
     if (live) code = codes[i];
     if (h == 0) Cw[ctx] = code;
     double t1[JH], n1[JH], e1[JH], d1[JH], dy1[JH];
@@ -1051,35 +1115,9 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
         // the forward pass kept no layer-1 sums: every position of these contexts came from a parent row and window rows
         // (cnn_level_io), and the sums are put together again exactly as the forward kernel did -- two or three gathers that
         // mostly hit the caches instead of a 128-byte row written and read back per context
-        if (io.t1_parent) {
-          const double2 *src = reinterpret_cast<const double2 *>(io.t1_parent + (size_t)io.parent[i] * CNN_L1 + h * JH);
-#pragma unroll
-          for (int j = 0; j < JH / 2; ++j) {
-            const double2 v = src[j];
-            t1[2 * j] = v.x;
-            t1[2 * j + 1] = v.y;
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < CNN_MAX_WIN; ++q) {
-          if (q < io.n_win) {
-            const double2 *src = reinterpret_cast<const double2 *>(io.win_rows[q] + (size_t)io.win_row_of[q][i] * CNN_L1 + h * JH);
-#pragma unroll
-            for (int j = 0; j < JH / 2; ++j) {
-              const double2 v = src[j];
-              t1[2 * j] += v.x;
-              t1[2 * j + 1] += v.y;
-            }
-          }
-        }
+        cnn_gather_t1<JH>(t1, io, i, h * JH);
       } else {
-      const double2 *src = reinterpret_cast<const double2 *>((io.head ? t1_save : io.dT1) + i * CNN_L1 + h * JH);
-#pragma unroll
-      for (int j = 0; j < JH / 2; ++j) {
-        const double2 v = src[j];
-        t1[2 * j] = v.x;
-        t1[2 * j + 1] = v.y;
-      }
+        cnn_load_row<JH>(t1, (io.head ? t1_save : io.dT1) + i * CNN_L1 + h * JH);
       }
       if (io.head) {
 #pragma unroll
@@ -1091,50 +1129,15 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
     }
     if (io.head) {      // (a level of prefixes: t1 holds the rows' dT1 already -- the sums of their children's)
     // layer 1 (as cnn_layer1, the 16 units over the Q parts)
-    double r1;
-    {
-      double mu = 0.0;
+    const double r1 = cnnq_layer1_norm<Q>(t1, n1);
 #pragma unroll
-      for (int j = 0; j < JH; ++j) mu += t1[j];
-      mu = cnnq_psum<Q>(mu) * (1.0 / CNN_L1);
-      double var = 0.0;
-#pragma unroll
-      for (int j = 0; j < JH; ++j) {
-        n1[j] = t1[j] - mu;
-        var = __builtin_fma(n1[j], n1[j], var);
-      }
-      r1 = cnn_rsqrt(cnnq_psum<Q>(var) * (1.0 / CNN_L1) + CNN_LN_EPS);
-#pragma unroll
-      for (int j = 0; j < JH; ++j) {
-        n1[j] *= r1;
-        e1[j] = cnn_elu(__builtin_fma(Ps1[h * JH + j], n1[j], Pb1[h * JH + j]), exptab, d1[j]);
-      }
+    for (int j = 0; j < JH; ++j) {
+      n1[j] *= r1;
+      e1[j] = cnn_elu(__builtin_fma(Ps1[h * JH + j], n1[j], Pb1[h * JH + j]), exptab, d1[j]);
     }
-    // softmax backward
-    double dz[5], sg = 0.0;
-#pragma unroll
-    for (int b = 0; b < 5; ++b) sg = __builtin_fma(pr[b], gp[b], sg);
-#pragma unroll
-    for (int b = 0; b < 5; ++b) dz[b] = pr[b] * (gp[b] - sg);
-    // layer 2 / layer-1 norm backward
-    {
-      double ma = 0.0, mb = 0.0;
-#pragma unroll
-      for (int j = 0; j < JH; ++j) {
-        double de = 0.0;
-#pragma unroll
-        for (int b = 0; b < 5; ++b) de = __builtin_fma(PW2[(h * JH + j) * 5 + b], dz[b], de);
-        dy1[j] = de * d1[j];
-        const double dn = dy1[j] * Ps1[h * JH + j];
-        t1[j] = dn;
-        ma += dn;
-        mb = __builtin_fma(dn, n1[j], mb);
-      }
-      ma = cnnq_psum<Q>(ma) * (1.0 / CNN_L1);
-      mb = cnnq_psum<Q>(mb) * (1.0 / CNN_L1);
-#pragma unroll
-      for (int j = 0; j < JH; ++j) t1[j] = r1 * (t1[j] - ma - n1[j] * mb);     // dT1
-    }
+    double dz[5];
+    cnn_softmax_back(pr, gp, dz);
+    cnnq_layer2_back<Q>(dz, PW2 + h * JH * 5, Ps1 + h * JH, n1, r1, [&](int j) { return d1[j]; }, dy1, t1);     // t1 <- dT1
     // d weights2[j][b] = the sum over the tile's contexts of e1[ctx][j] dz[ctx][b]: ONE 16 x 16 accumulation on the matrix core over
     // K = contexts (rows = units, columns = letters: 5 of 16 used) -- e1 and dz staged once (13 LDS writes, 16 reads per lane)
     // instead of three rounds of 32 staged product columns and their column sums (96 LDS operations per lane and tile)
@@ -1182,11 +1185,7 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
       const uint32_t c = lane & 31u;
       cnn_lds_add(G + (c < 16u ? D.os1 + (int)c : D.ob1 + (int)c - 16), cs);
     }
-    if (io.dT1 && live) {     // the contexts' dT1 rows: what the next level's rows are the sums of
-      double2 *o = reinterpret_cast<double2 *>(io.dT1 + i * CNN_L1 + h * JH);
-#pragma unroll
-      for (int j = 0; j < JH / 2; ++j) o[j] = make_double2(t1[2 * j], t1[2 * j + 1]);
-    }
+    if (io.dT1 && live) cnn_store_row<JH>(io.dT1 + i * CNN_L1 + h * JH, t1);     // the contexts' dT1 rows: what the next level's rows are the sums of
     }
     if (io.p_lo >= io.p_hi) continue;      // rows whose positions all come from window tables / the parent level: nothing else to do here
 #pragma unroll
@@ -1205,28 +1204,21 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
       const unsigned long long wm = (D.fw < 21 ? (1ull << (3 * D.fw)) : 0ull) - 1ull;
       const unsigned long long live_mask = __builtin_amdgcn_ballot_w64(live);
       {   // leading letters that all the tile's contexts share (taps inside them need no one-hot product below)
-        first = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(code >> 32)) << 32) |
-                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)code);   // lane 0: the tile's first context (always live)
+        first = cnn_read_first(code);   // lane 0: the tile's first context (always live)
         const unsigned long long diff = live ? code ^ first : 0ull;
         while (n_common < D.lag && __builtin_amdgcn_ballot_w64(((diff >> (3 * n_common)) & 7ull) != 0ull) == 0ull) ++n_common;
       }
-      auto next_run = [&](unsigned long long wid, unsigned long long rem, unsigned long long *w) {   // the contexts that share the window of rem's first
-        const int leader = __builtin_ctzll(rem);
-        *w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(wid >> 32), leader) << 32) |
-             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wid, leader);
-        return __builtin_amdgcn_ballot_w64(wid == *w) & rem;
-      };
       bool have_full = false;
       double s_full = 0.0;
       for (int p = io.p_lo; p < io.p_hi; ++p) {
         const unsigned long long wid = (code >> (3 * p)) & wm;
         unsigned long long rem = live_mask, w;
-        for (int runs = 0; rem != 0ull && runs < CNN_SHARED_RUNS; ++runs) rem &= ~next_run(wid, rem, &w);
+        for (int runs = 0; rem != 0ull && runs < CNN_SHARED_RUNS; ++runs) rem &= ~cnn_next_run(wid, rem, &w);
         if (rem != 0ull) break;               // more distinct windows than pay: the position loop below takes this position and the
                                               // later ones (in a sorted batch their windows reach further into the varying letters)
         shared |= 1u << p;
         for (rem = live_mask; rem != 0ull;) {
-          const unsigned long long m = next_run(wid, rem, &w);
+          const unsigned long long m = cnn_next_run(wid, rem, &w);
           rem &= ~m;
           // S = the run's column sums of dT1 (lane: unit ln & 15, contexts 8 (ln >> 4) .. + 7); a run of all the tile's contexts
           // (a fully shared window: most of them) reuses the tile's sums
@@ -1518,10 +1510,7 @@ __global__ __launch_bounds__(cnnq<Q>::WAVES * 64) void cnn_backward_parts_kernel
     if (n_items) drain_items(ln);
   }
 #endif
-#ifdef CNN_STAMPS
-  if (lane == 0)
-    for (int k = 0; k < 8; ++k) atomicAdd(&cnn_stamp_sums[k], tph[k]);
-#endif
+  CNN_STAMP_END
   __syncthreads();
   for (int k = threadIdx.x; k < D.total; k += blockDim.x) {
     double *dst = partials + (size_t)blockIdx.x * D.total + k;
@@ -1554,12 +1543,8 @@ __global__ __launch_bounds__(CNH_WAVES * 64) void cnn_backward_head_kernel(uint6
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   double *E = PW2 + CNN_L1 * 5 + wave * CNH_WAVE_DOUBLES;                 // [16 + 5][ES]: e1 rows, dz rows
   double *GW = PW2 + CNN_L1 * 5 + n_waves * CNH_WAVE_DOUBLES + wave * CNH_NG;   // this wave's sums
-  for (int k = threadIdx.x; k < BEAR_EXPTAB_N; k += blockDim.x) exptab[k] = exp2((double)k * (1.0 / BEAR_EXPTAB_N));
-  for (int k = threadIdx.x; k < CNN_L1; k += blockDim.x) {
-    Ps1[k] = params[D.os1 + k];
-    Pb1[k] = params[D.ob1 + k];
-  }
-  for (int k = threadIdx.x; k < CNN_L1 * 5; k += blockDim.x) PW2[k] = params[D.oW2 + k];
+  cnn_stage_exptab(exptab, blockDim.x);
+  cnn_stage_head_params(Ps1, Pb1, PW2, params, D, blockDim.x);
   __syncthreads();
   const uint32_t ctx = lane & (TILE - 1), h = lane / TILE, lq = lane >> 4, lr = lane & 15u;
   cnn_d4 acc_w2 = {0.0, 0.0, 0.0, 0.0};
@@ -1569,8 +1554,8 @@ __global__ __launch_bounds__(CNH_WAVES * 64) void cnn_backward_head_kernel(uint6
 #pragma unroll
   for (int b = 0; b < 5; ++b) acc_b2[b] = 0.0;
   const uint64_t n_tiles = (n_rows + TILE - 1) / TILE;
-  const uint64_t wave_id = (uint64_t)blockIdx.x * n_waves + wave, wave_cnt = (uint64_t)gridDim.x * n_waves;
-  for (uint64_t g = n_tiles * wave_id / wave_cnt; g < n_tiles * (wave_id + 1) / wave_cnt; ++g) {
+  const cnn_range tiles = cnn_wave_groups(n_tiles, wave, n_waves);
+  for (uint64_t g = tiles.lo; g < tiles.hi; ++g) {
     const uint64_t i = g * TILE + ctx;
     const bool live = i < n_rows;
     double t1[JH], n1[JH], e1[JH], dy1[JH];
@@ -1583,85 +1568,28 @@ __global__ __launch_bounds__(CNH_WAVES * 64) void cnn_backward_head_kernel(uint6
       gp[b] = 0.0;
     }
     if (live) {
-      if (!t1_save) {      // the layer-1 sums put together again from the rows the forward pass took them from (cnn_level_io)
-        if (io.t1_parent) {
-          const double2 *src = reinterpret_cast<const double2 *>(io.t1_parent + (size_t)io.parent[i] * CNN_L1 + h * JH);
-#pragma unroll
-          for (int j = 0; j < JH / 2; ++j) {
-            const double2 v = src[j];
-            t1[2 * j] = v.x;
-            t1[2 * j + 1] = v.y;
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < CNN_MAX_WIN; ++q) {
-          if (q < io.n_win) {
-            const double2 *src = reinterpret_cast<const double2 *>(io.win_rows[q] + (size_t)io.win_row_of[q][i] * CNN_L1 + h * JH);
-#pragma unroll
-            for (int j = 0; j < JH / 2; ++j) {
-              const double2 v = src[j];
-              t1[2 * j] += v.x;
-              t1[2 * j + 1] += v.y;
-            }
-          }
-        }
-      } else {
-        const double2 *src = reinterpret_cast<const double2 *>(t1_save + i * CNN_L1 + h * JH);
-#pragma unroll
-        for (int j = 0; j < JH / 2; ++j) {
-          const double2 v = src[j];
-          t1[2 * j] = v.x;
-          t1[2 * j + 1] = v.y;
-        }
-      }
+      if (!t1_save) cnn_gather_t1<JH>(t1, io, i, h * JH);      // the layer-1 sums put together again from the rows the forward pass took them from
+      else cnn_load_row<JH>(t1, t1_save + i * CNN_L1 + h * JH);
 #pragma unroll
       for (int b = 0; b < 5; ++b) {
         pr[b] = prior[i * 5 + b];
         gp[b] = grad_prior[i * 5 + b];
       }
     }
-    // layer 1 forward again (norm over the 16 units of the two halves, elu), as the part kernel
-    double r1;
-    {
-      double mu = 0.0;
+    // layer 1 forward again (norm over the 16 units of the two halves; the elu inside the backward loop), as the part kernel
+    const double r1 = cnnq_layer1_norm<2>(t1, n1);
+    double dz[5];
+    cnn_softmax_back(pr, gp, dz);
+    cnnq_layer2_back<2>(dz, PW2 + h * JH * 5, Ps1 + h * JH, n1, r1, [&](int j) {
+      n1[j] *= r1;
+      double d1;
+      e1[j] = cnn_elu(__builtin_fma(Ps1[h * JH + j], n1[j], Pb1[h * JH + j]), exptab, d1);
+      return d1;
+    }, dy1, t1);     // t1 <- dT1
 #pragma unroll
-      for (int j = 0; j < JH; ++j) mu += t1[j];
-      mu = cnnq_psum<2>(mu) * (1.0 / CNN_L1);
-      double var = 0.0;
-#pragma unroll
-      for (int j = 0; j < JH; ++j) {
-        n1[j] = t1[j] - mu;
-        var = __builtin_fma(n1[j], n1[j], var);
-      }
-      r1 = cnn_rsqrt(cnnq_psum<2>(var) * (1.0 / CNN_L1) + CNN_LN_EPS);
-    }
-    double dz[5], sg = 0.0;
-#pragma unroll
-    for (int b = 0; b < 5; ++b) sg = __builtin_fma(pr[b], gp[b], sg);
-#pragma unroll
-    for (int b = 0; b < 5; ++b) dz[b] = pr[b] * (gp[b] - sg);
-    {
-      double ma = 0.0, mb = 0.0;
-#pragma unroll
-      for (int j = 0; j < JH; ++j) {
-        n1[j] *= r1;
-        double d1;
-        e1[j] = cnn_elu(__builtin_fma(Ps1[h * JH + j], n1[j], Pb1[h * JH + j]), exptab, d1);
-        double de = 0.0;
-#pragma unroll
-        for (int b = 0; b < 5; ++b) de = __builtin_fma(PW2[(h * JH + j) * 5 + b], dz[b], de);
-        dy1[j] = de * d1;
-        const double dn = dy1[j] * Ps1[h * JH + j];
-        t1[j] = dn;
-        ma += dn;
-        mb = __builtin_fma(dn, n1[j], mb);
-        acc_s1[j] = __builtin_fma(dy1[j], n1[j], acc_s1[j]);       // d scale1, d intercept1: per lane, summed over lanes at the end
-        acc_b1[j] += dy1[j];
-      }
-      ma = cnnq_psum<2>(ma) * (1.0 / CNN_L1);
-      mb = cnnq_psum<2>(mb) * (1.0 / CNN_L1);
-#pragma unroll
-      for (int j = 0; j < JH; ++j) t1[j] = r1 * (t1[j] - ma - n1[j] * mb);     // dT1
+    for (int j = 0; j < JH; ++j) {
+      acc_s1[j] = __builtin_fma(dy1[j], n1[j], acc_s1[j]);       // d scale1, d intercept1: per lane, summed over lanes at the end
+      acc_b1[j] += dy1[j];
     }
 #pragma unroll
     for (int b = 0; b < 5; ++b) acc_b2[b] += dz[b];                 // (both halves hold the context's dz: half 0 is counted at the end)
@@ -1681,11 +1609,7 @@ __global__ __launch_bounds__(CNH_WAVES * 64) void cnn_backward_head_kernel(uint6
         acc_w2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc_w2, 0, 0, 0);
       }
     }
-    if (io.dT1 && live) {
-      double2 *o = reinterpret_cast<double2 *>(io.dT1 + i * CNN_L1 + h * JH);
-#pragma unroll
-      for (int j = 0; j < JH / 2; ++j) o[j] = make_double2(t1[2 * j], t1[2 * j + 1]);
-    }
+    if (io.dT1 && live) cnn_store_row<JH>(io.dT1 + i * CNN_L1 + h * JH, t1);
   }
   // this wave's sums into its LDS slot: sums over the 32 contexts of a half in a fixed butterfly, every entry written by one lane
   if (lr < 5u) {
@@ -1730,69 +1654,32 @@ __global__ __launch_bounds__(1024) void cnn_forward_head_kernel(uint64_t n_rows,
                                                                 double *__restrict__ prior, double *__restrict__ t1_save, const cnn_level_io io) {
   constexpr int TILE = 32, JH = CNN_L1 / 2;
   __shared__ double exptab[BEAR_EXPTAB_N], Ps1[CNN_L1], Pb1[CNN_L1], PW2[CNN_L1 * 5], Pb2[5];
-  for (int k = threadIdx.x; k < BEAR_EXPTAB_N; k += blockDim.x) exptab[k] = exp2((double)k * (1.0 / BEAR_EXPTAB_N));
-  for (int k = threadIdx.x; k < CNN_L1; k += blockDim.x) {
-    Ps1[k] = params[D.os1 + k];
-    Pb1[k] = params[D.ob1 + k];
-  }
-  for (int k = threadIdx.x; k < CNN_L1 * 5; k += blockDim.x) PW2[k] = params[D.oW2 + k];
+  cnn_stage_exptab(exptab, blockDim.x);
+  cnn_stage_head_params(Ps1, Pb1, PW2, params, D, blockDim.x);
   if (threadIdx.x < 5) Pb2[threadIdx.x] = params[D.ob2 + threadIdx.x];
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u, n_waves = blockDim.x >> 6;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t ctx = lane & (TILE - 1), h = lane / TILE;
   const uint64_t n_tiles = (n_rows + TILE - 1) / TILE;
-  const uint64_t wave_id = (uint64_t)blockIdx.x * n_waves + wave, wave_cnt = (uint64_t)gridDim.x * n_waves;
-  for (uint64_t g = n_tiles * wave_id / wave_cnt; g < n_tiles * (wave_id + 1) / wave_cnt; ++g) {
+  const cnn_range tiles = cnn_wave_groups(n_tiles, wave, n_waves);
+  for (uint64_t g = tiles.lo; g < tiles.hi; ++g) {
     const uint64_t i = g * TILE + ctx;
     const bool live = i < n_rows;
     double t1[JH];
 #pragma unroll
     for (int j = 0; j < JH; ++j) t1[j] = 0.0;
     if (live) {
-      if (io.t1_parent) {
-        const double2 *src = reinterpret_cast<const double2 *>(io.t1_parent + (size_t)io.parent[i] * CNN_L1 + h * JH);
-#pragma unroll
-        for (int j = 0; j < JH / 2; ++j) {
-          const double2 v = src[j];
-          t1[2 * j] = v.x;
-          t1[2 * j + 1] = v.y;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < CNN_MAX_WIN; ++q) {
-        if (q < io.n_win) {
-          const double2 *src = reinterpret_cast<const double2 *>(io.win_rows[q] + (size_t)io.win_row_of[q][i] * CNN_L1 + h * JH);
-#pragma unroll
-          for (int j = 0; j < JH / 2; ++j) {
-            const double2 v = src[j];
-            t1[2 * j] += v.x;
-            t1[2 * j + 1] += v.y;
-          }
-        }
-      }
-      if (t1_save) {
-        double2 *o = reinterpret_cast<double2 *>(t1_save + i * CNN_L1 + h * JH);
-#pragma unroll
-        for (int j = 0; j < JH / 2; ++j) o[j] = make_double2(t1[2 * j], t1[2 * j + 1]);
-      }
+      cnn_gather_t1<JH>(t1, io, i, h * JH);
+      if (t1_save) cnn_store_row<JH>(t1_save + i * CNN_L1 + h * JH, t1);
     }
-    double mu = 0.0;
-#pragma unroll
-    for (int j = 0; j < JH; ++j) mu += t1[j];
-    mu = cnnq_psum<2>(mu) * (1.0 / CNN_L1);
-    double var = 0.0;
-#pragma unroll
-    for (int j = 0; j < JH; ++j) {
-      t1[j] -= mu;
-      var = __builtin_fma(t1[j], t1[j], var);
-    }
-    const double r1 = cnn_rsqrt(cnnq_psum<2>(var) * (1.0 / CNN_L1) + CNN_LN_EPS);
+    double c1[JH];
+    const double r1 = cnnq_layer1_norm<2>(t1, c1);
     double z[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll 2
     for (int j = 0; j < JH; ++j) {      // (two units at a time: all eight exponentials in flight took 190 registers)
       double dv;
-      const double e = cnn_elu(__builtin_fma(Ps1[h * JH + j], t1[j] * r1, Pb1[h * JH + j]), exptab, dv);
+      const double e = cnn_elu(__builtin_fma(Ps1[h * JH + j], c1[j] * r1, Pb1[h * JH + j]), exptab, dv);
 #pragma unroll
       for (int b = 0; b < 5; ++b) z[b] = __builtin_fma(e, PW2[(h * JH + j) * 5 + b], z[b]);
     }

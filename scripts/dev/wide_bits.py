@@ -1,4 +1,5 @@
-"""Developer: the bits of every width-taking entry on seeded inputs, for holding one build of the library against another.
+"""Developer: the bits of every width-taking entry and of the width-5 convolutional entries on seeded inputs, for holding one build of
+the library against another.
     BEAR_AMD_LIB=before/libbear_hip.so python scripts/dev/wide_bits.py > before.json
     BEAR_AMD_LIB=bear_amd/libbear_hip.so python scripts/dev/wide_bits.py > after.json        # then: cmp before.json after.json
 One SHA-256 per output buffer, as one JSON object (case -> digest).  These kernels use no floating-point atomics and the library is
@@ -7,7 +8,14 @@ difference in the arithmetic or in its order.  Each build runs in a process of i
 
 Shapes: the smallest at which the routines the width-21 kernels share can go wrong -- the code bytes of a tile not a whole number
 of dwords, a ragged last tile and a second tile per block, rows of 3 tiles + 77 at either width, and per kernel one table with more
-tiles than its capped grid has blocks (cap * tile + tile + 3 rows)."""
+tiles than its capped grid has blocks (cap * tile + tile + 3 rows).
+
+The width-5 convolutional head (kernels_cnn.h; packed contexts, start symbols and unknown letters mixed in; one table in random and
+one in k-mer order with duplicate contexts per shape, so that shared and carried windows occur): the forward kernels, the row sums
+and the dT1 rows use no atomics and are hashed in either build.  The part kernel and the 64-context kernel add to their block's
+gradient image with LDS floating-point atomics from several waves: their parameter gradients are hashed in libbear_hip_det.so only
+(one wave per block); so is `packed` of the step over levels and tables, the head-only backward kernel's gradients included -- that
+kernel has no atomics itself, but the part-kernel launches of the same step add to the same partial rows."""
 import hashlib
 import json
 import os
@@ -29,6 +37,9 @@ EVAL_TILE, EVAL_PER_CU = 128, 8
 LINEAR_FWD_TILE, LINEAR_FWD_PER_CU = 512, 1
 CNN_FWD_TILE, CNN_FWD_PER_CU = 256, 2
 CNN_BWD_TILE, CNN_BWD_PER_CU = 64, 1
+# the width-5 convolutional kernels (kernels_cnn.h, bear_cnn.hip): waves per CU of each capped grid and contexts per wave tile
+CNN5_FWD_WAVES_PER_CU, CNN5_FWD_TILE = 16 * 4, 64
+CNN5_PARTS_WAVES_PER_CU, CNN5_HEAD_WAVES_PER_CU, CNN5_PARTS_TILE = 8, 12, 32
 
 
 def beyond(cus, per_cu, tile):
@@ -128,10 +139,99 @@ def cnn_kernels(cus):
         put("cnn_backward_wide/lag%d/fw%d/n%d" % (lag, fw, n), kernels.cnn_backward_wide(cd, params, lag, fw, t1, f, q - 0.3))
 
 
+def codes5(rng, n, lag, in_kmer_order):
+    """Packed contexts over ACGT with start symbols and unknown letters mixed in; in k-mer order with duplicates, or in random order."""
+    if in_kmer_order:
+        pool = rng.integers(0, 4, (max(1, (n + 2) // 3), lag)).astype(np.int8)
+        c = pool[rng.integers(0, pool.shape[0], n)]
+    else:
+        c = rng.integers(0, 4, (n, lag)).astype(np.int8)
+    c[rng.random(n) < 0.1, 0] = 4                        # '[' at a sequence start
+    c[rng.random((n, lag)) < 0.03] = -1                  # unknown letters
+    if in_kmer_order:
+        key = np.zeros(n, np.int64)
+        for l in range(lag):
+            key = key * 6 + np.where(c[:, l] >= 0, c[:, l], 5)
+        c = c[np.argsort(key, kind="stable")]
+    return kernels.pack_kmers(torch.from_numpy(np.ascontiguousarray(c)).cuda())
+
+
+def cnn5_pass(name, packed, lag, fw, rng, det, forms=("parts", "ctx64")):
+    n = packed.shape[0]
+    params = torch.from_numpy(rng.normal(size=kernels.cnn_param_count(lag, fw)) * 0.3).cuda()
+    f, t1 = kernels.cnn_forward(packed, params, lag, fw)
+    put("cnn_forward/" + name, f, t1)
+    if det:
+        g = rows(rng, n, 5) - 0.3
+        for form in forms:
+            if form == "ctx64":
+                os.environ["BEAR_CNN_BACKWARD"] = "1"
+            try:
+                put("cnn_backward/%s/%s" % (form, name), kernels.cnn_backward(packed, params, lag, fw, t1, f, g))
+            finally:
+                os.environ.pop("BEAR_CNN_BACKWARD", None)
+
+
+def cnn5_step(lag, fw, n, det):
+    """The training step over prefix levels and window tables (the tables of test_cnn_step_over_window_tables_equals_the_plain_kernels)."""
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(dev).manual_seed(lag * 131 + fw)
+    codes = torch.randint(0, 4, (n, lag), dtype=torch.int8, device=dev, generator=gen)
+    odd = torch.randperm(n, device=dev, generator=gen)[:max(2, n // 150)]
+    codes[odd[::2], 0] = 4
+    codes[odd[1::2], torch.randint(0, lag, (odd[1::2].numel(),), device=dev, generator=gen)] = -1
+    key = torch.zeros(n, dtype=torch.int64, device=dev)
+    for l in range(lag):
+        c = codes[:, l].to(torch.int64)
+        key = key * 6 + torch.where(c >= 0, c, torch.full_like(c, 5))
+    packed = kernels.pack_kmers(codes[torch.argsort(key, stable=True)].contiguous())
+    counts = kernels.synth_counts(11, 0, n, dev, want=("train",))["train"]
+    counts[:, 4] += (counts == 0).all(dim=1).to(counts.dtype)
+    flat = torch.from_numpy(np.random.default_rng(lag * 100 + fw).normal(size=kernels.cnn_param_count(lag, fw)) * 0.3).cuda()
+    theta = torch.cat([f64(0.2), flat]).contiguous()
+    plan = kernels.Plan(counts, 5)
+    bufs = kernels.cnn_step_buffers(n, lag, fw, dev, ws=plan.ws)
+    plan.attach_cnn_levels(packed, lag, fw)
+    (level_rows, letters), tables = plan.cnn_level_rows(with_letters=True), plan.cnn_window_rows()
+    own_hi = lag - fw + 1 - sum(1 for lev, _, _ in tables if lev == 0)
+    own_lo = letters[0] - fw + 1 if letters else 0
+    name = "lag%d/fw%d/n%d" % (lag, fw, n)
+    OUT["cnn_step/%s/shape" % name] = "levels %s tables %s head-only %s" % (level_rows, tables, own_lo >= own_hi)
+    for ar in (False, True):
+        pk = torch.zeros(2 + flat.numel(), dtype=torch.float64, device=dev)
+        kernels.net_cnn_train_reduce(plan, packed, lag, fw, theta, bufs, pk, train_ar=ar)
+        put("cnn_step/%s/ar%d/bufs" % (name, ar), *bufs)
+        if det:
+            put("cnn_step/%s/ar%d/packed" % (name, ar), pk)
+    put("cnn_forward_plan/" + name, *kernels.cnn_forward(packed, flat, lag, fw, plan=plan))
+
+
+def cnn5_kernels(cus, det):
+    for lag, fw, n in ((1, 1, 1), (2, 1, 3), (13, 8, 31), (13, 8, 33), (13, 8, 63), (13, 8, 65), (7, 7, 64),
+                       (21, 21, 130),                    # the window mask is 63 bits wide
+                       (21, 16, 200)):                   # only the 64-context form of the backward kernel fits
+        for order in ("random", "kmer"):
+            rng = np.random.default_rng(10000 * lag + 100 * fw + n + (order == "kmer"))
+            cnn5_pass("lag%d/fw%d/n%d/%s" % (lag, fw, n, order), codes5(rng, n, lag, order == "kmer"), lag, fw, rng, det)
+    # more groups than the grid has waves: every wave a range of two or more groups, the last one ragged
+    n_fwd = beyond(cus, CNN5_FWD_WAVES_PER_CU, CNN5_FWD_TILE)
+    rng = np.random.default_rng(n_fwd)
+    packed = codes5(rng, n_fwd, 13, True)
+    params = torch.from_numpy(rng.normal(size=kernels.cnn_param_count(13, 8)) * 0.3).cuda()
+    put("cnn_forward/beyond/n%d" % n_fwd, *kernels.cnn_forward(packed, params, 13, 8))
+    n_parts = beyond(cus, CNN5_PARTS_WAVES_PER_CU, CNN5_PARTS_TILE)
+    rng = np.random.default_rng(n_parts)
+    cnn5_pass("beyond/n%d" % n_parts, codes5(rng, n_parts, 13, True), 13, 8, rng, det, forms=("parts",))
+    for lag, fw, n in ((7, 3, 50_000), (8, 2, 100_000), (7, 3, beyond(cus, CNN5_HEAD_WAVES_PER_CU, CNN5_PARTS_TILE))):
+        cnn5_step(lag, fw, n, det)
+
+
 if __name__ == "__main__":
+    from bear_amd import _lib
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     row_kernels(cus)
     linear_kernels(cus)
     cnn_kernels(cus)
+    cnn5_kernels(cus, det=os.path.basename(_lib.LIB_PATH) == "libbear_hip_det.so")
     torch.cuda.synchronize()
     print(json.dumps(OUT, indent=0, sort_keys=True))
