@@ -4,7 +4,8 @@
 ``change_scope_params`` (:103-143) with the reference's signatures.  Per batch shard and step the
 AR rows come from the plugin (``ar_funcs``, PyTorch-ROCm ops with autograd), and the DM / multinomial
 log-likelihood, its gradient w.r.t. ``h_signed`` and w.r.t. the AR rows come from one launch of
-``bear_dm_prior_f64``; the row gradient is fed back through ``ar_func`` by ``Tensor.backward``.
+``bear_dm_prior_f64``; the row gradient is fed back through ``ar_func`` by ``Tensor.backward``.  The reference's linear and
+convolutional AR functions take fused steps instead, at either alphabet width (``step_form``).
 """
 import os
 
@@ -38,10 +39,26 @@ def linear_wide_step_selected(alphabet_size, lag, own_mat, width):
                 and not (unfused and unfused != "0"))
 
 
+def cnn_wide_step_selected(ar_func, ar_params, alphabet_size, lag, width):
+    """Whether ``train`` runs the protein alphabet's convolutional step as two launches per optimizer step
+    (``bear_net_cnn_train_step_wide_f64``, theta device-resident): the 20-letter alphabet on a 21-wide table, the fused AR function
+    of ``make_ar_func_cnn`` whose eight parameters ARE the kernels' (identity), and a shape the kernels take (``kernels.cnn_supported``:
+    30 filters, layer-1 width 16, 1 <= filter width <= lag <= 16).  Every shape timed is at least as fast as the three row kernels
+    under autograd (profiles/prot_cnn_step_time.jsonl).  BEAR_AMD_UNFUSED_CNN_WIDE=1 keeps those (tests and
+    scripts/prot_cnn_step_time.py compare)."""
+    unfused = os.environ.get("BEAR_AMD_UNFUSED_CNN_WIDE", "")
+    own = getattr(ar_func, "cnn_params", None)
+    return bool(alphabet_size == 20 and width == kernels.LINEAR_WIDE_WIDTH and getattr(ar_func, "fused", False)
+                and len(ar_params) == 8 and own is not None and len(own) == 8 and all(a is b for a, b in zip(own, ar_params))
+                and kernels.cnn_supported(lag, 20, getattr(ar_func, "cnn_filter_width", 0), kernels.CNN_NUM_FILTERS, kernels.CNN_LAYER1_WIDTH)
+                and not (unfused and unfused != "0"))
+
+
 def step_form(ar_func, ar_params, alphabet_size, lag, width):
     """How ``train`` runs an optimizer step with this AR function, and the ``ResidentBatches`` keyword arguments that go with it:
     ``"linear"`` / ``"cnn"`` (a 4-letter alphabet's fused heads: forward, ELBO and all gradients in one launch per batch),
-    ``"linear_wide"`` (the protein alphabet's linear step: ``linear_wide_step_selected``), or None (torch ops under autograd).
+    ``"linear_wide"`` / ``"cnn_wide"`` (the protein alphabet's steps: ``linear_wide_step_selected``, ``cnn_wide_step_selected``), or
+    None (torch ops under autograd).
     A fused form needs the AR function's parameters to BE the kernels' (identity, not equality)."""
     mat = getattr(ar_func, "linear_mat", None)
     # Fused heads: the sums of a step do not depend on the order of a batch's rows, so every batch is kept sorted by k-mer (first
@@ -57,6 +74,11 @@ def step_form(ar_func, ar_params, alphabet_size, lag, width):
     # ... and on the protein alphabet: the linear head on int8 codes in table order (no plan, no k-mer sort: kernels_linear_wide.h)
     if linear_wide_step_selected(alphabet_size, lag, mat is not None and len(ar_params) == 1 and mat is ar_params[0], width):
         return "linear_wide", dict(kmer_order=False, prebuild=[("train", _train.ROWS_IF_DENSE, None)], per_row_extra=0)
+    # ... the convolutional head likewise, in two launches (kernels_cnn_wide.h); per_row_extra: the dz and t1 rows of the step's one
+    # buffer pair, 8 * (21 + 16) B per context of the largest batch
+    if cnn_wide_step_selected(ar_func, ar_params, alphabet_size, lag, width):
+        return "cnn_wide", dict(kmer_order=False, prebuild=[("train", _train.ROWS_IF_DENSE, None)],
+                                per_row_extra=8 * (kernels.LINEAR_WIDE_WIDTH + kernels.CNN_LAYER1_WIDTH))
     return None, dict(kmer_order=False, prebuild=[("train", _train.ROWS_IF_DENSE, None)], per_row_extra=16 * (alphabet_size + 1))
 
 
@@ -132,6 +154,23 @@ def _linear_wide_step(res, theta, lag, train_ar):
     return make
 
 
+def _cnn_wide_step(res, theta, lag, fw, train_ar, device):
+    """``make(k)`` of the protein alphabet's convolutional form: count rows and codes as they are, 16-byte aligned, and ONE pair of
+    dz / t1 buffers sized for the largest batch (steps on one stream run one after the other)."""
+    bufs = kernels.cnn_step_buffers_wide(max([e["rows"] for e in res.batches] + [1]), device)
+
+    def make(k):
+        e = res.load(k)
+        if not e["rows"]:
+            return _train.zero_reduce
+        counts, codes = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (e["train"].contiguous(), e["codes"].contiguous()))
+        return _train.StepFns(
+            lambda packed: kernels.net_cnn_train_reduce_wide(counts, codes, lag, fw, theta, bufs, packed, train_ar=train_ar),
+            lambda packed, m, v, t, lr, scale, loss_buf: kernels.net_cnn_train_step_wide(counts, codes, lag, fw, theta, m, v, t, bufs, packed,
+                                                                                         lr, scale, loss_buf, train_ar=train_ar))
+    return make
+
+
 def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwargs,
           learning_rate, optimizer_name, train_ar, acc_steps=1,
           params_restart=None, writer=None, loss_save=None, dtype=torch.float64):
@@ -161,7 +200,8 @@ def train(data, num_kmers, epochs, ds_loc, alphabet, lag, make_ar_func, af_kwarg
         elif form == "cnn":
             make = _cnn_step(res, theta, lag, ar_func.cnn_filter_width, train_ar, device)
         else:
-            make = _linear_wide_step(res, theta, lag, train_ar)
+            make = (_linear_wide_step(res, theta, lag, train_ar) if form == "linear_wide"
+                    else _cnn_wide_step(res, theta, lag, ar_func.cnn_filter_width, train_ar, device))
             # the fused step pins no autograd intermediates in a graph's pool: no row cap of its own, but one that is set is honoured
             # (the tests force the eager loop of a protein run with BEAR_AMD_GRAPH_MAX_ROWS=0)
             cap = os.environ.get("BEAR_AMD_GRAPH_MAX_ROWS")

@@ -1,6 +1,6 @@
 // bear_cnn.hip -- the convolutional AR head (kernels_cnn.h): forward and backward passes, the prefix levels and window tables a
 // plan keeps for it (bear_levels.h), and its training step around the planned DM step of bear_hip.hip; the head as rows at the
-// protein alphabet's width (kernels_cnn_wide.h).  The other units: bear_host.h.
+// protein alphabet's width and bear_net's step with it there in two launches (kernels_cnn_wide.h).  The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_cnn.h"
 #include "kernels_cnn_wide.h"
@@ -14,8 +14,12 @@ int cnn_ws_setup(bear_ws *ws) {
   st = allow_dynamic_lds({BEAR_KFN(cnn_wide_forward_kernel)},
                          std::max(cnw_fwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG), cnw_fwd_lds(CNN_WIDE_MAX_LAG, 1)));
   if (st != BEAR_OK) return st;
-  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_backward_kernel)},
+  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_backward_kernel<false>), BEAR_KFN(cnn_wide_backward_kernel<true>)},
                          std::max(cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG), cnw_bwd_lds(CNN_WIDE_MAX_LAG, 1)));
+  if (st != BEAR_OK) return st;
+  // (the head kernel's block partials are two sums per block: ws->partials, as dm_wide_kernel's)
+  st = allow_dynamic_lds({BEAR_KFN(cnn_wide_head_dm_kernel<false>), BEAR_KFN(cnn_wide_head_dm_kernel<true>)},
+                         std::max(cnw_head_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG), cnw_head_lds(CNN_WIDE_MAX_LAG, 1)));
   if (st != BEAR_OK) return st;
   HIP_TRY(hipMalloc(&ws->cnnw_partials, sizeof(double) * CNW_MAX_TOTAL * WIDE_PARTIAL_ROWS(ws->num_cu, CNW_BWD_BLOCKS_PER_CU)));
   return BEAR_OK;
@@ -539,8 +543,77 @@ int bear_cnn_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows
   }
   if (!codes || !t1_save || !prior || !grad_prior) return BEAR_ERR_INVALID_ARG;
   if (misaligned(codes) || misaligned(t1_save) || misaligned(prior) || misaligned(grad_prior)) return BEAR_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(cnn_wide_backward_kernel, dim3(cnnwide_bwd_grid(ws, n_rows)), dim3(CNW_BWD_THREADS), cnw_bwd_lds(lag, filter_width), s, codes,
-                     n_rows, D, params, t1_save, prior, grad_prior, ws->cnnw_partials, ws_arrival(ws), grad_params);
+  hipLaunchKernelGGL(cnn_wide_backward_kernel<false>, dim3(cnnwide_bwd_grid(ws, n_rows)), dim3(CNW_BWD_THREADS), cnw_bwd_lds(lag, filter_width),
+                     s, codes, n_rows, D, params, t1_save, prior, grad_prior, ws->cnnw_partials, ws_arrival(ws), grad_params, NO_APPLY);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
+}
+
+// ---- bear_net's step with the convolutional AR function at the protein alphabet's width (kernels_cnn_wide.h): head + backward ----
+// the head kernel's grid is part of the two sums (block partials in ws->partials, summed in a fixed order per grid)
+static int cnnwide_head_grid(const bear_ws *ws, uint64_t n_rows) { return wide_grid(ws, n_rows, CNW_HEAD_TILE, CNW_HEAD_BLOCKS_PER_CU); }
+
+// The checks and the launches of all three entries.  theta != NULL: h_signed from the device-resident parameters (prm: eps only).
+// sums [2] and grad [param count] are the two ends of `packed` in the reduce / step forms; `apply`: the backward block that writes
+// the gradient's fixed-order sum runs the update on packed = grad - 2 behind it.  n_rows == 0: one block each, zeros (and the update).
+static int cnn_wide_reduce(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int fw, int nf, int l1,
+                           int width, const double *params, const double *theta, const bear_params &prm, int train_ar, double *dz_buf,
+                           double *t1_buf, double *sums, double *grad, hipStream_t s, const bear_apply_io &apply) {
+  if (!cnn_wide_shape_ok(lag, fw, nf, l1, width)) return BEAR_ERR_INVALID_ARG;
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  if (!params || !sums || !grad || (n_rows && (!counts || !codes || !dz_buf || !t1_buf))) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(counts) || misaligned(codes) || misaligned(dz_buf) || misaligned(t1_buf)) return BEAR_ERR_INVALID_ARG;
+  if (misaligned8(params) || misaligned8(sums) || misaligned8(grad) || !(prm.eps >= 0.0)) return BEAR_ERR_INVALID_ARG;
+  const cnn_dims D = cnw_make_dims(lag, fw);
+  const bear_step_io io = ws_io(ws, theta, BEAR_THETA_NET, sums);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+#define CNN_WIDE_HEAD(AR)                                                                                                              \
+  hipLaunchKernelGGL((cnn_wide_head_dm_kernel<AR>), dim3(cnnwide_head_grid(ws, n_rows)), dim3(CNW_HEAD_THREADS), cnw_head_lds(lag, fw), s, \
+                     counts, codes, n_rows, D, params, prm, lt, t1_buf, dz_buf, ws->partials, io)
+  BEAR_DISPATCH_1(train_ar, CNN_WIDE_HEAD);
+#undef CNN_WIDE_HEAD
+  // (a stamp of its own on the arrival words: the head's last block has left them at zero by the time this one starts)
+  hipLaunchKernelGGL(cnn_wide_backward_kernel<true>, dim3(cnnwide_bwd_grid(ws, n_rows)), dim3(CNW_BWD_THREADS), cnw_bwd_lds(lag, fw), s, codes,
+                     n_rows, D, params, t1_buf, dz_buf, static_cast<const double *>(nullptr), ws->cnnw_partials, ws_arrival(ws), grad, apply);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_dm_cnn_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int filter_width,
+                         int num_filters, int layer1_width, int width, const double *params, double h_signed, double eps, int train_ar,
+                         double *dz_buf, double *t1_buf, double *out, double *grad_params, void *stream) {
+  if (!isfinite(h_signed)) return BEAR_ERR_INVALID_ARG;
+  return cnn_wide_reduce(ws, counts, codes, n_rows, lag, filter_width, num_filters, layer1_width, width, params, nullptr,
+                         params_net(h_signed, eps), train_ar, dz_buf, t1_buf, out, grad_params, static_cast<hipStream_t>(stream), NO_APPLY);
+}
+
+int bear_net_cnn_train_reduce_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int filter_width,
+                                       int num_filters, int layer1_width, int width, const double *theta, double *dz_buf, double *t1_buf,
+                                       double eps, int train_ar, double *packed, void *stream) {
+  if (!theta || !packed || misaligned8(theta)) return BEAR_ERR_INVALID_ARG;
+  return cnn_wide_reduce(ws, counts, codes, n_rows, lag, filter_width, num_filters, layer1_width, width, theta + 1, theta, params_eps(eps),
+                         train_ar, dz_buf, t1_buf, packed, packed + 2, static_cast<hipStream_t>(stream), NO_APPLY);
+}
+
+int bear_net_cnn_train_step_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int filter_width,
+                                     int num_filters, int layer1_width, int width, double *theta, double *adam_m, double *adam_v,
+                                     double *adam_t, double *dz_buf, double *t1_buf, double eps, int train_ar, double learning_rate,
+                                     double scale, double *packed, double *loss_buf, uint64_t loss_cap, void *stream) {
+  if (!theta || !packed || !adam_m || !adam_v || !adam_t) return BEAR_ERR_INVALID_ARG;
+  if (misaligned8(theta) || misaligned8(adam_m) || misaligned8(adam_v) || misaligned8(adam_t) || misaligned8(loss_buf))
+    return BEAR_ERR_INVALID_ARG;
+  if (!cnn_wide_shape_ok(lag, filter_width, num_filters, layer1_width, width)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n_theta = 1 + cnw_make_dims(lag, filter_width).total;
+  if (two_launch_step()) {
+    int st = cnn_wide_reduce(ws, counts, codes, n_rows, lag, filter_width, num_filters, layer1_width, width, theta + 1, theta,
+                             params_eps(eps), train_ar, dz_buf, t1_buf, packed, packed + 2, s, NO_APPLY);
+    if (st != BEAR_OK) return st;
+    return launch_train_apply(theta, n_theta, packed, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap, s);
+  }
+  // the backward block that sums the gradient's partials runs the update behind them (bear_apply_in_block)
+  return cnn_wide_reduce(ws, counts, codes, n_rows, lag, filter_width, num_filters, layer1_width, width, theta + 1, theta, params_eps(eps),
+                         train_ar, dz_buf, t1_buf, packed, packed + 2, s,
+                         make_apply(theta, n_theta, adam_m, adam_v, adam_t, learning_rate, scale, train_ar, loss_buf, loss_cap));
 }

@@ -20,7 +20,7 @@ struct bear_ws {
   int device;
   int num_cu;
   int max_blocks;
-  double *partials;  // [max_blocks][BEAR_MAX_OUT]
+  double *partials;  // [max_blocks][BEAR_MAX_OUT] (block_finish: the DM steps; the head kernel of the wide convolutional step)
   double *logtab;    // [BEAR_LOGTAB_N][2] = {r_i, -log r_i} (bear_math.h, bear_log_tab)
   unsigned long long *dbg;  // developer timing buffer [max_blocks][8][6]
   double *eval_partials;    // [eval_blocks][EVL_MAX_OUT] (kernels_eval.h)
@@ -35,7 +35,8 @@ struct bear_ws {
   unsigned epoch;                  // host side: the stamp of the last launch that used `arrive` (never 0)
   double *cnn_partials;     // [cnn_blocks][cnn total] parameter-gradient partials (kernels_cnn.h), grown on demand
   size_t cnn_partials_cap;  // doubles
-  double *cnnw_partials;    // [num_cu + 16][CNW_MAX_TOTAL] parameter-gradient partials at width 21 (kernels_cnn_wide.h)
+  double *cnnw_partials;    // [num_cu + 16][CNW_MAX_TOTAL] parameter-gradient partials at width 21 (kernels_cnn_wide.h: the backward
+                            // kernel, as rows entry or as the second launch of the fused step -- one launch at a time)
 };
 
 struct bear_params {

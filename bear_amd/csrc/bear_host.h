@@ -4,7 +4,7 @@
 //   bear_hip.hip     status strings, the workspace, synthetic tables, samplers, the row shuffle; the DM steps (rows, sorted,
 //                    planned, reference-aware, ref-mix) and the plan itself
 //   bear_linear.hip  k-mer packing, the paired lists, the linear AR head (fused step and rows, both also at rows of 21), the Adam launch
-//   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21
+//   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21 and bear_net's step with it
 //   bear_eval.hip    held-out evaluation (5- and 21-wide), the wide DM step and bear_ref's wide steps, the evaluation plan, the BMM marginal
 // What a unit needs of another goes through the declarations at the end of this file.
 //

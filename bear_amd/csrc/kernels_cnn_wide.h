@@ -36,6 +36,19 @@
 //             same bits in both builds of the library (no deterministic twin).
 //             Grid: min(ceil(n / 64), CUs) blocks, at least one (bear_cnn.hip, cnnwide_bwd_grid) -- part of the result.
 //             A tile whose grad_prior rows are all zero is skipped.
+//
+// bear_net's training step with this AR function (bear_dm_cnn_wide_f64, bear_net_cnn_train_{reduce,step}_wide_f64) is TWO launches:
+//   head    : cnn_wide_head_dm_kernel<AR> -- the forward above plus the DM step of kernels_wide.h (wide_dm_row on the tile's staged
+//             count rows) plus dz = f (q - <f, q>) while f is still on the CU, a context per lane of all four waves, tiles of 256.  A
+//             context without counts forms no row and no item.  Leaves t1 [n, 16] and the dz rows [n, 21] (16-byte nontemporal
+//             stores): no prior row and no gradient row reaches memory.  Sum LL and d/dh: thread -> wave -> block partial, the last
+//             block sums the partials in a fixed order into packed[0..1] (block_finish).  Grid: min(ceil(n / 256), CUs) blocks.
+//   backward: cnn_wide_backward_kernel<true> -- the backward above with the dz rows loaded instead of formed, its
+//             fixed-order sum straight into packed + 2; in the step form the block that wrote it runs the Adam update on the whole
+//             packed vector (bear_apply_in_block: the head's two sums are complete by stream order).
+//   Why two and not one: the backward runs everything that is per context on wave 0 of a one-block-per-CU grid (the other waves hold
+//   the MFMA accumulators); the forward and the item walk run there would be on 64 lanes per CU, a quarter of the head kernel's.  Each
+//   launch gets its own stamp on the workspace's arrival words (ws_arrival) and leaves them at zero: they run in stream order.
 #pragma once
 #include "bear_common.h"
 #include "kernels_cnn.h"          // cnn_dims, cnn_elu, cnn_rsqrt, cnn_layer1
@@ -241,13 +254,17 @@ static_assert(cnw_bwd_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG) + 512 <= 160 * 102
               "convolutional rows backward at width 21: LDS");
 static_assert(cnw_bwd_lds(CNN_WIDE_MAX_LAG + 1, CNN_WIDE_MAX_LAG + 1) + 272 > 160 * 1024, "CNN_WIDE_MAX_LAG is what fits");
 
+// DZ = false: the rows entry (prior and grad_prior rows in, dz formed here; `apply` is not read).  DZ = true: the second launch of the
+// fused step -- `prior` holds the dz rows cnn_wide_head_dm_kernel left, grad_prior is not read, grad_params is packed + 2, and the block
+// that wrote the fixed-order sum runs the update on the whole packed vector when the launch carries one.
+template <bool DZ>
 __global__ __launch_bounds__(CNW_BWD_THREADS) void cnn_wide_backward_kernel(const int8_t *__restrict__ codes, uint64_t n, cnn_dims D,
                                                                             const double *__restrict__ params,
                                                                             const double *__restrict__ t1_save,
                                                                             const double *__restrict__ prior,
                                                                             const double *__restrict__ grad_prior,
                                                                             double *__restrict__ partials, const bear_arrival arrive,
-                                                                            double *__restrict__ grad_params) {
+                                                                            double *__restrict__ grad_params, const bear_apply_io apply) {
   extern __shared__ __attribute__((aligned(16))) double cnw_lds[];
   __shared__ unsigned s_flag;
   double *exptab = cnw_lds;
@@ -301,24 +318,35 @@ __global__ __launch_bounds__(CNW_BWD_THREADS) void cnn_wide_backward_kernel(cons
     if (wave == 0) {
       double *hb = HB + lane * CNW_HS, *he = HE + lane * CNW_ES;
       if (valid) {
-        const double *fr = prior + (row0 + lane) * CNW_W, *qr = grad_prior + (row0 + lane) * CNW_W;
-        double dz[CNW_W], s = 0.0;
+        const double *fr = prior + (row0 + lane) * CNW_W;
+        double dz[CNW_W];
+        if (DZ) {                                        // the head kernel's dz rows as they are
 #pragma unroll
-        for (int b = 0; b < CNW_W; ++b) {
-          const double q = qr[b];
-          dz[b] = q;
-          nz |= q != 0.0;
-        }
+          for (int b = 0; b < CNW_W; ++b) {
+            dz[b] = fr[b];
+            nz |= dz[b] != 0.0;
+            hb[b] = dz[b];
+          }
+        } else {
+          const double *qr = grad_prior + (row0 + lane) * CNW_W;
+          double s = 0.0;
 #pragma unroll
-        for (int b = 0; b < CNW_W; ++b) {
-          const double f = fr[b];
-          s = __builtin_fma(f, dz[b], s);
-          hb[b] = f;                                     // (parked: dz needs the whole sum)
-        }
+          for (int b = 0; b < CNW_W; ++b) {
+            const double q = qr[b];
+            dz[b] = q;
+            nz |= q != 0.0;
+          }
 #pragma unroll
-        for (int b = 0; b < CNW_W; ++b) {
-          dz[b] = hb[b] * (dz[b] - s);
-          hb[b] = dz[b];
+          for (int b = 0; b < CNW_W; ++b) {
+            const double f = fr[b];
+            s = __builtin_fma(f, dz[b], s);
+            hb[b] = f;                                   // (parked: dz needs the whole sum)
+          }
+#pragma unroll
+          for (int b = 0; b < CNW_W; ++b) {
+            dz[b] = hb[b] * (dz[b] - s);
+            hb[b] = dz[b];
+          }
         }
         double t1[CNN_L1], n1[CNN_L1], e1[CNN_L1], d1[CNN_L1];
         const double2 *tr = reinterpret_cast<const double2 *>(t1_save + (row0 + lane) * CNN_L1);
@@ -515,5 +543,134 @@ __global__ __launch_bounds__(CNW_BWD_THREADS) void cnn_wide_backward_kernel(cons
       }
     }
   }
-  lnw_sum_partials<CNW_BWD_THREADS>(partials, D.total, arrive, &s_flag, grad_params);
+  if (DZ) {
+    // the fused step: packed[0..1] are complete by stream order (the head kernel's launch), packed + 2 is written here
+    if (lnw_sum_partials<CNW_BWD_THREADS>(partials, D.total, arrive, &s_flag, grad_params)) bear_apply_in_block(apply, grad_params - 2);
+  } else {
+    lnw_sum_partials<CNW_BWD_THREADS>(partials, D.total, arrive, &s_flag, grad_params);
+  }
+}
+
+// ------------------------------------------------------------------ the fused step's first launch: forward + DM step
+// A context per lane, every lane of the block: the forward of cnn_wide_forward_kernel on its tile (256 contexts, the same routines, so
+// the row f has the bits of the row entry), then wide_dm_row on the tile's staged count rows -- q = d LL / d f in place of f in LDS,
+// f itself kept in registers -- and dz = f (q - <f, q>) in the arithmetic of the backward kernel's head.  What leaves: t1 [16] per
+// context (zeros for a context without counts: the backward reads every row) and the tile's dz rows; sum LL and d/dh as in
+// dm_wide_kernel (block_finish).
+#define CNW_HEAD_THREADS 256
+#define CNW_HEAD_TILE CNW_HEAD_THREADS                 // one context per thread
+#define CNW_HEAD_BLOCKS_PER_CU 1                       // the grid cap (part of the two sums): the count tile leaves no room for a second block
+// dynamic LDS (doubles): exp table | log table | a tile's f / q / dz rows | its uint32 count rows | its code bytes | scale0,
+// intercept0 [P][30] each | weights1 [P][30][16] | the filter image
+#define CNW_HEAD_FIXED_DOUBLES \
+  (BEAR_EXPTAB_N + 2 * BEAR_LOGTAB_N + CNW_HEAD_TILE * CNW_W + CNW_HEAD_TILE * CNW_W / 2 + CNW_HEAD_TILE * CNN_WIDE_MAX_LAG / 8)
+static_assert((BEAR_EXPTAB_N % 2 == 0) && (CNW_HEAD_TILE * CNW_W) % 4 == 0 && (CNW_HEAD_TILE * CNN_WIDE_MAX_LAG / 8) % 2 == 0,
+              "16-byte aligned tables, rows, counts and code bytes");
+__host__ __device__ static inline constexpr size_t cnw_head_lds(int lag, int fw) {
+  return sizeof(double) * (CNW_HEAD_FIXED_DOUBLES + (size_t)(lag - fw + 1) * (2 * CNN_NF + CNN_NF * CNN_L1) + (size_t)CNW_FROWS(fw) * CNW_FS);
+}
+// (the ends of the fw range are the extremes, as above; 1168 static bytes of block_finish next to it: 156.7 KiB at fw = lag = 16)
+static_assert(cnw_head_lds(CNN_WIDE_MAX_LAG, CNN_WIDE_MAX_LAG) + 1280 <= 160 * 1024 && cnw_head_lds(CNN_WIDE_MAX_LAG, 1) + 1280 <= 160 * 1024,
+              "convolutional step head at width 21: LDS");
+
+template <bool AR>
+__global__ __launch_bounds__(CNW_HEAD_THREADS) void cnn_wide_head_dm_kernel(const uint32_t *__restrict__ counts, const int8_t *__restrict__ codes,
+                                                                           uint64_t n, cnn_dims D, const double *__restrict__ params,
+                                                                           bear_params prm_arg, const double2 *__restrict__ logtab_g,
+                                                                           double *__restrict__ t1_save, double *__restrict__ dz_rows,
+                                                                           double *__restrict__ partials, const bear_step_io io) {
+  extern __shared__ __attribute__((aligned(16))) double cnw_lds[];
+  double *exptab = cnw_lds;
+  double2 *s_log = reinterpret_cast<double2 *>(exptab + BEAR_EXPTAB_N);
+  double *R = exptab + BEAR_EXPTAB_N + 2 * BEAR_LOGTAB_N;
+  uint32_t *s_cnt = reinterpret_cast<uint32_t *>(R + CNW_HEAD_TILE * CNW_W);
+  int8_t *s_c = reinterpret_cast<int8_t *>(R + CNW_HEAD_TILE * CNW_W + CNW_HEAD_TILE * CNW_W / 2);
+  double *S0 = cnw_lds + CNW_HEAD_FIXED_DOUBLES;
+  double *B0 = S0 + D.P * CNN_NF;
+  double *W1 = B0 + D.P * CNN_NF;
+  double *Fs = W1 + D.P * CNN_NF * CNN_L1;
+  const uint32_t tid = threadIdx.x;
+  const bear_params prm = bear_params_of(prm_arg, io);
+  if (tid < BEAR_EXPTAB_N) exptab[tid] = exp2((double)tid * (1.0 / BEAR_EXPTAB_N));
+  if (tid < BEAR_LOGTAB_N) s_log[tid] = logtab_g[tid];
+  cnw_stage_params<CNW_HEAD_THREADS>(S0, B0, W1, Fs, params, D);
+  const int lag = D.lag;
+  double acc[2] = {0.0, 0.0};
+  const uint64_t n_tiles = (n + CNW_HEAD_TILE - 1) / CNW_HEAD_TILE;
+  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const uint64_t row0 = tile * CNW_HEAD_TILE;
+    const uint32_t rows = (uint32_t)((n - row0 < (uint64_t)CNW_HEAD_TILE) ? (n - row0) : (uint64_t)CNW_HEAD_TILE);
+    __syncthreads();   // the previous tile has left R, s_cnt and s_c (and the tables are in place)
+    stage_dwords<CNW_HEAD_THREADS>(s_cnt, counts + row0 * CNW_W, rows * CNW_W);
+    wide_stage_codes<CNW_HEAD_THREADS>(s_c, codes, row0, rows, lag);
+    __syncthreads();
+    if (tid < rows) {
+      const uint32_t *cnt = s_cnt + tid * CNW_W;
+      double *r = R + tid * CNW_W;
+      double2 *o = reinterpret_cast<double2 *>(t1_save + (row0 + tid) * CNN_L1);
+      if (wide_nz_mask<CNW_W>(cnt) != 0u) {
+        const int8_t *c = s_c + tid * (uint32_t)lag;
+        double t1[CNN_L1];
+#pragma unroll
+        for (int u = 0; u < CNN_L1; ++u) t1[u] = 0.0;
+        for (int p = 0; p < D.P; ++p) {
+          double x[CNN_NF];
+          cnw_conv_norm(Fs, c, p, D.fw, true, x);
+          const double *s0 = S0 + p * CNN_NF, *b0 = B0 + p * CNN_NF;
+          const double2 *w1 = reinterpret_cast<const double2 *>(W1 + p * CNN_NF * CNN_L1);
+#pragma unroll
+          for (int f = 0; f < CNN_NF; ++f) {
+            double dv;
+            const double e = cnn_elu(__builtin_fma(s0[f], x[f], b0[f]), exptab, dv);
+#pragma unroll
+            for (int u2 = 0; u2 < CNN_L1 / 2; ++u2) {
+              const double2 w = w1[f * (CNN_L1 / 2) + u2];
+              t1[2 * u2] = __builtin_fma(e, w.x, t1[2 * u2]);
+              t1[2 * u2 + 1] = __builtin_fma(e, w.y, t1[2 * u2 + 1]);
+            }
+          }
+        }
+#pragma unroll
+        for (int u2 = 0; u2 < CNN_L1 / 2; ++u2) o[u2] = make_double2(t1[2 * u2], t1[2 * u2 + 1]);
+        double n1[CNN_L1], e1[CNN_L1], d1[CNN_L1];
+        cnn_layer1(t1, params, D, exptab, n1, e1, d1);
+        double z[CNW_W], m = -INFINITY;
+#pragma unroll
+        for (int b = 0; b < CNW_W; ++b) {
+          double s = params[D.ob2 + b];
+#pragma unroll
+          for (int u = 0; u < CNN_L1; ++u) s = __builtin_fma(e1[u], params[D.oW2 + u * CNW_W + b], s);
+          z[b] = s;
+          m = s > m ? s : m;
+        }
+        double tot = 0.0;
+#pragma unroll
+        for (int b = 0; b < CNW_W; ++b) {
+          z[b] = bear_exp_tab(z[b] - m, exptab);
+          tot += z[b];
+        }
+        const double rt = bear_rcp(tot);
+#pragma unroll
+        for (int b = 0; b < CNW_W; ++b) {
+          z[b] *= rt;                                    // the row f: kept here, and in LDS for the item walk
+          r[b] = z[b];
+        }
+        wide_dm_row<CNW_W, AR, true>(cnt, r, r, prm, s_log, acc);   // q = d LL / d f in place
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < CNW_W; ++b) s = __builtin_fma(z[b], r[b], s);
+#pragma unroll
+        for (int b = 0; b < CNW_W; ++b) r[b] = z[b] * (r[b] - s);
+      } else {                                           // no counts: no row, no item; exact zeros
+#pragma unroll
+        for (int b = 0; b < CNW_W; ++b) r[b] = 0.0;
+#pragma unroll
+        for (int u2 = 0; u2 < CNN_L1 / 2; ++u2) o[u2] = make_double2(0.0, 0.0);
+      }
+    }
+    __syncthreads();
+    wide_store_tile<CNW_HEAD_THREADS, CNW_W>(R, dz_rows + row0 * CNW_W, rows);
+  }
+  __syncthreads();
+  block_finish<2>(acc, partials, io);
 }

@@ -1152,3 +1152,84 @@ def cnn_step_buffers(n_rows, lag, filter_width, device, ws=None):
     # zeros: the step only fills the rows of contexts that hold training counts (nothing reads the others: kept finite)
     return (torch.zeros((n_rows, 5), dtype=torch.float64, device=device), torch.zeros((n_rows, CNN_LAYER1_WIDTH), dtype=torch.float64, device=device),
             torch.zeros((n_rows, 5), dtype=torch.float64, device=device))
+
+
+# tiles and resident blocks per CU of the two launches of the convolutional step at width 21 (kernels_cnn_wide.h: CNW_HEAD_TILE,
+# CNW_HEAD_BLOCKS_PER_CU; CNW_BWD_TILE, CNW_BWD_BLOCKS_PER_CU): each takes min(tiles, blocks per CU * CUs) blocks, and each grid is
+# part of the result -- tests size a table beyond both from these
+CNN_STEP_WIDE_TILE = 256
+CNN_STEP_WIDE_BLOCKS_PER_CU = 1
+CNN_STEP_WIDE_BACKWARD_TILE = 64
+CNN_STEP_WIDE_BACKWARD_BLOCKS_PER_CU = 1
+
+
+def cnn_step_buffers_wide(n_rows, device):
+    """Per-context scratch of the convolutional step at width 21 for (at most) ``n_rows`` contexts: (dz [n, 21], t1 [n, 16]), 296 B
+    per context.  Steps on one stream run one after the other, so one pair sized for the largest batch serves every batch."""
+    n = max(int(n_rows), 1)
+    return (torch.zeros((n, LINEAR_WIDE_WIDTH), dtype=torch.float64, device=device),
+            torch.zeros((n, CNN_LAYER1_WIDTH), dtype=torch.float64, device=device))
+
+
+def _check_cnn_step_wide(counts, codes, lag, filter_width, bufs):
+    """The shape checks of the three entries; returns (counts, codes, dz, t1, parameter count)."""
+    if not cnn_supported(int(lag), 20, int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH):
+        raise ValueError(f"1 <= filter_width <= lag <= {CNN_WIDE_MAX_LAG} (the filter image and a tile's staged rows live in LDS)")
+    counts, codes = _check_rows(counts, torch.int32, "counts", LINEAR_WIDE_WIDTH), _check_codes_wide(codes, lag)
+    if codes.shape[0] != counts.shape[0] or codes.device != counts.device:
+        raise ValueError("counts and codes must have the same number of rows, on one device")
+    n = counts.shape[0]
+    dz, t1 = bufs if bufs is not None else cnn_step_buffers_wide(n, counts.device)
+    for t, w, name in ((dz, LINEAR_WIDE_WIDTH, "dz"), (t1, CNN_LAYER1_WIDTH, "t1")):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == w and t.shape[0] >= n and t.is_contiguous()
+                and t.data_ptr() % 16 == 0 and t.device == counts.device):
+            raise ValueError(f"bufs: {name} must be a contiguous, 16-byte aligned CUDA float64 tensor [>= n_rows, {w}] (cnn_step_buffers_wide)")
+    return counts, codes, dz, t1, cnn_param_count_wide(lag, filter_width)
+
+
+def dm_cnn_wide(counts, codes, flat_params, lag, filter_width, h_signed, eps=EPSILON, train_ar=False, bufs=None, out=None, ws=None):
+    """``bear_dm_cnn_wide_f64``: the convolutional AR function, the DM step and the gradient of the parameters on protein rows in two
+    launches (what ``cnn_forward_wide``, ``dm_prior_wide(want_grad=True)`` and ``cnn_backward_wide`` compute in three, with the row
+    arrays through memory).  ``bufs``: ``cnn_step_buffers_wide`` (made here when None).  Returns (out [2] = sum LL, d/dh_signed;
+    d sum LL / d flat_params)."""
+    counts, codes, dz, t1, np_ = _check_cnn_step_wide(counts, codes, lag, filter_width, bufs)
+    _check_params_wide(flat_params, lag, filter_width)
+    if flat_params.device != counts.device:
+        raise ValueError("flat_params: on another device than counts")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=counts.device)
+    _f64_vec(out, 2, "out")
+    ws = ws or default_workspace(counts.device)
+    grad = torch.empty_like(flat_params)
+    _launch(counts.device, "bear_dm_cnn_wide_f64", ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag), int(filter_width),
+            CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, LINEAR_WIDE_WIDTH, _ptr(flat_params), float(h_signed), float(eps), int(bool(train_ar)),
+            _ptr(dz), _ptr(t1), _ptr(out), _ptr(grad))
+    return out, grad
+
+
+def net_cnn_train_reduce_wide(counts, codes, lag, filter_width, theta, bufs, packed, eps=EPSILON, train_ar=False, ws=None):
+    """Enqueues ``bear_net_cnn_train_reduce_wide_f64``: packed = [sum LL, d/dh_s, d/d params] of these rows, theta = {h_signed, flat
+    CNN parameters} device-resident; ``bufs`` = (dz [n, 21], t1 [n, 16]) from ``cnn_step_buffers_wide``."""
+    counts, codes, dz, t1, np_ = _check_cnn_step_wide(counts, codes, lag, filter_width, bufs)
+    _f64_vec(theta, 1 + np_, "theta")
+    _f64_vec(packed, 2 + np_, "packed")
+    ws = ws or default_workspace(counts.device)
+    _launch(counts.device, "bear_net_cnn_train_reduce_wide_f64", ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
+            int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, LINEAR_WIDE_WIDTH, _ptr(theta), _ptr(dz), _ptr(t1), float(eps),
+            int(bool(train_ar)), _ptr(packed))
+
+
+def net_cnn_train_step_wide(counts, codes, lag, filter_width, theta, adam_m, adam_v, adam_t, bufs, packed, learning_rate, scale,
+                            loss_buf=None, eps=EPSILON, train_ar=False, ws=None):
+    """Enqueues one ``bear_net_cnn_train_step_wide_f64`` (HIP-graph capturable): the reduce and tf.keras Adam on theta = {h_signed,
+    flat CNN parameters}, the update in the block of the second launch that sums the gradient."""
+    counts, codes, dz, t1, np_ = _check_cnn_step_wide(counts, codes, lag, filter_width, bufs)
+    for t, k, name in ((theta, 1 + np_, "theta"), (adam_m, 1 + np_, "adam_m"), (adam_v, 1 + np_, "adam_v"), (adam_t, 1, "adam_t"),
+                       (packed, 2 + np_, "packed")):
+        _f64_vec(t, k, name)
+    if loss_buf is not None:
+        _f64_vec(loss_buf, loss_buf.numel(), "loss_buf")
+    ws = ws or default_workspace(counts.device)
+    _launch(counts.device, "bear_net_cnn_train_step_wide_f64", ws.handle, _ptr(counts), _ptr(codes), counts.shape[0], int(lag),
+            int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, LINEAR_WIDE_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t),
+            _ptr(dz), _ptr(t1), float(eps), int(bool(train_ar)), float(learning_rate), float(scale), _ptr(packed), *_loss(loss_buf))

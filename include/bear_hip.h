@@ -49,7 +49,9 @@ extern "C" {
                                   bear_net_linear_train_reduce_wide_f64, bear_net_linear_train_step_wide_f64 (bear_net's step with the
                                   linear AR function on rows of 21 as one launch);
                                   + bear_kmer_sort_bytes, bear_kmer_bin_hist, bear_kmer_sort_create_range (counting in passes over
-                                  key ranges) */
+                                  key ranges);
+                                  + bear_dm_cnn_wide_f64, bear_net_cnn_train_reduce_wide_f64, bear_net_cnn_train_step_wide_f64
+                                  (bear_net's step with the convolutional AR function on rows of 21 as two launches) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -488,6 +490,41 @@ int bear_cnn_forward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows,
 int bear_cnn_backward_wide_f64(bear_ws *ws, const int8_t *codes, uint64_t n_rows, int lag, int filter_width, int num_filters,
                                int layer1_width, int width, const double *params, const double *t1_save, const double *prior,
                                const double *grad_prior, double *grad_params, void *stream);
+
+/*
+ * bear_net's training step with the convolutional AR function at the protein alphabet's width as TWO launches (kernels_cnn_wide.h):
+ * what bear_cnn_forward_wide_f64, bear_dm_prior_wide_f64 with gradient rows and bear_cnn_backward_wide_f64 compute in three, without
+ * a prior row or a gradient row reaching memory.  The first launch runs the forward pass, the DM step on the count rows and the way
+ * back through the softmax, a context per lane, and leaves the layer-1 sums and dz = d sum LL / d logits; the second is the backward
+ * kernel on those rows.  A context whose counts are all zero forms no row and no item (its dz row is exact zeros).  No plan, any row order.
+ *   counts     [dev] uint32 [n_rows,21]  16-byte aligned;  codes [dev] int8 [n_rows,lag], 16-byte aligned (as above)
+ *   lag, filter_width, num_filters, layer1_width, width: as bear_cnn_forward_wide_f64 (anything else: BEAR_ERR_INVALID_ARG, nothing is
+ *              launched; so is a NULL or misaligned pointer)
+ *   dz_buf     [dev] double [n_rows,21], t1_buf [dev] double [n_rows,16]: scratch lent by the caller, 16-byte aligned, overwritten
+ *              (may be NULL when n_rows == 0)
+ * bear_dm_cnn_wide_f64: the primitive, constants by value:
+ *   params [dev] double [bear_cnn_param_count_wide(...)];  out [dev] double [2] = {sum LL, d sum LL / d h_signed (0 with train_ar)};
+ *   grad_params [dev] double [param count] = d sum LL / d params, overwritten.
+ * bear_net_cnn_train_reduce_wide_f64 / bear_net_cnn_train_step_wide_f64: theta [dev] double [1 + param count] = {h_signed, params...},
+ *   read on the device;  packed [dev] double [2 + param count] = {sum LL, d/dh, d/d params...}.  The step form runs the tf.keras Adam
+ *   update of theta (adam_m, adam_v [1 + param count], adam_t [1]) and the loss record (bear_train_apply_f64's arguments) in the block
+ *   of the second launch that sums the gradient's partials: the same bits as reduce followed by bear_train_apply_f64, which is what
+ *   BEAR_AMD_TWO_LAUNCH_STEP=1 makes of it (three launches).
+ * n_rows == 0: zeros (the step form still updates and records).  No floating-point atomics: block partials are summed in a fixed
+ * order, the same inputs give the same bits from run to run for a given device (grids: min(ceil(n_rows / 256), CUs) and
+ * min(ceil(n_rows / 64), CUs) blocks), identically in both builds of the library.  Asynchronous on `stream`, no allocation, nothing is
+ * read back to the host: all three can be captured into a HIP graph.
+ */
+int bear_dm_cnn_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int filter_width,
+                         int num_filters, int layer1_width, int width, const double *params, double h_signed, double eps, int train_ar,
+                         double *dz_buf, double *t1_buf, double *out, double *grad_params, void *stream);
+int bear_net_cnn_train_reduce_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag,
+                                       int filter_width, int num_filters, int layer1_width, int width, const double *theta,
+                                       double *dz_buf, double *t1_buf, double eps, int train_ar, double *packed, void *stream);
+int bear_net_cnn_train_step_wide_f64(bear_ws *ws, const uint32_t *counts, const int8_t *codes, uint64_t n_rows, int lag, int filter_width,
+                                     int num_filters, int layer1_width, int width, double *theta, double *adam_m, double *adam_v,
+                                     double *adam_t, double *dz_buf, double *t1_buf, double eps, int train_ar, double learning_rate,
+                                     double scale, double *packed, double *loss_buf, uint64_t loss_cap, void *stream);
 
 /*
  * Held-out evaluation, one pass over a row range: replaces _evaluation_step of bear_model/bear_net.py:323-371

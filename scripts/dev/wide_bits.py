@@ -137,6 +137,18 @@ def cnn_kernels(cus):
         f, t1 = kernels.cnn_forward_wide(cd, params, lag, fw)
         put("cnn_forward_wide/lag%d/fw%d/n%d" % (lag, fw, n), f, t1)
         put("cnn_backward_wide/lag%d/fw%d/n%d" % (lag, fw, n), kernels.cnn_backward_wide(cd, params, lag, fw, t1, f, q - 0.3))
+        # the fused step (drawn after everything above: the entries above keep their inputs); the last size is beyond its head
+        # kernel's grid too (one block of CNN_STEP_WIDE_TILE per CU)
+        assert CNN_FWD_PER_CU * CNN_FWD_TILE >= kernels.CNN_STEP_WIDE_BLOCKS_PER_CU * kernels.CNN_STEP_WIDE_TILE
+        c = counts(rng, n, 21)
+        theta = torch.cat([f64(-0.3), params])
+        for ar in (False, True):
+            bufs = kernels.cnn_step_buffers_wide(n, "cuda")
+            put("dm_cnn_wide/lag%d/fw%d/n%d/ar%d" % (lag, fw, n, ar), *kernels.dm_cnn_wide(c, cd, params, lag, fw, -0.3, train_ar=ar, bufs=bufs))
+            put("dm_cnn_wide/lag%d/fw%d/n%d/ar%d/bufs" % (lag, fw, n, ar), *bufs)
+            packed = torch.zeros(theta.numel() + 1, dtype=torch.float64, device="cuda")
+            kernels.net_cnn_train_reduce_wide(c, cd, lag, fw, theta, bufs, packed, train_ar=ar)
+            put("net_cnn_train_reduce_wide/lag%d/fw%d/n%d/ar%d" % (lag, fw, n, ar), packed)
 
 
 def codes5(rng, n, lag, in_kmer_order):
