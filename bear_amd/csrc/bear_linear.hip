@@ -8,15 +8,33 @@
 #include "kernels_linrows_wide.h"
 #include "kernels_linear_wide.h"
 
+// ---- the fused step's kernel (kernels_linear.h), every instantiation: [AR][PAIRED][DET][slot].  A slot is a number of letter groups
+// as a compile-time constant: the lags 4 / 5 (2 groups: the bundled table), 12 / 13 (6: BASELINE's k = 13) and 14 / 15 (7); slot 0
+// takes the kernel that finds the number at run time (distinct13: 0.847 -> 0.833 ms, 128 -> 97 registers).  A count added to
+// LIN_NGK gets its kernels, their LDS attribute (linear_ws_setup) and its launches (launch_linear) from this one list.
+static constexpr int LIN_NGK[] = {0, 2, 6, 7};
+constexpr int LIN_SLOTS = (int)(sizeof(LIN_NGK) / sizeof(LIN_NGK[0]));
+using lin_kernel_fn = decltype(&dm_linear_plan_kernel<false, false, false, 0>);
+#define LIN_FORMS(AR, PAIRED, DET)                                                                                     \
+  {dm_linear_plan_kernel<AR, PAIRED, DET, LIN_NGK[0]>, dm_linear_plan_kernel<AR, PAIRED, DET, LIN_NGK[1]>, \
+   dm_linear_plan_kernel<AR, PAIRED, DET, LIN_NGK[2]>, dm_linear_plan_kernel<AR, PAIRED, DET, LIN_NGK[3]>}
+static_assert(LIN_SLOTS == 4, "LIN_FORMS names the slots");
+static const lin_kernel_fn LIN_KERNELS[2][2][2][LIN_SLOTS] = {
+    {{LIN_FORMS(false, false, false), LIN_FORMS(false, false, true)}, {LIN_FORMS(false, true, false), LIN_FORMS(false, true, true)}},
+    {{LIN_FORMS(true, false, false), LIN_FORMS(true, false, true)}, {LIN_FORMS(true, true, false), LIN_FORMS(true, true, true)}}};
+#undef LIN_FORMS
+// the slot of a number of groups (0: none of the specialised ones)
+static int lin_slot(int n_groups) {
+  for (int k = 1; k < LIN_SLOTS; ++k)
+    if (LIN_NGK[k] == n_groups) return k;
+  return 0;
+}
+
 int linear_ws_setup(bear_ws *ws) {
-#define LIN_ALL_NGK(AR, PAIRED, DET)                                                                          \
-  BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 0>), BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 2>), \
-      BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 6>), BEAR_KFN(dm_linear_plan_kernel<AR, PAIRED, DET, 7>)
-  int st = allow_dynamic_lds({LIN_ALL_NGK(false, false, false), LIN_ALL_NGK(true, false, false), LIN_ALL_NGK(false, true, false),
-                                    LIN_ALL_NGK(true, true, false), LIN_ALL_NGK(false, false, true), LIN_ALL_NGK(true, false, true),
-                                    LIN_ALL_NGK(false, true, true), LIN_ALL_NGK(true, true, true)},
-                                   sizeof(pln_lds_lin));
-#undef LIN_ALL_NGK
+  int st = BEAR_OK;
+  const lin_kernel_fn *all = &LIN_KERNELS[0][0][0][0];
+  for (size_t k = 0; st == BEAR_OK && k < sizeof(LIN_KERNELS) / sizeof(lin_kernel_fn); ++k)
+    st = allow_dynamic_lds({BEAR_KFN(all[k])}, sizeof(pln_lds_lin));
   if (st != BEAR_OK) return st;
   st = allow_dynamic_lds({BEAR_KFN(linear_wide_forward_kernel)}, LNW_FWD_LDS(LINEAR_WIDE_MAX_LAG));
   if (st != BEAR_OK) return st;
@@ -96,58 +114,39 @@ static void launch_linear(bear_ws *ws, const bear_plan *plan, const uint64_t *km
   // BEAR_AMD_DETERMINISTIC: fixed-point gradient tables (kernels_linear.h, lin_fx); the kernel derives their scale from these bounds
   const bool det = bear_deterministic() && plan->count_bound[0] >= 1.0 && plan->count_bound[0] < 0x1p50;
   const lin_fx_bound gt_bound = {plan->count_bound[0], plan->count_bound[1], log(plan->count_bound[2] > 1.0 ? plan->count_bound[2] : 1.0)};
-  // (the update, if any, goes with the step's LAST launch: the one that completes the sums)
-#define LIN_LAUNCH_K(AR, PAIRED, DET, NGK, PV, NT, ACC)                                                                                     \
-  hipLaunchKernelGGL((dm_linear_plan_kernel<AR, PAIRED, DET, NGK>), dim3(grid_plan(ws, NT)), dim3(PLN_THREADS), sizeof(pln_lds_lin), s, kc, \
-                     mat, lag, prm, PV, lt, ws->partials, ws->lin_accum, (ACC) == 1 ? io2 : io, grad_mat, ACC, gt_bound,                    \
-                     ((ACC) == 1 || !two_launches) ? apply : NO_APPLY)
-  // the group count as a compile-time constant for the lags 12 / 13 (6 groups: BASELINE's k = 13), 14 / 15 (7) and 4 / 5 (2: the
-  // bundled table); every other lag takes the kernel that finds it at run time (distinct13: 0.847 -> 0.833 ms, 128 -> 97 registers)
-#define LIN_LAUNCH_D(AR, PAIRED, DET, PV, NT, ACC)                       \
-  do {                                                                   \
-    if (n_groups == 6) LIN_LAUNCH_K(AR, PAIRED, DET, 6, PV, NT, ACC);    \
-    else if (n_groups == 7) LIN_LAUNCH_K(AR, PAIRED, DET, 7, PV, NT, ACC); \
-    else if (n_groups == 2) LIN_LAUNCH_K(AR, PAIRED, DET, 2, PV, NT, ACC); \
-    else LIN_LAUNCH_K(AR, PAIRED, DET, 0, PV, NT, ACC);                  \
-  } while (0)
-#define LIN_LAUNCH(AR, PAIRED, PV, NT, ACC)                    \
-  do {                                                         \
-    if (det) LIN_LAUNCH_D(AR, PAIRED, true, PV, NT, ACC);      \
-    else LIN_LAUNCH_D(AR, PAIRED, false, PV, NT, ACC);         \
-  } while (0)
   bear_step_io io2 = io;      // the second launch of a step: its own stamp on the arrival word
   io2.epoch = ws_arrival(ws).epoch;
-  pln_view pv = plan_view(plan);
+  const pln_view pv = plan_view(plan);
   const bool two_launches = paired && plan->n_tiles_u != 0;
   // (BEAR_AMD_LINEAR_GENERIC=1: always the kernel that takes the group count at run time; tests compare the two)
-  const int n_groups = getenv("BEAR_AMD_LINEAR_GENERIC") ? 0 : lin_make_geom(lag).ng;
+  const int slot = getenv("BEAR_AMD_LINEAR_GENERIC") ? 0 : lin_slot(lin_make_geom(lag).ng);
+  // one launch over `view`; acc 0: the step's only launch, 2: the first of two, 1: the second (its own stamp; it adds to the
+  // first one's sums).  The update, if any, goes with the step's LAST launch: the one that completes the sums.
+  auto launch = [&](bool paired_form, const pln_view &view, int acc) {
+    hipLaunchKernelGGL(LIN_KERNELS[train_ar != 0][paired_form][det][slot], dim3(grid_plan(ws, view.n_tiles)), dim3(PLN_THREADS),
+                       sizeof(pln_lds_lin), s, kc, mat, lag, prm, view, lt, ws->partials, ws->lin_accum, acc == 1 ? io2 : io, grad_mat, acc,
+                       gt_bound, (acc == 1 || !two_launches) ? apply : NO_APPLY);
+  };
+  // a launch over some of the plan's tiles (their descriptors carry the tile's number in the plan: pln_view::subset)
+  auto subset_view = [&](const pln_tile *tiles, uint64_t n_tiles) {
+    pln_view v = pv;
+    v.tiles = tiles;
+    v.n_tiles = n_tiles;
+    v.subset = 1;
+    return v;
+  };
   if (!paired) {
-    if (train_ar) LIN_LAUNCH(true, false, pv, plan->n_tiles, 0);
-    else LIN_LAUNCH(false, false, pv, plan->n_tiles, 0);
+    launch(false, pv, 0);
     return;
   }
-  pln_view pp = pv;           // the paired tiles; the plan's global lists and histogram go with this launch
-  pp.tiles = plan->tiles_p;
-  pp.n_tiles = plan->n_tiles_p;
-  pp.subset = 1;
-  if (two_launches) {
-    if (train_ar) LIN_LAUNCH(true, true, pp, plan->n_tiles_p, 2);
-    else LIN_LAUNCH(false, true, pp, plan->n_tiles_p, 2);
-  } else if (train_ar) LIN_LAUNCH(true, true, pp, plan->n_tiles_p, 0);
-  else LIN_LAUNCH(false, true, pp, plan->n_tiles_p, 0);
-  if (plan->n_tiles_u == 0) return;
-  pln_view pu = pv;           // the rest: tiles only
-  pu.tiles = plan->tiles_u;
-  pu.n_tiles = plan->n_tiles_u;
-  pu.subset = 1;
+  // the paired tiles; the plan's global lists and histogram go with this launch
+  launch(true, subset_view(plan->tiles_p, plan->n_tiles_p), two_launches ? 2 : 0);
+  if (!two_launches) return;
+  pln_view pu = subset_view(plan->tiles_u, plan->n_tiles_u);           // the rest: tiles only
   pu.n_heavy_col = pu.n_heavy_row = pu.n_heavy_stop = 0;
   pu.hist = nullptr;
   pu.hist_big = nullptr;
-  if (train_ar) LIN_LAUNCH(true, false, pu, plan->n_tiles_u, 1);
-  else LIN_LAUNCH(false, false, pu, plan->n_tiles_u, 1);
-#undef LIN_LAUNCH
-#undef LIN_LAUNCH_D
-#undef LIN_LAUNCH_K
+  launch(false, pu, 1);
 }
 
 void plan_unpair(bear_plan *plan) {

@@ -6,8 +6,9 @@
 //
 // Contexts arrive as one 64-bit word each (bear_linear_index_u64: the k-mer as row numbers of the letter-group tables below),
 // 8 bytes per context instead of the 40-byte prior row, and nothing is written per context.  Per tile of the plan, two barriers:
-//   A  one thread per LIVE context (entries tid, tid + 896 of the plan's per-tile list of contexts that hold counts; ~30% of
-//      the rows of a count table hold none in the training column and are never looked at): logits from GROUP tables -- pairs
+//   A  one row thread per LIVE context (entries tid, tid + LIN_ROW_THREADS of the plan's per-tile list of contexts that hold counts,
+//      or entries 2 tid, 2 tid + 1 of its PAIRED form below; ~30% of the rows of a count table hold none in the training column and
+//      are never looked at; the block's last LIN_DMA_WAVES waves issue the tiles' DMA instead): logits from GROUP tables -- pairs
 //      of letters T[g][a, a'] = mat[2g][a] + mat[2g+1][a'] over the leading letters and one triple over the last three, rows of
 //      four doubles relative to the fifth letter's logit and in units of ln2/128 (6 table rows of 32 bytes for lag 13, read
 //      back to back: the group count is a template parameter) -- softmax; the row goes to LDS for the items AND stays in the
@@ -21,14 +22,17 @@
 //      not depend on the order) they share all but the last few letters.  What an LDS fp64 atomic costs is its INSTRUCTION
 //      (~20 clocks of CU time whatever the number of active lanes, scripts/dev/lds_atomic_lanes.hip), so lanes are mapped to
 //      (group, letter) pairs: one instruction adds the wave's sums (DPP reductions) to every group the wave shares, one adds
-//      the row-of-16 sums to the groups a row of 16 shares, and only what is left (sorted: the triple) takes one add per
-//      context and letter, into letter-major tables so that the 64 adds of an instruction spread over all banks.  (Round 1:
-//      28 + 8 atomic instructions per 64 contexts = 2.2 of its 3.85 ms; now 6.)
+//      the row-of-16 sums to the groups a row of 16 shares, one the quad's sum at the group where a row splits, and only what
+//      is left (sorted: the triple) takes one add per context and letter, into letter-major tables so that the 64 adds of an
+//      instruction spread over all banks.  (Round 1: 28 + 8 atomic instructions per 64 contexts = 2.2 of its 3.85 ms; the paired
+//      form: ~33 per 128 contexts, its levels read from the list)
 //   C of tile t and A of tile t + 1 are one phase (a thread only touches its own row slots).
+// The tables hold exp(logit) when no partial sum can overflow (products, no exponential per context: lin_build_tables).
 // The context terms -D(A, n) come from the plan's histogram (A = u + 5 eps: softmax rows are normalised).
-// After the last tile the group tables fold into d/d mat partials; the last block to finish sums the blocks in fixed order.
+// After the last tile a block folds its group tables into the launch's d/d mat accumulator (one device atomic per entry and
+// block); the last block to finish takes the sums.
 // Note: LDS floating-point atomics make the summation order inside a block run-dependent (last-bit jitter in
-// grad_mat); the ELBO and d/dh sums keep the fixed-order reduction of the other kernels.
+// grad_mat; DET: fixed-point tables, exact in any order); the ELBO and d/dh sums keep the fixed-order reduction of the other kernels.
 #pragma once
 #include "plan_common.h"
 #include <type_traits>
@@ -405,68 +409,20 @@ __device__ __forceinline__ double lin_exp_units(double d, const double *__restri
   return __builtin_ldexp(__builtin_fma(t, r * p, t), ki >> 7);
 }
 
-// softmax row of one context from the group tables (the fifth logit is the zero the tables are relative to)
-template <int NG, bool EXP>
-__device__ __forceinline__ void lin_row(const double *T, const double *exptab, unsigned long long cv, double (&f)[5]) {
-  constexpr int CH = LIN_CH;   // table rows in flight (registers: 8 per row)
-  if (EXP) {              // the tables hold exp(logit) (see the table build): a product per letter and no exponential
-    double e[4] = {1.0, 1.0, 1.0, 1.0};
-    unsigned long long cw = cv;
+// ---- the normalised row of five from four products of exponentials (the fifth is the 1 the tables are relative to) ...
+__device__ __forceinline__ void lin_softmax_of_exp(const double (&e)[4], double (&f)[5]) {
+  const double r = bear_rcp(1.0 + ((e[0] + e[1]) + (e[2] + e[3])));
 #pragma unroll
-    for (int g0 = 0; g0 < NG; g0 += CH) {
-      double2 lo[CH], hi[CH];
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-        if (g0 + j < NG) {
-          lin_table_row<NG>(T, cw, g0 + j, lo[j], hi[j]);
-        }
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-        if (g0 + j < NG) {
-          if (g0 + j == 0) {
-            e[0] = lo[j].x;
-            e[1] = lo[j].y;
-            e[2] = hi[j].x;
-            e[3] = hi[j].y;
-          } else {
-            e[0] *= lo[j].x;
-            e[1] *= lo[j].y;
-            e[2] *= hi[j].x;
-            e[3] *= hi[j].y;
-          }
-        }
-      // the next rows' addresses wait for this product: otherwise all the rows are fetched at once (48 registers at six groups)
-      if (g0 + CH < NG) asm("" : "+v"(cw) : "v"(e[0]));
-    }
-    const double r = bear_rcp(1.0 + ((e[0] + e[1]) + (e[2] + e[3])));
-#pragma unroll
-    for (int b = 0; b < 4; ++b) f[b] = e[b] * r;
-    f[4] = r;
-    return;
-  }
-  double z[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int g0 = 0; g0 < NG; g0 += CH) {
-    double2 lo[CH], hi[CH];
-#pragma unroll
-    for (int j = 0; j < CH; ++j)
-      if (g0 + j < NG) {
-        lin_table_row<NG>(T, cv, g0 + j, lo[j], hi[j]);
-      }
-#pragma unroll
-    for (int j = 0; j < CH; ++j)
-      if (g0 + j < NG) {
-        z[0] += lo[j].x;
-        z[1] += lo[j].y;
-        z[2] += hi[j].x;
-        z[3] += hi[j].y;
-      }
-  }
-  // Logits within +-600 (in natural units) for the whole wave -- anything a fitted model produces: no maximum to subtract and
-  // the fifth exponential is 1.  Otherwise the shifted form (a saturated softmax needs it).
-  const double za = __builtin_fmax(__builtin_fmax(__builtin_fabs(z[0]), __builtin_fabs(z[1])), __builtin_fmax(__builtin_fabs(z[2]), __builtin_fabs(z[3])));
+  for (int b = 0; b < 4; ++b) f[b] = e[b] * r;
+  f[4] = r;
+}
+// ... and from four summed logits in units of ln2 / 128.  plain: every logit of the WAVE is within +-600 in natural units (the
+// caller's ballot; anything a fitted model produces): no maximum to subtract and the fifth exponential is 1.  Otherwise the
+// shifted form (a saturated softmax needs it).
+#define LIN_PLAIN_LOGIT_MAX (600.0 * LIN_EXP_UNIT)
+__device__ __forceinline__ void lin_softmax_of_logits(const double (&z)[4], bool plain, const double *exptab, double (&f)[5]) {
   double s;
-  if (__builtin_amdgcn_ballot_w64(!(za < 600.0 * LIN_EXP_UNIT)) == 0ull) {
+  if (plain) {
     s = 1.0;
     f[4] = 1.0;
 #pragma unroll
@@ -486,6 +442,50 @@ __device__ __forceinline__ void lin_row(const double *T, const double *exptab, u
   const double r = bear_rcp(s);
 #pragma unroll
   for (int b = 0; b < 5; ++b) f[b] *= r;
+}
+
+// softmax row of one context from the group tables
+template <int NG, bool EXP>
+__device__ __forceinline__ void lin_row(const double *T, const double *exptab, unsigned long long cv, double (&f)[5]) {
+  constexpr int CH = LIN_CH;   // table rows in flight (registers: 8 per row)
+  // EXP: the tables hold exp(logit) (see the table build): a product per letter and no exponential; otherwise sums of logits
+  double e[4] = {EXP ? 1.0 : 0.0, EXP ? 1.0 : 0.0, EXP ? 1.0 : 0.0, EXP ? 1.0 : 0.0};
+  unsigned long long cw = cv;
+#pragma unroll
+  for (int g0 = 0; g0 < NG; g0 += CH) {
+    double2 lo[CH], hi[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j)
+      if (g0 + j < NG) lin_table_row<NG>(T, cw, g0 + j, lo[j], hi[j]);
+#pragma unroll
+    for (int j = 0; j < CH; ++j)
+      if (g0 + j < NG) {
+        if (EXP && g0 + j == 0) {
+          e[0] = lo[j].x;
+          e[1] = lo[j].y;
+          e[2] = hi[j].x;
+          e[3] = hi[j].y;
+        } else if (EXP) {
+          e[0] *= lo[j].x;
+          e[1] *= lo[j].y;
+          e[2] *= hi[j].x;
+          e[3] *= hi[j].y;
+        } else {
+          e[0] += lo[j].x;
+          e[1] += lo[j].y;
+          e[2] += hi[j].x;
+          e[3] += hi[j].y;
+        }
+      }
+    // the next rows' addresses wait for this product: otherwise all the rows are fetched at once (48 registers at six groups)
+    if (EXP && g0 + CH < NG) asm("" : "+v"(cw) : "v"(e[0]));
+  }
+  if (EXP) {
+    lin_softmax_of_exp(e, f);
+    return;
+  }
+  const double za = __builtin_fmax(__builtin_fmax(__builtin_fabs(e[0]), __builtin_fabs(e[1])), __builtin_fmax(__builtin_fabs(e[2]), __builtin_fabs(e[3])));
+  lin_softmax_of_logits(e, __builtin_amdgcn_ballot_w64(!(za < LIN_PLAIN_LOGIT_MAX)) == 0ull, exptab, f);
 }
 
 // Two contexts that share every pair group (a thread's two entries of the PAIRED list): the pair rows are read and combined once,
@@ -535,55 +535,20 @@ __device__ __forceinline__ void lin_row2(const double *T, const double *exptab, 
   if (EXP) {
     const double x0[4] = {e[0] * a0.x, e[1] * a0.y, e[2] * b0.x, e[3] * b0.y};
     const double x1[4] = {e[0] * a1.x, e[1] * a1.y, e[2] * b1.x, e[3] * b1.y};
-    const double r0 = bear_rcp(1.0 + ((x0[0] + x0[1]) + (x0[2] + x0[3])));
-    const double r1 = bear_rcp(1.0 + ((x1[0] + x1[1]) + (x1[2] + x1[3])));
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      f0[b] = x0[b] * r0;
-      f1[b] = x1[b] * r1;
-    }
-    f0[4] = r0;
-    f1[4] = r1;
+    lin_softmax_of_exp(x0, f0);
+    lin_softmax_of_exp(x1, f1);
     return;
   }
-  double z[2][4] = {{e[0] + a0.x, e[1] + a0.y, e[2] + b0.x, e[3] + b0.y}, {e[0] + a1.x, e[1] + a1.y, e[2] + b1.x, e[3] + b1.y}};
+  const double z0[4] = {e[0] + a0.x, e[1] + a0.y, e[2] + b0.x, e[3] + b0.y};
+  const double z1[4] = {e[0] + a1.x, e[1] + a1.y, e[2] + b1.x, e[3] + b1.y};
   double za = 0.0;
 #pragma unroll
-  for (int k = 0; k < 2; ++k)
+  for (int b = 0; b < 4; ++b) za = __builtin_fmax(za, __builtin_fabs(z0[b]));
 #pragma unroll
-    for (int b = 0; b < 4; ++b) za = __builtin_fmax(za, __builtin_fabs(z[k][b]));
-  const bool plain = __builtin_amdgcn_ballot_w64(!(za < 600.0 * LIN_EXP_UNIT)) == 0ull;      // as in lin_row, for both contexts
-  double fo[2][5];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    double (&f)[5] = fo[k];
-    double sum;
-    if (plain) {
-      sum = 1.0;
-      f[4] = 1.0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        f[b] = lin_exp_units(z[k][b], exptab);
-        sum += f[b];
-      }
-    } else {
-      const double m = __builtin_fmax(__builtin_fmax(__builtin_fmax(z[k][0], z[k][1]), __builtin_fmax(z[k][2], z[k][3])), 0.0);
-      sum = 0.0;
-#pragma unroll
-      for (int b = 0; b < 5; ++b) {
-        f[b] = lin_exp_units(__builtin_fmax((b < 4 ? z[k][b] : 0.0) - m, -700.0 * LIN_EXP_UNIT), exptab);
-        sum += f[b];
-      }
-    }
-    const double r = bear_rcp(sum);
-#pragma unroll
-    for (int b = 0; b < 5; ++b) f[b] *= r;
-  }
-#pragma unroll
-  for (int b = 0; b < 5; ++b) {
-    f0[b] = fo[0][b];
-    f1[b] = fo[1][b];
-  }
+  for (int b = 0; b < 4; ++b) za = __builtin_fmax(za, __builtin_fabs(z1[b]));
+  const bool plain = __builtin_amdgcn_ballot_w64(!(za < LIN_PLAIN_LOGIT_MAX)) == 0ull;      // one vote for both contexts
+  lin_softmax_of_logits(z0, plain, exptab, f0);
+  lin_softmax_of_logits(z1, plain, exptab, f1);
 }
 
 // ---- BEAR_AMD_DETERMINISTIC: the gradient tables in 64-bit FIXED POINT.  LDS floating-point atomics from several waves land in
@@ -621,6 +586,18 @@ template <> __device__ __forceinline__ lin_fx lin_unbits<lin_fx>(long long q) { 
 // one add into a gradient table (the table's words hold doubles or fixed-point integers, one kind per launch)
 __device__ __forceinline__ void lin_gt_add(double *p, double v) { atomicAdd(p, v); }
 __device__ __forceinline__ void lin_gt_add(double *p, lin_fx v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
+// what a launch adds into them, and a gradient as such a value (DET: fixed point at gt_scale, see above)
+template <bool DET> using lin_gt_t = typename std::conditional<DET, lin_fx, double>::type;
+template <bool DET>
+__device__ __forceinline__ lin_gt_t<DET> lin_gt_value(double v, double gt_scale) {
+  if constexpr (DET) return lin_to_fixed(v, gt_scale);
+  else return v;
+}
+template <bool DET>
+__device__ __forceinline__ void lin_gt_values(const double (&g)[4], double gt_scale, lin_gt_t<DET> (&out)[4]) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) out[b] = lin_gt_value<DET>(g[b], gt_scale);
+}
 
 // ---- cross-lane sums on DPP (a double = two 32-bit moves + one add per step; the generic __shfl_xor of a double costs
 // two ds_bpermute round trips: measured 0.76 ms per 1e8 contexts for the 24 of them a wave needs here)
@@ -676,12 +653,6 @@ __device__ __forceinline__ unsigned long long lin_first_lane(unsigned long long 
 // The waves that issue a tile's DMA (the last LIN_DMA_WAVES of the block) take no rows in phases A / C: with HBM busy every DMA
 // instruction parks its wave for ~700 clocks, a tile is ~25 of them, and a wave that also had its share of rows reached the
 // phase barrier ~4000 clocks (a fifth of a tile's time) after the others.  Rows go to the first LIN_ROW_THREADS threads.
-#ifndef LIN_DMA_WAVES
-#define LIN_DMA_WAVES 2
-#endif
-#ifndef LIN_ROW_THREADS
-#define LIN_ROW_THREADS (PLN_THREADS - 64 * LIN_DMA_WAVES)
-#endif
 constexpr int LIN_RPT = (PLN_RMAX + LIN_ROW_THREADS - 1) / LIN_ROW_THREADS;   // contexts of a tile per row thread
 
 // ---- phase A over the tile's live contexts (entry tid + 1024 k of the plan's list): softmax rows into fA (kept until phase C
@@ -737,6 +708,12 @@ __device__ __forceinline__ uint32_t lin_phase_a_paired(pln_lds_lin &S, const lin
   return rows;
 }
 
+// the index word of lane `last` (wave-uniform): what the lanes beyond the end of a list take, so that they never break a run
+__device__ __forceinline__ unsigned long long lin_word_of_lane(unsigned long long v, uint32_t last) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)last), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)last);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // ---- the gradient of 64 consecutive contexts (one per lane: index word cv, g_b = d L / d logit_b for b < 4, nz = the lane has
 // anything to add; lanes beyond the end of a list repeat its last context's word with g = 0) into the letter-major gradient tables
 // GT.  One LDS fp64 atomic wave-instruction costs ~20 clocks of CU time whatever the number of active lanes (measured,
@@ -745,8 +722,7 @@ __device__ __forceinline__ uint32_t lin_phase_a_paired(pln_lds_lin &S, const lin
 //   2. up to four groups that a lane's row of 16 shares: lane (slot, b) of each row adds the row's sum   (one instruction)
 //   3. what is left (in a sorted table: the triple of the last letters): one add per context and letter (four per group)
 template <int NG, typename T = double>
-__device__ __forceinline__ void lin_scatter_grad(double *GT, unsigned long long cv, const T (&g)[4], bool nz, uint32_t lane,
-                                                 double (&acc)[2]) {
+__device__ __forceinline__ void lin_scatter_grad(double *GT, unsigned long long cv, const T (&g)[4], bool nz, uint32_t lane) {
   const T tq = lin_quad_letter_sum<T>(g, lane), th = lin_row16_sum<T>(tq), tw = lin_wave_sum<T>(th);   // of letter lin_letter(lane)
   const uint32_t bl = lin_letter(lane);
   // How many LEADING groups does my row of 16 share (l_row), how many the whole wave (l_wave)?  In a sorted table the shared
@@ -829,7 +805,7 @@ __device__ __forceinline__ void lin_scatter_grad(double *GT, unsigned long long 
 // ---- phase C for the thread's rows: g_b = w_b - f_b s into the gradient tables (lin_scatter_grad), whole waves at a time.
 template <int NG, bool DET>
 __device__ __forceinline__ void lin_phase_c(pln_lds_lin &S, uint32_t n_live, uint32_t tid, uint32_t lane_in, const double (&fA)[LIN_RPT][5],
-                                            const unsigned long long (&cA)[LIN_RPT], uint32_t rowA, double (&acc)[2], double gt_scale) {
+                                            const unsigned long long (&cA)[LIN_RPT], uint32_t rowA, double gt_scale) {
   uint32_t lane = lane_in;
 #pragma unroll
   for (int k = 0; k < LIN_RPT; ++k) {
@@ -856,15 +832,12 @@ __device__ __forceinline__ void lin_phase_c(pln_lds_lin &S, uint32_t n_live, uin
     const uint32_t last = n_live - j0 < 64u ? n_live - j0 - 1u : 63u;   // wave-uniform
     unsigned long long cv = code;
     if (last != 63u) {
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)code, (int)last), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(code >> 32), (int)last);
-      if (!live) cv = ((unsigned long long)hi << 32) | lo;
+      const unsigned long long end = lin_word_of_lane(code, last);
+      if (!live) cv = end;
     }
-    if (DET) {
-      const lin_fx gi[4] = {lin_to_fixed(g[0], gt_scale), lin_to_fixed(g[1], gt_scale), lin_to_fixed(g[2], gt_scale), lin_to_fixed(g[3], gt_scale)};
-      lin_scatter_grad<NG, lin_fx>(S.GT, cv, gi, nz, lane, acc);
-    } else {
-      lin_scatter_grad<NG, double>(S.GT, cv, g, nz, lane, acc);
-    }
+    lin_gt_t<DET> gv[4];
+    lin_gt_values<DET>(g, gt_scale, gv);
+    lin_scatter_grad<NG, lin_gt_t<DET>>(S.GT, cv, gv, nz, lane);
   }
 }
 
@@ -1004,8 +977,8 @@ __device__ __forceinline__ void lin_phase_c_paired(pln_lds_lin &S, uint32_t n_en
   const uint32_t last = n_pairs < 64u ? n_pairs - 1u : 63u;
   unsigned long long c0 = cA[0], c1 = cA[1];
   if (last != 63u) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cA[0], (int)last), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cA[0] >> 32), (int)last);
-    if (lane > last) c0 = c1 = ((unsigned long long)hi << 32) | lo;
+    const unsigned long long end = lin_word_of_lane(cA[0], last);
+    if (lane > last) c0 = c1 = end;
   }
   if (DET) {
     lin_fx gi[2][4];
@@ -1250,6 +1223,27 @@ __device__ unsigned long long lin_pe_stamps[12];
 #define LIN_STAMP(k)
 #define LIN_PE(k)
 #endif
+// ---- an item's terms (fb: the softmax entry of its cell, cnt: its count; D, P at x = fb u + eps, BEAR form only): adds its part
+// of sum LL (AR form: cnt log(fb + eps)) and of d/dh to acc and returns q = d LL / d f at the cell
+template <bool AR>
+__device__ __forceinline__ double lin_item_terms(double fb, double cnt, double x, double D, double P, double u, double eps,
+                                                 const double2 *logtab, double (&acc)[2]) {
+  if (AR) {
+    const double pp = fb + eps;
+    acc[0] = __builtin_fma(cnt, bear_log_tab(pp, logtab), acc[0]);
+    return cnt * bear_rcp(pp);
+  }
+  acc[0] += D;
+  acc[1] = __builtin_fma(eps - x, P, acc[1]);
+  return u * P;
+}
+// ... and the context term of a total n too large for the plan's histograms (A = u + 5 eps)
+__device__ __forceinline__ void lin_context_term(double n, double u, double eps5, const double2 *logtab, double (&acc)[2]) {
+  const bear_dp o = srt_general_fast(u + eps5, n, logtab);
+  acc[0] -= o.D;
+  acc[1] = __builtin_fma(u, o.P, acc[1]);
+}
+
 // DET (BEAR_AMD_DETERMINISTIC): the gradient tables hold fixed-point integers, gt_scale = 2^62 / bound (see lin_fx above)
 // NGK: the number of letter groups as a compile-time constant (0: taken from `lag` at run time through LIN_FOR_NG).  With it a
 // launch's kernel holds ONE form of phases A and C instead of ten behind a switch inside the tile loop: a tenth of the code (the
@@ -1385,7 +1379,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_linear_plan_kernel(
     if (PAIRED) {
       LIN_FOR_NGK(ng, (lin_phase_c_paired<NG, DET>(S, n_live, tid, lane, fA, cA, rowA, levA, gt_scale)))
     } else {
-      LIN_FOR_NGK(ng, (lin_phase_c<NG, DET>(S, n_live, tid, lane, fA, cA, rowA, acc, gt_scale)))
+      LIN_FOR_NGK(ng, (lin_phase_c<NG, DET>(S, n_live, tid, lane, fA, cA, rowA, gt_scale)))
     }
   };
 
@@ -1414,16 +1408,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_linear_plan_kernel(
     // ---- B: items (tickets, dearest first): ELBO / d/dh, and -w = -f q into the item's own cell
     auto item = [&](uint32_t off, double D, double P, double x, double cnt) {
       const double fb = S.pri[off];
-      double q;
-      if (AR) {
-        const double pp = fb + eps;
-        acc[0] = __builtin_fma(cnt, bear_log_tab(pp, S.logtab), acc[0]);
-        q = cnt * bear_rcp(pp);
-      } else {
-        acc[0] += D;
-        acc[1] = __builtin_fma(eps - x, P, acc[1]);
-        q = u * P;
-      }
+      const double q = lin_item_terms<AR>(fb, cnt, x, D, P, u, eps, S.logtab, acc);
       if (cnt != 0.0) S.pri[off] = -(fb * q);
     };
     const uint32_t n_hcu = (hc + 63u) >> 6, n_hru = AR ? 0u : (hr + 63u) >> 6, n_units = (n_light + 63u) >> 6;
@@ -1447,11 +1432,7 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_linear_plan_kernel(
         const double n = i < hr ? reinterpret_cast<const double *>(B.blk + L.hn)[i] : 0.0;
         const bool mine = i < hr && !pln_in_big_hist(pv, n);
         if (__builtin_amdgcn_ballot_w64(mine)) {
-          if (mine) {
-            const bear_dp o = srt_general_fast(u + eps5, n, S.logtab);
-            acc[0] -= o.D;
-            acc[1] = __builtin_fma(u, o.P, acc[1]);
-          }
+          if (mine) lin_context_term(n, u, eps5, S.logtab, acc);
         }
         continue;
       }
@@ -1516,36 +1497,24 @@ __global__ __launch_bounds__(PLN_THREADS, 4) void dm_linear_plan_kernel(
     } else {
       LIN_FOR_NGK(ng, (lin_row<NG, false>(S.T, S.exptab, cv, f)))
     }
-    double q;
-    if (AR) {
-      const double pp = f[b] + eps;
-      acc[0] = __builtin_fma((double)h.c, bear_log_tab(pp, S.logtab), acc[0]);
-      q = (double)h.c * bear_rcp(pp);
-    } else {
-      const double x = __builtin_fma(f[b], u, eps);
-      const bear_dp o = srt_general_fast(x, (double)h.c, S.logtab);
-      acc[0] += o.D;
-      acc[1] = __builtin_fma(eps - x, o.P, acc[1]);
-      q = u * o.P;
-    }
-    const double w = f[b] * q;
+    const double x = __builtin_fma(f[b], u, eps);
+    bear_dp o = {0.0, 0.0};
+    if (!AR) o = srt_general_fast(x, (double)h.c, S.logtab);
+    const double w = f[b] * lin_item_terms<AR>(f[b], (double)h.c, x, o.D, o.P, u, eps, S.logtab, acc);
     for (int g = 0; g < ng; ++g) {
       double *gt = &S.GT[lin_off_any(cv, (uint32_t)g, (uint32_t)ng) >> 2];
 #pragma unroll
       for (int bb = 0; bb < 4; ++bb) {
         // (an overflow item is ONE cell of its context: the context's g is the sum of these per-item parts, each bounded by its count)
         const double gv = (bb == (int)b ? w : 0.0) - f[bb] * w;
-        if (DET) lin_gt_add(&gt[bb * LIN_GT_PLANE], lin_to_fixed(gv, gt_scale));
-        else lin_gt_add(&gt[bb * LIN_GT_PLANE], gv);
+        lin_gt_add(&gt[bb * LIN_GT_PLANE], lin_gt_value<DET>(gv, gt_scale));
       }
     }
   }
   for (uint64_t i = gtid; !AR && i < pv.n_heavy_row; i += gsz) {
     const double n = pv.heavy_row[i].n;
     if (pln_in_big_hist(pv, n)) continue;
-    const bear_dp o = srt_general_fast(u + eps5, n, S.logtab);
-    acc[0] -= o.D;
-    acc[1] = __builtin_fma(u, o.P, acc[1]);
+    lin_context_term(n, u, eps5, S.logtab, acc);
   }
   if (!AR) pln_big_totals(pv, u + eps5, u, gtid, gsz, S.logtab, acc[0], acc[1]);      // totals in (SRT_CL, PLN_NBIG]: the plan's histogram
   if (!AR && pv.hist && blockIdx.x == 0 && tid < SRT_CL) {  // context terms of the small totals: the plan's histogram

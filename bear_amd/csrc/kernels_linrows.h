@@ -68,7 +68,6 @@ __global__ __launch_bounds__(LNR_THREADS) void linear_rows_backward_kernel(const
   const int ng = G.ng;
   for (int k = tid; k < LIN_TAB_DOUBLES; k += LNR_THREADS) S.GT[k] = 0.0;
   __syncthreads();
-  double unused[2] = {0.0, 0.0};
   const uint64_t n_chunks = (n + 63u) >> 6;
   for (uint64_t c = (uint64_t)blockIdx.x * LNR_WAVES + wave; c < n_chunks; c += (uint64_t)gridDim.x * LNR_WAVES) {
     const uint64_t i0 = c << 6;
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(LNR_THREADS) void linear_rows_backward_kernel(const
     for (int b = 0; b < 4; ++b) g[b] = in ? f[b] * (q[b] - s) : 0.0;      // softmax backward: d L / d logit_b
     const bool nz = (g[0] != 0.0) | (g[1] != 0.0) | (g[2] != 0.0) | (g[3] != 0.0);
     if (__builtin_amdgcn_ballot_w64(nz) == 0ull) continue;
-    LIN_FOR_NG(ng, (lin_scatter_grad<NG>(S.GT, cv, g, nz, lane, unused)))
+    LIN_FOR_NG(ng, (lin_scatter_grad<NG>(S.GT, cv, g, nz, lane)))
   }
   __syncthreads();
   lin_fold_tables(S.GT, G, (int)tid, LNR_THREADS, grad_partials + (size_t)blockIdx.x * LIN_MAX_GRAD);

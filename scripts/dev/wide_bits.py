@@ -1,5 +1,5 @@
-"""Developer: the bits of every width-taking entry and of the width-5 convolutional entries on seeded inputs, for holding one build of
-the library against another.
+"""Developer: the bits of every width-taking entry, of the width-5 convolutional entries and of the width-5 fused linear step on seeded
+inputs, for holding one build of the library against another.
     BEAR_AMD_LIB=before/libbear_hip.so python scripts/dev/wide_bits.py > before.json
     BEAR_AMD_LIB=bear_amd/libbear_hip.so python scripts/dev/wide_bits.py > after.json        # then: cmp before.json after.json
 One SHA-256 per output buffer, as one JSON object (case -> digest).  These kernels use no floating-point atomics and the library is
@@ -15,7 +15,20 @@ one in k-mer order with duplicate contexts per shape, so that shared and carried
 and the dT1 rows use no atomics and are hashed in either build.  The part kernel and the 64-context kernel add to their block's
 gradient image with LDS floating-point atomics from several waves: their parameter gradients are hashed in libbear_hip_det.so only
 (one wave per block); so is `packed` of the step over levels and tables, the head-only backward kernel's gradients included -- that
-kernel has no atomics itself, but the part-kernel launches of the same step add to the same partial rows."""
+kernel has no atomics itself, but the part-kernel launches of the same step add to the same partial rows.
+
+The width-5 fused linear step (kernels_linear.h, `dm_linear`): sizes of one context, 3 tiles + 77 and a second tile for every block
+(a tile is 1664 contexts, one block per CU); lags 1 and 3 (the triple alone), 5, 13, 14 (the specialised group counts), 9 and 21
+(run-time count; 21: the last arm of the switch), each once more with BEAR_AMD_LINEAR_GENERIC=1; three tables of contexts (`codes5`
+in k-mer order with copies of a k-mer, `codes5_prefixes`, `codes5` in random order, where pairing declines), each with its plain
+and its paired lists, BEAR and AR form; parameters that give tables of exponentials, tables of logits and a saturated softmax.  The
+section runs with BEAR_AMD_DETERMINISTIC=1 (set inside it only, restored after): the gradient tables are then fixed-point and
+`grad_mat` is the same bits in either library whatever the order of the adds -- hashed in both; `out` (sum LL, d/dh) is summed in
+the order the work units were drawn in libbear_hip.so and is hashed in libbear_hip_det.so only.  Without the switch d/d mat goes
+through LDS floating-point atomics from several waves and is not hashable in either library: those instantiations are held to the
+oracle by the parity tests.  A tile denser than its in-tile lists (the loop over the plan's overflow items) comes from the parity
+tests' `mixed_heavy_table`, in libbear_hip_det.so only: the other library's plan of such a table differs from build to build of
+the plan in which cells overflow, and with it the fixed-point roundings."""
 import hashlib
 import json
 import os
@@ -40,6 +53,8 @@ CNN_BWD_TILE, CNN_BWD_PER_CU = 64, 1
 # the width-5 convolutional kernels (kernels_cnn.h, bear_cnn.hip): waves per CU of each capped grid and contexts per wave tile
 CNN5_FWD_WAVES_PER_CU, CNN5_FWD_TILE = 16 * 4, 64
 CNN5_PARTS_WAVES_PER_CU, CNN5_HEAD_WAVES_PER_CU, CNN5_PARTS_TILE = 8, 12, 32
+# the width-5 fused linear step (kernels_plan.h: PLN_RMAX contexts per tile, one block per CU)
+LINEAR5_TILE, LINEAR5_PER_CU = 1664, 1
 
 
 def beyond(cus, per_cu, tile):
@@ -238,12 +253,120 @@ def cnn5_kernels(cus, det):
         cnn5_step(lag, fw, n, det)
 
 
+def codes5_prefixes(rng, n, lag):
+    """K-mer order; the first 70 % of the rows on a few prefixes (runs of many contexts that share all but the last three letters),
+    one row in 33 of them random; the rest random behind a first letter of their own, so that at the long lags the table ends in a
+    stretch of runs of one context, whose tiles keep their plain lists (the construction of test_fused_linear_head_paired_contexts,
+    plus that stretch)."""
+    lead = max(lag - 3, 0)
+    c = rng.integers(0, 4, (n, lag)).astype(np.int8)
+    head = n - (3 * n) // 10
+    pre = rng.integers(0, 3, (max(1, n // 40), lead)).astype(np.int8)
+    keep = rng.random(head) >= 1.0 / 33.0
+    c[:head][keep, :lead] = pre[rng.integers(0, pre.shape[0], int(keep.sum()))]
+    if lead:
+        c[:head, 0] = np.minimum(c[:head, 0], 2)
+        c[head:, 0] = 3
+    c[rng.random(n) < 0.02, 0] = 4                       # '[' at a sequence start
+    c[rng.random((n, lag)) < 0.01] = -1                  # unknown letters
+    key = np.zeros(n, np.int64)
+    for l in range(lag):
+        key = key * 6 + np.where(c[:, l] >= 0, c[:, l], 5)
+    return kernels.pack_kmers(torch.from_numpy(np.ascontiguousarray(c[np.argsort(key, kind="stable")])).cuda())
+
+
+def counts5(rng, n):
+    """Four contexts in five with counts, in one cell or two: tiles of the full 1664 rows (a denser table is cut into shorter
+    tiles by its items) whose lists of contexts with counts are long enough that a stretch of runs of one context does not fit
+    the paired form."""
+    c = np.zeros((n, 5), np.uint32)
+    rows = np.arange(n)
+    live = rng.random(n) < 0.8
+    c[rows[live], rng.integers(0, 5, n)[live]] = rng.poisson(6.0, int(live.sum())) + 1
+    two = live & (rng.random(n) < 0.15)
+    c[rows[two], rng.integers(0, 5, n)[two]] += rng.poisson(3.0, int(two.sum())).astype(np.uint32)
+    if n == 1:
+        c[0, 1] = 3
+    return torch.from_numpy(c.view(np.int32)).cuda()
+
+
+def linear5_mats(rng, lag):
+    """Parameters for tables of exponentials, for tables of logits (plain softmax) and for a saturated softmax (the shifted form)."""
+    mats = {}
+    for scale in (0.4, 150.0, 3000.0):
+        m = rng.normal(size=(lag, 5, 5)) * scale
+        if scale > 1:
+            m[0, 0] *= 0.001                             # contexts starting with letter 0 keep small logits from that position
+        mats["m%g" % scale] = torch.from_numpy(m).cuda()
+    return mats
+
+
+def linear5_steps(name, plan, idx, lag, mats, det):
+    """The step over the plan's plain lists, then -- where pairing takes -- over its paired lists."""
+    for form in ("plain", "paired"):
+        if form == "paired":
+            took = plan.pair_contexts(idx, lag)
+            n_paired, n_plain = plan.pair_info()
+            assert n_paired + n_plain == len(plan.tiles()[0]) and (n_paired >= 1) == took
+            OUT["dm_linear/%s/shape" % name] = "tiles paired %d plain %d" % (n_paired, n_plain) if took else "pairing declined"
+            if not took:
+                return
+        for generic in (0, 1):
+            if generic:
+                os.environ["BEAR_AMD_LINEAR_GENERIC"] = "1"
+            try:
+                for ar in (False, True):
+                    for mname, mat in mats.items():
+                        out, grad = kernels.dm_linear(plan, idx, mat, 0.3 if ar else 0.2, train_ar=ar)
+                        case = "dm_linear/%s/%s/generic%d/ar%d/%s" % (name, form, generic, ar, mname)
+                        put(case + "/grad_mat", grad)
+                        if det:
+                            put(case + "/out", out)
+            finally:
+                os.environ.pop("BEAR_AMD_LINEAR_GENERIC", None)
+
+
+def linear5_kernels(cus, det):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
+    from util import mixed_heavy_table                   # (NumPy only)
+    before = os.environ.get("BEAR_AMD_DETERMINISTIC")
+    os.environ["BEAR_AMD_DETERMINISTIC"] = "1"
+    try:
+        for n in (1, 3 * LINEAR5_TILE + 77, beyond(cus, LINEAR5_PER_CU, LINEAR5_TILE)):
+            for lag in (1, 3, 5, 9, 13, 14, 21):
+                rng = np.random.default_rng(100 * n + lag)
+                c = counts5(rng, n)
+                mats = linear5_mats(rng, lag)
+                for table, packed in (("twins", codes5(rng, n, lag, True)), ("prefixes", codes5_prefixes(rng, n, lag)),
+                                      ("random", codes5(rng, n, lag, False))):
+                    linear5_steps("n%d/lag%d/%s" % (n, lag, table), kernels.Plan(c, 5), kernels.linear_index(packed, lag), lag, mats, det)
+        # tiles denser than their in-tile lists: the plan's overflow items and contexts.  WHICH large-count cells of such a tile
+        # stay inside it is decided by atomic counters when libbear_hip.so builds the plan, and an overflow item's part of its
+        # context's gradient is rounded to fixed point on its own: the same bits from plan to plan in libbear_hip_det.so only
+        if not det:
+            return
+        heavy = mixed_heavy_table()[0]
+        c = torch.from_numpy(np.ascontiguousarray(heavy).view(np.int32)).cuda()
+        for lag in (5, 13):
+            rng = np.random.default_rng(7000 + lag)
+            mats = linear5_mats(rng, lag)
+            packed = codes5(rng, c.shape[0], lag, True)
+            linear5_steps("mixed_heavy/lag%d" % lag, kernels.Plan(c, 5), kernels.linear_index(packed, lag), lag, mats, det)
+    finally:
+        if before is None:
+            os.environ.pop("BEAR_AMD_DETERMINISTIC", None)
+        else:
+            os.environ["BEAR_AMD_DETERMINISTIC"] = before
+
+
 if __name__ == "__main__":
     from bear_amd import _lib
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     row_kernels(cus)
     linear_kernels(cus)
     cnn_kernels(cus)
-    cnn5_kernels(cus, det=os.path.basename(_lib.LIB_PATH) == "libbear_hip_det.so")
+    det = os.path.basename(_lib.LIB_PATH) == "libbear_hip_det.so"
+    cnn5_kernels(cus, det)
+    linear5_kernels(cus, det)
     torch.cuda.synchronize()
     print(json.dumps(OUT, indent=0, sort_keys=True))
