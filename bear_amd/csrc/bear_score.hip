@@ -1,0 +1,87 @@
+// bear_score.hip -- scoring on the device: the three entries between the device count tables and the samplers' tables
+// (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
+// of a sampled table's rows over the transitions of every segment.  The only unit that includes -- and so emits -- kernels_score.h.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "bear_dev.h"
+#include "bear_release_guard.h"
+#include "kernels_score.h"
+
+namespace {
+bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
+bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+// blocks of a grid-stride launch over `work` items, `per_block` to a block
+unsigned scr_grid(uint64_t work, uint64_t per_block) {
+  const uint64_t g = (work + per_block - 1) / per_block;
+  return (unsigned)(g < 1 ? 1 : (g > (1u << 20) ? (1u << 20) : g));
+}
+}  // namespace
+
+extern "C" {
+
+int bear_score_transitions_u64(const uint8_t *text, const uint64_t *seg, uint64_t n_sym, uint64_t n_seg, int lag, int width,
+                               const uint8_t *rank, uint64_t *keys, uint8_t *letters, void *stream) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  if (lag < 1 || lag > (width == 5 ? 21 : 12) || !rank) return BEAR_ERR_INVALID_ARG;
+  const int bits = width == 5 ? 3 : 5;
+  scr_ranks R;
+  memset(R.rank, 0xFF, sizeof(R.rank));
+  for (int c = 0; c <= width; ++c) {
+    if (rank[c] != 0xFF && rank[c] >= (1u << bits)) return BEAR_ERR_INVALID_ARG;
+    R.rank[c] = rank[c];
+  }
+  if (n_sym == 0) return BEAR_OK;
+  if (!text || !keys || !letters || misaligned8(keys) || (n_seg && (!seg || misaligned8(seg)))) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(scr_grid(n_sym, SCR_THREADS)), block(SCR_THREADS);
+  if (width == 5)
+    hipLaunchKernelGGL(score_transitions_kernel<3>, grid, block, 0, s, text, seg, n_sym, n_seg, lag, 5u, R, keys, letters);
+  else
+    hipLaunchKernelGGL(score_transitions_kernel<5>, grid, block, 0, s, text, seg, n_sym, n_seg, lag, 21u, R, keys, letters);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_kmer_find_u64(const uint64_t *table, uint64_t n_table, const uint64_t *query, uint64_t n_query, uint32_t *rows,
+                       void *stream) {
+  if (n_table >= SCR_ABSENT) return BEAR_ERR_INVALID_ARG;      // a row is a uint32, and the last one says "absent"
+  if (n_query == 0) return BEAR_OK;
+  if (!query || !rows || misaligned8(query) || misaligned4(rows) || (n_table && (!table || misaligned8(table))))
+    return BEAR_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(kmer_find_kernel, dim3(scr_grid(n_query, SCR_THREADS)), dim3(SCR_THREADS), 0, static_cast<hipStream_t>(stream),
+                     table, n_table, query, n_query, rows);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_values, const uint32_t *rows, const uint8_t *letters,
+                       uint64_t n_t, const uint64_t *seg, uint64_t n_seg, double *scores, void *stream) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  if (n_rows >= SCR_ABSENT || n_values > 65535ull * SCR_WAVE) return BEAR_ERR_INVALID_ARG;
+  if (n_seg == 0 || n_values == 0) return BEAR_OK;
+  if (!seg || !scores || misaligned8(seg) || misaligned8(scores)) return BEAR_ERR_INVALID_ARG;
+  if (n_t && (!rows || !letters || misaligned4(rows))) return BEAR_ERR_INVALID_ARG;
+  if (n_t && n_rows && (!lp || misaligned8(lp))) return BEAR_ERR_INVALID_ARG;
+  if (n_seg > (~0ull) / n_values / sizeof(double)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned tiles = (unsigned)((n_values + SCR_WAVE - 1) / SCR_WAVE);
+  // only a text of more than SCR_CHUNK transitions can hold a long segment: two partial rows per SCR_CHUNK positions of the text
+  dev_buf<double> partials;
+  if (n_t > SCR_CHUNK) {
+    const uint64_t n_blocks = (n_t + SCR_CHUNK - 1) / SCR_CHUNK;
+    if (n_blocks > (~0ull) / (2 * sizeof(double)) / n_values) return BEAR_ERR_INVALID_ARG;
+    HIP_TRY(partials.alloc(2 * n_blocks * n_values));
+    hipLaunchKernelGGL(score_chunk_kernel, dim3(scr_grid(n_blocks, 1), tiles), dim3(SCR_WAVE), 0, s, lp, n_rows, (uint32_t)width,
+                       n_values, rows, letters, seg, n_seg, n_t, n_blocks, partials.get());
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(score_sum_kernel, dim3(scr_grid(n_seg, 1), tiles), dim3(SCR_WAVE), 0, s, lp, n_rows, (uint32_t)width, n_values,
+                     rows, letters, seg, n_seg, n_t, partials.get(), scores);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;      // (partials goes with this frame: hipFree waits for the two launches)
+}
+
+}  // extern "C"

@@ -7,7 +7,8 @@ log-Gamma draws of ``log_gamma.log_gamma`` and their normalisation, or the MAP t
 ``bear_logdir_sample_f64`` over the batch of k-mers (``kernels_sample.h``); the exact marginal term
 (``get_marg``) is one launch of ``bear_eval_f64``.  The protein alphabet (rows of 21: 20 letters + stop) takes their
 width-taking twins, ``bear_logdir_sample_wide_f64`` and ``bear_eval_wide_f64``.  The k+1-mer bookkeeping stays on the host as in the
-reference (string windows, a lookup table indexed by k+1-mer).
+reference (string windows, a lookup table indexed by k+1-mer) -- unless the counts come from a ``DeviceCounter``: then
+``get_bear_probs`` / ``get_bear_probs_seqs`` run on the device from the queries' symbols to the scores (``kernels_score.h``).
 
 Differences a user can see: draws come from a counter-based stream (``seed`` argument; ``None`` takes a fresh
 seed from numpy's global generator) instead of numpy's Mersenne twister, and the KMC database look-up
@@ -110,7 +111,8 @@ def get_pdf(kmers, counts, h, ar_func, mc_samples, vans, train_col, alphabet_nam
     """get_var_probs.get_pdf (get_var_probs.py:91-194).  ``kmers``: strings; ``counts``: [K, num_ds, A+1];
     ``h``: sequence of h values (used when ``ar_func`` is given); ``vans``: BMM pseudo-counts.  Returns, by
     ``output``: 'func' a function of k+1-mers -> [num_models, mc_samples] (summed) or [n, num_models, mc_samples];
-    'df' a pandas DataFrame indexed by k+1-mer; 'numpy' an array [k-mer, letter, model, mc_sample].
+    'df' a pandas DataFrame indexed by k+1-mer; 'numpy' an array [k-mer, letter, model, mc_sample]; 'device' that array as the
+    CUDA tensor the sampler wrote (never copied to the host).
     With ``get_marg`` a function ``(kmers, counts) -> [num_models]`` (exact DM marginal, :155-173)."""
     assert not (get_marg and get_map), "pick marg or map"
     assert not (get_marg and output != "func"), "not implemented"
@@ -157,9 +159,12 @@ def get_pdf(kmers, counts, h, ar_func, mc_samples, vans, train_col, alphabet_nam
     if K:
         sample = kernels.logdir_sample if A1 == 5 else kernels.logdir_sample_wide
         log_probs = sample(col_dev, prior, hs, vans, mc_samples, get_map=get_map, with_ar=with_ar,
-                           seed=_next_seed() if seed is None else seed, row_base=row_base).cpu().numpy()
+                           seed=_next_seed() if seed is None else seed, row_base=row_base)
     else:
-        log_probs = np.zeros((0, A1, num_models, mc_samples))
+        log_probs = torch.zeros((0, A1, num_models, mc_samples), dtype=torch.float64, device=device)
+    if output == "device":      # the sampler's table where the sampler left it (kernels.score_sum reads it there)
+        return log_probs
+    log_probs = log_probs.cpu().numpy()
     if output == "numpy":
         return log_probs
     table = _Table(kmers, list(alphabet), log_probs)
@@ -218,6 +223,202 @@ def make_sequence_counter(seqs, lag, reverse=True, no_end=False, device=None, al
     return counter
 
 
+# ------------------------------------------------------------------------------------------- scoring on the device
+_NO_SYMBOL = 0xFE      # the code of a character outside the alphabet (beyond every symbol code: the kernel makes no key of it)
+
+
+def _symbol_lut(alphabet_name):
+    """byte -> symbol code of the scoring text (include/bear_hip.h): letters 0 .. W - 2, ']' W - 1, '[' W, anything else _NO_SYMBOL."""
+    alphabet = core.alphabets_en[alphabet_name]
+    lut = np.full(256, _NO_SYMBOL, dtype=np.uint8)
+    for c, ch in enumerate(alphabet):
+        lut[ord(ch)] = c
+    lut[ord("[")] = len(alphabet)
+    return lut
+
+
+class DeviceCounter:
+    """The pooled lag-``lag`` transition table of one dataset column in HBM, as a look-up: ASCII k-mers ``kmers`` uint8 [N, lag],
+    ``counts`` [N, W] (uint32 in int32 storage), and the k-mers' keys sorted once (``keys`` int64 [N'] ascending, ``perm`` their
+    rows; a k-mer with a character outside the alphabet has no key and is never found).  A key packs the ranks of a k-mer's
+    characters in byte order, first letter most significant (``kernels.score_ranks``), so keys sort as Python sorts the strings.
+
+    Called with k-mer strings it returns what ``make_sequence_counter``'s closure returns, ``no_end`` included, so it is a valid
+    ``counter=`` anywhere.  Handed to ``get_bear_probs`` / ``get_bear_probs_seqs`` (without ``get_marg``) the whole call runs on the
+    device: keys of the queries' transitions, their distinct k-mers, count rows by ``kernels.kmer_find``, the sampled or MAP table
+    and the per-variant / per-sequence sums (``kernels.score_sum``); only the scores come back.  ``train_col`` of those calls is
+    not used then: the counter is one column."""
+
+    def __init__(self, kmers, counts, alphabet_name, no_end=False):
+        if not (isinstance(kmers, torch.Tensor) and kmers.is_cuda and kmers.dtype == torch.uint8 and kmers.dim() == 2):
+            raise ValueError("kmers must be a CUDA uint8 tensor [N, lag] of ASCII k-mers")
+        if not (isinstance(counts, torch.Tensor) and counts.device == kmers.device and counts.dtype == torch.int32
+                and counts.dim() == 2 and counts.shape[0] == kmers.shape[0]):
+            raise ValueError("counts must be a CUDA int32 tensor [N, W] on the k-mers' device")
+        self.alphabet_name, self.no_end = alphabet_name, bool(no_end)
+        self.rank = kernels.score_ranks(alphabet_name)
+        self.width, self.lag = len(self.rank) - 1, int(kmers.shape[1])
+        if counts.shape[1] != self.width:
+            raise ValueError(f"counts: rows of {counts.shape[1]}, the alphabet {alphabet_name!r} has rows of {self.width}")
+        if not 1 <= self.lag <= kernels.SCORE_MAX_LAG[self.width]:
+            raise ValueError(f"lag {self.lag}: a look-up key holds contexts of 1..{kernels.SCORE_MAX_LAG[self.width]} letters of {alphabet_name!r}")
+        self.kmers, self.counts = kmers.contiguous(), counts.contiguous()
+        self._lut = _symbol_lut(alphabet_name)
+        keys = self._keys_of_codes(torch.from_numpy(self._lut).to(kmers.device)[self.kmers.long()])
+        held = torch.nonzero(keys >= 0).reshape(-1)
+        self.keys, order = torch.sort(keys[held])
+        self.perm = held[order]
+        if self.keys.numel() > 1 and bool((self.keys[1:] == self.keys[:-1]).any()):
+            raise ValueError("DeviceCounter: the table holds a k-mer twice")
+
+    @property
+    def device(self):
+        return self.kmers.device
+
+    def _keys_of_codes(self, codes):
+        """Keys int64 [n] of k-mers given as symbol codes uint8 [n, lag] on the device (-1: a symbol that is no letter of a context):
+        every k-mer becomes a segment of lag + 1 symbols, the k-mer and a stop, whose one transition carries the k-mer's key."""
+        n = codes.shape[0]
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64, device=codes.device)
+        text = torch.cat([codes, torch.full((n, 1), self.width - 1, dtype=torch.uint8, device=codes.device)], 1).reshape(-1)
+        seg = torch.arange(n + 1, dtype=torch.int64, device=codes.device) * (self.lag + 1)
+        keys, _ = kernels.score_transitions(text, seg, self.lag, self.rank)
+        return keys.reshape(n, self.lag + 1)[:, self.lag].contiguous()
+
+    def rows_of_keys(self, keys):
+        """Count rows int32 [n, W] of the k-mers with the given keys (int64 [n] on the device; ascending is the fast order): zeros for
+        an absent k-mer; under ``no_end`` also for a context that holds ``[``, and in the stop column."""
+        idx = kernels.kmer_find(self.keys, keys.contiguous())
+        rows = self.counts[self.perm[idx.clamp(min=0).long()]] if self.keys.numel() else \
+            torch.zeros((keys.numel(), self.width), dtype=torch.int32, device=self.device)
+        keep = idx >= 0
+        if self.no_end:
+            bits, start = kernels.SCORE_BITS[self.width], int(self.rank[self.width])
+            shifts = torch.arange(self.lag, dtype=torch.int64, device=self.device) * bits
+            keep = keep & ~(((keys[:, None] >> shifts[None, :]) & ((1 << bits) - 1)) == start).any(1)
+        rows = rows * keep[:, None].to(torch.int32)
+        if self.no_end:
+            rows[:, -1] = 0
+        return rows.contiguous()
+
+    def codes_of_keys(self, keys):
+        """``core.encode_kmers`` codes int8 [n, lag] (letters 0 .. A - 1, ``[`` = A) of the k-mers with the given valid keys."""
+        bits = kernels.SCORE_BITS[self.width]
+        code_of_rank = np.zeros(1 << bits, dtype=np.int8)
+        code_of_rank[self.rank[:self.width - 1]] = np.arange(self.width - 1)
+        code_of_rank[self.rank[self.width]] = self.width - 1
+        shifts = torch.arange(self.lag - 1, -1, -1, dtype=torch.int64, device=self.device) * bits
+        ranks = (keys[:, None] >> shifts[None, :]) & ((1 << bits) - 1)
+        return torch.from_numpy(code_of_rank).to(self.device)[ranks].contiguous()
+
+    def __call__(self, kmers):
+        kmers = np.asarray(kmers)
+        flat = [k.decode() if isinstance(k, bytes) else str(k) for k in kmers.reshape(-1).tolist()]
+        out = np.zeros((len(flat), self.width))
+        sized = [i for i, k in enumerate(flat) if len(k) == self.lag]
+        if sized:
+            raw = np.frombuffer("".join(flat[i] for i in sized).encode("ascii", "replace"), dtype=np.uint8)
+            keys = self._keys_of_codes(torch.from_numpy(self._lut[raw].reshape(len(sized), self.lag)).to(self.device))
+            rows = self.rows_of_keys(keys)
+            out[sized] = (rows.to(torch.int64) & 0xFFFFFFFF).to(torch.float64).cpu().numpy()
+        return out.reshape(kmers.shape + (self.width,))
+
+    @classmethod
+    def from_sequences(cls, seqs, lag, reverse=True, no_end=False, device=None, alphabet_name="dna"):
+        """``make_sequence_counter``'s arguments; the table is counted with ``summarize.count_transitions(..., on_device=True)`` and
+        stays where it was counted."""
+        from . import summarize
+        if alphabet_name == "prot" and reverse:
+            raise ValueError("DeviceCounter.from_sequences: the protein alphabet has no reverse complement, pass reverse=False")
+        if isinstance(seqs, str):
+            seqs, _ = summarize._load_sequences(seqs)
+        seqs = [str(s) for s in seqs]
+        text, grp = summarize.encode_sequences(seqs, [0] * len(seqs), reverse=reverse, alphabet=alphabet_name)
+        kmers, counts = summarize.count_transitions(text, grp, lag, 1, device=device, on_device=True, alphabet=alphabet_name)
+        return cls(kmers, counts[0], alphabet_name, no_end=no_end)
+
+    @classmethod
+    def from_dataset(cls, data, train_col, no_end=False, device=None):
+        """Column ``train_col`` of a ``CountDataset`` (uploaded) or a ``DeviceCountDataset`` (in place), e.g. ``load_bear(path)[4]``."""
+        if getattr(data, "shard", None) is not None:
+            raise ValueError("DeviceCounter.from_dataset: a row-sharded table holds only one rank's k-mers")
+        if isinstance(data, dataloader.DeviceCountDataset):
+            return cls(data.kmers_dev, data.counts_dev[int(train_col)], data.alphabet, no_end=no_end)
+        device = _device() if device is None else torch.device(device)
+        kmers = torch.from_numpy(np.ascontiguousarray(data.kmers, dtype=np.uint8)).to(device)
+        counts = torch.from_numpy(np.ascontiguousarray(data.counts[int(train_col)]).view(np.int32)).to(device)
+        return cls(kmers, counts, data.alphabet, no_end=no_end)
+
+
+def _segment_text(segments, lag, alphabet_name):
+    """Strings -> ``(codes uint8 [n_sym], offsets int64 [n_seg + 1], positions without a transition)`` of the scoring text.  What the
+    kernels would make no key of is refused here, before any launch: a character outside the alphabet, a ``]`` inside a context,
+    a ``[`` as a next symbol."""
+    lut = _symbol_lut(alphabet_name)
+    W = len(core.alphabets_en[alphabet_name])
+    lens = np.fromiter((len(s) for s in segments), dtype=np.int64, count=len(segments))
+    joined = "".join(segments)
+    codes = lut[np.frombuffer(joined.encode("ascii", "replace"), dtype=np.uint8)]
+    bad = np.flatnonzero(codes == _NO_SYMBOL)
+    if bad.size:
+        raise ValueError(f"character {joined[bad[0]]!r} is not a letter of the alphabet {alphabet_name!r}, '[' or ']'")
+    seg = np.zeros(len(segments) + 1, dtype=np.int64)
+    np.cumsum(lens, out=seg[1:])
+    pos = np.arange(codes.size, dtype=np.int64) - np.repeat(seg[:-1], lens)
+    seg_len = np.repeat(lens, lens)
+    in_context = (seg_len > lag) & (pos < seg_len - 1)
+    if np.any(in_context & (codes == W - 1)):
+        raise ValueError("character ']' inside a context: the stop symbol can only end a sequence")
+    if np.any((pos >= lag) & (codes == W)):
+        raise ValueError("character '[' behind a context: the start symbol can only pad the front of a sequence")
+    return codes, seg, int(np.minimum(lens, lag).sum())
+
+
+def _score_segments(counter, segments, lag, alphabet_name, h, ar_func, mc_samples, vans, get_map, seed):
+    """The device path of get_bear_probs / get_bear_probs_seqs: ``scores[i] = sum of log p(next | k-mer)`` over the transitions of
+    string ``i`` -> CUDA float64 [n_seg, num_models, mc_samples].  The distinct k-mers are numbered as
+    ``np.array(sorted(set(all_kmers)))`` numbers them (ascending keys), and that number keys the sampler's draws: with equal
+    ``seed`` the table is the one the host ``counter=`` path samples.
+
+    The table ``[K, W, num_models, mc_samples]`` is held whole: if it would not fit the free device memory a ``MemoryError`` says
+    so (score fewer strings or samples per call) -- rows are not processed in pieces, so a result never depends on what else
+    the device holds."""
+    if counter.lag != lag or counter.alphabet_name != alphabet_name:
+        raise ValueError(f"counter: a lag-{counter.lag} table of {counter.alphabet_name!r}, asked for lag {lag} of {alphabet_name!r}")
+    device, W = counter.device, counter.width
+    vans = np.atleast_1d(np.asarray(vans, dtype=np.float64)).reshape(-1)
+    hs = np.atleast_1d(np.asarray(h, dtype=np.float64)).reshape(-1) if ar_func is not None else np.zeros(0)
+    with_ar = ar_func is not None and get_map
+    num_models = len(vans) + len(hs) + int(with_ar)
+    if get_map:
+        mc_samples = 1
+    codes, seg, n_none = _segment_text(segments, lag, alphabet_name)
+    if codes.size == n_none:        # no transition anywhere
+        return torch.zeros((len(segments), num_models, mc_samples), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        seg = torch.from_numpy(seg).to(device)
+        keys, letters = kernels.score_transitions(torch.from_numpy(codes).to(device), seg, lag, counter.rank)
+        uniq, inverse = torch.unique(keys, return_inverse=True)     # ascending; -1 (no transition) in front where there is one
+        first = int(n_none > 0)
+        kmer_keys = uniq[first:].contiguous()
+        rows = (inverse - first).to(torch.int32)
+        K = kmer_keys.numel()
+        need = K * W * num_models * mc_samples * 8
+        free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+        if need > free:
+            raise MemoryError(f"the sampled table of {K} k-mers x {W} letters x {num_models} models x {mc_samples} samples takes "
+                              f"{need} bytes, the device has {free} free: score fewer variants / sequences or samples per call")
+        prior = None
+        if ar_func is not None:
+            with torch.no_grad():
+                prior = ar_func(counter.codes_of_keys(kmer_keys)).to(torch.float64).expand(K, W).contiguous()
+        sample = kernels.logdir_sample if W == 5 else kernels.logdir_sample_wide
+        lp = sample(counter.rows_of_keys(kmer_keys), prior, hs, vans, mc_samples, get_map=get_map, with_ar=with_ar, seed=seed,
+                    row_base=0)
+        return kernels.score_sum(lp, rows, letters, seg)
+
+
 # ------------------------------------------------------------------------------------------- variants
 def _add_kmer_probs_vars(vars_, scores, wt_seq, pdf, lag, seen_kmers):
     """get_var_probs.py:294-306."""
@@ -248,9 +449,10 @@ def _get_all_kmers_vars(vars_, wt_seq, lag):
 
 def parse_var(var):
     """'AAG23CC' -> ('AAG', 'CC', 23) (get_var_probs.py:339-344)."""
-    is_int = [ch.isnumeric() for ch in var]
-    pos_num = int(np.min(np.argwhere(is_int)))
-    len_num = int(np.sum(is_int))
+    digits = [i for i, ch in enumerate(var) if ch.isnumeric()]      # (plain Python: a tenth of the time of the NumPy form, which was most of a device-path call)
+    if not digits:
+        raise ValueError(f"variant {var!r} holds no position")
+    pos_num, len_num = digits[0], len(digits)
     return (var[:pos_num], var[pos_num + len_num:], int(var[pos_num:pos_num + len_num]))
 
 
@@ -298,12 +500,23 @@ def get_bear_probs(bear_path, wt_seq, vars_, train_col, mc_samples=41, vans=[0.1
     alphabet_size = len(core.alphabets_en[alphabet_name]) - 1
     wt_seq = lag * "[" + wt_seq + "]"
     vars_ = [parse_var(v) for v in vars_]
-    all_kmers = _get_all_kmers_vars(vars_, wt_seq, lag)
     if get_map:
         mc_samples = 1
     num_models = (ar_func is not None) * (len_h + get_map) + len(vans)
     scores = np.zeros([len(vars_), num_models, mc_samples])
     seed = _next_seed() if seed is None else seed
+    if isinstance(counter, DeviceCounter):      # the whole call on the device: a variant is two segments, mutant and wild-type window
+        windows = []
+        for wt_aa, mt_aa, pos in vars_:
+            pos = pos + lag
+            assert wt_aa == wt_seq[pos:pos + len(wt_aa)]
+            windows.append(wt_seq[pos - lag:pos] + mt_aa + wt_seq[pos + len(wt_aa):pos + lag + len(wt_aa)])
+            windows.append(wt_seq[pos - lag:pos + lag + len(wt_aa)])
+        if windows:
+            sums = _score_segments(counter, windows, lag, alphabet_name, h, ar_func, mc_samples, vans, get_map, seed)
+            scores = (sums[0::2] - sums[1::2]).cpu().numpy()
+        return scores[..., 0] if get_map else scores
+    all_kmers = _get_all_kmers_vars(vars_, wt_seq, lag)
 
     def make_pdf(kmers, counts, row0):
         return get_pdf(kmers, counts, h, ar_func, mc_samples, vans, train_col, alphabet_name, get_map, seed=seed, row_base=row0)
@@ -357,12 +570,18 @@ def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1,
     alphabet_size = len(alphabet) - 1
     if not no_ends:
         seqs = [lag * "[" + s + "]" for s in seqs]
-    all_kmers = _get_all_kmers_seqs(seqs, lag)
     if get_map or get_marg:
         mc_samples = 1
     num_models = (ar_func is not None) * (len_h + get_map) + len(vans)
     scores = np.zeros([len(seqs), num_models, mc_samples])
     seed = _next_seed() if seed is None else seed
+    if isinstance(counter, DeviceCounter) and not get_marg:     # the whole call on the device: a sequence is a segment
+        for seq in seqs:
+            assert len(seq.replace("[", "").replace("]", "")) >= lag
+        if len(seqs):
+            scores = _score_segments(counter, seqs, lag, alphabet_name, h, ar_func, mc_samples, vans, get_map, seed).cpu().numpy()
+        return scores[..., 0] if get_map else scores
+    all_kmers = _get_all_kmers_seqs(seqs, lag)
 
     def make_pdf(kmers, counts, row0):
         return get_pdf(kmers, counts, h, ar_func, mc_samples, vans, train_col, alphabet_name, get_map, get_marg,

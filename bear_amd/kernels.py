@@ -643,6 +643,97 @@ def logdir_sample_wide(counts, prior, h, vans, mc_samples, get_map=False, with_a
     return _logdir_sample(True, counts, prior, h, vans, mc_samples, get_map, with_ar, seed, row_base, n_rows, device, width)
 
 
+# ---- scoring under a sampled table (include/bear_hip.h, "Variant and sequence scoring"; kernels_score.h) ----------------------
+# torch has no general uint64 / uint32 arithmetic: keys and offsets travel in int64 storage (a key has at most 63 bits, so the
+# signed order is the key order; "no key" reads -1), table rows in int32 storage ("absent" reads -1).
+SCORE_BITS = {5: 3, 21: 5}           # key bits per letter at a row width
+SCORE_MAX_LAG = {5: 21, 21: 12}      # ... and the longest context one 64-bit key holds
+SCORE_SKIP = 0xFF                    # the letter of a position without a transition
+SCORE_CHUNK = 2048                   # BEAR_SCORE_CHUNK: transitions of a long segment summed by one wave
+
+
+def score_ranks(alphabet_name):
+    """The rank table of an alphabet of ``core.alphabets_en``: uint8 [W + 1], ``rank[c]`` = position of the character of symbol
+    code ``c`` (letters 0 .. W - 2, stop W - 1, start W) among the letters and ``[`` sorted as bytes; 0xFF for the stop, which
+    is no letter of a context.  A key packs these ranks, first letter most significant, so keys sort as the k-mer strings do."""
+    from . import core
+    letters = [str(ch) for ch in core.alphabets_en[alphabet_name][:-1]]
+    order = sorted(letters + ["["])
+    W = len(letters) + 1
+    if W not in WIDE_WIDTHS:
+        raise ValueError(f"alphabet {alphabet_name!r}: rows of {W}; the kernels take {WIDE_WIDTHS}")
+    rank = np.full(W + 1, 0xFF, dtype=np.uint8)
+    for c, ch in enumerate(letters):
+        rank[c] = order.index(ch)
+    rank[W] = order.index("[")
+    return rank
+
+
+def _check_vec(t, dtype, name, n=None, device=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()
+            and (n is None or t.numel() == n) and (device is None or t.device == device)):
+        raise ValueError(f"{name} must be a contiguous CUDA {dtype} vector" + ("" if n is None else f" of {n} elements")
+                         + ("" if device is None else f" on {device}"))
+    return t
+
+
+def _check_seg(seg, device):
+    _check_vec(seg, torch.int64, "seg", device=device)
+    if seg.numel() < 1:
+        raise ValueError("seg holds n_seg + 1 offsets: at least one")
+    return seg.numel() - 1
+
+
+def score_transitions(text, seg, lag, rank):
+    """One launch of ``bear_score_transitions_u64``.  ``text``: CUDA uint8 [n_sym] symbol codes (letters 0 .. W - 2, stop W - 1,
+    start W, all written out); ``seg``: CUDA int64 [n_seg + 1] ascending offsets from 0 to n_sym; ``rank``: ``score_ranks`` of the
+    alphabet (its length gives W).  Returns ``(keys int64 [n_sym], letters uint8 [n_sym])``: per symbol the key of the ``lag``
+    symbols in front of it and its letter index, or -1 / ``SCORE_SKIP`` where it stands less than ``lag`` symbols into its segment."""
+    _check_vec(text, torch.uint8, "text")
+    n_seg = _check_seg(seg, text.device)
+    rank = np.ascontiguousarray(rank, dtype=np.uint8)
+    W = rank.size - 1
+    if W not in WIDE_WIDTHS:
+        raise ValueError(f"rank: {rank.size} entries; a rank table holds W + 1 for W in {WIDE_WIDTHS}")
+    if not 1 <= int(lag) <= SCORE_MAX_LAG[W]:
+        raise ValueError(f"lag {lag}: a key of {SCORE_BITS[W]} bits per letter holds contexts of 1..{SCORE_MAX_LAG[W]} letters")
+    keys = torch.empty(text.numel(), dtype=torch.int64, device=text.device)
+    letters = torch.empty(text.numel(), dtype=torch.uint8, device=text.device)
+    _launch(text.device, "bear_score_transitions_u64", _ptr(text), _ptr(seg), text.numel(), n_seg, int(lag), W,
+            rank.ctypes.data_as(ctypes.c_void_p), _ptr(keys), _ptr(letters))
+    return keys, letters
+
+
+def kmer_find(table, query):
+    """One launch of ``bear_kmer_find_u64``: int32 [n_query], the index of every ``query`` key in ``table`` (CUDA int64, ascending
+    and distinct, non-negative), -1 where it is absent.  Sorted queries are the fast case; any order is correct."""
+    _check_vec(table, torch.int64, "table")
+    _check_vec(query, torch.int64, "query", device=table.device)
+    if table.numel() >= 2 ** 32 - 1:
+        raise ValueError("table: a row index is 32 bits wide")
+    rows = torch.empty(query.numel(), dtype=torch.int32, device=table.device)
+    _launch(table.device, "bear_kmer_find_u64", _ptr(table), table.numel(), _ptr(query), query.numel(), _ptr(rows))
+    return rows
+
+
+def score_sum(lp, rows, letters, seg):
+    """``bear_score_sum_f64``: ``scores[i] = sum_t lp[rows[t], letters[t]]`` over the transitions of segment ``i`` in text order ->
+    CUDA float64 [n_seg, M, S].  ``lp``: the sampler's table [K, W, M, S] as ``logdir_sample[_wide]`` returns it; ``rows`` int32
+    [n_t] and ``letters`` uint8 [n_t] per position of the text (``SCORE_SKIP``, a negative row: nothing is added); ``seg`` int64
+    [n_seg + 1] ascending from 0 to n_t.  Segments beyond ``SCORE_CHUNK`` transitions are summed in chunks, in a fixed order."""
+    if not (isinstance(lp, torch.Tensor) and lp.is_cuda and lp.dtype == torch.float64 and lp.dim() == 4 and lp.is_contiguous()
+            and lp.shape[1] in WIDE_WIDTHS):
+        raise ValueError(f"lp must be a contiguous CUDA float64 tensor [K, W, M, S] with W in {WIDE_WIDTHS}")
+    _check_vec(rows, torch.int32, "rows", device=lp.device)
+    _check_vec(letters, torch.uint8, "letters", rows.numel(), device=lp.device)
+    n_seg = _check_seg(seg, lp.device)
+    K, W, M, S = lp.shape
+    scores = torch.empty((n_seg, M, S), dtype=torch.float64, device=lp.device)
+    _launch(lp.device, "bear_score_sum_f64", _ptr(lp), K, W, M * S, _ptr(rows), _ptr(letters), rows.numel(), _ptr(seg), n_seg,
+            _ptr(scores))
+    return scores
+
+
 def shuffle_rows(src, seed):
     """One launch of ``bear_shuffle_rows``: a new tensor with ``dst[i] = src[perm_seed(i)]`` along dim 0."""
     if not (src.is_cuda and src.is_contiguous() and src.dim() >= 1):

@@ -51,7 +51,9 @@ extern "C" {
                                   + bear_kmer_sort_bytes, bear_kmer_bin_hist, bear_kmer_sort_create_range (counting in passes over
                                   key ranges);
                                   + bear_dm_cnn_wide_f64, bear_net_cnn_train_reduce_wide_f64, bear_net_cnn_train_step_wide_f64
-                                  (bear_net's step with the convolutional AR function on rows of 21 as two launches) */
+                                  (bear_net's step with the convolutional AR function on rows of 21 as two launches);
+                                  + bear_score_transitions_u64, bear_kmer_find_u64, bear_score_sum_f64 (variant and sequence
+                                  scoring on the device) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -843,6 +845,44 @@ int bear_kmer_sort_bytes(uint64_t n_pairs, int lag, int width, uint64_t *bytes_o
 int bear_kmer_bin_hist(const uint8_t *text, uint64_t n_pos, int lag, int width, uint64_t *hist, uint64_t n_bins, void *stream);
 int bear_kmer_sort_create_range(const uint8_t *text, const uint8_t *group, uint64_t n_pos, int lag, int width, uint64_t bin_lo,
                                 uint64_t bin_hi, uint64_t capacity, bear_kmer_sort **out, uint64_t *n_rows_out, void *stream);
+
+/*
+ * Variant and sequence scoring on the device (get_var_probs.get_bear_probs / get_bear_probs_seqs with a DeviceCounter): what
+ * stands between a count table in device memory and the samplers' tables above.  All three are asynchronous on `stream`.
+ *
+ * The symbol text: uint8 codes as in the counting text -- letters 0 .. width - 2, the stop ']' = width - 1, the start '[' = width
+ * -- with every start and stop written out (nothing is padded implicitly), cut into n_seg segments by
+ *   seg [dev] uint64 [n_seg + 1], ascending, seg[0] = 0, seg[n_seg] = the number of symbols
+ * (a variant window, a padded sequence).  A transition sits at every symbol that stands at least `lag` symbols into its segment.
+ *
+ * bear_score_transitions_u64: per symbol the key of the `lag` symbols in front of it and its letter.
+ *   text [dev] uint8 [n_sym];  width 5 (lag <= 21, 3 bits per letter) or 21 (lag <= 12, 5 bits per letter)
+ *   rank [host] uint8 [width + 1]: rank[c] = position of the character of code c among the alphabet's characters and '[' in byte
+ *        order, 0xFF for the stop (which is no letter of a context).  key = sum over the context's letters of rank << bits *
+ *        (lag - 1 - position): the first letter is the most significant, so the integer order of the keys is the order of the
+ *        k-mer strings, and the number of a k-mer among the sorted distinct keys is its number in sorted(set(strings)).
+ *   keys [dev] uint64 [n_sym], letters [dev] uint8 [n_sym]: the key and the letter index (stop = width - 1) of the transition at
+ *        the symbol; 0xFF in every byte of both where there is none -- less than `lag` symbols into the segment, or a symbol
+ *        that is no letter of its place (callers refuse those before the launch).
+ * bear_kmer_find_u64: rows[q] = the index of query[q] in `table`, or 0xFFFFFFFF where it is absent.
+ *   table [dev] uint64 [n_table] ascending and distinct, n_table < 2^32 - 1;  query [dev] uint64 [n_query] in any order (sorted
+ *   queries keep the lanes of a wave on neighbouring entries);  rows [dev] uint32 [n_query].  n_table = 0 and n_query = 0 are valid.
+ * bear_score_sum_f64: scores[i, :] = sum over the transitions t of segment i, in text order, of lp[rows[t], letters[t], :].
+ *   lp [dev] double [n_rows, width, n_values]: the table bear_logdir_sample[_wide]_f64 leaves (n_values = n_models * mc_samples)
+ *   rows [dev] uint32 [n_t], letters [dev] uint8 [n_t]: per position of the text the table row and the letter; a position with
+ *        letter 0xFF (or a row >= n_rows, a letter >= width) adds nothing;  seg as above with seg[n_seg] = n_t
+ *   scores [dev] double [n_seg, n_values].  A segment of at most BEAR_SCORE_CHUNK transitions is summed front to back; a longer one
+ *        in chunks of BEAR_SCORE_CHUNK transitions from its start, whose partial rows are added in chunk order.  No atomics: the
+ *        same arguments give the same bits, in both libraries, wherever the segment stands in the text.  Holds two partial rows
+ *        per BEAR_SCORE_CHUNK positions of a text longer than that, and frees them before it returns.
+ */
+#define BEAR_SCORE_CHUNK 2048
+int bear_score_transitions_u64(const uint8_t *text, const uint64_t *seg, uint64_t n_sym, uint64_t n_seg, int lag, int width,
+                               const uint8_t *rank, uint64_t *keys, uint8_t *letters, void *stream);
+int bear_kmer_find_u64(const uint64_t *table, uint64_t n_table, const uint64_t *query, uint64_t n_query, uint32_t *rows,
+                       void *stream);
+int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_values, const uint32_t *rows, const uint8_t *letters,
+                       uint64_t n_t, const uint64_t *seg, uint64_t n_seg, double *scores, void *stream);
 
 #ifdef __cplusplus
 }
