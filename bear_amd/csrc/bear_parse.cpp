@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <system_error>
 #include <thread>
 #include <vector>
 #include <stdlib.h>
@@ -19,6 +20,10 @@
 // host threads of the parser / row counter / writer: one chunk of the mapped text each (BEAR_PARSE_THREADS overrides the count)
 #ifndef BEAR_MAX_HOST_THREADS
 #define BEAR_MAX_HOST_THREADS 64u   // measured on the 256-thread host of an MI355X box: 16 .. 64 threads parse a 5.2 GB table in 0.39 s, 128 / 256 in 0.55
+#endif
+// developer build of tests/native/parse_check.cpp (`make parse-check`): creating thread k of every run_chunks call fails
+#if defined(BEAR_PARSE_TEST_THREAD_FAILS_AT) && !defined(BEAR_DEV_BUILD)
+#error "a developer test switch is defined without -DBEAR_DEV_BUILD: release builds refuse it"
 #endif
 
 namespace {
@@ -58,47 +63,145 @@ inline bool blank_line(const char *b, const char *e) {
     if (*b != ' ' && *b != '\r' && *b != '\t') return false;
   return true;
 }
-}  // namespace
 
-static uint64_t count_lines_mt(const char *base, size_t size);
-
-extern "C" int bear_count_rows(const char *path, uint64_t *n_rows_out) {
-  if (!path || !n_rows_out) return BEAR_ERR_INVALID_ARG;
-  mapped_file f;
-  int st = f.open_ro(path);
-  if (st != BEAR_OK) return st;
-  *n_rows_out = count_lines_mt(f.data, f.size);
-  return BEAR_OK;
+// The line that starts at p < end: its text [b, e) without the '\n', and where the next line starts -- `end` behind a last
+// line that has no newline, so no pointer beyond the text is ever formed.
+struct line {
+  const char *b, *e, *next;
+};
+inline line line_at(const char *p, const char *end) {
+  const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
+  return nl ? line{p, nl, nl + 1} : line{p, end, end};
 }
 
+uint64_t count_lines(const char *p, const char *end) {   // the non-blank ones
+  uint64_t n = 0;
+  while (p < end) {
+    const line l = line_at(p, end);
+    if (!blank_line(l.b, l.e)) ++n;
+    p = l.next;
+  }
+  return n;
+}
+
+// ------------------------------------------------------------------ threads: how many, which text each, start and join
+// The only exceptions of this file are failed allocations of its std::vectors (run_chunks turns a failed thread creation into
+// the same status itself): none leaves an entry.
+template <class F>
+int guarded(F body) noexcept {
+  try {
+    return body();
+  } catch (...) {
+    return BEAR_ERR_NOMEM;
+  }
+}
+
+// Hardware threads, or BEAR_PARSE_THREADS, up to BEAR_MAX_HOST_THREADS and to `most` (what the work is worth), at least 1.
+unsigned host_threads(uint64_t most) {
+  unsigned nt = std::thread::hardware_concurrency();
+  if (const char *env = getenv("BEAR_PARSE_THREADS")) nt = (unsigned)atoi(env);
+  if (nt > BEAR_MAX_HOST_THREADS) nt = BEAR_MAX_HOST_THREADS;
+  if (nt > most) nt = (unsigned)most;
+  return nt < 1 ? 1 : nt;
+}
+inline unsigned text_threads(size_t bytes) { return host_threads(bytes < (size_t)(1u << 20) ? 1 : BEAR_MAX_HOST_THREADS); }   // small files: not worth the threads
+
+// nt chunks of [base, end), cut[k] .. cut[k + 1], of about equal size, every boundary moved to the next line start.
+std::vector<const char *> cut_at_lines(const char *base, const char *end, unsigned nt) {
+  std::vector<const char *> cut(nt + 1, end);
+  cut[0] = base;
+  for (unsigned k = 1; k < nt; ++k) {
+    const char *p = base + (size_t)(end - base) / nt * k;
+    cut[k] = p < end ? line_at(p, end).next : end;
+  }
+  return cut;
+}
+
+// fn(0) .. fn(nt - 1), fn(0) on the calling thread and one thread for each of the others; fn does not throw.  If a thread
+// cannot be created, the ones already running are joined -- nothing works on the caller's buffers any more -- and the call
+// returns BEAR_ERR_NOMEM.
+template <class F>
+int run_chunks(unsigned nt, F fn) {
+  std::vector<std::thread> th;
+  th.reserve(nt - 1);
+  int st = BEAR_OK;
+  try {
+    for (unsigned k = 1; k < nt; ++k) {
+#ifdef BEAR_PARSE_TEST_THREAD_FAILS_AT
+      if (k == BEAR_PARSE_TEST_THREAD_FAILS_AT) throw std::system_error(std::make_error_code(std::errc::resource_unavailable_try_again));
+#endif
+      th.emplace_back([&fn, k] { fn(k); });
+    }
+  } catch (const std::system_error &) {
+    st = BEAR_ERR_NOMEM;
+  }
+  if (st == BEAR_OK) fn(0);
+  for (auto &t : th) t.join();
+  return st;
+}
+
+// One number per chunk of a file's text, summed: the row count of a 5 GB table is a pass at memory speed instead of half a
+// second of one thread's memchr.
+template <class Count>
+int count_file(const char *path, uint64_t *n_out, Count count) {
+  if (!path || !n_out) return BEAR_ERR_INVALID_ARG;
+  return guarded([&] {
+    mapped_file f;
+    int st = f.open_ro(path);
+    if (st != BEAR_OK) return st;
+    const unsigned nt = text_threads(f.size);
+    const std::vector<const char *> cut = cut_at_lines(f.data, f.data + f.size, nt);
+    std::vector<uint64_t> part(nt, 0);
+    st = run_chunks(nt, [&](unsigned k) { part[k] = count(cut[k], cut[k + 1]); });
+    if (st != BEAR_OK) return st;
+    uint64_t n = 0;
+    for (unsigned k = 0; k < nt; ++k) n += part[k];
+    *n_out = n;
+    return (int)BEAR_OK;
+  });
+}
+}  // namespace
+
+extern "C" int bear_count_rows(const char *path, uint64_t *n_rows_out) { return count_file(path, n_rows_out, count_lines); }
+
+// `wc -l` of a file (the reference's num_kmers, models/train_bear_net.py:52-55: newline bytes, blank lines and a sparse file's
+// header included), on all host threads: the Python block loop of the driver took five times as long as parsing the table.
+extern "C" int bear_count_newlines(const char *path, uint64_t *n_out) {
+  return count_file(path, n_out, [](const char *b, const char *e) {
+    populate_read(b, e);
+    uint64_t n = 0;
+    for (const char *p = b; p < e; ++p) n += *p == '\n';
+    return n;
+  });
+}
+
+// ------------------------------------------------------------------ the table readers
 namespace {
-// Parses the lines of [p, end) into rows row .. ; returns the status and the number of rows written.
+struct table_dst {   // kmers [host, nullable] char [max_rows, lag], counts [host] uint32 [num_ds, max_rows, RW]
+  int num_ds, lag;
+  uint64_t max_rows;
+  char *kmers;
+  uint32_t *counts;
+};
+
+// Parses the lines of [p, end) into rows row .. row_limit - 1 of t; returns the status and the number of rows written.
 // `keep(g)` (g = index of the line among the non-blank lines of [p, end), counted from g0) selects the lines that are decoded;
 // the others are skipped at memchr speed.  Kept lines fill consecutive rows.
-struct keep_all {
-  bool operator()(uint64_t) const { return true; }
-};
 // RW: the row width (BEAR_ROW_WIDTH; 21 for the protein alphabet, bear_parse_counts_tsv_wide).
-template <class Keep, int RW = BEAR_ROW_WIDTH>
-int parse_range(const char *p, const char *end, int num_ds, int lag, uint64_t max_rows, uint64_t row, uint64_t row_limit,
-                char *kmers, uint32_t *counts, uint64_t *rows_done, uint64_t g0 = 0, Keep keep = Keep()) {
-  const int per_row = num_ds * RW;
+template <int RW, class Keep>
+int parse_range(const char *p, const char *end, const table_dst t, uint64_t row, uint64_t row_limit, uint64_t *rows_done, uint64_t g0,
+                const Keep keep) {   // t and keep by value: the row loop holds them in registers across its stores
+  const int per_row = t.num_ds * RW, lag = t.lag;
   const uint64_t row_begin = row;
   uint64_t g = g0;
   while (p < end && row < row_limit) {
-    const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
-    const char *le = nl ? nl : end;
-    if (blank_line(p, le)) {
-      p = le + 1;
-      continue;
-    }
-    if (!keep(g++)) {
-      p = le + 1;
-      continue;
-    }
-    const char *tab = static_cast<const char *>(memchr(p, '\t', (size_t)(le - p)));
-    if (!tab || (tab - p) != lag) return BEAR_ERR_PARSE;
-    if (kmers) memcpy(kmers + row * (uint64_t)lag, p, (size_t)lag);
+    const line l = line_at(p, end);
+    const char *le = l.e;
+    p = l.next;
+    if (blank_line(l.b, le) || !keep(g++)) continue;
+    const char *tab = static_cast<const char *>(memchr(l.b, '\t', (size_t)(le - l.b)));
+    if (!tab || (tab - l.b) != lag) return BEAR_ERR_PARSE;
+    if (t.kmers) memcpy(t.kmers + row * (uint64_t)lag, l.b, (size_t)lag);
     const char *q = tab + 1;
     int got = 0;
     while (q < le) {
@@ -116,7 +219,7 @@ int parse_range(const char *p, const char *end, int num_ds, int lag, uint64_t ma
         }
         if (got >= per_row) return BEAR_ERR_PARSE;
         const int ds = got / RW, b = got % RW;
-        counts[((uint64_t)ds * max_rows + row) * RW + b] = (uint32_t)v;
+        t.counts[((uint64_t)ds * t.max_rows + row) * RW + b] = (uint32_t)v;
         ++got;
       } else if (ch == '[' || ch == ']' || ch == ',' || ch == ' ' || ch == '\r') {
         ++q;
@@ -126,139 +229,115 @@ int parse_range(const char *p, const char *end, int num_ds, int lag, uint64_t ma
     }
     if (got != per_row) return BEAR_ERR_PARSE;
     ++row;
-    p = le + 1;
   }
   *rows_done = row - row_begin;
   return BEAR_OK;
 }
 
-uint64_t count_lines(const char *p, const char *end) {
-  uint64_t n = 0;
-  while (p < end) {
-    const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
-    const char *le = nl ? nl : end;
-    if (!blank_line(p, le)) ++n;
-    p = le + 1;
+// Where a line lands -- the one thing the two readers differ in.  A placement has
+//   counts_first   whether it needs the file's row count even when one thread reads the file;
+//   begin(n)       called with that count (UINT64_MAX when it was not taken) before any row is decoded: may refuse;
+//   span(g0, g1)   the output rows [out0, out1) of the file's non-blank lines [g0, g1);
+//   operator()(g)  whether line g is decoded.
+// The plain reader: line g is row g, up to max_rows.  A line at or beyond max_rows is not decoded and a chunk wholly beyond it
+// is not looked at, so a malformed row there is not an error.
+struct keep_all {
+  static constexpr bool counts_first = false;
+  uint64_t max_rows;
+  int begin(uint64_t) const { return BEAR_OK; }
+  void span(uint64_t g0, uint64_t g1, uint64_t *out0, uint64_t *out1) const {
+    *out0 = g0;
+    *out1 = g1 < max_rows ? g1 : max_rows;
   }
-  return n;
-}
-}  // namespace
+  bool operator()(uint64_t) const { return true; }
+};
 
-// Non-blank lines of a mapped text, one chunk (cut at a line start) per hardware thread: the row count of a 5 GB table is a
-// pass at memory speed instead of half a second of one thread's memchr.
-static uint64_t count_lines_mt(const char *base, size_t size) {
-  const char *end = base + size;
-  unsigned nt = std::thread::hardware_concurrency();
-  if (const char *env = getenv("BEAR_PARSE_THREADS")) nt = (unsigned)atoi(env);
-  if (nt < 1) nt = 1;
-  if (nt > BEAR_MAX_HOST_THREADS) nt = BEAR_MAX_HOST_THREADS;
-  if (size < (size_t)(1u << 20)) nt = 1;
-  if (nt == 1) return count_lines(base, end);
-  std::vector<const char *> cut(nt + 1);
-  cut[0] = base;
-  cut[nt] = end;
-  for (unsigned k = 1; k < nt; ++k) {
-    const char *p = base + (size / nt) * k;
-    const char *nl = p < end ? static_cast<const char *>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-    cut[k] = nl ? nl + 1 : end;
-    if (cut[k] < cut[k - 1]) cut[k] = cut[k - 1];
+// One rank's rows of a row-sharded table.
+// Training shards every batch over the ranks (bear_net.py:273 `experimental_distribute_dataset`): of batch k = global rows
+// [kB, min(kB + B, N)) with m rows, rank r owns the contiguous piece [lo, hi) with base = m / W, extra = m % W,
+// lo = r base + min(r, extra), hi = lo + base + (r < extra)  (bear_amd.dist.shard_rows).  A rank decodes only its own lines;
+// the other lines are stepped over at memchr speed, so W ranks decode 1/W of the text each.
+struct shard_map {
+  uint64_t B, N, W, r;
+  void piece(uint64_t m, uint64_t *lo, uint64_t *hi) const {
+    const uint64_t base = m / W, extra = m % W;
+    *lo = r * base + (r < extra ? r : extra);
+    *hi = *lo + base + (r < extra ? 1 : 0);
   }
-  std::vector<uint64_t> part(nt, 0);
-  std::vector<std::thread> th;
-  for (unsigned k = 0; k < nt; ++k) th.emplace_back([&, k] { part[k] = count_lines(cut[k], cut[k + 1]); });
-  for (auto &t : th) t.join();
-  uint64_t n = 0;
-  for (unsigned k = 0; k < nt; ++k) n += part[k];
-  return n;
-}
-
-// `wc -l` of a file (the reference's num_kmers, models/train_bear_net.py:52-55: newline bytes, blank lines and a sparse file's
-// header included), on all host threads: the Python block loop of the driver took five times as long as parsing the table.
-extern "C" int bear_count_newlines(const char *path, uint64_t *n_out) {
-  if (!path || !n_out) return BEAR_ERR_INVALID_ARG;
-  mapped_file f;
-  int st = f.open_ro(path);
-  if (st != BEAR_OK) return st;
-  unsigned nt = std::thread::hardware_concurrency();
-  if (const char *env = getenv("BEAR_PARSE_THREADS")) nt = (unsigned)atoi(env);
-  if (nt < 1) nt = 1;
-  if (nt > BEAR_MAX_HOST_THREADS) nt = BEAR_MAX_HOST_THREADS;
-  if (f.size < (size_t)(1u << 20)) nt = 1;
-  std::vector<uint64_t> part(nt, 0);
-  auto count = [&](unsigned k) {
-    const char *b = f.data + (f.size / nt) * k, *e = k + 1 == nt ? f.data + f.size : f.data + (f.size / nt) * (k + 1);
-    populate_read(b, e);
-    uint64_t n = 0;
-    for (const char *p = b; p < e; ++p) n += *p == '\n';
-    part[k] = n;
-  };
-  if (nt == 1) count(0);
-  else {
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nt; ++k) th.emplace_back(count, k);
-    for (auto &t : th) t.join();
+  bool member(uint64_t g) const {
+    if (g >= N) return false;
+    const uint64_t a = (g / B) * B, m = (N - a < B) ? N - a : B;
+    uint64_t lo, hi;
+    piece(m, &lo, &hi);
+    return g - a >= lo && g - a < hi;
   }
-  uint64_t n = 0;
-  for (unsigned k = 0; k < nt; ++k) n += part[k];
-  *n_out = n;
-  return BEAR_OK;
-}
+  uint64_t below(uint64_t G) const {   // number of member rows with global index < G
+    if (G > N) G = N;
+    uint64_t lo, hi;
+    piece(B, &lo, &hi);
+    const uint64_t k = G / B, a = k * B;
+    uint64_t n = k * (hi - lo);
+    if (a < N) {
+      const uint64_t m = (N - a < B) ? N - a : B, off = G - a;
+      piece(m, &lo, &hi);
+      n += off <= lo ? 0 : (off >= hi ? hi - lo : off - lo);
+    }
+    return n;
+  }
+};
+// The sharded reader: line g is global row row_base + g, decoded if the rank owns it, into the row that counts the rank's rows
+// in front of it (shard_map::below per chunk).
+struct keep_shard {
+  static constexpr bool counts_first = true;
+  shard_map S;
+  uint64_t row_base, max_rows, *n_file_rows_out;
+  uint64_t l0 = 0;   // the rank's rows in front of this file
+  int begin(uint64_t file_rows) {
+    if (n_file_rows_out) *n_file_rows_out = file_rows;
+    if (row_base + file_rows > S.N) return BEAR_ERR_INVALID_ARG;   // the caller's row count does not match the file
+    l0 = S.below(row_base);
+    return S.below(row_base + file_rows) - l0 > max_rows ? BEAR_ERR_INVALID_ARG : BEAR_OK;
+  }
+  void span(uint64_t g0, uint64_t g1, uint64_t *out0, uint64_t *out1) const {
+    *out0 = S.below(row_base + g0) - l0;
+    *out1 = S.below(row_base + g1) - l0;
+  }
+  bool operator()(uint64_t g) const { return S.member(row_base + g); }
+};
 
 // Text decoding is the first-epoch cost of a large table (~60-80 GB of text at 1e9 rows), so the file is
 // cut at line boundaries into one chunk per hardware thread: pass 1 counts the rows of each chunk, a prefix sum gives
-// every chunk its first row, pass 2 parses the chunks in place into the shared output arrays.
-template <int RW>
-static int parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_rows, char *kmers, uint32_t *counts,
-                            uint64_t *n_rows_out) {
-  if (!path || !counts || !n_rows_out || num_ds < 1 || lag < 0) return BEAR_ERR_INVALID_ARG;
-  *n_rows_out = 0;
+// every chunk its first row, pass 2 parses the chunks in place into the shared output arrays.  One thread whose placement does
+// not ask for the row count reads the file once: its only chunk starts at row 0 and ends where the placement says.
+template <int RW, class Place>
+int read_table(const char *path, uint64_t skip_lines, const table_dst &t, uint64_t *n_rows_out, Place place) {
   mapped_file f;
   int st = f.open_ro(path);
   if (st != BEAR_OK) return st;
   const char *base = f.data, *end = f.data + f.size;
-  unsigned nt = std::thread::hardware_concurrency();
-  if (const char *env = getenv("BEAR_PARSE_THREADS")) nt = (unsigned)atoi(env);
-  if (nt < 1) nt = 1;
-  if (nt > BEAR_MAX_HOST_THREADS) nt = BEAR_MAX_HOST_THREADS;
-  if (f.size < (size_t)(1u << 20)) nt = 1;           // small files: not worth the threads
-  // chunk boundaries at line starts
-  std::vector<const char *> cut(nt + 1);
-  cut[0] = base;
-  cut[nt] = end;
-  for (unsigned k = 1; k < nt; ++k) {
-    const char *p = base + (f.size / nt) * k;
-    const char *nl = p < end ? static_cast<const char *>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-    cut[k] = nl ? nl + 1 : end;
-    if (cut[k] < cut[k - 1]) cut[k] = cut[k - 1];
-  }
+  for (uint64_t k = 0; k < skip_lines && base < end; ++k) base = line_at(base, end).next;   // header lines (dataloader.py:7 `header`)
+  const unsigned nt = text_threads((size_t)(end - base));
+  const std::vector<const char *> cut = cut_at_lines(base, end, nt);
   std::vector<uint64_t> first(nt + 1, 0), done(nt, 0);
   std::vector<int> status(nt, BEAR_OK);
-  if (nt == 1) {
-    st = parse_range<keep_all, RW>(base, end, num_ds, lag, max_rows, 0, max_rows, kmers, counts, &done[0]);
+  if (nt > 1 || Place::counts_first) {
+    st = run_chunks(nt, [&](unsigned k) {
+      populate_read(cut[k], cut[k + 1]);
+      first[k + 1] = count_lines(cut[k], cut[k + 1]);
+    });
     if (st != BEAR_OK) return st;
-    *n_rows_out = done[0];
-    return BEAR_OK;
+    for (unsigned k = 0; k < nt; ++k) first[k + 1] += first[k];
+  } else {
+    first[1] = UINT64_MAX;
   }
-  {
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nt; ++k)
-      th.emplace_back([&, k] {
-        populate_read(cut[k], cut[k + 1]);
-        first[k + 1] = count_lines(cut[k], cut[k + 1]);
-      });
-    for (auto &t : th) t.join();
-  }
-  for (unsigned k = 0; k < nt; ++k) first[k + 1] += first[k];
-  {
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nt; ++k)
-      th.emplace_back([&, k] {
-        const uint64_t lim = first[k + 1] < max_rows ? first[k + 1] : max_rows;
-        if (first[k] >= lim) return;
-        status[k] = parse_range<keep_all, RW>(cut[k], cut[k + 1], num_ds, lag, max_rows, first[k], lim, kmers, counts, &done[k]);
-      });
-    for (auto &t : th) t.join();
-  }
+  st = place.begin(first[nt]);
+  if (st != BEAR_OK) return st;
+  st = run_chunks(nt, [&](unsigned k) {
+    uint64_t out0, out1;
+    place.span(first[k], first[k + 1], &out0, &out1);
+    if (out0 < out1) status[k] = parse_range<RW>(cut[k], cut[k + 1], t, out0, out1, &done[k], first[k], place);
+  });
+  if (st != BEAR_OK) return st;
   uint64_t total = 0;
   for (unsigned k = 0; k < nt; ++k) {
     if (status[k] != BEAR_OK) return status[k];
@@ -268,25 +347,59 @@ static int parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_
   return BEAR_OK;
 }
 
-extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_rows, char *kmers,
-                                     uint32_t *counts, uint64_t *n_rows_out) {
-  return parse_counts_tsv<BEAR_ROW_WIDTH>(path, num_ds, lag, max_rows, kmers, counts, n_rows_out);
+// The width instantiation of read_table for all four entries.
+template <class Place>
+int read_table_of(int width, const char *path, uint64_t skip_lines, const table_dst &t, uint64_t *n_rows_out, const Place &place) {
+  if (!path || !t.counts || !n_rows_out || t.num_ds < 1 || t.lag < 0) return BEAR_ERR_INVALID_ARG;
+  *n_rows_out = 0;
+  return guarded([&] {
+    if (width == BEAR_ROW_WIDTH) return read_table<BEAR_ROW_WIDTH>(path, skip_lines, t, n_rows_out, place);
+    if (width == 21) return read_table<21>(path, skip_lines, t, n_rows_out, place);
+    return (int)BEAR_ERR_INVALID_ARG;
+  });
 }
+}  // namespace
 
 extern "C" int bear_parse_counts_tsv_wide(const char *path, int num_ds, int width, int lag, uint64_t max_rows, char *kmers,
                                           uint32_t *counts, uint64_t *n_rows_out) {
-  if (width == BEAR_ROW_WIDTH) return parse_counts_tsv<BEAR_ROW_WIDTH>(path, num_ds, lag, max_rows, kmers, counts, n_rows_out);
-  if (width == 21) return parse_counts_tsv<21>(path, num_ds, lag, max_rows, kmers, counts, n_rows_out);
-  return BEAR_ERR_INVALID_ARG;
+  return read_table_of(width, path, 0, table_dst{num_ds, lag, max_rows, kmers, counts}, n_rows_out, keep_all{max_rows});
+}
+
+extern "C" int bear_parse_counts_tsv(const char *path, int num_ds, int lag, uint64_t max_rows, char *kmers,
+                                     uint32_t *counts, uint64_t *n_rows_out) {
+  return bear_parse_counts_tsv_wide(path, num_ds, BEAR_ROW_WIDTH, lag, max_rows, kmers, counts, n_rows_out);
+}
+
+extern "C" int bear_shard_rows_count(uint64_t row_base, uint64_t file_rows, uint64_t total_rows, uint64_t batch_rows, int rank,
+                                     int world, uint64_t *n_local_out) {
+  if (!n_local_out || batch_rows == 0 || world < 1 || rank < 0 || rank >= world || row_base + file_rows > total_rows)
+    return BEAR_ERR_INVALID_ARG;
+  const shard_map S{batch_rows, total_rows, (uint64_t)world, (uint64_t)rank};
+  *n_local_out = S.below(row_base + file_rows) - S.below(row_base);
+  return BEAR_OK;
+}
+
+extern "C" int bear_parse_counts_tsv_shard_wide(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t row_base,
+                                                uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
+                                                char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
+  if (batch_rows == 0 || world < 1 || rank < 0 || rank >= world) return BEAR_ERR_INVALID_ARG;
+  const shard_map S{batch_rows, total_rows, (uint64_t)world, (uint64_t)rank};
+  return read_table_of(width, path, skip_lines, table_dst{num_ds, lag, max_rows, kmers, counts}, n_local_out,
+                       keep_shard{S, row_base, max_rows, n_file_rows_out});
+}
+
+extern "C" int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base,
+                                           uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
+                                           char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
+  return bear_parse_counts_tsv_shard_wide(path, num_ds, BEAR_ROW_WIDTH, lag, skip_lines, row_base, total_rows, batch_rows, rank, world,
+                                          max_rows, kmers, counts, n_local_out, n_file_rows_out);
 }
 
 // ------------------------------------------------------------------ the sparse row format
 // `kmer; [[ds, col], ...]; [value, ...]` (bear_model/dataloader.py:52-109: CsvDataset with ';' + two decode_json calls +
 // SparseTensor -> to_dense).  One pass over the mapped text; rows land in the same planar layout as the dense reader's.
-extern "C" int bear_parse_sparse_counts(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t max_rows,
-                                        char *kmers, uint32_t *counts, uint64_t *n_rows_out) {
-  if (!path || !n_rows_out || num_ds < 1 || width < 1 || lag < 0 || (max_rows && (!counts || (lag && !kmers)))) return BEAR_ERR_INVALID_ARG;
-  *n_rows_out = 0;
+static int parse_sparse_counts(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t max_rows, char *kmers,
+                               uint32_t *counts, uint64_t *n_rows_out) {
   mapped_file f;
   int st = f.open_ro(path);
   if (st != BEAR_OK) return st;
@@ -295,10 +408,9 @@ extern "C" int bear_parse_sparse_counts(const char *path, int num_ds, int width,
   uint64_t row = 0, line_no = 0;
   std::vector<long long> pos;
   while (p < end && row < max_rows) {
-    const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
-    const char *le = nl ? nl : end;
-    const char *q = p;
-    p = le + 1;
+    const line l = line_at(p, end);
+    const char *q = l.b, *le = l.e;
+    p = l.next;
     if (line_no++ < skip_lines || blank_line(q, le)) continue;
     const char *s1 = static_cast<const char *>(memchr(q, ';', (size_t)(le - q)));
     const char *s2 = s1 ? static_cast<const char *>(memchr(s1 + 1, ';', (size_t)(le - s1 - 1))) : nullptr;
@@ -343,147 +455,17 @@ extern "C" int bear_parse_sparse_counts(const char *path, int num_ds, int width,
   return BEAR_OK;
 }
 
-// ------------------------------------------------------------------ one rank's rows of a row-sharded table
-// Training shards every batch over the ranks (bear_net.py:273 `experimental_distribute_dataset`): of batch k = global rows
-// [kB, min(kB + B, N)) with m rows, rank r owns the contiguous piece [lo, hi) with base = m / W, extra = m % W,
-// lo = r base + min(r, extra), hi = lo + base + (r < extra)  (bear_amd.dist.shard_rows).  A rank decodes only its own lines;
-// the other lines are stepped over at memchr speed, so W ranks decode 1/W of the text each.
-namespace {
-struct shard_map {
-  uint64_t B, N, W, r;
-  void piece(uint64_t m, uint64_t *lo, uint64_t *hi) const {
-    const uint64_t base = m / W, extra = m % W;
-    *lo = r * base + (r < extra ? r : extra);
-    *hi = *lo + base + (r < extra ? 1 : 0);
-  }
-  bool member(uint64_t g) const {
-    if (g >= N) return false;
-    const uint64_t a = (g / B) * B, m = (N - a < B) ? N - a : B;
-    uint64_t lo, hi;
-    piece(m, &lo, &hi);
-    return g - a >= lo && g - a < hi;
-  }
-  uint64_t below(uint64_t G) const {   // number of member rows with global index < G
-    if (G > N) G = N;
-    uint64_t lo, hi;
-    piece(B, &lo, &hi);
-    const uint64_t k = G / B, a = k * B;
-    uint64_t n = k * (hi - lo);
-    if (a < N) {
-      const uint64_t m = (N - a < B) ? N - a : B, off = G - a;
-      piece(m, &lo, &hi);
-      n += off <= lo ? 0 : (off >= hi ? hi - lo : off - lo);
-    }
-    return n;
-  }
-};
-struct keep_shard {
-  shard_map S;
-  uint64_t row_base;
-  bool operator()(uint64_t g) const { return S.member(row_base + g); }
-};
-}  // namespace
-
-extern "C" int bear_shard_rows_count(uint64_t row_base, uint64_t file_rows, uint64_t total_rows, uint64_t batch_rows, int rank,
-                                     int world, uint64_t *n_local_out) {
-  if (!n_local_out || batch_rows == 0 || world < 1 || rank < 0 || rank >= world || row_base + file_rows > total_rows)
-    return BEAR_ERR_INVALID_ARG;
-  const shard_map S{batch_rows, total_rows, (uint64_t)world, (uint64_t)rank};
-  *n_local_out = S.below(row_base + file_rows) - S.below(row_base);
-  return BEAR_OK;
-}
-
-template <int RW>
-static int parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base, uint64_t total_rows,
-                                  uint64_t batch_rows, int rank, int world, uint64_t max_rows, char *kmers, uint32_t *counts,
-                                  uint64_t *n_local_out, uint64_t *n_file_rows_out) {
-  if (!path || !counts || !n_local_out || num_ds < 1 || lag < 0 || batch_rows == 0 || world < 1 || rank < 0 || rank >= world)
-    return BEAR_ERR_INVALID_ARG;
-  *n_local_out = 0;
-  mapped_file f;
-  int st = f.open_ro(path);
-  if (st != BEAR_OK) return st;
-  const char *base = f.data, *end = f.data + f.size;
-  for (uint64_t k = 0; k < skip_lines && base < end; ++k) {   // header lines (dataloader.py:7 `header`)
-    const char *nl = static_cast<const char *>(memchr(base, '\n', (size_t)(end - base)));
-    base = nl ? nl + 1 : end;
-  }
-  const size_t body = (size_t)(end - base);
-  unsigned nt = std::thread::hardware_concurrency();
-  if (const char *env = getenv("BEAR_PARSE_THREADS")) nt = (unsigned)atoi(env);
-  if (nt < 1) nt = 1;
-  if (nt > BEAR_MAX_HOST_THREADS) nt = BEAR_MAX_HOST_THREADS;
-  if (body < (size_t)(1u << 20)) nt = 1;
-  std::vector<const char *> cut(nt + 1);
-  cut[0] = base;
-  cut[nt] = end;
-  for (unsigned k = 1; k < nt; ++k) {
-    const char *p = base + (body / nt) * k;
-    const char *nl = p < end ? static_cast<const char *>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-    cut[k] = nl ? nl + 1 : end;
-    if (cut[k] < cut[k - 1]) cut[k] = cut[k - 1];
-  }
-  std::vector<uint64_t> first(nt + 1, 0), done(nt, 0);
-  std::vector<int> status(nt, BEAR_OK);
-  {
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nt; ++k)
-      th.emplace_back([&, k] {
-        populate_read(cut[k], cut[k + 1]);
-        first[k + 1] = count_lines(cut[k], cut[k + 1]);
-      });
-    for (auto &t : th) t.join();
-  }
-  for (unsigned k = 0; k < nt; ++k) first[k + 1] += first[k];
-  const uint64_t file_rows = first[nt];
-  if (n_file_rows_out) *n_file_rows_out = file_rows;
-  if (row_base + file_rows > total_rows) return BEAR_ERR_INVALID_ARG;   // the caller's row count does not match the file
-  const shard_map S{batch_rows, total_rows, (uint64_t)world, (uint64_t)rank};
-  const uint64_t l0 = S.below(row_base);
-  if (S.below(row_base + file_rows) - l0 > max_rows) return BEAR_ERR_INVALID_ARG;
-  {
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nt; ++k)
-      th.emplace_back([&, k] {
-        const uint64_t out0 = S.below(row_base + first[k]) - l0, out1 = S.below(row_base + first[k + 1]) - l0;
-        if (out0 >= out1) return;
-        status[k] = parse_range<keep_shard, RW>(cut[k], cut[k + 1], num_ds, lag, max_rows, out0, out1, kmers, counts, &done[k], first[k],
-                                                keep_shard{S, row_base});
-      });
-    for (auto &t : th) t.join();
-  }
-  uint64_t total = 0;
-  for (unsigned k = 0; k < nt; ++k) {
-    if (status[k] != BEAR_OK) return status[k];
-    total += done[k];
-  }
-  *n_local_out = total;
-  return BEAR_OK;
-}
-
-extern "C" int bear_parse_counts_tsv_shard(const char *path, int num_ds, int lag, uint64_t skip_lines, uint64_t row_base,
-                                           uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
-                                           char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
-  return parse_counts_tsv_shard<BEAR_ROW_WIDTH>(path, num_ds, lag, skip_lines, row_base, total_rows, batch_rows, rank, world, max_rows,
-                                                kmers, counts, n_local_out, n_file_rows_out);
-}
-
-extern "C" int bear_parse_counts_tsv_shard_wide(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t row_base,
-                                                uint64_t total_rows, uint64_t batch_rows, int rank, int world, uint64_t max_rows,
-                                                char *kmers, uint32_t *counts, uint64_t *n_local_out, uint64_t *n_file_rows_out) {
-  if (width == BEAR_ROW_WIDTH)
-    return parse_counts_tsv_shard<BEAR_ROW_WIDTH>(path, num_ds, lag, skip_lines, row_base, total_rows, batch_rows, rank, world, max_rows,
-                                                  kmers, counts, n_local_out, n_file_rows_out);
-  if (width == 21)
-    return parse_counts_tsv_shard<21>(path, num_ds, lag, skip_lines, row_base, total_rows, batch_rows, rank, world, max_rows, kmers,
-                                      counts, n_local_out, n_file_rows_out);
-  return BEAR_ERR_INVALID_ARG;
+extern "C" int bear_parse_sparse_counts(const char *path, int num_ds, int width, int lag, uint64_t skip_lines, uint64_t max_rows,
+                                        char *kmers, uint32_t *counts, uint64_t *n_rows_out) {
+  if (!path || !n_rows_out || num_ds < 1 || width < 1 || lag < 0 || (max_rows && (!counts || (lag && !kmers)))) return BEAR_ERR_INVALID_ARG;
+  *n_rows_out = 0;
+  return guarded([&] { return parse_sparse_counts(path, num_ds, width, lag, skip_lines, max_rows, kmers, counts, n_rows_out); });
 }
 
 // ------------------------------------------------------------------ binary cache of a parsed table
 // The reference decodes the text of every file again in every process and keeps the tensors in host RAM
 // (dataloader.py:47-48, `.cache()`); at 1e9 rows the text is 60-80 GB and decoding it is the first-epoch cost.
-// The cache is the parsed table as it is uploaded: header, k-mer bytes, planar uint32 slabs.
+// The cache is the parsed table as it is uploaded: header, k-mer bytes, planar uint32 slabs.  (Nothing here throws.)
 namespace {
 struct cache_header {
   char magic[8];          // "BEARCT01"
@@ -644,46 +626,37 @@ inline char *format_row(char *o, const char *kmers, const uint32_t *counts, uint
   *o++ = '\n';
   return o;
 }
-}  // namespace
 
-// Two passes over the selected rows, both cut into one contiguous range per hardware thread: the byte length of every range
-// (digit counting), a prefix sum, then each thread formats its range into 4 MiB pieces and writes them at its own file offset
-// (pwrite) -- the text of a 1e8-row, three-column table (5 GB) in seconds instead of the half minute of one thread.
-static int write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag, int num_ds, int width,
-                            uint64_t row_begin, uint64_t row_step, int append) {
-  if (!path || !counts || (!kmers && lag > 0 && n_rows) || lag < 0 || num_ds < 1 || row_step == 0) return BEAR_ERR_INVALID_ARG;
-  const int fd = open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
+struct out_file {   // closed when the writer leaves early
+  int fd;
+  ~out_file() {
+    if (fd >= 0) ::close(fd);
+  }
+};
+
+// Two passes over the selected rows, both cut into one contiguous range per thread (at least 64 Ki rows each): the byte length of
+// every range (digit counting), a prefix sum, then each thread formats its range into 4 MiB pieces and writes them at its own file
+// offset (pwrite) -- the text of a 1e8-row, three-column table (5 GB) in seconds instead of the half minute of one thread.
+int write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag, int num_ds, int width,
+                     uint64_t row_begin, uint64_t row_step, int append) {
+  out_file f{open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644)};
+  const int fd = f.fd;
   if (fd < 0) return BEAR_ERR_IO;
   off_t base = 0;
-  if (append) {
-    base = lseek(fd, 0, SEEK_END);
-    if (base < 0) {
-      close(fd);
-      return BEAR_ERR_IO;
-    }
-  }
+  if (append && (base = lseek(fd, 0, SEEK_END)) < 0) return BEAR_ERR_IO;
   const uint64_t n_sel = row_begin < n_rows ? (n_rows - row_begin + row_step - 1) / row_step : 0;   // rows row_begin + i row_step
-  unsigned nt = std::thread::hardware_concurrency();
-  if (nt == 0) nt = 1;
-  if (nt > BEAR_MAX_HOST_THREADS) nt = BEAR_MAX_HOST_THREADS;
-  if ((uint64_t)nt > (n_sel + 65535) / 65536) nt = (unsigned)((n_sel + 65535) / 65536);   // at least 64 Ki rows per thread
-  if (nt == 0) nt = 1;
+  const unsigned nt = host_threads((n_sel + 65535) / 65536);
   std::vector<uint64_t> first(nt + 1), bytes(nt + 1, 0);
   for (unsigned t = 0; t <= nt; ++t) first[t] = n_sel * t / nt;
-  auto measure = [&](unsigned t) {
+  int st = run_chunks(nt, [&](unsigned t) {
     size_t n = 0;
     for (uint64_t i = first[t]; i < first[t + 1]; ++i) n += row_bytes(counts, n_rows, row_begin + i * row_step, lag, num_ds, width);
     bytes[t + 1] = n;
-  };
-  {
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; ++t) th.emplace_back(measure, t);
-    measure(0);
-    for (auto &x : th) x.join();
-  }
+  });
+  if (st != BEAR_OK) return st;
   for (unsigned t = 0; t < nt; ++t) bytes[t + 1] += bytes[t];
   std::vector<int> status(nt, BEAR_OK);
-  auto emit = [&](unsigned t) {
+  st = run_chunks(nt, [&](unsigned t) {
     static const size_t PIECE = 4u << 20;
     const size_t slack = 64 + (size_t)lag + (size_t)num_ds * (4 + 11 * (size_t)width);   // one row beyond PIECE at most
     char *buf = static_cast<char *>(malloc(PIECE + slack));
@@ -713,29 +686,25 @@ static int write_counts_tsv(const char *path, const char *kmers, const uint32_t 
     if (status[t] == BEAR_OK && o != buf) flush();
     if (status[t] == BEAR_OK && at != base + (off_t)bytes[t + 1]) status[t] = BEAR_ERR_IO;   // the two passes disagree: never silently
     free(buf);
-  };
-  {
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; ++t) th.emplace_back(emit, t);
-    emit(0);
-    for (auto &x : th) x.join();
-  }
-  int st = BEAR_OK;
+  });
   for (unsigned t = 0; t < nt; ++t)
     if (status[t] != BEAR_OK) st = status[t];
+  f.fd = -1;
   if (close(fd) != 0 && st == BEAR_OK) st = BEAR_ERR_IO;
   return st;
+}
+}  // namespace
+
+extern "C" int bear_write_counts_tsv_wide(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag,
+                                          int num_ds, int width, uint64_t row_begin, uint64_t row_step, int append) {
+  if (!path || !counts || (!kmers && lag > 0 && n_rows) || lag < 0 || num_ds < 1 || row_step == 0 || (width != 5 && width != 21))
+    return BEAR_ERR_INVALID_ARG;
+  return guarded([&] { return write_counts_tsv(path, kmers, counts, n_rows, lag, num_ds, width, row_begin, row_step, append); });
 }
 
 extern "C" int bear_write_counts_tsv(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag,
                                      int num_ds, uint64_t row_begin, uint64_t row_step, int append) {
-  return write_counts_tsv(path, kmers, counts, n_rows, lag, num_ds, BEAR_ROW_WIDTH, row_begin, row_step, append);
-}
-
-extern "C" int bear_write_counts_tsv_wide(const char *path, const char *kmers, const uint32_t *counts, uint64_t n_rows, int lag,
-                                          int num_ds, int width, uint64_t row_begin, uint64_t row_step, int append) {
-  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
-  return write_counts_tsv(path, kmers, counts, n_rows, lag, num_ds, width, row_begin, row_step, append);
+  return bear_write_counts_tsv_wide(path, kmers, counts, n_rows, lag, num_ds, BEAR_ROW_WIDTH, row_begin, row_step, append);
 }
 
 // ------------------------------------------------------------------ FASTA / FASTQ -> device code text (summarize path)
@@ -744,41 +713,30 @@ extern "C" int bear_write_counts_tsv_wide(const char *path, const char *kmers, c
 // `reverse` every sequence is followed by its reverse complement (summarize.py:202-207).  Two calls: size, then fill.
 // The `_wide` twins take the row width of the alphabet: 5 is the text above; 21 is the protein text -- start marker 21, residues
 // ARNDCEQGHILKMFPSTWYV -> 0..19 (any other character 22), stop 20, no reverse complement.  A '*' that ends a record is the stop
-// the encoder writes anyway and is left out (by both passes); a '*' anywhere else is an ordinary "other" character.
+// the encoder writes anyway and is left out; a '*' anywhere else is an ordinary "other" character.
 namespace {
-struct prot_lut {
+struct code_lut {   // letters (either case) -> 0 .., every other character -> `other`
   uint8_t code[256];
-  prot_lut() {
-    memset(code, 22, sizeof code);
-    const char *letters = "ARNDCEQGHILKMFPSTWYV";
-    for (int i = 0; i < 20; ++i) {
+  code_lut(const char *letters, uint8_t other) {
+    memset(code, other, sizeof code);
+    for (int i = 0; letters[i]; ++i) {
       code[(unsigned char)letters[i]] = (uint8_t)i;
       code[(unsigned char)(letters[i] + ('a' - 'A'))] = (uint8_t)i;
     }
   }
 };
-const prot_lut PROT_LUT;
+const code_lut DNA_LUT("ACGT", 6), PROT_LUT("ARNDCEQGHILKMFPSTWYV", 22);
 
-inline uint8_t letter_code(unsigned char ch) {
-  switch (ch) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-    default: return 6;
-  }
-}
-
-// Calls emit(begin, end) for every sequence line-segment and flush() at the end of each record.
+// Calls seg(begin, end) for every sequence line-segment and end_record() at the end of each record.
 template <class Seg, class End>
 int walk_fastx(const mapped_file &f, int fastq, Seg seg, End end_record) {
   const char *p = f.data, *end = f.data + f.size;
   auto next_line = [&](const char *&b, const char *&e) {
     if (p >= end) return false;
-    const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
-    b = p;
-    e = nl ? nl : end;
-    p = e + 1;
+    const line l = line_at(p, end);
+    b = l.b;
+    e = l.e;
+    p = l.next;
     if (e > b && e[-1] == '\r') --e;
     return true;
   };
@@ -810,108 +768,109 @@ int walk_fastx(const mapped_file &f, int fastq, Seg seg, End end_record) {
   }
   return BEAR_OK;
 }
-}  // namespace
 
-// width 5 or 21.  `prot`: a '*' is held back until the next character of the record arrives; the record's end drops it.
-static int fastx_size(const char *path, int fastq, int reverse, int width, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
-  if (!path || !n_pos_out || (width != 5 && width != 21) || (width == 21 && reverse)) return BEAR_ERR_INVALID_ARG;
-  mapped_file f;
-  int st = f.open_ro(path);
-  if (st != BEAR_OK) return st;
-  uint64_t letters = 0, seqs = 0;
-  bool last_star = false;      // the last character of the open record so far is a '*'
-  const bool prot = width == 21;
-  st = walk_fastx(
-      f, fastq,
-      [&](const char *b, const char *e) {
-        letters += (uint64_t)(e - b);
-        if (e > b) last_star = e[-1] == '*';
-      },
-      [&] {
-        ++seqs;
-        if (prot && last_star) --letters;
-        last_star = false;
-      });
-  if (st != BEAR_OK) return st;
-  const uint64_t mult = reverse ? 2 : 1;
-  *n_pos_out = mult * (letters + 2 * seqs);
-  if (n_seqs_out) *n_seqs_out = mult * seqs;
-  return BEAR_OK;
-}
-
-static int fastx_encode(const char *path, int fastq, int reverse, int width, int group, uint64_t capacity, uint8_t *text,
-                        uint8_t *group_out, uint64_t *n_pos_out) {
-  if (!path || !text || !n_pos_out || group < 0 || group > 254 || (width != 5 && width != 21) || (width == 21 && reverse))
-    return BEAR_ERR_INVALID_ARG;
-  mapped_file f;
-  int st = f.open_ro(path);
-  if (st != BEAR_OK) return st;
-  const bool prot = width == 21;
-  const uint8_t START = (uint8_t)width, STOP = (uint8_t)(width - 1);
+// Where the code text goes.  A sink takes single codes (put), the codes of a run of characters (run), the start of a record
+// (open) and, behind a DNA record's stop, the request for that record's reverse complement (mirror).
+struct fastx_count {   // the size pass: positions only
   uint64_t pos = 0, start = 0;
-  bool overflow = false, in_seq = false, held_star = false;
-  auto put = [&](uint8_t v) {
+  void put(uint8_t) { ++pos; }
+  void run(const char *b, const char *e, const uint8_t *) { pos += (uint64_t)(e - b); }
+  void open() { start = pos; }
+  void mirror() { pos += pos - start; }
+};
+struct fastx_store {   // the fill pass: stores within the capacity, goes on counting beyond it
+  uint8_t *text;
+  uint64_t capacity, pos = 0, start = 0;
+  bool overflow = false;
+  void put(uint8_t v) {
     if (pos < capacity) text[pos] = v;
     else overflow = true;
     ++pos;
+  }
+  void run(const char *b, const char *e, const uint8_t *code) {
+    for (; b < e; ++b) put(code[(unsigned char)*b]);
+  }
+  void open() { start = pos; }
+  void mirror() {   // read back from the stored record
+    if (overflow) return;
+    const uint64_t first = start + 1, last = pos - 1;   // letters in [first, last)
+    put(5);
+    for (uint64_t q = last; q > first; --q) {
+      const uint8_t c = text[q - 1];
+      put(c < 4 ? (uint8_t)(3 - c) : c);
+    }
+    put(4);
+  }
+};
+
+// The record rules, for both passes: start marker, the characters' codes, stop; an empty record is start + stop; with `reverse`
+// the record once more as its reverse complement.  A protein record's '*' at the end of a segment is held back until another
+// character of the record arrives (then it is the "other" code it maps to anyway); the record's end drops it.
+template <class Sink>
+int emit_fastx(const char *path, int fastq, int reverse, int width, Sink &out, uint64_t *n_seqs) {
+  if ((width != 5 && width != 21) || (width == 21 && reverse)) return BEAR_ERR_INVALID_ARG;
+  mapped_file f;
+  int st = f.open_ro(path);
+  if (st != BEAR_OK) return st;
+  const bool prot = width == 21;
+  const code_lut &lut = prot ? PROT_LUT : DNA_LUT;
+  const uint8_t START = (uint8_t)width, STOP = (uint8_t)(width - 1);
+  bool in_seq = false, held_star = false;
+  auto begin = [&] {
+    if (in_seq) return;
+    out.open();
+    out.put(START);
+    in_seq = true;
   };
-  st = walk_fastx(
+  return walk_fastx(
       f, fastq,
       [&](const char *b, const char *e) {
-        if (!in_seq) {
-          start = pos;
-          put(START);
-          in_seq = true;
-        }
-        if (!prot) {
-          for (const char *q = b; q < e; ++q) put(letter_code((unsigned char)*q));
-          return;
-        }
-        for (const char *q = b; q < e; ++q) {
-          if (held_star) put(22);          // it was not the record's last character
-          held_star = *q == '*';
-          if (!held_star) put(PROT_LUT.code[(unsigned char)*q]);
-        }
+        begin();
+        if (b == e) return;
+        if (held_star) out.put(lut.code[(unsigned char)'*']);   // it was not the record's last character
+        held_star = prot && e[-1] == '*';
+        out.run(b, held_star ? e - 1 : e, lut.code);
       },
       [&] {
-        if (!in_seq) {   // empty record: start + stop
-          start = pos;
-          put(START);
-        }
+        begin();
         held_star = false;
-        put(STOP);
+        out.put(STOP);
         in_seq = false;
-        if (reverse && !overflow) {
-          const uint64_t first = start + 1, last = pos - 1;   // letters in [first, last)
-          put(5);
-          for (uint64_t q = last; q > first; --q) {
-            const uint8_t c = text[q - 1];
-            put(c < 4 ? (uint8_t)(3 - c) : c);
-          }
-          put(4);
-        }
+        *n_seqs += reverse ? 2 : 1;
+        if (reverse) out.mirror();
       });
+}
+}  // namespace
+
+extern "C" int bear_fastx_size_wide(const char *path, int fastq, int reverse, int width, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
+  if (!path || !n_pos_out) return BEAR_ERR_INVALID_ARG;
+  fastx_count out;
+  uint64_t seqs = 0;
+  const int st = emit_fastx(path, fastq, reverse, width, out, &seqs);
   if (st != BEAR_OK) return st;
-  if (overflow) return BEAR_ERR_INVALID_ARG;
-  if (group_out) memset(group_out, group, (size_t)pos);
-  *n_pos_out = pos;
+  *n_pos_out = out.pos;
+  if (n_seqs_out) *n_seqs_out = seqs;
   return BEAR_OK;
 }
 
 extern "C" int bear_fastx_size(const char *path, int fastq, int reverse, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
-  return fastx_size(path, fastq, reverse, BEAR_ROW_WIDTH, n_pos_out, n_seqs_out);
-}
-
-extern "C" int bear_fastx_size_wide(const char *path, int fastq, int reverse, int width, uint64_t *n_pos_out, uint64_t *n_seqs_out) {
-  return fastx_size(path, fastq, reverse, width, n_pos_out, n_seqs_out);
-}
-
-extern "C" int bear_fastx_encode(const char *path, int fastq, int reverse, int group, uint64_t capacity, uint8_t *text,
-                                 uint8_t *group_out, uint64_t *n_pos_out) {
-  return fastx_encode(path, fastq, reverse, BEAR_ROW_WIDTH, group, capacity, text, group_out, n_pos_out);
+  return bear_fastx_size_wide(path, fastq, reverse, BEAR_ROW_WIDTH, n_pos_out, n_seqs_out);
 }
 
 extern "C" int bear_fastx_encode_wide(const char *path, int fastq, int reverse, int width, int group, uint64_t capacity, uint8_t *text,
                                       uint8_t *group_out, uint64_t *n_pos_out) {
-  return fastx_encode(path, fastq, reverse, width, group, capacity, text, group_out, n_pos_out);
+  if (!path || !text || !n_pos_out || group < 0 || group > 254) return BEAR_ERR_INVALID_ARG;
+  fastx_store out{text, capacity};
+  uint64_t seqs = 0;
+  const int st = emit_fastx(path, fastq, reverse, width, out, &seqs);
+  if (st != BEAR_OK) return st;
+  if (out.overflow) return BEAR_ERR_INVALID_ARG;
+  if (group_out) memset(group_out, group, (size_t)out.pos);
+  *n_pos_out = out.pos;
+  return BEAR_OK;
+}
+
+extern "C" int bear_fastx_encode(const char *path, int fastq, int reverse, int group, uint64_t capacity, uint8_t *text,
+                                 uint8_t *group_out, uint64_t *n_pos_out) {
+  return bear_fastx_encode_wide(path, fastq, reverse, BEAR_ROW_WIDTH, group, capacity, text, group_out, n_pos_out);
 }

@@ -698,6 +698,10 @@ int bear_synth_prior_f64(uint64_t seed, uint64_t row0, uint64_t n_rows, double *
  *     kmers  [host] char  [max_rows, lag]      (no terminator; '[' padded as in the file)
  *     counts [host] uint32 [num_ds, max_rows, 5] (planar by dataset column)
  *   *n_rows_out receives the number of rows parsed.
+ * Host threads: the counters, the dense readers and bear_write_counts_tsv[_wide] work on one chunk of the text (of the selected
+ * rows) per thread -- the hardware threads, or BEAR_PARSE_THREADS [environment] of them, at most 64; one thread for a text below
+ * 1 MiB, and for the writer at least 64 Ki rows per thread.  No result depends on the thread count.  BEAR_ERR_NOMEM: a thread or a
+ * host buffer could not be had (the threads already started have ended when the call returns).
  */
 int bear_count_rows(const char *path, uint64_t *n_rows_out);
 int bear_count_newlines(const char *path, uint64_t *n_out);

@@ -120,3 +120,105 @@ def test_parser_fuzz_against_oracle(tmp_path):
         assert np.array_equal(d.counts.transpose(1, 0, 2), want_c.astype(np.uint32))
         batches = list(d)
         assert sum(len(b[0]) for b in batches) == n and batches[0][1].shape[1:] == (num_ds, 5)
+
+
+_BIG = {}
+
+
+def _big_table():
+    """The table of test_threaded_parser_matches_single_thread (60 000 rows, lag 7, 2 columns: 2.04 MB of text), generated once."""
+    if not _BIG:
+        rng = np.random.default_rng(1)
+        n, lag = 60000, 7
+        letters = np.frombuffer(b"ACGT[", dtype=np.uint8)
+        kmers = letters[rng.integers(0, 5, size=(n, lag))]
+        counts = rng.integers(0, 5, size=(2, n, 5)).astype(np.uint32)
+        counts[0, ::97, 0] = 4000000000
+        _BIG.update(kmers=kmers, counts=counts, text=_format_table(kmers, counts))
+        assert len(_BIG["text"]) > (1 << 20)
+    return _BIG["kmers"], _BIG["counts"], _BIG["text"]
+
+
+def _format_table(kmers, counts):
+    """`kmer \\t [[...],[...]] \\n` per row, formatted by Python from the arrays: no part of the library is in it."""
+    n, lag = kmers.shape
+    keys = kmers.tobytes().decode()
+    fmt = "%s\t[" + ",".join(["[" + ",".join(["%d"] * counts.shape[2]) + "]"] * counts.shape[0]) + "]\n"
+    rows = counts.transpose(1, 0, 2).reshape(n, -1).tolist()
+    return "".join(fmt % (keys[i * lag:(i + 1) * lag], *r) for i, r in enumerate(rows)).encode()
+
+
+def test_sharded_reader_above_the_thread_threshold(tmp_path, monkeypatch):
+    """The sharded reader on several chunks (keep_shard and the shard_map::below offset of every chunk), behind a header line:
+    every rank gets the generated rows at the indices dist.shard_rows gives per batch, the ranks cover the table once, and
+    the file's row count comes back -- for one thread and for thread counts that do and do not divide the text evenly."""
+    from bear_amd import _lib, dist
+    kmers, counts, text = _big_table()
+    n, lag = kmers.shape
+    batch, world = 1000, 3
+    path = tmp_path / "big.tsv"
+    path.write_bytes(b"kmer\tcounts\n" + text)
+    L = _lib.lib()
+    for threads in ("1", "8", "3"):
+        monkeypatch.setenv("BEAR_PARSE_THREADS", threads)
+        seen = np.zeros(n, dtype=int)
+        for r in range(world):
+            idx = np.concatenate([a + np.arange(*dist.shard_rows(min(batch, n - a), r, world)) for a in range(0, n, batch)])
+            km = np.full((len(idx), lag), 0xEE, dtype=np.uint8)
+            cn = np.full((2, len(idx), 5), 0xEEEEEEEE, dtype=np.uint32)
+            n_local, n_file = ctypes.c_uint64(), ctypes.c_uint64()
+            st = L.bear_parse_counts_tsv_shard(str(path).encode(), 2, lag, 1, 0, n, batch, r, world, len(idx), km.ctypes.data,
+                                               cn.ctypes.data, ctypes.byref(n_local), ctypes.byref(n_file))
+            assert (st, n_local.value, n_file.value) == (0, len(idx), n), (threads, r)
+            assert np.array_equal(km, kmers[idx]) and np.array_equal(cn, counts[:, idx]), (threads, r)
+            seen[idx] += 1
+        assert np.all(seen == 1), threads
+
+
+def test_plain_reader_clips_at_max_rows(tmp_path, monkeypatch):
+    """max_rows below the file's rows: status 0, max_rows rows, and nothing written behind them -- neither in the k-mer buffer
+    nor behind counts[num_ds, max_rows, 5] -- whether one thread stops reading there or several threads clip their chunks."""
+    from bear_amd import _lib
+    kmers, counts, text = _big_table()
+    n, lag = kmers.shape
+    max_rows = 41234
+    path = tmp_path / "big.tsv"
+    path.write_bytes(text)
+    L = _lib.lib()
+    for threads in ("1", "8"):
+        monkeypatch.setenv("BEAR_PARSE_THREADS", threads)
+        km = np.full((n, lag), 0xEE, dtype=np.uint8)
+        flat = np.full(2 * max_rows * 5 + 4096, 0xEEEEEEEE, dtype=np.uint32)
+        cn, canary = flat[:2 * max_rows * 5].reshape(2, max_rows, 5), flat[2 * max_rows * 5:]
+        got = ctypes.c_uint64()
+        st = L.bear_parse_counts_tsv(str(path).encode(), 2, lag, max_rows, km.ctypes.data, cn.ctypes.data, ctypes.byref(got))
+        assert (st, got.value) == (0, max_rows), threads
+        assert np.array_equal(km[:max_rows], kmers[:max_rows]) and np.array_equal(cn, counts[:, :max_rows]), threads
+        assert np.all(km[max_rows:] == 0xEE) and np.all(canary == 0xEEEEEEEE), threads
+
+
+def test_writer_bytes_do_not_depend_on_threads(tmp_path, monkeypatch):
+    """3 * 65536 + 17 rows give the writer up to four ranges of 64 Ki rows: with BEAR_PARSE_THREADS 1, 3 and 8 (one, three and
+    four writer threads) the file is the text Python formats from the arrays, and a table written as four appended calls of
+    every fourth row reads back as those rows."""
+    from bear_amd import _lib
+    rng = np.random.default_rng(5)
+    n, lag = 3 * 65536 + 17, 6
+    letters = np.frombuffer(b"ACGT[", dtype=np.uint8)
+    kmers = letters[rng.integers(0, 5, size=(n, lag))]
+    counts = (10 ** rng.integers(0, 10, size=(2, n, 5)) * rng.integers(0, 5, size=(2, n, 5))).clip(0, 2 ** 32 - 1).astype(np.uint32)
+    want = _format_table(kmers, counts)
+    order = np.concatenate([np.arange(j, n, 4) for j in range(4)])
+    L = _lib.lib()
+    whole, parts = tmp_path / "whole.tsv", tmp_path / "parts.tsv"
+    for threads in ("1", "3", "8"):
+        monkeypatch.setenv("BEAR_PARSE_THREADS", threads)
+        assert L.bear_write_counts_tsv(str(whole).encode(), kmers.ctypes.data, counts.ctypes.data, n, lag, 2, 0, 1, 0) == 0
+        assert whole.read_bytes() == want, threads
+        for j in range(4):
+            assert L.bear_write_counts_tsv(str(parts).encode(), kmers.ctypes.data, counts.ctypes.data, n, lag, 2, j, 4, int(j > 0)) == 0
+        km = np.zeros((n, lag), dtype=np.uint8)
+        cn = np.zeros((2, n, 5), dtype=np.uint32)
+        got = ctypes.c_uint64()
+        assert L.bear_parse_counts_tsv(str(parts).encode(), 2, lag, n, km.ctypes.data, cn.ctypes.data, ctypes.byref(got)) == 0
+        assert got.value == n and np.array_equal(km, kmers[order]) and np.array_equal(cn, counts[:, order]), threads
