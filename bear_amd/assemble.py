@@ -11,6 +11,12 @@ table look-up) instead of a KMC database (``kmc_path`` still works where ``py_km
 (``van=...``) does not need a trained-model folder; and a new k-mer's table row is stored under the index the k-mer
 was given (the reference indexes k-mers in order of appearance but stores their rows in sorted order, assemble.py:96-99,
 so that rows can be swapped between k-mers that first appear in the same step).
+
+With a ``get_var_probs.DeviceCounter`` as ``counter=`` the flanks grow on the device instead (``kernels.generate_steps``,
+kernels_generate.h): look-up, table values and Gumbel-max draws of every letter in one launch per direction for a BMM, one
+launch per step behind the AR function for a trained model.  A table value is keyed by (seed, sequence, k-mer, letter), so the
+sample a sequence sees is the same whenever it meets a k-mer again and ``batch_size`` has no effect; ``device_path=False``
+keeps the host loop for such a counter.
 """
 import os
 
@@ -26,39 +32,11 @@ def reverse_complement(seq):
     return seq.translate(_COMP)[::-1]
 
 
-def assemble_no_ends(seqs_fa_file, lengths_to_gen, num_to_gen, bear_path, kmc_path,
-                     h=None, reverse=True, save_folder=None, batch_size=100,
-                     van=None, lag=None, alphabet_name=None, get_map=False, counter=None, seed=None):
-    """assemble.assemble_no_ends (assemble.py:21-184) -> ``(gen_seqs [len(seqs), num_to_gen], sw_ent)``."""
-    if bear_path is not None:
-        lag, alphabet_name, h_bear, ar_func, _ = get_var_probs.load_bear(bear_path)
-        if h is None:
-            h = h_bear
-    else:
-        assert van is not None, "without a trained model folder only a BMM (van=...) can generate"
-        ar_func = None
-    h = np.array([h]) if h is not None else None
-    if van is not None:
-        assert lag is not None and alphabet_name is not None
-        vans, ar_func, h = van * np.ones(1), None, None
-    else:
-        vans = []
-    train_col = 0
-    alphabet = core.alphabets_en[alphabet_name][:-1]
-    alphabet_size = len(alphabet)
-    if counter is None:
-        counter = get_var_probs.make_kmc_genome_counter(kmc_path, lag, reverse=reverse, no_end=True)
-    rng = np.random if seed is None else np.random.RandomState(seed)
-
-    with open(seqs_fa_file) as fh:
-        fwd_seqs = np.array([s for _, s in summarize.load_input(fh, "fa")])
-    n_seeds = len(fwd_seqs)
-    fwd_seqs = np.repeat(fwd_seqs, num_to_gen)
-    lengths = np.repeat(np.asarray(lengths_to_gen).reshape(n_seeds, 2), num_to_gen, axis=0)     # [:, 0] left, [:, 1] right
-    rev_seqs = np.array([reverse_complement(s) for s in fwd_seqs])
-
+def _host_flanks(counter, seqs_by_dir, lengths_by_dir, lag, alphabet, alphabet_name, h, ar_func, vans, train_col, get_map, batch_size,
+                 rng, seed):
+    """The reference's loop (assemble.py:60-130): letter by letter on the host, a sampled table row per new k-mer and live sequence."""
     flanks = []
-    for seqs_all_b, length_all_b in zip([rev_seqs, fwd_seqs], [lengths[:, 0], lengths[:, 1]]):
+    for seqs_all_b, length_all_b in zip(seqs_by_dir, lengths_by_dir):
         all_batch_new = []
         for lo in range(0, len(seqs_all_b), batch_size):
             seqs = seqs_all_b[lo:lo + batch_size]
@@ -94,6 +72,106 @@ def assemble_no_ends(seqs_fa_file, lengths_to_gen, num_to_gen, bear_path, kmc_pa
                 step += 1
             all_batch_new.append(new_seq)
         flanks.append(np.concatenate(all_batch_new) if all_batch_new else np.array([]))
+    return flanks
+
+
+def _device_flanks(counter, seqs_by_dir, lengths_by_dir, lag, alphabet_name, h, ar_func, vans, get_map, seed):
+    """The flanks of both directions grown on the device (``kernels.generate_steps``, kernels_generate.h): no table, no dictionary
+    and no host round trip per letter.  A BMM takes one launch per direction; a trained model one AR-function call and one launch
+    per step, and nothing is synchronised before the letters of both directions are copied back.  The sample index of a sequence is
+    ``direction * n_total + its index``: left and right flanks are different posterior samples, as in the reference."""
+    import torch
+    from . import kernels
+    from .log_gamma import _next_seed
+    if counter.lag != lag or counter.alphabet_name != alphabet_name:
+        raise ValueError(f"counter: a lag-{counter.lag} table of {counter.alphabet_name!r}, asked for lag {lag} of {alphabet_name!r}")
+    letters_en = [str(ch) for ch in core.alphabets_en[alphabet_name][:-1]]
+    W, device = counter.width, counter.device
+    n_total = len(seqs_by_dir[1])
+    if alphabet_name == "prot" and n_total and np.any(np.asarray(lengths_by_dir[0]) > 0):
+        raise ValueError("a left flank grows along the reverse complement: the protein alphabet has none, ask for left lengths of 0")
+    ends = []
+    for seqs in seqs_by_dir:                                   # every refusal comes before the first launch
+        for s_ in seqs:
+            s_ = str(s_)
+            if len(s_) < lag:
+                raise ValueError(f"seed {s_!r} is shorter than the lag {lag}")
+            for ch in set(s_):
+                if ch not in letters_en:
+                    raise ValueError(f"character {ch!r} of seed {s_!r} is not a letter of the alphabet {alphabet_name!r}")
+        raw = np.frombuffer("".join(str(s_)[-lag:] for s_ in seqs).encode("ascii"), dtype=np.uint8)
+        ends.append(counter._lut[raw].reshape(len(seqs), lag))
+    seed = _next_seed() if seed is None else seed
+    char_of = np.frombuffer("".join(letters_en).encode("ascii"), dtype=np.uint8)
+    grown = []
+    with torch.cuda.device(device):
+        for direction, (codes, lens) in enumerate(zip(ends, lengths_by_dir)):
+            lens = np.maximum(np.asarray(lens, dtype=np.int64).reshape(-1), 0)
+            n_steps = int(lens.max()) if lens.size else 0
+            letters = torch.full((n_total, n_steps), 0xFF, dtype=torch.uint8, device=device)
+            grown.append((letters, lens))
+            if n_steps == 0:
+                continue
+            keys = counter._keys_of_codes(torch.from_numpy(np.ascontiguousarray(codes)).to(device))
+            sample = torch.arange(n_total, dtype=torch.int64, device=device) + direction * n_total
+            left = torch.from_numpy(lens.astype(np.int32)).to(device)
+            common = (counter.keys, counter.counts_by_key, counter.rank, lag, keys, sample, left, letters)
+            if ar_func is None:
+                kernels.generate_steps(*common, 0, n_steps, seed, van=float(vans[0]), get_map=get_map)
+            else:
+                kmer_codes = counter.codes_of_keys(keys)
+                for t in range(n_steps):
+                    with torch.no_grad():
+                        prior = ar_func(kmer_codes).to(torch.float64).expand(n_total, W).contiguous()
+                    kernels.generate_steps(*common, t, 1, seed, prior=prior, h=None if get_map else float(h[0]), get_map=get_map,
+                                           codes=kmer_codes)
+        flanks = []
+        for letters, lens in grown:                            # the one copy back (and the first synchronisation)
+            chars = char_of[np.minimum(letters.cpu().numpy(), W - 2)]
+            flanks.append(np.array([chars[i, :int(l)].tobytes().decode("ascii") for i, l in enumerate(lens)]))
+    return flanks
+
+
+def assemble_no_ends(seqs_fa_file, lengths_to_gen, num_to_gen, bear_path, kmc_path,
+                     h=None, reverse=True, save_folder=None, batch_size=100,
+                     van=None, lag=None, alphabet_name=None, get_map=False, counter=None, seed=None, device_path=True):
+    """assemble.assemble_no_ends (assemble.py:21-184) -> ``(gen_seqs [len(seqs), num_to_gen], sw_ent)``.  A ``DeviceCounter`` as
+    ``counter`` takes the device path (``device_path=False``: the host loop); it refuses, with ``ValueError`` and before any launch, a
+    seed shorter than ``lag`` or with a character outside the alphabet, a counter of another lag or alphabet, and a left flank for
+    ``prot``."""
+    if bear_path is not None:
+        lag, alphabet_name, h_bear, ar_func, _ = get_var_probs.load_bear(bear_path)
+        if h is None:
+            h = h_bear
+    else:
+        assert van is not None, "without a trained model folder only a BMM (van=...) can generate"
+        ar_func = None
+    h = np.array([h]) if h is not None else None
+    if van is not None:
+        assert lag is not None and alphabet_name is not None
+        vans, ar_func, h = van * np.ones(1), None, None
+    else:
+        vans = []
+    train_col = 0
+    alphabet = core.alphabets_en[alphabet_name][:-1]
+    alphabet_size = len(alphabet)
+    if counter is None:
+        counter = get_var_probs.make_kmc_genome_counter(kmc_path, lag, reverse=reverse, no_end=True)
+    rng = np.random if seed is None else np.random.RandomState(seed)
+
+    with open(seqs_fa_file) as fh:
+        fwd_seqs = np.array([s for _, s in summarize.load_input(fh, "fa")])
+    n_seeds = len(fwd_seqs)
+    fwd_seqs = np.repeat(fwd_seqs, num_to_gen)
+    lengths = np.repeat(np.asarray(lengths_to_gen).reshape(n_seeds, 2), num_to_gen, axis=0)     # [:, 0] left, [:, 1] right
+    rev_seqs = np.array([reverse_complement(s) for s in fwd_seqs])
+
+    if isinstance(counter, get_var_probs.DeviceCounter) and device_path:
+        flanks = _device_flanks(counter, [rev_seqs, fwd_seqs], [lengths[:, 0], lengths[:, 1]], lag, alphabet_name, h, ar_func, vans,
+                                get_map, seed)
+    else:
+        flanks = _host_flanks(counter, [rev_seqs, fwd_seqs], [lengths[:, 0], lengths[:, 1]], lag, alphabet, alphabet_name, h, ar_func,
+                              vans, train_col, get_map, batch_size, rng, seed)
 
     gen_seqs = [reverse_complement(left) + seed_seq + right for left, right, seed_seq in zip(flanks[0], flanks[1], fwd_seqs)]
     gen_seqs = np.array(gen_seqs).reshape([-1, num_to_gen])

@@ -1,12 +1,14 @@
 // bear_score.hip -- scoring on the device: the three entries between the device count tables and the samplers' tables
 // (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
-// of a sampled table's rows over the transitions of every segment.  The only unit that includes -- and so emits -- kernels_score.h.
+// of a sampled table's rows over the transitions of every segment -- and sequence generation over the same key tables ("Sequence
+// generation").  The only unit that includes -- and so emits -- kernels_score.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "bear_dev.h"
 #include "bear_release_guard.h"
+#include "kernels_generate.h"
 #include "kernels_score.h"
 
 namespace {
@@ -82,6 +84,56 @@ int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_
                      rows, letters, seg, n_seg, n_t, partials.get(), scores);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;      // (partials goes with this frame: hipFree waits for the two launches)
+}
+
+int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
+                            int mode, int map, double h, double van, const double *prior, uint64_t seed, uint64_t *keys,
+                            const uint64_t *sample, uint32_t *left, uint64_t n_seq, uint64_t step0, uint64_t n_steps,
+                            uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  if (lag < 1 || lag > (width == 5 ? 21 : 12) || !rank) return BEAR_ERR_INVALID_ARG;
+  if (mode != BEAR_GEN_BMM && mode != BEAR_GEN_BEAR && mode != BEAR_GEN_AR) return BEAR_ERR_INVALID_ARG;
+  if (mode != BEAR_GEN_BMM && !prior) return BEAR_ERR_INVALID_ARG;
+  if (mode == BEAR_GEN_AR && !map) return BEAR_ERR_INVALID_ARG;          // the AR model is a table only at its MAP value
+  if (prior && n_steps > 1) return BEAR_ERR_INVALID_ARG;                 // the rows are those of the current end k-mers
+  if (mode == BEAR_GEN_BEAR && !(h > 0.0)) return BEAR_ERR_INVALID_ARG;
+  if (mode == BEAR_GEN_BMM && !(van > 0.0)) return BEAR_ERR_INVALID_ARG;
+  if (n_table >= SCR_ABSENT || n_steps > 0xFFFFFFFFull || step0 > (~0ull) - n_steps || letters_stride < step0 + n_steps)
+    return BEAR_ERR_INVALID_ARG;
+  const int bits = width == 5 ? 3 : 5;
+  gen_args A;
+  memset(&A, 0, sizeof(A));
+  for (int c = 0; c <= width; ++c) {
+    if (c == width - 1) continue;                                        // the stop: no letter of a context, never drawn
+    if (rank[c] >= (1u << bits)) return BEAR_ERR_INVALID_ARG;
+    if (c < width - 1) A.rank[c >> 3] |= (uint64_t)rank[c] << ((c & 7) * 8);
+    A.code[rank[c] >> 3] |= (uint64_t)(c < width - 1 ? c : width - 1) << ((rank[c] & 7) * 8);      // core.encode_kmers: '[' = A
+  }
+  if (n_seq == 0) return BEAR_OK;
+  if (!keys || !sample || !left || (n_steps && !letters) || misaligned8(keys) || misaligned8(sample) || misaligned4(left) ||
+      (prior && misaligned8(prior)) || (n_table && (!table || !counts || misaligned8(table) || misaligned4(counts))))
+    return BEAR_ERR_INVALID_ARG;
+  if (letters_stride && n_seq > (~0ull) / letters_stride) return BEAR_ERR_INVALID_ARG;
+  A.lag = lag;
+  A.mode = mode;
+  A.map = map != 0;
+  A.inv_h = mode == BEAR_GEN_BEAR ? 1.0 / h : 0.0;
+  A.van = mode == BEAR_GEN_BMM ? van : 0.0;
+  A.seed = seed;
+  A.step0 = step0;
+  A.n_steps = n_steps;
+  A.stride = letters_stride;
+  if (n_steps == 0 && !codes) return BEAR_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 block(GEN_THREADS);
+  if (width == 5)
+    hipLaunchKernelGGL((generate_steps_kernel<3, 5>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_GROUP(5))), block, 0, s, table, counts,
+                       n_table, prior, keys, sample, left, n_seq, A, letters, codes);
+  else
+    hipLaunchKernelGGL((generate_steps_kernel<5, 21>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_GROUP(21))), block, 0, s, table, counts,
+                       n_table, prior, keys, sample, left, n_seq, A, letters, codes);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,111 @@
+// kernels_generate.h -- sequence generation on the device (assemble.assemble_no_ends with a DeviceCounter): every sequence grows
+// letter by letter from its end k-mer, the transition table row of that k-mer is looked up in the sorted key table of a column and
+// sampled (or taken at its MAP value) where it is needed, and the letter is a Gumbel-max draw over the row.
+//
+// The host loop of assemble.py keeps "one posterior sample of the transition table per generated sequence" (assemble.py:126) as an
+// array, because it cannot draw the same row again later.  Here a table value is a pure function of (seed, sequence's sample index,
+// k-mer key, letter): a sequence that returns to a k-mer forms the same row again, and nothing is stored.
+//
+// Lane mapping: the letters of one sequence sit on neighbouring lanes, GEN_GROUP(W) lanes per sequence -- 4 at W = 5 (every lane a
+// letter), 32 at W = 21 (20 letters, 12 lanes that only take part in the exchange).  Per step the first lane of a group finds the
+// row (the loop of kmer_find_kernel) and hands it round, every letter lane forms ONE concentration, ONE log-Gamma draw and ONE
+// Gumbel draw, and the arg-max is log2(group) lane exchanges of (value, letter).  A sequence per lane would run W - 1 rejection
+// samplers one behind the other (and hold them all in registers: the 169 VGPRs of logdir_sample_kernel<21>).
+// No atomics and no sum across lanes: the letters are the same in both libraries and for any cut of the steps into launches.
+#pragma once
+#include "kernels_score.h"   // scr_ranks, SCR_ABSENT: keys are those of bear_score_transitions_u64
+#include "sample_common.h"
+
+#define GEN_THREADS 256
+#define GEN_ID_GUMBEL 3000u   // the model id of the Gumbel stream (the table values are model 0; beside EVL_ID_ARM / EVL_ID_VAN)
+#define GEN_GROUP(W) ((W) == 5 ? 4 : 32)
+
+struct gen_args {
+  int lag, mode, map;          // mode: BEAR_GEN_BMM / BEAR_GEN_BEAR / BEAR_GEN_AR (include/bear_hip.h)
+  double inv_h, van;
+  uint64_t seed, step0, n_steps, stride;
+  uint64_t rank[3];            // byte c: the rank of the letter code c < W - 1 (scr_ranks, eight to a word: selected, never indexed)
+  uint64_t code[4];            // byte r: the core.encode_kmers code of the rank r
+};
+
+// byte i of words held in scalar registers, as selects (indexing the argument block per lane would put it in scratch)
+__device__ __forceinline__ uint32_t gen_byte3(const uint64_t (&w)[3], uint32_t i) {
+  const uint64_t x = i < 8u ? w[0] : (i < 16u ? w[1] : w[2]);
+  return (uint32_t)(x >> ((i & 7u) * 8u)) & 0xFFu;
+}
+__device__ __forceinline__ uint32_t gen_byte4(const uint64_t (&w)[4], uint32_t i) {
+  const uint64_t x = i < 16u ? (i < 8u ? w[0] : w[1]) : (i < 24u ? w[2] : w[3]);
+  return (uint32_t)(x >> ((i & 7u) * 8u)) & 0xFFu;
+}
+
+// Steps step0 .. step0 + n_steps - 1 of every sequence that has letters left (left[i] of them; the sequence takes min(left[i],
+// n_steps) steps and left[i] goes down by that number).  keys[i]: the end key, read and written.  table / counts: the ascending
+// distinct keys of a column and their count rows in that order (an absent k-mer: a row of zeros).  prior: NULL, or [n_seq, W]
+// rows for the current end k-mers (then n_steps = 1: the host forms the next rows from `codes`).
+// Every loop runs the same number of times on all lanes of a wave (a finished sequence idles), so each exchange finds its group whole.
+template <int BITS, int W>
+__global__ __launch_bounds__(GEN_THREADS) void generate_steps_kernel(const uint64_t *__restrict__ table,
+                                                                     const uint32_t *__restrict__ counts, uint64_t n_table,
+                                                                     const double *__restrict__ prior, uint64_t *__restrict__ keys,
+                                                                     const uint64_t *__restrict__ sample, uint32_t *__restrict__ left,
+                                                                     uint64_t n_seq, gen_args A, uint8_t *__restrict__ letters,
+                                                                     int8_t *__restrict__ codes) {
+  constexpr int G = GEN_GROUP(W);
+  constexpr uint32_t PER_BLOCK = GEN_THREADS / G;
+  const uint32_t b = threadIdx.x % G, g = threadIdx.x / G;
+  const uint64_t mask = (1ull << (BITS * A.lag)) - 1ull;       // BITS * lag <= 63
+  for (uint64_t base = (uint64_t)blockIdx.x * PER_BLOCK; base < n_seq; base += (uint64_t)gridDim.x * PER_BLOCK) {
+    const uint64_t i = base + g;
+    const bool have = i < n_seq;
+    uint64_t q = have ? keys[i] : 0ull;
+    const uint64_t s = have ? sample[i] : 0ull;
+    const uint32_t left0 = have ? left[i] : 0u;
+    const uint32_t todo = (uint64_t)left0 < A.n_steps ? left0 : (uint32_t)A.n_steps;
+    for (uint32_t k = 0; __any(k < todo); ++k) {
+      const bool live = k < todo;
+      const uint64_t t = A.step0 + k;
+      uint32_t row = SCR_ABSENT;
+      if (live && b == 0 && n_table > 0) {
+        uint64_t lo = 0, n = n_table;
+        while (n > 1) {
+          const uint64_t half = n >> 1;
+          lo = table[lo + half] <= q ? lo + half : lo;      // the last entry <= q, or entry 0
+          n -= half;
+        }
+        row = table[lo] == q ? (uint32_t)lo : SCR_ABSENT;
+      }
+      row = (uint32_t)__shfl((int)row, 0, G);
+      double v = -INFINITY;
+      if (live && b < W - 1) {
+        const double c = row != SCR_ABSENT ? (double)counts[(uint64_t)row * W + b] : 0.0;
+        const double f = prior ? prior[i * W + b] : 0.0;
+        const double conc = A.mode == BEAR_GEN_BMM ? A.van + c : (A.mode == BEAR_GEN_BEAR ? __builtin_fma(f, A.inv_h, c) : f);
+        const double tv = A.map ? log(conc) : smp_log_gamma(conc, smp_cell_key(A.seed, 0u, s, mix64(q) + b));
+        v = tv - log(-log(u01(smp_cell_key(A.seed, GEN_ID_GUMBEL, s, t * W + b))));
+      }
+      uint32_t best = b;       // the lowest letter with the largest value; an idle lane holds -inf under a letter beyond the row
+#pragma unroll
+      for (int off = G / 2; off >= 1; off >>= 1) {
+        const double ov = __shfl_xor(v, off, G);
+        const uint32_t ob = (uint32_t)__shfl_xor((int)best, off, G);
+        const bool take = ov > v || (ov == v && ob < best);
+        v = take ? ov : v;
+        best = take ? ob : best;
+      }
+      best = (uint32_t)__shfl((int)best, 0, G);      // (one answer per group whatever a NaN did to the comparisons)
+      if (live) {
+        q = ((q << BITS) | (uint64_t)gen_byte3(A.rank, best)) & mask;
+        if (b == 0) letters[i * A.stride + t] = (uint8_t)best;
+      }
+    }
+    if (have) {
+      if (b == 0) {
+        keys[i] = q;
+        left[i] = left0 - todo;
+      }
+      if (codes)
+        for (int p = (int)b; p < A.lag; p += G)
+          codes[i * (uint64_t)A.lag + p] = (int8_t)gen_byte4(A.code, (uint32_t)(q >> (BITS * (A.lag - 1 - p))) & ((1u << BITS) - 1u));
+    }
+  }
+}

@@ -247,7 +247,8 @@ class DeviceCounter:
     ``counter=`` anywhere.  Handed to ``get_bear_probs`` / ``get_bear_probs_seqs`` (without ``get_marg``) the whole call runs on the
     device: keys of the queries' transitions, their distinct k-mers, count rows by ``kernels.kmer_find``, the sampled or MAP table
     and the per-variant / per-sequence sums (``kernels.score_sum``); only the scores come back.  ``train_col`` of those calls is
-    not used then: the counter is one column."""
+    not used then: the counter is one column.  Handed to ``assemble.assemble_no_ends`` the flanks grow on the device
+    (``kernels.generate_steps`` over ``keys`` and ``counts_by_key``)."""
 
     def __init__(self, kmers, counts, alphabet_name, no_end=False):
         if not (isinstance(kmers, torch.Tensor) and kmers.is_cuda and kmers.dtype == torch.uint8 and kmers.dim() == 2):
@@ -274,6 +275,14 @@ class DeviceCounter:
     @property
     def device(self):
         return self.kmers.device
+
+    @property
+    def counts_by_key(self):
+        """The count rows in key order, int32 [N', W] with row j the counts of ``keys[j]`` (``counts[perm]``): what
+        ``kernels.generate_steps`` looks rows up in.  Built on first use and kept."""
+        if getattr(self, "_counts_by_key", None) is None:
+            self._counts_by_key = self.counts[self.perm].contiguous()
+        return self._counts_by_key
 
     def _keys_of_codes(self, codes):
         """Keys int64 [n] of k-mers given as symbol codes uint8 [n, lag] on the device (-1: a symbol that is no letter of a context):

@@ -734,6 +734,68 @@ def score_sum(lp, rows, letters, seg):
     return scores
 
 
+# ---- sequence generation over a key table (include/bear_hip.h, "Sequence generation"; kernels_generate.h) ----------------------
+GEN_BMM, GEN_BEAR, GEN_AR = 0, 1, 2  # BEAR_GEN_*: where a letter's concentration comes from
+GEN_ID_GUMBEL = 3000                 # the model id that keys the Gumbel draws (the table values are model 0)
+
+
+def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van=None, prior=None, h=None,
+                   get_map=False, codes=None):
+    """One launch of ``bear_generate_steps_f64``: steps ``step0 .. step0 + n_steps - 1`` of every sequence that has letters left.
+    ``table``: CUDA int64 [N] ascending distinct keys, ``counts`` int32 [N, W] their count rows in that order (None with an empty
+    table); ``rank``: ``score_ranks`` of the alphabet.  Per sequence, all on the table's device and updated in place: ``keys``
+    int64 [n] the end key, ``left`` int32 [n] the letters still to write; ``sample`` int64 [n] the sample index; ``letters`` uint8
+    [n, L >= step0 + n_steps] receives the letter codes at columns ``step0 ..``.  The model: ``van`` (a BMM: any ``n_steps``, a whole
+    flank in one launch), or ``prior`` float64 [n, W] rows of the current end k-mers (``n_steps`` 1) with ``h`` (BEAR) or without
+    (the AR model, ``get_map`` only).  ``codes`` int8 [n, lag], if given, receives the new end k-mers as ``core.encode_kmers`` codes."""
+    _check_vec(table, torch.int64, "table")
+    device = table.device
+    rank = np.ascontiguousarray(rank, dtype=np.uint8)
+    W = rank.size - 1
+    if W not in WIDE_WIDTHS:
+        raise ValueError(f"rank: {rank.size} entries; a rank table holds W + 1 for W in {WIDE_WIDTHS}")
+    if not 1 <= int(lag) <= SCORE_MAX_LAG[W]:
+        raise ValueError(f"lag {lag}: a key of {SCORE_BITS[W]} bits per letter holds contexts of 1..{SCORE_MAX_LAG[W]} letters")
+    if table.numel():
+        counts = _check_rows(counts, torch.int32, "counts", W, n=table.numel())
+    else:
+        counts = None
+    n = keys.numel() if isinstance(keys, torch.Tensor) else -1
+    _check_vec(keys, torch.int64, "keys", device=device)
+    _check_vec(sample, torch.int64, "sample", n, device=device)
+    _check_vec(left, torch.int32, "left", n, device=device)
+    step0, n_steps = int(step0), int(n_steps)
+    if step0 < 0 or n_steps < 0:
+        raise ValueError("step0 and n_steps count steps: not negative")
+    if not (isinstance(letters, torch.Tensor) and letters.device == device and letters.dtype == torch.uint8 and letters.dim() == 2
+            and letters.is_contiguous() and letters.shape[0] == n):
+        raise ValueError(f"letters must be a contiguous CUDA uint8 tensor [{n}, L] on {device}")
+    if letters.shape[1] < step0 + n_steps:
+        raise ValueError(f"letters: rows of {letters.shape[1]}, steps {step0} .. {step0 + n_steps} do not fit")
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", W, n=n)
+        if prior.device != device:
+            raise ValueError(f"prior must be on {device}")
+        if n_steps > 1:
+            raise ValueError("prior rows belong to the current end k-mers: one step per launch")
+        if h is None and not get_map:
+            raise ValueError("the AR model (prior without h) is a table only at its MAP value: get_map=True")
+        mode = GEN_AR if h is None else GEN_BEAR
+    elif van is None:
+        raise ValueError("a BMM (van=...) or prior rows")
+    else:
+        mode = GEN_BMM
+    if mode == GEN_BEAR and not float(h) > 0 or mode == GEN_BMM and not float(van) > 0:
+        raise ValueError("h and van must be > 0")
+    if codes is not None and not (isinstance(codes, torch.Tensor) and codes.device == device and codes.dtype == torch.int8
+                                  and codes.is_contiguous() and tuple(codes.shape) == (n, int(lag))):
+        raise ValueError(f"codes must be a contiguous CUDA int8 tensor [{n}, {int(lag)}] on {device}")
+    _launch(device, "bear_generate_steps_f64", _ptr(table), _ptr(counts), table.numel(), int(lag), W,
+            rank.ctypes.data_as(ctypes.c_void_p), mode, int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0,
+            float(van) if mode == GEN_BMM else 0.0, _ptr(prior), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample), _ptr(left), n,
+            step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
+
+
 def shuffle_rows(src, seed):
     """One launch of ``bear_shuffle_rows``: a new tensor with ``dst[i] = src[perm_seed(i)]`` along dim 0."""
     if not (src.is_cuda and src.is_contiguous() and src.dim() >= 1):

@@ -888,6 +888,45 @@ int bear_kmer_find_u64(const uint64_t *table, uint64_t n_table, const uint64_t *
 int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_values, const uint32_t *rows, const uint8_t *letters,
                        uint64_t n_t, const uint64_t *seg, uint64_t n_seg, double *scores, void *stream);
 
+/*
+ * Sequence generation on the device (assemble.assemble_no_ends with a DeviceCounter): every sequence grows from its end k-mer, one
+ * letter per step, under the transition table of a count column -- sampled from its posterior, one sample per sequence, or at its
+ * MAP value.  Asynchronous on `stream`; one launch.
+ *
+ * bear_generate_steps_f64: steps t = step0 .. step0 + n_steps - 1 of the sequences that have letters left.
+ *   table  [dev, nullable] uint64 [n_table] ascending and distinct keys of bear_score_transitions_u64 (same lag, width, rank),
+ *          n_table < 2^32 - 1;  counts [dev, nullable] uint32 [n_table, width], row j the counts of table[j] (KEY order).  A k-mer
+ *          that is absent is a row of zeros; n_table = 0 (then both may be NULL) is valid.
+ *   lag, width, rank [host] uint8 [width + 1]: as for bear_score_transitions_u64
+ *   keys   [dev] uint64 [n_seq]: the end key of every sequence; read, and written back after its last step here
+ *   sample [dev] uint64 [n_seq]: the sample index s of every sequence (two sequences with one index share their table)
+ *   left   [dev] uint32 [n_seq]: letters still to write; a sequence takes min(left, n_steps) steps and left goes down by as many
+ *   Per step, for the letters b < width - 1 (the stop is never drawn), with c[] the count row of the key q:
+ *     concentration  mode BEAR_GEN_BMM: van + c[b];  BEAR_GEN_BEAR: fma(prior[i, b], 1 / h, c[b]);  BEAR_GEN_AR: prior[i, b]
+ *     table value    map == 0: one log Gamma(concentration) draw keyed by (seed, model 0, s, mix64(q) + b) -- the draw of
+ *                    bear_log_gamma_f64; a pure function of the key, so a sequence that returns to a k-mer meets the same row;
+ *                    map != 0: log(concentration).  (The row's common normaliser is not formed: it cannot change the letter.)
+ *     letter         the lowest b with the largest value + Gumbel draw keyed by (seed, model 3000, s, t * width + b); it goes to
+ *                    letters[i * letters_stride + t] and q becomes ((q << bits) | rank[letter]) & (2^(bits * lag) - 1)
+ *   prior  [dev, nullable] double [n_seq, width]: the rows of the sequences' CURRENT end k-mers (an AR function's output); with a
+ *          prior n_steps must be at most 1 (the caller forms the next rows from `codes`); NULL: BEAR_GEN_BMM only, any n_steps --
+ *          a whole flank in one launch.  BEAR_GEN_AR is a table only at its MAP value (map != 0).
+ *   letters [dev] uint8 [n_seq, letters_stride], letters_stride >= step0 + n_steps; entries of steps not taken are left alone
+ *   codes  [dev, nullable] int8 [n_seq, lag]: the new end k-mer of EVERY sequence as letter codes 0 .. width - 2, '[' = width - 1
+ *          (what an AR function takes)
+ * Refused with BEAR_ERR_INVALID_ARG before any launch: a width other than 5 / 21, a lag outside 1..21 / 1..12, n_steps > 1 with a
+ * prior, a mode that needs a prior without one, BEAR_GEN_AR without map, h (BEAR_GEN_BEAR) or van (BEAR_GEN_BMM) not > 0, a
+ * letters_stride below step0 + n_steps.  No atomics and no sums across lanes: the same arguments give the same letters in both
+ * libraries, and n steps in one launch are the letters of any cut of them into launches that continue at step0.
+ */
+#define BEAR_GEN_BMM 0
+#define BEAR_GEN_BEAR 1
+#define BEAR_GEN_AR 2
+int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
+                            int mode, int map, double h, double van, const double *prior, uint64_t seed, uint64_t *keys,
+                            const uint64_t *sample, uint32_t *left, uint64_t n_seq, uint64_t step0, uint64_t n_steps,
+                            uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
