@@ -236,7 +236,12 @@ class ResidentBatches:
     resident batch gets), drops every other batch and starts the upload of the batch after it on the side stream, so that a
     step's kernels run under the next batch's PCIe transfer.  ``self.batches[k]`` is then the same dict object for the whole
     run -- meta data only (``global_rows``, ``row0``, the uploaded row count) while the batch is not loaded -- and every
-    epoch re-uploads every batch: such a run is bound by PCIe (~45 GB/s), not by the kernels; more ranks are the fast way."""
+    epoch re-uploads every batch: such a run is bound by PCIe (~45 GB/s), not by the kernels; more ranks are the fast way.
+
+    A SHUFFLED table (``data.shuffle_seed``): batch [a, b) is rows perm(a) .. perm(b - 1) of the table in file order.  One rank's
+    resident epoch sends whole columns up and permutes them in HBM (``_upload_shuffled``).  A streamed epoch, and a rank that
+    keeps only its pieces (``world > 1``), gather each batch's rows by range instead (``_gather``): the table stays on the
+    host, host threads collect the batch's rows, and the block goes up through the ring."""
 
     def __init__(self, data, columns, device, want_codes=False, drop_empty=None, kmer_order=False, prebuild=(), per_row_extra=0,
                  stream=None):
@@ -269,6 +274,10 @@ class ResidentBatches:
         self._pieces = pieces = [Piece(a, b, *mine) for (a, b), mine in zip(data.batch_bounds(), data.rank_pieces(rank, world))]
         piece_rows = [p.g1 - p.g0 for p in pieces]
         shuffled = data.shuffle_seed is not None
+        if shuffled and data.shard is not None:
+            raise ValueError("a sharded table cannot be shuffled on the device")
+        # a host table's shuffled batch is gathered by row range (``_gather``): nothing of it needs a whole column in HBM
+        by_range = shuffled and not on_dev and data.num_rows > 0
         self.streaming = False
         self.loads = 0                      # streaming: batches made resident so far
         if not on_dev:
@@ -279,31 +288,51 @@ class ResidentBatches:
             # wrongly (and the job hang at its end).  (hbm_budget_check: the module's, whatever it is when the check is made)
             status, why = residency_status(
                 lambda rows: hbm_budget_check(data, len(columns), want_codes, device, rows=rows, per_row_extra=per_row_extra),
-                sum(piece_rows), 3 * max(piece_rows + [0]), stream, shuffled, len(pieces))
+                sum(piece_rows), 3 * max(piece_rows + [0]), stream, shuffled and not by_range, len(pieces))
             agreed = dist.agree_max(status, device)
             if agreed == 2:
                 raise MemoryError(why or "another rank's share of the epoch fits its HBM neither resident nor streamed: every rank stops")
             if agreed == 1:
-                if shuffled:
-                    raise ValueError("a streamed epoch cannot be shuffled on the device (the shuffle permutes the whole shard in HBM)")
                 if why is not None:
                     warnings.warn(f"{why}  --  streaming the epoch instead: batches are re-uploaded every epoch (PCIe-bound)")
                 elif not stream:
                     warnings.warn("another rank has to stream its share of the epoch: this rank streams too (the ranks run the same loop)")
                 self.streaming = True
         LAST_RUN["streaming"] = self.streaming
+        # The range gather serves a streamed epoch and a rank that keeps less than the whole table; one rank's resident epoch
+        # still sends whole columns up and permutes them there (``_upload_shuffled``: one pass over HBM).
+        self._by_range = by_range = by_range and (self.streaming or world > 1)
         self._up = None if on_dev else Uploader(device, expect_bytes=max(
-            [4 * self.width * n for n in piece_rows] + [4 * self.width * data.local_rows if shuffled else 0, 1]))
+            [4 * self.width * n for n in piece_rows] + [4 * self.width * data.local_rows if shuffled and not by_range else 0, 1]))
         self.upload_bytes = 0
-        self._shuffled = self._upload_shuffled() if shuffled and data.num_rows else {}
-        if self._shuffled and data.shard is not None:
-            raise ValueError("a sharded table cannot be shuffled on the device")
+        self._sources = self._gather_sources() if by_range else {}      # range gather: name -> (host array, torch dtype)
+        self._shuffled = self._upload_shuffled() if shuffled and data.num_rows and not by_range else {}
         if self.streaming:
             self._pool = concurrent.futures.ThreadPoolExecutor(1)
             self._pending = None            # (batch, future of its enqueued upload)
             self.batches = [unloaded_entry(p) for p in pieces]
         else:
             self._upload_all()
+
+    def _gather_sources(self):
+        """The host arrays a shuffled epoch's batches are gathered from: the requested columns and the k-mers (their ASCII bytes,
+        or the host encoder's codes where the alphabet has no device encoder)."""
+        data, arrays = self.data, {}
+        for name in self._names:
+            if name != "codes":
+                arrays[name] = (data.counts[self._columns[name]].view(np.int32), torch.int32)
+            elif self._fast_codes:
+                arrays[name] = (data.kmers, torch.uint8)
+            else:
+                arrays[name] = (self._host_codes, torch.int8)
+        return {name: (np.ascontiguousarray(array), dtype) for name, (array, dtype) in arrays.items()}     # (they are: no copy)
+
+    def _gather(self, name, lo, hi):
+        """Rows perm(lo) .. perm(hi - 1) of a source of ``_gather_sources`` on the device: gathered by host threads
+        (``bear_shuffle_gather_host``; the call releases the GIL) into a block that goes up through the ring like any other, so
+        the worker thread still enqueues nothing but ``Uploader.put`` (see ``_enqueue``)."""
+        array, dtype = self._sources[name]
+        return self._up.put(kernels.shuffle_gather_host(array, lo, hi - lo, self.data.shuffle_seed), dtype)
 
     def _slab(self, name, lo, hi):
         """-> (rows [lo, hi) of a count column, or of the k-mer codes, on the device; whether these are ASCII bytes still to be encoded)"""
@@ -331,10 +360,12 @@ class ResidentBatches:
         return shuffled
 
     def _enqueue(self, k):
-        """Batch k's slabs: asynchronous uploads on the side stream (or slices of the shuffled columns)."""
+        """Batch k's slabs: asynchronous uploads on the side stream (or slices of the shuffled columns, or their rows gathered by
+        range on the host and uploaded)."""
         # INVARIANT: host tables in file order take this on the WORKER thread (``_upload_all``, ``_prefetch``), next to the compute
-        # stream's work on the batch before: nothing here may enqueue on the compute stream -- ``Uploader.put`` only.  (The slices of
-        # a shuffled epoch and of a table already in HBM are cut on the calling thread: no worker exists then.)
+        # stream's work on the batch before: nothing here may enqueue on the compute stream -- ``Uploader.put`` only (``_gather`` ends
+        # in it).  (The slices of a shuffled epoch permuted in HBM and of a table already in HBM are cut on the calling thread: no
+        # worker exists then.)
         piece, shuffled = self._pieces[k], self._shuffled
         lo, hi = piece.off, piece.off + (piece.g1 - piece.g0)          # this rank's piece of the batch inside the dataset's arrays
         entry = {"global_rows": piece.b - piece.a, "rows": hi - lo, "row0": piece.g0, "plans": {}}
@@ -342,7 +373,10 @@ class ResidentBatches:
             entry["row_ids"] = self._up.put(self._row_index[lo:hi], torch.int32)
         for name in self._names:
             # (the codes come last: theirs is the flag that stays)
-            entry[name], entry["_raw_codes"] = (shuffled[name][lo:hi].clone(), False) if shuffled else self._slab(name, lo, hi)
+            if self._by_range:
+                entry[name], entry["_raw_codes"] = self._gather(name, lo, hi), name == "codes" and self._fast_codes
+            else:
+                entry[name], entry["_raw_codes"] = (shuffled[name][lo:hi].clone(), False) if shuffled else self._slab(name, lo, hi)
         return entry
 
     def _finish(self, entry):

@@ -1,5 +1,5 @@
 // bear_hip.hip -- the C ABI (include/bear_hip.h) of the workspace and of the Dirichlet-multinomial steps on gfx950: status strings,
-// workspace, synthetic tables, samplers and the row shuffle; the row and sorted kernels (kernels_rows.h, kernels_sorted.h), plans and
+// workspace, synthetic tables and samplers; the row and sorted kernels (kernels_rows.h, kernels_sorted.h), plans and
 // the planned mode-N / mode-R steps (kernels_plan.h, kernels_refplan.h), bear_ref's mixing (kernels_refmix.h, kernels_mixplan.h).
 // The linear head, the convolutional head and evaluation are units of their own (bear_linear.hip, bear_cnn.hip, bear_eval.hip);
 // what the units share on the host is in bear_host.h.
@@ -12,7 +12,6 @@
 #include "kernels_refmix.h"
 #include "kernels_mixplan.h"
 #include "kernels_sample.h"
-#include "kernels_shuffle.h"
 #include "kernels_refplan.h"
 
 #ifdef PLN_STAMPS  // developer build: per-wave phase timers of dm_prior_plan_kernel land in ws->dbg
@@ -974,29 +973,6 @@ int bear_logdir_sample_wide_f64(const uint32_t *counts, const double *prior, uin
   if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
   return logdir_sample_launch(counts, prior, n_rows, width, h, n_h, with_ar, van, n_van, mc_samples, map, seed, row_base, out,
                               stream);
-}
-
-int bear_shuffle_rows(const void *src, void *dst, uint64_t n_rows, uint32_t row_bytes, uint64_t seed, void *stream) {
-  if (n_rows == 0 || row_bytes == 0) return BEAR_OK;
-  if (!src || !dst || src == dst) return BEAR_ERR_INVALID_ARG;
-  if (n_rows > (1ull << 62) / row_bytes) return BEAR_ERR_INVALID_ARG;
-  const uint32_t hb = shf_half_bits(n_rows);
-  const bool words = (row_bytes % 4 == 0) && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 4 == 0);
-  const uint64_t total = words ? n_rows * (row_bytes / 4) : n_rows * (uint64_t)row_bytes;
-  uint64_t blocks = (total + 255) / 256;
-  if (blocks > 1u << 20) blocks = 1u << 20;
-  if (words)
-    hipLaunchKernelGGL(shuffle_words_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint32_t *>(src), static_cast<uint32_t *>(dst), n_rows, row_bytes / 4, hb, seed);
-  else
-    hipLaunchKernelGGL(shuffle_bytes_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), n_rows, row_bytes, hb, seed);
-  HIP_TRY(hipGetLastError());
-  return BEAR_OK;
-}
-
-uint64_t bear_shuffle_source_row(uint64_t i, uint64_t n_rows, uint64_t seed) {
-  return (n_rows == 0 || i >= n_rows) ? i : shf_perm(i, n_rows, shf_half_bits(n_rows), seed);
 }
 
 int bear_stream_read(bear_ws *ws, const void *src, uint64_t n_bytes, void *stream) {

@@ -1,12 +1,13 @@
 // bear_host.h -- internal: the host side that the units of libbear_hip share.
 //
 // One unit per kernel family, each the only one to include -- and so to emit -- the kernels it launches:
-//   bear_hip.hip     status strings, the workspace, synthetic tables, samplers, the row shuffle; the DM steps (rows, sorted,
+//   bear_hip.hip     status strings, the workspace, synthetic tables, samplers; the DM steps (rows, sorted,
 //                    planned, reference-aware, ref-mix) and the plan itself
 //   bear_linear.hip  k-mer packing, the paired lists, the linear AR head (fused step and rows, both also at rows of 21), the Adam launch
 //   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21 and bear_net's step with it
 //   bear_eval.hip    held-out evaluation (5- and 21-wide), the wide DM step and bear_ref's wide steps, the evaluation plan, the BMM marginal
-//   (bear_score.hip, scoring under a sampled table, and bear_count.hip, counting, need nothing of this file: bear_dev.h alone)
+//   (bear_score.hip, scoring under a sampled table, bear_shuffle.hip, the row shuffle, and bear_count.hip, counting, need nothing of
+//   this file: bear_dev.h alone)
 // What a unit needs of another goes through the declarations at the end of this file.
 //
 // Device memory and HIP errors, in every unit (bear_dev.h): a temporary sits in a dev_buf, which frees it when the function returns

@@ -5,8 +5,9 @@
 // table).  Here the permutation is a keyed bijection of [0, n): a 4-round Feistel network on the smallest even
 // number of bits covering n, cycle-walked back into range (expected < 4 evaluations), so any rank can compute any
 // row's source without a permutation table, and the oracle restates it (bear_oracle.py:shuffle_perm).
-// dst[i] = src[perm(i)] as one gather pass: rows of `row_bytes` bytes (20 for a count slab, 8 for packed k-mers,
-// lag for k-mer bytes).
+// dst[j] = src[perm(first + j)] for j < n_out as one gather pass: rows of `row_bytes` bytes (20 or 84 for a count slab, 8 for
+// packed k-mers, lag for k-mer bytes).  first = 0, n_out = n is the whole column (bear_shuffle_rows); a batch is a range of it
+// (bear_shuffle_rows_range).  The lanes next to each other read the words (bytes) next to each other of one source row.
 #pragma once
 #include "bear_common.h"
 #include "synth_hash.h"
@@ -42,25 +43,30 @@ static inline uint32_t shf_half_bits(uint64_t n) {
   return b;
 }
 
-// one thread per 4-byte word of the destination (row_bytes % 4 == 0) -- coalesced stores, gathered loads
+// Blocks of 256 threads a gather launches at most: twice the 2048 threads each of the 256 CUs holds, so the device stays full while
+// blocks retire, and a range beyond 2^20 words (bytes) takes further trips of the loop.
+#define SHF_MAX_BLOCKS 4096u
+
+// one thread per 4-byte word of the destination (row_bytes % 4 == 0) -- coalesced stores, gathered loads; the grid strides over
+// the n_out * row_words words, so a capped grid serves any range
 __global__ __launch_bounds__(256) void shuffle_words_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst,
-                                                            uint64_t n_rows, uint32_t row_words, uint32_t half_bits,
-                                                            uint64_t seed) {
-  const uint64_t total = n_rows * row_words;
+                                                            uint64_t n_rows, uint64_t first, uint64_t n_out, uint32_t row_words,
+                                                            uint32_t half_bits, uint64_t seed) {
+  const uint64_t total = n_out * row_words;
   for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256) {
-    const uint64_t i = e / row_words;
-    const uint32_t w = (uint32_t)(e - i * row_words);
-    dst[e] = src[shf_perm(i, n_rows, half_bits, seed) * row_words + w];
+    const uint64_t j = e / row_words;
+    const uint32_t w = (uint32_t)(e - j * row_words);
+    dst[e] = src[shf_perm(first + j, n_rows, half_bits, seed) * row_words + w];
   }
 }
 
 __global__ __launch_bounds__(256) void shuffle_bytes_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
-                                                            uint64_t n_rows, uint32_t row_bytes, uint32_t half_bits,
-                                                            uint64_t seed) {
-  const uint64_t total = n_rows * row_bytes;
+                                                            uint64_t n_rows, uint64_t first, uint64_t n_out, uint32_t row_bytes,
+                                                            uint32_t half_bits, uint64_t seed) {
+  const uint64_t total = n_out * row_bytes;
   for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256) {
-    const uint64_t i = e / row_bytes;
-    const uint32_t w = (uint32_t)(e - i * row_bytes);
-    dst[e] = src[shf_perm(i, n_rows, half_bits, seed) * row_bytes + w];
+    const uint64_t j = e / row_bytes;
+    const uint32_t w = (uint32_t)(e - j * row_bytes);
+    dst[e] = src[shf_perm(first + j, n_rows, half_bits, seed) * row_bytes + w];
   }
 }

@@ -153,8 +153,9 @@ class CountDataset:
 
     def shuffle(self, seed):
         """The `shuf` step of docs/usage.rst:191-200 without rewriting the file: training and evaluation see the rows
-        in the order ``perm_seed`` (one gather pass on the device at upload, ``bear_shuffle_rows``).  Iterating the
-        dataset on the host still yields file order."""
+        in the order ``perm_seed`` (one gather pass on the device at upload, ``bear_shuffle_rows``; a streamed epoch and a
+        rank's pieces are gathered batch by batch, ``bear_shuffle_rows_range``).  Iterating the dataset on the host still
+        yields file order."""
         if self.shard is not None:
             raise ValueError("the device shuffle permutes whole columns: load the table unsharded (or pre-shuffle the file, "
                              "docs/usage.rst:191-200) to combine it with row sharding")

@@ -807,6 +807,49 @@ def shuffle_rows(src, seed):
     return dst
 
 
+def shuffle_rows_range(src, first, n_out, seed, n_rows=None, row_shape=None, dtype=None, out=None):
+    """One launch of ``bear_shuffle_rows_range`` on the current stream: ``dst[j] = src[perm_seed(first + j)]`` for ``j < n_out``
+    along dim 0 -- rows ``[first, first + n_out)`` of ``shuffle_rows(src, seed)``.  ``src``: a contiguous CUDA tensor; ``n_rows``
+    / ``row_shape`` / ``dtype`` (of the source's element size) describe its bytes as rows and default to the tensor's own.
+    ``out``: the destination, a contiguous CUDA tensor ``[n_out, *row_shape]``; a new one otherwise."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dim() >= 1):
+        raise ValueError("src must be a contiguous CUDA tensor")
+    device, item = src.device, src.element_size()
+    dtype = src.dtype if dtype is None else dtype
+    n_rows = src.shape[0] if n_rows is None else int(n_rows)
+    row_shape = tuple(src.shape[1:]) if row_shape is None else tuple(row_shape)
+    first, n_out = int(first), int(n_out)
+    row_elems = int(np.prod(row_shape, dtype=np.int64))
+    if torch.empty(0, dtype=dtype).element_size() != item or n_rows * row_elems != src.numel():
+        raise ValueError("n_rows, row_shape and dtype must describe the source's own bytes")
+    if not (0 <= first and 0 <= n_out and first + n_out <= n_rows):
+        raise ValueError(f"rows [{first}, {first + n_out}) of {n_rows}")
+    if out is None:
+        out = torch.empty((n_out,) + row_shape, dtype=dtype, device=device)
+    elif not (isinstance(out, torch.Tensor) and out.device == device and out.is_contiguous() and out.dtype == dtype
+              and tuple(out.shape) == (n_out,) + row_shape):
+        raise ValueError(f"out must be a contiguous {dtype} tensor {(n_out,) + row_shape} on {device}")
+    _launch(device, "bear_shuffle_rows_range", _ptr(src), _ptr(out), n_rows, first, n_out, item * row_elems, int(seed) & (2 ** 64 - 1))
+    return out
+
+
+HOST_GATHER_THREADS = 16
+
+
+def shuffle_gather_host(array, first, n_out, seed, n_threads=HOST_GATHER_THREADS):
+    """``bear_shuffle_gather_host``: rows ``perm_seed(first) .. perm_seed(first + n_out - 1)`` of the C-contiguous NumPy ``array``
+    (along axis 0) as a new array, gathered by ``n_threads`` host threads.  Needs no device."""
+    if not (isinstance(array, np.ndarray) and array.flags.c_contiguous and array.ndim >= 1):
+        raise ValueError("a C-contiguous NumPy array")
+    n = array.shape[0]
+    first, n_out = int(first), int(n_out)
+    out = np.empty((max(n_out, 0),) + array.shape[1:], dtype=array.dtype)
+    row_bytes = array.nbytes // n if n else 0
+    _lib.call("bear_shuffle_gather_host", ctypes.c_void_p(array.ctypes.data), ctypes.c_void_p(out.ctypes.data), n, first & (2 ** 64 - 1),
+              n_out & (2 ** 64 - 1), row_bytes, int(seed) & (2 ** 64 - 1), int(n_threads))
+    return out
+
+
 def kmer_order(kmer_code, lag):
     """``bear_kmer_order_u64``: int32-storage permutation [n] that sorts packed contexts (``pack_kmers``) lexicographically, first
     letter most significant, stable.  Stream-ordered: the sort's scratch (``kmer_order_scratch_bytes``: ~20 B per row) is a torch

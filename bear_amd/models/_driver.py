@@ -78,7 +78,8 @@ def _run(config, kind):
     num_ds = int(config["data"]["num_ds"])
     load = dataloader.sparse_dataloader if sparse else dataloader.dataloader
     # two optional keys beyond the reference's: [data] binary_cache (True or a directory: parsed tables are kept on disk,
-    # dense format only) and [data] shuffle_seed (rows are permuted on the device at upload instead of `shuf`-ing the file)
+    # dense format only) and [data] shuffle_seed (rows are permuted at upload instead of `shuf`-ing the file; a table that does not fit
+    # the device is streamed all the same, every batch gathered by row range)
     extra_kw = {}
     if config["data"].get("binary_cache") and load is dataloader.dataloader:
         bc = config["data"]["binary_cache"]
@@ -96,8 +97,9 @@ def _run(config, kind):
         parts = [whole.deal_by_kmer(rank, world)]
         del whole
     elif world > 1 and load is dataloader.dataloader and not shuffle_seed:
-        # every rank decodes and holds only its pieces of the batches (the device shuffle needs whole columns: then, as for the
-        # small sparse format, each rank loads the table and slices its rows at upload)
+        # every rank decodes and holds only its pieces of the batches (a shuffled table's rows come from anywhere in the file: then,
+        # as for the small sparse format, each rank parses the whole table -- and ResidentBatches gathers only the rank's pieces of
+        # the shuffled batches out of it, by row range: no rank sends a whole column to its device)
         if extra_kw.get("binary_cache"):
             # a sharded load reads a binary cache but cannot write one (no rank holds the whole table): rank 0 builds the missing
             # ones with a plain load first, the others wait, then every rank reads its row ranges

@@ -53,7 +53,9 @@ extern "C" {
                                   + bear_dm_cnn_wide_f64, bear_net_cnn_train_reduce_wide_f64, bear_net_cnn_train_step_wide_f64
                                   (bear_net's step with the convolutional AR function on rows of 21 as two launches);
                                   + bear_score_transitions_u64, bear_kmer_find_u64, bear_score_sum_f64 (variant and sequence
-                                  scoring on the device) */
+                                  scoring on the device);
+                                  + bear_shuffle_rows_range, bear_shuffle_gather_host (a range of
+                                  the shuffled rows: streamed and multi-rank shuffled epochs) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -755,9 +757,23 @@ int bear_cache_read(const char *path, uint64_t row0, uint64_t n_rows, char *kmer
  * cycle walking; bear_shuffle_source_row evaluates it on the host, oracle/bear_oracle.py:shuffle_perm restates it).
  *   src, dst [dev] n_rows rows of row_bytes bytes (20: a count slab; 8: packed k-mers; lag: k-mer bytes); dst != src.
  * Calling it with the same seed on every column of a table keeps the columns aligned.
+ *
+ * A range of the shuffled rows, for an epoch whose whole columns do not go through the device (a streamed epoch, a rank's pieces):
+ * batch [a, b) of the shuffled table is rows perm(a) .. perm(b - 1) of the table in file order.
+ *   bear_shuffle_rows_range: dst[j] = src[perm(first + j)] for j < n_out, perm as above (bear_shuffle_rows is first = 0, n_out =
+ *     n_rows).  src [dev] n_rows rows; dst [dev] n_out rows, dst != src.  Asynchronous on `stream`; first + n_out > n_rows is
+ *     BEAR_ERR_INVALID_ARG, n_out = 0 BEAR_OK without a launch.  The lanes that read one row read neighbouring words (bytes).
+ *     (bear_amd itself calls it through bear_shuffle_rows only: its streamed epochs gather on the host, below.)
+ *   bear_shuffle_gather_host: the same rows from host `src` into host `dst` by n_threads (clamped to 1 .. 64) host threads, each
+ *     a contiguous piece of the range.  Needs no device; synchronous.  This is how a streamed epoch and a rank's pieces of a
+ *     shuffled table are gathered: the block then goes up like any other.
  */
 int bear_shuffle_rows(const void *src, void *dst, uint64_t n_rows, uint32_t row_bytes, uint64_t seed, void *stream);
 uint64_t bear_shuffle_source_row(uint64_t i, uint64_t n_rows, uint64_t seed);
+int bear_shuffle_rows_range(const void *src, void *dst, uint64_t n_rows, uint64_t first, uint64_t n_out, uint32_t row_bytes,
+                            uint64_t seed, void *stream);
+int bear_shuffle_gather_host(const void *src, void *dst, uint64_t n_rows, uint64_t first, uint64_t n_out, uint32_t row_bytes,
+                             uint64_t seed, int n_threads);
 
 /*
  * k-mer order of a batch.  The sums of a training step (bear_net.py:146-197) do not depend on the order of a batch's rows, and
