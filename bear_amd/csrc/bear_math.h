@@ -213,6 +213,38 @@ __device__ __forceinline__ double bear_exp_tab(double z, const double *__restric
   return __longlong_as_double(__double_as_longlong(v) + ((long long)(ki >> 7) << 52));
 }
 
+// The two near-copies of bear_exp_tab, kept beside it (and within reach of the probe unit, kernels_probe.h): the convolutional
+// head's (kernels_cnn.h, cnn_elu) and the linear head's (kernels_linear.h, lin_softmax_of_logits).
+__device__ __forceinline__ double cnn_exp_neg(double z, const double *__restrict__ tab) {   // bear_exp_tab without its branch
+  z = z > -700.0 ? z : -700.0;
+  const double kf = __builtin_rint(z * 184.66496523378731);
+  double r = __builtin_fma(kf, -0x1.62e42fee00000p-8, z);
+  r = __builtin_fma(kf, -0x1.a39ef35793c76p-40, r);
+  const int ki = (int)kf;
+  const double t = tab[ki & (BEAR_EXPTAB_N - 1)];
+  double p = __builtin_fma(r, 1.0 / 120.0, 1.0 / 24.0);
+  p = __builtin_fma(r, p, 1.0 / 6.0);
+  p = __builtin_fma(r, p, 0.5);
+  p = __builtin_fma(r, p, 1.0);
+  const double v = __builtin_fma(t, r * p, t);
+  return __longlong_as_double(__double_as_longlong(v) + ((long long)(ki >> 7) << 52));
+}
+
+// exp(d ln2 / 128): the tables hold logits in units of ln2 / 128, so the argument reduction of bear_exp_tab is a
+// rounding and an exact subtraction; 2^(j/128) from the table, degree-5 polynomial on |r| <= 1/2 unit, v_ldexp for the rest.
+__device__ __forceinline__ double lin_exp_units(double d, const double *__restrict__ tab) {
+  const double kf = __builtin_rint(d), r = d - kf;
+  const int ki = (int)kf;
+  const double t = tab[ki & (BEAR_EXPTAB_N - 1)];
+  constexpr double c1 = 0.0054152123481245727, c2 = c1 * c1 / 2.0, c3 = c1 * c1 * c1 / 6.0, c4 = c1 * c1 * c1 * c1 / 24.0,
+                   c5 = c1 * c1 * c1 * c1 * c1 / 120.0;
+  double p = __builtin_fma(r, c5, c4);
+  p = __builtin_fma(r, p, c3);
+  p = __builtin_fma(r, p, c2);
+  p = __builtin_fma(r, p, c1);
+  return __builtin_ldexp(__builtin_fma(t, r * p, t), ki >> 7);
+}
+
 // ---- reductions -----------------------------------------------------------------
 // Sum over the 64 lanes, in every lane: quads and rows of 16 on DPP moves, the rows and halves on v_permlane16/32_swap (gfx950) --
 // ~25 instructions where six __shfl_down of a double were twelve ds_bpermute round trips (every planned kernel's epilogue, twice).
@@ -236,7 +268,12 @@ __device__ __forceinline__ double bear_wave_sum(double v) {
     const auto c = step == 0 ? __builtin_amdgcn_permlane16_swap(hi, hi, false, false) : __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
     v = __longlong_as_double(((long long)c[0] << 32) | a[0]) + __longlong_as_double(((long long)c[1] << 32) | a[1]);
   }
-  return v;  // in every lane
+  // In every lane -- lane 0's value: behind row_ror the four quads of a row add the quads' sums in four different orders, so the
+  // lanes agreed to an ulp, not to the bit (tests/test_math_probe_gpu.py).  Lane 0's is the one every caller has stored all along.
+  const long long q = __double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)q);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(q >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 // ... and the largest of 64 non-negative values, the same way
 __device__ __forceinline__ double bear_wave_max(double v) {

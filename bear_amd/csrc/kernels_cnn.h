@@ -251,22 +251,7 @@ __device__ __forceinline__ void cnn_gather_t1(double (&t1)[N], const cnn_level_i
   }
 }
 
-// elu(y) and its derivative: y > 0 ? (y, 1) : (exp(y) - 1, exp(y))     (tf.nn.elu, alpha = 1)
-__device__ __forceinline__ double cnn_exp_neg(double z, const double *__restrict__ tab) {   // bear_exp_tab without its branch
-  z = z > -700.0 ? z : -700.0;
-  const double kf = __builtin_rint(z * 184.66496523378731);
-  double r = __builtin_fma(kf, -0x1.62e42fee00000p-8, z);
-  r = __builtin_fma(kf, -0x1.a39ef35793c76p-40, r);
-  const int ki = (int)kf;
-  const double t = tab[ki & (BEAR_EXPTAB_N - 1)];
-  double p = __builtin_fma(r, 1.0 / 120.0, 1.0 / 24.0);
-  p = __builtin_fma(r, p, 1.0 / 6.0);
-  p = __builtin_fma(r, p, 0.5);
-  p = __builtin_fma(r, p, 1.0);
-  const double v = __builtin_fma(t, r * p, t);
-  return __longlong_as_double(__double_as_longlong(v) + ((long long)(ki >> 7) << 52));
-}
-
+// elu(y) and its derivative: y > 0 ? (y, 1) : (exp(y) - 1, exp(y))     (tf.nn.elu, alpha = 1; cnn_exp_neg: bear_math.h)
 __device__ __forceinline__ double cnn_elu(double y, const double *exptab, double &deriv) {
   const double ex = cnn_exp_neg(y < 0.0 ? y : 0.0, exptab);
   deriv = y > 0.0 ? 1.0 : ex;

@@ -393,21 +393,8 @@ __device__ __forceinline__ void lin_table_row(const double *T, unsigned long lon
   }
 }
 
-// exp(d ln2 / 128): the tables hold logits in units of ln2 / 128, so the argument reduction of bear_exp_tab is a
-// rounding and an exact subtraction; 2^(j/128) from the table, degree-5 polynomial on |r| <= 1/2 unit, v_ldexp for the rest.
+// the tables hold logits in units of ln2 / 128: lin_exp_units (bear_math.h) takes them as they are
 #define LIN_EXP_UNIT 184.66496523378731    // 128 / ln 2
-__device__ __forceinline__ double lin_exp_units(double d, const double *__restrict__ tab) {
-  const double kf = __builtin_rint(d), r = d - kf;
-  const int ki = (int)kf;
-  const double t = tab[ki & (BEAR_EXPTAB_N - 1)];
-  constexpr double c1 = 0.0054152123481245727, c2 = c1 * c1 / 2.0, c3 = c1 * c1 * c1 / 6.0, c4 = c1 * c1 * c1 * c1 / 24.0,
-                   c5 = c1 * c1 * c1 * c1 * c1 / 120.0;
-  double p = __builtin_fma(r, c5, c4);
-  p = __builtin_fma(r, p, c3);
-  p = __builtin_fma(r, p, c2);
-  p = __builtin_fma(r, p, c1);
-  return __builtin_ldexp(__builtin_fma(t, r * p, t), ki >> 7);
-}
 
 // ---- the normalised row of five from four products of exponentials (the fifth is the 1 the tables are relative to) ...
 __device__ __forceinline__ void lin_softmax_of_exp(const double (&e)[4], double (&f)[5]) {

@@ -414,6 +414,32 @@ def dm_items(x, c, path=0, ws=None):
     return D, P
 
 
+def _probe_ops():
+    import re
+    text = open(_lib.HEADER_PATH).read()
+    return {name.lower(): int(v) for name, v in re.findall(r"^#define BEAR_PROBE_(\w+) (\d+)\s*$", text, flags=re.M) if name != "N_OPS"}
+
+
+PROBE_OPS = _probe_ops()                                    # name -> op of bear_math_probe_f64, as include/bear_hip.h numbers them
+PROBE_ITEM_OPS = ("srt_general", "srt_general_fast", "srt_general_auto", "row_item_tab", "row_item")
+
+
+def math_probe(op, a, b=None, ws=None):
+    """One device math routine, element by element (diagnostic entry; include/bear_hip.h, bear_math_probe_f64): ``op`` a key of
+    ``PROBE_OPS``, ``a`` a contiguous CUDA float64 [n].  The item routines (``PROBE_ITEM_OPS``) take the counts ``b`` as float64 [n]
+    and return (D, P); every other routine returns one tensor."""
+    item = op in PROBE_ITEM_OPS
+    if not (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous() and a.dim() == 1):
+        raise ValueError("a: contiguous CUDA float64 [n]")
+    if item != (b is not None) or (item and not (b.is_cuda and b.dtype == torch.float64 and b.is_contiguous() and b.shape == a.shape)):
+        raise ValueError("b: contiguous CUDA float64 [n] for the item routines, None otherwise")
+    ws = ws or default_workspace(a.device)
+    out0 = torch.empty_like(a)
+    out1 = torch.empty_like(a) if item else None
+    _launch(a.device, "bear_math_probe_f64", ws.handle, int(PROBE_OPS[op]), _ptr(a), _ptr(b), a.shape[0], _ptr(out0), _ptr(out1))
+    return (out0, out1) if item else out0
+
+
 LINEAR_MAX_LAG = 21   # LIN_MAX_LAG of kernels_linear.h (3 bits per letter in one 64-bit word)
 
 

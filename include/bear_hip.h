@@ -55,7 +55,8 @@ extern "C" {
                                   + bear_score_transitions_u64, bear_kmer_find_u64, bear_score_sum_f64 (variant and sequence
                                   scoring on the device);
                                   + bear_shuffle_rows_range, bear_shuffle_gather_host (a range of
-                                  the shuffled rows: streamed and multi-rank shuffled epochs) */
+                                  the shuffled rows: streamed and multi-rank shuffled epochs);
+                                  + bear_math_probe_f64 (the device math routines one at a time: tests and diagnostics) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -642,6 +643,45 @@ int bear_bmm_f64(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, const dou
  */
 int bear_dm_items_f64(bear_ws *ws, const double *x, const uint32_t *c, uint64_t n, int path, double *D,
                       double *P, void *stream);
+
+/*
+ * The device math routines underneath every kernel, one routine per launch and element by element (tests / diagnostics, as
+ * bear_dm_items_f64; no production path calls it).  The kernel calls the routine the production kernels call, on tables staged
+ * as they stage them (the workspace's log table into LDS, the exp table by exp2(k / 128) on the device).
+ *   a, out0 [dev] double [n];  b, out1 [dev] double [n], read and written by the item routines only (NULL elsewhere)
+ *   out0[i] = routine(a[i]):
+ *     RCP 1/a;  LOG_TAB[_V] the table log, a > 0 finite (_V: the form with its leading coefficient in vector registers; the same
+ *     bits);  LOG1P_SMALL[_V] log(1 + a), |a| <= 2^-8;  LOG1P_POS log(1 + a), a >= 0;  EXP_TAB / CNN_EXP_NEG exp(a), a <= 0 (0 /
+ *     exp(-700) below -700);  LIN_EXP_UNITS 2^(a / 128);  STIR_LG / STIR_PSI the Stirling tails of lgamma / digamma at y = 1 / a;
+ *     WAVE_SUM / WAVE_MAX the sum / the largest (of non-negative values) of each whole wave of 64 elements, in every lane of it
+ *     (elements past n count as 0)
+ *   item routines, x = a[i] and the count c = b[i], an exact integer >= 1 as a double (row totals pass 2^32):
+ *     out0[i] = lgamma(x + c) - lgamma(x), out1[i] = digamma(x + c) - digamma(x) by
+ *     SRT_GENERAL[_FAST|_AUTO] the sorted / planned family's general routine on the library log, on the table log (NaN outside
+ *     0 < x < 2^1000), and the kernels' choice between the two;  ROW_ITEM_TAB / ROW_ITEM the rows family's item with / without
+ *     the log table.  x <= 0 or NaN gives NaN from SRT_GENERAL, SRT_GENERAL_FAST and SRT_GENERAL_AUTO.
+ */
+#define BEAR_PROBE_RCP 0
+#define BEAR_PROBE_LOG_TAB 1
+#define BEAR_PROBE_LOG_TAB_V 2
+#define BEAR_PROBE_LOG1P_SMALL 3
+#define BEAR_PROBE_LOG1P_SMALL_V 4
+#define BEAR_PROBE_LOG1P_POS 5
+#define BEAR_PROBE_EXP_TAB 6
+#define BEAR_PROBE_CNN_EXP_NEG 7
+#define BEAR_PROBE_LIN_EXP_UNITS 8
+#define BEAR_PROBE_STIR_LG 9
+#define BEAR_PROBE_STIR_PSI 10
+#define BEAR_PROBE_WAVE_SUM 11
+#define BEAR_PROBE_WAVE_MAX 12
+#define BEAR_PROBE_SRT_GENERAL 13
+#define BEAR_PROBE_SRT_GENERAL_FAST 14
+#define BEAR_PROBE_SRT_GENERAL_AUTO 15
+#define BEAR_PROBE_ROW_ITEM_TAB 16
+#define BEAR_PROBE_ROW_ITEM 17
+#define BEAR_PROBE_N_OPS 18
+int bear_math_probe_f64(bear_ws *ws, int op, const double *a, const double *b, uint64_t n, double *out0, double *out1,
+                        void *stream);
 
 /*
  * Posterior sampling of transition probabilities (inference apps).

@@ -150,6 +150,7 @@ def test_one_hot_and_linear():
 
 # ---- the width-generic oracle (oracle_dm_prior_w_f64): what the wide kernels are held to
 H_GRID = (-20.0, -6.0, -3.0, 0.0, 0.37, 2.5, 6.0, 10.0)      # the h_signed values of tests/test_wide_kernels_gpu.py
+H_LARGE = (-30.0, -45.0)     # ... and its large concentrations: x up to 21 e^45 = 7e20, past the 2^60 switch of the device's item routine
 
 
 @pytest.mark.parametrize("train_ar", [False, True])
@@ -198,20 +199,23 @@ def _item_sample():
     cells = np.unique(np.r_[t[t > 0], t.sum(1, dtype=np.uint64)[t.sum(1) > 0].astype(np.float64), 64, 65, 66])
     fs = np.concatenate([prior_rows_wide(8, 21, k, seed=2).ravel() for k in PRIOR_KINDS])
     pairs = []
-    for h_s in H_GRID:
+    for h_s in H_GRID + H_LARGE:                                      # (H_LARGE last: the draws of H_GRID stay what they were)
         h = np.exp(h_s)
         x = fs[rng.integers(0, fs.size, 25)] / h + 1e-7
         x[:3] = [1e-7, 21 / h + 21e-7, 3.0 / h + 1e-7]                # an empty cell, a row total A, a scaled row's largest cell
+        if h_s in H_LARGE:                                            # cells of 0.04 .. 5 and one at the switch itself
+            x[3:9] = np.array([0.04, 0.2, 0.5, 1.0, 5.0, 2.0 ** 60 * h]) / h + 1e-7
         pairs += list(zip(x, rng.choice(cells, x.size)))
     return pairs
 
 
 def test_oracle_w_items_match_mpmath():
     mp = pytest.importorskip("mpmath")
-    mp.mp.dps = 40
     pairs = _item_sample()
-    assert len(pairs) >= 200
+    assert len(pairs) >= 250 and sum(x > 2.0 ** 60 for x, _ in pairs) >= 8
     for x, c in pairs:
+        # digits to spare behind the cancellation of the two digamma values, ~x / c of them (at 40 digits the difference is 0 from x ~ 1e20)
+        mp.mp.dps = 40 if x <= 1.0 else int(50 + 2.2 * np.log10(x))
         D, P = co.dm_item_w(x, c)
         X, C = mp.mpf(float(x)), mp.mpf(float(c))
         wD = mp.loggamma(X + C) - mp.loggamma(X)

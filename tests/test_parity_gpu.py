@@ -8,7 +8,7 @@ import torch
 
 import bear_oracle as o
 import c_oracle as co
-from util import dense_table, edge_table, mixed_heavy_table, prior_rows, sparse_table
+from util import dense_table, edge_table, mixed_heavy_table, prior_rows, prior_rows_wide, sparse_table
 
 pytestmark = pytest.mark.gpu
 
@@ -190,12 +190,11 @@ def test_additivity_and_permutation_full_size(dev):
 
 
 def test_item_paths_against_mpmath_grid(dev):
-    """Every branch of the lgamma/digamma-difference evaluation, item by item, against
-    SciPy (loggamma / digamma differences are computed where they are well conditioned,
-    and by the exact rising-factorial sums for small c): product path for each c = 1..31,
-    the c = 31/32 switch to the Stirling path, the x < 8 shift, tiny and huge x."""
+    """Every branch of the lgamma/digamma-difference evaluation, item by item, against mpmath (loggamma / digamma differences at 40
+    digits for c > 64, the exact rising-factorial sums for small c): the product path for each c = 1..24 of srt_light (path 0) and
+    c = 1..16 of bear_dm_item (paths 1, 2), the 24/25 and 16/17 switches to the Stirling path, the x < 8 shift, tiny and huge x.
+    (The whole domain -- x from 1e-300 to 2^999, counts past 2^32, the rows family's routine: tests/test_math_probe_gpu.py.)"""
     import torch
-    from scipy.special import gammaln, digamma
     from bear_amd import kernels
     xs = np.array([1e-7, 3e-5, 0.013, 0.1 + 1e-7, 0.5, 0.999, 1.0, 1.7, 4.0, 7.99, 8.0, 8.01, 31.4, 250.0,
                    1e4, 1e7, 2.0 ** 30, 2.0 ** 31, 1e12])
@@ -220,15 +219,63 @@ def test_item_paths_against_mpmath_grid(dev):
     for path in (0, 1, 2):
         D, P = kernels.dm_items(dx, dc, path=path)
         D, P = D.cpu().numpy(), P.cpu().numpy()
-        # absolute tolerance scaled by the L1 mass of the sum (sum |log(x+j)|), relative 1e-13
-        massD = np.array([np.sum(np.abs(np.log(x + np.arange(min(int(c), 64))))) + abs(d) + abs(gammaln(x)) * (c > 0)
-                          for x, c, d in zip(X, C, Dw)])
+        # absolute tolerance scaled by the L1 mass of the sum itself, sum_j |log(x + j)| = D - 2 min(log x, 0) (only the first term can
+        # be negative), relative 1e-13.  (It carried |gammaln(x)| until the reference stopped being a SciPy difference: 2.7e13 at
+        # x = 1e12, which let D be wrong by 10.)
+        massD = Dw - 2.0 * np.minimum(np.log(X), 0.0) * (C > 0)
         assert np.all(np.abs(D - Dw) <= 4e-13 * massD + 1e-15)  # 1e-15: the table log of exactly 1.0 is ~1e-16, not 0, (path, np.max(np.abs(D - Dw) / (massD + 1e-300)))
         assert np.all(np.abs(P - Pw) <= 1e-13 * np.abs(Pw) + 1e-300), (path, np.max(np.abs(P - Pw) / (np.abs(Pw) + 1e-300)))
     # out-of-domain concentration -> NaN, never a silent number
     bad = torch.tensor([0.0, -1.0, float("nan")], dtype=torch.float64, device=dev)
     D, P = kernels.dm_items(bad, torch.tensor([3, 3, 3], dtype=torch.int32, device=dev))
     assert torch.isnan(D).all() and torch.isnan(P).all()
+
+
+H_LARGE = (-30.0, -45.0)   # concentrations f e^30 .. 5 e^45 = 1e13 .. 1.7e20: past SRT_XMAX = 2^30 and past the 2^60 switch of the item routines
+
+
+@pytest.mark.parametrize("kind", ["softmax", "tiny"])
+@pytest.mark.parametrize("h_s", H_LARGE)
+def test_large_concentrations(kind, h_s, dev):
+    """Every mode-N path on the edge rows at concentrations the other tables never reach (their h_signed grids stop at -20, x <= 4.9e8):
+    the sorted kernel, the rows kernel with gradient rows, the multinomial mode, the planned kernels and the dense form of the plan.
+    The reference is the width-generic oracle at width 5 -- every item in long double, held to mpmath at these very concentrations
+    (test_oracle.py::test_oracle_w_items_match_mpmath); the 5-wide oracle's lgamma differences cancel at x ~ 1e19."""
+    from bear_amd import kernels
+    tr = edge_table()
+    # ... and a table of its large-count rows alone, which gets the dense form
+    heavy = edge_table()
+    heavy = np.ascontiguousarray(np.tile(heavy[(heavy > 24).sum(1) >= 3], (40, 1)))
+    for tab, dense in ((tr, False), (heavy, True)):
+        n = len(tab)
+        f = prior_rows_wide(n, 5, kind, seed=4)
+        d_tr, d_f = _to_dev(tab, dev), _to_dev(f, dev)
+        want, wg = co.dm_prior_w(tab, f, h_s, want_grad=True, nthreads=4)
+        mass_h = co.dm_prior_mass_w(tab, f, h_s, nthreads=4)[0][0]
+        assert np.isfinite(want).all() and np.isfinite(wg).all() and mass_h > 0
+
+        def hold(got, g, what):
+            got = got.cpu().numpy()
+            _close(got[0], want[0], ELBO_RTOL)
+            _mass_close(got[1], want[1], mass_h, (kind, h_s, what))
+            if g is not None:
+                g = g.cpu().numpy()
+                assert np.allclose(g, wg, rtol=1e-9, atol=1e-9 * np.abs(wg).max()), (kind, h_s, what, np.abs(g - wg).max())
+        plan = kernels.Plan(d_tr, 5, rows_if_dense=True)
+        assert plan.rowwise == dense
+        norms = [False, True] if kind == "softmax" else [False]       # (the tiny cells leave rows that no longer sum to one)
+        for norm in norms:
+            hold(kernels.dm_prior_planned(plan, d_f, h_s, normalized=norm), None, ("planned", dense, norm))
+            hold(*kernels.dm_prior_planned(plan, d_f, h_s, normalized=norm, want_grad=True), ("planned rows", dense, norm))
+        if dense:
+            continue
+        hold(*kernels.dm_prior(d_tr, d_f, h_s), "sorted")
+        hold(*kernels.dm_prior(d_tr, d_f, h_s, want_grad=True), "rows")
+        want_ar, wg_ar = co.dm_prior_w(tab, f, h_s, train_ar=True, want_grad=True, nthreads=4)
+        got, g = kernels.dm_prior(d_tr, d_f, h_s, train_ar=True, want_grad=True)
+        _close(got.cpu().numpy()[0], want_ar[0], ELBO_RTOL)
+        assert got.cpu().numpy()[1] == 0.0 and want_ar[1] == 0.0
+        assert np.allclose(g.cpu().numpy(), wg_ar, rtol=1e-9, atol=1e-9 * np.abs(wg_ar).max())
 
 
 def test_sorted_kernel_matches_rows_kernel(dev):

@@ -100,6 +100,22 @@ def test_edge_rows_w21(kind, train_ar, want_grad):
     assert not bad, "\n".join(map(str, bad))
 
 
+H_LARGE = (-30.0, -45.0)   # concentrations up to 21 e^45 = 7e20: past the 2^60 switch of the item routine (the oracle's items are held
+#                            to mpmath there: test_oracle.py::test_oracle_w_items_match_mpmath)
+
+
+@pytest.mark.parametrize("want_grad", [False, True])
+@pytest.mark.parametrize("kind", ["softmax", "tiny"])
+def test_edge_rows_w21_large_concentrations(kind, want_grad):
+    c = edge_table_wide(21)
+    f = prior_rows_wide(len(c), 21, kind, seed=11)
+    bad = []
+    for h_s in H_LARGE:
+        got, g = _run(c, f, h_s, False, want_grad)
+        bad += _errors(got, g, c, f, h_s, False, want_grad, h_s)
+    assert not bad, "\n".join(map(str, bad))
+
+
 def _mp_rows(c, f, h_s, eps=EPS):
     """sum LL, d/dh_signed, gradient rows and their masses at 40 digits (mpmath)."""
     import mpmath as mp
