@@ -1,7 +1,8 @@
-// bear_score.hip -- scoring on the device: the three entries between the device count tables and the samplers' tables
+// bear_score.hip -- scoring on the device: the entries between the device count tables and the samplers' tables
 // (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
-// of a sampled table's rows over the transitions of every segment -- and sequence generation over the same key tables ("Sequence
-// generation").  The only unit that includes -- and so emits -- kernels_score.h and kernels_generate.h.
+// of a sampled table's rows over the transitions of every segment; the exact marginal of every segment, which needs no table -- and
+// sequence generation over the same key tables ("Sequence generation").  The only unit that includes -- and so emits --
+// kernels_score.h, kernels_marg.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -9,6 +10,7 @@
 #include "bear_dev.h"
 #include "bear_release_guard.h"
 #include "kernels_generate.h"
+#include "kernels_marg.h"
 #include "kernels_score.h"
 
 namespace {
@@ -84,6 +86,59 @@ int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_
                      rows, letters, seg, n_seg, n_t, partials.get(), scores);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;      // (partials goes with this frame: hipFree waits for the two launches)
+}
+
+int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
+                        const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van,
+                        int n_van, double *scores, void *stream) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  if (n_h < 0 || n_van < 0 || n_h > MRG_MAX_MODELS || n_van > MRG_MAX_MODELS || n_h + n_van < 1 || n_h + n_van > MRG_MAX_MODELS)
+    return BEAR_ERR_INVALID_ARG;
+  if ((n_h > 0 && (!h || !prior)) || (n_van > 0 && !van)) return BEAR_ERR_INVALID_ARG;
+  mrg_models P;
+  memset(&P, 0, sizeof(P));
+  P.n_h = n_h;
+  P.n_m = n_h + n_van;
+  for (int m = 0; m < n_h; ++m) {
+    if (!(h[m] > 0.0)) return BEAR_ERR_INVALID_ARG;
+    P.w[m] = 1.0 / h[m];
+  }
+  for (int m = 0; m < n_van; ++m) {
+    if (!(van[m] > 0.0)) return BEAR_ERR_INVALID_ARG;
+    P.w[n_h + m] = van[m];
+  }
+  if (n_rows >= SCR_ABSENT) return BEAR_ERR_INVALID_ARG;
+  if (n_seg == 0) return BEAR_OK;
+  if (!seg || !scores || misaligned8(seg) || misaligned8(scores)) return BEAR_ERR_INVALID_ARG;
+  if (n_t && (!rows || !letters || misaligned4(rows))) return BEAR_ERR_INVALID_ARG;
+  if (n_t && n_rows && (!train || misaligned4(train))) return BEAR_ERR_INVALID_ARG;
+  if (n_h > 0 && misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
+  const uint64_t M = (uint64_t)P.n_m;
+  if (n_seg > (~0ull) / M / sizeof(double) || n_t > (~0ull) / M / sizeof(double)) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dev_buf<double> terms, partials;       // one term per position and model; two partial rows per MRG_CHUNK positions of a long text
+  if (n_t) {
+    HIP_TRY(terms.alloc(n_t * M));
+    const dim3 grid(scr_grid(n_t, MRG_THREADS)), block(MRG_THREADS);
+    if (width == 5)
+      hipLaunchKernelGGL(marg_terms_kernel<5>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train, n_h > 0 ? prior : nullptr,
+                         n_rows, P, terms.get());
+    else
+      hipLaunchKernelGGL(marg_terms_kernel<21>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train, n_h > 0 ? prior : nullptr,
+                         n_rows, P, terms.get());
+    HIP_TRY(hipGetLastError());
+  }
+  if (n_t > MRG_CHUNK) {                 // only such a text can hold a long segment
+    const uint64_t n_blocks = (n_t + MRG_CHUNK - 1) / MRG_CHUNK;
+    HIP_TRY(partials.alloc(2 * n_blocks * M));
+    hipLaunchKernelGGL(marg_chunk_kernel, dim3(scr_grid(n_blocks, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms.get(), (uint32_t)M, seg,
+                       n_seg, n_t, n_blocks, partials.get());
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(marg_sum_kernel, dim3(scr_grid(n_seg, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms.get(), (uint32_t)M, seg, n_seg,
+                     n_t, partials.get(), scores);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;      // (terms and partials go with this frame: hipFree waits for the launches)
 }
 
 int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,

@@ -8,7 +8,8 @@ log-Gamma draws of ``log_gamma.log_gamma`` and their normalisation, or the MAP t
 (``get_marg``) is one launch of ``bear_eval_f64``.  The protein alphabet (rows of 21: 20 letters + stop) takes their
 width-taking twins, ``bear_logdir_sample_wide_f64`` and ``bear_eval_wide_f64``.  The k+1-mer bookkeeping stays on the host as in the
 reference (string windows, a lookup table indexed by k+1-mer) -- unless the counts come from a ``DeviceCounter``: then
-``get_bear_probs`` / ``get_bear_probs_seqs`` run on the device from the queries' symbols to the scores (``kernels_score.h``).
+``get_bear_probs`` / ``get_bear_probs_seqs`` run on the device from the queries' symbols to the scores (``kernels_score.h``; the
+exact marginal when ``marg_on_device=True`` asks for it, ``kernels_marg.h``).
 
 Differences a user can see: draws come from a counter-based stream (``seed`` argument; ``None`` takes a fresh
 seed from numpy's global generator) instead of numpy's Mersenne twister, and the KMC database look-up
@@ -247,7 +248,8 @@ class DeviceCounter:
     ``counter=`` anywhere.  Handed to ``get_bear_probs`` / ``get_bear_probs_seqs`` (without ``get_marg``) the whole call runs on the
     device: keys of the queries' transitions, their distinct k-mers, count rows by ``kernels.kmer_find``, the sampled or MAP table
     and the per-variant / per-sequence sums (``kernels.score_sum``); only the scores come back.  ``train_col`` of those calls is
-    not used then: the counter is one column.  Handed to ``assemble.assemble_no_ends`` the flanks grow on the device
+    not used then: the counter is one column.  ``get_marg=True`` runs on the device too when ``marg_on_device=True`` is passed
+    with it (``kernels.score_marg``); by default that one mode calls the counter per k-mer on the host.  Handed to ``assemble.assemble_no_ends`` the flanks grow on the device
     (``kernels.generate_steps`` over ``keys`` and ``counts_by_key``)."""
 
     def __init__(self, kmers, counts, alphabet_name, no_end=False):
@@ -428,6 +430,42 @@ def _score_segments(counter, segments, lag, alphabet_name, h, ar_func, mc_sample
         return kernels.score_sum(lp, rows, letters, seg)
 
 
+def _marg_segments(counter, segments, lag, alphabet_name, h, ar_func, vans):
+    """The device path of ``get_bear_probs_seqs(..., get_marg=True, marg_on_device=True)``: the exact Dirichlet-multinomial marginal
+    of string ``i`` under every model -> CUDA float64 [n_seg, num_models], BEAR models first.  ``_score_segments`` up to the
+    sampler -- the same refusals, keys, distinct k-mers, count rows and prior rows -- then ``kernels.score_marg`` instead of a table.
+
+    Per distinct k-mer the call holds a count row, a prior row and the rows' gather temporaries, per position one term per model:
+    if that would not fit the free device memory a ``MemoryError`` says so, as ``_score_segments`` does."""
+    if counter.lag != lag or counter.alphabet_name != alphabet_name:
+        raise ValueError(f"counter: a lag-{counter.lag} table of {counter.alphabet_name!r}, asked for lag {lag} of {alphabet_name!r}")
+    device, W = counter.device, counter.width
+    vans = np.atleast_1d(np.asarray(vans, dtype=np.float64)).reshape(-1)
+    hs = np.atleast_1d(np.asarray(h, dtype=np.float64)).reshape(-1) if ar_func is not None else np.zeros(0)
+    num_models = len(vans) + len(hs)
+    codes, seg, n_none = _segment_text(segments, lag, alphabet_name)
+    if codes.size == n_none:        # no transition anywhere
+        return torch.zeros((len(segments), num_models), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        seg = torch.from_numpy(seg).to(device)
+        keys, letters = kernels.score_transitions(torch.from_numpy(codes).to(device), seg, lag, counter.rank)
+        uniq, inverse = torch.unique(keys, return_inverse=True)     # ascending; -1 (no transition) in front where there is one
+        first = int(n_none > 0)
+        kmer_keys = uniq[first:].contiguous()
+        rows = (inverse - first).to(torch.int32)
+        K = kmer_keys.numel()
+        need = K * W * 3 * 8 + codes.size * (num_models * 8 + 3 * 8)
+        free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+        if need > free:
+            raise MemoryError(f"the rows of {K} k-mers x {W} letters and the terms of {codes.size} positions x {num_models} models take "
+                              f"{need} bytes, the device has {free} free: score fewer sequences per call")
+        prior = None
+        if ar_func is not None:
+            with torch.no_grad():
+                prior = ar_func(counter.codes_of_keys(kmer_keys)).to(torch.float64).expand(K, W).contiguous()
+        return kernels.score_marg(rows, letters, seg, counter.rows_of_keys(kmer_keys), prior, hs, vans)
+
+
 # ------------------------------------------------------------------------------------------- variants
 def _add_kmer_probs_vars(vars_, scores, wt_seq, pdf, lag, seen_kmers):
     """get_var_probs.py:294-306."""
@@ -571,9 +609,18 @@ def _get_all_kmers_seqs(seqs, lag):
 
 def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1, 10], get_map=False, get_marg=False,
                         lag=None, alphabet_name=None, h=None, data=None, kmc_path=None, kmc_reverse=False,
-                        no_ends=False, seed=None, counter=None):
+                        no_ends=False, seed=None, counter=None, marg_on_device=False):
     """get_var_probs.get_bear_probs_seqs (get_var_probs.py:511-631): log-probabilities of whole sequences ->
-    [num sequences, num models, mc_samples] (last axis dropped with ``get_map`` / ``get_marg``)."""
+    [num sequences, num models, mc_samples] (last axis dropped with ``get_map`` / ``get_marg``).
+
+    ``marg_on_device=True`` (with ``get_marg=True`` and a ``DeviceCounter``; anything else is a ``ValueError``, raised before a
+    device is touched): the exact marginals are formed on the device from the sequences' symbols to the scores
+    (``_marg_segments``, ``kernels.score_marg``) -> [num sequences, num models].  The default stays ``False``, the host loop with
+    the counter called per k-mer: the device sums a sequence's terms in another order, so its scores agree with the host loop's
+    to rounding (1e-11 of the terms' L1 mass is what the tests hold it to), not to the bit, and the bits of the default are
+    pinned.  Making the device path the default is a later decision."""
+    if marg_on_device and not (get_marg and isinstance(counter, DeviceCounter)):
+        raise ValueError("marg_on_device=True is the device path of get_marg=True with a DeviceCounter as counter=")
     lag, alphabet_name, h, ar_func, data, len_h = _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter)
     alphabet = core.alphabets_en[alphabet_name]
     alphabet_size = len(alphabet) - 1
@@ -584,6 +631,12 @@ def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1,
     num_models = (ar_func is not None) * (len_h + get_map) + len(vans)
     scores = np.zeros([len(seqs), num_models, mc_samples])
     seed = _next_seed() if seed is None else seed
+    if marg_on_device:                                          # the exact marginal on the device: a sequence is a segment
+        for seq in seqs:
+            assert len(seq.replace("[", "").replace("]", "")) >= lag
+        if len(seqs):
+            return _marg_segments(counter, seqs, lag, alphabet_name, h, ar_func, vans).cpu().numpy()
+        return scores[..., 0]
     if isinstance(counter, DeviceCounter) and not get_marg:     # the whole call on the device: a sequence is a segment
         for seq in seqs:
             assert len(seq.replace("[", "").replace("]", "")) >= lag

@@ -760,6 +760,51 @@ def score_sum(lp, rows, letters, seg):
     return scores
 
 
+MARG_CHUNK = 2048                    # BEAR_MARG_CHUNK: positions of a long segment that one wave sums
+MARG_MAX_MODELS = 16                 # BEAR_MARG_MAX_MODELS: BEAR and vanilla models of one call
+
+
+def score_marg(rows, letters, seg, train, prior, h, vans):
+    """``bear_score_marg_f64``: the exact Dirichlet-multinomial marginal of every segment -> CUDA float64 [n_seg, H + V], the H BEAR
+    models (``prior / h + train``) first, then the V vanilla ones (``van + train``).  ``rows`` int32 [n_t] and ``letters`` uint8 [n_t]
+    per position of the text, in TEXT order (``SCORE_SKIP``, a negative row: no transition there); ``seg`` int64 [n_seg + 1]
+    ascending from 0 to n_t; ``train`` int32 [K, W] (uint32 in int32 storage) and ``prior`` float64 [K, W] or None: the rows of
+    the k-mers the text's rows number; ``h``, ``vans``: host values, each > 0.
+
+    The kernel wants every segment's positions sorted by (row, letter): one ``torch.sort`` of the int64 composite
+    ``(segment * (K + 1) + row + 1) * 256 + letter`` (0 and ``SCORE_SKIP`` where there is no transition) does that here, and rows
+    and letters are read back out of the sorted values.  ``ValueError`` if the composite would not fit 63 bits."""
+    train = _check_rows(train, torch.int32, "train", None)
+    K, W = train.shape
+    device = train.device
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", W, n=K)
+    _check_vec(rows, torch.int32, "rows", device=device)
+    _check_vec(letters, torch.uint8, "letters", rows.numel(), device=device)
+    n_seg = _check_seg(seg, device)
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
+    if hs.size and prior is None:
+        raise ValueError("the BEAR models (h) need prior rows")
+    if not 1 <= hs.size + vs.size <= MARG_MAX_MODELS:
+        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{MARG_MAX_MODELS}")
+    if not (np.all(hs > 0) and np.all(vs > 0)):
+        raise ValueError("every h and every vanilla pseudo-count must be > 0")
+    if max(n_seg, 1) * (K + 1) * 256 >= 2 ** 63:
+        raise ValueError(f"{n_seg} segments x {K} k-mers: the sort key (segment, row, letter) does not fit 63 bits")
+    n_t = rows.numel()
+    with torch.cuda.device(device):
+        live = (rows >= 0) & (rows < K) & (letters < W)
+        segment = torch.searchsorted(seg[1:], torch.arange(n_t, dtype=torch.int64, device=device), right=True).clamp_(max=max(n_seg - 1, 0))
+        key = (segment * (K + 1) + torch.where(live, rows.to(torch.int64) + 1, 0)) * 256 + torch.where(live, letters.to(torch.int64), SCORE_SKIP)
+        key = torch.sort(key).values
+        letters = (key & 0xFF).to(torch.uint8)
+        rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+    scores = torch.empty((n_seg, hs.size + vs.size), dtype=torch.float64, device=device)
+    _launch(device, "bear_score_marg_f64", _ptr(rows), _ptr(letters), n_t, _ptr(seg), n_seg, W, _ptr(train), _ptr(prior), K,
+            hp, hs.size, vp, vs.size, _ptr(scores))
+    return scores
+
+
 # ---- sequence generation over a key table (include/bear_hip.h, "Sequence generation"; kernels_generate.h) ----------------------
 GEN_BMM, GEN_BEAR, GEN_AR = 0, 1, 2  # BEAR_GEN_*: where a letter's concentration comes from
 GEN_ID_GUMBEL = 3000                 # the model id that keys the Gumbel draws (the table values are model 0)

@@ -908,7 +908,8 @@ int bear_kmer_sort_create_range(const uint8_t *text, const uint8_t *group, uint6
 
 /*
  * Variant and sequence scoring on the device (get_var_probs.get_bear_probs / get_bear_probs_seqs with a DeviceCounter): what
- * stands between a count table in device memory and the samplers' tables above.  All three are asynchronous on `stream`.
+ * stands between a count table in device memory and the samplers' tables above, and the exact marginal of whole segments, which
+ * needs no table.  All four are asynchronous on `stream`.
  *
  * The symbol text: uint8 codes as in the counting text -- letters 0 .. width - 2, the stop ']' = width - 1, the start '[' = width
  * -- with every start and stop written out (nothing is padded implicitly), cut into n_seg segments by
@@ -943,6 +944,39 @@ int bear_kmer_find_u64(const uint64_t *table, uint64_t n_table, const uint64_t *
                        void *stream);
 int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_values, const uint32_t *rows, const uint8_t *letters,
                        uint64_t n_t, const uint64_t *seg, uint64_t n_seg, double *scores, void *stream);
+
+/*
+ * bear_score_marg_f64: the exact Dirichlet-multinomial marginal of every segment under n_h BEAR and n_van vanilla models
+ * (get_bear_probs_seqs(..., get_marg=True)): scores[s, m] = sum over the distinct k-mers r of segment s of
+ *     lgamma(A) - lgamma(A + n) + sum over the letters j with q_j > 0 of [lgamma(a_j + q_j) - lgamma(a_j)]
+ * with q[] the letter counts of r's transitions inside s, n their sum, c[] = train[r, :],
+ *     a_j = fma(prior[r, j], 1 / h_m, c_j) for the BEAR model m < n_h,   a_j = van_(m - n_h) + c_j for a vanilla model,
+ * and A the sum of a_0 .. a_(width - 1) in that order.  Both brackets are log rising factorials over an exact integer (the item
+ * routine of the training kernels); there is no multinomial coefficient.
+ *   rows [dev] int32 [n_t], letters [dev] uint8 [n_t]: per position of the text the k-mer's row in `train` and the letter, SORTED
+ *        inside every segment by (row, letter), so that seg stays valid; a position without a transition has a negative row and
+ *        the letter 0xFF and sorts in front (a row >= n_rows or a letter >= width is such a position too).  A run -- a maximal
+ *        stretch of equal (row, letter) inside a segment -- is one q_j, the stretch of equal row is the k-mer's n.  Unsorted input
+ *        gives another sum (every run is then a k-mer's letter of its own); nothing is read outside the arrays whatever they hold.
+ *   seg  [dev] uint64 [n_seg + 1] as above with seg[n_seg] = n_t;  width 5 or 21
+ *   train [dev] uint32 [n_rows, width] (n_rows < 2^32 - 1);  prior [dev, nullable] double [n_rows, width], needed when n_h > 0
+ *   h [host] double [n_h], van [host] double [n_van], every value > 0;  1 <= n_h + n_van <= BEAR_MARG_MAX_MODELS
+ *   scores [dev] double [n_seg, n_h + n_van]: BEAR models first, then the vanilla ones; a segment without transitions scores 0.
+ * Every position's term is formed once (one thread per position; the head of a run finds its end by binary search), then summed
+ * per segment in chunks of BEAR_MARG_CHUNK positions cut from the segment's own start: inside a chunk position p goes to lane
+ * (p - chunk start) mod 64, a lane adds its positions front to back, the 64 lanes are added in a fixed tree, and the chunks'
+ * sums are added in chunk order.  No atomics: a segment's bits depend on its own content only -- not on where it stands in the
+ * text, on the other segments, on the grid or on the library.  Holds n_t * (n_h + n_van) terms and, for a text beyond
+ * BEAR_MARG_CHUNK positions, two partial rows per BEAR_MARG_CHUNK positions, and frees them before it returns.
+ * Refused with BEAR_ERR_INVALID_ARG before any device call: a width other than 5 / 21, n_h > 0 without a prior, an h or van that
+ * is not > 0, n_h + n_van of 0 or beyond BEAR_MARG_MAX_MODELS, n_rows >= 2^32 - 1, a missing or misaligned pointer.  n_seg = 0 is
+ * valid and launches nothing.
+ */
+#define BEAR_MARG_CHUNK 2048
+#define BEAR_MARG_MAX_MODELS 16
+int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
+                        const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van,
+                        int n_van, double *scores, void *stream);
 
 /*
  * Sequence generation on the device (assemble.assemble_no_ends with a DeviceCounter): every sequence grows from its end k-mer, one
