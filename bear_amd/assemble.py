@@ -17,6 +17,9 @@ kernels_generate.h): look-up, table values and Gumbel-max draws of every letter 
 launch per step behind the AR function for a trained model.  A table value is keyed by (seed, sequence, k-mer, letter), so the
 sample a sequence sees is the same whenever it meets a k-mer again and ``batch_size`` has no effect; ``device_path=False``
 keeps the host loop for such a counter.
+
+``generate_sequences`` (no counterpart in the reference) samples WHOLE sequences from such a counter: from the start context or a
+prompt, letter by letter until the stop symbol is drawn or ``max_len`` letters are written (``kernels.generate_whole``).
 """
 import os
 
@@ -199,3 +202,95 @@ def assemble_no_ends(seqs_fa_file, lengths_to_gen, num_to_gen, bear_path, kmc_pa
         except Exception:
             pass
     return gen_seqs, sw_ent
+
+
+def _any_left(left):
+    """Whether any sequence still has steps to take: the one synchronising look of the per-step path."""
+    return bool(left.any().item())
+
+
+def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=None, h=None, van=None, get_map=False, prompts=None,
+                       seed=None, save_folder=None, stepwise=False):
+    """Whole sequences from the model over ``counter`` (a ``get_var_probs.DeviceCounter`` counted WITH ends; its lag and alphabet
+    are the model's) -> ``(seqs, stopped)``, both ``[len(prompts), num_to_gen]``: every prompt (strings over the alphabet, shorter
+    than the lag or empty if need be; default one empty prompt, the start of a sequence) continued ``num_to_gen`` times, the
+    prompt included, and whether the stop symbol was drawn -- False: cut at ``max_len`` generated letters.  The model is ``van`` (a
+    BMM), ``bear_path`` (``load_bear``) or ``ar_func`` with ``h``; with ``get_map`` a BMM / BEAR table is taken at its MAP value and a
+    trained model generates at its AR function's.  The start key is the last ``lag`` symbols of ``'[' * lag + prompt``; the sample
+    index of a sequence is ``prompt index * num_to_gen + replicate`` and steps count generated letters from 0, so equal seeds give
+    equal strings.
+
+    The device is the only path (``kernels.generate_whole``, kernels_generate.h).  A BMM takes one launch; a trained model one AR
+    call and one launch per step, looking every 16 steps whether any sequence is still growing; the linear AR function of the
+    protein alphabet (``make_ar_func_linear(lag, 20)``: ``linear_mat``, ``fused``) runs inside the kernel instead, one launch for
+    everything, unless ``stepwise``.  ``ValueError`` before any launch: a ``no_end`` counter (its stop column is zeroed), a prompt
+    character outside the alphabet, ``max_len < 0``, no model or more than one.  ``save_folder`` receives ``seqs.fa``."""
+    import torch
+    from . import kernels
+    from .log_gamma import _next_seed
+    if not isinstance(counter, get_var_probs.DeviceCounter):
+        raise TypeError("generate_sequences runs on the device only: counter must be a get_var_probs.DeviceCounter")
+    if counter.no_end:
+        raise ValueError("a no_end counter has its stop column zeroed: no sequence would ever end")
+    if (van is not None) + (bear_path is not None) + (ar_func is not None) != 1:
+        raise ValueError("exactly one model: van=... (a BMM), bear_path=... or ar_func=... with h=...")
+    if ar_func is not None and h is None and not get_map:
+        raise ValueError("ar_func needs h (the AR model alone is a table only at its MAP value: get_map=True)")
+    num_to_gen, max_len = int(num_to_gen), int(max_len)
+    if max_len < 0 or num_to_gen < 0:
+        raise ValueError("max_len and num_to_gen count letters and sequences: not negative")
+    lag, W, device, name = counter.lag, counter.width, counter.device, counter.alphabet_name
+    letters_en = "".join(str(ch) for ch in core.alphabets_en[name][:-1])
+    prompts = [""] if prompts is None else [str(p) for p in prompts]
+    for p in prompts:
+        for ch in set(p):
+            if ch not in letters_en:
+                raise ValueError(f"character {ch!r} of prompt {p!r} is not a letter of the alphabet {name!r}")
+    if bear_path is not None:
+        lag_b, name_b, h_b, ar_func, _ = get_var_probs.load_bear(bear_path)
+        if (lag_b, name_b) != (lag, name):
+            raise ValueError(f"counter: a lag-{lag} table of {name!r}, the model at {bear_path!r} has lag {lag_b} of {name_b!r}")
+        h = h_b if h is None else h
+    n_total = len(prompts) * num_to_gen
+    seed = _next_seed() if seed is None else seed
+    starts = np.frombuffer("".join(("[" * lag + p)[-lag:] for p in prompts).encode("ascii"), dtype=np.uint8)
+    with torch.cuda.device(device):
+        keys = counter._keys_of_codes(torch.from_numpy(counter._lut[starts].reshape(len(prompts), lag)).to(device))
+        keys = keys.repeat_interleave(num_to_gen).contiguous()
+        sample = torch.arange(n_total, dtype=torch.int64, device=device)
+        left = torch.full((n_total,), max_len, dtype=torch.int32, device=device)
+        length = torch.zeros(n_total, dtype=torch.int32, device=device)
+        stopped = torch.zeros(n_total, dtype=torch.uint8, device=device)
+        letters = torch.full((n_total, max_len), 0xFF, dtype=torch.uint8, device=device)
+        state = (counter.keys, counter.counts_by_key, counter.rank, lag, keys, sample, left, length, stopped, letters)
+        mat = getattr(ar_func, "linear_mat", None)
+        if n_total == 0:
+            pass
+        elif ar_func is None:
+            kernels.generate_whole(*state, 0, max_len, seed, van=float(van), get_map=get_map)
+        elif not stepwise and mat is not None and getattr(ar_func, "fused", False) and W == kernels.LINEAR_WIDE_WIDTH and mat.device == device:
+            # (a protein key holds at most 12 letters, SCORE_MAX_LAG: every lag of such a counter fits the kernel's LDS image of mat)
+            kernels.generate_whole(*state, 0, max_len, seed, mat=mat.detach().contiguous(), h=None if get_map else float(h),
+                                   get_map=get_map)
+        else:
+            kmer_codes = counter.codes_of_keys(keys)
+            for t in range(max_len):
+                with torch.no_grad():
+                    prior = ar_func(kmer_codes).to(torch.float64).expand(n_total, W).contiguous()
+                kernels.generate_whole(*state, t, 1, seed, prior=prior, h=None if get_map else float(h), get_map=get_map,
+                                       codes=kmer_codes)
+                if (t + 1) % 16 == 0 and t + 1 < max_len and not _any_left(left):
+                    break
+        # the one copy back: letters | length as four bytes | stopped, a row per sequence
+        back = torch.cat([letters, length.view(torch.uint8).reshape(n_total, 4), stopped[:, None]], 1).cpu().numpy()
+    chars = np.frombuffer(letters_en.encode("ascii"), dtype=np.uint8)[np.minimum(back[:, :max_len], W - 2)]
+    lens = np.ascontiguousarray(back[:, max_len:max_len + 4]).view(np.int32).reshape(-1)
+    seqs = [prompts[i // num_to_gen] + chars[i, :int(l)].tobytes().decode("ascii") for i, l in enumerate(lens)]
+    seqs = np.array(seqs, dtype=str).reshape(len(prompts), num_to_gen)
+    if save_folder is not None:
+        os.makedirs(save_folder, exist_ok=True)
+        with open(os.path.join(save_folder, "seqs.fa"), "w") as f:
+            for i, row in enumerate(seqs):
+                for j, seq in enumerate(row):
+                    f.write(">seq{}_rep{}\n{}\n".format(i, j, seq))
+    return seqs, back[:, max_len + 4].astype(bool).reshape(len(prompts), num_to_gen)

@@ -1,7 +1,8 @@
 // bear_score.hip -- scoring on the device: the entries between the device count tables and the samplers' tables
 // (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
 // of a sampled table's rows over the transitions of every segment; the exact marginal of every segment, which needs no table -- and
-// sequence generation over the same key tables ("Sequence generation").  The only unit that includes -- and so emits --
+// sequence generation over the same key tables ("Sequence generation": flanks of given lengths, and whole sequences from start to
+// stop).  The only unit that includes -- and so emits --
 // kernels_score.h, kernels_marg.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,6 +22,49 @@ bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) !
 unsigned scr_grid(uint64_t work, uint64_t per_block) {
   const uint64_t g = (work + per_block - 1) / per_block;
   return (unsigned)(g < 1 ? 1 : (g > (1u << 20) ? (1u << 20) : g));
+}
+
+// What the two generation entries check before any device call, and their argument block.  has_f: rows of the AR function are at
+// hand (prior rows, or mat for the kernel to form them); per_step: they are prior rows, those of the CURRENT end k-mers.
+bool gen_prepare(int lag, int width, const uint8_t *rank, int mode, int map, double h, double van, bool has_f, bool per_step,
+                 uint64_t n_table, uint64_t seed, uint64_t step0, uint64_t n_steps, uint64_t letters_stride, gen_args &A) {
+  if (width != 5 && width != 21) return false;
+  if (lag < 1 || lag > (width == 5 ? 21 : 12) || !rank) return false;
+  if (mode != BEAR_GEN_BMM && mode != BEAR_GEN_BEAR && mode != BEAR_GEN_AR) return false;
+  if (mode != BEAR_GEN_BMM && !has_f) return false;
+  if (mode == BEAR_GEN_AR && !map) return false;                         // the AR model is a table only at its MAP value
+  if (per_step && n_steps > 1) return false;
+  if (mode == BEAR_GEN_BEAR && !(h > 0.0)) return false;
+  if (mode == BEAR_GEN_BMM && !(van > 0.0)) return false;
+  if (n_table >= SCR_ABSENT || n_steps > 0xFFFFFFFFull || step0 > (~0ull) - n_steps || letters_stride < step0 + n_steps) return false;
+  const int bits = width == 5 ? 3 : 5;
+  memset(&A, 0, sizeof(A));
+  for (int c = 0; c <= width; ++c) {
+    if (c == width - 1) continue;                                        // the stop: no letter of a context
+    if (rank[c] >= (1u << bits)) return false;
+    if (c < width - 1) A.rank[c >> 3] |= (uint64_t)rank[c] << ((c & 7) * 8);
+    A.code[rank[c] >> 3] |= (uint64_t)(c < width - 1 ? c : width - 1) << ((rank[c] & 7) * 8);      // core.encode_kmers: '[' = A
+  }
+  A.lag = lag;
+  A.mode = mode;
+  A.map = map != 0;
+  A.inv_h = mode == BEAR_GEN_BEAR ? 1.0 / h : 0.0;
+  A.van = mode == BEAR_GEN_BMM ? van : 0.0;
+  A.seed = seed;
+  A.step0 = step0;
+  A.n_steps = n_steps;
+  A.stride = letters_stride;
+  return true;
+}
+
+// ... and of their pointers, once there are sequences
+bool gen_pointers_ok(const uint64_t *table, const uint32_t *counts, uint64_t n_table, const double *prior, const uint64_t *keys,
+                     const uint64_t *sample, const uint32_t *left, uint64_t n_seq, uint64_t n_steps, const uint8_t *letters,
+                     uint64_t letters_stride) {
+  if (!keys || !sample || !left || (n_steps && !letters) || misaligned8(keys) || misaligned8(sample) || misaligned4(left) ||
+      (prior && misaligned8(prior)) || (n_table && (!table || !counts || misaligned8(table) || misaligned4(counts))))
+    return false;
+  return !(letters_stride && n_seq > (~0ull) / letters_stride);
 }
 }  // namespace
 
@@ -145,39 +189,12 @@ int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint6
                             int mode, int map, double h, double van, const double *prior, uint64_t seed, uint64_t *keys,
                             const uint64_t *sample, uint32_t *left, uint64_t n_seq, uint64_t step0, uint64_t n_steps,
                             uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream) {
-  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
-  if (lag < 1 || lag > (width == 5 ? 21 : 12) || !rank) return BEAR_ERR_INVALID_ARG;
-  if (mode != BEAR_GEN_BMM && mode != BEAR_GEN_BEAR && mode != BEAR_GEN_AR) return BEAR_ERR_INVALID_ARG;
-  if (mode != BEAR_GEN_BMM && !prior) return BEAR_ERR_INVALID_ARG;
-  if (mode == BEAR_GEN_AR && !map) return BEAR_ERR_INVALID_ARG;          // the AR model is a table only at its MAP value
-  if (prior && n_steps > 1) return BEAR_ERR_INVALID_ARG;                 // the rows are those of the current end k-mers
-  if (mode == BEAR_GEN_BEAR && !(h > 0.0)) return BEAR_ERR_INVALID_ARG;
-  if (mode == BEAR_GEN_BMM && !(van > 0.0)) return BEAR_ERR_INVALID_ARG;
-  if (n_table >= SCR_ABSENT || n_steps > 0xFFFFFFFFull || step0 > (~0ull) - n_steps || letters_stride < step0 + n_steps)
-    return BEAR_ERR_INVALID_ARG;
-  const int bits = width == 5 ? 3 : 5;
   gen_args A;
-  memset(&A, 0, sizeof(A));
-  for (int c = 0; c <= width; ++c) {
-    if (c == width - 1) continue;                                        // the stop: no letter of a context, never drawn
-    if (rank[c] >= (1u << bits)) return BEAR_ERR_INVALID_ARG;
-    if (c < width - 1) A.rank[c >> 3] |= (uint64_t)rank[c] << ((c & 7) * 8);
-    A.code[rank[c] >> 3] |= (uint64_t)(c < width - 1 ? c : width - 1) << ((rank[c] & 7) * 8);      // core.encode_kmers: '[' = A
-  }
-  if (n_seq == 0) return BEAR_OK;
-  if (!keys || !sample || !left || (n_steps && !letters) || misaligned8(keys) || misaligned8(sample) || misaligned4(left) ||
-      (prior && misaligned8(prior)) || (n_table && (!table || !counts || misaligned8(table) || misaligned4(counts))))
+  if (!gen_prepare(lag, width, rank, mode, map, h, van, prior != nullptr, prior != nullptr, n_table, seed, step0, n_steps, letters_stride, A))
     return BEAR_ERR_INVALID_ARG;
-  if (letters_stride && n_seq > (~0ull) / letters_stride) return BEAR_ERR_INVALID_ARG;
-  A.lag = lag;
-  A.mode = mode;
-  A.map = map != 0;
-  A.inv_h = mode == BEAR_GEN_BEAR ? 1.0 / h : 0.0;
-  A.van = mode == BEAR_GEN_BMM ? van : 0.0;
-  A.seed = seed;
-  A.step0 = step0;
-  A.n_steps = n_steps;
-  A.stride = letters_stride;
+  if (n_seq == 0) return BEAR_OK;
+  if (!gen_pointers_ok(table, counts, n_table, prior, keys, sample, left, n_seq, n_steps, letters, letters_stride))
+    return BEAR_ERR_INVALID_ARG;
   if (n_steps == 0 && !codes) return BEAR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 block(GEN_THREADS);
@@ -187,6 +204,34 @@ int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint6
   else
     hipLaunchKernelGGL((generate_steps_kernel<5, 21>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_GROUP(21))), block, 0, s, table, counts,
                        n_table, prior, keys, sample, left, n_seq, A, letters, codes);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_generate_whole_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
+                            int mode, int map, double h, double van, const double *prior, const double *mat, uint64_t seed,
+                            uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
+                            uint64_t step0, uint64_t n_steps, uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream) {
+  if ((prior && mat) || (mat && width != 21)) return BEAR_ERR_INVALID_ARG;      // one source of rows; the function in the kernel: width 21
+  gen_args A;
+  if (!gen_prepare(lag, width, rank, mode, map, h, van, prior || mat, prior != nullptr, n_table, seed, step0, n_steps, letters_stride, A))
+    return BEAR_ERR_INVALID_ARG;
+  if (n_seq == 0) return BEAR_OK;
+  if (!gen_pointers_ok(table, counts, n_table, prior, keys, sample, left, n_seq, n_steps, letters, letters_stride) || !length ||
+      !stopped || misaligned4(length) || (mat && misaligned8(mat)))
+    return BEAR_ERR_INVALID_ARG;
+  if (n_steps == 0 && !codes) return BEAR_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 block(GEN_THREADS);
+  if (width == 5) {
+    hipLaunchKernelGGL((generate_whole_kernel<3, 5>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_WHOLE_GROUP(5))), block, 0, s, table,
+                       counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
+  } else {
+    unsigned grid = scr_grid(n_seq, GEN_THREADS / GEN_WHOLE_GROUP(21));
+    if (mat && grid > GEN_WHOLE_MAT_BLOCKS) grid = GEN_WHOLE_MAT_BLOCKS;        // every block stages mat: few blocks, a stride
+    hipLaunchKernelGGL((generate_whole_kernel<5, 21>), dim3(grid), block, mat ? GEN_WHOLE_MAT_LDS(lag) : 0, s, table, counts, n_table,
+                       prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
+  }
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }

@@ -22,14 +22,13 @@
 //             give the same bits, in both builds of the library (no deterministic twin).
 //             Grid: min(tiles of 128 contexts, 2 x CUs) blocks (bear_linear.hip, linwide_bwd_grid) -- part of the result.
 //             A tile whose g is zero everywhere (contexts without counts) is skipped.
-// The row steps (lnw_forward_row, lnw_softmax_back_row) and the product (lnw_own_rows, lnw_onehot_product, lnw_store_acc) are routines:
+// The row steps (lnw_forward_row of rows_wide_common.h, lnw_softmax_back_row) and the product (lnw_own_rows, lnw_onehot_product, lnw_store_acc) are routines:
 // the fused step (kernels_linear_wide.h) runs the same ones on the same block and tile geometry (LNW_BWD_*).
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"
-#include "rows_wide_common.h"   // LNW_W, wide_store_tile, wide_stage_codes, lnw_sum_rows / lnw_sum_partials
+#include "rows_wide_common.h"   // LNW_W, LNW_MAT, lnw_forward_row, wide_store_tile, wide_stage_codes, lnw_sum_rows / lnw_sum_partials
 
-#define LNW_MAT (LNW_W * LNW_W)                        // doubles of mat per position
 #define LNW_MAX_GRAD (LINEAR_WIDE_MAX_LAG * LNW_MAT)
 
 // the block of the backward kernel and of the fused step: four waves, tiles of 128 contexts, the (l, a) rows of d mat in tiles of 16
@@ -41,33 +40,6 @@
 #define LNW_RT_PER_WAVE ((LNW_MAX_RT + LNW_BWD_WAVES - 1) / LNW_BWD_WAVES)
 
 // ------------------------------------------------------------------ the steps of one context
-// f = softmax_b(sum_l M[l, cd[l], b]): the logits from the LDS image M of mat, the max-shifted softmax on the exp table
-__device__ __forceinline__ void lnw_forward_row(const int8_t *cd, int lag, const double *M, const double *exptab, double *f) {
-  double z[LNW_W];
-#pragma unroll
-  for (int b = 0; b < LNW_W; ++b) z[b] = 0.0;
-  for (int l = 0; l < lag; ++l) {
-    const uint32_t a = (uint32_t)(int)cd[l];
-    if (a < (uint32_t)LNW_W) {                           // anything else: an all-zero one-hot row
-      const double *m = M + (l * LNW_W + (int)a) * LNW_W;
-#pragma unroll
-      for (int b = 0; b < LNW_W; ++b) z[b] += m[b];
-    }
-  }
-  double zmax = z[0];
-#pragma unroll
-  for (int b = 1; b < LNW_W; ++b) zmax = __builtin_fmax(zmax, z[b]);
-  double s = 0.0;
-#pragma unroll
-  for (int b = 0; b < LNW_W; ++b) {
-    z[b] = bear_exp_tab(z[b] - zmax, exptab);
-    s += z[b];
-  }
-  const double inv = 1.0 / s;                            // s >= 1: the largest logit contributes exp(0)
-#pragma unroll
-  for (int b = 0; b < LNW_W; ++b) f[b] = z[b] * inv;
-}
-
 // softmax backward in place over the row q = d L / d f:  g = f (q - <f, q>) = d L / d logit; true if any entry is not zero
 __device__ __forceinline__ bool lnw_softmax_back_row(const double *f, double *g) {
   double s = 0.0;

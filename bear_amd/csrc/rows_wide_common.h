@@ -1,14 +1,16 @@
 // rows_wide_common.h -- device routines the kernels of the protein alphabet's width share (kernels_wide.h, kernels_refmix_wide.h,
 // kernels_linrows_wide.h, kernels_linear_wide.h, kernels_cnn_wide.h), each step written once: the DM step of one staged context (the
 // sparse item walk, wide_dm_row), a tile of fp64 rows out of LDS (wide_store_tile), a tile's int8 code bytes into LDS
-// (wide_stage_codes), the rows of a partials buffer (WIDE_PARTIAL_ROWS) and the fixed-order sum over them (lnw_sum_partials).  The
-// steps of the linear function, which need its MFMA geometry (lnw_forward_row, lnw_softmax_back_row, lnw_own_rows, lnw_onehot_product,
-// lnw_store_acc), sit at the top of kernels_linrows_wide.h.  No kernels here.
+// (wide_stage_codes), the rows of a partials buffer (WIDE_PARTIAL_ROWS), the fixed-order sum over them (lnw_sum_partials) and the
+// forward row of the linear function (lnw_forward_row: kernels_linrows_wide.h, kernels_linear_wide.h and, in the unit
+// bear_score.hip, kernels_generate.h).  The steps of the linear function that need its MFMA geometry (lnw_softmax_back_row,
+// lnw_own_rows, lnw_onehot_product, lnw_store_acc) sit at the top of kernels_linrows_wide.h.  No kernels here.
 #pragma once
 #include "bear_common.h"
 #include "kernels_rows.h"   // dm_row_item
 
 #define LNW_W 21
+#define LNW_MAT (LNW_W * LNW_W)                        // doubles of mat per position
 
 typedef double lnw_d4 __attribute__((ext_vector_type(4)));
 typedef uint32_t lnw_v4u __attribute__((ext_vector_type(4)));
@@ -80,6 +82,34 @@ __device__ __forceinline__ void wide_dm_row(const uint32_t *c, const double *f, 
     acc[0] += ll;
     acc[1] -= dh * prm.inv_h;  // d alpha_b / d h_signed = -f_b / h
   }
+}
+
+// ------------------------------------------------------------------ the forward row of the linear function at width 21
+// f = softmax_b(sum_l M[l, cd[l], b]): the logits from the LDS image M of mat, the max-shifted softmax on the exp table
+__device__ __forceinline__ void lnw_forward_row(const int8_t *cd, int lag, const double *M, const double *exptab, double *f) {
+  double z[LNW_W];
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) z[b] = 0.0;
+  for (int l = 0; l < lag; ++l) {
+    const uint32_t a = (uint32_t)(int)cd[l];
+    if (a < (uint32_t)LNW_W) {                           // anything else: an all-zero one-hot row
+      const double *m = M + (l * LNW_W + (int)a) * LNW_W;
+#pragma unroll
+      for (int b = 0; b < LNW_W; ++b) z[b] += m[b];
+    }
+  }
+  double zmax = z[0];
+#pragma unroll
+  for (int b = 1; b < LNW_W; ++b) zmax = __builtin_fmax(zmax, z[b]);
+  double s = 0.0;
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) {
+    z[b] = bear_exp_tab(z[b] - zmax, exptab);
+    s += z[b];
+  }
+  const double inv = 1.0 / s;                            // s >= 1: the largest logit contributes exp(0)
+#pragma unroll
+  for (int b = 0; b < LNW_W; ++b) f[b] = z[b] * inv;
 }
 
 // rows [0, rows) of an LDS tile of W-wide fp64 rows to dst (16-byte aligned) as 16-byte stores; nontemporal: not read again here

@@ -250,7 +250,8 @@ class DeviceCounter:
     and the per-variant / per-sequence sums (``kernels.score_sum``); only the scores come back.  ``train_col`` of those calls is
     not used then: the counter is one column.  ``get_marg=True`` runs on the device too when ``marg_on_device=True`` is passed
     with it (``kernels.score_marg``); by default that one mode calls the counter per k-mer on the host.  Handed to ``assemble.assemble_no_ends`` the flanks grow on the device
-    (``kernels.generate_steps`` over ``keys`` and ``counts_by_key``)."""
+    (``kernels.generate_steps`` over ``keys`` and ``counts_by_key``); handed to ``assemble.generate_sequences`` (counted with ends:
+    ``no_end=False``) whole sequences are sampled from the start context to the stop (``kernels.generate_whole``)."""
 
     def __init__(self, kmers, counts, alphabet_name, no_end=False):
         if not (isinstance(kmers, torch.Tensor) and kmers.is_cuda and kmers.dtype == torch.uint8 and kmers.dim() == 2):

@@ -810,15 +810,8 @@ GEN_BMM, GEN_BEAR, GEN_AR = 0, 1, 2  # BEAR_GEN_*: where a letter's concentratio
 GEN_ID_GUMBEL = 3000                 # the model id that keys the Gumbel draws (the table values are model 0)
 
 
-def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van=None, prior=None, h=None,
-                   get_map=False, codes=None):
-    """One launch of ``bear_generate_steps_f64``: steps ``step0 .. step0 + n_steps - 1`` of every sequence that has letters left.
-    ``table``: CUDA int64 [N] ascending distinct keys, ``counts`` int32 [N, W] their count rows in that order (None with an empty
-    table); ``rank``: ``score_ranks`` of the alphabet.  Per sequence, all on the table's device and updated in place: ``keys``
-    int64 [n] the end key, ``left`` int32 [n] the letters still to write; ``sample`` int64 [n] the sample index; ``letters`` uint8
-    [n, L >= step0 + n_steps] receives the letter codes at columns ``step0 ..``.  The model: ``van`` (a BMM: any ``n_steps``, a whole
-    flank in one launch), or ``prior`` float64 [n, W] rows of the current end k-mers (``n_steps`` 1) with ``h`` (BEAR) or without
-    (the AR model, ``get_map`` only).  ``codes`` int8 [n, lag], if given, receives the new end k-mers as ``core.encode_kmers`` codes."""
+def _generate_checks(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, van, prior, mat, h, get_map, codes):
+    """What ``generate_steps`` and ``generate_whole`` check alike -> ``(device, rank, W, counts, n, step0, n_steps, prior, mode)``."""
     _check_vec(table, torch.int64, "table")
     device = table.device
     rank = np.ascontiguousarray(rank, dtype=np.uint8)
@@ -849,11 +842,12 @@ def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0,
             raise ValueError(f"prior must be on {device}")
         if n_steps > 1:
             raise ValueError("prior rows belong to the current end k-mers: one step per launch")
+    if prior is not None or mat is not None:
         if h is None and not get_map:
-            raise ValueError("the AR model (prior without h) is a table only at its MAP value: get_map=True")
+            raise ValueError("the AR model (rows without h) is a table only at its MAP value: get_map=True")
         mode = GEN_AR if h is None else GEN_BEAR
     elif van is None:
-        raise ValueError("a BMM (van=...) or prior rows")
+        raise ValueError("a BMM (van=...) or rows of an AR function")
     else:
         mode = GEN_BMM
     if mode == GEN_BEAR and not float(h) > 0 or mode == GEN_BMM and not float(van) > 0:
@@ -861,10 +855,50 @@ def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0,
     if codes is not None and not (isinstance(codes, torch.Tensor) and codes.device == device and codes.dtype == torch.int8
                                   and codes.is_contiguous() and tuple(codes.shape) == (n, int(lag))):
         raise ValueError(f"codes must be a contiguous CUDA int8 tensor [{n}, {int(lag)}] on {device}")
+    return device, rank, W, counts, n, step0, n_steps, prior, mode
+
+
+def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van=None, prior=None, h=None,
+                   get_map=False, codes=None):
+    """One launch of ``bear_generate_steps_f64``: steps ``step0 .. step0 + n_steps - 1`` of every sequence that has letters left.
+    ``table``: CUDA int64 [N] ascending distinct keys, ``counts`` int32 [N, W] their count rows in that order (None with an empty
+    table); ``rank``: ``score_ranks`` of the alphabet.  Per sequence, all on the table's device and updated in place: ``keys``
+    int64 [n] the end key, ``left`` int32 [n] the letters still to write; ``sample`` int64 [n] the sample index; ``letters`` uint8
+    [n, L >= step0 + n_steps] receives the letter codes at columns ``step0 ..``.  The model: ``van`` (a BMM: any ``n_steps``, a whole
+    flank in one launch), or ``prior`` float64 [n, W] rows of the current end k-mers (``n_steps`` 1) with ``h`` (BEAR) or without
+    (the AR model, ``get_map`` only).  ``codes`` int8 [n, lag], if given, receives the new end k-mers as ``core.encode_kmers`` codes."""
+    device, rank, W, counts, n, step0, n_steps, prior, mode = _generate_checks(
+        table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, van, prior, None, h, get_map, codes)
     _launch(device, "bear_generate_steps_f64", _ptr(table), _ptr(counts), table.numel(), int(lag), W,
             rank.ctypes.data_as(ctypes.c_void_p), mode, int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0,
             float(van) if mode == GEN_BMM else 0.0, _ptr(prior), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample), _ptr(left), n,
             step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
+
+
+def generate_whole(table, counts, rank, lag, keys, sample, left, length, stopped, letters, step0, n_steps, seed, van=None, prior=None,
+                   mat=None, h=None, get_map=False, codes=None):
+    """One launch of ``bear_generate_whole_f64``: ``generate_steps`` with the stop drawn like a letter.  A sequence that has steps
+    ``left`` (int32 [n]: the cut) takes them until the stop wins: then ``stopped`` (uint8 [n]) is set, ``left`` becomes 0, nothing is
+    written and the key stays; a letter goes to ``letters`` and adds 1 to ``length`` (int32 [n]).  ``keys``, ``left``, ``length`` and
+    ``stopped`` are the whole state, updated in place.  The model: ``van``; ``prior`` rows of the current end k-mers (``n_steps`` 1); or,
+    for the protein alphabet, ``mat`` float64 [lag, 21, 21] -- the linear AR function inside the kernel, any ``n_steps`` -- the last
+    two with ``h`` (BEAR) or without (the AR model, ``get_map`` only)."""
+    if prior is not None and mat is not None:
+        raise ValueError("prior rows or mat: one source of the AR function's rows")
+    device, rank, W, counts, n, step0, n_steps, prior, mode = _generate_checks(
+        table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, van, prior, mat, h, get_map, codes)
+    _check_vec(length, torch.int32, "length", n, device=device)
+    _check_vec(stopped, torch.uint8, "stopped", n, device=device)
+    if mat is not None:
+        if W != LINEAR_WIDE_WIDTH:
+            raise ValueError(f"mat: the linear AR function runs inside the kernel at rows of {LINEAR_WIDE_WIDTH} only")
+        if not (isinstance(mat, torch.Tensor) and mat.device == device and mat.dtype == torch.float64 and mat.is_contiguous()
+                and tuple(mat.shape) == (int(lag), W, W)):
+            raise ValueError(f"mat must be a contiguous CUDA float64 tensor [{int(lag)}, {W}, {W}] on {device}")
+    _launch(device, "bear_generate_whole_f64", _ptr(table), _ptr(counts), table.numel(), int(lag), W,
+            rank.ctypes.data_as(ctypes.c_void_p), mode, int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0,
+            float(van) if mode == GEN_BMM else 0.0, _ptr(prior), _ptr(mat), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample),
+            _ptr(left), _ptr(length), _ptr(stopped), n, step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
 
 
 def shuffle_rows(src, seed):

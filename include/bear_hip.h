@@ -1017,6 +1017,33 @@ int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint6
                             const uint64_t *sample, uint32_t *left, uint64_t n_seq, uint64_t step0, uint64_t n_steps,
                             uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream);
 
+/*
+ * bear_generate_whole_f64: whole sequences, from a start context to the stop (assemble.generate_sequences).  The steps, streams
+ * and arguments of bear_generate_steps_f64, with the stop b = width - 1 drawn like a letter: per step the values of ALL width
+ * letters are formed (for b < width - 1 bit for bit those of bear_generate_steps_f64: same keys, same concentration) and the
+ * lowest b with the largest value wins.
+ *   the stop wins:    stopped[i] = 1, left[i] = 0; nothing is written to letters, the key is not advanced
+ *   a letter wins:    letters[i * letters_stride + t] = b, the key is shifted as above, length[i] += 1, left[i] -= 1
+ *   left    [dev] uint32 [n_seq]: steps the sequence may still take (the cut: a sequence that reaches 0 unstopped was cut there)
+ *   length  [dev] uint32 [n_seq]: letters written so far;  stopped [dev] uint8 [n_seq]: set to 1 by the stop, else left alone.
+ *           keys, left, length and stopped are the whole state, read and written: n steps in one launch are the bytes of any cut
+ *           of them into launches that continue at step0.
+ *   The rows f of the AR function (BEAR_GEN_BEAR: fma(f[b], 1 / h, c[b]); BEAR_GEN_AR: f[b]) come from one of
+ *   prior  [dev, nullable] double [n_seq, width]: the rows of the CURRENT end k-mers, n_steps at most 1, as above; or
+ *   mat    [dev, nullable] double [lag, 21, 21], width 21 only: the linear AR function inside the kernel -- per step the row
+ *          softmax_b(sum_l mat[l, code[l], b]) of the end k-mer's codes ('[' = 20), bit for bit the row
+ *          bear_linear_forward_wide_f64 writes for them; any n_steps: whole sequences under a trained linear model in one launch.
+ *          mat and the exp table are staged in LDS once per block; the grid of this variant is capped at 512 blocks.
+ * Refused with BEAR_ERR_INVALID_ARG before any device call: everything bear_generate_steps_f64 refuses (a mode that needs rows
+ * with neither prior nor mat), prior and mat both given, mat at width 5, n_steps > 1 with a prior, a missing or misaligned
+ * length or stopped.  n_seq = 0 is valid and launches nothing.  No atomics and no sums across lanes: the same bytes in both
+ * libraries.
+ */
+int bear_generate_whole_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
+                            int mode, int map, double h, double van, const double *prior, const double *mat, uint64_t seed,
+                            uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
+                            uint64_t step0, uint64_t n_steps, uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
