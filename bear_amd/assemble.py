@@ -78,6 +78,31 @@ def _host_flanks(counter, seqs_by_dir, lengths_by_dir, lag, alphabet, alphabet_n
     return flanks
 
 
+def _require_letters(s, letters_en, what, alphabet_name):
+    """Every character of a seed or a prompt is a letter of the alphabet, or ``ValueError``."""
+    for ch in set(s):
+        if ch not in letters_en:
+            raise ValueError(f"character {ch!r} of {what} {s!r} is not a letter of the alphabet {alphabet_name!r}")
+
+
+def _ar_step(generate, state, t, seed, ar_func, kmer_codes, W, h, get_map):
+    """Step ``t`` of a trained model: the AR function's rows of the current end k-mers, then one launch of ``generate``
+    (``kernels.generate_steps`` / ``generate_whole`` over its ``state``), which also writes the next end k-mers to ``kmer_codes``."""
+    import torch
+    with torch.no_grad():
+        prior = ar_func(kmer_codes).to(torch.float64).expand(kmer_codes.shape[0], W).contiguous()
+    generate(*state, t, 1, seed, prior=prior, h=None if get_map else float(h), get_map=get_map, codes=kmer_codes)
+
+
+def _write_seqs_fa(save_folder, gen_seqs):
+    """``seqs.fa`` in ``save_folder``: row i, replicate j as ``>seq{i}_rep{j}``."""
+    os.makedirs(save_folder, exist_ok=True)
+    with open(os.path.join(save_folder, "seqs.fa"), "w") as f:
+        for i, seqs in enumerate(gen_seqs):
+            for j, seq in enumerate(seqs):
+                f.write(">seq{}_rep{}\n{}\n".format(i, j, seq))
+
+
 def _device_flanks(counter, seqs_by_dir, lengths_by_dir, lag, alphabet_name, h, ar_func, vans, get_map, seed):
     """The flanks of both directions grown on the device (``kernels.generate_steps``, kernels_generate.h): no table, no dictionary
     and no host round trip per letter.  A BMM takes one launch per direction; a trained model one AR-function call and one launch
@@ -99,9 +124,7 @@ def _device_flanks(counter, seqs_by_dir, lengths_by_dir, lag, alphabet_name, h, 
             s_ = str(s_)
             if len(s_) < lag:
                 raise ValueError(f"seed {s_!r} is shorter than the lag {lag}")
-            for ch in set(s_):
-                if ch not in letters_en:
-                    raise ValueError(f"character {ch!r} of seed {s_!r} is not a letter of the alphabet {alphabet_name!r}")
+            _require_letters(s_, letters_en, "seed", alphabet_name)
         raw = np.frombuffer("".join(str(s_)[-lag:] for s_ in seqs).encode("ascii"), dtype=np.uint8)
         ends.append(counter._lut[raw].reshape(len(seqs), lag))
     seed = _next_seed() if seed is None else seed
@@ -124,10 +147,7 @@ def _device_flanks(counter, seqs_by_dir, lengths_by_dir, lag, alphabet_name, h, 
             else:
                 kmer_codes = counter.codes_of_keys(keys)
                 for t in range(n_steps):
-                    with torch.no_grad():
-                        prior = ar_func(kmer_codes).to(torch.float64).expand(n_total, W).contiguous()
-                    kernels.generate_steps(*common, t, 1, seed, prior=prior, h=None if get_map else float(h[0]), get_map=get_map,
-                                           codes=kmer_codes)
+                    _ar_step(kernels.generate_steps, common, t, seed, ar_func, kmer_codes, W, None if get_map else h[0], get_map)
         flanks = []
         for letters, lens in grown:                            # the one copy back (and the first synchronisation)
             chars = char_of[np.minimum(letters.cpu().numpy(), W - 2)]
@@ -183,11 +203,7 @@ def assemble_no_ends(seqs_fa_file, lengths_to_gen, num_to_gen, bear_path, kmc_pa
         probs = np.average(core.tf_one_hot(list(seqs), alphabet_name).cpu().numpy(), axis=0)
         sw_ent.append(-np.sum(xlogy(probs, probs), axis=-1))
     if save_folder is not None:
-        os.makedirs(save_folder, exist_ok=True)
-        with open(os.path.join(save_folder, "seqs.fa"), "w") as f:
-            for i, seqs in enumerate(gen_seqs):
-                for j, seq in enumerate(seqs):
-                    f.write(">seq{}_rep{}\n{}\n".format(i, j, seq))
+        _write_seqs_fa(save_folder, gen_seqs)
         try:
             import matplotlib
             matplotlib.use("Agg")
@@ -243,9 +259,7 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
     letters_en = "".join(str(ch) for ch in core.alphabets_en[name][:-1])
     prompts = [""] if prompts is None else [str(p) for p in prompts]
     for p in prompts:
-        for ch in set(p):
-            if ch not in letters_en:
-                raise ValueError(f"character {ch!r} of prompt {p!r} is not a letter of the alphabet {name!r}")
+        _require_letters(p, letters_en, "prompt", name)
     if bear_path is not None:
         lag_b, name_b, h_b, ar_func, _ = get_var_probs.load_bear(bear_path)
         if (lag_b, name_b) != (lag, name):
@@ -275,10 +289,7 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
         else:
             kmer_codes = counter.codes_of_keys(keys)
             for t in range(max_len):
-                with torch.no_grad():
-                    prior = ar_func(kmer_codes).to(torch.float64).expand(n_total, W).contiguous()
-                kernels.generate_whole(*state, t, 1, seed, prior=prior, h=None if get_map else float(h), get_map=get_map,
-                                       codes=kmer_codes)
+                _ar_step(kernels.generate_whole, state, t, seed, ar_func, kmer_codes, W, h, get_map)
                 if (t + 1) % 16 == 0 and t + 1 < max_len and not _any_left(left):
                     break
         # the one copy back: letters | length as four bytes | stopped, a row per sequence
@@ -288,9 +299,5 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
     seqs = [prompts[i // num_to_gen] + chars[i, :int(l)].tobytes().decode("ascii") for i, l in enumerate(lens)]
     seqs = np.array(seqs, dtype=str).reshape(len(prompts), num_to_gen)
     if save_folder is not None:
-        os.makedirs(save_folder, exist_ok=True)
-        with open(os.path.join(save_folder, "seqs.fa"), "w") as f:
-            for i, row in enumerate(seqs):
-                for j, seq in enumerate(row):
-                    f.write(">seq{}_rep{}\n{}\n".format(i, j, seq))
+        _write_seqs_fa(save_folder, seqs)
     return seqs, back[:, max_len + 4].astype(bool).reshape(len(prompts), num_to_gen)

@@ -24,6 +24,15 @@ unsigned scr_grid(uint64_t work, uint64_t per_block) {
   return (unsigned)(g < 1 ? 1 : (g > (1u << 20) ? (1u << 20) : g));
 }
 
+// the width-5 or the width-21 instantiation of a kernel (the entries have refused every other width)
+#define LAUNCH_BY_WIDTH(width, k5, k21, grid, block, lds, stream, ...)              \
+  do {                                                                              \
+    if ((width) == 5)                                                               \
+      hipLaunchKernelGGL(k5, grid, block, lds, stream, __VA_ARGS__);                \
+    else                                                                            \
+      hipLaunchKernelGGL(k21, grid, block, lds, stream, __VA_ARGS__);               \
+  } while (0)
+
 // What the two generation entries check before any device call, and their argument block.  has_f: rows of the AR function are at
 // hand (prior rows, or mat for the kernel to form them); per_step: they are prior rows, those of the CURRENT end k-mers.
 bool gen_prepare(int lag, int width, const uint8_t *rank, int mode, int map, double h, double van, bool has_f, bool per_step,
@@ -66,6 +75,28 @@ bool gen_pointers_ok(const uint64_t *table, const uint32_t *counts, uint64_t n_t
     return false;
   return !(letters_stride && n_seq > (~0ull) / letters_stride);
 }
+
+// The one launch of both entries: generate_whole_kernel (STOP) or generate_steps_kernel of the width, a block per GEN_THREADS /
+// GEN_GROUP(letter lanes) sequences.  With mat (width 21, STOP) every block stages mat: few blocks, a stride, and the dynamic LDS image.
+template <bool STOP>
+int gen_launch(int width, const uint64_t *table, const uint32_t *counts, uint64_t n_table, const double *prior, const double *mat,
+               uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
+               const gen_args &A, uint8_t *letters, int8_t *codes, void *stream) {
+  if (A.n_steps == 0 && !codes) return BEAR_OK;
+  const int nl = STOP ? width : width - 1;
+  unsigned grid = scr_grid(n_seq, GEN_THREADS / GEN_GROUP(nl));
+  if (mat && grid > GEN_WHOLE_MAT_BLOCKS) grid = GEN_WHOLE_MAT_BLOCKS;
+  const dim3 blocks(grid), block(GEN_THREADS);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if constexpr (STOP)
+    LAUNCH_BY_WIDTH(width, (generate_whole_kernel<3, 5>), (generate_whole_kernel<5, 21>), blocks, block, mat ? GEN_WHOLE_MAT_LDS(A.lag) : 0,
+                    s, table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
+  else
+    LAUNCH_BY_WIDTH(width, (generate_steps_kernel<3, 5>), (generate_steps_kernel<5, 21>), blocks, block, 0, s, table, counts, n_table,
+                    prior, keys, sample, left, n_seq, A, letters, codes);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -85,10 +116,8 @@ int bear_score_transitions_u64(const uint8_t *text, const uint64_t *seg, uint64_
   if (!text || !keys || !letters || misaligned8(keys) || (n_seg && (!seg || misaligned8(seg)))) return BEAR_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(scr_grid(n_sym, SCR_THREADS)), block(SCR_THREADS);
-  if (width == 5)
-    hipLaunchKernelGGL(score_transitions_kernel<3>, grid, block, 0, s, text, seg, n_sym, n_seg, lag, 5u, R, keys, letters);
-  else
-    hipLaunchKernelGGL(score_transitions_kernel<5>, grid, block, 0, s, text, seg, n_sym, n_seg, lag, 21u, R, keys, letters);
+  LAUNCH_BY_WIDTH(width, score_transitions_kernel<3>, score_transitions_kernel<5>, grid, block, 0, s, text, seg, n_sym, n_seg, lag,
+                  (uint32_t)width, R, keys, letters);
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
@@ -164,12 +193,8 @@ int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_
   if (n_t) {
     HIP_TRY(terms.alloc(n_t * M));
     const dim3 grid(scr_grid(n_t, MRG_THREADS)), block(MRG_THREADS);
-    if (width == 5)
-      hipLaunchKernelGGL(marg_terms_kernel<5>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train, n_h > 0 ? prior : nullptr,
-                         n_rows, P, terms.get());
-    else
-      hipLaunchKernelGGL(marg_terms_kernel<21>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train, n_h > 0 ? prior : nullptr,
-                         n_rows, P, terms.get());
+    LAUNCH_BY_WIDTH(width, marg_terms_kernel<5>, marg_terms_kernel<21>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train,
+                    n_h > 0 ? prior : nullptr, n_rows, P, terms.get());
     HIP_TRY(hipGetLastError());
   }
   if (n_t > MRG_CHUNK) {                 // only such a text can hold a long segment
@@ -195,17 +220,8 @@ int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint6
   if (n_seq == 0) return BEAR_OK;
   if (!gen_pointers_ok(table, counts, n_table, prior, keys, sample, left, n_seq, n_steps, letters, letters_stride))
     return BEAR_ERR_INVALID_ARG;
-  if (n_steps == 0 && !codes) return BEAR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 block(GEN_THREADS);
-  if (width == 5)
-    hipLaunchKernelGGL((generate_steps_kernel<3, 5>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_GROUP(5))), block, 0, s, table, counts,
-                       n_table, prior, keys, sample, left, n_seq, A, letters, codes);
-  else
-    hipLaunchKernelGGL((generate_steps_kernel<5, 21>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_GROUP(21))), block, 0, s, table, counts,
-                       n_table, prior, keys, sample, left, n_seq, A, letters, codes);
-  HIP_TRY(hipGetLastError());
-  return BEAR_OK;
+  return gen_launch<false>(width, table, counts, n_table, prior, nullptr, keys, sample, left, nullptr, nullptr, n_seq, A, letters, codes,
+                           stream);
 }
 
 int bear_generate_whole_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
@@ -220,20 +236,7 @@ int bear_generate_whole_f64(const uint64_t *table, const uint32_t *counts, uint6
   if (!gen_pointers_ok(table, counts, n_table, prior, keys, sample, left, n_seq, n_steps, letters, letters_stride) || !length ||
       !stopped || misaligned4(length) || (mat && misaligned8(mat)))
     return BEAR_ERR_INVALID_ARG;
-  if (n_steps == 0 && !codes) return BEAR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 block(GEN_THREADS);
-  if (width == 5) {
-    hipLaunchKernelGGL((generate_whole_kernel<3, 5>), dim3(scr_grid(n_seq, GEN_THREADS / GEN_WHOLE_GROUP(5))), block, 0, s, table,
-                       counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
-  } else {
-    unsigned grid = scr_grid(n_seq, GEN_THREADS / GEN_WHOLE_GROUP(21));
-    if (mat && grid > GEN_WHOLE_MAT_BLOCKS) grid = GEN_WHOLE_MAT_BLOCKS;        // every block stages mat: few blocks, a stride
-    hipLaunchKernelGGL((generate_whole_kernel<5, 21>), dim3(grid), block, mat ? GEN_WHOLE_MAT_LDS(lag) : 0, s, table, counts, n_table,
-                       prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
-  }
-  HIP_TRY(hipGetLastError());
-  return BEAR_OK;
+  return gen_launch<true>(width, table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes, stream);
 }
 
 }  // extern "C"

@@ -1,27 +1,31 @@
-// kernels_generate.h -- sequence generation on the device (assemble.assemble_no_ends with a DeviceCounter): every sequence grows
-// letter by letter from its end k-mer, the transition table row of that k-mer is looked up in the sorted key table of a column and
-// sampled (or taken at its MAP value) where it is needed, and the letter is a Gumbel-max draw over the row.
+// kernels_generate.h -- sequence generation on the device (assemble.assemble_no_ends and assemble.generate_sequences with a
+// DeviceCounter): every sequence grows letter by letter from its end k-mer, the transition table row of that k-mer is looked up in
+// the sorted key table of a column and sampled (or taken at its MAP value) where it is needed, and the letter is a Gumbel-max draw
+// over the row.
 //
 // The host loop of assemble.py keeps "one posterior sample of the transition table per generated sequence" (assemble.py:126) as an
 // array, because it cannot draw the same row again later.  Here a table value is a pure function of (seed, sequence's sample index,
 // k-mer key, letter): a sequence that returns to a k-mer forms the same row again, and nothing is stored.
 //
-// Lane mapping: the letters of one sequence sit on neighbouring lanes, GEN_GROUP(W) lanes per sequence -- 4 at W = 5 (every lane a
-// letter), 32 at W = 21 (20 letters, 12 lanes that only take part in the exchange).  Per step the first lane of a group finds the
-// row (the loop of kmer_find_kernel) and hands it round, every letter lane forms ONE concentration, ONE log-Gamma draw and ONE
-// Gumbel draw, and the arg-max is log2(group) lane exchanges of (value, letter).  A sequence per lane would run W - 1 rejection
-// samplers one behind the other (and hold them all in registers: the 169 VGPRs of logdir_sample_kernel<21>).
+// ONE body, gen_run<BITS, W, STOP>, under two kernels.  generate_steps_kernel (STOP = false) grows flanks of given lengths and never
+// draws the stop: the NL = W - 1 letters take part.  generate_whole_kernel (STOP = true) draws over all NL = W letters -- the stop
+// b = W - 1 is a letter like the others (same two streams, so a cell b < W - 1 holds bit for bit the value it holds without the
+// stop) -- and a sequence ends when it wins (assemble.generate_sequences).
+//
+// Lane mapping: the letters of one sequence sit on neighbouring lanes, GEN_GROUP(NL) lanes per sequence -- 4 and 8 at W = 5 (every
+// lane a letter; three lanes of the 8 only take part in the exchange), 32 at W = 21.  Per step the first lane of a group finds the
+// row (scr_find_row) and hands it round, every letter lane forms ONE concentration, ONE log-Gamma draw and ONE Gumbel draw, and the
+// arg-max is log2(group) lane exchanges of (value, letter).  A sequence per lane would run W - 1 rejection samplers one behind the
+// other (and hold them all in registers: the 169 VGPRs of logdir_sample_kernel<21>).
 // No atomics and no sum across lanes: the letters are the same in both libraries and for any cut of the steps into launches.
-// generate_steps_kernel grows flanks of given lengths and never draws the stop; generate_whole_kernel (below) draws over all W
-// letters and ends a sequence when the stop wins (assemble.generate_sequences).
 #pragma once
-#include "kernels_score.h"   // scr_ranks, SCR_ABSENT: keys are those of bear_score_transitions_u64
-#include "rows_wide_common.h"   // LNW_W, LNW_MAT, lnw_forward_row: the linear AR function's row inside generate_whole_kernel
+#include "kernels_score.h"   // scr_ranks, scr_find_row: keys are those of bear_score_transitions_u64
+#include "rows_wide_common.h"   // LNW_W, LNW_MAT, lnw_forward_row: the linear AR function's row inside generate_whole_kernel<5, 21>
 #include "sample_common.h"
 
 #define GEN_THREADS 256
 #define GEN_ID_GUMBEL 3000u   // the model id of the Gumbel stream (the table values are model 0; beside EVL_ID_ARM / EVL_ID_VAN)
-#define GEN_GROUP(W) ((W) == 5 ? 4 : 32)
+#define GEN_GROUP(NL) ((NL) <= 4 ? 4 : ((NL) <= 8 ? 8 : 32))   // lanes per sequence for NL letter lanes
 
 struct gen_args {
   int lag, mode, map;          // mode: BEAR_GEN_BMM / BEAR_GEN_BEAR / BEAR_GEN_AR (include/bear_hip.h)
@@ -41,157 +45,91 @@ __device__ __forceinline__ uint32_t gen_byte4(const uint64_t (&w)[4], uint32_t i
   return (uint32_t)(x >> ((i & 7u) * 8u)) & 0xFFu;
 }
 
-// Steps step0 .. step0 + n_steps - 1 of every sequence that has letters left (left[i] of them; the sequence takes min(left[i],
-// n_steps) steps and left[i] goes down by that number).  keys[i]: the end key, read and written.  table / counts: the ascending
-// distinct keys of a column and their count rows in that order (an absent k-mer: a row of zeros).  prior: NULL, or [n_seq, W]
-// rows for the current end k-mers (then n_steps = 1: the host forms the next rows from `codes`).
-// Every loop runs the same number of times on all lanes of a wave (a finished sequence idles), so each exchange finds its group whole.
-template <int BITS, int W>
-__global__ __launch_bounds__(GEN_THREADS) void generate_steps_kernel(const uint64_t *__restrict__ table,
-                                                                     const uint32_t *__restrict__ counts, uint64_t n_table,
-                                                                     const double *__restrict__ prior, uint64_t *__restrict__ keys,
-                                                                     const uint64_t *__restrict__ sample, uint32_t *__restrict__ left,
-                                                                     uint64_t n_seq, gen_args A, uint8_t *__restrict__ letters,
-                                                                     int8_t *__restrict__ codes) {
-  constexpr int G = GEN_GROUP(W);
-  constexpr uint32_t PER_BLOCK = GEN_THREADS / G;
-  const uint32_t b = threadIdx.x % G, g = threadIdx.x / G;
-  const uint64_t mask = (1ull << (BITS * A.lag)) - 1ull;       // BITS * lag <= 63
-  for (uint64_t base = (uint64_t)blockIdx.x * PER_BLOCK; base < n_seq; base += (uint64_t)gridDim.x * PER_BLOCK) {
-    const uint64_t i = base + g;
-    const bool have = i < n_seq;
-    uint64_t q = have ? keys[i] : 0ull;
-    const uint64_t s = have ? sample[i] : 0ull;
-    const uint32_t left0 = have ? left[i] : 0u;
-    const uint32_t todo = (uint64_t)left0 < A.n_steps ? left0 : (uint32_t)A.n_steps;
-    for (uint32_t k = 0; __any(k < todo); ++k) {
-      const bool live = k < todo;
-      const uint64_t t = A.step0 + k;
-      uint32_t row = SCR_ABSENT;
-      if (live && b == 0 && n_table > 0) {
-        uint64_t lo = 0, n = n_table;
-        while (n > 1) {
-          const uint64_t half = n >> 1;
-          lo = table[lo + half] <= q ? lo + half : lo;      // the last entry <= q, or entry 0
-          n -= half;
-        }
-        row = table[lo] == q ? (uint32_t)lo : SCR_ABSENT;
-      }
-      row = (uint32_t)__shfl((int)row, 0, G);
-      double v = -INFINITY;
-      if (live && b < W - 1) {
-        const double c = row != SCR_ABSENT ? (double)counts[(uint64_t)row * W + b] : 0.0;
-        const double f = prior ? prior[i * W + b] : 0.0;
-        const double conc = A.mode == BEAR_GEN_BMM ? A.van + c : (A.mode == BEAR_GEN_BEAR ? __builtin_fma(f, A.inv_h, c) : f);
-        const double tv = A.map ? log(conc) : smp_log_gamma(conc, smp_cell_key(A.seed, 0u, s, mix64(q) + b));
-        v = tv - log(-log(u01(smp_cell_key(A.seed, GEN_ID_GUMBEL, s, t * W + b))));
-      }
-      uint32_t best = b;       // the lowest letter with the largest value; an idle lane holds -inf under a letter beyond the row
-#pragma unroll
-      for (int off = G / 2; off >= 1; off >>= 1) {
-        const double ov = __shfl_xor(v, off, G);
-        const uint32_t ob = (uint32_t)__shfl_xor((int)best, off, G);
-        const bool take = ov > v || (ov == v && ob < best);
-        v = take ? ov : v;
-        best = take ? ob : best;
-      }
-      best = (uint32_t)__shfl((int)best, 0, G);      // (one answer per group whatever a NaN did to the comparisons)
-      if (live) {
-        q = ((q << BITS) | (uint64_t)gen_byte3(A.rank, best)) & mask;
-        if (b == 0) letters[i * A.stride + t] = (uint8_t)best;
-      }
-    }
-    if (have) {
-      if (b == 0) {
-        keys[i] = q;
-        left[i] = left0 - todo;
-      }
-      if (codes)
-        for (int p = (int)b; p < A.lag; p += G)
-          codes[i * (uint64_t)A.lag + p] = (int8_t)gen_byte4(A.code, (uint32_t)(q >> (BITS * (A.lag - 1 - p))) & ((1u << BITS) - 1u));
-    }
-  }
+// the core.encode_kmers code of letter p (0: the first) of the k-mer with the key q
+template <int BITS>
+__device__ __forceinline__ int8_t gen_code_at(const gen_args &A, uint64_t q, int p) {
+  return (int8_t)gen_byte4(A.code, (uint32_t)(q >> (BITS * (A.lag - 1 - p))) & ((1u << BITS) - 1u));
 }
 
-// ------------------------------------------------------------------ whole sequences, start to stop (assemble.generate_sequences)
-// The sibling of generate_steps_kernel that draws over all W letters: the stop b = W - 1 is a letter like the others (same two
-// streams, so a cell b < W - 1 holds bit for bit the value of the kernel above), and a sequence ends when it wins -- stopped[i] = 1,
-// left[i] = 0, nothing written to letters, the key not advanced.  GEN_WHOLE_GROUP(W) lanes per sequence: 8 at W = 5, 32 at W = 21.
-// length[i] counts the letters written.  keys, left, length and stopped are the whole state: any cut of the steps into launches
-// that continue at step0 gives the same bytes.
-//
-// f, the AR function's row of the current end k-mer, is prior [n_seq, W] (then n_steps <= 1, as above) or, at W = 21, formed here
-// from mat [lag, 21, 21]: lnw_forward_row on the LDS image of mat and the exp table, the row bear_linear_forward_wide_f64 writes
-// for the same codes ('[' = 20), bit for bit -- whole sequences under a trained linear model in one launch.  The group's lanes
-// p < lag put the k-mer's code bytes into LDS, its first lane forms the row there, every lane reads its own entry back.  A group
-// lies inside one wave, whose LDS accesses complete in order: the hand-over needs no barrier, only that the compiler keeps the
-// order (the wave-scope fences).  Dynamic LDS: exp table | a row per group | mat | 16 code bytes per group.  The grid of this
-// variant is capped (GEN_WHOLE_MAT_BLOCKS: every block loads mat) and strides over the sequences.
-#define GEN_WHOLE_GROUP(W) ((W) == 5 ? 8 : 32)
+// With mat (W = 21, STOP) every block stages mat, so the grid is capped and strides over the sequences.  Dynamic LDS: exp table |
+// a row per group | mat | 16 code bytes per group.
 #define GEN_WHOLE_MAT_BLOCKS 512
 #define GEN_WHOLE_MAT_LDS(lag) \
-  (sizeof(double) * (BEAR_EXPTAB_N + (size_t)(GEN_THREADS / GEN_WHOLE_GROUP(21)) * LNW_W + (size_t)(lag) * LNW_MAT) + \
-   (size_t)(GEN_THREADS / GEN_WHOLE_GROUP(21)) * 16)
+  (sizeof(double) * (BEAR_EXPTAB_N + (size_t)(GEN_THREADS / GEN_GROUP(21)) * LNW_W + (size_t)(lag) * LNW_MAT) + \
+   (size_t)(GEN_THREADS / GEN_GROUP(21)) * 16)
 static_assert(GEN_WHOLE_MAT_LDS(12) <= 64 * 1024, "generate_whole_kernel with mat: LDS");
 
-template <int BITS, int W>
-__global__ __launch_bounds__(GEN_THREADS) void generate_whole_kernel(const uint64_t *__restrict__ table,
-                                                                     const uint32_t *__restrict__ counts, uint64_t n_table,
-                                                                     const double *__restrict__ prior, const double *__restrict__ mat,
-                                                                     uint64_t *__restrict__ keys, const uint64_t *__restrict__ sample,
-                                                                     uint32_t *__restrict__ left, uint32_t *__restrict__ length,
-                                                                     uint8_t *__restrict__ stopped, uint64_t n_seq, gen_args A,
-                                                                     uint8_t *__restrict__ letters, int8_t *__restrict__ codes) {
-  constexpr int G = GEN_WHOLE_GROUP(W);
+// Steps step0 .. step0 + n_steps - 1 of every sequence that has steps left (left[i] of them: it takes them until n_steps are done
+// or, with STOP, the stop wins, and left[i] goes down by the steps taken).  keys[i]: the end key, read and written.  table /
+// counts: the ascending distinct keys of a column and their count rows in that order (an absent k-mer: a row of zeros).
+// STOP: when the stop wins stopped[i] = 1, left[i] = 0, nothing is written to letters and the key is not advanced; length[i] counts
+// the letters written.  keys, left, length and stopped are the whole state: any cut of the steps into launches that continue at
+// step0 gives the same bytes.  Without STOP length, stopped and mat are not read (NULL).
+//
+// f, the AR function's row of the current end k-mer, is prior: NULL, or [n_seq, W] rows (then n_steps <= 1: the host forms the
+// next rows from `codes`) -- or, with STOP at W = 21, formed here from mat [lag, 21, 21]: lnw_forward_row on the LDS image of mat
+// and the exp table, the row bear_linear_forward_wide_f64 writes for the same codes ('[' = 20), bit for bit -- whole sequences under a
+// trained linear model in one launch.  The group's lanes p < lag put the k-mer's code bytes into LDS, its first lane forms the row
+// there, every lane reads its own entry back.  A group lies inside one wave, whose LDS accesses complete in order: the hand-over
+// needs no barrier, only that the compiler keeps the order (the wave-scope fences).
+// Every loop runs the same number of times on all lanes of a wave (a finished sequence idles), so each exchange finds its group whole.
+template <int BITS, int W, bool STOP>
+__device__ __forceinline__ void gen_run(const uint64_t *__restrict__ table, const uint32_t *__restrict__ counts, uint64_t n_table,
+                                        const double *__restrict__ prior, const double *__restrict__ mat, uint64_t *__restrict__ keys,
+                                        const uint64_t *__restrict__ sample, uint32_t *__restrict__ left, uint32_t *__restrict__ length,
+                                        uint8_t *__restrict__ stopped, uint64_t n_seq, const gen_args &A, uint8_t *__restrict__ letters,
+                                        int8_t *__restrict__ codes) {
+  constexpr int NL = STOP ? W : W - 1;                           // the letters that are drawn
+  constexpr int G = GEN_GROUP(NL);
   constexpr uint32_t PER_BLOCK = GEN_THREADS / G;
-  extern __shared__ __attribute__((aligned(16))) double gen_lds[];
-  double *exptab = gen_lds;
-  double *R = gen_lds + BEAR_EXPTAB_N;                           // [PER_BLOCK][W]: the row of every group
-  double *M = R + PER_BLOCK * W;                                 // [lag][W][W]
-  int8_t *s_cd = reinterpret_cast<int8_t *>(M + A.lag * W * W);  // [PER_BLOCK][16]: the code bytes of every group's k-mer
+  constexpr bool MAT = STOP && W == 21;
   const uint32_t b = threadIdx.x % G, g = threadIdx.x / G;
   const uint64_t mask = (1ull << (BITS * A.lag)) - 1ull;         // BITS * lag <= 63
-  if (W == 21 && mat) {                                          // (the same for every thread of the launch)
-    if (threadIdx.x < BEAR_EXPTAB_N) exptab[threadIdx.x] = exp2((double)threadIdx.x * (1.0 / BEAR_EXPTAB_N));
-    for (int k = threadIdx.x; k < A.lag * W * W; k += GEN_THREADS) M[k] = mat[k];
-    __syncthreads();
+  [[maybe_unused]] double *exptab = nullptr, *R = nullptr, *M = nullptr;
+  [[maybe_unused]] int8_t *s_cd = nullptr;
+  if constexpr (MAT) {
+    extern __shared__ __attribute__((aligned(16))) double gen_lds[];
+    exptab = gen_lds;
+    R = gen_lds + BEAR_EXPTAB_N;                                 // [PER_BLOCK][W]: the row of every group
+    M = R + PER_BLOCK * W;                                       // [lag][W][W]
+    s_cd = reinterpret_cast<int8_t *>(M + A.lag * W * W);        // [PER_BLOCK][16]: the code bytes of every group's k-mer
+    if (mat) {                                                   // (the same for every thread of the launch)
+      if (threadIdx.x < BEAR_EXPTAB_N) exptab[threadIdx.x] = exp2((double)threadIdx.x * (1.0 / BEAR_EXPTAB_N));
+      for (int k = threadIdx.x; k < A.lag * W * W; k += GEN_THREADS) M[k] = mat[k];
+      __syncthreads();
+    }
   }
   for (uint64_t base = (uint64_t)blockIdx.x * PER_BLOCK; base < n_seq; base += (uint64_t)gridDim.x * PER_BLOCK) {
     const uint64_t i = base + g;
     const bool have = i < n_seq;
     uint64_t q = have ? keys[i] : 0ull;
     const uint64_t s = have ? sample[i] : 0ull;
-    uint32_t rem = have ? left[i] : 0u, len = have ? length[i] : 0u;
-    bool stop = false;
-    for (uint32_t k = 0; __any((uint64_t)k < A.n_steps && rem > 0u); ++k) {
-      const bool live = (uint64_t)k < A.n_steps && rem > 0u;       // the same on all lanes of a group
+    uint32_t rem = have ? left[i] : 0u;
+    [[maybe_unused]] uint32_t len = 0u;
+    [[maybe_unused]] bool stop = false;
+    if constexpr (STOP) len = have ? length[i] : 0u;
+    const uint32_t n_steps = (uint32_t)A.n_steps;                // (the entries refuse more than 2^32 - 1 steps)
+    for (uint32_t k = 0; __any(k < n_steps && rem > 0u); ++k) {
+      const bool live = k < n_steps && rem > 0u;       // the same on all lanes of a group
       const uint64_t t = A.step0 + k;
       uint32_t row = SCR_ABSENT;
-      if (live && b == 0 && n_table > 0) {
-        uint64_t lo = 0, n = n_table;
-        while (n > 1) {
-          const uint64_t half = n >> 1;
-          lo = table[lo + half] <= q ? lo + half : lo;      // the last entry <= q, or entry 0
-          n -= half;
-        }
-        row = table[lo] == q ? (uint32_t)lo : SCR_ABSENT;
-      }
+      if (live && b == 0) row = scr_find_row(table, n_table, q);
       row = (uint32_t)__shfl((int)row, 0, G);
       double f = 0.0;
-      if (W == 21 && mat) {
-        if (live && (int)b < A.lag)
-          s_cd[g * 16 + b] = (int8_t)gen_byte4(A.code, (uint32_t)(q >> (BITS * (A.lag - 1 - (int)b))) & ((1u << BITS) - 1u));
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (live && b == 0) lnw_forward_row(s_cd + g * 16, A.lag, M, exptab, R + g * W);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (live && b < W) f = R[g * W + b];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // ... before the next step's row overwrites it
-      } else if (prior && live && b < W) {
-        f = prior[i * W + b];
+      if constexpr (MAT) {
+        if (mat) {
+          if (live && (int)b < A.lag) s_cd[g * 16 + b] = gen_code_at<BITS>(A, q, (int)b);
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          if (live && b == 0) lnw_forward_row(s_cd + g * 16, A.lag, M, exptab, R + g * W);
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          if (live && b < NL) f = R[g * W + b];
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // ... before the next step's row overwrites it
+        }
       }
       double v = -INFINITY;
-      if (live && b < W) {
+      if (live && b < NL) {
         const double c = row != SCR_ABSENT ? (double)counts[(uint64_t)row * W + b] : 0.0;
+        if (prior) f = prior[i * W + b];                           // (never beside mat: the entry refuses the two together)
         const double conc = A.mode == BEAR_GEN_BMM ? A.van + c : (A.mode == BEAR_GEN_BEAR ? __builtin_fma(f, A.inv_h, c) : f);
         const double tv = A.map ? log(conc) : smp_log_gamma(conc, smp_cell_key(A.seed, 0u, s, mix64(q) + b));
         v = tv - log(-log(u01(smp_cell_key(A.seed, GEN_ID_GUMBEL, s, t * W + b))));
@@ -207,7 +145,7 @@ __global__ __launch_bounds__(GEN_THREADS) void generate_whole_kernel(const uint6
       }
       best = (uint32_t)__shfl((int)best, 0, G);      // (one answer per group whatever a NaN did to the comparisons)
       if (live) {
-        if (best == (uint32_t)(W - 1)) {             // the stop won: the sequence ends, its key stays
+        if (STOP && best == (uint32_t)(W - 1)) {     // the stop won: the sequence ends, its key stays
           stop = true;
           rem = 0u;
         } else {
@@ -222,12 +160,35 @@ __global__ __launch_bounds__(GEN_THREADS) void generate_whole_kernel(const uint6
       if (b == 0) {
         keys[i] = q;
         left[i] = rem;
-        length[i] = len;
-        if (stop) stopped[i] = 1;
+        if constexpr (STOP) {
+          length[i] = len;
+          if (stop) stopped[i] = 1;
+        }
       }
       if (codes)
-        for (int p = (int)b; p < A.lag; p += G)
-          codes[i * (uint64_t)A.lag + p] = (int8_t)gen_byte4(A.code, (uint32_t)(q >> (BITS * (A.lag - 1 - p))) & ((1u << BITS) - 1u));
+        for (int p = (int)b; p < A.lag; p += G) codes[i * (uint64_t)A.lag + p] = gen_code_at<BITS>(A, q, p);
     }
   }
+}
+
+// The two kernels: each carries the arguments its body reads and nothing else (no LDS, length, stopped or mat without STOP).
+template <int BITS, int W>
+__global__ __launch_bounds__(GEN_THREADS) void generate_steps_kernel(const uint64_t *__restrict__ table,
+                                                                     const uint32_t *__restrict__ counts, uint64_t n_table,
+                                                                     const double *__restrict__ prior, uint64_t *__restrict__ keys,
+                                                                     const uint64_t *__restrict__ sample, uint32_t *__restrict__ left,
+                                                                     uint64_t n_seq, gen_args A, uint8_t *__restrict__ letters,
+                                                                     int8_t *__restrict__ codes) {
+  gen_run<BITS, W, false>(table, counts, n_table, prior, nullptr, keys, sample, left, nullptr, nullptr, n_seq, A, letters, codes);
+}
+
+template <int BITS, int W>
+__global__ __launch_bounds__(GEN_THREADS) void generate_whole_kernel(const uint64_t *__restrict__ table,
+                                                                     const uint32_t *__restrict__ counts, uint64_t n_table,
+                                                                     const double *__restrict__ prior, const double *__restrict__ mat,
+                                                                     uint64_t *__restrict__ keys, const uint64_t *__restrict__ sample,
+                                                                     uint32_t *__restrict__ left, uint32_t *__restrict__ length,
+                                                                     uint8_t *__restrict__ stopped, uint64_t n_seq, gen_args A,
+                                                                     uint8_t *__restrict__ letters, int8_t *__restrict__ codes) {
+  gen_run<BITS, W, true>(table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
 }

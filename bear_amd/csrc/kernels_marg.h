@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "bear_math.h"
-#include "kernels_score.h"   // scr_segment_of, scr_off: the segments are those of the scoring text
+#include "kernels_score.h"   // scr_last_le, scr_off, the chunk rule: the segments are those of the scoring text
 
 #define MRG_THREADS 256
 #define MRG_WAVE 64                      // threads of a block of marg_chunk_kernel / marg_sum_kernel: one wave over 64 positions
@@ -43,7 +43,7 @@ __device__ __forceinline__ uint64_t mrg_key(const int32_t *__restrict__ rows, co
 }
 
 // the end of the stretch of positions [i, end) inside [i, s1) whose keys, shifted right by `shift`, equal `want` (position i's does):
-// the loop of kmer_find_kernel -- its trip count is set by s1 - i alone, no branch on what is read.  n = 1: no search.
+// the loop of scr_last_le on a computed key -- its trip count is set by s1 - i alone, no branch on what is read.  n = 1: no search.
 __device__ __forceinline__ uint64_t mrg_stretch_end(const int32_t *__restrict__ rows, const uint8_t *__restrict__ letters,
                                                     uint64_t i, uint64_t n, uint64_t want, int shift, uint32_t width,
                                                     uint64_t n_rows) {
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(MRG_THREADS) void marg_terms_kernel(const int32_t *
     bool run_head = false, group_head = false;
     uint64_t key = MRG_NO_KEY, left = 1;                 // left: positions from i to the end of its segment
     if (first <= i && i < end) {
-      const uint64_t s = scr_segment_of(seg, n_seg, i);
+      const uint64_t s = scr_last_le(seg, n_seg, i);
       const uint64_t s0 = scr_off(seg, s, n_t), s1 = scr_off(seg, s + 1, n_t);
       if (s0 <= i && i < s1) {
         key = mrg_key(rows, letters, i, W, n_rows);
@@ -132,35 +132,18 @@ __device__ __forceinline__ double mrg_sum_range(const double *__restrict__ t, ui
   return bear_wave_sum(acc);
 }
 
-// The chunks of the long segments, by score_chunk_kernel's rule: block g looks at text positions [g C, (g + 1) C) and sums the
-// chunks that START there, at most two -- slot 2 g: the chunk of the segment that holds position g C; slot 2 g + 1: chunk 0 of the
-// last segment that starts behind g C.  partials [2 n_blocks, M]; a slot without a chunk is never read.  blockIdx.y: the model.
+// The chunks of the segments of more than MRG_CHUNK positions (scr_chunks_of_block, the rule of kernels_score.h): one wave per
+// block of the text and model.  partials [2 n_blocks, M].  blockIdx.y: the model.
 __global__ __launch_bounds__(MRG_WAVE) void marg_chunk_kernel(const double *__restrict__ terms, uint32_t n_m,
                                                              const uint64_t *__restrict__ seg, uint64_t n_seg, uint64_t n_t,
                                                              uint64_t n_blocks, double *__restrict__ partials) {
   const uint32_t m = blockIdx.y;
   const double *__restrict__ t = terms + (uint64_t)m * n_t;
-  for (uint64_t g = blockIdx.x; g < n_blocks; g += gridDim.x) {
-    const uint64_t p0 = g * MRG_CHUNK;
-    const uint64_t p1 = p0 + MRG_CHUNK < n_t ? p0 + MRG_CHUNK : n_t;
-    const uint64_t first = scr_off(seg, 0, n_t), end = scr_off(seg, n_seg, n_t);
-    if (p0 >= p1 || first >= p1 || end <= p0 || first >= end) continue;
-    const uint64_t sb = scr_segment_of(seg, n_seg, (end < p1 ? end : p1) - 1);
-    if (first <= p0) {
-      const uint64_t sa = scr_segment_of(seg, n_seg, p0);
-      const uint64_t s0 = scr_off(seg, sa, n_t), s1 = scr_off(seg, sa + 1, n_t);
-      const uint64_t a = s0 + (p0 - s0 + MRG_CHUNK - 1) / MRG_CHUNK * MRG_CHUNK;      // its first chunk start at or behind p0
-      if (s0 <= p0 && s1 > s0 && s1 - s0 > MRG_CHUNK && a < s1) {
-        const double v = mrg_sum_range(t, a, a + MRG_CHUNK < s1 ? a + MRG_CHUNK : s1);
-        if (threadIdx.x == 0) partials[2 * g * n_m + m] = v;
-      }
-    }
-    const uint64_t s0 = scr_off(seg, sb, n_t), s1 = scr_off(seg, sb + 1, n_t);
-    if (s0 > p0 && s1 > s0 && s1 - s0 > MRG_CHUNK) {
-      const double v = mrg_sum_range(t, s0, s0 + MRG_CHUNK);
-      if (threadIdx.x == 0) partials[(2 * g + 1) * n_m + m] = v;
-    }
-  }
+  for (uint64_t g = blockIdx.x; g < n_blocks; g += gridDim.x)
+    scr_chunks_of_block<MRG_CHUNK>(seg, n_seg, n_t, g, [&](uint64_t slot, uint64_t a, uint64_t b) {
+      const double v = mrg_sum_range(t, a, b);
+      if (threadIdx.x == 0) partials[slot * n_m + m] = v;
+    });
 }
 
 // scores[i, m]: one wave per segment and model.  At most MRG_CHUNK positions: the one chunk, summed here; more: the chunks'
@@ -181,8 +164,8 @@ __global__ __launch_bounds__(MRG_WAVE) void marg_sum_kernel(const double *__rest
         double x[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const uint64_t aj = a + (uint64_t)j * MRG_CHUNK, g = aj / MRG_CHUNK;
-          x[j] = aj < s1 ? partials[(2 * g + (s0 <= g * MRG_CHUNK ? 0 : 1)) * n_m + m] : 0.0;
+          const uint64_t aj = a + (uint64_t)j * MRG_CHUNK;
+          x[j] = aj < s1 ? partials[scr_chunk_slot<MRG_CHUNK>(s0, aj) * n_m + m] : 0.0;
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc += x[j];

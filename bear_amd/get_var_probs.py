@@ -387,44 +387,65 @@ def _segment_text(segments, lag, alphabet_name):
     return codes, seg, int(np.minimum(lens, lag).sum())
 
 
-def _score_segments(counter, segments, lag, alphabet_name, h, ar_func, mc_samples, vans, get_map, seed):
-    """The device path of get_bear_probs / get_bear_probs_seqs: ``scores[i] = sum of log p(next | k-mer)`` over the transitions of
-    string ``i`` -> CUDA float64 [n_seg, num_models, mc_samples].  The distinct k-mers are numbered as
-    ``np.array(sorted(set(all_kmers)))`` numbers them (ascending keys), and that number keys the sampler's draws: with equal
-    ``seed`` the table is the one the host ``counter=`` path samples.
+def _free_memory(device):
+    """Bytes a call can still take on ``device``: what the driver reports plus what torch's allocator caches."""
+    return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
-    The table ``[K, W, num_models, mc_samples]`` is held whole: if it would not fit the free device memory a ``MemoryError`` says
-    so (score fewer strings or samples per call) -- rows are not processed in pieces, so a result never depends on what else
-    the device holds."""
+
+def _segment_rows(counter, segments, lag, alphabet_name, h, ar_func, vans):
+    """What ``_score_segments`` and ``_marg_segments`` do alike, up to their memory figure: the refusals, the scoring text, its keys,
+    the distinct k-mers -- numbered as ``np.array(sorted(set(all_kmers)))`` numbers them (ascending keys) -- and the row of every
+    position -> ``(hs, vans, text)``, ``text`` = ``(seg, rows, letters, kmer_keys, positions)``, tensors on the device, or None
+    where there is no transition anywhere."""
     if counter.lag != lag or counter.alphabet_name != alphabet_name:
         raise ValueError(f"counter: a lag-{counter.lag} table of {counter.alphabet_name!r}, asked for lag {lag} of {alphabet_name!r}")
-    device, W = counter.device, counter.width
+    device = counter.device
     vans = np.atleast_1d(np.asarray(vans, dtype=np.float64)).reshape(-1)
     hs = np.atleast_1d(np.asarray(h, dtype=np.float64)).reshape(-1) if ar_func is not None else np.zeros(0)
-    with_ar = ar_func is not None and get_map
-    num_models = len(vans) + len(hs) + int(with_ar)
-    if get_map:
-        mc_samples = 1
     codes, seg, n_none = _segment_text(segments, lag, alphabet_name)
-    if codes.size == n_none:        # no transition anywhere
-        return torch.zeros((len(segments), num_models, mc_samples), dtype=torch.float64, device=device)
+    if codes.size == n_none:
+        return hs, vans, None
     with torch.cuda.device(device):
         seg = torch.from_numpy(seg).to(device)
         keys, letters = kernels.score_transitions(torch.from_numpy(codes).to(device), seg, lag, counter.rank)
         uniq, inverse = torch.unique(keys, return_inverse=True)     # ascending; -1 (no transition) in front where there is one
         first = int(n_none > 0)
-        kmer_keys = uniq[first:].contiguous()
-        rows = (inverse - first).to(torch.int32)
-        K = kmer_keys.numel()
-        need = K * W * num_models * mc_samples * 8
-        free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-        if need > free:
-            raise MemoryError(f"the sampled table of {K} k-mers x {W} letters x {num_models} models x {mc_samples} samples takes "
-                              f"{need} bytes, the device has {free} free: score fewer variants / sequences or samples per call")
-        prior = None
-        if ar_func is not None:
-            with torch.no_grad():
-                prior = ar_func(counter.codes_of_keys(kmer_keys)).to(torch.float64).expand(K, W).contiguous()
+        return hs, vans, (seg, (inverse - first).to(torch.int32), letters, uniq[first:].contiguous(), codes.size)
+
+
+def _prior_rows(counter, ar_func, kmer_keys, need, what, advice):
+    """The AR function's rows [K, W] of the distinct k-mers (None without one), formed only once the caller's ``need`` bytes are
+    known to fit the free device memory: otherwise ``MemoryError``, before the AR function is called."""
+    free = _free_memory(counter.device)
+    if need > free:
+        raise MemoryError(f"{what} {need} bytes, the device has {free} free: {advice}")
+    if ar_func is None:
+        return None
+    with torch.no_grad():
+        return ar_func(counter.codes_of_keys(kmer_keys)).to(torch.float64).expand(kmer_keys.numel(), counter.width).contiguous()
+
+
+def _score_segments(counter, segments, lag, alphabet_name, h, ar_func, mc_samples, vans, get_map, seed):
+    """The device path of get_bear_probs / get_bear_probs_seqs: ``scores[i] = sum of log p(next | k-mer)`` over the transitions of
+    string ``i`` -> CUDA float64 [n_seg, num_models, mc_samples].  The number of a distinct k-mer (``_segment_rows``) keys the
+    sampler's draws: with equal ``seed`` the table is the one the host ``counter=`` path samples.
+
+    The table ``[K, W, num_models, mc_samples]`` is held whole: if it would not fit the free device memory a ``MemoryError`` says
+    so (score fewer strings or samples per call) -- rows are not processed in pieces, so a result never depends on what else
+    the device holds."""
+    hs, vans, text = _segment_rows(counter, segments, lag, alphabet_name, h, ar_func, vans)
+    with_ar = ar_func is not None and get_map
+    num_models = len(vans) + len(hs) + int(with_ar)
+    if get_map:
+        mc_samples = 1
+    if text is None:                # no transition anywhere
+        return torch.zeros((len(segments), num_models, mc_samples), dtype=torch.float64, device=counter.device)
+    seg, rows, letters, kmer_keys, _ = text
+    K, W = kmer_keys.numel(), counter.width
+    with torch.cuda.device(counter.device):
+        prior = _prior_rows(counter, ar_func, kmer_keys, K * W * num_models * mc_samples * 8,
+                            f"the sampled table of {K} k-mers x {W} letters x {num_models} models x {mc_samples} samples takes",
+                            "score fewer variants / sequences or samples per call")
         sample = kernels.logdir_sample if W == 5 else kernels.logdir_sample_wide
         lp = sample(counter.rows_of_keys(kmer_keys), prior, hs, vans, mc_samples, get_map=get_map, with_ar=with_ar, seed=seed,
                     row_base=0)
@@ -433,37 +454,22 @@ def _score_segments(counter, segments, lag, alphabet_name, h, ar_func, mc_sample
 
 def _marg_segments(counter, segments, lag, alphabet_name, h, ar_func, vans):
     """The device path of ``get_bear_probs_seqs(..., get_marg=True, marg_on_device=True)``: the exact Dirichlet-multinomial marginal
-    of string ``i`` under every model -> CUDA float64 [n_seg, num_models], BEAR models first.  ``_score_segments`` up to the
-    sampler -- the same refusals, keys, distinct k-mers, count rows and prior rows -- then ``kernels.score_marg`` instead of a table.
+    of string ``i`` under every model -> CUDA float64 [n_seg, num_models], BEAR models first.  ``_segment_rows`` and ``_prior_rows``
+    -- the refusals, keys, distinct k-mers and prior rows of ``_score_segments`` -- then the count rows and ``kernels.score_marg``
+    instead of a table.
 
     Per distinct k-mer the call holds a count row, a prior row and the rows' gather temporaries, per position one term per model:
     if that would not fit the free device memory a ``MemoryError`` says so, as ``_score_segments`` does."""
-    if counter.lag != lag or counter.alphabet_name != alphabet_name:
-        raise ValueError(f"counter: a lag-{counter.lag} table of {counter.alphabet_name!r}, asked for lag {lag} of {alphabet_name!r}")
-    device, W = counter.device, counter.width
-    vans = np.atleast_1d(np.asarray(vans, dtype=np.float64)).reshape(-1)
-    hs = np.atleast_1d(np.asarray(h, dtype=np.float64)).reshape(-1) if ar_func is not None else np.zeros(0)
+    hs, vans, text = _segment_rows(counter, segments, lag, alphabet_name, h, ar_func, vans)
     num_models = len(vans) + len(hs)
-    codes, seg, n_none = _segment_text(segments, lag, alphabet_name)
-    if codes.size == n_none:        # no transition anywhere
-        return torch.zeros((len(segments), num_models), dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        seg = torch.from_numpy(seg).to(device)
-        keys, letters = kernels.score_transitions(torch.from_numpy(codes).to(device), seg, lag, counter.rank)
-        uniq, inverse = torch.unique(keys, return_inverse=True)     # ascending; -1 (no transition) in front where there is one
-        first = int(n_none > 0)
-        kmer_keys = uniq[first:].contiguous()
-        rows = (inverse - first).to(torch.int32)
-        K = kmer_keys.numel()
-        need = K * W * 3 * 8 + codes.size * (num_models * 8 + 3 * 8)
-        free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-        if need > free:
-            raise MemoryError(f"the rows of {K} k-mers x {W} letters and the terms of {codes.size} positions x {num_models} models take "
-                              f"{need} bytes, the device has {free} free: score fewer sequences per call")
-        prior = None
-        if ar_func is not None:
-            with torch.no_grad():
-                prior = ar_func(counter.codes_of_keys(kmer_keys)).to(torch.float64).expand(K, W).contiguous()
+    if text is None:                # no transition anywhere
+        return torch.zeros((len(segments), num_models), dtype=torch.float64, device=counter.device)
+    seg, rows, letters, kmer_keys, positions = text
+    K, W = kmer_keys.numel(), counter.width
+    with torch.cuda.device(counter.device):
+        prior = _prior_rows(counter, ar_func, kmer_keys, K * W * 3 * 8 + positions * (num_models * 8 + 3 * 8),
+                            f"the rows of {K} k-mers x {W} letters and the terms of {positions} positions x {num_models} models take",
+                            "score fewer sequences per call")
         return kernels.score_marg(rows, letters, seg, counter.rows_of_keys(kmer_keys), prior, hs, vans)
 
 

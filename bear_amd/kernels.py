@@ -810,8 +810,11 @@ GEN_BMM, GEN_BEAR, GEN_AR = 0, 1, 2  # BEAR_GEN_*: where a letter's concentratio
 GEN_ID_GUMBEL = 3000                 # the model id that keys the Gumbel draws (the table values are model 0)
 
 
-def _generate_checks(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, van, prior, mat, h, get_map, codes):
-    """What ``generate_steps`` and ``generate_whole`` check alike -> ``(device, rank, W, counts, n, step0, n_steps, prior, mode)``."""
+def _generate_launch(entry, table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van, prior, h, get_map, codes,
+                     mat=None, state=None):
+    """What ``generate_steps`` and ``generate_whole`` check alike, and the launch of ``entry`` with its complete argument list.
+    ``state`` = (length, stopped) says ``bear_generate_whole_f64``: it takes ``mat`` behind ``prior`` and the state behind ``left``.
+    The checked ``counts`` and ``prior`` (``_check_rows`` may have copied them) live in this frame across the launch."""
     _check_vec(table, torch.int64, "table")
     device = table.device
     rank = np.ascontiguousarray(rank, dtype=np.uint8)
@@ -855,7 +858,20 @@ def _generate_checks(table, counts, rank, lag, keys, sample, left, letters, step
     if codes is not None and not (isinstance(codes, torch.Tensor) and codes.device == device and codes.dtype == torch.int8
                                   and codes.is_contiguous() and tuple(codes.shape) == (n, int(lag))):
         raise ValueError(f"codes must be a contiguous CUDA int8 tensor [{n}, {int(lag)}] on {device}")
-    return device, rank, W, counts, n, step0, n_steps, prior, mode
+    whole = state is not None
+    if whole:
+        _check_vec(state[0], torch.int32, "length", n, device=device)
+        _check_vec(state[1], torch.uint8, "stopped", n, device=device)
+    if mat is not None:
+        if W != LINEAR_WIDE_WIDTH:
+            raise ValueError(f"mat: the linear AR function runs inside the kernel at rows of {LINEAR_WIDE_WIDTH} only")
+        if not (isinstance(mat, torch.Tensor) and mat.device == device and mat.dtype == torch.float64 and mat.is_contiguous()
+                and tuple(mat.shape) == (int(lag), W, W)):
+            raise ValueError(f"mat must be a contiguous CUDA float64 tensor [{int(lag)}, {W}, {W}] on {device}")
+    _launch(device, entry, _ptr(table), _ptr(counts), table.numel(), int(lag), W, rank.ctypes.data_as(ctypes.c_void_p), mode,
+            int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0, float(van) if mode == GEN_BMM else 0.0, _ptr(prior),
+            *([_ptr(mat)] if whole else []), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample), _ptr(left),
+            *([_ptr(state[0]), _ptr(state[1])] if whole else []), n, step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
 
 
 def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van=None, prior=None, h=None,
@@ -867,12 +883,8 @@ def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0,
     [n, L >= step0 + n_steps] receives the letter codes at columns ``step0 ..``.  The model: ``van`` (a BMM: any ``n_steps``, a whole
     flank in one launch), or ``prior`` float64 [n, W] rows of the current end k-mers (``n_steps`` 1) with ``h`` (BEAR) or without
     (the AR model, ``get_map`` only).  ``codes`` int8 [n, lag], if given, receives the new end k-mers as ``core.encode_kmers`` codes."""
-    device, rank, W, counts, n, step0, n_steps, prior, mode = _generate_checks(
-        table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, van, prior, None, h, get_map, codes)
-    _launch(device, "bear_generate_steps_f64", _ptr(table), _ptr(counts), table.numel(), int(lag), W,
-            rank.ctypes.data_as(ctypes.c_void_p), mode, int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0,
-            float(van) if mode == GEN_BMM else 0.0, _ptr(prior), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample), _ptr(left), n,
-            step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
+    _generate_launch("bear_generate_steps_f64", table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van, prior,
+                     h, get_map, codes)
 
 
 def generate_whole(table, counts, rank, lag, keys, sample, left, length, stopped, letters, step0, n_steps, seed, van=None, prior=None,
@@ -885,20 +897,8 @@ def generate_whole(table, counts, rank, lag, keys, sample, left, length, stopped
     two with ``h`` (BEAR) or without (the AR model, ``get_map`` only)."""
     if prior is not None and mat is not None:
         raise ValueError("prior rows or mat: one source of the AR function's rows")
-    device, rank, W, counts, n, step0, n_steps, prior, mode = _generate_checks(
-        table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, van, prior, mat, h, get_map, codes)
-    _check_vec(length, torch.int32, "length", n, device=device)
-    _check_vec(stopped, torch.uint8, "stopped", n, device=device)
-    if mat is not None:
-        if W != LINEAR_WIDE_WIDTH:
-            raise ValueError(f"mat: the linear AR function runs inside the kernel at rows of {LINEAR_WIDE_WIDTH} only")
-        if not (isinstance(mat, torch.Tensor) and mat.device == device and mat.dtype == torch.float64 and mat.is_contiguous()
-                and tuple(mat.shape) == (int(lag), W, W)):
-            raise ValueError(f"mat must be a contiguous CUDA float64 tensor [{int(lag)}, {W}, {W}] on {device}")
-    _launch(device, "bear_generate_whole_f64", _ptr(table), _ptr(counts), table.numel(), int(lag), W,
-            rank.ctypes.data_as(ctypes.c_void_p), mode, int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0,
-            float(van) if mode == GEN_BMM else 0.0, _ptr(prior), _ptr(mat), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample),
-            _ptr(left), _ptr(length), _ptr(stopped), n, step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
+    _generate_launch("bear_generate_whole_f64", table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van, prior,
+                     h, get_map, codes, mat=mat, state=(length, stopped))
 
 
 def shuffle_rows(src, seed):

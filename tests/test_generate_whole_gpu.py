@@ -110,16 +110,26 @@ def test_any_cut_of_the_steps_gives_the_same_bytes(case, dev):
     assert_equals_replica(whole, w.expected(case), case)
 
 
-@pytest.mark.parametrize("case", [("prot", 5, "bmm"), ("dna", 21, "bmm")], ids=lambda c: "-".join(map(str, c)))
-def test_letters_are_those_of_generate_steps(case, dev):
-    """The prefix property on the device: kernels.generate_steps from the same keys with ``left = length`` writes the same letters."""
+@pytest.mark.parametrize("case,n_seq", [(("prot", 5, "bmm"), w.N_SEQ), (("dna", 21, "bmm"), w.N_SEQ), (("dna", 1, "bmm"), 65),
+                                        (("prot", 12, "bmm"), 65)],
+                         ids=["prot-5-bmm", "dna-21-bmm", "dna-1-bmm-65", "prot-12-bmm-65"])
+def test_letters_are_those_of_generate_steps(case, n_seq, dev):
+    """The prefix property on the device: kernels.generate_steps from the same keys with ``left = length`` writes the same letters.
+    The shortest and the longest key run 65 sequences: one more than a block of generate_steps_kernel holds at 4 lanes a sequence,
+    a partly filled last group at 32."""
     import torch
     from bear_amd import kernels
     inputs, kw = w.case_inputs(case)
-    got = run_case(case, dev)
-    keys, sample = _i64(inputs["starts"], dev), _i64(inputs["sample"], dev)
+    sample = np.arange(n_seq, dtype=np.uint64) * np.uint64(3) + np.uint64(7)
+    assert np.array_equal(sample[:w.N_SEQ], inputs["sample"])
+    got = run_case(case, dev, n_seq=n_seq, sample=sample)
+    if n_seq != w.N_SEQ:
+        want = w.run_replica(case, n_seq=n_seq, sample=sample)
+        assert want["gap"] > g.MIN_GAP
+        assert_equals_replica(got, want, case)
+    keys, sample = _i64(w.start_keys(n_seq, inputs["rank"], inputs["lag"]), dev), _i64(sample, dev)
     left = torch.from_numpy(got["length"].copy()).to(dev)
-    letters = torch.full((w.N_SEQ, L), 0xFF, dtype=torch.uint8, device=dev)
+    letters = torch.full((n_seq, L), 0xFF, dtype=torch.uint8, device=dev)
     kernels.generate_steps(_i64(inputs["table"], dev), torch.from_numpy(inputs["counts"].copy()).to(dev), inputs["rank"], inputs["lag"],
                            keys, sample, left, letters, 0, L, inputs["seed"], **kw)
     assert np.array_equal(letters.cpu().numpy(), got["letters"]) and got["length"].max() > 0

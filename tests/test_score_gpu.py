@@ -147,6 +147,53 @@ def test_score_sum_against_a_sequential_sum(sum_case, W, M, S):
     assert np.array_equal(moved, got[order])
 
 
+LONG_LENS = [5, 2049, 4097, 0, 2049, 1]      # starts 0, 5, 2054, 6151, 6151, 8200: text block 1 (positions 2048 .. 4095) holds the
+#                                              second chunk of segment 1 (slot 2 g) AND chunk 0 of segment 2 (slot 2 g + 1); segment 4
+#                                              starts directly behind an empty one
+
+
+@pytest.mark.parametrize("W", [5, 21])
+@pytest.mark.parametrize("M,S", [(1, 1), (2, 33)])
+def test_score_sum_of_long_segments_bit_for_bit(W, M, S):
+    """The order of a long segment's sum is fully specified: every chunk of SCORE_CHUNK transitions front to back from 0.0, then the
+    chunks' sums in order from 0.0, plain fp64 adds.  A NumPy sum in that order equals the device bytes, wherever the segment stands."""
+    assert kernels.SCORE_CHUNK == 2048
+    K = 37
+    rng = np.random.default_rng(W * 1000 + M * S)
+    n_t = sum(LONG_LENS)
+    rows = rng.integers(0, K, size=n_t).astype(np.int32)
+    rows[rng.random(n_t) < 0.01] = -1
+    letters = np.where(rng.random(n_t) < 0.1, 0xFF, (rng.random(n_t) * W).astype(np.int64)).astype(np.uint8)
+    lp = -rng.exponential(3.0, size=(K, W, M, S))
+    seg = np.concatenate([[0], np.cumsum(LONG_LENS)]).astype(np.int64)
+    assert seg.tolist() == [0, 5, 2054, 6151, 6151, 8200, 8201]
+
+    def chunk_sum(a, b):
+        acc = np.zeros((M, S))
+        for t in range(a, b):
+            if letters[t] != 0xFF and rows[t] >= 0:
+                acc = acc + lp[rows[t], letters[t]]
+        return acc
+    want = []
+    for a, b in zip(seg[:-1], seg[1:]):
+        if b - a <= kernels.SCORE_CHUNK:
+            want.append(chunk_sum(a, b))
+        else:
+            acc = np.zeros((M, S))
+            for c in range(a, b, kernels.SCORE_CHUNK):
+                acc = acc + chunk_sum(c, min(c + kernels.SCORE_CHUNK, b))
+            want.append(acc)
+    got = kernels.score_sum(_dev(lp), _dev(rows), _dev(letters), _dev(seg)).cpu().numpy()
+    for i in range(len(LONG_LENS)):
+        assert np.array_equal(got[i], want[i]), (i, LONG_LENS[i], float(np.abs(got[i] - want[i]).max()))
+    for order in ([2, 4, 1, 0, 5, 3], [5, 4, 3, 2, 1, 0]):
+        idx = np.concatenate([np.arange(seg[i], seg[i + 1]) for i in order])
+        seg2 = np.concatenate([[0], np.cumsum([LONG_LENS[i] for i in order])]).astype(np.int64)
+        moved = kernels.score_sum(_dev(lp), _dev(rows[idx]), _dev(letters[idx]), _dev(seg2)).cpu().numpy()
+        for j, i in enumerate(order):
+            assert np.array_equal(moved[j], want[i]), (order, i)
+
+
 def test_score_sum_edges():
     lp = _dev(-np.ones((3, 5, 2, 2)))
     none = torch.empty(0, dtype=torch.int32, device="cuda"), torch.empty(0, dtype=torch.uint8, device="cuda")
