@@ -225,8 +225,38 @@ def _any_left(left):
     return bool(left.any().item())
 
 
+def _generate_ref(model, counter, ref_counter, state, max_len, seed, h, get_map, stepwise):
+    """``generate_sequences`` under a bear_ref model (``kernels.generate_whole_ref`` over ``state``, ``generate_whole``'s): the stop
+    net function and the fused protein linear one in one launch, the mixing and the net function inside the kernel; otherwise (or
+    ``stepwise``) the net function's rows and one launch per step, looking every 16 steps whether anything is left."""
+    import torch
+    from . import kernels
+    table, counts, rank, lag, keys, sample, left = state[:7]
+    W, device = counter.width, counter.device
+    ref = (ref_counter.keys, ref_counter.counts_by_key if ref_counter.keys.numel() else None)
+    args = (table, counts, *ref, *state[2:])
+    kw = dict(h=h, get_map=get_map)
+    net = model.net_func
+    mat = getattr(net, "linear_mat", None)
+    if not stepwise and net is None:
+        kernels.generate_whole_ref(*args, 0, max_len, seed, model.tau, model.net_weight, **kw)
+    elif not stepwise and mat is not None and getattr(net, "fused", False) and W == kernels.LINEAR_WIDE_WIDTH and mat.device == device:
+        kernels.generate_whole_ref(*args, 0, max_len, seed, model.tau, model.net_weight, mat=mat.detach().contiguous(), **kw)
+    else:
+        kmer_codes = counter.codes_of_keys(keys)
+        stop_rows = None
+        if net is None:             # the stop net function as rows: the one-hot at the stop
+            stop_rows = torch.zeros((keys.numel(), W), dtype=torch.float64, device=device)
+            stop_rows[:, -1] = 1.0
+        for t in range(max_len):
+            g = stop_rows if net is None else model.net_rows(kmer_codes)
+            kernels.generate_whole_ref(*args, t, 1, seed, model.tau, model.net_weight, net_rows=g, codes=kmer_codes, **kw)
+            if (t + 1) % 16 == 0 and t + 1 < max_len and not _any_left(left):
+                break
+
+
 def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=None, h=None, van=None, get_map=False, prompts=None,
-                       seed=None, save_folder=None, stepwise=False):
+                       seed=None, save_folder=None, stepwise=False, ref_model=None, ref_counter=None):
     """Whole sequences from the model over ``counter`` (a ``get_var_probs.DeviceCounter`` counted WITH ends; its lag and alphabet
     are the model's) -> ``(seqs, stopped)``, both ``[len(prompts), num_to_gen]``: every prompt (strings over the alphabet, shorter
     than the lag or empty if need be; default one empty prompt, the start of a sequence) continued ``num_to_gen`` times, the
@@ -240,7 +270,14 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
     call and one launch per step, looking every 16 steps whether any sequence is still growing; the linear AR function of the
     protein alphabet (``make_ar_func_linear(lag, 20)``: ``linear_mat``, ``fused``) runs inside the kernel instead, one launch for
     everything, unless ``stepwise``.  ``ValueError`` before any launch: a ``no_end`` counter (its stop column is zeroed), a prompt
-    character outside the alphabet, ``max_len < 0``, no model or more than one.  ``save_folder`` receives ``seqs.fa``."""
+    character outside the alphabet, ``max_len < 0``, no model or more than one.  ``save_folder`` receives ``seqs.fa``.
+
+    ``ref_model=`` (a ``get_var_probs.RefModel`` or a folder of ``train_bear_ref.py``) with ``ref_counter=`` (the ``DeviceCounter`` of
+    the reference column) is a model trained by ``bear_ref``: the reference mixing runs inside the kernel
+    (``kernels.generate_whole_ref``), so the stop net function -- the standard configuration -- and the protein linear one take one
+    launch for everything; any other net function, or ``stepwise``, one net call and one launch per step.  ``h`` defaults to the
+    model's.  ``ValueError`` before any launch: only one of the two, a counter of another lag or alphabet than the model's, a
+    ``no_end`` reference counter, another model (``van``, ``bear_path``, ``ar_func``) beside them."""
     import torch
     from . import kernels
     from .log_gamma import _next_seed
@@ -248,8 +285,9 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
         raise TypeError("generate_sequences runs on the device only: counter must be a get_var_probs.DeviceCounter")
     if counter.no_end:
         raise ValueError("a no_end counter has its stop column zeroed: no sequence would ever end")
-    if (van is not None) + (bear_path is not None) + (ar_func is not None) != 1:
-        raise ValueError("exactly one model: van=... (a BMM), bear_path=... or ar_func=... with h=...")
+    ref_model = get_var_probs._ref_setup(ref_model, ref_counter, counter, dict(van=van, bear_path=bear_path, ar_func=ar_func))
+    if (van is not None) + (bear_path is not None) + (ar_func is not None) + (ref_model is not None) != 1:
+        raise ValueError("exactly one model: van=... (a BMM), bear_path=..., ar_func=... with h=... or ref_model=... with ref_counter=...")
     if ar_func is not None and h is None and not get_map:
         raise ValueError("ar_func needs h (the AR model alone is a table only at its MAP value: get_map=True)")
     num_to_gen, max_len = int(num_to_gen), int(max_len)
@@ -265,6 +303,8 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
         if (lag_b, name_b) != (lag, name):
             raise ValueError(f"counter: a lag-{lag} table of {name!r}, the model at {bear_path!r} has lag {lag_b} of {name_b!r}")
         h = h_b if h is None else h
+    if ref_model is not None:
+        h = ref_model.h if h is None else h
     n_total = len(prompts) * num_to_gen
     seed = _next_seed() if seed is None else seed
     starts = np.frombuffer("".join(("[" * lag + p)[-lag:] for p in prompts).encode("ascii"), dtype=np.uint8)
@@ -280,6 +320,8 @@ def generate_sequences(counter, num_to_gen, max_len, bear_path=None, ar_func=Non
         mat = getattr(ar_func, "linear_mat", None)
         if n_total == 0:
             pass
+        elif ref_model is not None:
+            _generate_ref(ref_model, counter, ref_counter, state, max_len, seed, None if get_map else float(h), get_map, stepwise)
         elif ar_func is None:
             kernels.generate_whole(*state, 0, max_len, seed, van=float(van), get_map=get_map)
         elif not stepwise and mat is not None and getattr(ar_func, "fused", False) and W == kernels.LINEAR_WIDE_WIDTH and mat.device == device:

@@ -2,9 +2,11 @@
 // (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
 // of a sampled table's rows over the transitions of every segment; the exact marginal of every segment, which needs no table -- and
 // sequence generation over the same key tables ("Sequence generation": flanks of given lengths, and whole sequences from start to
-// stop).  The only unit that includes -- and so emits --
-// kernels_score.h, kernels_marg.h and kernels_generate.h.
+// stop) -- and, for bear_ref models, the reference-mixed prior rows of queried k-mers and whole sequences under such a model.
+// The only unit that includes -- and so emits --
+// kernels_score.h, kernels_marg.h, kernels_refscore.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -12,6 +14,7 @@
 #include "bear_release_guard.h"
 #include "kernels_generate.h"
 #include "kernels_marg.h"
+#include "kernels_refscore.h"
 #include "kernels_score.h"
 
 namespace {
@@ -33,7 +36,7 @@ unsigned scr_grid(uint64_t work, uint64_t per_block) {
       hipLaunchKernelGGL(k21, grid, block, lds, stream, __VA_ARGS__);               \
   } while (0)
 
-// What the two generation entries check before any device call, and their argument block.  has_f: rows of the AR function are at
+// What the generation entries check before any device call, and their argument block.  has_f: rows of the AR function are at
 // hand (prior rows, or mat for the kernel to form them); per_step: they are prior rows, those of the CURRENT end k-mers.
 bool gen_prepare(int lag, int width, const uint8_t *rank, int mode, int map, double h, double van, bool has_f, bool per_step,
                  uint64_t n_table, uint64_t seed, uint64_t step0, uint64_t n_steps, uint64_t letters_stride, gen_args &A) {
@@ -97,6 +100,7 @@ int gen_launch(int width, const uint64_t *table, const uint32_t *counts, uint64_
   HIP_TRY(hipGetLastError());
   return BEAR_OK;
 }
+
 }  // namespace
 
 extern "C" {
@@ -237,6 +241,88 @@ int bear_generate_whole_f64(const uint64_t *table, const uint32_t *counts, uint6
       !stopped || misaligned4(length) || (mat && misaligned8(mat)))
     return BEAR_ERR_INVALID_ARG;
   return gen_launch<true>(width, table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes, stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ bear_ref models downstream of training
+namespace {
+// The mixing constants of a bear_ref model from its two scalars, on the host: E = exp(-tau), V = 1 / (nw + 1).  False: tau or nw not
+// finite and > 0, or eps not finite and >= 0.
+bool ref_params(double tau, double net_weight, double eps, bear_params &prm) {
+  if (!(isfinite(tau) && tau > 0.0 && isfinite(net_weight) && net_weight > 0.0 && isfinite(eps) && eps >= 0.0)) return false;
+  memset(&prm, 0, sizeof(prm));
+  prm.eps = eps;
+  prm.tau = tau;
+  prm.E = exp(-tau);
+  prm.tauE = tau * prm.E;
+  prm.nw = net_weight;
+  prm.V = 1.0 / (net_weight + 1.0);
+  return true;
+}
+
+// ... and generate_whole_kernel's launch for generate_whole_ref_kernel
+int gen_launch_ref(int width, const uint64_t *table, const uint32_t *counts, uint64_t n_table, const double *prior, const double *mat,
+                   uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
+                   const gen_args &A, uint8_t *letters, int8_t *codes, const gen_ref_args &ref, void *stream) {
+  if (A.n_steps == 0 && !codes) return BEAR_OK;
+  unsigned grid = scr_grid(n_seq, GEN_THREADS / GEN_GROUP(width));
+  if (mat && grid > GEN_WHOLE_MAT_BLOCKS) grid = GEN_WHOLE_MAT_BLOCKS;
+  LAUNCH_BY_WIDTH(width, (generate_whole_ref_kernel<3, 5>), (generate_whole_ref_kernel<5, 21>), dim3(grid), dim3(GEN_THREADS),
+                  mat ? GEN_WHOLE_MAT_LDS(A.lag) : 0, static_cast<hipStream_t>(stream), table, counts, n_table, prior, mat, keys, sample, left,
+                  length, stopped, n_seq, A, letters, codes, ref);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int bear_ref_prior_rows_f64(const uint64_t *ref_table, const uint32_t *ref_counts, uint64_t n_ref, int width, const uint64_t *query,
+                            uint64_t n_query, const double *net_rows, double tau, double net_weight, double eps, double *prior,
+                            void *stream) {
+  if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
+  bear_params prm;
+  if (!ref_params(tau, net_weight, eps, prm)) return BEAR_ERR_INVALID_ARG;
+  if (n_ref >= SCR_ABSENT || n_query > (~0ull) / sizeof(double) / (uint64_t)width) return BEAR_ERR_INVALID_ARG;
+  if (n_ref && (!ref_table || !ref_counts || misaligned8(ref_table) || misaligned4(ref_counts))) return BEAR_ERR_INVALID_ARG;
+  if (n_query == 0) return BEAR_OK;
+  if (!query || !prior || misaligned8(query) || misaligned8(prior) || (net_rows && misaligned8(net_rows))) return BEAR_ERR_INVALID_ARG;
+  const dim3 grid(scr_grid(n_query, SCR_THREADS)), block(SCR_THREADS);
+  LAUNCH_BY_WIDTH(width, ref_prior_rows_kernel<5>, ref_prior_rows_kernel<21>, grid, block, 0, static_cast<hipStream_t>(stream), ref_table,
+                  ref_counts, n_ref, query, n_query, net_rows, prm, prior);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+int bear_generate_whole_ref_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
+                                int mode, int map, double h, double van, const double *prior, const double *mat, uint64_t seed,
+                                uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
+                                uint64_t step0, uint64_t n_steps, uint8_t *letters, uint64_t letters_stride, int8_t *codes,
+                                const uint64_t *ref_table, const uint32_t *ref_counts, uint64_t n_ref, double tau, double net_weight,
+                                double eps, int net, void *stream) {
+  if (mode != BEAR_GEN_BEAR && mode != BEAR_GEN_AR) return BEAR_ERR_INVALID_ARG;       // a BMM has no AR function to mix
+  // the one source of the net function's rows that `net` names, and no other
+  if (net != BEAR_GEN_NET_STOP && net != BEAR_GEN_NET_ROWS && net != BEAR_GEN_NET_MAT) return BEAR_ERR_INVALID_ARG;
+  if ((prior != nullptr) != (net == BEAR_GEN_NET_ROWS) || (mat != nullptr) != (net == BEAR_GEN_NET_MAT)) return BEAR_ERR_INVALID_ARG;
+  if (mat && width != 21) return BEAR_ERR_INVALID_ARG;
+  gen_ref_args ref;
+  memset(&ref, 0, sizeof(ref));
+  if (!ref_params(tau, net_weight, eps, ref.prm) || n_ref >= SCR_ABSENT) return BEAR_ERR_INVALID_ARG;
+  gen_args A;
+  if (!gen_prepare(lag, width, rank, mode, map, h, van, true, prior != nullptr, n_table, seed, step0, n_steps, letters_stride, A))
+    return BEAR_ERR_INVALID_ARG;
+  if (n_seq == 0) return BEAR_OK;
+  if (!gen_pointers_ok(table, counts, n_table, prior, keys, sample, left, n_seq, n_steps, letters, letters_stride) || !length ||
+      !stopped || misaligned4(length) || (mat && misaligned8(mat)) ||
+      (n_ref && (!ref_table || !ref_counts || misaligned8(ref_table) || misaligned4(ref_counts))))
+    return BEAR_ERR_INVALID_ARG;
+  ref.table = ref_table;
+  ref.counts = ref_counts;
+  ref.n_table = n_ref;
+  ref.net = net;
+  return gen_launch_ref(width, table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes, ref,
+                        stream);
 }
 
 }  // extern "C"

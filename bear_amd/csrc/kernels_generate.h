@@ -7,10 +7,12 @@
 // array, because it cannot draw the same row again later.  Here a table value is a pure function of (seed, sequence's sample index,
 // k-mer key, letter): a sequence that returns to a k-mer forms the same row again, and nothing is stored.
 //
-// ONE body, gen_run<BITS, W, STOP>, under two kernels.  generate_steps_kernel (STOP = false) grows flanks of given lengths and never
+// ONE body, gen_run<BITS, W, STOP, Ref...>, under three kernels.  generate_steps_kernel (STOP = false) grows flanks of given lengths and never
 // draws the stop: the NL = W - 1 letters take part.  generate_whole_kernel (STOP = true) draws over all NL = W letters -- the stop
 // b = W - 1 is a letter like the others (same two streams, so a cell b < W - 1 holds bit for bit the value it holds without the
-// stop) -- and a sequence ends when it wins (assemble.generate_sequences).
+// stop) -- and a sequence ends when it wins (assemble.generate_sequences).  generate_whole_ref_kernel (STOP and REF) is that kernel
+// under a bear_ref model: the AR function's row of the end k-mer is the reference-mixed row of kernels_refscore.h, formed inside
+// the step from the k-mer's row in a second key table, the reference column's.
 //
 // Lane mapping: the letters of one sequence sit on neighbouring lanes, GEN_GROUP(NL) lanes per sequence -- 4 and 8 at W = 5 (every
 // lane a letter; three lanes of the 8 only take part in the exchange), 32 at W = 21.  Per step the first lane of a group finds the
@@ -19,6 +21,7 @@
 // other (and hold them all in registers: the 169 VGPRs of logdir_sample_kernel<21>).
 // No atomics and no sum across lanes: the letters are the same in both libraries and for any cut of the steps into launches.
 #pragma once
+#include "kernels_refscore.h"   // rfs_ref_row, rfs_prior_cell: the reference-mixed row of generate_whole_ref_kernel
 #include "kernels_score.h"   // scr_ranks, scr_find_row: keys are those of bear_score_transitions_u64
 #include "rows_wide_common.h"   // LNW_W, LNW_MAT, lnw_forward_row: the linear AR function's row inside generate_whole_kernel<5, 21>
 #include "sample_common.h"
@@ -73,12 +76,31 @@ static_assert(GEN_WHOLE_MAT_LDS(12) <= 64 * 1024, "generate_whole_kernel with ma
 // there, every lane reads its own entry back.  A group lies inside one wave, whose LDS accesses complete in order: the hand-over
 // needs no barrier, only that the compiler keeps the order (the wave-scope fences).
 // Every loop runs the same number of times on all lanes of a wave (a finished sequence idles), so each exchange finds its group whole.
-template <int BITS, int W, bool STOP>
+//
+// REF (with STOP): a bear_ref model.  What prior or mat yields -- or, with neither (net 0), the one-hot at the stop -- is the NET
+// function's row g, and f_b = rfs_prior_cell(ref row of the end k-mer, b, g_b): the group's first lane finds the row in ref_table
+// as it finds the train row and hands both round, every letter lane forms R = rfw_ref_total of that row itself -- the same
+// loads in the same order, so all lanes hold the same bits and nothing is summed across lanes -- and then its own cell.
+struct gen_ref_args {
+  const uint64_t *table;       // the reference column's ascending distinct keys
+  const uint32_t *counts;      // ... and their count rows in that order (an absent k-mer: rfs_zero_row)
+  uint64_t n_table;
+  int net;                     // BEAR_GEN_NET_STOP / _ROWS / _MAT (include/bear_hip.h)
+  bear_params prm;             // E, nw, V, eps (host values)
+};
+
+// (The reference arguments are a parameter pack -- empty, or one gen_ref_args -- and everything REF adds sits in one block of its
+// own, so that without them the body is, token for token, the one generate_steps_kernel and generate_whole_kernel had before.)
+__device__ __forceinline__ const gen_ref_args &gen_ref_of(const gen_ref_args &ref) { return ref; }
+
+template <int BITS, int W, bool STOP, class... Ref>
 __device__ __forceinline__ void gen_run(const uint64_t *__restrict__ table, const uint32_t *__restrict__ counts, uint64_t n_table,
                                         const double *__restrict__ prior, const double *__restrict__ mat, uint64_t *__restrict__ keys,
                                         const uint64_t *__restrict__ sample, uint32_t *__restrict__ left, uint32_t *__restrict__ length,
                                         uint8_t *__restrict__ stopped, uint64_t n_seq, const gen_args &A, uint8_t *__restrict__ letters,
-                                        int8_t *__restrict__ codes) {
+                                        int8_t *__restrict__ codes, const Ref &...ref_args) {
+  constexpr bool REF = sizeof...(Ref) == 1;
+  static_assert(sizeof...(Ref) <= 1 && (STOP || !REF), "a reference model generates whole sequences only");
   constexpr int NL = STOP ? W : W - 1;                           // the letters that are drawn
   constexpr int G = GEN_GROUP(NL);
   constexpr uint32_t PER_BLOCK = GEN_THREADS / G;
@@ -126,10 +148,22 @@ __device__ __forceinline__ void gen_run(const uint64_t *__restrict__ table, cons
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // ... before the next step's row overwrites it
         }
       }
+      if constexpr (REF) {     // f (so far the net function's row g, or nothing) becomes the reference-mixed row
+        const gen_ref_args &ref = gen_ref_of(ref_args...);
+        uint32_t ref_row = SCR_ABSENT;
+        if (live && b == 0) ref_row = scr_find_row(ref.table, ref.n_table, q);
+        ref_row = (uint32_t)__shfl((int)ref_row, 0, G);
+        if (live && b < NL) {
+          const uint32_t *rf = rfs_ref_row<W>(ref.counts, ref_row);
+          const double Rt = rfw_ref_total<W>(rf, ref.prm.eps);
+          const double gb = ref.net == BEAR_GEN_NET_STOP ? (b == (uint32_t)(W - 1) ? 1.0 : 0.0) : (prior ? prior[i * W + b] : f);
+          f = rfs_prior_cell<W>(rf, (int)b, gb, Rt, 1.0 / Rt, ref.prm);
+        }
+      }
       double v = -INFINITY;
       if (live && b < NL) {
         const double c = row != SCR_ABSENT ? (double)counts[(uint64_t)row * W + b] : 0.0;
-        if (prior) f = prior[i * W + b];                           // (never beside mat: the entry refuses the two together)
+        if (!REF && prior) f = prior[i * W + b];                   // (never beside mat: the entry refuses the two together)
         const double conc = A.mode == BEAR_GEN_BMM ? A.van + c : (A.mode == BEAR_GEN_BEAR ? __builtin_fma(f, A.inv_h, c) : f);
         const double tv = A.map ? log(conc) : smp_log_gamma(conc, smp_cell_key(A.seed, 0u, s, mix64(q) + b));
         v = tv - log(-log(u01(smp_cell_key(A.seed, GEN_ID_GUMBEL, s, t * W + b))));
@@ -171,7 +205,8 @@ __device__ __forceinline__ void gen_run(const uint64_t *__restrict__ table, cons
   }
 }
 
-// The two kernels: each carries the arguments its body reads and nothing else (no LDS, length, stopped or mat without STOP).
+// The three kernels: each carries the arguments its body reads and nothing else (no LDS, length, stopped or mat without STOP; the
+// reference column and the mixing constants with REF only).
 template <int BITS, int W>
 __global__ __launch_bounds__(GEN_THREADS) void generate_steps_kernel(const uint64_t *__restrict__ table,
                                                                      const uint32_t *__restrict__ counts, uint64_t n_table,
@@ -191,4 +226,16 @@ __global__ __launch_bounds__(GEN_THREADS) void generate_whole_kernel(const uint6
                                                                      uint8_t *__restrict__ stopped, uint64_t n_seq, gen_args A,
                                                                      uint8_t *__restrict__ letters, int8_t *__restrict__ codes) {
   gen_run<BITS, W, true>(table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes);
+}
+
+template <int BITS, int W>
+__global__ __launch_bounds__(GEN_THREADS) void generate_whole_ref_kernel(const uint64_t *__restrict__ table,
+                                                                         const uint32_t *__restrict__ counts, uint64_t n_table,
+                                                                         const double *__restrict__ prior, const double *__restrict__ mat,
+                                                                         uint64_t *__restrict__ keys, const uint64_t *__restrict__ sample,
+                                                                         uint32_t *__restrict__ left, uint32_t *__restrict__ length,
+                                                                         uint8_t *__restrict__ stopped, uint64_t n_seq, gen_args A,
+                                                                         uint8_t *__restrict__ letters, int8_t *__restrict__ codes,
+                                                                         gen_ref_args ref) {
+  gen_run<BITS, W, true>(table, counts, n_table, prior, mat, keys, sample, left, length, stopped, n_seq, A, letters, codes, ref);
 }

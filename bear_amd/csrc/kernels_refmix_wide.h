@@ -30,7 +30,7 @@
 #include "bear_common.h"
 #include "kernels_rows.h"
 #include "kernels_wide.h"
-#include "rows_wide_common.h"   // wide_nz_mask, wide_store_tile
+#include "rows_wide_common.h"   // wide_nz_mask, wide_store_tile; rfw_ref_total, rfw_dev, rfw_mix_cell (shared with the scoring unit)
 
 #define RFW_THREADS 256
 // dm_ref_wide_kernel, W = 21: 256 contexts = two count tiles of 21 KiB (+ 2 KiB log table): a context on every thread, three blocks
@@ -42,43 +42,6 @@
 #define RMW_TILE(W) ((W) > 8 ? 128 : 512)
 #define RMW_BLOCKS_PER_CU 3
 
-// R = sum of the letters' r_b = ref_b + eps over a row whose stop entry is zero, added in the order NumPy's add.reduce takes over W
-// contiguous doubles: below 8 entries one after the other; else eight running sums over the whole blocks of eight, combined pairwise,
-// then the rest one after the other.  (The zero of the stop column changes no partial sum: r >= 0.)
-template <int W>
-__device__ __forceinline__ double rfw_ref_total(const uint32_t *ref, double eps) {
-  constexpr int A = W - 1;
-  if (W < 8) {
-    double s = (double)ref[0] + eps;
-#pragma unroll
-    for (int b = 1; b < A; ++b) s += (double)ref[b] + eps;
-    return s;
-  }
-  constexpr int FULL = W - W % 8;
-  double q[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) q[j] = j < A ? (double)ref[j] + eps : 0.0;
-#pragma unroll
-  for (int i = 8; i < FULL; i += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (i + j < A) q[j] += (double)ref[i + j] + eps;
-  double s = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
-#pragma unroll
-  for (int i = FULL; i < A; ++i) s += (double)ref[i] + eps;
-  return s;
-}
-
-// dev = r / R - 1/A with the quotient rounded as the division rounds it: q = r invR (invR = 1 / R correctly rounded) is within an
-// ulp, the remainder r - q R is exact in one fma, and one step on it gives the rounded quotient -- three instructions instead of a
-// division sequence per cell.  The subtraction is not fused (the Makefile's -ffp-contract=off).
-template <int W>
-__device__ __forceinline__ double rfw_dev(double r, double R, double invR) {
-  const double q = r * invR;
-  const double q1 = __builtin_fma(__builtin_fma(-q, R, r), invR, q);
-  return q1 - 1.0 / (W - 1);
-}
-
 // sum_b dev_b over the letters (all W cells: dev of the stop column is zero)
 template <int W>
 __device__ __forceinline__ double rfw_dev_total(const uint32_t *ref, double eps, double R, double invR) {
@@ -86,22 +49,6 @@ __device__ __forceinline__ double rfw_dev_total(const uint32_t *ref, double eps,
 #pragma unroll
   for (int b = 0; b < W - 1; ++b) s += rfw_dev<W>((double)ref[b] + eps, R, invR);
   return s;
-}
-
-// cell b of a row whose net entry is g: f_b, d f_b / d tau_signed, d f_b / d nu_signed
-struct rfw_cell {
-  double f, dft, dfn;
-};
-template <int W>
-__device__ __forceinline__ rfw_cell rfw_mix_cell(const uint32_t *ref, int b, double g, double R, double invR, const bear_params &prm) {
-  const bool letter = b < W - 1;
-  const double dev = letter ? rfw_dev<W>((double)ref[b] + prm.eps, R, invR) : 0.0;
-  const double jc = __builtin_fma(prm.E, dev, letter ? 1.0 / (W - 1) : 0.0);
-  rfw_cell o;
-  o.f = __builtin_fma(prm.nw, g, jc) * prm.V;
-  o.dft = -prm.tauE * dev * prm.V;
-  o.dfn = prm.nw * (g - o.f) * prm.V;
-  return o;
 }
 
 // c log p of the multinomial mode, as dm_wide_kernel forms it (near p = 1 -- the stop entry under a large net weight -- the

@@ -3,7 +3,9 @@
 // sparse item walk, wide_dm_row), a tile of fp64 rows out of LDS (wide_store_tile), a tile's int8 code bytes into LDS
 // (wide_stage_codes), the rows of a partials buffer (WIDE_PARTIAL_ROWS), the fixed-order sum over them (lnw_sum_partials) and the
 // forward row of the linear function (lnw_forward_row: kernels_linrows_wide.h, kernels_linear_wide.h and, in the unit
-// bear_score.hip, kernels_generate.h).  The steps of the linear function that need its MFMA geometry (lnw_softmax_back_row,
+// bear_score.hip, kernels_generate.h) and the reference mixing of one row (rfw_ref_total, rfw_dev, rfw_mix_cell:
+// kernels_refmix_wide.h and, in bear_score.hip, kernels_refscore.h and kernels_generate.h).  The steps of the linear function
+// that need its MFMA geometry (lnw_softmax_back_row,
 // lnw_own_rows, lnw_onehot_product, lnw_store_acc) sit at the top of kernels_linrows_wide.h.  No kernels here.
 #pragma once
 #include "bear_common.h"
@@ -82,6 +84,63 @@ __device__ __forceinline__ void wide_dm_row(const uint32_t *c, const double *f, 
     acc[0] += ll;
     acc[1] -= dh * prm.inv_h;  // d alpha_b / d h_signed = -f_b / h
   }
+}
+
+// ------------------------------------------------------------------ the reference mixing of one row at width W
+// bear_ref's prior row f = (nw g + jukes_cantor(ref, tau)) / (nw + 1) cell by cell (the formulas: kernels_refmix_wide.h), for the
+// training kernels there and, in the unit bear_score.hip, for the rows of queried k-mers (kernels_refscore.h) and the generation
+// step (kernels_generate.h).
+// R = sum of the letters' r_b = ref_b + eps over a row whose stop entry is zero, added in the order NumPy's add.reduce takes over W
+// contiguous doubles: below 8 entries one after the other; else eight running sums over the whole blocks of eight, combined pairwise,
+// then the rest one after the other.  (The zero of the stop column changes no partial sum: r >= 0.)
+template <int W>
+__device__ __forceinline__ double rfw_ref_total(const uint32_t *ref, double eps) {
+  constexpr int A = W - 1;
+  if (W < 8) {
+    double s = (double)ref[0] + eps;
+#pragma unroll
+    for (int b = 1; b < A; ++b) s += (double)ref[b] + eps;
+    return s;
+  }
+  constexpr int FULL = W - W % 8;
+  double q[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] = j < A ? (double)ref[j] + eps : 0.0;
+#pragma unroll
+  for (int i = 8; i < FULL; i += 8)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (i + j < A) q[j] += (double)ref[i + j] + eps;
+  double s = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+#pragma unroll
+  for (int i = FULL; i < A; ++i) s += (double)ref[i] + eps;
+  return s;
+}
+
+// dev = r / R - 1/A with the quotient rounded as the division rounds it: q = r invR (invR = 1 / R correctly rounded) is within an
+// ulp, the remainder r - q R is exact in one fma, and one step on it gives the rounded quotient -- three instructions instead of a
+// division sequence per cell.  The subtraction is not fused (the Makefile's -ffp-contract=off).
+template <int W>
+__device__ __forceinline__ double rfw_dev(double r, double R, double invR) {
+  const double q = r * invR;
+  const double q1 = __builtin_fma(__builtin_fma(-q, R, r), invR, q);
+  return q1 - 1.0 / (W - 1);
+}
+
+// cell b of a row whose net entry is g: f_b, d f_b / d tau_signed, d f_b / d nu_signed
+struct rfw_cell {
+  double f, dft, dfn;
+};
+template <int W>
+__device__ __forceinline__ rfw_cell rfw_mix_cell(const uint32_t *ref, int b, double g, double R, double invR, const bear_params &prm) {
+  const bool letter = b < W - 1;
+  const double dev = letter ? rfw_dev<W>((double)ref[b] + prm.eps, R, invR) : 0.0;
+  const double jc = __builtin_fma(prm.E, dev, letter ? 1.0 / (W - 1) : 0.0);
+  rfw_cell o;
+  o.f = __builtin_fma(prm.nw, g, jc) * prm.V;
+  o.dft = -prm.tauE * dev * prm.V;
+  o.dfn = prm.nw * (g - o.f) * prm.V;
+  return o;
 }
 
 // ------------------------------------------------------------------ the forward row of the linear function at width 21

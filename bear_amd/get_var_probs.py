@@ -18,13 +18,14 @@ from the sequence files themselves, counted on the device and passed as ``counte
 """
 import configparser
 import json
+import math
 import os
 import pickle
 
 import numpy as np
 import torch
 
-from . import ar_funcs, bear_net, core, dataloader, kernels
+from . import ar_funcs, bear_net, bear_ref, core, dataloader, kernels
 from .log_gamma import _next_seed
 
 epsilon = core.epsilon
@@ -63,19 +64,113 @@ def load_bear(path):
     params, h_signed, ar_func = bear_net.change_scope_params(lag, alphabet_size, make_ar_func, af_kwargs, params_restart,
                                                              dtype=dtype, device=device)
     h = float(np.exp(h_signed.item()))
-    files_path = config["data"]["files_path"]
-    if files_path == "TEST":
-        data = dataloader.dataloader(os.path.join(os.path.dirname(os.path.abspath(__file__)), "data",
-                                                  "ysd1_lag_5_file_0_preshuf.tsv"), alphabet,
-                                     int(float(config["train"]["batch_size"])) or 1, int(config["data"]["num_ds"]))
-    else:
-        data = load_ds(files_path, config["data"]["start_token"], int(float(config["train"]["batch_size"])),
-                       config["data"]["sparse"] == "True", alphabet, int(config["data"]["num_ds"]))
+    data = _load_data(config)
 
     def ar_func_tf(kmers):
         with torch.no_grad():
             return torch.softmax(ar_func(kmers), dim=-1) + epsilon
     return lag, alphabet, h, ar_func_tf, data
+
+
+def _load_data(config):
+    """The count table a model folder's config names, as ``load_bear`` loads it."""
+    alphabet, files_path = config["data"]["alphabet"], config["data"]["files_path"]
+    if files_path == "TEST":
+        return dataloader.dataloader(os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "ysd1_lag_5_file_0_preshuf.tsv"),
+                                     alphabet, int(float(config["train"]["batch_size"])) or 1, int(config["data"]["num_ds"]))
+    return load_ds(files_path, config["data"]["start_token"], int(float(config["train"]["batch_size"])),
+                   config["data"]["sparse"] == "True", alphabet, int(config["data"]["num_ds"]))
+
+
+class RefModel:
+    """A model trained by ``bear_ref`` as scoring and generation take it: ``lag``, ``alphabet`` (a name of ``core.alphabets_en``),
+    ``h``, ``tau`` and ``net_weight`` (host floats: the exponentials of the trained ``h_signed``, ``tau_signed`` and
+    ``net_weight_signed``) and ``net_func``: None for the stop net function, else the callable from ``core.encode_kmers`` codes to
+    the net function's rows ``g`` (the linear one carries ``linear_mat`` / ``fused``).  The AR function's row of a k-mer is
+    ``(net_weight g + jukes_cantor(reference row, tau)) / (net_weight + 1) + epsilon`` (``kernels.ref_prior_rows``): a function of
+    the k-mer's reference counts, which ``ref_counter=`` supplies."""
+
+    def __init__(self, lag, alphabet, h, tau, net_weight, net_func=None):
+        self.lag, self.alphabet = int(lag), str(alphabet)
+        self.h, self.tau, self.net_weight = float(h), float(tau), float(net_weight)
+        self.net_func = net_func
+        if self.alphabet not in core.alphabets_en:
+            raise ValueError(f"alphabet {alphabet!r} is none of {sorted(core.alphabets_en)}")
+        if not (self.lag >= 1 and all(np.isfinite(v) and v > 0 for v in (self.h, self.tau, self.net_weight))):
+            raise ValueError("RefModel: lag >= 1, and h, tau and net_weight finite and > 0")
+
+    def net_rows(self, codes):
+        """The net function's rows float64 [n, W] of k-mers given as codes int8 [n, lag]; None for the stop net function."""
+        if self.net_func is None:
+            return None
+        with torch.no_grad():
+            return self.net_func(codes).to(torch.float64).expand(codes.shape[0], len(core.alphabets_en[self.alphabet])).contiguous()
+
+
+def load_bear_ref(path):
+    """A folder written by ``models/train_bear_ref.py`` (config.cfg + results.pickle) -> ``(ref_model, data, ds_loc, ds_loc_ref)``:
+    the ``RefModel``, the count table as ``load_bear`` loads it, and its training and reference columns
+    (``DeviceCounter.from_dataset(data, ds_loc)`` and ``(data, ds_loc_ref)`` are the ``counter=`` and ``ref_counter=`` of the model).
+    ``ValueError`` for a folder trained by ``bear_net``: its parameter list has no ``tau_signed`` / ``net_weight_signed``."""
+    config = configparser.ConfigParser()
+    config.read(os.path.join(path, "config.cfg"))
+    dtype = getattr(torch, config["general"]["precision"])
+    lag = int(config["hyperp"]["lag"])
+    alphabet = config["data"]["alphabet"]
+    alphabet_size = len(core.alphabets_tf[alphabet]) - 1
+    make_net_func = getattr(ar_funcs, "make_ar_func_" + config["model"]["ar_func_name"])
+    af_kwargs = json.loads(config["model"]["af_kwargs"])
+    with open(os.path.join(path, "results.pickle"), "rb") as fr:
+        params_restart = pickle.load(fr)["params"]
+    if "reference_column" not in config["data"]:
+        raise ValueError(f"{path}: config.cfg names no [data] reference_column: not a folder of train_bear_ref.py")
+    device = torch.device("cuda", torch.cuda.current_device())
+    if len(params_restart) < 3 or any(np.ndim(p) != 0 for p in params_restart[:3]):
+        raise ValueError(f"{path}: the saved parameters do not start with the scalars h_signed, tau_signed, net_weight_signed of a "
+                         "bear_ref model: the folder was trained by bear_net (load_bear reads it)")
+    params, h_signed, ar_func = bear_ref.change_scope_params(lag, alphabet_size, make_net_func, af_kwargs, params_restart,
+                                                             dtype=dtype, device=device)
+    model = RefModel(lag, alphabet, math.exp(h_signed.item()), math.exp(ar_func.tau_signed.item()), math.exp(ar_func.net_weight_signed.item()),
+                     None if ar_func.net_is_stop else ar_func.net_func)
+    return model, _load_data(config), int(config["data"]["train_column"]), int(config["data"]["reference_column"])
+
+
+class _RefRows:
+    """What stands in the place of ``ar_func`` on the device path when a reference model scores: ``_prior_rows`` takes the rows from
+    ``kernels.ref_prior_rows`` instead of calling it."""
+
+    def __init__(self, model, ref_counter):
+        self.model, self.ref_counter = model, ref_counter
+
+    def rows(self, counter, kmer_keys):
+        m, rc = self.model, self.ref_counter
+        g = m.net_rows(counter.codes_of_keys(kmer_keys))
+        return kernels.ref_prior_rows(rc.keys, rc.counts_by_key if rc.keys.numel() else None, kmer_keys, g, m.tau, m.net_weight,
+                                      eps=epsilon, width=rc.width)
+
+
+def _ref_setup(ref_model, ref_counter, counter, others):
+    """The checks of ``ref_model=`` / ``ref_counter=`` (every one a ``ValueError``, before any launch) -> the ``RefModel``, or None
+    where neither is given.  ``others``: the model arguments they cannot be combined with, by name."""
+    if ref_model is None and ref_counter is None:
+        return None
+    if ref_model is None or ref_counter is None:
+        raise ValueError("ref_model= and ref_counter= go together: the model and the reference column its rows are a function of")
+    given = [name for name, v in others.items() if v is not None]
+    if given:
+        raise ValueError(f"ref_model= is the model: it cannot be combined with {', '.join(given)}")
+    if not isinstance(counter, DeviceCounter) or not isinstance(ref_counter, DeviceCounter):
+        raise ValueError("a reference model runs on the device only: counter= and ref_counter= must be DeviceCounters")
+    if ref_counter.no_end:
+        raise ValueError("ref_counter: a no_end counter; the look-up reads its keys and count rows directly")
+    if counter.device != ref_counter.device:
+        raise ValueError(f"counter is on {counter.device}, ref_counter on {ref_counter.device}")
+    if not isinstance(ref_model, RefModel):
+        ref_model = load_bear_ref(os.fspath(ref_model))[0]
+    for name, c in (("counter", counter), ("ref_counter", ref_counter)):
+        if (c.lag, c.alphabet_name) != (ref_model.lag, ref_model.alphabet):
+            raise ValueError(f"{name}: a lag-{c.lag} table of {c.alphabet_name!r}, the model has lag {ref_model.lag} of {ref_model.alphabet!r}")
+    return ref_model
 
 
 class _Table:
@@ -396,7 +491,7 @@ def _segment_rows(counter, segments, lag, alphabet_name, h, ar_func, vans):
     """What ``_score_segments`` and ``_marg_segments`` do alike, up to their memory figure: the refusals, the scoring text, its keys,
     the distinct k-mers -- numbered as ``np.array(sorted(set(all_kmers)))`` numbers them (ascending keys) -- and the row of every
     position -> ``(hs, vans, text)``, ``text`` = ``(seg, rows, letters, kmer_keys, positions)``, tensors on the device, or None
-    where there is no transition anywhere."""
+    where there is no transition anywhere.  (``ar_func``: anything but None says "with BEAR models"; it is not called here.)"""
     if counter.lag != lag or counter.alphabet_name != alphabet_name:
         raise ValueError(f"counter: a lag-{counter.lag} table of {counter.alphabet_name!r}, asked for lag {lag} of {alphabet_name!r}")
     device = counter.device
@@ -421,6 +516,8 @@ def _prior_rows(counter, ar_func, kmer_keys, need, what, advice):
         raise MemoryError(f"{what} {need} bytes, the device has {free} free: {advice}")
     if ar_func is None:
         return None
+    if isinstance(ar_func, _RefRows):
+        return ar_func.rows(counter, kmer_keys)
     with torch.no_grad():
         return ar_func(counter.codes_of_keys(kmer_keys)).to(torch.float64).expand(kmer_keys.numel(), counter.width).contiguous()
 
@@ -530,7 +627,11 @@ def _scan(data, all_kmers, add, make_pdf, alphabet_size, train_col):
             all_kmers[unseen].astype(str))
 
 
-def _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter=None):
+def _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter=None, ref_model=None, ref_counter=None):
+    ref_model = _ref_setup(ref_model, ref_counter, counter, dict(bear_path=bear_path))
+    if ref_model is not None:       # a bear_ref model: its rows come from kernels.ref_prior_rows (_prior_rows)
+        h = np.array([ref_model.h]) if h is None else np.atleast_1d(h)
+        return ref_model.lag, ref_model.alphabet, h, _RefRows(ref_model, ref_counter), data, len(h)
     if bear_path is not None:
         lag, alphabet_name, h_bear, ar_func, data = load_bear(bear_path)
         if h is None:
@@ -547,10 +648,14 @@ def _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter=None)
 
 def get_bear_probs(bear_path, wt_seq, vars_, train_col, mc_samples=41, vans=[0.1, 1, 10], get_map=False,
                    lag=None, alphabet_name=None, h=None, data=None, kmc_path=None, kmc_reverse=False,
-                   kmc_no_end=False, seed=None, counter=None):
+                   kmc_no_end=False, seed=None, counter=None, ref_model=None, ref_counter=None):
     """get_var_probs.get_bear_probs (get_var_probs.py:346-452): posterior predictive log-probability ratios of
-    variants -> [num variants, num models, mc_samples] ([num variants, num models] with ``get_map``)."""
-    lag, alphabet_name, h, ar_func, data, len_h = _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter)
+    variants -> [num variants, num models, mc_samples] ([num variants, num models] with ``get_map``).
+
+    ``ref_model=`` (a ``RefModel`` or a folder of ``train_bear_ref.py``) with ``ref_counter=`` (the ``DeviceCounter`` of the reference
+    column) scores under a model trained by ``bear_ref``, on the device: ``counter`` must be a ``DeviceCounter`` too, ``bear_path`` None."""
+    lag, alphabet_name, h, ar_func, data, len_h = _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter,
+                                                         ref_model, ref_counter)
     alphabet_size = len(core.alphabets_en[alphabet_name]) - 1
     wt_seq = lag * "[" + wt_seq + "]"
     vars_ = [parse_var(v) for v in vars_]
@@ -616,7 +721,7 @@ def _get_all_kmers_seqs(seqs, lag):
 
 def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1, 10], get_map=False, get_marg=False,
                         lag=None, alphabet_name=None, h=None, data=None, kmc_path=None, kmc_reverse=False,
-                        no_ends=False, seed=None, counter=None, marg_on_device=False):
+                        no_ends=False, seed=None, counter=None, marg_on_device=False, ref_model=None, ref_counter=None):
     """get_var_probs.get_bear_probs_seqs (get_var_probs.py:511-631): log-probabilities of whole sequences ->
     [num sequences, num models, mc_samples] (last axis dropped with ``get_map`` / ``get_marg``).
 
@@ -625,10 +730,16 @@ def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1,
     (``_marg_segments``, ``kernels.score_marg``) -> [num sequences, num models].  The default stays ``False``, the host loop with
     the counter called per k-mer: the device sums a sequence's terms in another order, so its scores agree with the host loop's
     to rounding (1e-11 of the terms' L1 mass is what the tests hold it to), not to the bit, and the bits of the default are
-    pinned.  Making the device path the default is a later decision."""
+    pinned.  Making the device path the default is a later decision.
+
+    ``ref_model=`` / ``ref_counter=``: as for ``get_bear_probs``; ``get_marg=True`` then needs ``marg_on_device=True`` (a reference
+    model has no host path)."""
     if marg_on_device and not (get_marg and isinstance(counter, DeviceCounter)):
         raise ValueError("marg_on_device=True is the device path of get_marg=True with a DeviceCounter as counter=")
-    lag, alphabet_name, h, ar_func, data, len_h = _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter)
+    if (ref_model is not None or ref_counter is not None) and get_marg and not marg_on_device:
+        raise ValueError("a reference model runs on the device only: get_marg=True needs marg_on_device=True with it")
+    lag, alphabet_name, h, ar_func, data, len_h = _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter,
+                                                         ref_model, ref_counter)
     alphabet = core.alphabets_en[alphabet_name]
     alphabet_size = len(alphabet) - 1
     if not no_ends:

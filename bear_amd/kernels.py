@@ -742,6 +742,54 @@ def kmer_find(table, query):
     return rows
 
 
+def _check_ref_model(tau, net_weight, eps):
+    """The two scalars of a bear_ref model and its epsilon as the C ABI takes them: finite host floats, tau and net_weight > 0."""
+    tau, net_weight, eps = float(tau), float(net_weight), float(eps)
+    if not (np.isfinite(tau) and tau > 0 and np.isfinite(net_weight) and net_weight > 0):
+        raise ValueError("tau and net_weight must be finite and > 0")
+    if not (np.isfinite(eps) and eps >= 0):
+        raise ValueError("eps must be finite and >= 0")
+    return tau, net_weight, eps
+
+
+def _check_ref_table(ref_table, ref_counts, W, device):
+    """The reference column as a look-up: ``ref_table`` int64 [N] ascending distinct keys on ``device``, ``ref_counts`` int32 [N, W]
+    their count rows in that order (None with an empty table) -> the checked ``ref_counts`` (``_check_rows`` may have copied it)."""
+    _check_vec(ref_table, torch.int64, "ref_table", device=device)
+    if ref_table.numel() >= 2 ** 32 - 1:
+        raise ValueError("ref_table: a row index is 32 bits wide")
+    if not ref_table.numel():
+        return None
+    ref_counts = _check_rows(ref_counts, torch.int32, "ref_counts", W, n=ref_table.numel())
+    if ref_counts.device != device:
+        raise ValueError(f"ref_counts must be on {device}")
+    return ref_counts
+
+
+def ref_prior_rows(ref_table, ref_counts, query, net_rows, tau, net_weight, eps=EPSILON, width=None):
+    """One launch of ``bear_ref_prior_rows_f64``: float64 [n_query, W], the AR function's row of every ``query`` key (CUDA int64, any
+    order) under a bear_ref model -- ``(net_weight g + jukes_cantor(ref row, tau)) / (net_weight + 1) + eps`` in the kernel's fixed
+    arithmetic (include/bear_hip.h).  ``ref_table`` / ``ref_counts``: the reference column's ascending distinct keys and their int32
+    [N, W] count rows in key order (``DeviceCounter.keys`` / ``.counts_by_key``; None with an empty table, then ``width`` says W); an
+    absent key has a row of zeros.  ``net_rows``: the net function's rows ``g`` float64 [n_query, W], or None for the stop net
+    function.  ``tau``, ``net_weight``: host floats, the model's ``exp(tau_signed)`` and ``exp(net_weight_signed)``."""
+    _check_vec(query, torch.int64, "query")
+    device = query.device
+    W = ref_counts.shape[1] if isinstance(ref_counts, torch.Tensor) and ref_counts.dim() == 2 else width
+    if W not in WIDE_WIDTHS:
+        raise ValueError(f"rows of width {W}; the kernels take {WIDE_WIDTHS}")
+    ref_counts = _check_ref_table(ref_table, ref_counts, W, device)
+    tau, net_weight, eps = _check_ref_model(tau, net_weight, eps)
+    if net_rows is not None:
+        net_rows = _check_rows(net_rows, torch.float64, "net_rows", W, n=query.numel())
+        if net_rows.device != device:
+            raise ValueError(f"net_rows must be on {device}")
+    prior = torch.empty((query.numel(), W), dtype=torch.float64, device=device)
+    _launch(device, "bear_ref_prior_rows_f64", _ptr(ref_table), _ptr(ref_counts), ref_table.numel(), W, _ptr(query), query.numel(),
+            _ptr(net_rows), tau, net_weight, eps, _ptr(prior))
+    return prior
+
+
 def score_sum(lp, rows, letters, seg):
     """``bear_score_sum_f64``: ``scores[i] = sum_t lp[rows[t], letters[t]]`` over the transitions of segment ``i`` in text order ->
     CUDA float64 [n_seg, M, S].  ``lp``: the sampler's table [K, W, M, S] as ``logdir_sample[_wide]`` returns it; ``rows`` int32
@@ -808,12 +856,15 @@ def score_marg(rows, letters, seg, train, prior, h, vans):
 # ---- sequence generation over a key table (include/bear_hip.h, "Sequence generation"; kernels_generate.h) ----------------------
 GEN_BMM, GEN_BEAR, GEN_AR = 0, 1, 2  # BEAR_GEN_*: where a letter's concentration comes from
 GEN_ID_GUMBEL = 3000                 # the model id that keys the Gumbel draws (the table values are model 0)
+GEN_NET_STOP, GEN_NET_ROWS, GEN_NET_MAT = 0, 1, 2      # BEAR_GEN_NET_*: where a bear_ref model's net rows come from
 
 
 def _generate_launch(entry, table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van, prior, h, get_map, codes,
-                     mat=None, state=None):
+                     mat=None, state=None, ref=None):
     """What ``generate_steps`` and ``generate_whole`` check alike, and the launch of ``entry`` with its complete argument list.
     ``state`` = (length, stopped) says ``bear_generate_whole_f64``: it takes ``mat`` behind ``prior`` and the state behind ``left``.
+    ``ref`` = (ref_table, ref_counts, tau, net_weight, eps) says ``bear_generate_whole_ref_f64``: ``prior`` / ``mat`` are then the net
+    function's rows (neither: the stop net function), and the reference column and the model's scalars go behind ``codes``.
     The checked ``counts`` and ``prior`` (``_check_rows`` may have copied them) live in this frame across the launch."""
     _check_vec(table, torch.int64, "table")
     device = table.device
@@ -845,7 +896,12 @@ def _generate_launch(entry, table, counts, rank, lag, keys, sample, left, letter
             raise ValueError(f"prior must be on {device}")
         if n_steps > 1:
             raise ValueError("prior rows belong to the current end k-mers: one step per launch")
-    if prior is not None or mat is not None:
+    if ref is not None:
+        if van is not None:
+            raise ValueError("a reference model mixes an AR function's rows: no BMM (van)")
+        ref_counts = _check_ref_table(ref[0], ref[1], W, device)
+        ref_scalars = _check_ref_model(*ref[2:])
+    if prior is not None or mat is not None or ref is not None:
         if h is None and not get_map:
             raise ValueError("the AR model (rows without h) is a table only at its MAP value: get_map=True")
         mode = GEN_AR if h is None else GEN_BEAR
@@ -871,7 +927,9 @@ def _generate_launch(entry, table, counts, rank, lag, keys, sample, left, letter
     _launch(device, entry, _ptr(table), _ptr(counts), table.numel(), int(lag), W, rank.ctypes.data_as(ctypes.c_void_p), mode,
             int(bool(get_map)), float(h) if mode == GEN_BEAR else 0.0, float(van) if mode == GEN_BMM else 0.0, _ptr(prior),
             *([_ptr(mat)] if whole else []), int(seed) & (2 ** 64 - 1), _ptr(keys), _ptr(sample), _ptr(left),
-            *([_ptr(state[0]), _ptr(state[1])] if whole else []), n, step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes))
+            *([_ptr(state[0]), _ptr(state[1])] if whole else []), n, step0, n_steps, _ptr(letters), letters.shape[1], _ptr(codes),
+            *([] if ref is None else [_ptr(ref[0]), _ptr(ref_counts), ref[0].numel(), *ref_scalars,
+                                      GEN_NET_ROWS if prior is not None else (GEN_NET_MAT if mat is not None else GEN_NET_STOP)]))
 
 
 def generate_steps(table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van=None, prior=None, h=None,
@@ -899,6 +957,20 @@ def generate_whole(table, counts, rank, lag, keys, sample, left, length, stopped
         raise ValueError("prior rows or mat: one source of the AR function's rows")
     _generate_launch("bear_generate_whole_f64", table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, van, prior,
                      h, get_map, codes, mat=mat, state=(length, stopped))
+
+
+def generate_whole_ref(table, counts, ref_table, ref_counts, rank, lag, keys, sample, left, length, stopped, letters, step0, n_steps, seed,
+                       tau, net_weight, net_rows=None, mat=None, h=None, get_map=False, codes=None, eps=EPSILON):
+    """One launch of ``bear_generate_whole_ref_f64``: ``generate_whole`` under a bear_ref model.  The AR function's row of an end
+    k-mer is formed inside the step, as ``ref_prior_rows`` forms it, from the k-mer's row in the reference column (``ref_table`` /
+    ``ref_counts``, as there) and the net function's row: the one-hot at the stop (neither ``net_rows`` nor ``mat``: any ``n_steps``,
+    whole sequences in one launch), ``net_rows`` float64 [n, W] of the current end k-mers (``n_steps`` 1), or, for the protein
+    alphabet, the linear function of ``mat`` [lag, 21, 21] inside the kernel (any ``n_steps``).  With ``h`` a BEAR model, without the
+    AR model (``get_map`` only)."""
+    if net_rows is not None and mat is not None:
+        raise ValueError("net_rows or mat: one source of the net function's rows")
+    _generate_launch("bear_generate_whole_ref_f64", table, counts, rank, lag, keys, sample, left, letters, step0, n_steps, seed, None,
+                     net_rows, h, get_map, codes, mat=mat, state=(length, stopped), ref=(ref_table, ref_counts, tau, net_weight, eps))
 
 
 def shuffle_rows(src, seed):

@@ -56,7 +56,9 @@ extern "C" {
                                   scoring on the device);
                                   + bear_shuffle_rows_range, bear_shuffle_gather_host (a range of
                                   the shuffled rows: streamed and multi-rank shuffled epochs);
-                                  + bear_math_probe_f64 (the device math routines one at a time: tests and diagnostics) */
+                                  + bear_math_probe_f64 (the device math routines one at a time: tests and diagnostics);
+                                  + bear_ref_prior_rows_f64, bear_generate_whole_ref_f64 (bear_ref models downstream: scoring and
+                                  generation under a reference-mixed prior) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -1043,6 +1045,52 @@ int bear_generate_whole_f64(const uint64_t *table, const uint32_t *counts, uint6
                             int mode, int map, double h, double van, const double *prior, const double *mat, uint64_t seed,
                             uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
                             uint64_t step0, uint64_t n_steps, uint8_t *letters, uint64_t letters_stride, int8_t *codes, void *stream);
+
+/*
+ * bear_ref models downstream of training.  The AR function's row of a k-mer under a model trained by bear_ref is a function of the
+ * k-mer's REFERENCE count row as well: with A = width - 1 letters, the stop last, ref the uint32 row of the reference column (zeros
+ * where the reference table lacks the k-mer) and g the net function's row (the one-hot at the stop for the stop net function),
+ *     r_b = ref_b + eps (b < A), r_A = 0;   R = sum_b r_b, added as NumPy's add.reduce adds W contiguous doubles
+ *     dev_b = r_b / R - 1/A (b < A), dev_A = 0: the quotient rounded as a division, the subtraction unfused
+ *     jc_b = fma(E, dev_b, [b < A] / A);   f_b = fma(nw, g_b, jc_b) * V;   prior_b = f_b + eps
+ * E = exp(-tau) and V = 1 / (nw + 1) are formed ONCE on the host from tau and net_weight (the model's exp(tau_signed) and
+ * exp(net_weight_signed)) and reach the kernel by value; on the device there is nothing but add, multiply, fma and the rounded
+ * quotient, so a host replica with an exact fma gives the same bits.  prior is "the AR function's row" every consumer takes: the
+ * + eps is load_bear's wrapper of an AR function, not the f / h + c + eps of a training step.
+ *
+ * bear_ref_prior_rows_f64: prior[q, :] for every query key.
+ *   ref_table [dev, nullable] uint64 [n_ref] ascending and distinct keys of bear_score_transitions_u64, n_ref < 2^32 - 1;
+ *   ref_counts [dev, nullable] uint32 [n_ref, width], row j the reference counts of ref_table[j] (KEY order); n_ref = 0 is valid
+ *   query [dev] uint64 [n_query] in any order;  net_rows [dev, nullable] double [n_query, width]: g, NULL for the stop net function
+ *   prior [dev] double [n_query, width].  n_query = 0 is valid and launches nothing.  One thread per query; no atomics.
+ * Refused with BEAR_ERR_INVALID_ARG before any launch: a width other than 5 / 21, tau or net_weight not finite and > 0, eps not
+ * finite and >= 0, n_ref >= 2^32 - 1, a missing or misaligned pointer.
+ *
+ * bear_generate_whole_ref_f64: bear_generate_whole_f64 under such a model -- its arguments, steps, streams and state, with the row
+ * f of the current end k-mer formed inside the step: the group's first lane finds the k-mer in `table` and in `ref_table`, every
+ * letter lane forms R of the reference row itself (the same additions in the same order: equal bits on all lanes, no sum across
+ * lanes) and its own prior_b, and goes on as bear_generate_whole_f64 does with f from `prior`.  The net function's row g is
+ *   net BEAR_GEN_NET_STOP  the one-hot at the stop; prior and mat NULL, any n_steps: whole sequences in one launch
+ *   net BEAR_GEN_NET_ROWS  prior [dev] double [n_seq, width]: g of the CURRENT end k-mers, n_steps at most 1
+ *   net BEAR_GEN_NET_MAT   formed from mat [dev] double [lag, 21, 21] as bear_generate_whole_f64 forms f from it; width 21, any n_steps
+ * mode is BEAR_GEN_BEAR (fma(prior_b, 1 / h, c[b])) or BEAR_GEN_AR (prior_b; map != 0); van is not read.
+ * Refused with BEAR_ERR_INVALID_ARG before any device call: everything bear_generate_whole_f64 refuses, BEAR_GEN_BMM, a net other
+ * than the three, prior or mat given or missing against `net`, tau / net_weight / eps as above, n_ref >= 2^32 - 1, a missing or
+ * misaligned ref_table / ref_counts with n_ref > 0.  n_seq = 0 is valid and launches nothing.  The same bytes in both libraries
+ * and for any cut of the steps into launches.
+ */
+#define BEAR_GEN_NET_STOP 0
+#define BEAR_GEN_NET_ROWS 1
+#define BEAR_GEN_NET_MAT 2
+int bear_ref_prior_rows_f64(const uint64_t *ref_table, const uint32_t *ref_counts, uint64_t n_ref, int width, const uint64_t *query,
+                            uint64_t n_query, const double *net_rows, double tau, double net_weight, double eps, double *prior,
+                            void *stream);
+int bear_generate_whole_ref_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,
+                                int mode, int map, double h, double van, const double *prior, const double *mat, uint64_t seed,
+                                uint64_t *keys, const uint64_t *sample, uint32_t *left, uint32_t *length, uint8_t *stopped, uint64_t n_seq,
+                                uint64_t step0, uint64_t n_steps, uint8_t *letters, uint64_t letters_stride, int8_t *codes,
+                                const uint64_t *ref_table, const uint32_t *ref_counts, uint64_t n_ref, double tau, double net_weight,
+                                double eps, int net, void *stream);
 
 #ifdef __cplusplus
 }
