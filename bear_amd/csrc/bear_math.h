@@ -69,6 +69,55 @@ __device__ __forceinline__ double bear_stir_psi(double r) {
   return s * r2;
 }
 
+// Stirling tail of trigamma:  psi1(y) = 1/y + 1/(2 y^2) + bear_stir_psi1(1/y): the terms B_2k / y^(2k+1), k = 1 .. 9.  The first
+// omitted one is 174611/330 y^-21: 5.8e-17 at y = 8, 4.3e-16 of psi1(8) (with seven terms it was 3.2e-15, 2.4e-14 of psi1(8)).
+__device__ __forceinline__ double bear_stir_psi1(double r) {
+  double r2 = r * r;
+  double s = 43867.0 / 798.0;
+  s = __builtin_fma(s, r2, -3617.0 / 510.0);
+  s = __builtin_fma(s, r2, 7.0 / 6.0);
+  s = __builtin_fma(s, r2, -691.0 / 2730.0);
+  s = __builtin_fma(s, r2, 5.0 / 66.0);
+  s = __builtin_fma(s, r2, -1.0 / 30.0);
+  s = __builtin_fma(s, r2, 1.0 / 42.0);
+  s = __builtin_fma(s, r2, -1.0 / 30.0);
+  s = __builtin_fma(s, r2, 1.0 / 6.0);
+  return s * (r2 * r);
+}
+
+// digamma and trigamma of ONE argument (the posterior moments of kernels_moments.h; everything above forms differences), x > 0
+// finite and normal: shift to y = x + m >= BEAR_TSTIR with m <= 8 steps, the Stirling series at y, and the m shifted reciprocals
+//   psi(x)  = psi(y)  - sum_{j<m} 1 / (x + j)        the sum as p'/p of p = prod_j (x + j), as bear_dm_item forms it: one reciprocal
+//   psi1(x) = psi1(y) + sum_{j<m} 1 / (x + j)^2      every term positive: m reciprocals, nothing cancels
+// x + j is formed from x every time (one rounding; a chain t += 1 would carry j of them into y).  DESIGN.md 3.1 has the bounds.
+__device__ __forceinline__ double bear_psi(double x) {
+  const double need = BEAR_TSTIR - x;
+  const uint32_t m = need > 0.0 ? (uint32_t)ceil(need) : 0u;
+  double p = 1.0, dp = 0.0;
+  for (uint32_t j = 0; j < m; ++j) {
+    const double t = x + (double)j;
+    dp = __builtin_fma(dp, t, p);
+    p *= t;
+  }
+  const double y = x + (double)m;
+  const double r = bear_rcp(y);
+  double v = (bear_log(y) - 0.5 * r) - bear_stir_psi(r);
+  if (m > 0) v -= dp * bear_rcp(p);
+  return v;
+}
+
+__device__ __forceinline__ double bear_psi1(double x) {
+  const double need = BEAR_TSTIR - x;
+  const uint32_t m = need > 0.0 ? (uint32_t)ceil(need) : 0u;
+  double s = 0.0;
+  for (uint32_t j = 0; j < m; ++j) {
+    const double q = bear_rcp(x + (double)j);
+    s = __builtin_fma(q, q, s);
+  }
+  const double r = bear_rcp(x + (double)m);
+  return s + (r + __builtin_fma(0.5 * r, r, bear_stir_psi1(r)));
+}
+
 // D, P between y and y + c for y >= BEAR_TSTIR, c >= 1 (c as double, exact integer).
 __device__ __forceinline__ bear_dp bear_stirling_diff(double y, double c) {
   double y1 = y + c;

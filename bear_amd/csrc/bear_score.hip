@@ -1,10 +1,11 @@
 // bear_score.hip -- scoring on the device: the entries between the device count tables and the samplers' tables
 // (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
-// of a sampled table's rows over the transitions of every segment; the exact marginal of every segment, which needs no table -- and
+// of a sampled table's rows over the transitions of every segment; the exact marginal of every segment and the exact posterior
+// mean and variance of every segment's score, which need no table -- and
 // sequence generation over the same key tables ("Sequence generation": flanks of given lengths, and whole sequences from start to
 // stop) -- and, for bear_ref models, the reference-mixed prior rows of queried k-mers and whole sequences under such a model.
 // The only unit that includes -- and so emits --
-// kernels_score.h, kernels_marg.h, kernels_refscore.h and kernels_generate.h.
+// kernels_score.h, kernels_marg.h, kernels_moments.h, kernels_refscore.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 #include "bear_release_guard.h"
 #include "kernels_generate.h"
 #include "kernels_marg.h"
+#include "kernels_moments.h"
 #include "kernels_refscore.h"
 #include "kernels_score.h"
 
@@ -165,14 +167,18 @@ int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_
   return BEAR_OK;      // (partials goes with this frame: hipFree waits for the two launches)
 }
 
-int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
-                        const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van,
-                        int n_van, double *scores, void *stream) {
+}  // extern "C"
+
+namespace {
+// What bear_score_marg_f64 and bear_score_moments_f64 check alike before any device call, and their models: BEAR_OK with
+// P filled, or the status to return.  out: the scores / the moments; planes: values per segment and model (1 / 2).
+int mrg_prepare(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
+                const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van, int n_van,
+                const double *out, uint64_t planes, mrg_models &P) {
   if (width != 5 && width != 21) return BEAR_ERR_INVALID_ARG;
   if (n_h < 0 || n_van < 0 || n_h > MRG_MAX_MODELS || n_van > MRG_MAX_MODELS || n_h + n_van < 1 || n_h + n_van > MRG_MAX_MODELS)
     return BEAR_ERR_INVALID_ARG;
   if ((n_h > 0 && (!h || !prior)) || (n_van > 0 && !van)) return BEAR_ERR_INVALID_ARG;
-  mrg_models P;
   memset(&P, 0, sizeof(P));
   P.n_h = n_h;
   P.n_m = n_h + n_van;
@@ -186,21 +192,19 @@ int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_
   }
   if (n_rows >= SCR_ABSENT) return BEAR_ERR_INVALID_ARG;
   if (n_seg == 0) return BEAR_OK;
-  if (!seg || !scores || misaligned8(seg) || misaligned8(scores)) return BEAR_ERR_INVALID_ARG;
+  if (!seg || !out || misaligned8(seg) || misaligned8(out)) return BEAR_ERR_INVALID_ARG;
   if (n_t && (!rows || !letters || misaligned4(rows))) return BEAR_ERR_INVALID_ARG;
   if (n_t && n_rows && (!train || misaligned4(train))) return BEAR_ERR_INVALID_ARG;
   if (n_h > 0 && misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
-  const uint64_t M = (uint64_t)P.n_m;
+  const uint64_t M = (uint64_t)P.n_m * planes;
   if (n_seg > (~0ull) / M / sizeof(double) || n_t > (~0ull) / M / sizeof(double)) return BEAR_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dev_buf<double> terms, partials;       // one term per position and model; two partial rows per MRG_CHUNK positions of a long text
-  if (n_t) {
-    HIP_TRY(terms.alloc(n_t * M));
-    const dim3 grid(scr_grid(n_t, MRG_THREADS)), block(MRG_THREADS);
-    LAUNCH_BY_WIDTH(width, marg_terms_kernel<5>, marg_terms_kernel<21>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train,
-                    n_h > 0 ? prior : nullptr, n_rows, P, terms.get());
-    HIP_TRY(hipGetLastError());
-  }
+  return BEAR_OK;
+}
+
+// ... and the sums behind their terms [M, n_t]: scores [n_seg, M]
+int mrg_sums(const dev_buf<double> &terms, uint64_t M, const uint64_t *seg, uint64_t n_seg, uint64_t n_t, double *scores,
+             hipStream_t s) {
+  dev_buf<double> partials;              // two partial rows per MRG_CHUNK positions of a long text
   if (n_t > MRG_CHUNK) {                 // only such a text can hold a long segment
     const uint64_t n_blocks = (n_t + MRG_CHUNK - 1) / MRG_CHUNK;
     HIP_TRY(partials.alloc(2 * n_blocks * M));
@@ -211,7 +215,50 @@ int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_
   hipLaunchKernelGGL(marg_sum_kernel, dim3(scr_grid(n_seg, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms.get(), (uint32_t)M, seg, n_seg,
                      n_t, partials.get(), scores);
   HIP_TRY(hipGetLastError());
-  return BEAR_OK;      // (terms and partials go with this frame: hipFree waits for the launches)
+  return BEAR_OK;      // (partials goes with this frame: hipFree waits for the launches)
+}
+}  // namespace
+
+extern "C" {
+
+int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
+                        const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van,
+                        int n_van, double *scores, void *stream) {
+  mrg_models P;
+  const int st = mrg_prepare(rows, letters, n_t, seg, n_seg, width, train, prior, n_rows, h, n_h, van, n_van, scores, 1, P);
+  if (st != BEAR_OK || n_seg == 0) return st;
+  const uint64_t M = (uint64_t)P.n_m;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dev_buf<double> terms;                 // one term per position and model
+  if (n_t) {
+    HIP_TRY(terms.alloc(n_t * M));
+    const dim3 grid(scr_grid(n_t, MRG_THREADS)), block(MRG_THREADS);
+    LAUNCH_BY_WIDTH(width, marg_terms_kernel<5>, marg_terms_kernel<21>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train,
+                    n_h > 0 ? prior : nullptr, n_rows, P, terms.get());
+    HIP_TRY(hipGetLastError());
+  }
+  return mrg_sums(terms, M, seg, n_seg, n_t, scores, s);      // (terms goes with this frame: hipFree waits for the launches)
+}
+
+int bear_score_moments_f64(const int32_t *rows, const uint8_t *letters, const int64_t *weight_prefix, uint64_t n_t, const uint64_t *seg,
+                           uint64_t n_seg, int width, const uint32_t *train, const double *prior, uint64_t n_rows, const double *h,
+                           int n_h, const double *van, int n_van, double *moments, void *stream) {
+  mrg_models P;
+  const int st = mrg_prepare(rows, letters, n_t, seg, n_seg, width, train, prior, n_rows, h, n_h, van, n_van, moments, 2, P);
+  if (st != BEAR_OK) return st;
+  if (weight_prefix && misaligned8(weight_prefix)) return BEAR_ERR_INVALID_ARG;
+  if (n_seg == 0) return BEAR_OK;
+  const uint64_t M = 2 * (uint64_t)P.n_m;                     // planes: the mean and the variance of every model
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dev_buf<double> terms;
+  if (n_t) {
+    HIP_TRY(terms.alloc(n_t * M));
+    const dim3 grid(scr_grid(n_t, MRG_THREADS)), block(MRG_THREADS);
+    LAUNCH_BY_WIDTH(width, moments_terms_kernel<5>, moments_terms_kernel<21>, grid, block, 0, s, rows, letters, weight_prefix, n_t, seg,
+                    n_seg, train, n_h > 0 ? prior : nullptr, n_rows, P, terms.get());
+    HIP_TRY(hipGetLastError());
+  }
+  return mrg_sums(terms, M, seg, n_seg, n_t, moments, s);     // plane 2 m + k of segment i lands at moments[i, m, k]
 }
 
 int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,

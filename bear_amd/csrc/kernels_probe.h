@@ -46,6 +46,8 @@ __global__ __launch_bounds__(256) void math_probe_kernel(int op, const double *_
     case BEAR_PROBE_SRT_GENERAL_AUTO: o = srt_general_auto(x, c, logtab); r0 = o.D; r1 = o.P; break;
     case BEAR_PROBE_ROW_ITEM_TAB: o = dm_row_item(x, c, logtab); r0 = o.D; r1 = o.P; break;
     case BEAR_PROBE_ROW_ITEM: o = dm_row_item(x, c, nullptr); r0 = o.D; r1 = o.P; break;
+    case BEAR_PROBE_PSI: r0 = bear_psi(x); break;
+    case BEAR_PROBE_PSI1: r0 = bear_psi1(x); break;
     default: break;
   }
   if (on) {

@@ -9,7 +9,8 @@ log-Gamma draws of ``log_gamma.log_gamma`` and their normalisation, or the MAP t
 width-taking twins, ``bear_logdir_sample_wide_f64`` and ``bear_eval_wide_f64``.  The k+1-mer bookkeeping stays on the host as in the
 reference (string windows, a lookup table indexed by k+1-mer) -- unless the counts come from a ``DeviceCounter``: then
 ``get_bear_probs`` / ``get_bear_probs_seqs`` run on the device from the queries' symbols to the scores (``kernels_score.h``; the
-exact marginal when ``marg_on_device=True`` asks for it, ``kernels_marg.h``).
+exact marginal when ``marg_on_device=True`` asks for it, ``kernels_marg.h``; with ``moments=True`` the exact mean and variance of
+the scores instead of samples of them, ``kernels_moments.h``).
 
 Differences a user can see: draws come from a counter-based stream (``seed`` argument; ``None`` takes a fresh
 seed from numpy's global generator) instead of numpy's Mersenne twister, and the KMC database look-up
@@ -570,6 +571,72 @@ def _marg_segments(counter, segments, lag, alphabet_name, h, ar_func, vans):
         return kernels.score_marg(rows, letters, seg, counter.rows_of_keys(kmer_keys), prior, hs, vans)
 
 
+def _check_moments(counter, **others):
+    """The refusals of ``moments=True`` (every one a ``ValueError``, before a device is touched): it is the device path's, and
+    ``others`` -- by name -- are the results it cannot be combined with."""
+    if not isinstance(counter, DeviceCounter):
+        raise ValueError("moments=True runs on the device only: counter= must be a DeviceCounter")
+    given = [name for name, v in others.items() if v]
+    if given:
+        raise ValueError(f"moments=True is the mean and variance of the sampled scores: it cannot be combined with {', '.join(given)}")
+
+
+def _signed_pairs(seg):
+    """Windows in pairs (mutant, wild type) -> one signed segment per pair: ``seg`` int64 [2 n + 1], the windows' offsets ->
+    ``(seg[0::2], weights int8 [seg[-1]])``, +1 on the positions of every mutant window and -1 on the wild type's.  The transitions
+    are formed under the windows' own offsets (``_segment_rows``): none crosses from one window of a pair into the other."""
+    seg = np.asarray(seg, dtype=np.int64)
+    assert seg.size % 2 == 1
+    sign = np.tile(np.array([1, -1], dtype=np.int8), seg.size // 2)
+    return seg[0::2].copy(), np.repeat(sign, np.diff(seg))
+
+
+def _moment_segments(counter, segments, lag, alphabet_name, h, ar_func, vans, pair=False):
+    """The device path of ``moments=True``: the exact mean and variance, over the posterior the sampled path draws from, of the score
+    of string ``i`` under every model -> CUDA float64 [n_seg, num_models, 2] (variance as summed), BEAR models first.
+    ``_segment_rows`` and ``_prior_rows`` as ``_marg_segments`` calls them, then ``kernels.score_moments``.  ``pair``: the strings
+    are windows in pairs (mutant, wild type) and a pair is ONE signed segment (``_signed_pairs``) -> [n_seg / 2, num_models, 2].
+
+    Per distinct k-mer the call holds what ``_marg_segments`` holds, per position two terms per model, the sort's key and order,
+    the weight's prefix sum and the rows: if that would not fit the free device memory a ``MemoryError`` says so.  There is no
+    sampled table."""
+    hs, vans, text = _segment_rows(counter, segments, lag, alphabet_name, h, ar_func, vans)
+    num_models = len(vans) + len(hs)
+    n_out = len(segments) // 2 if pair else len(segments)
+    if text is None:                # no transition anywhere
+        return torch.zeros((n_out, num_models, 2), dtype=torch.float64, device=counter.device)
+    seg, rows, letters, kmer_keys, positions = text
+    K, W = kmer_keys.numel(), counter.width
+    with torch.cuda.device(counter.device):
+        prior = _prior_rows(counter, ar_func, kmer_keys, K * W * 3 * 8 + positions * (2 * num_models + 4) * 8,
+                            f"the rows of {K} k-mers x {W} letters and the terms of {positions} positions x 2 x {num_models} models take",
+                            "score fewer variants / sequences per call")
+        weights = None
+        if pair:
+            coarse, weights = _signed_pairs(seg.cpu().numpy())
+            seg, weights = torch.from_numpy(coarse).to(counter.device), torch.from_numpy(weights).to(counter.device)
+        return kernels.score_moments(rows, letters, seg, counter.rows_of_keys(kmer_keys), prior, hs, vans, weights=weights)
+
+
+def _moments_result(moments):
+    """What ``moments=True`` returns: NumPy float64 [n, num_models, 2], the variance -- a sum that rounding can leave a few ulps
+    below 0 -- not below 0 (its user takes a square root)."""
+    out = moments.cpu().numpy()
+    np.maximum(out[..., 1], 0.0, out=out[..., 1])
+    return out
+
+
+def _variant_windows(vars_, wt_seq, lag):
+    """Per variant its two windows, the mutant's then the wild type's (get_var_probs.py:294-306): ``wt_seq`` padded, ``vars_`` parsed."""
+    windows = []
+    for wt_aa, mt_aa, pos in vars_:
+        pos = pos + lag
+        assert wt_aa == wt_seq[pos:pos + len(wt_aa)]
+        windows.append(wt_seq[pos - lag:pos] + mt_aa + wt_seq[pos + len(wt_aa):pos + lag + len(wt_aa)])
+        windows.append(wt_seq[pos - lag:pos + lag + len(wt_aa)])
+    return windows
+
+
 # ------------------------------------------------------------------------------------------- variants
 def _add_kmer_probs_vars(vars_, scores, wt_seq, pdf, lag, seen_kmers):
     """get_var_probs.py:294-306."""
@@ -648,12 +715,20 @@ def _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter=None,
 
 def get_bear_probs(bear_path, wt_seq, vars_, train_col, mc_samples=41, vans=[0.1, 1, 10], get_map=False,
                    lag=None, alphabet_name=None, h=None, data=None, kmc_path=None, kmc_reverse=False,
-                   kmc_no_end=False, seed=None, counter=None, ref_model=None, ref_counter=None):
+                   kmc_no_end=False, seed=None, counter=None, ref_model=None, ref_counter=None, moments=False):
     """get_var_probs.get_bear_probs (get_var_probs.py:346-452): posterior predictive log-probability ratios of
     variants -> [num variants, num models, mc_samples] ([num variants, num models] with ``get_map``).
 
     ``ref_model=`` (a ``RefModel`` or a folder of ``train_bear_ref.py``) with ``ref_counter=`` (the ``DeviceCounter`` of the reference
-    column) scores under a model trained by ``bear_ref``, on the device: ``counter`` must be a ``DeviceCounter`` too, ``bear_path`` None."""
+    column) scores under a model trained by ``bear_ref``, on the device: ``counter`` must be a ``DeviceCounter`` too, ``bear_path`` None.
+
+    ``moments=True`` (with a ``DeviceCounter``, without ``get_map``; anything else is a ``ValueError``, raised before a device is
+    touched): instead of ``mc_samples`` draws, the exact mean and variance of what that axis samples -> float64 [num variants, num
+    models, 2], ``[..., 0]`` the mean and ``[..., 1]`` the variance (not below 0), the models in the sampled path's order.  Closed
+    form (digamma and trigamma of the posterior's concentrations, ``kernels.score_moments``): no Monte-Carlo noise, the same
+    result whatever ``seed``, ``mc_samples`` and the other variants of the call are, and no sampled table in memory."""
+    if moments:
+        _check_moments(counter, get_map=get_map)
     lag, alphabet_name, h, ar_func, data, len_h = _setup(bear_path, lag, alphabet_name, h, data, vans, kmc_path, counter,
                                                          ref_model, ref_counter)
     alphabet_size = len(core.alphabets_en[alphabet_name]) - 1
@@ -664,13 +739,13 @@ def get_bear_probs(bear_path, wt_seq, vars_, train_col, mc_samples=41, vans=[0.1
     num_models = (ar_func is not None) * (len_h + get_map) + len(vans)
     scores = np.zeros([len(vars_), num_models, mc_samples])
     seed = _next_seed() if seed is None else seed
+    if moments:                                 # a variant is ONE signed segment: its mutant window counts +1, its wild type's -1
+        windows = _variant_windows(vars_, wt_seq, lag)
+        if not windows:
+            return np.zeros([0, num_models, 2])
+        return _moments_result(_moment_segments(counter, windows, lag, alphabet_name, h, ar_func, vans, pair=True))
     if isinstance(counter, DeviceCounter):      # the whole call on the device: a variant is two segments, mutant and wild-type window
-        windows = []
-        for wt_aa, mt_aa, pos in vars_:
-            pos = pos + lag
-            assert wt_aa == wt_seq[pos:pos + len(wt_aa)]
-            windows.append(wt_seq[pos - lag:pos] + mt_aa + wt_seq[pos + len(wt_aa):pos + lag + len(wt_aa)])
-            windows.append(wt_seq[pos - lag:pos + lag + len(wt_aa)])
+        windows = _variant_windows(vars_, wt_seq, lag)
         if windows:
             sums = _score_segments(counter, windows, lag, alphabet_name, h, ar_func, mc_samples, vans, get_map, seed)
             scores = (sums[0::2] - sums[1::2]).cpu().numpy()
@@ -721,7 +796,8 @@ def _get_all_kmers_seqs(seqs, lag):
 
 def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1, 10], get_map=False, get_marg=False,
                         lag=None, alphabet_name=None, h=None, data=None, kmc_path=None, kmc_reverse=False,
-                        no_ends=False, seed=None, counter=None, marg_on_device=False, ref_model=None, ref_counter=None):
+                        no_ends=False, seed=None, counter=None, marg_on_device=False, ref_model=None, ref_counter=None,
+                        moments=False):
     """get_var_probs.get_bear_probs_seqs (get_var_probs.py:511-631): log-probabilities of whole sequences ->
     [num sequences, num models, mc_samples] (last axis dropped with ``get_map`` / ``get_marg``).
 
@@ -733,7 +809,13 @@ def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1,
     pinned.  Making the device path the default is a later decision.
 
     ``ref_model=`` / ``ref_counter=``: as for ``get_bear_probs``; ``get_marg=True`` then needs ``marg_on_device=True`` (a reference
-    model has no host path)."""
+    model has no host path).
+
+    ``moments=True``: as for ``get_bear_probs`` -> float64 [num sequences, num models, 2], the exact mean and variance of what the
+    ``mc_samples`` axis samples; a ``ValueError`` together with ``get_map``, ``get_marg`` or ``marg_on_device`` or without a
+    ``DeviceCounter``."""
+    if moments:
+        _check_moments(counter, get_map=get_map, get_marg=get_marg, marg_on_device=marg_on_device)
     if marg_on_device and not (get_marg and isinstance(counter, DeviceCounter)):
         raise ValueError("marg_on_device=True is the device path of get_marg=True with a DeviceCounter as counter=")
     if (ref_model is not None or ref_counter is not None) and get_marg and not marg_on_device:
@@ -749,6 +831,12 @@ def get_bear_probs_seqs(bear_path, seqs, train_col, mc_samples=41, vans=[0.1, 1,
     num_models = (ar_func is not None) * (len_h + get_map) + len(vans)
     scores = np.zeros([len(seqs), num_models, mc_samples])
     seed = _next_seed() if seed is None else seed
+    if moments:                                                 # the exact moments on the device: a sequence is a segment
+        for seq in seqs:
+            assert len(seq.replace("[", "").replace("]", "")) >= lag
+        if not len(seqs):
+            return np.zeros([0, num_models, 2])
+        return _moments_result(_moment_segments(counter, seqs, lag, alphabet_name, h, ar_func, vans))
     if marg_on_device:                                          # the exact marginal on the device: a sequence is a segment
         for seq in seqs:
             assert len(seq.replace("[", "").replace("]", "")) >= lag

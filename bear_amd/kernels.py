@@ -822,6 +822,22 @@ def score_marg(rows, letters, seg, train, prior, h, vans):
     The kernel wants every segment's positions sorted by (row, letter): one ``torch.sort`` of the int64 composite
     ``(segment * (K + 1) + row + 1) * 256 + letter`` (0 and ``SCORE_SKIP`` where there is no transition) does that here, and rows
     and letters are read back out of the sorted values.  ``ValueError`` if the composite would not fit 63 bits."""
+    train, prior, n_seg, (hs, hp), (vs, vp) = _check_marg(rows, letters, seg, train, prior, h, vans)
+    K, W = train.shape
+    device = train.device
+    n_t = rows.numel()
+    with torch.cuda.device(device):
+        key = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W)).values
+        letters = (key & 0xFF).to(torch.uint8)
+        rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+    scores = torch.empty((n_seg, hs.size + vs.size), dtype=torch.float64, device=device)
+    _launch(device, "bear_score_marg_f64", _ptr(rows), _ptr(letters), n_t, _ptr(seg), n_seg, W, _ptr(train), _ptr(prior), K,
+            hp, hs.size, vp, vs.size, _ptr(scores))
+    return scores
+
+
+def _check_marg(rows, letters, seg, train, prior, h, vans):
+    """What ``score_marg`` and ``score_moments`` check alike -> ``(train, prior, n_seg, (hs, its pointer), (vans, its pointer))``."""
     train = _check_rows(train, torch.int32, "train", None)
     K, W = train.shape
     device = train.device
@@ -839,18 +855,46 @@ def score_marg(rows, letters, seg, train, prior, h, vans):
         raise ValueError("every h and every vanilla pseudo-count must be > 0")
     if max(n_seg, 1) * (K + 1) * 256 >= 2 ** 63:
         raise ValueError(f"{n_seg} segments x {K} k-mers: the sort key (segment, row, letter) does not fit 63 bits")
+    return train, prior, n_seg, (hs, hp), (vs, vp)
+
+
+def _marg_sort_key(rows, letters, seg, n_seg, K, W):
+    """The int64 composite ``(segment * (K + 1) + row + 1) * 256 + letter`` of every position, in text order."""
     n_t = rows.numel()
+    live = (rows >= 0) & (rows < K) & (letters < W)
+    segment = torch.searchsorted(seg[1:], torch.arange(n_t, dtype=torch.int64, device=rows.device), right=True).clamp_(max=max(n_seg - 1, 0))
+    return (segment * (K + 1) + torch.where(live, rows.to(torch.int64) + 1, 0)) * 256 + torch.where(live, letters.to(torch.int64), SCORE_SKIP)
+
+
+def score_moments(rows, letters, seg, train, prior, h, vans, weights=None):
+    """``bear_score_moments_f64``: the exact posterior mean and variance of every segment's score -> CUDA float64 [n_seg, H + V, 2]
+    (``[..., 0]`` the mean, ``[..., 1]`` the variance as summed, not clamped), the models in ``score_marg``'s order.  With
+    ``p ~ Dirichlet(a)`` the row of a k-mer under a model (``a`` as ``score_marg`` forms it), a segment's score is the sum over its
+    transitions of ``w log p[letter]``; different k-mers are independent.  The arguments of ``score_marg``, and ``weights``: int8
+    [n_t] of +1 / -1 in text order (a mutant window's transitions count for the score, the wild type's against it), None for all +1.
+
+    The sort of ``score_marg`` carries the weights along; their prefix sum over the sorted text (one ``torch.cumsum``) gives the
+    kernel the signed count of any run in two loads."""
+    train, prior, n_seg, (hs, hp), (vs, vp) = _check_marg(rows, letters, seg, train, prior, h, vans)
+    K, W = train.shape
+    device = train.device
+    n_t = rows.numel()
+    if weights is not None:
+        _check_vec(weights, torch.int8, "weights", n_t, device=device)
+    prefix = None
     with torch.cuda.device(device):
-        live = (rows >= 0) & (rows < K) & (letters < W)
-        segment = torch.searchsorted(seg[1:], torch.arange(n_t, dtype=torch.int64, device=device), right=True).clamp_(max=max(n_seg - 1, 0))
-        key = (segment * (K + 1) + torch.where(live, rows.to(torch.int64) + 1, 0)) * 256 + torch.where(live, letters.to(torch.int64), SCORE_SKIP)
-        key = torch.sort(key).values
+        key, order = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W))
         letters = (key & 0xFF).to(torch.uint8)
         rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
-    scores = torch.empty((n_seg, hs.size + vs.size), dtype=torch.float64, device=device)
-    _launch(device, "bear_score_marg_f64", _ptr(rows), _ptr(letters), n_t, _ptr(seg), n_seg, W, _ptr(train), _ptr(prior), K,
-            hp, hs.size, vp, vs.size, _ptr(scores))
-    return scores
+        if weights is not None:
+            if n_t and not bool((weights.abs() == 1).all()):
+                raise ValueError("weights: every entry is +1 or -1")
+            prefix = torch.zeros(n_t + 1, dtype=torch.int64, device=device)
+            torch.cumsum(weights[order], 0, dtype=torch.int64, out=prefix[1:])
+    moments = torch.empty((n_seg, hs.size + vs.size, 2), dtype=torch.float64, device=device)
+    _launch(device, "bear_score_moments_f64", _ptr(rows), _ptr(letters), _ptr(prefix), n_t, _ptr(seg), n_seg, W, _ptr(train),
+            _ptr(prior), K, hp, hs.size, vp, vs.size, _ptr(moments))
+    return moments
 
 
 # ---- sequence generation over a key table (include/bear_hip.h, "Sequence generation"; kernels_generate.h) ----------------------

@@ -58,7 +58,9 @@ extern "C" {
                                   the shuffled rows: streamed and multi-rank shuffled epochs);
                                   + bear_math_probe_f64 (the device math routines one at a time: tests and diagnostics);
                                   + bear_ref_prior_rows_f64, bear_generate_whole_ref_f64 (bear_ref models downstream: scoring and
-                                  generation under a reference-mixed prior) */
+                                  generation under a reference-mixed prior);
+                                  + bear_score_moments_f64 (the exact posterior mean and variance of scores; the probe
+                                  operations BEAR_PROBE_PSI, BEAR_PROBE_PSI1) */
 #define BEAR_ROW_WIDTH 5 /* alphabet_size + 1 for dna/rna */
 
 typedef enum bear_status {
@@ -656,7 +658,8 @@ int bear_dm_items_f64(bear_ws *ws, const double *x, const uint32_t *c, uint64_t 
  *     bits);  LOG1P_SMALL[_V] log(1 + a), |a| <= 2^-8;  LOG1P_POS log(1 + a), a >= 0;  EXP_TAB / CNN_EXP_NEG exp(a), a <= 0 (0 /
  *     exp(-700) below -700);  LIN_EXP_UNITS 2^(a / 128);  STIR_LG / STIR_PSI the Stirling tails of lgamma / digamma at y = 1 / a;
  *     WAVE_SUM / WAVE_MAX the sum / the largest (of non-negative values) of each whole wave of 64 elements, in every lane of it
- *     (elements past n count as 0)
+ *     (elements past n count as 0);  PSI / PSI1 digamma / trigamma of a, a > 0 finite and normal (bear_psi, bear_psi1: the routines of
+ *     bear_score_moments_f64)
  *   item routines, x = a[i] and the count c = b[i], an exact integer >= 1 as a double (row totals pass 2^32):
  *     out0[i] = lgamma(x + c) - lgamma(x), out1[i] = digamma(x + c) - digamma(x) by
  *     SRT_GENERAL[_FAST|_AUTO] the sorted / planned family's general routine on the library log, on the table log (NaN outside
@@ -681,7 +684,9 @@ int bear_dm_items_f64(bear_ws *ws, const double *x, const uint32_t *c, uint64_t 
 #define BEAR_PROBE_SRT_GENERAL_AUTO 15
 #define BEAR_PROBE_ROW_ITEM_TAB 16
 #define BEAR_PROBE_ROW_ITEM 17
-#define BEAR_PROBE_N_OPS 18
+#define BEAR_PROBE_PSI 18
+#define BEAR_PROBE_PSI1 19
+#define BEAR_PROBE_N_OPS 20
 int bear_math_probe_f64(bear_ws *ws, int op, const double *a, const double *b, uint64_t n, double *out0, double *out1,
                         void *stream);
 
@@ -979,6 +984,28 @@ int bear_score_sum_f64(const double *lp, uint64_t n_rows, int width, uint64_t n_
 int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
                         const uint32_t *train, const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van,
                         int n_van, double *scores, void *stream);
+
+/*
+ * bear_score_moments_f64: the exact posterior mean and variance of every segment's score under n_h BEAR and n_van vanilla models
+ * (get_bear_probs / get_bear_probs_seqs with moments=True): what the mc_samples axis of bear_logdir_sample[_wide]_f64 +
+ * bear_score_sum_f64 samples, in closed form.  The arguments, models, concentrations (a_j and A bit for bit), sums, checks and
+ * status codes of bear_score_marg_f64, and
+ *   weight_prefix [dev, nullable] int64 [n_t + 1]: weight_prefix[k] = the sum of the weights (+1: the transition counts for the
+ *        score, a sequence or a mutant window; -1: against it, the wild-type window) of the SORTED positions in front of k, so
+ *        weight_prefix[0] = 0; NULL: every weight is +1.  The signed count of a stretch is the difference of two entries.
+ *   moments [dev] double [n_seg, n_h + n_van, 2]: with m_j the signed count of the run (r, j) inside segment s and M_r their sum,
+ *        moments[s, m, 0] = sum over the k-mers r of s of [sum_j m_j psi(a_j) - M_r psi(A)]                    (the mean)
+ *        moments[s, m, 1] = sum over the k-mers r of s of [sum_j m_j^2 psi1(a_j) - M_r^2 psi1(A)]              (the variance)
+ *        psi the digamma, psi1 the trigamma function (log p of p ~ Dirichlet(a) has the covariance delta_jk psi1(a_j) - psi1(A);
+ *        the k-mers are independent).  The variance comes out as summed: rounding can leave it a few ulps of its terms below 0,
+ *        nothing is clamped.  A run with m_j = 0 and a k-mer with M_r = 0 add exact zeros: psi is not evaluated for them.
+ * Holds 2 * n_t * (n_h + n_van) terms and, for a text beyond BEAR_MARG_CHUNK positions, two partial rows per BEAR_MARG_CHUNK
+ * positions, and frees them before it returns.  Refused with BEAR_ERR_INVALID_ARG before any device call: everything
+ * bear_score_marg_f64 refuses, and a misaligned weight_prefix.  n_seg = 0 is valid and launches nothing.
+ */
+int bear_score_moments_f64(const int32_t *rows, const uint8_t *letters, const int64_t *weight_prefix, uint64_t n_t, const uint64_t *seg,
+                           uint64_t n_seg, int width, const uint32_t *train, const double *prior, uint64_t n_rows, const double *h,
+                           int n_h, const double *van, int n_van, double *moments, void *stream);
 
 /*
  * Sequence generation on the device (assemble.assemble_no_ends with a DeviceCounter): every sequence grows from its end k-mer, one
