@@ -240,7 +240,12 @@ def dm_ref(train, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, train_ar=Fa
 
 class Plan(_Handle):
     """Count-dependent part of the hot path for a table that stays resident across optimizer steps
-    (work items sorted by count; include/bear_hip.h "Planned variants").  Keeps the count tensor alive."""
+    (work items sorted by count; include/bear_hip.h "Planned variants").  Keeps the count tensor alive.
+
+    Streams: construction waits for the current stream, runs on the default stream and ends in a device-wide wait (a set-up path).
+    ``self.ws`` is the workspace it was created with -- the current stream's unless one is given; a STEP on the plan launches with
+    the workspace of the stream that is current when it is enqueued (``_step_ws``), so a plan built on one stream may be stepped on
+    another.  The convolutional step alone keeps state in ``self.ws`` (its reservation) and is refused on any other stream."""
     _destroy = "bear_plan_destroy"
 
     def __init__(self, counts, ncol, ws=None, ref=None, rows_if_dense=False):
@@ -367,6 +372,23 @@ class Plan(_Handle):
         return row0, rows, items, off
 
 
+def _step_ws(plan, owns=None):
+    """The workspace a step on ``plan`` (a ``Plan`` or an ``EvalPlan``) launches with: the CURRENT stream's (``default_workspace``),
+    whichever stream the plan was built on.  A workspace serves one stream at a time (include/bear_hip.h) and a plan binds none
+    -- ``ws`` is an argument of every planned entry -- so a plan built on the default stream and stepped on a side stream must not
+    take the default stream's block partials and arrival word along (``plan.ws`` is the workspace the plan was CREATED with).
+    ``owns``: what of the step lives in ``plan.ws`` itself (the convolutional step's reservation, ``cnn_step_buffers``): such a step
+    runs on the stream that owns that workspace and is refused with a ValueError on any other.  A capturing stream resolves to the
+    device's first workspace, the default stream's; a workspace handed to the plan explicitly is the caller's to keep to one stream."""
+    ws = default_workspace((plan.counts if isinstance(plan, Plan) else plan.test).device)
+    if owns is None or ws is plan.ws:
+        return ws
+    if any(plan.ws is w for w in _default_ws.values()):
+        raise ValueError(f"one workspace serves one stream at a time: {owns} lives in the workspace of the stream this plan was built "
+                         "on, and the current stream is another one -- build the plan (and reserve) under the stream that steps it")
+    return plan.ws
+
+
 def _check_planned(plan, ncol, rows, dtype, name):
     """``rows``: the caller's aligned buffer with one row per context of a plan of ``ncol`` columns."""
     if plan.ncol != ncol:
@@ -384,10 +406,10 @@ def dm_prior_planned(plan, prior, h_signed, eps=EPSILON, out=None, normalized=Fa
         out = torch.empty(2, dtype=torch.float64, device=counts.device)
     if want_grad:
         grad = torch.empty_like(prior)
-        _launch(counts.device, "bear_dm_prior_plan_grad_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
+        _launch(counts.device, "bear_dm_prior_plan_grad_f64", _step_ws(plan).handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
                 float(h_signed), float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out), _ptr(grad))
         return out, grad
-    _launch(counts.device, "bear_dm_prior_plan_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0], float(h_signed),
+    _launch(counts.device, "bear_dm_prior_plan_f64", _step_ws(plan).handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0], float(h_signed),
             float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out))
     return out
 
@@ -398,7 +420,7 @@ def dm_ref_planned(plan, ref, h_signed, tau_signed, nu_signed, eps=EPSILON, out=
     _check_planned(plan, 4, ref, torch.int32, "ref")
     if out is None:
         out = torch.empty(4, dtype=torch.float64, device=train.device)
-    _launch(train.device, "bear_dm_ref_plan_f64", plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], float(h_signed),
+    _launch(train.device, "bear_dm_ref_plan_f64", _step_ws(plan).handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], float(h_signed),
             float(tau_signed), float(nu_signed), float(eps), int(bool(train_ar)), _ptr(out))
     return out
 
@@ -477,7 +499,7 @@ def dm_linear(plan, kmer_index, mat, h_signed, eps=EPSILON, train_ar=False, out=
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=mat.device)
     grad = torch.empty_like(mat)
-    _launch(mat.device, "bear_dm_linear_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), _ptr(mat), mat.shape[0], n,
+    _launch(mat.device, "bear_dm_linear_f64", _step_ws(plan).handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), _ptr(mat), mat.shape[0], n,
             float(h_signed), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
@@ -523,7 +545,9 @@ def evaluate_wide(test, prior, h, van_reg, train=None, eps=EPSILON, with_ar=True
 class EvalPlan(_Handle):
     """Sorted plan of a resident TEST column (``bear_eval_plan_create``): per tile the cells and row totals with a non-zero
     count, sorted by count, and the rows whose largest counts in the conditioning column ``train`` tie.  Keeps the count
-    tensors alive; built asynchronously on the current stream."""
+    tensors alive; built asynchronously on the current stream (an evaluation enqueued on ANOTHER stream is not ordered behind the
+    build: order the two yourself).  An evaluation launches with the workspace of the stream current at the call (``_step_ws``),
+    not with ``self.ws``; destroying the plan frees device memory, which waits for the device."""
     _destroy = "bear_eval_plan_destroy"
 
     def __init__(self, test, train=None, ws=None):
@@ -558,7 +582,7 @@ def evaluate_planned(plan, prior, h, van_reg, eps=EPSILON, with_ar=True, noise_s
         raise ValueError("a planned evaluation decides the vanilla models' arg-max on the integer counts: it needs 1750 eps < 0.5 "
                          "and 0 <= van_reg <= 2^30 (kernels.evaluate takes any values)")
     out = torch.empty(2 * (hs.size + vs.size) + 3, dtype=torch.float64, device=test.device)
-    _launch(test.device, "bear_eval_plan_f64", plan.ws.handle, plan._h, _ptr(test), _ptr(train), _ptr(prior), n, hp, hs.size,
+    _launch(test.device, "bear_eval_plan_f64", _step_ws(plan).handle, plan._h, _ptr(test), _ptr(train), _ptr(prior), n, hp, hs.size,
             int(bool(with_ar)), vp, vs.size, float(eps), int(noise_seed), int(row_base), _ptr(row_ids), _ptr(out))
     return out
 
@@ -1087,7 +1111,7 @@ def kmer_order(kmer_code, lag):
 def kmer_order_scratch_bytes(n_rows, lag):
     """Device scratch ``bear_kmer_order_u64`` asks of its caller for a batch of n_rows contexts."""
     nbytes = ctypes.c_uint64(0)
-    _lib.call("bear_kmer_order_u64", None, int(n_rows), int(lag), None, None, ctypes.byref(nbytes), None)
+    _lib.call("bear_kmer_order_u64", None, int(n_rows), int(lag), None, None, ctypes.byref(nbytes), _stream())   # (a size query launches nothing)
     return int(nbytes.value)
 
 
@@ -1155,7 +1179,7 @@ def cnn_forward(kmer_code, flat_params, lag, filter_width, save=True, ws=None, p
             raise ValueError("plan: built for another number of rows than kmer_code holds")
         prior = torch.empty((n, 5), dtype=torch.float64, device=kmer_code.device)
         t1 = torch.empty((n, CNN_LAYER1_WIDTH), dtype=torch.float64, device=kmer_code.device)
-        _launch(kmer_code.device, "bear_cnn_forward_plan_f64", plan.ws.handle, plan._h, _ptr(kmer_code), n, int(lag), int(filter_width),
+        _launch(kmer_code.device, "bear_cnn_forward_plan_f64", _step_ws(plan).handle, plan._h, _ptr(kmer_code), n, int(lag), int(filter_width),
                 CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(flat_params), _ptr(prior), _ptr(t1))
         return prior, t1
     ws = ws or default_workspace(kmer_code.device)
@@ -1378,7 +1402,7 @@ def dm_prior_planned_dev(plan, prior, h_signed_dev, eps=EPSILON, out=None, norma
     if out is None:
         out = torch.empty(2, dtype=torch.float64, device=counts.device)
     grad = torch.empty_like(prior) if want_grad else None
-    _launch(counts.device, "bear_dm_prior_plan_dev_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
+    _launch(counts.device, "bear_dm_prior_plan_dev_f64", _step_ws(plan).handle, plan._h, _ptr(counts), _ptr(prior), counts.shape[0],
             _ptr(h_signed_dev), float(eps), int(bool(train_ar)), int(bool(normalized)), _ptr(out), _ptr(grad))
     return (out, grad) if want_grad else out
 
@@ -1398,7 +1422,7 @@ def dm_refmix_planned_dev(plan, net_rows, ref_rows, h_signed_dev, tau_signed_dev
         out = torch.empty(4, dtype=torch.float64, device=counts.device)
     _f64_vec(out, 4, "out")
     grad = torch.empty_like(net_rows)
-    _launch(counts.device, "bear_dm_refmix_plan_grad_f64", plan.ws.handle, plan._h, _ptr(counts), _ptr(net_rows), _ptr(ref_rows), n,
+    _launch(counts.device, "bear_dm_refmix_plan_grad_f64", _step_ws(plan).handle, plan._h, _ptr(counts), _ptr(net_rows), _ptr(ref_rows), n,
             _ptr(h_signed_dev), _ptr(tau_signed_dev), _ptr(net_weight_signed_dev), float(eps), int(bool(train_ar)), _ptr(out), _ptr(grad))
     return out, grad
 
@@ -1420,7 +1444,7 @@ def ref_train_reduce(plan, ref, theta, packed, eps=EPSILON, train_ar=False):
     _check_planned(plan, 4, ref, torch.int32, "ref")
     _f64_vec(theta, 3, "theta")
     _f64_vec(packed, 4, "packed")
-    _launch(train.device, "bear_ref_train_reduce_f64", plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta),
+    _launch(train.device, "bear_ref_train_reduce_f64", _step_ws(plan).handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta),
             float(eps), int(bool(train_ar)), _ptr(packed))
 
 
@@ -1431,7 +1455,7 @@ def ref_train_step(plan, ref, theta, adam_m, adam_v, adam_t, learning_rate, scal
     _check_planned(plan, 4, ref, torch.int32, "ref")
     for t, n, name in ((theta, 3, "theta"), (adam_m, 3, "adam_m"), (adam_v, 3, "adam_v"), (adam_t, 1, "adam_t"), (out, 4, "out")):
         _f64_vec(t, n, name)
-    _launch(train.device, "bear_ref_train_step_f64", plan.ws.handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta),
+    _launch(train.device, "bear_ref_train_step_f64", _step_ws(plan).handle, plan._h, _ptr(train), _ptr(ref), train.shape[0], _ptr(theta),
             _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), float(eps), int(bool(train_ar)), float(learning_rate), float(scale), _ptr(out),
             *_loss(loss_buf))
 
@@ -1450,7 +1474,7 @@ def net_linear_train_reduce(plan, kmer_code, lag, theta, packed, eps=EPSILON, tr
     """Enqueues ``bear_net_linear_train_reduce_f64``: packed = [sum LL, d/dh_s, d/d mat (lag*25)] of this shard, theta = {h_signed, mat}
     device-resident."""
     n = _check_linear_step(plan, kmer_code, lag, theta, packed)
-    _launch(theta.device, "bear_net_linear_train_reduce_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n,
+    _launch(theta.device, "bear_net_linear_train_reduce_f64", _step_ws(plan).handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n,
             _ptr(theta), float(eps), int(bool(train_ar)), _ptr(packed))
 
 
@@ -1461,7 +1485,7 @@ def net_linear_train_step(plan, kmer_code, lag, theta, adam_m, adam_v, adam_t, p
     size = 1 + lag * 25
     for t, k in ((adam_m, size), (adam_v, size), (adam_t, 1)):
         _f64_vec(t, k, "adam state")
-    _launch(theta.device, "bear_net_linear_train_step_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n,
+    _launch(theta.device, "bear_net_linear_train_step_f64", _step_ws(plan).handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), int(lag), n,
             _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), _ptr(packed), float(eps), int(bool(train_ar)), float(learning_rate),
             float(scale), *_loss(loss_buf))
 
@@ -1532,15 +1556,19 @@ def net_linear_train_step_wide(counts, codes, lag, theta, adam_m, adam_v, adam_t
             float(scale), _ptr(packed), *_loss(loss_buf))
 
 
+_CNN_RESERVATION = "the convolutional step's reservation (cnn_step_buffers)"
+
+
 def net_cnn_train_reduce(plan, kmer_code, lag, filter_width, theta, bufs, packed, eps=EPSILON, train_ar=False):
     """Enqueues ``bear_net_cnn_train_reduce_f64``: forward, planned DM kernel with gradient rows, backward;
-    packed = [sum LL, d/dh_s, d/d params] of this shard.  ``bufs`` = (prior [n,5], t1 [n,16], grad_rows [n,5]) from ``cnn_step_buffers``."""
+    packed = [sum LL, d/dh_s, d/d params] of this shard.  ``bufs`` = (prior [n,5], t1 [n,16], grad_rows [n,5]) from ``cnn_step_buffers``.
+    The reservation lives in ``plan.ws``: the step runs on the stream that workspace belongs to (``_step_ws``; ValueError otherwise)."""
     n = plan.counts.shape[0]
     prior, t1, grad_rows = bufs
     np_ = cnn_param_count(lag, filter_width)
     _f64_vec(theta, 1 + np_, "theta")
     _f64_vec(packed, 2 + np_, "packed")
-    _launch(theta.device, "bear_net_cnn_train_reduce_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag),
+    _launch(theta.device, "bear_net_cnn_train_reduce_f64", _step_ws(plan, owns=_CNN_RESERVATION).handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag),
             int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(theta), _ptr(prior), _ptr(t1), _ptr(grad_rows), float(eps),
             int(bool(train_ar)), _ptr(packed))
 
@@ -1548,13 +1576,14 @@ def net_cnn_train_reduce(plan, kmer_code, lag, filter_width, theta, bufs, packed
 def net_cnn_train_step(plan, kmer_code, lag, filter_width, theta, adam_m, adam_v, adam_t, bufs, packed, learning_rate, scale, loss_buf=None,
                        eps=EPSILON, train_ar=False):
     """Enqueues one ``bear_net_cnn_train_step_f64`` (HIP-graph capturable): theta = {h_signed, flat CNN parameters} on the device;
-    ``bufs`` = (prior [n,5], t1 [n,16], grad_rows [n,5]) lent by the caller (``cnn_step_buffers``)."""
+    ``bufs`` = (prior [n,5], t1 [n,16], grad_rows [n,5]) lent by the caller (``cnn_step_buffers``).  Like the reduce, on the stream
+    that owns ``plan.ws`` only."""
     n = plan.counts.shape[0]
     prior, t1, grad_rows = bufs
     np_ = cnn_param_count(lag, filter_width)
     _f64_vec(theta, 1 + np_, "theta")
     _f64_vec(packed, 2 + np_, "packed")
-    _launch(theta.device, "bear_net_cnn_train_step_f64", plan.ws.handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag),
+    _launch(theta.device, "bear_net_cnn_train_step_f64", _step_ws(plan, owns=_CNN_RESERVATION).handle, plan._h, _ptr(plan.counts), _ptr(kmer_code), n, int(lag),
             int(filter_width), CNN_NUM_FILTERS, CNN_LAYER1_WIDTH, _ptr(theta), _ptr(adam_m), _ptr(adam_v), _ptr(adam_t), _ptr(prior),
             _ptr(t1), _ptr(grad_rows), _ptr(packed), float(eps), int(bool(train_ar)), float(learning_rate), float(scale), *_loss(loss_buf))
 

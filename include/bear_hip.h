@@ -916,7 +916,10 @@ int bear_kmer_sort_create_range(const uint8_t *text, const uint8_t *group, uint6
 /*
  * Variant and sequence scoring on the device (get_var_probs.get_bear_probs / get_bear_probs_seqs with a DeviceCounter): what
  * stands between a count table in device memory and the samplers' tables above, and the exact marginal of whole segments, which
- * needs no table.  All four are asynchronous on `stream`.
+ * needs no table.  All four launch on `stream`; the look-ups (bear_score_transitions_u64, bear_kmer_find_u64) and a
+ * bear_score_sum_f64 over a text of at most BEAR_SCORE_CHUNK positions are asynchronous, the entries that hold scratch of their own
+ * (bear_score_sum_f64 beyond that, bear_score_marg_f64, bear_score_moments_f64) free it before they return, which waits for the
+ * device: their outputs are then complete, and they do not belong inside a graph capture.
  *
  * The symbol text: uint8 codes as in the counting text -- letters 0 .. width - 2, the stop ']' = width - 1, the start '[' = width
  * -- with every start and stop written out (nothing is padded implicitly), cut into n_seg segments by

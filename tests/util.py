@@ -30,6 +30,13 @@ def abi_header(path=HEADER):
     return int(re.search(r"#define BEAR_ABI_VERSION (\d+)", src).group(1)), sigs
 
 
+def stream_entries(path=HEADER):
+    """The functions ``path`` declares with ``void *stream`` as their last parameter, in the header's order."""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    decls = re.findall(r"^(?:int|uint64_t|const char \*) ?(bear_[a-z0-9_]+)\(([^()]*)\);", src, flags=re.M)
+    return [name for name, params in decls if " ".join(params.split(",")[-1].split()) == "void *stream"]
+
+
 def sparse_table(n, seed=0, lam_scale=1.0):
     """NumPy twin (same recipe, not the same bits) of the 'k=13 sparse' synthetic table."""
     rng = np.random.default_rng(seed)
