@@ -1,11 +1,12 @@
 // bear_eval.hip -- held-out evaluation and the BMM marginal (kernels_eval.h), their 21-wide forms and the wide DM step
 // (kernels_wide.h), bear_ref's wide steps (kernels_refmix_wide.h), evaluation on a sorted plan of the test column
-// (kernels_evalplan.h).  The other units: bear_host.h.
+// (kernels_evalplan.h), the two-sample Bayes factors of two count columns (kernels_twosample.h).  The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_eval.h"
 #include "kernels_wide.h"
 #include "kernels_refmix_wide.h"
 #include "kernels_evalplan.h"
+#include "kernels_twosample.h"
 
 #ifdef EVP_STAMPS
 #define EVP_DBG_ARG , ws->dbg
@@ -145,6 +146,50 @@ int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train,
     BEAR_DISPATCH_W(width, hipLaunchKernelGGL(eval_wide_kernel<W>, dim3(grid), dim3(EVW_THREADS), 0, s, test, train, prior, n_rows, A, m0,
                                               m_cnt, common, lt, ws->eval_partials));
     hipLaunchKernelGGL(eval_sorted_finalize_kernel, dim3((EVS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, S, out);
+  }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// ---- two-sample and goodness-of-fit Bayes factors (kernels_twosample.h) ----------------------------------------------------
+// Every refusal comes before the first device call; h and van are read here, before the entry returns (they travel by value).
+int bear_two_sample_f64(bear_ws *ws, const uint32_t *a, const uint32_t *b, const double *prior, uint64_t n_rows, int width,
+                        const double *h, int n_h, const double *van, int n_van, void *stream, double *out, double *out_ar,
+                        double *row_terms) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  if (n_h < 0 || n_van < 0 || n_h + n_van < 1 || n_h + n_van > BEAR_TWO_SAMPLE_MAX_MODELS) return BEAR_ERR_INVALID_ARG;
+  if ((n_h && !h) || (n_van && !van) || (n_rows && (n_h || out_ar) && !prior)) return BEAR_ERR_INVALID_ARG;
+  if (!ws || !out || (n_rows && (!a || !b))) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(a) || misaligned(b) || misaligned(prior) || misaligned8(out) || misaligned8(out_ar) || misaligned8(row_terms))
+    return BEAR_ERR_INVALID_ARG;
+  ts_args A;
+  memset(&A, 0, sizeof(A));
+  A.n_h = n_h;
+  A.n_models = n_h + n_van;
+  for (int j = 0; j < n_h; ++j) {
+    if (!(h[j] > 0.0 && h[j] < INFINITY)) return BEAR_ERR_INVALID_ARG;
+    A.w[j] = 1.0 / h[j];
+  }
+  for (int k = 0; k < n_van; ++k) {
+    if (!(van[k] > 0.0 && van[k] < INFINITY)) return BEAR_ERR_INVALID_ARG;
+    A.w[n_h + k] = van[k];
+  }
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  static_assert(TS_NOUT <= EVL_MAX_OUT, "compact partials fit the evaluation partial buffer");
+  uint64_t cap = ws_blocks(ws, TS_BLOCKS_PER_CU);
+  if (cap > (uint64_t)ws->eval_blocks) cap = (uint64_t)ws->eval_blocks;
+  const int grid = grid_capped((n_rows + TS_TILE(width) - 1) / TS_TILE(width), cap);
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+  for (int m0 = 0; m0 < A.n_models; m0 += TS_CHUNK) {
+    const int m_cnt = A.n_models - m0 < TS_CHUNK ? A.n_models - m0 : TS_CHUNK;
+    const int do_ar = m0 == 0 && out_ar;
+    const int use_prior = do_ar || m0 < n_h;
+    BEAR_DISPATCH_W(width, hipLaunchKernelGGL(two_sample_kernel<W>, dim3(grid), dim3(TS_THREADS), 0, s, a, b, prior, n_rows, A, m0, m_cnt,
+                                              use_prior, do_ar, lt, ws->eval_partials, row_terms));
+    hipLaunchKernelGGL(two_sample_finalize_kernel, dim3((TS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, m0, m_cnt, out,
+                       do_ar ? out_ar : nullptr);
   }
   HIP_TRY(hipGetLastError());
   return BEAR_OK;

@@ -597,6 +597,42 @@ def bmm(counts, alpha, ws=None):
     return out
 
 
+TWO_SAMPLE_MAX_MODELS = 16                          # BEAR_TWO_SAMPLE_MAX_MODELS: BEAR and vanilla models of one call
+TWO_SAMPLE_TILE = {21: 128, 5: 512}                 # TS_TILE, TS_BLOCKS_PER_CU of kernels_twosample.h: a launch takes
+TWO_SAMPLE_BLOCKS_PER_CU = 3                        # min(tiles, blocks per CU * CUs) blocks -- tests size a table beyond that
+
+
+def two_sample(a, b, prior, h, vans, want_ar=False, want_rows=False, ws=None):
+    """``bear_two_sample_f64``: the sums of the two-sample and goodness-of-fit Bayes factors over the rows of two count columns
+    ``a``, ``b`` [N, W] (uint32 in int32 storage) -> ``(out [H + V, 4] = {M_a, M_b, M_ab, B}, out_ar [2] = {L_a, L_b} or None,
+    row_terms [N, H + V] = B_k or None)``, CUDA float64; the H BEAR models (``prior / h``) first, then the V vanilla ones.
+    ``prior`` float64 [N, W] or None; ``h``, ``vans``: host values, each > 0 and finite.  One asynchronous call on the current
+    stream.  The entry's stream is not its last argument (include/bear_hip.h says why), so the call does not go through
+    ``_launch``."""
+    a = _check_rows(a, torch.int32, "a", None)
+    n, width = a.shape
+    b = _check_rows(b, torch.int32, "b", width, n=n)
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", width, n=n)
+    if b.device != a.device or (prior is not None and prior.device != a.device):
+        raise ValueError("a, b and prior must be on one device")
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
+    if (hs.size or want_ar) and prior is None:
+        raise ValueError("the BEAR models (h) and the AR model's likelihood (want_ar) need prior rows")
+    if not 1 <= hs.size + vs.size <= TWO_SAMPLE_MAX_MODELS:
+        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{TWO_SAMPLE_MAX_MODELS}")
+    if not (np.all(hs > 0) and np.all(vs > 0) and np.all(np.isfinite(hs)) and np.all(np.isfinite(vs))):
+        raise ValueError("every h and every vanilla pseudo-count must be > 0 and finite")
+    ws = ws or default_workspace(a.device)
+    out = torch.empty((hs.size + vs.size, 4), dtype=torch.float64, device=a.device)
+    out_ar = torch.empty(2, dtype=torch.float64, device=a.device) if want_ar else None
+    rows = torch.empty((n, hs.size + vs.size), dtype=torch.float64, device=a.device) if want_rows else None
+    with torch.cuda.device(a.device):
+        _lib.call("bear_two_sample_f64", ws.handle, _ptr(a), _ptr(b), _ptr(prior), n, width, hp, hs.size, vp, vs.size, _stream(),
+                  _ptr(out), _ptr(out_ar), _ptr(rows))
+    return out, out_ar, rows
+
+
 def synth_counts(seed, row0, n_rows, device, dense=False, want=("train", "test", "ref")):
     """Rows [row0, row0+n_rows) of the synthetic k=13 table, generated on the device."""
     bufs = {k: torch.empty((n_rows, 5), dtype=torch.int32, device=device) for k in want}

@@ -637,6 +637,38 @@ int bear_bmm_f64(bear_ws *ws, const uint32_t *counts, uint64_t n_rows, const dou
                  void *stream);
 
 /*
+ * bear_two_sample_f64: hypothesis tests on two count columns a, b of one table (kernels_twosample.h), one pass over its rows.
+ * Per context k and model, with concentrations alpha_j > 0 and A = alpha_0 + ... + alpha_(W-1) added in that order,
+ *   T(c) = lgamma(A) - lgamma(A + n) + sum_j [lgamma(alpha_j + c_j) - lgamma(alpha_j)],   n = sum_j c_j
+ * -- the log marginal of the transitions as SEQUENCES (no multinomial coefficient, as bear_score_marg_f64: the coefficient of a
+ * pooled row is not the product of the two).  Models in bear_score_marg_f64's order: n_h BEAR models alpha_j = prior[k, j] *
+ * (1.0 / h_m), then n_van vanilla models alpha_j = van.
+ *   a, b   [dev] uint32 [n_rows, W], prior [dev, nullable] double [n_rows, W]: 16-byte aligned; `width` W: 5 or 21.  A prior entry
+ *          under a non-zero count must be > 0.
+ *   h [host] n_h values, van [host] n_van values, each > 0 and finite: read before the entry returns;
+ *          1 <= n_h + n_van <= BEAR_TWO_SAMPLE_MAX_MODELS.
+ *   out    [dev] double [n_h + n_van, 4] = { M_a, M_b, M_ab, B }: M_a = sum_k T(a_k), M_b = sum_k T(b_k), M_ab = sum_k T(a_k + b_k),
+ *          B = sum_k B_k with B_k = (T(a_k) + T(b_k)) - T(a_k + b_k) formed PER ROW: the log Bayes factor of "two distributions"
+ *          over "one" (positive favours different).  A row with n_a = 0 or n_b = 0 has B_k = 0.0 exactly (no lgamma is evaluated
+ *          for it; its T still enters M_a or M_b, and M_ab with the same bits); pooled counts are exact beyond 2^32.
+ *   out_ar [dev, nullable] double [2] = { L_a, L_b }, L_a = sum_k sum_{j: a_j > 0} a_j log(prior[k, j]): the AR model's
+ *          log-likelihood of each sample; M_a[m] - L_a is the goodness-of-fit log Bayes factor of BEAR(h_m) over its AR model.
+ *   row_terms [dev, nullable] double [n_rows, n_h + n_van] = B_k.  out, out_ar, row_terms: 8-byte aligned.
+ * Asynchronous on `stream`, allocates nothing; at most four models a launch, sixteen in four; per-thread -> wave -> block partial
+ * -> fixed-order sum, no atomics: equal inputs give equal bits (for a given n_rows) in both libraries.  n_rows = 0 writes zeros.
+ * BEAR_ERR_INVALID_ARG, before any device call: a width other than 5 or 21, n_h > 0 or out_ar without prior (of a table with rows:
+ * as a, b, it may be NULL when n_rows = 0), an h or van that is
+ * not > 0 and finite, n_h + n_van of 0 or beyond the maximum, a missing or misaligned pointer.
+ * The stream is deliberately NOT the last parameter: tests/test_stream_contract_gpu.py keeps a row for every declaration that ends
+ * in `void *stream`, and this entry came after that table.  The contract is not waived: tests/test_two_sample_gpu.py holds the
+ * entry to it with the same harness (tests/stream_util.py).
+ */
+#define BEAR_TWO_SAMPLE_MAX_MODELS 16
+int bear_two_sample_f64(bear_ws *ws, const uint32_t *a, const uint32_t *b, const double *prior, uint64_t n_rows, int width,
+                        const double *h, int n_h, const double *van, int n_van, void *stream,
+                        double *out, double *out_ar, double *row_terms);
+
+/*
  * The primitive underneath both entry points, item by item (tests / diagnostics): for x > 0 and
  * integer c >= 0,  D[i] = lgamma(x+c) - lgamma(x)  and  P[i] = digamma(x+c) - digamma(x)
  * -- the two quantities TFP's lbeta and its autodiff yield in bear_model/core.py:73-74.
