@@ -1,11 +1,12 @@
 // bear_score.hip -- scoring on the device: the entries between the device count tables and the samplers' tables
 // (include/bear_hip.h, "Variant and sequence scoring"): symbols -> look-up keys, keys -> rows of a sorted key table, and the sums
-// of a sampled table's rows over the transitions of every segment; the exact marginal of every segment and the exact posterior
+// of a sampled table's rows over the transitions of every segment; the exact marginal of every segment (under one column, or under
+// every column of a table with a leave-one-out column per segment) and the exact posterior
 // mean and variance of every segment's score, which need no table -- and
 // sequence generation over the same key tables ("Sequence generation": flanks of given lengths, and whole sequences from start to
 // stop) -- and, for bear_ref models, the reference-mixed prior rows of queried k-mers and whole sequences under such a model.
 // The only unit that includes -- and so emits --
-// kernels_score.h, kernels_marg.h, kernels_moments.h, kernels_refscore.h and kernels_generate.h.
+// kernels_score.h, kernels_marg.h, kernels_groups.h, kernels_moments.h, kernels_refscore.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 #include "bear_dev.h"
 #include "bear_release_guard.h"
 #include "kernels_generate.h"
+#include "kernels_groups.h"
 #include "kernels_marg.h"
 #include "kernels_moments.h"
 #include "kernels_refscore.h"
@@ -201,22 +203,52 @@ int mrg_prepare(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const
   return BEAR_OK;
 }
 
-// ... and the sums behind their terms [M, n_t]: scores [n_seg, M]
-int mrg_sums(const dev_buf<double> &terms, uint64_t M, const uint64_t *seg, uint64_t n_seg, uint64_t n_t, double *scores,
-             hipStream_t s) {
-  dev_buf<double> partials;              // two partial rows per MRG_CHUNK positions of a long text
-  if (n_t > MRG_CHUNK) {                 // only such a text can hold a long segment
-    const uint64_t n_blocks = (n_t + MRG_CHUNK - 1) / MRG_CHUNK;
-    HIP_TRY(partials.alloc(2 * n_blocks * M));
-    hipLaunchKernelGGL(marg_chunk_kernel, dim3(scr_grid(n_blocks, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms.get(), (uint32_t)M, seg,
-                       n_seg, n_t, n_blocks, partials.get());
+// ... and the sums behind their terms [M, n_t]: scores [n_seg, M].  partials: two rows per MRG_CHUNK positions of a text of
+// n_blocks > 0 chunks (only a text beyond one chunk can hold a long segment); not read otherwise.
+int mrg_sum_launches(const double *terms, uint64_t M, const uint64_t *seg, uint64_t n_seg, uint64_t n_t, uint64_t n_blocks,
+                     double *partials, double *scores, hipStream_t s) {
+  if (n_blocks) {
+    hipLaunchKernelGGL(marg_chunk_kernel, dim3(scr_grid(n_blocks, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms, (uint32_t)M, seg, n_seg,
+                       n_t, n_blocks, partials);
     HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(marg_sum_kernel, dim3(scr_grid(n_seg, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms.get(), (uint32_t)M, seg, n_seg,
-                     n_t, partials.get(), scores);
+  hipLaunchKernelGGL(marg_sum_kernel, dim3(scr_grid(n_seg, 1), (unsigned)M), dim3(MRG_WAVE), 0, s, terms, (uint32_t)M, seg, n_seg, n_t,
+                     partials, scores);
   HIP_TRY(hipGetLastError());
-  return BEAR_OK;      // (partials goes with this frame: hipFree waits for the launches)
+  return BEAR_OK;
 }
+
+// the chunks of a text: 0 up to MRG_CHUNK positions
+uint64_t mrg_chunk_blocks(uint64_t n_t) { return n_t > MRG_CHUNK ? (n_t + MRG_CHUNK - 1) / MRG_CHUNK : 0; }
+
+// the sums of bear_score_marg_f64 and bear_score_moments_f64, which hold their partial rows in a dev_buf
+int mrg_sums(const dev_buf<double> &terms, uint64_t M, const uint64_t *seg, uint64_t n_seg, uint64_t n_t, double *scores,
+             hipStream_t s) {
+  dev_buf<double> partials;
+  const uint64_t n_blocks = mrg_chunk_blocks(n_t);
+  if (n_blocks) HIP_TRY(partials.alloc(2 * n_blocks * M));
+  return mrg_sum_launches(terms.get(), M, seg, n_seg, n_t, n_blocks, partials.get(), scores, s);
+  // (partials goes with this frame: hipFree waits for the launches)
+}
+
+// Scratch of bear_score_groups_f64: taken from and given back to the device's memory pool IN STREAM ORDER (hipMallocAsync /
+// hipFreeAsync), so the entry neither waits for its stream nor for the device.  Given back with the owner, behind whatever the
+// entry has launched on the stream by then.
+class stream_buf {
+ public:
+  explicit stream_buf(hipStream_t s) : s_(s) {}
+  stream_buf(const stream_buf &) = delete;
+  stream_buf &operator=(const stream_buf &) = delete;
+  ~stream_buf() {
+    if (p_) (void)hipFreeAsync(p_, s_);
+  }
+  double *get() const { return p_; }
+  hipError_t alloc(size_t n) { return hipMallocAsync(reinterpret_cast<void **>(&p_), n * sizeof(double), s_); }
+
+ private:
+  hipStream_t s_;
+  double *p_ = nullptr;
+};
 }  // namespace
 
 extern "C" {
@@ -259,6 +291,32 @@ int bear_score_moments_f64(const int32_t *rows, const uint8_t *letters, const in
     HIP_TRY(hipGetLastError());
   }
   return mrg_sums(terms, M, seg, n_seg, n_t, moments, s);     // plane 2 m + k of segment i lands at moments[i, m, k]
+}
+
+int bear_score_groups_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int width,
+                          const uint32_t *train, int n_groups, const double *prior, uint64_t n_rows, const int32_t *own,
+                          const double *h, int n_h, const double *van, int n_van, void *stream, double *scores, uint8_t *short_of) {
+  if (n_groups < 1 || n_groups > BEAR_GROUPS_MAX) return BEAR_ERR_INVALID_ARG;
+  mrg_models P;
+  const int st = mrg_prepare(rows, letters, n_t, seg, n_seg, width, train, prior, n_rows, h, n_h, van, n_van, scores, (uint64_t)n_groups, P);
+  if (st != BEAR_OK) return st;
+  if (own && misaligned4(own)) return BEAR_ERR_INVALID_ARG;
+  if (n_seg == 0) return BEAR_OK;
+  if (!short_of) return BEAR_ERR_INVALID_ARG;
+  const uint64_t M = (uint64_t)n_groups * (uint64_t)P.n_m;    // planes: group-major, a group's models as bear_score_marg_f64 orders them
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemsetAsync(short_of, 0, n_seg, s));
+  stream_buf terms(s), partials(s);
+  const uint64_t n_blocks = mrg_chunk_blocks(n_t);
+  if (n_t) {
+    HIP_TRY(terms.alloc(n_t * M));
+    if (n_blocks) HIP_TRY(partials.alloc(2 * n_blocks * M));
+    const dim3 grid(scr_grid(n_t, MRG_THREADS)), block(MRG_THREADS);
+    LAUNCH_BY_WIDTH(width, groups_terms_kernel<5>, groups_terms_kernel<21>, grid, block, 0, s, rows, letters, n_t, seg, n_seg, train,
+                    (uint32_t)n_groups, n_h > 0 ? prior : nullptr, n_rows, own, P, terms.get(), short_of);
+    HIP_TRY(hipGetLastError());
+  }
+  return mrg_sum_launches(terms.get(), M, seg, n_seg, n_t, n_blocks, partials.get(), scores, s);   // scores [n_seg, n_groups, n_m]
 }
 
 int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,

@@ -334,7 +334,84 @@ def _symbol_lut(alphabet_name):
     return lut
 
 
-class DeviceCounter:
+class _KeyLookup:
+    """What ``DeviceCounter`` and ``classify.GroupCounter`` share: the k-mers of a table in HBM as a look-up -- ``kmers`` uint8
+    [N, lag] (ASCII) and their keys sorted once (``keys`` int64 [N'] ascending, ``perm`` their rows)."""
+
+    _counts_shape = "[N, W]"          # the counts a subclass holds per k-mer: the first axis is the k-mers', the last has W entries
+
+    def _build_lookup(self, kmers, counts, alphabet_name, no_end):
+        if not (isinstance(kmers, torch.Tensor) and kmers.is_cuda and kmers.dtype == torch.uint8 and kmers.dim() == 2):
+            raise ValueError("kmers must be a CUDA uint8 tensor [N, lag] of ASCII k-mers")
+        if not (isinstance(counts, torch.Tensor) and counts.device == kmers.device and counts.dtype == torch.int32
+                and counts.dim() == len(self._counts_shape.split(",")) and counts.shape[0] == kmers.shape[0]):
+            raise ValueError(f"counts must be a CUDA int32 tensor {self._counts_shape} on the k-mers' device")
+        self.alphabet_name, self.no_end = alphabet_name, bool(no_end)
+        self.rank = kernels.score_ranks(alphabet_name)
+        self.width, self.lag = len(self.rank) - 1, int(kmers.shape[1])
+        if counts.shape[-1] != self.width:
+            raise ValueError(f"counts: rows of {counts.shape[-1]}, the alphabet {alphabet_name!r} has rows of {self.width}")
+        if not 1 <= self.lag <= kernels.SCORE_MAX_LAG[self.width]:
+            raise ValueError(f"lag {self.lag}: a look-up key holds contexts of 1..{kernels.SCORE_MAX_LAG[self.width]} letters of {alphabet_name!r}")
+        self.kmers, self.counts = kmers.contiguous(), counts.contiguous()
+        self._lut = _symbol_lut(alphabet_name)
+        keys = self._keys_of_codes(torch.from_numpy(self._lut).to(kmers.device)[self.kmers.long()])
+        held = torch.nonzero(keys >= 0).reshape(-1)
+        self.keys, order = torch.sort(keys[held])
+        self.perm = held[order]
+        if self.keys.numel() > 1 and bool((self.keys[1:] == self.keys[:-1]).any()):
+            raise ValueError(f"{type(self).__name__}: the table holds a k-mer twice")
+
+    @property
+    def device(self):
+        return self.kmers.device
+
+    def _keys_of_codes(self, codes):
+        """Keys int64 [n] of k-mers given as symbol codes uint8 [n, lag] on the device (-1: a symbol that is no letter of a context):
+        every k-mer becomes a segment of lag + 1 symbols, the k-mer and a stop, whose one transition carries the k-mer's key."""
+        n = codes.shape[0]
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64, device=codes.device)
+        text = torch.cat([codes, torch.full((n, 1), self.width - 1, dtype=torch.uint8, device=codes.device)], 1).reshape(-1)
+        seg = torch.arange(n + 1, dtype=torch.int64, device=codes.device) * (self.lag + 1)
+        keys, _ = kernels.score_transitions(text, seg, self.lag, self.rank)
+        return keys.reshape(n, self.lag + 1)[:, self.lag].contiguous()
+
+    def _find(self, keys):
+        """Per key (int64 [n] on the device) ``(idx int64, keep bool)``: its place in ``perm`` (0 where it is absent) and whether its
+        counts are to be read at all -- not for an absent k-mer, nor, under ``no_end``, for a context that holds ``[``."""
+        idx = kernels.kmer_find(self.keys, keys.contiguous())
+        keep = idx >= 0
+        if self.no_end:
+            bits, start = kernels.SCORE_BITS[self.width], int(self.rank[self.width])
+            shifts = torch.arange(self.lag, dtype=torch.int64, device=self.device) * bits
+            keep = keep & ~(((keys[:, None] >> shifts[None, :]) & ((1 << bits) - 1)) == start).any(1)
+        return idx.clamp(min=0).long(), keep
+
+    def rows_of_keys(self, keys):
+        """Count rows int32 [n, W] (``counts`` [N, G, W]: [n, G, W]) of the k-mers with the given keys (int64 [n] on the device;
+        ascending is the fast order): zeros for an absent k-mer; under ``no_end`` also for a context that holds ``[``, and in the
+        stop column."""
+        idx, keep = self._find(keys)
+        rows = self.counts[self.perm[idx]] if self.keys.numel() else \
+            torch.zeros((keys.numel(),) + tuple(self.counts.shape[1:]), dtype=torch.int32, device=self.device)
+        rows = rows * keep.reshape((-1,) + (1,) * (rows.dim() - 1)).to(torch.int32)
+        if self.no_end:
+            rows[..., -1] = 0
+        return rows.contiguous()
+
+    def codes_of_keys(self, keys):
+        """``core.encode_kmers`` codes int8 [n, lag] (letters 0 .. A - 1, ``[`` = A) of the k-mers with the given valid keys."""
+        bits = kernels.SCORE_BITS[self.width]
+        code_of_rank = np.zeros(1 << bits, dtype=np.int8)
+        code_of_rank[self.rank[:self.width - 1]] = np.arange(self.width - 1)
+        code_of_rank[self.rank[self.width]] = self.width - 1
+        shifts = torch.arange(self.lag - 1, -1, -1, dtype=torch.int64, device=self.device) * bits
+        ranks = (keys[:, None] >> shifts[None, :]) & ((1 << bits) - 1)
+        return torch.from_numpy(code_of_rank).to(self.device)[ranks].contiguous()
+
+
+class DeviceCounter(_KeyLookup):
     """The pooled lag-``lag`` transition table of one dataset column in HBM, as a look-up: ASCII k-mers ``kmers`` uint8 [N, lag],
     ``counts`` [N, W] (uint32 in int32 storage), and the k-mers' keys sorted once (``keys`` int64 [N'] ascending, ``perm`` their
     rows; a k-mer with a character outside the alphabet has no key and is never found).  A key packs the ranks of a k-mer's
@@ -350,30 +427,7 @@ class DeviceCounter:
     ``no_end=False``) whole sequences are sampled from the start context to the stop (``kernels.generate_whole``)."""
 
     def __init__(self, kmers, counts, alphabet_name, no_end=False):
-        if not (isinstance(kmers, torch.Tensor) and kmers.is_cuda and kmers.dtype == torch.uint8 and kmers.dim() == 2):
-            raise ValueError("kmers must be a CUDA uint8 tensor [N, lag] of ASCII k-mers")
-        if not (isinstance(counts, torch.Tensor) and counts.device == kmers.device and counts.dtype == torch.int32
-                and counts.dim() == 2 and counts.shape[0] == kmers.shape[0]):
-            raise ValueError("counts must be a CUDA int32 tensor [N, W] on the k-mers' device")
-        self.alphabet_name, self.no_end = alphabet_name, bool(no_end)
-        self.rank = kernels.score_ranks(alphabet_name)
-        self.width, self.lag = len(self.rank) - 1, int(kmers.shape[1])
-        if counts.shape[1] != self.width:
-            raise ValueError(f"counts: rows of {counts.shape[1]}, the alphabet {alphabet_name!r} has rows of {self.width}")
-        if not 1 <= self.lag <= kernels.SCORE_MAX_LAG[self.width]:
-            raise ValueError(f"lag {self.lag}: a look-up key holds contexts of 1..{kernels.SCORE_MAX_LAG[self.width]} letters of {alphabet_name!r}")
-        self.kmers, self.counts = kmers.contiguous(), counts.contiguous()
-        self._lut = _symbol_lut(alphabet_name)
-        keys = self._keys_of_codes(torch.from_numpy(self._lut).to(kmers.device)[self.kmers.long()])
-        held = torch.nonzero(keys >= 0).reshape(-1)
-        self.keys, order = torch.sort(keys[held])
-        self.perm = held[order]
-        if self.keys.numel() > 1 and bool((self.keys[1:] == self.keys[:-1]).any()):
-            raise ValueError("DeviceCounter: the table holds a k-mer twice")
-
-    @property
-    def device(self):
-        return self.kmers.device
+        self._build_lookup(kmers, counts, alphabet_name, no_end)
 
     @property
     def counts_by_key(self):
@@ -382,43 +436,6 @@ class DeviceCounter:
         if getattr(self, "_counts_by_key", None) is None:
             self._counts_by_key = self.counts[self.perm].contiguous()
         return self._counts_by_key
-
-    def _keys_of_codes(self, codes):
-        """Keys int64 [n] of k-mers given as symbol codes uint8 [n, lag] on the device (-1: a symbol that is no letter of a context):
-        every k-mer becomes a segment of lag + 1 symbols, the k-mer and a stop, whose one transition carries the k-mer's key."""
-        n = codes.shape[0]
-        if n == 0:
-            return torch.empty(0, dtype=torch.int64, device=codes.device)
-        text = torch.cat([codes, torch.full((n, 1), self.width - 1, dtype=torch.uint8, device=codes.device)], 1).reshape(-1)
-        seg = torch.arange(n + 1, dtype=torch.int64, device=codes.device) * (self.lag + 1)
-        keys, _ = kernels.score_transitions(text, seg, self.lag, self.rank)
-        return keys.reshape(n, self.lag + 1)[:, self.lag].contiguous()
-
-    def rows_of_keys(self, keys):
-        """Count rows int32 [n, W] of the k-mers with the given keys (int64 [n] on the device; ascending is the fast order): zeros for
-        an absent k-mer; under ``no_end`` also for a context that holds ``[``, and in the stop column."""
-        idx = kernels.kmer_find(self.keys, keys.contiguous())
-        rows = self.counts[self.perm[idx.clamp(min=0).long()]] if self.keys.numel() else \
-            torch.zeros((keys.numel(), self.width), dtype=torch.int32, device=self.device)
-        keep = idx >= 0
-        if self.no_end:
-            bits, start = kernels.SCORE_BITS[self.width], int(self.rank[self.width])
-            shifts = torch.arange(self.lag, dtype=torch.int64, device=self.device) * bits
-            keep = keep & ~(((keys[:, None] >> shifts[None, :]) & ((1 << bits) - 1)) == start).any(1)
-        rows = rows * keep[:, None].to(torch.int32)
-        if self.no_end:
-            rows[:, -1] = 0
-        return rows.contiguous()
-
-    def codes_of_keys(self, keys):
-        """``core.encode_kmers`` codes int8 [n, lag] (letters 0 .. A - 1, ``[`` = A) of the k-mers with the given valid keys."""
-        bits = kernels.SCORE_BITS[self.width]
-        code_of_rank = np.zeros(1 << bits, dtype=np.int8)
-        code_of_rank[self.rank[:self.width - 1]] = np.arange(self.width - 1)
-        code_of_rank[self.rank[self.width]] = self.width - 1
-        shifts = torch.arange(self.lag - 1, -1, -1, dtype=torch.int64, device=self.device) * bits
-        ranks = (keys[:, None] >> shifts[None, :]) & ((1 << bits) - 1)
-        return torch.from_numpy(code_of_rank).to(self.device)[ranks].contiguous()
 
     def __call__(self, kmers):
         kmers = np.asarray(kmers)

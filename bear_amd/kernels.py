@@ -899,8 +899,11 @@ def score_marg(rows, letters, seg, train, prior, h, vans):
 def _check_marg(rows, letters, seg, train, prior, h, vans):
     """What ``score_marg`` and ``score_moments`` check alike -> ``(train, prior, n_seg, (hs, its pointer), (vans, its pointer))``."""
     train = _check_rows(train, torch.int32, "train", None)
-    K, W = train.shape
-    device = train.device
+    return (train,) + _check_marg_text(rows, letters, seg, train.shape[0], train.shape[1], train.device, prior, h, vans)
+
+
+def _check_marg_text(rows, letters, seg, K, W, device, prior, h, vans):
+    """... and ``score_groups``: everything but the table [K, ..., W] on ``device`` itself -> ``_check_marg``'s result without it."""
     if prior is not None:
         prior = _check_rows(prior, torch.float64, "prior", W, n=K)
     _check_vec(rows, torch.int32, "rows", device=device)
@@ -915,7 +918,7 @@ def _check_marg(rows, letters, seg, train, prior, h, vans):
         raise ValueError("every h and every vanilla pseudo-count must be > 0")
     if max(n_seg, 1) * (K + 1) * 256 >= 2 ** 63:
         raise ValueError(f"{n_seg} segments x {K} k-mers: the sort key (segment, row, letter) does not fit 63 bits")
-    return train, prior, n_seg, (hs, hp), (vs, vp)
+    return prior, n_seg, (hs, hp), (vs, vp)
 
 
 def _marg_sort_key(rows, letters, seg, n_seg, K, W):
@@ -924,6 +927,44 @@ def _marg_sort_key(rows, letters, seg, n_seg, K, W):
     live = (rows >= 0) & (rows < K) & (letters < W)
     segment = torch.searchsorted(seg[1:], torch.arange(n_t, dtype=torch.int64, device=rows.device), right=True).clamp_(max=max(n_seg - 1, 0))
     return (segment * (K + 1) + torch.where(live, rows.to(torch.int64) + 1, 0)) * 256 + torch.where(live, letters.to(torch.int64), SCORE_SKIP)
+
+
+GROUPS_MAX = 256                     # BEAR_GROUPS_MAX: groups (columns) of the table of one bear_score_groups_f64 call
+
+
+def score_groups(rows, letters, seg, train, prior, h, vans, own=None):
+    """``bear_score_groups_f64``: ``score_marg`` under every group of a count table at once -> ``(scores [n_seg, G, H + V] CUDA float64,
+    short_of [n_seg] CUDA uint8)``.  The arguments of ``score_marg``, except ``train``: int32 [K, G, W] (uint32 in int32 storage), the
+    G count rows of a k-mer adjacent; and ``own``: int32 [n_seg] on the device or None -- the group whose counts contain the segment
+    itself (negative, or >= G: none), which is scored with the segment's own counts taken out of it (leave-one-out).
+    ``short_of[s]`` = 1: segment ``s`` has a transition more often than its own group holds it, its own-group scores are NaN.
+
+    The composite-key sort of ``score_marg``; one asynchronous call on the current stream.  The entry's stream is not its last
+    argument (include/bear_hip.h says why), so the call does not go through ``_launch``."""
+    if not (isinstance(train, torch.Tensor) and train.is_cuda and train.dtype == torch.int32 and train.dim() == 3
+            and train.is_contiguous() and train.shape[2] in WIDE_WIDTHS):
+        raise ValueError(f"train must be a contiguous CUDA int32 tensor [K, G, W] with W in {WIDE_WIDTHS}")
+    K, G, W = train.shape
+    if not 1 <= G <= GROUPS_MAX:
+        raise ValueError(f"{G} groups: one call takes 1..{GROUPS_MAX}")
+    if train.data_ptr() % 16:
+        train = train.clone()
+    device = train.device
+    prior, n_seg, (hs, hp), (vs, vp) = _check_marg_text(rows, letters, seg, K, W, device, prior, h, vans)
+    if own is not None:
+        _check_vec(own, torch.int32, "own", n_seg, device=device)
+    n_t = rows.numel()
+    if max(n_seg, 1) * G * (hs.size + vs.size) * 8 >= 2 ** 63 or max(n_t, 1) * G * (hs.size + vs.size) * 8 >= 2 ** 63:
+        raise ValueError(f"{n_seg} segments, {n_t} positions x {G} groups x {hs.size + vs.size} models: too many terms for one call")
+    with torch.cuda.device(device):
+        key = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W)).values
+        letters = (key & 0xFF).to(torch.uint8)
+        rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+        scores = torch.empty((n_seg, G, hs.size + vs.size), dtype=torch.float64, device=device)
+        short_of = torch.empty(n_seg, dtype=torch.uint8, device=device)
+        _lib.call("bear_score_groups_f64", _ptr(rows), _ptr(letters), n_t, _ptr(seg), n_seg, W, _ptr(train), G, _ptr(prior), K, _ptr(own),
+                  hp, hs.size, vp, vs.size, _stream(), _ptr(scores), _ptr(short_of))
+    return scores, short_of
 
 
 def score_moments(rows, letters, seg, train, prior, h, vans, weights=None):

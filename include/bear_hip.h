@@ -1021,6 +1021,36 @@ int bear_score_marg_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_
                         int n_van, double *scores, void *stream);
 
 /*
+ * bear_score_groups_f64: bear_score_marg_f64 under every group (column) of a count table at once, with an optional leave-one-out
+ * group per segment (bear_amd.classify, kernels_groups.h): which group does a segment belong to.  rows, letters, seg, width, prior,
+ * h and van are exactly bear_score_marg_f64's, positions sorted by (row, letter) inside each segment; a position's run, its k-mer's
+ * stretch and its prior row are found once and serve every group.
+ *   train [dev] uint32 [n_rows, n_groups, width]: the n_groups count rows of one k-mer are adjacent;  1 <= n_groups <= BEAR_GROUPS_MAX
+ *   own   [dev, nullable] int32 [n_seg]: the group whose counts contain segment s itself; negative or >= n_groups: none; NULL: no
+ *         segment has one
+ *   scores [dev] double [n_seg, n_groups, n_h + n_van]: the formula of bear_score_marg_f64 with c[] = train[r, g, :] -- and with
+ *         c_j - q_j in place of c_j, for every letter j of the k-mer, an exact integer subtraction before the conversion to double,
+ *         where g = own[s]: the marginal of s under the posterior of the group WITHOUT s.  Without own, scores[:, g, :] are the
+ *         bits of bear_score_marg_f64 on column g; with it, scores[s, own[s], :] are its bits on that column less the segment's
+ *         counts.
+ *   short_of [dev] uint8 [n_seg], zeroed by the entry: 1 where some c_j < q_j in the segment's own group -- the table does not
+ *         hold that segment.  Its own-group scores are NaN; every other score of the call is what it is without that own[s].
+ * Terms [n_groups * (n_h + n_van), n_t] and the sums of bear_score_marg_f64 with n_groups * (n_h + n_van) models; no atomics: a
+ * segment's bits depend on its content, its own[] value and the table only, in both libraries.  Asynchronous on `stream`: the
+ * terms and the partial rows come from the device's memory pool in stream order (hipMallocAsync / hipFreeAsync), the entry waits
+ * for nothing; outputs are valid once the stream is synchronised.  It does not belong inside a graph capture.
+ * Refused with BEAR_ERR_INVALID_ARG before any device call: everything bear_score_marg_f64 refuses, n_groups out of range, a missing
+ * scores or short_of, a misaligned own.  n_seg = 0 is valid and launches nothing.
+ * The stream is deliberately NOT the last parameter, as for bear_two_sample_f64 and for the same reason; tests/test_classify_gpu.py
+ * holds the entry to the contract with the harness of tests/stream_util.py.
+ */
+#define BEAR_GROUPS_MAX 256
+int bear_score_groups_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, const uint64_t *seg, uint64_t n_seg,
+                          int width, const uint32_t *train, int n_groups, const double *prior, uint64_t n_rows,
+                          const int32_t *own, const double *h, int n_h, const double *van, int n_van,
+                          void *stream, double *scores, uint8_t *short_of);
+
+/*
  * bear_score_moments_f64: the exact posterior mean and variance of every segment's score under n_h BEAR and n_van vanilla models
  * (get_bear_probs / get_bear_probs_seqs with moments=True): what the mc_samples axis of bear_logdir_sample[_wide]_f64 +
  * bear_score_sum_f64 samples, in closed form.  The arguments, models, concentrations (a_j and A bit for bit), sums, checks and
