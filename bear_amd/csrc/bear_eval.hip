@@ -1,12 +1,14 @@
 // bear_eval.hip -- held-out evaluation and the BMM marginal (kernels_eval.h), their 21-wide forms and the wide DM step
 // (kernels_wide.h), bear_ref's wide steps (kernels_refmix_wide.h), evaluation on a sorted plan of the test column
-// (kernels_evalplan.h), the two-sample Bayes factors of two count columns (kernels_twosample.h).  The other units: bear_host.h.
+// (kernels_evalplan.h), the two-sample Bayes factors of two count columns (kernels_twosample.h)
+// and those among up to sixteen (kernels_ksample.h).  The other units: bear_host.h.
 #include "bear_host.h"
 #include "kernels_eval.h"
 #include "kernels_wide.h"
 #include "kernels_refmix_wide.h"
 #include "kernels_evalplan.h"
 #include "kernels_twosample.h"
+#include "kernels_ksample.h"
 
 #ifdef EVP_STAMPS
 #define EVP_DBG_ARG , ws->dbg
@@ -190,6 +192,81 @@ int bear_two_sample_f64(bear_ws *ws, const uint32_t *a, const uint32_t *b, const
                                               use_prior, do_ar, lt, ws->eval_partials, row_terms));
     hipLaunchKernelGGL(two_sample_finalize_kernel, dim3((TS_NOUT + 3) / 4), dim3(256), 0, s, ws->eval_partials, grid, m0, m_cnt, out,
                        do_ar ? out_ar : nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+// ---- Bayes factors among G columns (kernels_ksample.h) ----------------------------------------------------------------------
+static inline int ks_padded_groups(int g) { return g <= 2 ? 2 : g <= 4 ? 4 : g <= 8 ? 8 : 16; }
+static inline uint64_t ks_npart(int gp) { return gp == 2 ? KS_NPART(2) : gp == 4 ? KS_NPART(4) : gp == 8 ? KS_NPART(8) : KS_NPART(16); }
+// the blocks any device takes for a table: the tiles, at most KS_MAX_BLOCKS (a launch: and at most KS_BLOCKS_PER_CU a CU)
+static inline uint64_t ks_blocks(uint64_t n_rows, int width, int gp) {
+  const uint64_t tile = (uint64_t)(KS_TILE(width, gp)), tiles = n_rows / tile + (n_rows % tile ? 1 : 0);
+  return tiles < 1 ? 1 : (tiles < KS_MAX_BLOCKS ? tiles : KS_MAX_BLOCKS);
+}
+
+uint64_t bear_k_sample_scratch(bear_ws *ws, uint64_t n_rows, int width, int n_groups) {
+  (void)ws;
+  if (!wide_width_ok(width) || n_groups < 2 || n_groups > BEAR_K_SAMPLE_MAX_GROUPS) return 0;
+  const int gp = ks_padded_groups(n_groups);
+  return ks_blocks(n_rows, width, gp) * ks_npart(gp);
+}
+
+// Every refusal comes before the first device call; col_rows, h and van are read here (they travel by value).
+int bear_k_sample_f64(bear_ws *ws, const uint32_t *counts, const uint64_t *col_rows, int n_groups, const double *prior,
+                      uint64_t n_rows, int width, const double *h, int n_h, const double *van, int n_van, void *stream,
+                      double *scratch, uint64_t n_scratch, double *out_group, double *out_pair, double *out_all,
+                      double *out_ar, double *row_terms) {
+  if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
+  if (n_groups < 2 || n_groups > BEAR_K_SAMPLE_MAX_GROUPS || !col_rows) return BEAR_ERR_INVALID_ARG;
+  if (n_h < 0 || n_van < 0 || n_h + n_van < 1 || n_h + n_van > BEAR_TWO_SAMPLE_MAX_MODELS) return BEAR_ERR_INVALID_ARG;
+  if ((n_h && !h) || (n_van && !van) || (n_rows && (n_h || out_ar) && !prior)) return BEAR_ERR_INVALID_ARG;
+  if (!ws || !scratch || !out_group || !out_pair || !out_all || (n_rows && !counts)) return BEAR_ERR_INVALID_ARG;
+  if (n_scratch < bear_k_sample_scratch(ws, n_rows, width, n_groups)) return BEAR_ERR_INVALID_ARG;
+  if (misaligned(prior) || misaligned8(scratch) || misaligned8(out_group) || misaligned8(out_pair) || misaligned8(out_all) ||
+      misaligned8(out_ar) || misaligned8(row_terms))
+    return BEAR_ERR_INVALID_ARG;
+  ks_args A;
+  memset(&A, 0, sizeof(A));
+  A.n_h = n_h;
+  A.n_models = n_h + n_van;
+  A.n_groups = n_groups;
+  for (int g = 0; g < n_groups; ++g) {
+    if (counts && misaligned(counts + col_rows[g] * (uint64_t)width)) return BEAR_ERR_INVALID_ARG;
+    A.col[g] = col_rows[g];
+  }
+  for (int j = 0; j < n_h; ++j) {
+    if (!(h[j] > 0.0 && h[j] < INFINITY)) return BEAR_ERR_INVALID_ARG;
+    A.w[j] = 1.0 / h[j];
+  }
+  for (int k = 0; k < n_van; ++k) {
+    if (!(van[k] > 0.0 && van[k] < INFINITY)) return BEAR_ERR_INVALID_ARG;
+    A.w[n_h + k] = van[k];
+  }
+  int st = check_ws(ws);
+  if (st != BEAR_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int gp = ks_padded_groups(n_groups), n_part = (int)ks_npart(gp);
+  const int sl = gp == 2 ? KS_SLOTS(2) : gp == 4 ? KS_SLOTS(4) : gp == 8 ? KS_SLOTS(8) : KS_SLOTS(16);
+  const int grid = grid_capped(ks_blocks(n_rows, width, gp), ws_blocks(ws, KS_BLOCKS_PER_CU));
+  const double2 *lt = reinterpret_cast<const double2 *>(ws->logtab);
+  for (int m0 = 0; m0 < A.n_models; m0 += KS_CHUNK) {
+    const int m_cnt = A.n_models - m0 < KS_CHUNK ? A.n_models - m0 : KS_CHUNK;
+    const int do_ar = m0 == 0 && out_ar;
+    const int use_prior = do_ar || m0 < n_h;
+#define KS_LAUNCH(GP_)                                                                                                              \
+  hipLaunchKernelGGL((k_sample_kernel<W, GP_>), dim3(grid), dim3(KS_THREADS), 0, s, counts, prior, n_rows, A, m0, m_cnt, use_prior, \
+                     do_ar, lt, scratch, row_terms)
+    BEAR_DISPATCH_W(width, do {
+      if (gp == 2) KS_LAUNCH(2);
+      else if (gp == 4) KS_LAUNCH(4);
+      else if (gp == 8) KS_LAUNCH(8);
+      else KS_LAUNCH(16);
+    } while (0));
+#undef KS_LAUNCH
+    hipLaunchKernelGGL(k_sample_finalize_kernel, dim3((n_part + 3) / 4), dim3(256), 0, s, scratch, grid, gp, sl, n_groups, m0, m_cnt,
+                       out_group, out_pair, out_all, do_ar ? out_ar : nullptr);
   }
   HIP_TRY(hipGetLastError());
   return BEAR_OK;

@@ -6,7 +6,7 @@
 //   bear_linear.hip  k-mer packing, the paired lists, the linear AR head (fused step and rows, both also at rows of 21), the Adam launch
 //   bear_cnn.hip     the convolutional AR head and its prefix levels / window tables; the head as rows of 21 and bear_net's step with it
 //   bear_eval.hip    held-out evaluation (5- and 21-wide), the wide DM step and bear_ref's wide steps, the evaluation plan, the BMM marginal,
-//                    the two-sample Bayes factors
+//                    the two-sample and the k-sample Bayes factors
 //   (bear_score.hip, scoring under a sampled table, bear_shuffle.hip, the row shuffle, and bear_count.hip, counting, need nothing of
 //   this file: bear_dev.h alone)
 // What a unit needs of another goes through the declarations at the end of this file.

@@ -633,6 +633,75 @@ def two_sample(a, b, prior, h, vans, want_ar=False, want_rows=False, ws=None):
     return out, out_ar, rows
 
 
+K_SAMPLE_MAX_GROUPS = 16                            # BEAR_K_SAMPLE_MAX_GROUPS: columns of one call
+K_SAMPLE_TILES = {21: {2: 128, 4: 64, 8: 48, 16: 24}, 5: {2: 256, 4: 128, 8: 96, 16: 48}}    # KS_TILE(W, GP) of kernels_ksample.h
+K_SAMPLE_TILE = {21: 24, 5: 48}                     # ... at sixteen groups, the smallest: a launch takes min(tiles, blocks per CU
+K_SAMPLE_BLOCKS_PER_CU = 2                          # * CUs) blocks -- tests size a table beyond that
+
+
+def k_sample_tile(width, n_groups):
+    """The contexts of one tile of ``bear_k_sample_f64`` at ``n_groups`` columns (rounded up to 2, 4, 8 or 16)."""
+    return K_SAMPLE_TILES[width][next(g for g in (2, 4, 8, 16) if n_groups <= g)]
+
+
+def k_sample(counts, cols, prior, h, vans, want_ar=False, want_rows=False, ws=None):
+    """``bear_k_sample_f64``: the Bayes factors among the columns ``cols`` (G = 2..16 indices, any subset and order) of the count
+    table ``counts`` [C, N, W] (uint32 in int32 storage) in one pass -> ``(out_group [M, G], out_pair [M, P, 2], out_all [M, 2],
+    out_ar [G] or None, row_terms [N, M] or None)``, CUDA float64, M = H + V models (BEAR first), the P = G (G - 1) / 2 pairs in the
+    order (0, 1), (0, 2), ..., (G - 2, G - 1) of ``cols``; include/bear_hip.h has the formulas.  The table is used in place where
+    its rows are contiguous and every chosen column starts on a 16-byte boundary (a ``[C, N, W]`` tensor, or its rows
+    ``[:, lo:hi]`` where ``lo * W`` is a multiple of four); any other piece is copied, the chosen columns only.  Outputs and the
+    scratch of block partials are allocated here, on the current stream; one asynchronous call (the entry's stream is not its
+    last argument: the call does not go through ``_launch``)."""
+    if not (torch.is_tensor(counts) and counts.is_cuda and counts.dtype == torch.int32 and counts.dim() == 3):
+        raise ValueError("counts must be a CUDA tensor of shape [C, N, W] and dtype torch.int32")
+    n_cols, n, width = counts.shape
+    if width not in WIDE_WIDTHS:
+        raise ValueError(f"counts: rows of width {width}; the kernels take {WIDE_WIDTHS}")
+    cols = [int(c) for c in cols]
+    if not 2 <= len(cols) <= K_SAMPLE_MAX_GROUPS:
+        raise ValueError(f"{len(cols)} columns: one call takes 2..{K_SAMPLE_MAX_GROUPS}")
+    if any(not 0 <= c < n_cols for c in cols):
+        raise ValueError(f"columns {cols}: the table has {n_cols}")
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", width, n=n)
+        if prior.device != counts.device:
+            raise ValueError("counts and prior must be on one device")
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
+    if (hs.size or want_ar) and prior is None:
+        raise ValueError("the BEAR models (h) and the AR model's likelihood (want_ar) need prior rows")
+    if not 1 <= hs.size + vs.size <= TWO_SAMPLE_MAX_MODELS:
+        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{TWO_SAMPLE_MAX_MODELS}")
+    if not (np.all(hs > 0) and np.all(vs > 0) and np.all(np.isfinite(hs)) and np.all(np.isfinite(vs))):
+        raise ValueError("every h and every vanilla pseudo-count must be > 0 and finite")
+    dev, G, M = counts.device, len(cols), hs.size + vs.size
+    stride = counts.stride(0)
+    in_place = n > 0 and counts.stride(2) == 1 and counts.stride(1) == width and stride >= 0 and stride % width == 0 \
+        and all((counts.data_ptr() + 4 * c * stride) % 16 == 0 for c in cols)
+    if in_place:
+        table, col_rows = counts, np.array([c * (stride // width) for c in cols], dtype=np.uint64)
+    else:       # the chosen columns, each on a 16-byte boundary: a column of the copy holds a multiple of four rows
+        n_pad = max(4, (n + 3) // 4 * 4)
+        table = torch.empty((G, n_pad, width), dtype=torch.int32, device=dev)
+        for g, c in enumerate(cols):
+            table[g, :n] = counts[c]
+        col_rows = np.arange(G, dtype=np.uint64) * np.uint64(n_pad)
+    ws = ws or default_workspace(dev)
+    lib = _lib.lib()
+    n_scratch = int(lib.bear_k_sample_scratch(ws.handle, n, width, G))
+    scratch = torch.empty(max(n_scratch, 1), dtype=torch.float64, device=dev)
+    out_group = torch.empty((M, G), dtype=torch.float64, device=dev)
+    out_pair = torch.empty((M, G * (G - 1) // 2, 2), dtype=torch.float64, device=dev)
+    out_all = torch.empty((M, 2), dtype=torch.float64, device=dev)
+    out_ar = torch.empty(G, dtype=torch.float64, device=dev) if want_ar else None
+    rows = torch.empty((n, M), dtype=torch.float64, device=dev) if want_rows else None
+    with torch.cuda.device(dev):
+        _lib.call("bear_k_sample_f64", ws.handle, _ptr(table), col_rows.ctypes.data_as(ctypes.c_void_p), G, _ptr(prior), n, width,
+                  hp, hs.size, vp, vs.size, _stream(), _ptr(scratch), n_scratch, _ptr(out_group), _ptr(out_pair), _ptr(out_all),
+                  _ptr(out_ar), _ptr(rows))
+    return out_group, out_pair, out_all, out_ar, rows
+
+
 def synth_counts(seed, row0, n_rows, device, dense=False, want=("train", "test", "ref")):
     """Rows [row0, row0+n_rows) of the synthetic k=13 table, generated on the device."""
     bufs = {k: torch.empty((n_rows, 5), dtype=torch.int32, device=device) for k in want}

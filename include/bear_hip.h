@@ -669,6 +669,44 @@ int bear_two_sample_f64(bear_ws *ws, const uint32_t *a, const uint32_t *b, const
                         double *out, double *out_ar, double *row_terms);
 
 /*
+ * bear_k_sample_f64: bear_two_sample_f64 among G = n_groups columns of one table at once (kernels_ksample.h) -- which samples differ
+ * from which, and are all of them one distribution -- in ONE pass: every column is read once and T(c_g) evaluated once, where a loop
+ * of G (G - 1) / 2 two-sample calls does both G - 1 times.  T, the order and meaning of the models, prior, h, van and the widths
+ * are exactly bear_two_sample_f64's.
+ *   counts, col_rows: row k of column g is at counts + (col_rows[g] + k) * W; col_rows [host] n_groups values, read before the
+ *          entry returns; every column start 16-byte aligned.  A [num_ds, N, W] device table and any subset or order of its
+ *          columns is used in place (col_rows[g] = column * N).  2 <= n_groups <= BEAR_K_SAMPLE_MAX_GROUPS.
+ *   With M = n_h + n_van and the P = G (G - 1) / 2 pairs in the order (0, 1), (0, 2), ..., (G - 2, G - 1):
+ *   out_group [dev] double [M, G]    = sum_k T(c_g)
+ *   out_pair  [dev] double [M, P, 2] = { sum_k T(c_g + c_g'), sum_k B_k }, B_k = (T(c_g) + T(c_g')) - T(c_g + c_g') formed PER ROW
+ *   out_all   [dev] double [M, 2]    = { sum_k T(sum_g c_g), sum_k [(sum_g T(c_g)) - T(sum_g c_g)] }, the bracket formed per row and
+ *          the T(c_g) added in group order: the log Bayes factor of "G distributions" over "one"
+ *   out_ar    [dev, nullable] double [G] = sum_k sum_j c_gj log(prior[k, j])
+ *   row_terms [dev, nullable] double [n_rows, M] = the per-row bracket of out_all[:, 1]: which contexts drive the difference
+ *   scratch   [dev] double [n_scratch], n_scratch >= bear_k_sample_scratch(ws, n_rows, width, n_groups): the block partials (the
+ *          workspace's evaluation partials are too small for up to 258 sums a model); the query needs no device and no workspace
+ *          (ws may be NULL there) and is 0 for a width or n_groups the entry refuses.
+ * Exact zeros: a pair whose row has an empty side adds exactly +0.0 to B, the row's pooled T is the other side's T (no item is
+ * evaluated again); a row with at most one non-empty group adds exactly +0.0 to out_all[:, 1] and has row_terms +0.0; a row with no
+ * transition costs its bytes only.  Pooled counts are exact integers (a pair's cell below 2^33, all sixteen below 2^36, a row total
+ * below 2^41).
+ * Asynchronous on `stream`, allocates nothing; no floating-point atomics: equal inputs give equal bits for a given n_rows and
+ * n_groups, in both libraries -- NOT the bits of bear_two_sample_f64 on a pair, nor the same bits under a permutation of the columns
+ * (other reduction orders).  At most four models a launch; more are further launches, each with the bits of a call of its own.
+ * n_rows = 0 writes zeros.  Out of scope: more than 16 groups a call, sharded tables.
+ * BEAR_ERR_INVALID_ARG, before any device call: everything bear_two_sample_f64 refuses, n_groups out of range, a missing col_rows,
+ * n_scratch below the query, a missing scratch, out_group, out_pair or out_all, a misaligned column (16 bytes) or output (8).
+ * The stream is deliberately NOT the last parameter, as for bear_two_sample_f64; tests/test_k_sample_gpu.py holds the entry to the
+ * contract with the harness of tests/stream_util.py.
+ */
+#define BEAR_K_SAMPLE_MAX_GROUPS 16
+uint64_t bear_k_sample_scratch(bear_ws *ws, uint64_t n_rows, int width, int n_groups);
+int bear_k_sample_f64(bear_ws *ws, const uint32_t *counts, const uint64_t *col_rows, int n_groups, const double *prior,
+                      uint64_t n_rows, int width, const double *h, int n_h, const double *van, int n_van, void *stream,
+                      double *scratch, uint64_t n_scratch, double *out_group, double *out_pair, double *out_all,
+                      double *out_ar, double *row_terms);
+
+/*
  * The primitive underneath both entry points, item by item (tests / diagnostics): for x > 0 and
  * integer c >= 0,  D[i] = lgamma(x+c) - lgamma(x)  and  P[i] = digamma(x+c) - digamma(x)
  * -- the two quantities TFP's lbeta and its autodiff yield in bear_model/core.py:73-74.
