@@ -154,28 +154,33 @@ int bear_eval_wide_f64(bear_ws *ws, const uint32_t *test, const uint32_t *train,
 }
 
 // ---- two-sample and goodness-of-fit Bayes factors (kernels_twosample.h) ----------------------------------------------------
+// What bear_two_sample_f64 and bear_k_sample_f64 refuse alike about their models, and the models' weights w: [0, n_h) 1 / h,
+// [n_h, n_h + n_van) van, every h and van > 0 and finite -> the number of models, or BEAR_ERR_INVALID_ARG.  No device call.
+static int bayes_models(const double *h, int n_h, const double *van, int n_van, const double *prior, uint64_t n_rows, bool want_ar,
+                        double w[BEAR_TWO_SAMPLE_MAX_MODELS]) {
+  if (n_h < 0 || n_van < 0 || n_h + n_van < 1 || n_h + n_van > BEAR_TWO_SAMPLE_MAX_MODELS) return BEAR_ERR_INVALID_ARG;
+  if ((n_h && !h) || (n_van && !van) || (n_rows && (n_h || want_ar) && !prior)) return BEAR_ERR_INVALID_ARG;
+  for (int m = 0; m < n_h + n_van; ++m) {
+    const double v = m < n_h ? h[m] : van[m - n_h];
+    if (!(v > 0.0 && v < INFINITY)) return BEAR_ERR_INVALID_ARG;
+    w[m] = m < n_h ? 1.0 / v : v;
+  }
+  return n_h + n_van;
+}
+
 // Every refusal comes before the first device call; h and van are read here, before the entry returns (they travel by value).
 int bear_two_sample_f64(bear_ws *ws, const uint32_t *a, const uint32_t *b, const double *prior, uint64_t n_rows, int width,
                         const double *h, int n_h, const double *van, int n_van, void *stream, double *out, double *out_ar,
                         double *row_terms) {
   if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
-  if (n_h < 0 || n_van < 0 || n_h + n_van < 1 || n_h + n_van > BEAR_TWO_SAMPLE_MAX_MODELS) return BEAR_ERR_INVALID_ARG;
-  if ((n_h && !h) || (n_van && !van) || (n_rows && (n_h || out_ar) && !prior)) return BEAR_ERR_INVALID_ARG;
   if (!ws || !out || (n_rows && (!a || !b))) return BEAR_ERR_INVALID_ARG;
   if (misaligned(a) || misaligned(b) || misaligned(prior) || misaligned8(out) || misaligned8(out_ar) || misaligned8(row_terms))
     return BEAR_ERR_INVALID_ARG;
   ts_args A;
   memset(&A, 0, sizeof(A));
   A.n_h = n_h;
-  A.n_models = n_h + n_van;
-  for (int j = 0; j < n_h; ++j) {
-    if (!(h[j] > 0.0 && h[j] < INFINITY)) return BEAR_ERR_INVALID_ARG;
-    A.w[j] = 1.0 / h[j];
-  }
-  for (int k = 0; k < n_van; ++k) {
-    if (!(van[k] > 0.0 && van[k] < INFINITY)) return BEAR_ERR_INVALID_ARG;
-    A.w[n_h + k] = van[k];
-  }
+  A.n_models = bayes_models(h, n_h, van, n_van, prior, n_rows, out_ar != nullptr, A.w);
+  if (A.n_models < 0) return A.n_models;
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -220,8 +225,6 @@ int bear_k_sample_f64(bear_ws *ws, const uint32_t *counts, const uint64_t *col_r
                       double *out_ar, double *row_terms) {
   if (!wide_width_ok(width)) return BEAR_ERR_INVALID_ARG;
   if (n_groups < 2 || n_groups > BEAR_K_SAMPLE_MAX_GROUPS || !col_rows) return BEAR_ERR_INVALID_ARG;
-  if (n_h < 0 || n_van < 0 || n_h + n_van < 1 || n_h + n_van > BEAR_TWO_SAMPLE_MAX_MODELS) return BEAR_ERR_INVALID_ARG;
-  if ((n_h && !h) || (n_van && !van) || (n_rows && (n_h || out_ar) && !prior)) return BEAR_ERR_INVALID_ARG;
   if (!ws || !scratch || !out_group || !out_pair || !out_all || (n_rows && !counts)) return BEAR_ERR_INVALID_ARG;
   if (n_scratch < bear_k_sample_scratch(ws, n_rows, width, n_groups)) return BEAR_ERR_INVALID_ARG;
   if (misaligned(prior) || misaligned8(scratch) || misaligned8(out_group) || misaligned8(out_pair) || misaligned8(out_all) ||
@@ -230,20 +233,13 @@ int bear_k_sample_f64(bear_ws *ws, const uint32_t *counts, const uint64_t *col_r
   ks_args A;
   memset(&A, 0, sizeof(A));
   A.n_h = n_h;
-  A.n_models = n_h + n_van;
   A.n_groups = n_groups;
   for (int g = 0; g < n_groups; ++g) {
     if (counts && misaligned(counts + col_rows[g] * (uint64_t)width)) return BEAR_ERR_INVALID_ARG;
     A.col[g] = col_rows[g];
   }
-  for (int j = 0; j < n_h; ++j) {
-    if (!(h[j] > 0.0 && h[j] < INFINITY)) return BEAR_ERR_INVALID_ARG;
-    A.w[j] = 1.0 / h[j];
-  }
-  for (int k = 0; k < n_van; ++k) {
-    if (!(van[k] > 0.0 && van[k] < INFINITY)) return BEAR_ERR_INVALID_ARG;
-    A.w[n_h + k] = van[k];
-  }
+  A.n_models = bayes_models(h, n_h, van, n_van, prior, n_rows, out_ar != nullptr, A.w);
+  if (A.n_models < 0) return A.n_models;
   int st = check_ws(ws);
   if (st != BEAR_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);

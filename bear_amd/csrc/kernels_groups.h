@@ -6,9 +6,10 @@
 // differs between the table's groups.  (A "group" of POSITIONS -- the stretch of equal row -- is kernels_marg.h's word; a "group" of
 // the TABLE is one of its n_groups columns.  Below: k-mer head / k-mer end for the former, group for the latter.)
 //
-//   groups_terms_kernel<W>  one thread per position, as marg_terms_kernel<W>: the run's end and the k-mer's end by binary search,
-//                           the prior row once, then a loop over the table's groups that reads that group's count row (k-mer
-//                           head) and run cell, and inside it marg_terms_kernel's model loop, term for term.
+//   groups_terms_kernel<W>  one thread per position: what it heads, its segment, the run's end and the k-mer's end from
+//                           mrg_classify (kernels_marg.h), the prior row once, then a loop over the table's groups that reads that
+//                           group's count row (k-mer head) and run cell, and inside it marg_terms_kernel's model loop (written out
+//                           in each kernel: DESIGN.md, "Exact marginals and Bayes factors: each copied part once").
 //                           train [n_rows, n_groups, W]: the rows of one k-mer are adjacent, a k-mer head reads one stretch.
 //                           terms [n_groups * n_m, n_t], plane g * n_m + m: marg_chunk_kernel and marg_sum_kernel sum them as they
 //                           stand, with n_groups * n_m models.
@@ -36,26 +37,11 @@ __global__ __launch_bounds__(MRG_THREADS) void groups_terms_kernel(const int32_t
                                                                    double *__restrict__ terms, uint8_t *__restrict__ short_of) {
   const uint64_t first = scr_off(seg, 0, n_t), end = scr_off(seg, n_seg, n_t);
   for (uint64_t i = (uint64_t)blockIdx.x * MRG_THREADS + threadIdx.x; i < n_t; i += (uint64_t)gridDim.x * MRG_THREADS) {
-    bool run_head = false, kmer_head = false;
-    uint64_t key = MRG_NO_KEY, left = 1, s = 0;          // left: positions from i to the end of its segment s
-    if (first <= i && i < end) {
-      s = scr_last_le(seg, n_seg, i);
-      const uint64_t s0 = scr_off(seg, s, n_t), s1 = scr_off(seg, s + 1, n_t);
-      if (s0 <= i && i < s1) {
-        key = mrg_key(rows, letters, i, W, n_rows);
-        if (key != MRG_NO_KEY) {
-          const uint64_t prev = i > s0 ? mrg_key(rows, letters, i - 1, W, n_rows) : MRG_NO_KEY;
-          kmer_head = (prev >> 8) != (key >> 8);
-          run_head = prev != key;
-          left = s1 - i;
-        }
-      }
-    }
-    const uint64_t row = run_head ? key >> 8 : 0;
-    const uint32_t letter = run_head ? (uint32_t)(key & 0xFFu) : 0u;
-    const uint64_t qu = mrg_stretch_end(rows, letters, i, run_head ? left : 1, key, 0, W, n_rows) - i;
-    const uint64_t nu = mrg_stretch_end(rows, letters, i, kmer_head ? left : 1, key >> 8, 8, W, n_rows) - i;
-    const double q = (double)qu, n = (double)nu;
+    const mrg_pos p = mrg_classify<W>(i, rows, letters, n_t, seg, n_seg, first, end, n_rows);
+    const bool run_head = p.run_head, kmer_head = p.group_head;        // (this file's words, above)
+    const uint64_t s = p.seg, key = p.key, row = p.row, qu = p.run_end - i;
+    const uint32_t letter = p.letter;
+    const double q = (double)qu, n = (double)(p.group_end - i);
     int32_t mine = -1;                                   // the segment's own group: only a head asks
     if (run_head && own) {
       mine = own[s];
@@ -73,7 +59,7 @@ __global__ __launch_bounds__(MRG_THREADS) void groups_terms_kernel(const int32_t
       for (int j = 0; j < W; ++j) f[j] = prior ? prior[row * W + j] : 0.0;
       if (mine >= 0) {                                   // q_j of every letter: the k-mer's runs stand in ascending letters
         const uint32_t *__restrict__ mr = tr + (uint32_t)mine * W;
-        const uint64_t kmer_end = i + nu;
+        const uint64_t kmer_end = p.group_end;
         uint64_t p = i;
 #pragma unroll
         for (int j = 0; j < W; ++j) {

@@ -56,6 +56,45 @@ __device__ __forceinline__ uint64_t mrg_stretch_end(const int32_t *__restrict__ 
   return lo + 1;
 }
 
+// What position i of the sorted text is, for the three terms kernels (marg, moments, groups): the position walk, written once.
+struct mrg_pos {
+  bool run_head, group_head;             // the first position of its run (equal key), of its group (equal row); neither: no term
+  uint64_t key, left, seg;               // left: positions from i to the end of its segment `seg` (1 where i is no head)
+  uint64_t row;                          // of a run head, else 0: nothing that is no head's becomes an index
+  uint32_t letter;
+  uint64_t run_end, group_end;           // in (i, i + left], inside the segment and so inside the text; i + 1 where i is no head
+};
+
+// first / end: the text's seg[0] and seg[n_seg], hoisted out of the grid-stride loop.  Integer work only.
+template <int W>
+__device__ __forceinline__ mrg_pos mrg_classify(uint64_t i, const int32_t *__restrict__ rows, const uint8_t *__restrict__ letters,
+                                                uint64_t n_t, const uint64_t *__restrict__ seg, uint64_t n_seg, uint64_t first,
+                                                uint64_t end, uint64_t n_rows) {
+  mrg_pos p;
+  p.run_head = p.group_head = false;
+  p.key = MRG_NO_KEY;
+  p.left = 1;
+  p.seg = 0;
+  if (first <= i && i < end) {
+    p.seg = scr_last_le(seg, n_seg, i);
+    const uint64_t s0 = scr_off(seg, p.seg, n_t), s1 = scr_off(seg, p.seg + 1, n_t);
+    if (s0 <= i && i < s1) {
+      p.key = mrg_key(rows, letters, i, W, n_rows);
+      if (p.key != MRG_NO_KEY) {
+        const uint64_t prev = i > s0 ? mrg_key(rows, letters, i - 1, W, n_rows) : MRG_NO_KEY;
+        p.group_head = (prev >> 8) != (p.key >> 8);
+        p.run_head = prev != p.key;
+        p.left = s1 - i;
+      }
+    }
+  }
+  p.row = p.run_head ? p.key >> 8 : 0;
+  p.letter = p.run_head ? (uint32_t)(p.key & 0xFFu) : 0u;
+  p.run_end = mrg_stretch_end(rows, letters, i, p.run_head ? p.left : 1, p.key, 0, W, n_rows);
+  p.group_end = mrg_stretch_end(rows, letters, i, p.group_head ? p.left : 1, p.key >> 8, 8, W, n_rows);
+  return p;
+}
+
 // kept out of line: two call sites inside the model loop, ~500 instructions each
 __device__ __noinline__ double mrg_item_D(double x, double c) { return bear_dm_item(x, c).D; }
 
@@ -66,50 +105,33 @@ __global__ __launch_bounds__(MRG_THREADS) void marg_terms_kernel(const int32_t *
                                                                  uint64_t n_rows, mrg_models P, double *__restrict__ terms) {
   const uint64_t first = scr_off(seg, 0, n_t), end = scr_off(seg, n_seg, n_t);
   for (uint64_t i = (uint64_t)blockIdx.x * MRG_THREADS + threadIdx.x; i < n_t; i += (uint64_t)gridDim.x * MRG_THREADS) {
-    bool run_head = false, group_head = false;
-    uint64_t key = MRG_NO_KEY, left = 1;                 // left: positions from i to the end of its segment
-    if (first <= i && i < end) {
-      const uint64_t s = scr_last_le(seg, n_seg, i);
-      const uint64_t s0 = scr_off(seg, s, n_t), s1 = scr_off(seg, s + 1, n_t);
-      if (s0 <= i && i < s1) {
-        key = mrg_key(rows, letters, i, W, n_rows);
-        if (key != MRG_NO_KEY) {
-          const uint64_t prev = i > s0 ? mrg_key(rows, letters, i - 1, W, n_rows) : MRG_NO_KEY;
-          group_head = (prev >> 8) != (key >> 8);
-          run_head = prev != key;
-          left = s1 - i;
-        }
-      }
-    }
-    const uint64_t row = run_head ? key >> 8 : 0;
-    const uint32_t letter = run_head ? (uint32_t)(key & 0xFFu) : 0u;
-    const double q = (double)(mrg_stretch_end(rows, letters, i, run_head ? left : 1, key, 0, W, n_rows) - i);
-    const double n = (double)(mrg_stretch_end(rows, letters, i, group_head ? left : 1, key >> 8, 8, W, n_rows) - i);
+    const mrg_pos p = mrg_classify<W>(i, rows, letters, n_t, seg, n_seg, first, end, n_rows);
+    const double q = (double)(p.run_end - i), n = (double)(p.group_end - i);
     uint32_t c[W];                                       // the two rows of a group head, read once for every model's A
     double f[W];
     double cl = 0.0, fl = 0.0;                           // ... and the run's own cell
-    if (group_head) {
+    if (p.group_head) {
 #pragma unroll
       for (int j = 0; j < W; ++j) {
-        c[j] = train[row * W + j];
-        f[j] = prior ? prior[row * W + j] : 0.0;
+        c[j] = train[p.row * W + j];
+        f[j] = prior ? prior[p.row * W + j] : 0.0;
       }
     }
-    if (run_head) {
-      cl = (double)train[row * W + letter];
-      fl = prior ? prior[row * W + letter] : 0.0;
+    if (p.run_head) {
+      cl = (double)train[p.row * W + p.letter];
+      fl = prior ? prior[p.row * W + p.letter] : 0.0;
     }
     for (int m = 0; m < P.n_m; ++m) {
       const double w = P.w[m];
       const bool bear = m < P.n_h;
       double t = 0.0;
-      if (group_head) {
+      if (p.group_head) {
         double A = 0.0;
 #pragma unroll
         for (int j = 0; j < W; ++j) A += bear ? __builtin_fma(f[j], w, (double)c[j]) : (double)c[j] + w;
         t = -mrg_item_D(A, n);
       }
-      if (run_head) t += mrg_item_D(bear ? __builtin_fma(fl, w, cl) : cl + w, q);
+      if (p.run_head) t += mrg_item_D(bear ? __builtin_fma(fl, w, cl) : cl + w, q);
       terms[(uint64_t)m * n_t + i] = t;
     }
   }

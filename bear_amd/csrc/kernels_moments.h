@@ -9,10 +9,10 @@
 //     E[S] = sum_b m_b psi(a_b) - M psi(A),      Var[S] = sum_b m_b^2 psi1(a_b) - M^2 psi1(A)
 // and the k-mers of a segment are independent: a segment's moments are the sums of these terms.
 //
-//   moments_terms_kernel<W>  the sibling of marg_terms_kernel<W>: one thread per position; a run head writes m psi(a) and
-//                            m^2 psi1(a) of its cell, a group head also -M psi(A) and -M^2 psi1(A), every other position 0.  The
-//                            ends of run and group come from mrg_stretch_end, the signed counts from an inclusive prefix sum of the
-//                            sorted weights (two loads; without weights the stretch's length): nobody walks a run.  a and A are
+//   moments_terms_kernel<W>  one thread per position, which mrg_classify (kernels_marg.h) tells what it heads; a run head writes
+//                            m psi(a) and m^2 psi1(a) of its cell, a group head also -M psi(A) and -M^2 psi1(A), every other position
+//                            0.  The ends of run and group are mrg_classify's, the signed counts come from an inclusive prefix sum of
+//                            the sorted weights (two loads; without weights the stretch's length): nobody walks a run.  a and A are
 //                            formed as marg_terms_kernel forms them, bit for bit.  m = 0 / M = 0: exact zeros, psi is not evaluated
 //                            (the first transition of a substitution: its psi(A) terms cancel exactly, not numerically).
 //                            terms [2 M, n_t]: plane 2 * model + 0 the means, 2 * model + 1 the variances.
@@ -37,42 +37,24 @@ __global__ __launch_bounds__(MRG_THREADS) void moments_terms_kernel(const int32_
                                                                     uint64_t n_rows, mrg_models P, double *__restrict__ terms) {
   const uint64_t first = scr_off(seg, 0, n_t), end = scr_off(seg, n_seg, n_t);
   for (uint64_t i = (uint64_t)blockIdx.x * MRG_THREADS + threadIdx.x; i < n_t; i += (uint64_t)gridDim.x * MRG_THREADS) {
-    bool run_head = false, group_head = false;
-    uint64_t key = MRG_NO_KEY, left = 1;                 // left: positions from i to the end of its segment
-    if (first <= i && i < end) {
-      const uint64_t s = scr_last_le(seg, n_seg, i);
-      const uint64_t s0 = scr_off(seg, s, n_t), s1 = scr_off(seg, s + 1, n_t);
-      if (s0 <= i && i < s1) {
-        key = mrg_key(rows, letters, i, W, n_rows);
-        if (key != MRG_NO_KEY) {
-          const uint64_t prev = i > s0 ? mrg_key(rows, letters, i - 1, W, n_rows) : MRG_NO_KEY;
-          group_head = (prev >> 8) != (key >> 8);
-          run_head = prev != key;
-          left = s1 - i;
-        }
-      }
-    }
-    const uint64_t row = run_head ? key >> 8 : 0;
-    const uint32_t letter = run_head ? (uint32_t)(key & 0xFFu) : 0u;
-    // the ends lie in (i, i + left], inside the segment and so inside the text: wpre [n_t + 1] is read at no other index
-    const uint64_t run_end = mrg_stretch_end(rows, letters, i, run_head ? left : 1, key, 0, W, n_rows);
-    const uint64_t group_end = mrg_stretch_end(rows, letters, i, group_head ? left : 1, key >> 8, 8, W, n_rows);
-    const double q = run_head ? mom_count(wpre, i, run_end) : 0.0;         // m of the run, M of the group
-    const double n = group_head ? mom_count(wpre, i, group_end) : 0.0;
-    const bool cell = run_head && q != 0.0, kmer = group_head && n != 0.0;
+    const mrg_pos p = mrg_classify<W>(i, rows, letters, n_t, seg, n_seg, first, end, n_rows);
+    // the ends lie inside the text: wpre [n_t + 1] is read at no other index
+    const double q = p.run_head ? mom_count(wpre, i, p.run_end) : 0.0;         // m of the run, M of the group
+    const double n = p.group_head ? mom_count(wpre, i, p.group_end) : 0.0;
+    const bool cell = p.run_head && q != 0.0, kmer = p.group_head && n != 0.0;
     uint32_t c[W];                                       // the two rows of a group head, read once for every model's A
     double f[W];
     double cl = 0.0, fl = 0.0;                           // ... and the run's own cell
     if (kmer) {
 #pragma unroll
       for (int j = 0; j < W; ++j) {
-        c[j] = train[row * W + j];
-        f[j] = prior ? prior[row * W + j] : 0.0;
+        c[j] = train[p.row * W + j];
+        f[j] = prior ? prior[p.row * W + j] : 0.0;
       }
     }
     if (cell) {
-      cl = (double)train[row * W + letter];
-      fl = prior ? prior[row * W + letter] : 0.0;
+      cl = (double)train[p.row * W + p.letter];
+      fl = prior ? prior[p.row * W + p.letter] : 0.0;
     }
     for (int m = 0; m < P.n_m; ++m) {
       const double w = P.w[m];

@@ -63,13 +63,83 @@ def _check_model(bear_path, ar_func, h, vans):
     return hs, vs
 
 
-def _check_table(data, col_a, col_b):
+def _check_whole_table(data):
     if not isinstance(data, dataloader.CountDataset):
         raise ValueError("data must be a CountDataset or a DeviceCountDataset")
     if isinstance(data, dataloader.KmerDealtDataset) or data.shard is not None:
         raise ValueError("a sharded or k-mer-dealt table holds part of the rows: the test sums over the whole table (load it unsharded)")
+
+
+def _check_table(data, col_a, col_b):
+    _check_whole_table(data)
     if int(col_a) == int(col_b):
         raise ValueError(f"col_a and col_b are both {col_a}: a sample is not tested against itself")
+
+
+def _check_col_range(data, cols):
+    for c in cols:
+        if not 0 <= int(c) < data.num_ds:
+            raise ValueError(f"column {c}: the table has {data.num_ds}")
+
+
+def _resolve_models(data, bear_path, ar_func, hs, vs, late_cols=()):
+    """Behind ``_check_model`` and the table's refusals: the AR function and fitted h of ``bear_path``, held to the table's lag and
+    alphabet; no h: none; the width the kernels take -> ``(ar_func, hs, the models' labels)``.  ``late_cols``: the columns that
+    ``two_sample`` holds to the table's range behind the model load (``k_sample`` has done so in front of it)."""
+    if bear_path is not None:
+        from . import get_var_probs
+        lag, alphabet, h_fit, ar_func, _ = get_var_probs.load_bear(bear_path)
+        if lag != data.lag or alphabet != data.alphabet:
+            raise ValueError(f"{bear_path}: a lag-{lag} model of {alphabet!r}, the table has lag {data.lag} of {data.alphabet!r}")
+        hs = np.array([h_fit], dtype=np.float64)
+    if hs is None:
+        hs = np.zeros(0)
+    _check_col_range(data, late_cols)
+    if data.width not in kernels.WIDE_WIDTHS:
+        raise ValueError(f"rows of width {data.width}; the kernels take {kernels.WIDE_WIDTHS}")
+    return ar_func, hs, [f"bear(h={v:g})" for v in hs] + [f"van({v:g})" for v in vs]
+
+
+def _device_of(data, device):
+    """``device``, or where a ``DeviceCountDataset`` lives, or "cuda"."""
+    on_device = isinstance(data, dataloader.DeviceCountDataset)
+    return torch.device(device if device is not None else (data.counts_dev.device if on_device else "cuda"))
+
+
+def _pieces(data, ar_func, device):
+    """The table in pieces of ``data.batch_size`` rows -> ``(lo, hi, prior)`` per piece, ``prior`` the AR function's float64 rows
+    [hi - lo, W] of the piece's k-mers on ``device`` (None without ``ar_func``): one piece's rows are resident at a time."""
+    for lo, hi in data.batch_bounds():
+        prior = None
+        if ar_func is not None:
+            if isinstance(data, dataloader.DeviceCountDataset):
+                codes = kernels.encode_kmers(data.kmers_dev[lo:hi].contiguous(), data.alphabet)
+            else:
+                codes = torch.from_numpy(core.encode_kmers(data.kmers[lo:hi], data.alphabet)).to(device)
+            with torch.no_grad():
+                prior = ar_func(codes).to(torch.float64).expand(hi - lo, data.width).contiguous()
+        yield lo, hi, prior
+
+
+def _sum_pieces(data, ar_func, device, shapes, n_ar, n_models, per_kmer, piece):
+    """``piece(lo, hi, prior)`` -> ``(*outs, out_ar, row_terms)`` on every piece of the table, the outputs (of ``shapes``; ``out_ar``
+    [n_ar]) added in piece order, the row terms collected -> ``(the sums on the host, log_ar on the host or None, per_kmer [N,
+    n_models] on the device or None)``.  Under the caller's device context."""
+    sums = [torch.zeros(shape, dtype=torch.float64, device=device) for shape in shapes]
+    log_ar = torch.zeros(n_ar, dtype=torch.float64, device=device) if ar_func is not None else None
+    rows = []
+    for lo, hi, prior in _pieces(data, ar_func, device):
+        *out, out_ar, terms = piece(lo, hi, prior)
+        sums = [s + o for s, o in zip(sums, out)]
+        if out_ar is not None:
+            log_ar = log_ar + out_ar
+        if terms is not None:
+            rows.append(terms)
+        del prior
+    terms = None
+    if per_kmer:
+        terms = torch.cat(rows, 0) if rows else torch.zeros((0, n_models), dtype=torch.float64, device=device)
+    return [s.cpu().numpy() for s in sums], None if log_ar is None else log_ar.cpu().numpy(), terms
 
 
 def two_sample(data, col_a, col_b, *, bear_path=None, ar_func=None, h=None, vans=(), per_kmer=False, device=None):
@@ -83,49 +153,14 @@ def two_sample(data, col_a, col_b, *, bear_path=None, ar_func=None, h=None, vans
     sharded or k-mer-dealt table, equal columns, no model, an h or van that is not > 0."""
     hs, vs = _check_model(bear_path, ar_func, h, vans)
     _check_table(data, col_a, col_b)
-    if bear_path is not None:
-        from . import get_var_probs
-        lag, alphabet, h_fit, ar_func, _ = get_var_probs.load_bear(bear_path)
-        if lag != data.lag or alphabet != data.alphabet:
-            raise ValueError(f"{bear_path}: a lag-{lag} model of {alphabet!r}, the table has lag {data.lag} of {data.alphabet!r}")
-        hs = np.array([h_fit], dtype=np.float64)
-    if hs is None:
-        hs = np.zeros(0)
-    for c in (col_a, col_b):
-        if not 0 <= int(c) < data.num_ds:
-            raise ValueError(f"column {c}: the table has {data.num_ds}")
-    width = data.width
-    if width not in kernels.WIDE_WIDTHS:
-        raise ValueError(f"rows of width {width}; the kernels take {kernels.WIDE_WIDTHS}")
-    on_device = isinstance(data, dataloader.DeviceCountDataset)
-    device = torch.device(device if device is not None else (data.counts_dev.device if on_device else "cuda"))
-    n_models = hs.size + vs.size
-    models = [f"bear(h={v:g})" for v in hs] + [f"van({v:g})" for v in vs]
+    ar_func, hs, models = _resolve_models(data, bear_path, ar_func, hs, vs, late_cols=(col_a, col_b))
+    device = _device_of(data, device)
     with torch.cuda.device(device):
         a, b = data.device_column(int(col_a), device), data.device_column(int(col_b), device)
-        sums = torch.zeros((n_models, 4), dtype=torch.float64, device=device)
-        log_ar = torch.zeros(2, dtype=torch.float64, device=device) if ar_func is not None else None
-        rows = []
-        for lo, hi in data.batch_bounds():
-            prior = None
-            if ar_func is not None:
-                if on_device:
-                    codes = kernels.encode_kmers(data.kmers_dev[lo:hi].contiguous(), data.alphabet)
-                else:
-                    codes = torch.from_numpy(core.encode_kmers(data.kmers[lo:hi], data.alphabet)).to(device)
-                with torch.no_grad():
-                    prior = ar_func(codes).to(torch.float64).expand(hi - lo, width).contiguous()
-            out, out_ar, terms = kernels.two_sample(a[lo:hi], b[lo:hi], prior, hs, vs, want_ar=ar_func is not None, want_rows=per_kmer)
-            sums = sums + out
-            if out_ar is not None:
-                log_ar = log_ar + out_ar
-            if terms is not None:
-                rows.append(terms)
-            del prior
-        terms = None
-        if per_kmer:
-            terms = torch.cat(rows, 0) if rows else torch.zeros((0, n_models), dtype=torch.float64, device=device)
-        return TwoSampleResult(models, hs.size, sums.cpu().numpy(), None if log_ar is None else log_ar.cpu().numpy(), terms)
+        (sums,), log_ar, terms = _sum_pieces(
+            data, ar_func, device, [(len(models), 4)], 2, len(models), per_kmer,
+            lambda lo, hi, prior: kernels.two_sample(a[lo:hi], b[lo:hi], prior, hs, vs, want_ar=ar_func is not None, want_rows=per_kmer))
+        return TwoSampleResult(models, hs.size, sums, log_ar, terms)
 
 
 def two_sample_from_sequences(seqs_a, seqs_b, lags, alphabet_name="dna", reverse=False, batch_size=1 << 30, **model):
@@ -184,10 +219,7 @@ class KSampleResult:
 
 def _check_cols(data, cols):
     """The refusals of the chosen columns -> the list of them (None: every column of the table)."""
-    if not isinstance(data, dataloader.CountDataset):
-        raise ValueError("data must be a CountDataset or a DeviceCountDataset")
-    if isinstance(data, dataloader.KmerDealtDataset) or data.shard is not None:
-        raise ValueError("a sharded or k-mer-dealt table holds part of the rows: the test sums over the whole table (load it unsharded)")
+    _check_whole_table(data)
     cols = list(range(data.num_ds)) if cols is None else [int(c) for c in cols]
     if len(cols) < 2:
         raise ValueError(f"{len(cols)} columns: a test among samples takes at least 2")
@@ -195,14 +227,8 @@ def _check_cols(data, cols):
         raise ValueError(f"{len(cols)} columns: one call takes at most {kernels.K_SAMPLE_MAX_GROUPS}")
     if len(set(cols)) != len(cols):
         raise ValueError(f"columns {cols}: a column is repeated, and a sample is not tested against itself")
-    for c in cols:
-        if not 0 <= c < data.num_ds:
-            raise ValueError(f"column {c}: the table has {data.num_ds}")
+    _check_col_range(data, cols)
     return cols
-
-
-def _is_host_table(data):
-    return not isinstance(data, dataloader.DeviceCountDataset)
 
 
 def k_sample(data, cols=None, *, bear_path=None, ar_func=None, h=None, vans=(), per_kmer=False, device=None):
@@ -215,49 +241,18 @@ def k_sample(data, cols=None, *, bear_path=None, ar_func=None, h=None, vans=(), 
     bits of ``two_sample`` on a pair, nor the same bits under another order of the columns (the reduction orders differ)."""
     hs, vs = _check_model(bear_path, ar_func, h, vans)
     cols = _check_cols(data, cols)
-    if bear_path is not None:
-        from . import get_var_probs
-        lag, alphabet, h_fit, ar_func, _ = get_var_probs.load_bear(bear_path)
-        if lag != data.lag or alphabet != data.alphabet:
-            raise ValueError(f"{bear_path}: a lag-{lag} model of {alphabet!r}, the table has lag {data.lag} of {data.alphabet!r}")
-        hs = np.array([h_fit], dtype=np.float64)
-    if hs is None:
-        hs = np.zeros(0)
-    width = data.width
-    if width not in kernels.WIDE_WIDTHS:
-        raise ValueError(f"rows of width {width}; the kernels take {kernels.WIDE_WIDTHS}")
-    on_device = not _is_host_table(data)
-    device = torch.device(device if device is not None else (data.counts_dev.device if on_device else "cuda"))
-    n_models, G = hs.size + vs.size, len(cols)
-    models = [f"bear(h={v:g})" for v in hs] + [f"van({v:g})" for v in vs]
+    ar_func, hs, models = _resolve_models(data, bear_path, ar_func, hs, vs)
+    device = _device_of(data, device)
+    n_models, G = len(models), len(cols)
     with torch.cuda.device(device):
-        if on_device:
+        if isinstance(data, dataloader.DeviceCountDataset):
             table, use = data.counts_dev.to(device), cols
         else:
             table, use = torch.stack([data.device_column(c, device) for c in cols]), list(range(G))
-        sums = [torch.zeros(shape, dtype=torch.float64, device=device) for shape in ((n_models, G), (n_models, G * (G - 1) // 2, 2), (n_models, 2))]
-        log_ar = torch.zeros(G, dtype=torch.float64, device=device) if ar_func is not None else None
-        rows = []
-        for lo, hi in data.batch_bounds():
-            prior = None
-            if ar_func is not None:
-                if on_device:
-                    codes = kernels.encode_kmers(data.kmers_dev[lo:hi].contiguous(), data.alphabet)
-                else:
-                    codes = torch.from_numpy(core.encode_kmers(data.kmers[lo:hi], data.alphabet)).to(device)
-                with torch.no_grad():
-                    prior = ar_func(codes).to(torch.float64).expand(hi - lo, width).contiguous()
-            *out, out_ar, terms = kernels.k_sample(table[:, lo:hi], use, prior, hs, vs, want_ar=ar_func is not None, want_rows=per_kmer)
-            sums = [s + o for s, o in zip(sums, out)]
-            if out_ar is not None:
-                log_ar = log_ar + out_ar
-            if terms is not None:
-                rows.append(terms)
-            del prior
-        terms = None
-        if per_kmer:
-            terms = torch.cat(rows, 0) if rows else torch.zeros((0, n_models), dtype=torch.float64, device=device)
-        return KSampleResult(models, hs.size, *(s.cpu().numpy() for s in sums), None if log_ar is None else log_ar.cpu().numpy(), terms)
+        sums, log_ar, terms = _sum_pieces(
+            data, ar_func, device, [(n_models, G), (n_models, G * (G - 1) // 2, 2), (n_models, 2)], G, n_models, per_kmer,
+            lambda lo, hi, prior: kernels.k_sample(table[:, lo:hi], use, prior, hs, vs, want_ar=ar_func is not None, want_rows=per_kmer))
+        return KSampleResult(models, hs.size, *sums, log_ar, terms)
 
 
 def k_sample_from_sequences(seqs_by_group, lags, alphabet_name="dna", reverse=False, batch_size=1 << 30, **model):
@@ -338,10 +333,9 @@ def agglomerate(data, cols=None, *, model=0, device=None, **model_kwargs):
         raise ValueError(f"model {model}: the test has {n_models}")
     if "per_kmer" in model_kwargs:
         raise ValueError("agglomerate returns no per-context terms (per_kmer belongs to k_sample)")
-    on_device = not _is_host_table(data)
-    device = torch.device(device if device is not None else (data.counts_dev.device if on_device else "cuda"))
+    device = _device_of(data, device)
     with torch.cuda.device(device):
-        kmers = data.kmers_dev.to(device) if on_device else torch.from_numpy(np.ascontiguousarray(data.kmers)).to(device)
+        kmers = data.kmers_dev.to(device) if isinstance(data, dataloader.DeviceCountDataset) else torch.from_numpy(np.ascontiguousarray(data.kmers)).to(device)
         columns = [data.device_column(c, device) for c in cols]
 
         def evaluate(tables):

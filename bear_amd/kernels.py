@@ -602,6 +602,18 @@ TWO_SAMPLE_TILE = {21: 128, 5: 512}                 # TS_TILE, TS_BLOCKS_PER_CU 
 TWO_SAMPLE_BLOCKS_PER_CU = 3                        # min(tiles, blocks per CU * CUs) blocks -- tests size a table beyond that
 
 
+def _check_bayes_models(h, vans, prior, want_ar):
+    """The models of ``two_sample`` and ``k_sample`` as the C ABI takes them -> ``(hs, its pointer), (vans, its pointer)``."""
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
+    if (hs.size or want_ar) and prior is None:
+        raise ValueError("the BEAR models (h) and the AR model's likelihood (want_ar) need prior rows")
+    if not 1 <= hs.size + vs.size <= TWO_SAMPLE_MAX_MODELS:
+        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{TWO_SAMPLE_MAX_MODELS}")
+    if not (np.all(hs > 0) and np.all(vs > 0) and np.all(np.isfinite(hs)) and np.all(np.isfinite(vs))):
+        raise ValueError("every h and every vanilla pseudo-count must be > 0 and finite")
+    return (hs, hp), (vs, vp)
+
+
 def two_sample(a, b, prior, h, vans, want_ar=False, want_rows=False, ws=None):
     """``bear_two_sample_f64``: the sums of the two-sample and goodness-of-fit Bayes factors over the rows of two count columns
     ``a``, ``b`` [N, W] (uint32 in int32 storage) -> ``(out [H + V, 4] = {M_a, M_b, M_ab, B}, out_ar [2] = {L_a, L_b} or None,
@@ -616,13 +628,7 @@ def two_sample(a, b, prior, h, vans, want_ar=False, want_rows=False, ws=None):
         prior = _check_rows(prior, torch.float64, "prior", width, n=n)
     if b.device != a.device or (prior is not None and prior.device != a.device):
         raise ValueError("a, b and prior must be on one device")
-    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
-    if (hs.size or want_ar) and prior is None:
-        raise ValueError("the BEAR models (h) and the AR model's likelihood (want_ar) need prior rows")
-    if not 1 <= hs.size + vs.size <= TWO_SAMPLE_MAX_MODELS:
-        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{TWO_SAMPLE_MAX_MODELS}")
-    if not (np.all(hs > 0) and np.all(vs > 0) and np.all(np.isfinite(hs)) and np.all(np.isfinite(vs))):
-        raise ValueError("every h and every vanilla pseudo-count must be > 0 and finite")
+    (hs, hp), (vs, vp) = _check_bayes_models(h, vans, prior, want_ar)
     ws = ws or default_workspace(a.device)
     out = torch.empty((hs.size + vs.size, 4), dtype=torch.float64, device=a.device)
     out_ar = torch.empty(2, dtype=torch.float64, device=a.device) if want_ar else None
@@ -667,13 +673,7 @@ def k_sample(counts, cols, prior, h, vans, want_ar=False, want_rows=False, ws=No
         prior = _check_rows(prior, torch.float64, "prior", width, n=n)
         if prior.device != counts.device:
             raise ValueError("counts and prior must be on one device")
-    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
-    if (hs.size or want_ar) and prior is None:
-        raise ValueError("the BEAR models (h) and the AR model's likelihood (want_ar) need prior rows")
-    if not 1 <= hs.size + vs.size <= TWO_SAMPLE_MAX_MODELS:
-        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{TWO_SAMPLE_MAX_MODELS}")
-    if not (np.all(hs > 0) and np.all(vs > 0) and np.all(np.isfinite(hs)) and np.all(np.isfinite(vs))):
-        raise ValueError("every h and every vanilla pseudo-count must be > 0 and finite")
+    (hs, hp), (vs, vp) = _check_bayes_models(h, vans, prior, want_ar)
     dev, G, M = counts.device, len(cols), hs.size + vs.size
     stride = counts.stride(0)
     in_place = n > 0 and counts.stride(2) == 1 and counts.stride(1) == width and stride >= 0 and stride % width == 0 \
@@ -956,9 +956,7 @@ def score_marg(rows, letters, seg, train, prior, h, vans):
     device = train.device
     n_t = rows.numel()
     with torch.cuda.device(device):
-        key = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W)).values
-        letters = (key & 0xFF).to(torch.uint8)
-        rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+        rows, letters = _marg_sorted_text(rows, letters, seg, n_seg, K, W)
     scores = torch.empty((n_seg, hs.size + vs.size), dtype=torch.float64, device=device)
     _launch(device, "bear_score_marg_f64", _ptr(rows), _ptr(letters), n_t, _ptr(seg), n_seg, W, _ptr(train), _ptr(prior), K,
             hp, hs.size, vp, vs.size, _ptr(scores))
@@ -998,6 +996,17 @@ def _marg_sort_key(rows, letters, seg, n_seg, K, W):
     return (segment * (K + 1) + torch.where(live, rows.to(torch.int64) + 1, 0)) * 256 + torch.where(live, letters.to(torch.int64), SCORE_SKIP)
 
 
+def _marg_sorted_text(rows, letters, seg, n_seg, K, W, want_order=False):
+    """One ``torch.sort`` of ``_marg_sort_key``, rows and letters read back out of the sorted values -> ``(rows int32, letters uint8)``
+    sorted inside every segment by (row, letter), and with ``want_order`` the sort's permutation.  Under the caller's device context."""
+    key, order = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W))
+    if not want_order:
+        order = None                     # freed in front of the read-back's temporaries
+    letters = (key & 0xFF).to(torch.uint8)
+    rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+    return (rows, letters) if order is None else (rows, letters, order)
+
+
 GROUPS_MAX = 256                     # BEAR_GROUPS_MAX: groups (columns) of the table of one bear_score_groups_f64 call
 
 
@@ -1026,9 +1035,7 @@ def score_groups(rows, letters, seg, train, prior, h, vans, own=None):
     if max(n_seg, 1) * G * (hs.size + vs.size) * 8 >= 2 ** 63 or max(n_t, 1) * G * (hs.size + vs.size) * 8 >= 2 ** 63:
         raise ValueError(f"{n_seg} segments, {n_t} positions x {G} groups x {hs.size + vs.size} models: too many terms for one call")
     with torch.cuda.device(device):
-        key = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W)).values
-        letters = (key & 0xFF).to(torch.uint8)
-        rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+        rows, letters = _marg_sorted_text(rows, letters, seg, n_seg, K, W)
         scores = torch.empty((n_seg, G, hs.size + vs.size), dtype=torch.float64, device=device)
         short_of = torch.empty(n_seg, dtype=torch.uint8, device=device)
         _lib.call("bear_score_groups_f64", _ptr(rows), _ptr(letters), n_t, _ptr(seg), n_seg, W, _ptr(train), G, _ptr(prior), K, _ptr(own),
@@ -1053,9 +1060,7 @@ def score_moments(rows, letters, seg, train, prior, h, vans, weights=None):
         _check_vec(weights, torch.int8, "weights", n_t, device=device)
     prefix = None
     with torch.cuda.device(device):
-        key, order = torch.sort(_marg_sort_key(rows, letters, seg, n_seg, K, W))
-        letters = (key & 0xFF).to(torch.uint8)
-        rows = (torch.div(key, 256, rounding_mode="floor") % (K + 1) - 1).to(torch.int32)
+        rows, letters, order = _marg_sorted_text(rows, letters, seg, n_seg, K, W, want_order=True)
         if weights is not None:
             if n_t and not bool((weights.abs() == 1).all()):
                 raise ValueError("weights: every entry is +1 or -1")

@@ -2,7 +2,8 @@
 inputs, for holding one build of the library against another.
     BEAR_AMD_LIB=before/libbear_hip.so python scripts/dev/wide_bits.py > before.json
     BEAR_AMD_LIB=bear_amd/libbear_hip.so python scripts/dev/wide_bits.py > after.json        # then: cmp before.json after.json
-One SHA-256 per output buffer, as one JSON object (case -> digest).  These kernels use no floating-point atomics and the library is
+Section names (the functions below: row_kernels, linear_kernels, cnn_kernels, cnn5_kernels, linear5_kernels, exact_kernels) behind
+the script's name run those sections alone; none: all of them.  One SHA-256 per output buffer, as one JSON object (case -> digest).  These kernels use no floating-point atomics and the library is
 built without contraction: on one device two builds that compute the same thing give the same file, and any difference is a
 difference in the arithmetic or in its order.  Each build runs in a process of its own (the library is loaded once).
 
@@ -28,7 +29,16 @@ the order the work units were drawn in libbear_hip.so and is hashed in libbear_h
 through LDS floating-point atomics from several waves and is not hashable in either library: those instantiations are held to the
 oracle by the parity tests.  A tile denser than its in-tile lists (the loop over the plan's overflow items) comes from the parity
 tests' `mixed_heavy_table`, in libbear_hip_det.so only: the other library's plan of such a table differs from build to build of
-the plan in which cells overflow, and with it the fixed-point roundings."""
+the plan in which cells overflow, and with it the fixed-point roundings.
+
+The exact marginals and the Bayes factors (`exact_kernels`: score_marg, score_moments, score_groups; two_sample, k_sample) have no
+atomics and are hashed in both libraries, at both widths.  One text for the first three: 3 * 256 + 77 positions cut into four
+segments, one of them empty, then one segment of 2 * MARG_CHUNK + 5 positions that holds a run of 150 equal (row, letter);
+positions with SCORE_SKIP, with a negative row and with a row beyond the table.  score_groups at G = 1 and 3, without `own` and
+with an `own` that holds -1, a value >= G and, for the long segment, a group whose counts do not hold it (NaN scores, `short_of`);
+the other segments' own groups hold them.  The tables of the Bayes factors: tile - 1 and tile + 1 rows and one table beyond the
+capped grid; four models (two BEAR, two vanilla) and five (a second launch), each plain and with the AR sums and the row terms;
+k_sample at G = 2, 3 and 16 columns of an 18-column table."""
 import hashlib
 import json
 import os
@@ -359,14 +369,78 @@ def linear5_kernels(cus, det):
             os.environ["BEAR_AMD_DETERMINISTIC"] = before
 
 
+def exact_text(rng, K, width):
+    """-> (rows int32, letters uint8, seg int64, weights int8) on the device, and the host rows / letters / offsets."""
+    n_short, n_long = 3 * 256 + 77, 2 * kernels.MARG_CHUNK + 5
+    offsets = np.array([0, 100, 100, 400, n_short, n_short + n_long], dtype=np.int64)
+    r = rng.integers(0, K, n_short + n_long).astype(np.int32)
+    l = rng.integers(0, width, n_short + n_long).astype(np.uint8)
+    r[n_short + 300:n_short + 450], l[n_short + 300:n_short + 450] = 5, 2      # a run longer than a wave
+    l[::17] = kernels.SCORE_SKIP
+    r[3::29] = -1
+    r[11::31] = K + 3
+    w = np.where(rng.random(r.size) < 0.4, -1, 1).astype(np.int8)
+    return [torch.from_numpy(x).cuda() for x in (r, l, offsets, w)], (r, l, offsets)
+
+
+def exact_kernels(cus):
+    hs, vs = [0.5, 2.0], [0.1, 1.0]
+    for width in kernels.WIDE_WIDTHS:
+        K = 37
+        rng = np.random.default_rng(4200 + width)
+        (r, l, seg, wts), (hr, hl, offsets) = exact_text(rng, K, width)
+        prior = rows(rng, K, width)
+        name = "w%d" % width
+        put("score_marg/" + name, kernels.score_marg(r, l, seg, counts(rng, K, width, 0.5), prior, hs, vs))
+        train = counts(rng, K, width, 0.5)
+        put("score_moments/%s/weights0" % name, kernels.score_moments(r, l, seg, train, prior, hs, vs))
+        put("score_moments/%s/weights1" % name, kernels.score_moments(r, l, seg, train, prior, hs, vs, weights=wts))
+        for G in (1, 3):
+            table = counts(rng, K * G, width, 0.5).cpu().numpy().view(np.uint32).reshape(K, G, width)
+            own = np.array([G - 1, G // 2, -1, G, 0], dtype=np.int32)       # the long segment: group 0, which does not hold it
+            for s in (0, 1, 3):
+                if 0 <= own[s] < G:
+                    a, b = offsets[s], offsets[s + 1]
+                    live = (hr[a:b] >= 0) & (hr[a:b] < K) & (hl[a:b] < width)
+                    np.add.at(table[:, own[s], :], (hr[a:b][live], hl[a:b][live]), 1)
+            table = torch.from_numpy(np.ascontiguousarray(table).view(np.int32)).cuda()
+            put("score_groups/%s/G%d/own0" % (name, G), *kernels.score_groups(r, l, seg, table, prior, hs, vs))
+            scores, short_of = kernels.score_groups(r, l, seg, table, prior, hs, vs, own=torch.from_numpy(own).cuda())
+            assert short_of.cpu().tolist() == [0, 0, 0, 0, 1] and bool(scores[4, 0].isnan().all()), "the long segment alone is short"
+            put("score_groups/%s/G%d/own1" % (name, G), scores, short_of)
+        models = {"m4": ([0.5, 2.0], [0.1, 1.0]), "m5": ([0.05, 0.7, 3.0], [0.1, 1.0])}         # m5: two launches
+        tile = kernels.TWO_SAMPLE_TILE[width]
+        for n in (tile - 1, tile + 1, beyond(cus, kernels.TWO_SAMPLE_BLOCKS_PER_CU, tile)):
+            rng = np.random.default_rng(n + width + 4)
+            a, b, f = counts(rng, n, width), counts(rng, n, width, 0.2), rows(rng, n, width)
+            for mname, (h, v) in models.items():
+                for more in (False, True):
+                    out = kernels.two_sample(a, b, f, h, v, want_ar=more, want_rows=more)
+                    put("two_sample/%s/n%d/%s/more%d" % (name, n, mname, more), *[t for t in out if t is not None])
+        for G in (2, 3, 16):
+            tile = kernels.k_sample_tile(width, G)
+            cols = [int(c) for c in np.random.default_rng(G).permutation(18)[:G]]
+            for n in (tile - 1, tile + 1, beyond(cus, kernels.K_SAMPLE_BLOCKS_PER_CU, tile)):
+                rng = np.random.default_rng(n + width + G + 5)
+                table, f = counts(rng, 18 * n, width).reshape(18, n, width), rows(rng, n, width)
+                for mname, (h, v) in models.items():
+                    for more in (False, True):
+                        out = kernels.k_sample(table, cols, f, h, v, want_ar=more, want_rows=more)
+                        put("k_sample/%s/G%d/n%d/%s/more%d" % (name, G, n, mname, more), *[t for t in out if t is not None])
+
+
 if __name__ == "__main__":
     from bear_amd import _lib
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    row_kernels(cus)
-    linear_kernels(cus)
-    cnn_kernels(cus)
     det = os.path.basename(_lib.LIB_PATH) == "libbear_hip_det.so"
-    cnn5_kernels(cus, det)
-    linear5_kernels(cus, det)
+    sections = {"row_kernels": lambda: row_kernels(cus), "linear_kernels": lambda: linear_kernels(cus), "cnn_kernels": lambda: cnn_kernels(cus),
+                "cnn5_kernels": lambda: cnn5_kernels(cus, det), "linear5_kernels": lambda: linear5_kernels(cus, det),
+                "exact_kernels": lambda: exact_kernels(cus)}
+    unknown = [a for a in sys.argv[1:] if a not in sections]
+    if unknown:
+        sys.exit("no section %s: %s" % (unknown, list(sections)))
+    for name, run in sections.items():
+        if name in sys.argv[1:] or not sys.argv[1:]:
+            run()
     torch.cuda.synchronize()
     print(json.dumps(OUT, indent=0, sort_keys=True))
