@@ -6,7 +6,8 @@
 // sequence generation over the same key tables ("Sequence generation": flanks of given lengths, and whole sequences from start to
 // stop) -- and, for bear_ref models, the reference-mixed prior rows of queried k-mers and whole sequences under such a model.
 // The only unit that includes -- and so emits --
-// kernels_score.h, kernels_marg.h, kernels_groups.h, kernels_moments.h, kernels_refscore.h and kernels_generate.h.
+// kernels_score.h, kernels_marg.h, kernels_groups.h, kernels_segment.h (every position's letter under every group, and the chain over
+// the groups that segments a sequence), kernels_moments.h, kernels_refscore.h and kernels_generate.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #include "kernels_moments.h"
 #include "kernels_refscore.h"
 #include "kernels_score.h"
+#include "kernels_segment.h"
 
 namespace {
 bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
@@ -317,6 +319,109 @@ int bear_score_groups_f64(const int32_t *rows, const uint8_t *letters, uint64_t 
     HIP_TRY(hipGetLastError());
   }
   return mrg_sum_launches(terms.get(), M, seg, n_seg, n_t, n_blocks, partials.get(), scores, s);   // scores [n_seg, n_groups, n_m]
+}
+
+int bear_score_emit_groups_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, int width, const uint32_t *train, int n_groups,
+                               const double *prior, uint64_t n_rows, const double *h, int n_h, const double *van, int n_van, void *stream,
+                               double *emit) {
+  if (n_groups < 1 || n_groups > BEAR_GROUPS_MAX) return BEAR_ERR_INVALID_ARG;
+  mrg_models P;      // (no segments here: the width, the models and n_rows as bear_score_groups_f64 checks them, the pointers below)
+  const int st = mrg_prepare(nullptr, nullptr, 0, nullptr, 0, width, train, prior, n_rows, h, n_h, van, n_van, nullptr, 1, P);
+  if (st != BEAR_OK) return st;
+  if (n_h > 0 && misaligned8(prior)) return BEAR_ERR_INVALID_ARG;
+  if (n_t == 0) return BEAR_OK;
+  if (!rows || !letters || !emit || misaligned4(rows) || misaligned8(emit)) return BEAR_ERR_INVALID_ARG;
+  if (n_rows && (!train || misaligned4(train))) return BEAR_ERR_INVALID_ARG;
+  if (n_t > (~0ull) / ((uint64_t)n_groups * (uint64_t)P.n_m) / sizeof(double)) return BEAR_ERR_INVALID_ARG;
+  const dim3 grid(scr_grid(n_t, EMT_THREADS)), block(EMT_THREADS);
+  LAUNCH_BY_WIDTH(width, emit_groups_kernel<5>, emit_groups_kernel<21>, grid, block, 0, static_cast<hipStream_t>(stream), rows, letters, n_t,
+                  train, (uint32_t)n_groups, n_h > 0 ? prior : nullptr, n_rows, P, emit);
+  HIP_TRY(hipGetLastError());
+  return BEAR_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The chain of bear_hmm_groups_f64 as the kernels take it.  False: NaN or +inf anywhere, a row of log_trans or a log_start without
+// a finite entry.
+bool hmm_chain_of(const double *log_trans, const double *log_start, int S, hmm_chain &P) {
+  memset(&P, 0, sizeof(P));
+  P.S = S;
+  for (int g = 0; g <= S; ++g) {                         // the rows of log_trans, then log_start
+    const double *src = g < S ? log_trans + g * S : log_start;
+    double *dst = g < S ? P.lt + g * S : P.start;
+    bool any = false;
+    for (int k = 0; k < S; ++k) {
+      if (isnan(src[k]) || src[k] == HUGE_VAL) return false;
+      any = any || isfinite(src[k]);
+      dst[k] = src[k];
+    }
+    if (!any) return false;
+  }
+  return true;
+}
+
+// One pass of the chain in the semiring SR: the chunks' matrices and the carried vectors where the text goes beyond one chunk
+// (n_blocks > 0), then every chunk.
+template <class SR, int LW>
+int hmm_pass(const double *emit, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, uint64_t n_blocks, const hmm_chain &P, double *mats,
+             double *carry, double *fwd, double *log_post, uint8_t *path, double *scalar, hipStream_t s) {
+  constexpr uint64_t groups = HMM_THREADS / LW;
+  if (n_blocks) {
+    hipLaunchKernelGGL((hmm_matrix_kernel<SR, LW>), dim3(scr_grid(n_blocks * (uint64_t)P.S, groups)), dim3(HMM_THREADS), 0, s, emit, n_t, seg,
+                       n_seg, n_blocks, P, mats);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((hmm_carry_kernel<SR, LW>), dim3(scr_grid(2 * n_seg, groups)), dim3(HMM_THREADS), 0, s, seg, n_seg, n_t, P, mats,
+                       fwd != nullptr, carry);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL((hmm_chunk_kernel<SR, LW>), dim3(scr_grid(n_seg + n_blocks, groups)), dim3(HMM_THREADS), 0, s, emit, n_t, seg, n_seg,
+                     n_blocks, P, carry, fwd, log_post, path, scalar);
+  HIP_TRY(hipGetLastError());
+  if (n_blocks && log_post) {                            // the chunks of the longer segments wrote alpha + beta: less the evidence
+    hipLaunchKernelGGL(hmm_normalise_kernel, dim3(scr_grid(n_t, HMM_NORM_THREADS)), dim3(HMM_NORM_THREADS), 0, s, seg, n_seg, n_t,
+                       (uint32_t)P.S, scalar, log_post);
+    HIP_TRY(hipGetLastError());
+  }
+  return BEAR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int bear_hmm_groups_f64(const double *emit, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int n_states, const double *log_trans,
+                        const double *log_start, void *stream, double *log_evidence, double *log_best, uint8_t *path, double *log_post) {
+  if (n_states < 1 || n_states > BEAR_HMM_MAX_STATES || !log_trans || !log_start) return BEAR_ERR_INVALID_ARG;
+  hmm_chain P;
+  if (!hmm_chain_of(log_trans, log_start, n_states, P)) return BEAR_ERR_INVALID_ARG;
+  if (log_post && misaligned8(log_post)) return BEAR_ERR_INVALID_ARG;
+  if (n_seg == 0) return BEAR_OK;
+  if (!seg || !log_evidence || !log_best || misaligned8(seg) || misaligned8(log_evidence) || misaligned8(log_best))
+    return BEAR_ERR_INVALID_ARG;
+  if (n_t && (!emit || !path || misaligned8(emit))) return BEAR_ERR_INVALID_ARG;
+  const uint64_t S = (uint64_t)n_states;
+  if (n_t > (~0ull) / S / sizeof(double) / 4 || n_seg > (~0ull) / sizeof(double) / 4) return BEAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // only a text of more than BEAR_HMM_CHUNK steps can hold a segment of more than one chunk: two slots per chunk of the text
+  const uint64_t n_blocks = n_t > HMM_CHUNK ? (n_t + HMM_CHUNK - 1) / HMM_CHUNK : 0;
+  stream_buf mats(s), carry(s), delta(s);                // both passes use them in turn, in stream order
+  if (n_blocks) {
+    HIP_TRY(mats.alloc(2 * n_blocks * S * S));
+    HIP_TRY(carry.alloc(2 * n_blocks * 2 * S));
+  }
+  if (n_t) HIP_TRY(delta.alloc(n_t * S));                // the forward values of the max pass (the sum pass keeps its own in log_post)
+  int st;
+  if (n_states <= 4) {
+    st = hmm_pass<hmm_lse, 4>(emit, n_t, seg, n_seg, n_blocks, P, mats.get(), carry.get(), log_post, log_post, nullptr, log_evidence, s);
+    if (st == BEAR_OK)
+      st = hmm_pass<hmm_max, 4>(emit, n_t, seg, n_seg, n_blocks, P, mats.get(), carry.get(), delta.get(), nullptr, path, log_best, s);
+  } else {
+    st = hmm_pass<hmm_lse, 16>(emit, n_t, seg, n_seg, n_blocks, P, mats.get(), carry.get(), log_post, log_post, nullptr, log_evidence, s);
+    if (st == BEAR_OK)
+      st = hmm_pass<hmm_max, 16>(emit, n_t, seg, n_seg, n_blocks, P, mats.get(), carry.get(), delta.get(), nullptr, path, log_best, s);
+  }
+  return st;
 }
 
 int bear_generate_steps_f64(const uint64_t *table, const uint32_t *counts, uint64_t n_table, int lag, int width, const uint8_t *rank,

@@ -1043,6 +1043,93 @@ def score_groups(rows, letters, seg, train, prior, h, vans, own=None):
     return scores, short_of
 
 
+HMM_MAX_STATES = 16                  # BEAR_HMM_MAX_STATES: states of the chain of one bear_hmm_groups_f64 call
+HMM_CHUNK = 512                      # BEAR_HMM_CHUNK: steps of a segment that one lane group runs front to back and back
+
+
+def emit_groups(rows, letters, train, prior, h, vans):
+    """``bear_score_emit_groups_f64``: the posterior-predictive log-probability of every position's letter under every group and
+    model -> CUDA float64 [H + V, n_t, G], the H BEAR models first; plane ``m`` is the ``emit`` of ``hmm_groups``.  ``rows`` int32
+    [n_t] and ``letters`` uint8 [n_t] per position in TEXT order (nothing is sorted); ``train`` int32 [K, G, W], ``prior`` float64
+    [K, W] or None, ``h`` and ``vans`` as ``score_groups`` takes them.  A position without a transition (``SCORE_SKIP``, a negative
+    row, a row >= K) holds exactly 0.0.  One asynchronous call on the current stream (the entry's stream is not its last argument)."""
+    if not (isinstance(train, torch.Tensor) and train.is_cuda and train.dtype == torch.int32 and train.dim() == 3
+            and train.is_contiguous() and train.shape[2] in WIDE_WIDTHS):
+        raise ValueError(f"train must be a contiguous CUDA int32 tensor [K, G, W] with W in {WIDE_WIDTHS}")
+    K, G, W = train.shape
+    if not 1 <= G <= GROUPS_MAX:
+        raise ValueError(f"{G} groups: one call takes 1..{GROUPS_MAX}")
+    if train.data_ptr() % 16:
+        train = train.clone()
+    device = train.device
+    if prior is not None:
+        prior = _check_rows(prior, torch.float64, "prior", W, n=K)
+    _check_vec(rows, torch.int32, "rows", device=device)
+    _check_vec(letters, torch.uint8, "letters", rows.numel(), device=device)
+    (hs, hp), (vs, vp) = _host_f64(h), _host_f64(vans)
+    if hs.size and prior is None:
+        raise ValueError("the BEAR models (h) need prior rows")
+    if not 1 <= hs.size + vs.size <= MARG_MAX_MODELS:
+        raise ValueError(f"{hs.size} + {vs.size} models: one call takes 1..{MARG_MAX_MODELS}")
+    if not (np.all(hs > 0) and np.all(vs > 0)):
+        raise ValueError("every h and every vanilla pseudo-count must be > 0")
+    n_t, M = rows.numel(), hs.size + vs.size
+    if max(n_t, 1) * G * M * 8 >= 2 ** 63:
+        raise ValueError(f"{n_t} positions x {G} groups x {M} models: too many values for one call")
+    with torch.cuda.device(device):
+        emit = torch.empty((M, n_t, G), dtype=torch.float64, device=device)
+        _lib.call("bear_score_emit_groups_f64", _ptr(rows), _ptr(letters), n_t, W, _ptr(train), G, _ptr(prior), K, hp, hs.size, vp, vs.size,
+                  _stream(), _ptr(emit))
+    return emit
+
+
+def check_chain(log_trans, log_start, n_states):
+    """The chain of ``hmm_groups`` as the C ABI takes it -> ``(log_trans float64 [S, S], log_start float64 [S])``, C-contiguous host
+    arrays.  -inf is allowed and rows need not be normalised; ``ValueError`` for a wrong shape, a NaN or +inf, a row or a start
+    without a finite entry, or S outside 1..``HMM_MAX_STATES``.  Needs no device."""
+    S = int(n_states)
+    if not 1 <= S <= HMM_MAX_STATES:
+        raise ValueError(f"{S} states: a chain has 1..{HMM_MAX_STATES}")
+    log_trans = np.ascontiguousarray(np.asarray(log_trans, dtype=np.float64))
+    log_start = np.ascontiguousarray(np.asarray(log_start, dtype=np.float64))
+    if log_trans.shape != (S, S) or log_start.shape != (S,):
+        raise ValueError(f"log_trans must be [{S}, {S}] (from-state by row) and log_start [{S}]")
+    for name, a in (("log_trans", log_trans), ("log_start", log_start[None, :])):
+        if np.isnan(a).any() or np.isposinf(a).any():
+            raise ValueError(f"{name}: log probabilities (-inf rules a step out), no NaN and no +inf")
+        if not np.isfinite(a).any(axis=1).all():
+            raise ValueError(f"{name}: every row needs a finite entry")
+    return log_trans, log_start
+
+
+def hmm_groups(emit, seg, log_trans, log_start, want_post=True):
+    """``bear_hmm_groups_f64``: a hidden-Markov chain over the S states along every segment -> ``(log_evidence [n_seg] float64,
+    log_best [n_seg] float64, path [n_t] uint8, log_post [n_t, S] float64 or None)``, CUDA tensors.  ``emit``: contiguous CUDA
+    float64 [n_t, S], the log-probability of step ``t`` under state ``g``; ``seg`` int64 [n_seg + 1] ascending from 0 to n_t -- it
+    MUST cover the text: the offsets live on the device, so they are not checked here, and ``path`` / ``log_post`` of a step that no
+    segment covers are returned as allocated, unwritten;
+    ``log_trans`` [S, S] from-state by row and ``log_start`` [S]: host values (``check_chain``).  ``path[t]``: the lowest state of
+    the largest max-marginal, 255 where every path is -inf; ``log_post``: every step's posterior over the states
+    (``want_post=False``: not formed).  Segments beyond ``HMM_CHUNK`` steps run in chunks (include/bear_hip.h, the chunk rule).
+    One asynchronous call on the current stream."""
+    if not (isinstance(emit, torch.Tensor) and emit.is_cuda and emit.dtype == torch.float64 and emit.dim() == 2 and emit.is_contiguous()):
+        raise ValueError("emit must be a contiguous CUDA float64 tensor [n_t, S]")
+    n_t, S = emit.shape
+    log_trans, log_start = check_chain(log_trans, log_start, S)
+    device = emit.device
+    n_seg = _check_seg(seg, device)
+    if emit.data_ptr() % 8:
+        emit = emit.clone()
+    with torch.cuda.device(device):
+        log_evidence = torch.empty(n_seg, dtype=torch.float64, device=device)
+        log_best = torch.empty(n_seg, dtype=torch.float64, device=device)
+        path = torch.empty(n_t, dtype=torch.uint8, device=device)
+        log_post = torch.empty((n_t, S), dtype=torch.float64, device=device) if want_post else None
+        _lib.call("bear_hmm_groups_f64", _ptr(emit), n_t, _ptr(seg), n_seg, S, log_trans.ctypes.data_as(ctypes.c_void_p),
+                  log_start.ctypes.data_as(ctypes.c_void_p), _stream(), _ptr(log_evidence), _ptr(log_best), _ptr(path), _ptr(log_post))
+    return log_evidence, log_best, path, log_post
+
+
 def score_moments(rows, letters, seg, train, prior, h, vans, weights=None):
     """``bear_score_moments_f64``: the exact posterior mean and variance of every segment's score -> CUDA float64 [n_seg, H + V, 2]
     (``[..., 0]`` the mean, ``[..., 1]`` the variance as summed, not clamped), the models in ``score_marg``'s order.  With

@@ -1089,6 +1089,78 @@ int bear_score_groups_f64(const int32_t *rows, const uint8_t *letters, uint64_t 
                           void *stream, double *scores, uint8_t *short_of);
 
 /*
+ * Segmenting sequences among the groups of a count table (bear_amd.classify.segment, kernels_segment.h): WHERE in a sequence does
+ * which group speak.  Two entries: the log-probability of every position's letter under every group, and a hidden-Markov chain
+ * over the groups.  Both are asynchronous on `stream`, which is deliberately NOT their last parameter (as for
+ * bear_score_groups_f64 and for the same reason; tests/test_segment_gpu.py holds them to the contract with the harness of
+ * tests/stream_util.py).
+ *
+ * bear_score_emit_groups_f64: the posterior-predictive log-probability of the letter of every position under every group and model.
+ * rows, letters, width, train, n_groups, prior, n_rows, h, van are bear_score_groups_f64's, but the positions stand in TEXT order
+ * (nothing is sorted, there are no segments here: a position is one transition).  For position t with row r and letter l, group g
+ * and model m, with c[] = train[r, g, :],
+ *     a_j = fma(prior[r, j], 1 / h_m, c_j) for the BEAR model m < n_h,   a_j = van_(m - n_h) + c_j for a vanilla model,
+ *     A = a_0 + ... + a_(width - 1) in that order  (a_j and A bit for bit those of bear_score_groups_f64),
+ *     emit[m, t, g] = log(a_l) - log(A): a DIFFERENCE of two logs, not one log of the quotient -- each log is off by its own
+ *     rounding only, so the error is relative to |log a_l| + |log A| even where both are tiny (an unseen k-mer at h = 1 under a
+ *     prior row that one letter dominates: a_l and A are both next to 1, and the quotient's rounding would be all of the value).
+ * This is the exact marginal of the single transition, so a k-mer that no group has seen scores through the prior alone.  A
+ * position without a transition (a negative row, a row >= n_rows, a letter >= width) has exactly 0.0 for every group and model.
+ *   emit [dev] double [n_h + n_van, n_t, n_groups]: model-major, the n_groups values of a position adjacent -- plane m is the
+ *        emit [n_t, n_states] that bear_hmm_groups_f64 takes.
+ * One thread per position; the prior row and the k-mer's n_groups rows are read once.  Refused with BEAR_ERR_INVALID_ARG before
+ * any device call: everything bear_score_groups_f64 refuses of these arguments (the width, the models, n_groups, n_rows), a missing
+ * or misaligned pointer.  n_t = 0 is valid and launches nothing.
+ *
+ * bear_hmm_groups_f64: a hidden-Markov chain over n_states states along every segment, generic over where its emissions came from.
+ *   emit [dev] double [n_t, n_states];  seg [dev] uint64 [n_seg + 1] ascending offsets into the steps, seg[0] = 0 and seg[n_seg] =
+ *        n_t -- the entry cannot check device values: a step that no segment covers keeps whatever path and log_post held: segment i
+ *        has the steps 0 .. T - 1 = seg[i] .. seg[i + 1] - 1, e_t its emission rows.  Every step emits: the entry knows no silent
+ *        step (the caller drops the positions without a transition, or keeps their zeros as uninformative steps).
+ *   log_trans [host] double [n_states, n_states], from-state by row;  log_start [host] double [n_states].  -inf is allowed and
+ *        rows need not be normalised;  1 <= n_states <= BEAR_HMM_MAX_STATES
+ *   Sum-product:  alpha_0 = log_start + e_0;  alpha_t(g) = e_t(g) + lse_h(alpha_(t-1)(h) + log_trans[h, g]);  beta_(T-1) = 0;
+ *        beta_t(g) = lse_h(log_trans[g, h] + e_(t+1)(h) + beta_(t+1)(h));  lse = max + log(sum of exp(x - max)) in state order, and
+ *        -inf over only -inf, never NaN.
+ *   Max-plus: the same recurrences with max in place of lse give delta and eta.
+ *   log_evidence [dev] double [n_seg] = lse_g alpha_(T-1)(g);   log_best [dev] double [n_seg] = max_g delta_(T-1)(g)
+ *   path [dev] uint8 [n_t]: the LOWEST g that maximises the max-marginal delta_t(g) + eta_t(g).  Wherever the best path is unique
+ *        this is the Viterbi path.  On a tie the lowest index is taken position by position, which need not be one consistent
+ *        path (two best paths A A B B and A B B B give A A B B here only by the index rule).
+ *   log_post [dev, nullable] double [n_t, n_states] = alpha_t(g) + beta_t(g) - log_evidence; exactly -inf for a state no path of
+ *        finite value passes through at t.  NULL: not formed -- the sum pass then carries no backward vector and only a
+ *        segment's last chunk recomputes its forward values, for log_evidence (the max pass runs whole: path needs eta).
+ *   T = 0: log_evidence = lse(log_start), log_best = max(log_start), nothing per position.  Every path -inf: log_evidence and
+ *        log_best are -inf, the segment's log_post is NaN and its path 255.
+ * The chunk rule.  A segment is cut from its own start into chunks of BEAR_HMM_CHUNK steps.  A segment of one chunk is run front
+ * to back and back to front by one lane group, nothing else.  For a longer one (1) every chunk's n_states x n_states transfer
+ * matrix is formed -- row i: the forward recurrence over the chunk's steps from the unit vector of state i, in the semiring of the
+ * pass; the first chunk's first step takes no transition --, (2) the vector that enters each chunk (log_start, then one
+ * vector-matrix product per chunk in chunk order) and the vector that leaves it (0, then one product per chunk in reverse order)
+ * are carried along, (3) every chunk recomputes its forward values from the vector that enters it and its backward values from
+ * the one that leaves it.  The scalars are those of the last chunk's recomputed forward values, and (4) one more launch takes that
+ * log_evidence off the alpha + beta of every step of such a segment, so log_post + log_evidence is alpha + beta to the bit in
+ * every chunk.  A text beyond BEAR_HMM_CHUNK steps that holds only short segments still pays for the launches of (1), (2) and
+ * (4) and for the scratch below: the host sees n_t, not the offsets -- their items find no long segment and form nothing.
+ * No atomics; every reduction runs in state order: a segment's bits depend on its own emissions and the chain
+ * only -- not on where it stands in the text, on its neighbours, on the grid or on the library.
+ * Holds n_t * n_states forward values and, for a text beyond BEAR_HMM_CHUNK steps, two matrices and four vectors per
+ * BEAR_HMM_CHUNK steps, from the device's memory pool in stream order (hipMallocAsync / hipFreeAsync): the entry waits for
+ * nothing, outputs are valid once the stream is synchronised; it does not belong inside a graph capture.
+ * Refused with BEAR_ERR_INVALID_ARG before any device call: n_states out of range; a log_trans or log_start that is missing, holds
+ * a NaN or +inf, or has a row (log_start: the vector) without a finite entry; a missing or misaligned pointer.  n_seg = 0 is valid
+ * and launches nothing (n_t = 0 with segments: every one is empty and gets the T = 0 scalars).
+ */
+#define BEAR_HMM_MAX_STATES 16
+#define BEAR_HMM_CHUNK 512
+int bear_score_emit_groups_f64(const int32_t *rows, const uint8_t *letters, uint64_t n_t, int width, const uint32_t *train,
+                               int n_groups, const double *prior, uint64_t n_rows, const double *h, int n_h,
+                               const double *van, int n_van, void *stream, double *emit);
+int bear_hmm_groups_f64(const double *emit, uint64_t n_t, const uint64_t *seg, uint64_t n_seg, int n_states,
+                        const double *log_trans, const double *log_start, void *stream,
+                        double *log_evidence, double *log_best, uint8_t *path, double *log_post);
+
+/*
  * bear_score_moments_f64: the exact posterior mean and variance of every segment's score under n_h BEAR and n_van vanilla models
  * (get_bear_probs / get_bear_probs_seqs with moments=True): what the mc_samples axis of bear_logdir_sample[_wide]_f64 +
  * bear_score_sum_f64 samples, in closed form.  The arguments, models, concentrations (a_j and A bit for bit), sums, checks and
